@@ -11,10 +11,12 @@ fregrid_parallel decomposition, fregrid_util.c:592-597); the only exchange is th
 (area, clon, clat) sums of the cells present on several ranks, handed from rank to rank in the reference's
 order (RCCL broadcasts of a short list, conserve_interp.c:203-221).  Fixed total work => "strong".
 
-value = steps * (sum over ranks of nxgrid) / max-over-ranks wall time, inputs resident in HBM.
-A second timed region measures the sweep (do_scalar_conserve_interp) on nz levels: remapped-points/s.
+value = steps * (sum over ranks of nxgrid) / max-over-ranks wall time of ONE timed region of `steps` steps, inputs resident in HBM.
+A plain run does only that (set-up, warm-up, the timed steps, --dump-outputs) and prints the result line.  --full adds the rest:
+the spread over --repeats regions, per-phase device times, the sweep (do_scalar_conserve_interp) on nz levels (remapped-points/s),
+mass conservation, rooflines, the multi-rank exchange check and the --legs jobs (CPU baseline, PCIe-inclusive, configs 4 and 5, C768).
 
-Run: python bench.py --gpus 1 --steps 20 --warmup 3
+Run: python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
      python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 """
@@ -393,23 +395,47 @@ def exchange_in_place(fg, torch, plan, bidx_t, ncell, dev):
     fg.allreduce_cell_sums_sparse(sums, bidx_t, ncell)
 
 
+def dump_outputs(out_dir, plan, prefix, max_cells):
+    """What the timed path hands its caller after its last step: the plan's exchange grid (XgridPlan.get_xgrid: t_in, i_in, j_in,
+    i_out, j_out, area and, order 2, c1 / c2) as out_dir/<prefix>xgrid_<name>.npy.  Above `max_cells` exchange cells a fixed,
+    seeded sample is written, the same positions in every run with the same nxgrid (xgrid_index: positions in exchange-cell order);
+    <prefix>nxgrid.npy holds the count.  Indices as float32 (exact below 2**24), the rest as float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = plan.nxgrid
+    xg = plan.get_xgrid()
+    idx = np.arange(n) if n <= max_cells else np.sort(np.random.default_rng(0).choice(n, max_cells, replace=False))
+    save = lambda name, a: np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    save("nxgrid", np.array([n], dtype=np.float64))
+    save("xgrid_index", idx.astype(np.float64))
+    for k, v in xg.items():
+        save("xgrid_" + k, v[idx].astype(np.float32 if v.dtype == np.int32 else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the headline")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--ni", type=int, default=384, help="C<ni> source cubed sphere")
     ap.add_argument("--nlon", type=int, default=1440)
     ap.add_argument("--nlat", type=int, default=720)
-    ap.add_argument("--nz", type=int, default=8, help="levels per sweep launch")
-    ap.add_argument("--apply-steps", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each (median reported)")
-    ap.add_argument("--no-phase-timing", action="store_true", help="skip the separate pass that records per-phase HIP events")
-    ap.add_argument("--legs", default="all", help="comma list of extra legs: gc,pcie,config4,config5,cpu,c768,c768gc,config5_full (or all / none); "
-                                                  "all = the first five; with --gpus N > 1 the c768 jobs always run")
-    ap.add_argument("--cpu-rows", type=int, default=32, help="source rows in the CPU baseline sample (0 = skip)")
-    ap.add_argument("--gc-steps", type=int, default=3, help="timed great-circle searches of the same grids (N=1 only; 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's exchange grid to DIR/*.npy "
+                                                          "(a seeded sample of at most 2**20 exchange cells in all)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the spread over "
+                                                         "--repeats regions, two-call steps, per-phase device times, the sweep and "
+                                                         "pipeline legs, mass conservation, rooflines, the multi-rank exchange check, "
+                                                         "the --legs jobs")
+    ap.add_argument("--nz", type=int, default=8, help="levels per sweep launch (--full)")
+    ap.add_argument("--apply-steps", type=int, default=50, help="timed calls per sweep leg (--full)")
+    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each, the headline's the first (--full)")
+    ap.add_argument("--no-phase-timing", action="store_true", help="skip the separate pass that records per-phase HIP events (--full)")
+    ap.add_argument("--legs", default=None, help="with --full: comma list of extra legs: gc,pcie,config4,config5,cpu,c768,c768gc,config5_full "
+                                                 "(or all / none; default all); all = the first five; with --gpus N > 1 the c768 jobs always run")
+    ap.add_argument("--cpu-rows", type=int, default=32, help="source rows in the CPU baseline sample (0 = skip; --full)")
+    ap.add_argument("--gc-steps", type=int, default=3, help="timed great-circle searches of the same grids (N=1 only; 0 = skip; --full)")
     args = ap.parse_args()
+    if args.legs is not None and not args.full:
+        ap.error("--legs selects jobs of the --full run: add --full")
 
     import torch
     import torch.distributed as dist
@@ -437,7 +463,7 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    ni, nlon, nlat, nz = args.ni, args.nlon, args.nlat, args.nz
+    ni, nlon, nlat = args.ni, args.nlon, args.nlat
     lon, lat, lont, latt = fg.gnomonic_ed_grid(ni)
     lo, la = fg.latlon_corners(nlon, nlat)
     j0, j1 = fg.band_rows(nlat, world, rank)
@@ -447,33 +473,9 @@ def main():
     lo_t = torch.from_numpy(np.ascontiguousarray(lo[j0:j1 + 1])).to(dev)
     la_t = torch.from_numpy(np.ascontiguousarray(la[j0:j1 + 1])).to(dev)
     ncell_in = 6 * ni * ni
-    src_h = synth_fields(lont, latt, nz)
-    src_t = torch.from_numpy(src_h).to(dev)
-    out_t = torch.empty(nz * ny_band * nlon, dtype=torch.float64, device=dev)
-    # order-2 input preparation on the device: halo update across the cube edges + grad_c2l
-    prep = fg.C2lPrep([ni] * 6, [ni] * 6, lon, lat, lont, latt, fg.find_contacts([ni] * 6, [ni] * 6, lon, lat), device=local_rank)
-    prep.set_stream(torch.cuda.current_stream().cuda_stream)
-    data_t = torch.empty(nz, prep.F, dtype=torch.float64, device=dev)
-    gx_t = torch.empty(nz, ncell_in, dtype=torch.float64, device=dev)
-    gy_t = torch.empty_like(gx_t)
-
-    def prepare():
-        prep.fill_halo(src_t, data_t, nz)
-        prep.gradient(data_t, nz, gx_t, gy_t)
-
-    for _ in range(3):
-        prepare()
-    torch.cuda.synchronize()
-    tp = time.perf_counter()
-    prep_steps = 20
-    for _ in range(prep_steps):
-        prepare()
-    torch.cuda.synchronize()
-    dtp = (time.perf_counter() - tp) / prep_steps
-    total_sums = torch.empty(3 * ncell_in, dtype=torch.float64, device=dev)
     mean_dlat, mean_dlon = np.pi / nlat, 2 * np.pi / nlon
     stream = torch.cuda.current_stream().cuda_stream
-    legs = {"gc", "pcie", "config4", "config5", "cpu"} if args.legs == "all" else set(x for x in args.legs.split(",") if x and x != "none")
+    legs = {"gc", "pcie", "config4", "config5", "cpu"} if args.legs in (None, "all") else set(x for x in args.legs.split(",") if x and x != "none")
 
     def barrier():
         if world > 1:
@@ -489,29 +491,32 @@ def main():
     mk = lambda: fg.XgridPlan.create_dev(2, [ni] * 6, [ni] * 6, lon_t, lat_t, nlon, ny_band, lo_t, la_t, mean_dlat, mean_dlon,
                                          device=local_rank, stream=stream)
     if world > 1:
-        lo_full, la_full = torch.from_numpy(lo).to(dev), torch.from_numpy(la).to(dev)
-        pf = fg.XgridPlan.create_dev(2, [ni] * 6, [ni] * 6, lon_t, lat_t, nlon, nlat, lo_full, la_full, mean_dlat, mean_dlon,
-                                     device=local_rank, stream=stream)        # the un-banded job: the single-rank sums, for the check
-        cs = pf.get_cell_struct(0, ncell_in)          # 0 = source cells
-        a_in_full = np.asarray(pf.get_cell_area(nlon * nlat)[0]).copy()       # (a culled plan reports area 0 for the cells it skipped)
-        serial = torch.empty(3 * ncell_in, dtype=torch.float64, device=dev)
-        pf.copy_cell_sums(serial)
-        pf.destroy(); del lo_full, la_full
-        bidx = fg.boundary_source_cells(cs["lat_min"], cs["lat_max"], la, nlat, world)
-        bidx_t = torch.from_numpy(bidx.astype(np.int64)).to(dev)
+        if args.full:
+            lo_full, la_full = torch.from_numpy(lo).to(dev), torch.from_numpy(la).to(dev)
+            pf = fg.XgridPlan.create_dev(2, [ni] * 6, [ni] * 6, lon_t, lat_t, nlon, nlat, lo_full, la_full, mean_dlat, mean_dlon,
+                                         device=local_rank, stream=stream)        # the un-banded job: the single-rank sums, for the check
+            cs = pf.get_cell_struct(0, ncell_in)          # 0 = source cells
+            a_in_full = np.asarray(pf.get_cell_area(nlon * nlat)[0]).copy()       # (a culled plan reports area 0 for the cells it skipped)
+            serial = torch.empty(3 * ncell_in, dtype=torch.float64, device=dev)
+            pf.copy_cell_sums(serial)
+            pf.destroy(); del lo_full, la_full
+            bidx = fg.boundary_source_cells(cs["lat_min"], cs["lat_max"], la, nlat, world)
+            bidx_t = torch.from_numpy(bidx.astype(np.int64)).to(dev)
         fg.lib().fg_set_search_cull(1)          # each rank builds records only for the source cells that can meet its band
         pc = mk()
         ex = fg.CellSumExchange([pc], str(dev))
-        # one-off check of the exchange the timed steps use: for every source cell with exchange cells on this rank the handed-over
-        # sums must carry the BITS of the single-rank search's sums (bands in rank order = ascending destination index)
-        total = ex.run([pc], complete=False)
-        loc = torch.empty(3 * ncell_in, dtype=torch.float64, device=dev)
-        pc.copy_cell_sums(loc)
-        mine3 = (loc[:ncell_in] != 0).repeat(3)
-        exchange_check = {"cells_on_this_rank": int(mine3.sum().item()) // 3, "shared_cells": ex.nsh,
-                          "bit_identical_to_single_rank_sums": bool(torch.equal(total[mine3], serial[mine3]))}
-        torch.cuda.synchronize()
-        pc.destroy(); del serial, loc, total
+        if args.full:
+            # one-off check of the exchange the timed steps use: for every source cell with exchange cells on this rank the handed-over
+            # sums must carry the BITS of the single-rank search's sums (bands in rank order = ascending destination index)
+            total = ex.run([pc], complete=False)
+            loc = torch.empty(3 * ncell_in, dtype=torch.float64, device=dev)
+            pc.copy_cell_sums(loc)
+            mine3 = (loc[:ncell_in] != 0).repeat(3)
+            exchange_check = {"cells_on_this_rank": int(mine3.sum().item()) // 3, "shared_cells": ex.nsh,
+                              "bit_identical_to_single_rank_sums": bool(torch.equal(total[mine3], serial[mine3]))}
+            torch.cuda.synchronize()
+            del serial, loc, total
+        pc.destroy()
 
     def step(mode="ordered"):
         if plan[0] is not None:
@@ -527,7 +532,7 @@ def main():
         plan[0] = p
         return p
 
-    # ---- headline: K steps per timed region, profiling events OFF; the region is repeated to show the spread
+    # ---- headline: one timed region of --steps steps, profiling events OFF (--full repeats the region to show the spread)
     fg.lib().fg_set_profiling(0)
     # one rank, one destination tile: the plan's own per-cell sums are the totals, so the search queues its finalize work itself
     # (fg_set_search_finalize; what setup_conserve_interp does in that case) -- same kernels, one host round trip less per step
@@ -536,7 +541,7 @@ def main():
     for _ in range(args.warmup):
         step()
     reps = []
-    for rep in range(max(1, args.repeats)):
+    for rep in range(max(1, args.repeats) if args.full else 1):
         barrier(); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -544,6 +549,42 @@ def main():
         torch.cuda.synchronize(); barrier()
         reps.append(time.perf_counter() - t0)
     fg.lib().fg_set_search_finalize(0)
+    p = plan[0]
+    nx_local = p.nxgrid
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, p, "" if world == 1 else f"rank{rank}_", (1 << 20) // world)
+    reps_t = torch.tensor(reps, dtype=torch.float64, device=dev)
+    nx_t = torch.tensor([float(nx_local)], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(reps_t, op=dist.ReduceOp.MAX)
+        dist.all_reduce(nx_t)
+    reps = [float(v) for v in reps_t.cpu()]
+    nx_total = int(nx_t.item())
+    dt = reps[0]
+    nsteps = max(args.steps, 1)
+    line = {
+        "metric": "exchange-cells/s", "value": args.steps * nx_total / dt, "unit": "exchange-cells/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / nsteps * 1e3,
+        "timing_note": "one timed region of `steps` steps after `warmup` warm-up steps (max over ranks); HIP-event phase timing is OFF in it",
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"C{ni} cubed sphere (6 tiles) -> {nlon}x{nlat} lat-lon, conservative_order2: "
+                               "exchange-grid search + centroid pass + CSR build per step",
+                   "nxgrid": nx_total, "parallelism": f"{world} latitude band(s) of the target, one per GPU", "world_size": world,
+                   "exchange": (None if world == 1 else f"the product's: running (area, clon, clat) sums of the {ex.nsh} source cells present on "
+                                f"several ranks ({100.0 * ex.nsh / ncell_in:.2f} % of {ncell_in}) handed from rank to rank by {world} broadcasts "
+                                "(parallel.CellSumExchange, conserve_interp.c:203-221's order: bit-identical to one rank)")},
+        "step_calls": ("one: the search queues its finalize work itself before its single synchronisation (fg_set_search_finalize: one destination "
+                       "tile on one rank, the plan's own per-cell sums are the totals)" if fused else
+                       "fg_plan_create_dev, exchange of the shared cells' sums, fg_plan_finalize(totals)"),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     two_call_ms = None
     if fused:                # the same steps as two calls (fg_plan_create_dev, then fg_plan_finalize): what a multi-tile / multi-rank job does
         for _ in range(3):
@@ -566,7 +607,6 @@ def main():
         alt_ms = float(alt_t[0]) / args.steps * 1e3
         step()
     p = plan[0]
-    nx_local = p.nxgrid
     stats = p.stats()
     # ---- per-phase device times: a separate pass with HIP events on the plan's streams (they cost ~0.1 ms per step)
     phase_acc = {}
@@ -578,15 +618,34 @@ def main():
                 for k, v in p.phase_ms().items():
                     phase_acc[k] = phase_acc.get(k, 0.0) + v / 5.0
     fg.lib().fg_set_profiling(1)
-    reps_t = torch.tensor(reps, dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(reps_t, op=dist.ReduceOp.MAX)
-    reps = [float(v) for v in reps_t.cpu()]
-    dt = float(np.median(reps))
     fg.lib().fg_set_search_cull(0)
 
     trace = (lambda m: print(f"[trace rank {rank}] {m}", file=sys.stderr, flush=True)) if os.environ.get("FG_BENCH_TRACE") else (lambda m: None)
     trace("search done")
+    # ---- order-2 input preparation on the device: halo update across the cube edges + grad_c2l
+    nz = args.nz
+    src_h = synth_fields(lont, latt, nz)
+    src_t = torch.from_numpy(src_h).to(dev)
+    out_t = torch.empty(nz * ny_band * nlon, dtype=torch.float64, device=dev)
+    prep = fg.C2lPrep([ni] * 6, [ni] * 6, lon, lat, lont, latt, fg.find_contacts([ni] * 6, [ni] * 6, lon, lat), device=local_rank)
+    prep.set_stream(torch.cuda.current_stream().cuda_stream)
+    data_t = torch.empty(nz, prep.F, dtype=torch.float64, device=dev)
+    gx_t = torch.empty(nz, ncell_in, dtype=torch.float64, device=dev)
+    gy_t = torch.empty_like(gx_t)
+
+    def prepare():
+        prep.fill_halo(src_t, data_t, nz)
+        prep.gradient(data_t, nz, gx_t, gy_t)
+
+    for _ in range(3):
+        prepare()
+    torch.cuda.synchronize()
+    tp = time.perf_counter()
+    prep_steps = 20
+    for _ in range(prep_steps):
+        prepare()
+    torch.cuda.synchronize()
+    dtp = (time.perf_counter() - tp) / prep_steps
     # ---- sweep leg
     apply_steps = args.apply_steps
     for _ in range(3):
@@ -684,10 +743,8 @@ def main():
     nx_total, gsum_out, gsum_xgrid = int(tot[0].item()), float(tot[1].item()), float(tot[2].item())
 
     if rank == 0:
-        value = args.steps * nx_total / dt
         ndst = nlon * nlat
         remap_pts = apply_steps * ndst * nz / dta
-        nsteps = max(args.steps, 1)
         phases = dict(phase_acc)
         # algorithmic bytes (destination corners counted once because all six source
         # tiles are searched in one pass): 16 B per corner read, 8 B per source cell (mask), 40 B per xcell written
@@ -749,24 +806,12 @@ def main():
         # mass conservation (conserve_interp.c:874-907): input flux uses get_grid_area cell areas
         a_in = a_in_full if a_in_full is not None else np.asarray(p.get_cell_area(nlon * ny_band)[0])
         gsum_in = float(np.sum(src_h[0] * a_in))
-        line = {
-            "metric": "exchange-cells/s", "value": value, "unit": "exchange-cells/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / nsteps * 1e3,
+        line.update({
             "repeats": len(reps), "ms_per_step_min": min(reps) / nsteps * 1e3, "ms_per_step_all": [r / nsteps * 1e3 for r in reps],
-            "timing_note": "median over `repeats` timed regions of `steps` steps each (max over ranks per region); HIP-event phase "
-                           "timing is OFF in them, phase_ms comes from a separate pass",
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"C{ni} cubed sphere (6 tiles) -> {nlon}x{nlat} lat-lon, conservative_order2: "
-                                   "exchange-grid search + centroid pass + CSR build per step",
-                       "nxgrid": nx_total, "parallelism": f"{world} latitude band(s) of the target, one per GPU", "world_size": world,
-                       "exchange": (None if world == 1 else f"the product's: running (area, clon, clat) sums of the {ex.nsh} source cells present on "
-                                    f"several ranks ({100.0 * ex.nsh / ncell_in:.2f} % of {ncell_in}) handed from rank to rank by {world} broadcasts "
-                                    "(parallel.CellSumExchange, conserve_interp.c:203-221's order: bit-identical to one rank)")},
+            "ms_per_step_median": float(np.median(reps)) / nsteps * 1e3,
+            "repeats_note": "`repeats` timed regions of `steps` steps each, the first the headline's (max over ranks per region); "
+                            "phase_ms comes from a separate pass with HIP-event phase timing on",
             "exchange_check": exchange_check,
-            "step_calls": ("one: the search queues its finalize work itself before its single synchronisation (fg_set_search_finalize: one destination "
-                           "tile on one rank, the plan's own per-cell sums are the totals)" if fused else
-                           "fg_plan_create_dev, exchange of the shared cells' sums, fg_plan_finalize(totals)"),
             "ms_per_step_two_calls": two_call_ms,
             "ms_per_step_allreduce_exchange": alt_ms,
             "allreduce_exchange_note": (None if world == 1 else "same steps with ONE sparse all-reduce of partial sums in place of the hand-over: "
@@ -792,8 +837,7 @@ def main():
                         "the sweep's [cell][field,grad_x,grad_y][level] records (no halo'd copy, no level-major gradients, no merge pass)"},
             "phase_ms": phases, "search_stats": stats,
             "roofline": roof, "roofline_apply": roof_a,
-        }
-        pass
+        })
     # ---- the larger job of BASELINE config 4 (C768 -> 0.125 deg, 16.7 M exchange cells), same decomposition: where strong scaling
     # is not bound by launch latency.  Collective: every rank takes part.
     c768 = c768gc = None

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-3 rocprofv3 passes (each counter group in its own run with --kernel-trace only).
-#   bench headline (bench.py --legs none): stats -- the kernel averages the bench line's roofline quotes
+#   bench headline (bench.py --full --legs none): stats -- the kernel averages the bench line's roofline quotes
 #   search (prof_step.py legacy): stats, FETCH_SIZE, WRITE_SIZE, instruction mix (f64 / int / cycles)
 #   gc     (prof_step.py gc):     stats, FETCH/WRITE, instruction mix
 #   sweep  (prof_step.py sweep):  stats, fabric requests by size, L2
@@ -12,7 +12,7 @@ run() { # tag mode counters...
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $R/r03_pmc_$tag -o p -- python3 scripts/prof_step.py 3 $mode > $R/r03_pmc_$tag.log 2>&1 || { echo "pmc $tag failed"; tail -3 $R/r03_pmc_$tag.log; exit 1; }
   echo "pmc $tag done"
 }
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/r03_stats_bench_headline -o s -- python3 bench.py --legs none --cpu-rows 0 --gc-steps 0 > $R/r03_stats_bench_headline.log 2>&1 || exit 5
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/r03_stats_bench_headline -o s -- python3 bench.py --full --legs none --cpu-rows 0 --gc-steps 0 > $R/r03_stats_bench_headline.log 2>&1 || exit 5
 echo "stats bench headline done"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $R/r03_stats_search -o s -- python3 scripts/prof_step.py 10 legacy > $R/r03_stats_search.log 2>&1 || exit 2
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $R/r03_stats_sweep -o s -- python3 scripts/prof_step.py 10 sweep > $R/r03_stats_sweep.log 2>&1 || exit 3

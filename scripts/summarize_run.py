@@ -4,7 +4,8 @@ tag = sys.argv[1]
 try:
     d = json.loads(open(f"gpurun_out/{tag}_b.json").read().strip().split("\n")[-1])
     print("cells/s %.3e  ms/step %.4f" % (d["value"], d["ms_per_step"]))
-    print({k: round(v, 4) for k, v in d["phase_ms"].items()})
+    if "phase_ms" in d:                       # bench.py --full only
+        print({k: round(v, 4) for k, v in d["phase_ms"].items()})
 except Exception as e:
     print("no bench line:", e)
 for f in glob.glob(f"gpurun_out/{tag}_prof/*/*_kernel_stats.csv"):

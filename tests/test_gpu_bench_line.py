@@ -1,10 +1,11 @@
 """bench.py prints ONE JSON line with the keys the driver and the judge read (metric / value / unit / n_gpus / steps / warmup /
-ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, plus roofline and cpu_baseline)."""
+ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload; --full adds roofline and cpu_baseline)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_schema(gpu_ok):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "2", "--apply-steps", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--repeats", "2", "--apply-steps", "5",
                         "--legs", "cpu", "--cpu-rows", "1", "--gc-steps", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -34,6 +35,35 @@ def test_bench_line_schema(gpu_ok):
     assert abs(d["mass_rel_err"]) < 2e-9 and abs(d["mass_rel_err_xgrid"]) < 1e-13
 
 
+def test_bench_plain_run_and_dumped_outputs(gpu_ok, tmp_path):
+    """A plain run times exactly --steps steps and prints only the headline; --dump-outputs writes the last step's exchange grid
+    (a seeded sample of at most 2**20 cells, the same in every run) as float32 / float64 .npy files, at most 64 MB in all."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == d["unit"] == "exchange-cells/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["config"]["nxgrid"] == 4160000
+    assert abs(d["value"] - 4 * 4160000 / (d["ms_per_step"] * 4e-3)) < 1e-6 * d["value"]
+    assert 0.5 < d["ms_per_step"] < 5.0
+    assert not {"roofline", "cpu_baseline", "phase_ms", "ms_per_step_all", "remapped_points_per_s"} & set(d)
+    files = {f.name: f for f in out.iterdir()}
+    fields = ("t_in", "i_in", "j_in", "i_out", "j_out", "area", "c1", "c2")
+    assert set(files) == {"nxgrid.npy", "xgrid_index.npy"} | {f"xgrid_{k}.npy" for k in fields}
+    assert sum(f.stat().st_size for f in files.values()) <= 64 << 20
+    x = {k[:-4]: np.load(f) for k, f in files.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in x.values())
+    assert x["nxgrid"][0] == 4160000
+    idx = x["xgrid_index"]
+    assert idx.size == 1 << 20 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 4160000
+    assert all(x["xgrid_" + k].shape == idx.shape for k in fields)
+    assert set(np.unique(x["xgrid_t_in"])) <= set(range(6)) and x["xgrid_i_in"].max() < 384 and x["xgrid_j_in"].max() < 384
+    assert x["xgrid_i_out"].max() < 1440 and x["xgrid_j_out"].max() < 720 and np.all(x["xgrid_area"] > 0)
+
+
 def test_bench_two_ranks_rehearsal(gpu_ok):
     """`bench.py --gpus 2` the way the driver launches it (torch.distributed.run, one process per rank), but with both ranks on
     this one GPU and gloo for the collectives (FG_BENCH_BACKEND=gloo): times mean nothing, the N > 1 code path does -- the
@@ -41,7 +71,7 @@ def test_bench_two_ranks_rehearsal(gpu_ok):
     wrong flux sum that no single-process test could see.)"""
     env = dict(os.environ, FG_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1",
+                        "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "1",
                         "--apply-steps", "5"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
