@@ -27,6 +27,8 @@ from .remap_file import write_remap_file, read_remap_file  # noqa: F401
 from .field_io import NcFile, Sweep, HostBuffer, read_field_levels  # noqa: F401
 from . import field_io  # noqa: F401
 from .coupler import coupler_xgrid  # noqa: F401
+from .bilinear import (BilinearPlan, setup_bilinear_interp, do_scalar_bilinear_interp, do_vector_bilinear_interp,  # noqa: F401
+                       write_bilinear_remap_file, read_bilinear_remap_file)
 from .parallel import (band_rows, row_cost, allreduce_cell_sums, allreduce_scalar_sum, allreduce_minmax,  # noqa: F401
                        boundary_source_cells, allreduce_cell_sums_sparse, ordered_cell_sums, CellSumExchange)
 from .conserve_interp import (  # noqa: F401
@@ -40,6 +42,8 @@ __all__ = [
     "conserve_interp", "setup_conserve_interp", "do_scalar_conserve_interp",
     "GridConfig", "InterpConfig", "FieldConfig", "VarConfig", "XgridPlan",
     "gnomonic_ed_corners", "latlon_corners", "lib", "lib_path", "FregridHipError",
+    "BilinearPlan", "setup_bilinear_interp", "do_scalar_bilinear_interp", "do_vector_bilinear_interp",
+    "write_bilinear_remap_file", "read_bilinear_remap_file",
 ]
 
 

@@ -47,6 +47,10 @@ EXPORTS = [
     "fg_nc_get_att_double", "fg_nc_get_att_text", "fg_nc_get_vara", "fg_nc_get_vara_double", "fg_nc_put_vara", "fg_nc_put_vara_double",
     "fg_nc_close", "fg_nc_last_error", "fg_dev_widen", "fg_dev_narrow", "fg_sweep_create", "fg_sweep_run", "fg_sweep_destroy", "fg_host_alloc", "fg_host_free",
     "fg_plan_stats", "fg_set_search_mode", "fg_set_search_chunks", "fg_set_search_cull", "fg_set_search_finalize", "fg_set_search_rect", "fg_set_search_frame", "fg_set_apply_xcd", "fg_set_apply_vec", "fg_set_apply_ep", "fg_set_gc_split", "fg_set_profiling", "fg_plan_phase_ms", "fg_gnomonic_ed_corners", "fg_latlon_corners",
+    "fg_bilin_create", "fg_bilin_create_from_weights", "fg_bilin_destroy", "fg_bilin_get_index_weight", "fg_bilin_npoints_fine",
+    "fg_bilin_nlon_fine", "fg_bilin_nlat_fine", "fg_bilin_nlon", "fg_bilin_nlat", "fg_bilin_ncells", "fg_bilin_set_stream",
+    "fg_bilin_sync", "fg_bilin_apply_scalar", "fg_bilin_apply_vector", "fg_bilin_remap_write", "fg_bilin_remap_read",
+    "fg_unit_vect_latlon", "fg_bilin_fine_grid", "fg_bilin_ambiguous_ties",
 ]
 
 
@@ -256,6 +260,36 @@ def lib():
     L.fg_plan_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
     L.fg_plan_phase_ms.restype = C.c_int
     lp = C.POINTER(C.c_long)
+    L.fg_bilin_create.argtypes = [C.c_int, ip, ip, dpp, dpp, C.c_int] + [ip] * 10 + [C.c_int] * 3 + [C.c_double] * 4 + \
+        [C.c_int, C.c_int, C.POINTER(vp)]
+    L.fg_bilin_create.restype = C.c_int
+    L.fg_bilin_create_from_weights.argtypes = [C.c_int, ip, ip, dpp, dpp, C.c_int] + [ip] * 10 + [C.c_int] * 3 + \
+        [C.c_double] * 4 + [C.c_int, ip, dp, C.c_int, C.POINTER(vp)]
+    L.fg_bilin_create_from_weights.restype = C.c_int
+    L.fg_bilin_destroy.argtypes = [vp]
+    L.fg_bilin_destroy.restype = None
+    L.fg_bilin_get_index_weight.argtypes = [vp, ip, dp]
+    L.fg_bilin_get_index_weight.restype = C.c_int
+    for name in ("fg_bilin_nlon_fine", "fg_bilin_nlat_fine", "fg_bilin_nlon", "fg_bilin_nlat", "fg_bilin_sync"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = C.c_int
+    for name in ("fg_bilin_npoints_fine", "fg_bilin_ncells", "fg_bilin_ambiguous_ties"):
+        getattr(L, name).argtypes = [vp]
+        getattr(L, name).restype = C.c_long
+    L.fg_bilin_set_stream.argtypes = [vp, vp]
+    L.fg_bilin_set_stream.restype = C.c_int
+    L.fg_bilin_apply_scalar.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp]
+    L.fg_bilin_apply_scalar.restype = C.c_int
+    L.fg_bilin_apply_vector.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp]
+    L.fg_bilin_apply_vector.restype = C.c_int
+    L.fg_bilin_remap_write.argtypes = [C.c_char_p, C.c_int, C.c_int, ip, dp]
+    L.fg_bilin_remap_write.restype = C.c_int
+    L.fg_bilin_remap_read.argtypes = [C.c_char_p, C.c_int, C.c_int, ip, dp]
+    L.fg_bilin_remap_read.restype = C.c_int
+    L.fg_unit_vect_latlon.argtypes = [C.c_long, dp, dp, dp, dp]
+    L.fg_unit_vect_latlon.restype = None
+    L.fg_bilin_fine_grid.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int, dp, dp, dp]
+    L.fg_bilin_fine_grid.restype = None
     L.fg_c2l_create.argtypes = [C.c_int, ip, ip, dpp, dpp, dpp, dpp, C.c_int] + [ip] * 10 + [C.c_int, C.POINTER(vp)]
     L.fg_c2l_create.restype = C.c_int
     L.fg_c2l_destroy.argtypes = [vp]

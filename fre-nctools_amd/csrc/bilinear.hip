@@ -1,0 +1,394 @@
+// bilinear.hip -- host orchestration of the bilinear plan (fg_bilin_*): setup_bilinear_interp's compute and READ branches
+// (tools/fregrid/bilinear_interp.c:72-434) and do_scalar / do_vector_bilinear_interp (:436-560) on the device.
+// Kernels: bilinear_kernels.hip.  Host arithmetic that must round like the reference: bilinear_host.c, c2l_host.c.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+#include <string>
+#include <thread>
+#include <vector>
+#include "bilinear.h"
+#include "fregrid_hip.h"
+
+void fg_set_last_error(const char *msg);
+
+extern "C" {
+void fg_unit_vect_latlon(long size, const double *lon, const double *lat, double *vlon, double *vlat);
+void fg_bilin_fine_grid(int nlon, int nlat, int finer_step, double lonbegin, double lonend, double latbegin, double latend,
+                        int center_y, double *lont, double *latt, double *latt1d);
+void fg_bilin_redu2x_coef(int ny, const double *ylat, double *cosp, double *acosp);
+void fg_bilin_cell_dist(int N, long c0, long c1, const double *x, const double *y, const double *z, double *dist);
+void fg_bilin_dist2side_tail(long n, const double *angle, const double *side_cos, double *dist);
+}
+
+// host threads for the libm passes (bilinear_host.c); each processes [lo, hi) of an index range
+template <typename F> static void bl_parallel(long n, F fn)
+{
+  unsigned nt = std::thread::hardware_concurrency();
+  nt = nt < 1 ? 1 : (nt > 16 ? 16 : nt);
+  if (n < 65536) nt = 1;
+  std::vector<std::thread> w;
+  const long chunk = (n + nt - 1) / nt;
+  for (unsigned t = 1; t < nt; t++) {
+    const long lo = t * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    if (lo < hi) w.emplace_back(fn, lo, hi);
+  }
+  fn(0L, chunk < n ? chunk : n);
+  for (std::thread &x : w) x.join();
+}
+
+static int bl_fail(int code, const char *fmt, ...)
+{
+  char buf[512];
+  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+  fg_set_last_error(buf);
+  return code;
+}
+#define BLCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
+  return bl_fail(FG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+#define BL_MAX_ITER 10                    // setup_bilinear_interp's max_iter (:76)
+
+struct fg_bilin {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  int N = 0, nlon = 0, nlat = 0, finer_step = 0, nxo = 0, nyo = 0;
+  long npts = 0, ncells = 0, F = 0;
+  unsigned ambiguous_ties = 0;             // nearest-centre comparisons libm rounding could decide otherwise (search)
+  std::vector<void *> owned;
+  double *xt = nullptr, *lont = nullptr, *vlon_in = nullptr, *vlat_in = nullptr;   // xt holds xt | yt | zt; lont holds lont | latt
+  double *xo = nullptr, *vlon_o = nullptr, *vlat_o = nullptr;                       // xo holds xo | yo | zo
+  double *cell_dist = nullptr;                                                      // [ncells], see BlGeom
+  int *cell_of = nullptr, *index = nullptr, *elem = nullptr, *cell = nullptr;
+  double *weight = nullptr;
+  std::vector<double *> cosp, acosp;       // per coarsening step, device
+  double *ws = nullptr;                    // apply workspace
+  size_t ws_cap = 0;
+  template <typename T> T *alloc(size_t n)
+  {
+    void *p = nullptr;
+    if (hipMalloc(&p, n * sizeof(T) + 16) != hipSuccess) return nullptr;
+    owned.push_back(p);
+    return (T *)p;
+  }
+  BlGeom geom() const
+  {
+    BlGeom g;
+    g.N = N; g.nxo = nxo; g.nyo = nyo;
+    g.xt = xt; g.yt = xt + F; g.zt = xt + 2 * F; g.lont = lont; g.latt = lont + F;
+    g.xo = xo; g.yo = xo + npts; g.zo = xo + 2 * npts;
+    g.cell_dist = cell_dist;
+    return g;
+  }
+};
+
+extern "C" void fg_bilin_destroy(fg_bilin *h)
+{
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->own_stream) (void)hipStreamDestroy(h->stream);
+  for (void *p : h->owned) (void)hipFree(p);
+  if (h->ws) (void)hipFree(h->ws);
+  delete h;
+}
+
+template <typename T> static bool up(T *dst, const T *src, size_t n)
+{
+  return hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// everything but the search: the halo'd source geometry, the fine lat-lon grid, the coarsening factors
+static int bl_prepare(int ntiles, const int *nx, const int *ny, const double *const *lont, const double *const *latt, int ncontacts,
+                      const int *tile1, const int *tile2, const int *istart1, const int *iend1, const int *jstart1, const int *jend1,
+                      const int *istart2, const int *iend2, const int *jstart2, const int *jend2, int nlon, int nlat, int finer_step,
+                      double lonbegin, double lonend, double latbegin, double latend, int center_y, int device, fg_bilin **out,
+                      std::vector<double> *lat_fine_out)
+{
+  if (!out) return bl_fail(FG_ERR_ARG, "fg_bilin: null output handle");
+  *out = nullptr;
+  if (ntiles != 6) return bl_fail(FG_ERR_ARG, "bilinear_interp: source mosaic should be cubic mosaic and have six tiles when using bilinear option");
+  if (ncontacts != 12) return bl_fail(FG_ERR_ARG, "bilinear_interp: a cubic mosaic has 12 contacts, got %d", ncontacts);
+  if (finer_step < 0) return bl_fail(FG_ERR_ARG, "bilinear_interp: finer_step must be >= 0");
+  if (nlat < 2) return bl_fail(FG_ERR_ARG, "bilinear_interp: nlat must be >= 2");
+  if (nlon < 1 || finer_step > 10) return bl_fail(FG_ERR_ARG, "bilinear_interp: bad nlon / finer_step");
+  if (!nx || !ny || !lont || !latt || !tile1 || !tile2) return bl_fail(FG_ERR_ARG, "fg_bilin: null argument");
+  for (int t = 0; t < 6; t++)
+    if (nx[t] != nx[0] || ny[t] != nx[0] || nx[t] < 2 || nx[t] > 8191 || !lont[t] || !latt[t])
+      return bl_fail(FG_ERR_ARG, "bilinear_interp: the six tiles must be N x N with the same 2 <= N <= 8191");
+  int ndev = 0;
+  BLCHK(hipGetDeviceCount(&ndev));
+  if (ndev < 1) return bl_fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
+  if (device < 0 || device >= ndev) return bl_fail(FG_ERR_ARG, "device out of range");
+  BLCHK(hipSetDevice(device));
+
+  const int N = nx[0], nxd = N + 2;
+  const long T = (long)nxd * nxd, F = 6 * T, ncells = 6L * N * N;
+  // halo map -> halo'd centres with init_halo's zero corners (fregrid_util.c:236-297), and the cell each element holds
+  std::vector<long> map_off(7);
+  std::vector<int> map(F);
+  int rc = fg_halo_map(6, nx, ny, ncontacts, tile1, tile2, istart1, iend1, jstart1, jend1, istart2, iend2, jstart2, jend2,
+                       map_off.data(), map.data());
+  if (rc) return bl_fail(rc, "fregrid_util: inconsistent contact description (size mismatch between the boundary)");
+  std::vector<double> lh(2 * F, 0.0);
+  std::vector<int> cell_of(F, -1);
+  for (int t = 0; t < 6; t++)
+    for (int j = 0; j < N; j++) for (int i = 0; i < N; i++) {
+      const long e = t * T + (long)(j + 1) * nxd + i + 1;
+      lh[e] = lont[t][(long)j * N + i];
+      lh[F + e] = latt[t][(long)j * N + i];
+      cell_of[e] = (int)((long)t * N * N + (long)j * N + i);
+    }
+  for (long e = 0; e < F; e++)
+    if (map[e] >= 0) { lh[e] = lh[map[e]]; lh[F + e] = lh[F + map[e]]; cell_of[e] = cell_of[map[e]]; }
+  std::vector<double> xyz(3 * F), vlon(3 * F), vlat(3 * F);
+  fg_latlon2xyz(F, lh.data(), lh.data() + F, xyz.data(), xyz.data() + F, xyz.data() + 2 * F);
+  std::vector<double> cdist(ncells);
+  bl_parallel(ncells, [&](long lo, long hi) { fg_bilin_cell_dist(N, lo, hi, xyz.data(), xyz.data() + F, xyz.data() + 2 * F, cdist.data()); });
+  fg_unit_vect_latlon(F, lh.data(), lh.data() + F, vlon.data(), vlat.data());
+  // fine lat-lon grid (get_output_grid_by_size, fregrid_util.c:564-641)
+  const int nxo = (int)(pow(2, finer_step) * nlon), nyo = (int)(pow(2, finer_step) * (nlat - 1) + 1);
+  const long npts = (long)nxo * nyo;
+  std::vector<double> lo(npts), la(npts), la1(nyo), xo(3 * npts), vlo(3 * npts), vla(3 * npts);
+  fg_bilin_fine_grid(nlon, nlat, finer_step, lonbegin, lonend, latbegin, latend, center_y, lo.data(), la.data(), la1.data());
+  fg_latlon2xyz(npts, lo.data(), la.data(), xo.data(), xo.data() + npts, xo.data() + 2 * npts);
+  fg_unit_vect_latlon(npts, lo.data(), la.data(), vlo.data(), vla.data());
+
+  fg_bilin *h = new fg_bilin();
+  h->device = device; h->N = N; h->nlon = nlon; h->nlat = nlat; h->finer_step = finer_step;
+  h->nxo = nxo; h->nyo = nyo; h->npts = npts; h->ncells = ncells; h->F = F;
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return bl_fail(FG_ERR_HIP, "hipStreamCreate failed"); }
+  h->own_stream = true;
+  h->xt = h->alloc<double>(3 * F); h->lont = h->alloc<double>(2 * F);
+  h->vlon_in = h->alloc<double>(3 * F); h->vlat_in = h->alloc<double>(3 * F);
+  h->xo = h->alloc<double>(3 * npts); h->vlon_o = h->alloc<double>(3 * npts); h->vlat_o = h->alloc<double>(3 * npts);
+  h->cell_dist = h->alloc<double>(ncells);
+  h->cell_of = h->alloc<int>(F); h->index = h->alloc<int>(3 * npts); h->weight = h->alloc<double>(4 * npts);
+  h->elem = h->alloc<int>(4 * npts); h->cell = h->alloc<int>(4 * npts);
+  bool ok = h->cell_dist && h->xt && h->lont && h->vlon_in && h->vlat_in && h->xo && h->vlon_o && h->vlat_o && h->cell_of && h->index &&
+            h->weight && h->elem && h->cell;
+  ok = ok && up(h->xt, xyz.data(), 3 * F) && up(h->lont, lh.data(), 2 * F) && up(h->vlon_in, vlon.data(), 3 * F) &&
+       up(h->vlat_in, vlat.data(), 3 * F) && up(h->xo, xo.data(), 3 * npts) && up(h->vlon_o, vlo.data(), 3 * npts) &&
+       up(h->vlat_o, vla.data(), 3 * npts) && up(h->cell_of, cell_of.data(), F) && up(h->cell_dist, cdist.data(), ncells);
+  // coarsening factors per step (do_latlon_coarsening :994-1040): step 1 on the fine latitudes, later steps on -90..90
+  int ny_s = nyo;
+  for (int s = 1; s <= finer_step && ok; s++) {
+    std::vector<double> c(ny_s), a(ny_s);
+    fg_bilin_redu2x_coef(ny_s, s == 1 ? la1.data() : nullptr, c.data(), a.data());
+    double *dc = h->alloc<double>(ny_s), *da = h->alloc<double>(ny_s);
+    ok = dc && da && up(dc, c.data(), ny_s) && up(da, a.data(), ny_s);
+    h->cosp.push_back(dc); h->acosp.push_back(da);
+    ny_s = (ny_s - 1) / 2 + 1;
+  }
+  if (!ok) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: out of device memory or upload failed"); }
+  if (lat_fine_out) *lat_fine_out = la1;
+  *out = h;
+  return 0;
+}
+
+// fregrid.c:944-963: the search's longitude / latitude span and origin
+static void bl_span(double lonbegin, double lonend, double latbegin, double latend, double *dlon_in, double *dlat_in,
+                    double *lonbegin_in, double *latbegin_in)
+{
+  const double D2R = M_PI / 180, EPSLN10 = 1.e-10;
+  *dlon_in = (fabs(lonend - lonbegin - 360) < EPSLN10) ? M_PI + M_PI : (lonend - lonbegin) * D2R;
+  *dlat_in = (fabs(latend - latbegin - 180) < EPSLN10) ? M_PI : (latend - latbegin) * D2R;
+  *lonbegin_in = (fabs(lonbegin) < EPSLN10) ? 0.0 : lonbegin * D2R;
+  *latbegin_in = (fabs(latbegin + 90) < EPSLN10) ? -0.5 * M_PI : latbegin * D2R;
+}
+
+extern "C" int fg_bilin_create(int ntiles, const int *nx, const int *ny, const double *const *lont, const double *const *latt,
+                               int ncontacts, const int *tile1, const int *tile2, const int *istart1, const int *iend1,
+                               const int *jstart1, const int *jend1, const int *istart2, const int *iend2, const int *jstart2,
+                               const int *jend2, int nlon, int nlat, int finer_step, double lonbegin, double lonend,
+                               double latbegin, double latend, int center_y, int device, fg_bilin **out)
+{
+  fg_bilin *h = nullptr;
+  int rc = bl_prepare(ntiles, nx, ny, lont, latt, ncontacts, tile1, tile2, istart1, iend1, jstart1, jend1, istart2, iend2, jstart2,
+                      jend2, nlon, nlat, finer_step, lonbegin, lonend, latbegin, latend, center_y, device, &h, nullptr);
+  if (rc) return rc;
+  double dlon_in, dlat_in, lonbegin_in, latbegin_in;
+  bl_span(lonbegin, lonend, latbegin, latend, &dlon_in, &dlat_in, &lonbegin_in, &latbegin_in);
+  const double dlon = dlon_in / h->nxo, dlat = dlat_in / (h->nyo - 1);
+  const long ncell = h->ncells, nb = fgd_bl_scan_blocks(ncell);
+  // search scratch
+  BlWin *win = h->alloc<BlWin>(ncell);
+  unsigned long long *cnt = h->alloc<unsigned long long>(ncell), *off = h->alloc<unsigned long long>(ncell);
+  unsigned long long *bsum = h->alloc<unsigned long long>(nb + 1), *total = h->alloc<unsigned long long>(1);
+  unsigned long long *key = h->alloc<unsigned long long>(h->npts);
+  int *found = h->alloc<int>(h->npts);
+  unsigned *unfound = h->alloc<unsigned>(BL_MAX_ITER + 2);      // [BL_MAX_ITER + 1]: ambiguous ties
+  if (!win || !cnt || !off || !bsum || !total || !key || !found || !unfound) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: out of device memory"); }
+  hipStream_t st = h->stream;
+  bool ok = hipMemsetAsync(key, 0xff, h->npts * sizeof(unsigned long long), st) == hipSuccess &&
+            hipMemsetAsync(found, 0, h->npts * sizeof(int), st) == hipSuccess &&
+            hipMemsetAsync(unfound, 0, (BL_MAX_ITER + 2) * sizeof(unsigned), st) == hipSuccess &&
+            hipMemsetAsync(h->index, 0, 3 * h->npts * sizeof(int), st) == hipSuccess;
+  hipDeviceProp_t prop;
+  int pair_blocks = 4096;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) pair_blocks = prop.multiProcessorCount * 16;
+  const BlGeom g = h->geom();
+  for (int iter = 1; iter <= BL_MAX_ITER && ok; iter++)
+    fgd_bl_search_iter(g, iter, dlon, dlat, lonbegin_in, latbegin_in, unfound, win, cnt, off, bsum, total, found, key, h->index,
+                       unfound + BL_MAX_ITER + 1, pair_blocks, st);
+  unsigned left2[2] = {0, 0};
+  ok = ok && hipGetLastError() == hipSuccess &&
+       hipMemcpyAsync(left2, unfound + BL_MAX_ITER, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st) == hipSuccess &&
+       hipStreamSynchronize(st) == hipSuccess;
+  const unsigned left = left2[0];
+  h->ambiguous_ties = left2[1];
+  if (!ok) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: search kernels failed"); }
+  if (left) {
+    fg_bilin_destroy(h);
+    return bl_fail(FG_ERR_BILIN_NOTFOUND, "bilinear_interp: %u lat-lon points have no lower-left corner after %d sweeps "
+                   "(the reference would start its global sweep here, which reads past its arrays; not reproduced)", left, BL_MAX_ITER);
+  }
+  // weights: angles and side cosines on the device, acos / sin / asin with the host libm, the combination on the device
+  {
+    const long n4 = 4 * h->npts;
+    double *dev = h->alloc<double>(2 * n4);
+    std::vector<double> side(2 * n4), dist(n4);
+    ok = dev != nullptr;
+    if (ok) fgd_bl_weight_sides(g, h->index, dev, dev + n4, st);
+    ok = ok && hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(side.data(), dev, 2 * n4 * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipStreamSynchronize(st) == hipSuccess;
+    if (ok) bl_parallel(n4, [&](long lo, long hi) { fg_bilin_dist2side_tail(hi - lo, side.data() + lo, side.data() + n4 + lo, dist.data() + lo); });
+    ok = ok && hipMemcpyAsync(dev, dist.data(), n4 * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) fgd_bl_weight_final(h->npts, h->N, h->index, dev, h->weight, st);
+    if (ok) fgd_bl_corners(g, h->index, h->cell_of, h->elem, h->cell, st);
+    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    for (size_t k = 0; dev && k < h->owned.size(); k++) if (h->owned[k] == dev) { (void)hipFree(dev); h->owned.erase(h->owned.begin() + k); break; }
+  }
+  // the search scratch goes back at once
+  for (void *p : {(void *)win, (void *)cnt, (void *)off, (void *)bsum, (void *)total, (void *)key, (void *)found, (void *)unfound}) {
+    for (size_t k = 0; k < h->owned.size(); k++) if (h->owned[k] == p) { (void)hipFree(p); h->owned.erase(h->owned.begin() + k); break; }
+  }
+  if (!ok) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: weight kernel failed"); }
+  *out = h;
+  return 0;
+}
+
+extern "C" int fg_bilin_create_from_weights(int ntiles, const int *nx, const int *ny, const double *const *lont,
+                                            const double *const *latt, int ncontacts, const int *tile1, const int *tile2,
+                                            const int *istart1, const int *iend1, const int *jstart1, const int *jend1,
+                                            const int *istart2, const int *iend2, const int *jstart2, const int *jend2, int nlon,
+                                            int nlat, int finer_step, double lonbegin, double lonend, double latbegin, double latend,
+                                            int center_y, const int *index, const double *weight, int device, fg_bilin **out)
+{
+  if (!index || !weight) return bl_fail(FG_ERR_ARG, "fg_bilin_create_from_weights: null index / weight");
+  fg_bilin *h = nullptr;
+  int rc = bl_prepare(ntiles, nx, ny, lont, latt, ncontacts, tile1, tile2, istart1, iend1, jstart1, jend1, istart2, iend2, jstart2,
+                      jend2, nlon, nlat, finer_step, lonbegin, lonend, latbegin, latend, center_y, device, &h, nullptr);
+  if (rc) return rc;
+  for (long n = 0; n < h->npts; n++)                   // every corner read by the gather must lie in the halo'd tile
+    if (index[3 * n] < 0 || index[3 * n] > h->N || index[3 * n + 1] < 0 || index[3 * n + 1] > h->N || index[3 * n + 2] < 0 ||
+        index[3 * n + 2] > 5) {
+      fg_bilin_destroy(h);
+      return bl_fail(FG_ERR_ARG, "fg_bilin_create_from_weights: index of point %ld out of range", n);
+    }
+  if (!up(h->index, index, 3 * h->npts) || !up(h->weight, weight, 4 * h->npts)) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "upload failed"); }
+  fgd_bl_corners(h->geom(), h->index, h->cell_of, h->elem, h->cell, h->stream);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "corner kernel failed"); }
+  *out = h;
+  return 0;
+}
+
+extern "C" int fg_bilin_get_index_weight(const fg_bilin *h, int *index, double *weight)
+{
+  if (!h) return bl_fail(FG_ERR_ARG, "null handle");
+  BLCHK(hipSetDevice(h->device));
+  BLCHK(hipStreamSynchronize(h->stream));
+  if (index) BLCHK(hipMemcpy(index, h->index, 3 * h->npts * sizeof(int), hipMemcpyDeviceToHost));
+  if (weight) BLCHK(hipMemcpy(weight, h->weight, 4 * h->npts * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" long fg_bilin_npoints_fine(const fg_bilin *h) { return h ? h->npts : FG_ERR_ARG; }
+extern "C" int fg_bilin_nlon_fine(const fg_bilin *h) { return h ? h->nxo : FG_ERR_ARG; }
+extern "C" int fg_bilin_nlat_fine(const fg_bilin *h) { return h ? h->nyo : FG_ERR_ARG; }
+extern "C" int fg_bilin_nlon(const fg_bilin *h) { return h ? h->nlon : FG_ERR_ARG; }
+extern "C" int fg_bilin_nlat(const fg_bilin *h) { return h ? h->nlat : FG_ERR_ARG; }
+extern "C" long fg_bilin_ncells(const fg_bilin *h) { return h ? h->ncells : FG_ERR_ARG; }
+extern "C" long fg_bilin_ambiguous_ties(const fg_bilin *h) { return h ? (long)h->ambiguous_ties : FG_ERR_ARG; }
+
+extern "C" int fg_bilin_set_stream(fg_bilin *h, void *stream)
+{
+  if (!h) return bl_fail(FG_ERR_ARG, "null handle");
+  BLCHK(hipSetDevice(h->device));
+  BLCHK(hipStreamSynchronize(h->stream));
+  if (h->own_stream) BLCHK(hipStreamDestroy(h->stream));
+  h->stream = (hipStream_t)stream; h->own_stream = false;
+  return 0;
+}
+extern "C" int fg_bilin_sync(fg_bilin *h)
+{
+  if (!h) return bl_fail(FG_ERR_ARG, "null handle");
+  BLCHK(hipSetDevice(h->device));
+  BLCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+static double *bl_workspace(fg_bilin *h, size_t n)
+{
+  if (n <= h->ws_cap) return h->ws;
+  if (h->ws) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->ws); h->ws = nullptr; h->ws_cap = 0; }
+  if (hipMalloc(&h->ws, n * sizeof(double)) != hipSuccess) { h->ws = nullptr; return nullptr; }
+  h->ws_cap = n;
+  return h->ws;
+}
+
+// do_latlon_coarsening (:994-1040) of nz levels: fine [nz][nyo][nxo] -> out [nz][nlat][nlon]; fine and b are scratch of the same
+// size (overwritten), tmp holds nz * nyo * nxo / 2
+static void bl_coarsen(fg_bilin *h, double *fine, double *b, double *tmp, int nz, int has_missing, double missing, double *out)
+{
+  int nx = h->nxo, ny = h->nyo;
+  double *cur = fine, *other = b;
+  for (int s = 1; s <= h->finer_step; s++) {
+    double *dst = (s == h->finer_step) ? out : other;
+    fgd_bl_redu2x(cur, nx, ny, nz, h->cosp[s - 1], h->acosp[s - 1], has_missing, missing, tmp, dst, h->stream);
+    other = cur; cur = dst;
+    nx = nx / 2; ny = (ny - 1) / 2 + 1;
+  }
+}
+
+extern "C" int fg_bilin_apply_scalar(fg_bilin *h, const double *src, int nz, int has_missing, double missing, int fill_missing,
+                                     double *out)
+{
+  if (!h || !src || !out || nz < 1) return bl_fail(FG_ERR_ARG, "fg_bilin_apply_scalar: bad argument");
+  BLCHK(hipSetDevice(h->device));
+  const size_t nf = (size_t)nz * h->npts;
+  if (h->finer_step == 0) {
+    fgd_bl_gather_scalar(h->npts, h->ncells, nz, h->cell, h->weight, src, has_missing, missing, fill_missing, out, h->stream);
+  } else {
+    double *ws = bl_workspace(h, 3 * nf);
+    if (!ws) return bl_fail(FG_ERR_HIP, "fg_bilin_apply_scalar: out of device memory");
+    fgd_bl_gather_scalar(h->npts, h->ncells, nz, h->cell, h->weight, src, has_missing, missing, fill_missing, ws, h->stream);
+    bl_coarsen(h, ws, ws + nf, ws + 2 * nf, nz, has_missing, missing, out);
+  }
+  BLCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int fg_bilin_apply_vector(fg_bilin *h, const double *u, const double *v, int nz, int has_missing, double missing,
+                                     int fill_missing, double *u_out, double *v_out)
+{
+  if (!h || !u || !v || !u_out || !v_out || nz < 1) return bl_fail(FG_ERR_ARG, "fg_bilin_apply_vector: bad argument");
+  BLCHK(hipSetDevice(h->device));
+  const size_t nf = (size_t)nz * h->npts;
+  if (h->finer_step == 0) {
+    fgd_bl_gather_vector(h->npts, h->ncells, nz, h->elem, h->cell, h->weight, h->vlon_in, h->vlat_in, h->vlon_o, h->vlat_o, u, v,
+                         has_missing, missing, fill_missing, u_out, v_out, h->stream);
+  } else {
+    double *ws = bl_workspace(h, 4 * nf);
+    if (!ws) return bl_fail(FG_ERR_HIP, "fg_bilin_apply_vector: out of device memory");
+    fgd_bl_gather_vector(h->npts, h->ncells, nz, h->elem, h->cell, h->weight, h->vlon_in, h->vlat_in, h->vlon_o, h->vlat_o, u, v,
+                         has_missing, missing, fill_missing, ws, ws + nf, h->stream);
+    bl_coarsen(h, ws, ws + 2 * nf, ws + 3 * nf, nz, has_missing, missing, u_out);
+    bl_coarsen(h, ws + nf, ws + 2 * nf, ws + 3 * nf, nz, has_missing, missing, v_out);
+  }
+  BLCHK(hipGetLastError());
+  return 0;
+}

@@ -19,10 +19,15 @@
 
 #ifdef __HIPCC__
 #define FG_HD __host__ __device__ __forceinline__
-#define FG_HDN __host__ __device__
 #else
 #define FG_HD static inline
+#endif
+#ifndef FG_HDN            /* a second translation unit of the library defines it `static` to keep its own copies */
+#ifdef __HIPCC__
+#define FG_HDN __host__ __device__
+#else
 #define FG_HDN static inline
+#endif
 #endif
 
 // value = (-1)^s * m * 2^(e-63); m has bit 63 set, or m == 0 for zero

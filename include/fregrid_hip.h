@@ -58,6 +58,7 @@ extern "C" {
 #define FG_ERR_GEOM       (-8)   /* the great-circle clip hit one of the reference's fatal geometry checks (create_xgrid.c:1575-1834) */
 #define FG_ERR_IO         (-9)   /* file I/O (fg_nc_*, fg_remap_*)                            */
 #define FG_ERR_NOTFOUND   (-10)  /* attribute / variable not present                          */
+#define FG_ERR_BILIN_NOTFOUND (-11) /* bilinear search: points without a lower-left corner after 10 sweeps (fg_bilin_create) */
 #define FG_ERR_DATA       (-7)   /* the field data hit one of the reference's fatal checks (conserve_interp.c:584,:697,:709) */
 
 /* option bits, same values as tools/libfrencutils/globals.h:46-61 where they exist */
@@ -612,6 +613,68 @@ int fg_sincos_batch(long n, const double *x, double *s, double *c, int device);
  * nlon x nlat model cells, bounds in degrees, lonc/latc[(nlat+1)*(nlon+1)] radians.  Input synthesis only (see grid_gen.c). */
 int fg_tripolar_corners(int nlon, int nlat, double xbnd0, double xbnd1, double ybnd0, double ybnd1, double lat_join,
                         double *lonc, double *latc);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Bilinear cubed-sphere -> lat-lon regridding (fregrid --interp_method bilinear; tools/fregrid/bilinear_interp.c):
+ * setup_bilinear_interp (:72-434) and do_scalar / do_vector_bilinear_interp (:436-560) on the device.
+ * Source: the six N x N tiles of a cubed sphere as T-cell centres lont/latt [N][N] (radians, host) and the mosaic's 12 contacts
+ * in fg_c2l_create's convention; the halo'd centres are built as get_input_grid does (fregrid_util.c:236-312: CENTER halo
+ * update, halo corners left at init_halo's zero).  Target: the lat-lon grid of get_output_grid_by_size (degrees), refined
+ * finer_step times; the search and the weights run on the fine grid, [nlat_fine][nlon_fine] with
+ * nlon_fine = 2^finer_step * nlon and nlat_fine = 2^finer_step * (nlat - 1) + 1.
+ * The libm functions of the search windows and of the weights (acos, sin, asin) are evaluated with the host libm between
+ * two device passes, so the weights round as the reference's do.
+ * index [npts][3] = (ic, jc, tile) of the lower-left source centre in halo'd coordinates (0..N), weight [npts][4] in the order
+ * (ic, jc), (ic, jc+1), (ic+1, jc+1), (ic+1, jc) -- the reference's Interp_config arrays.
+ * Refused with FG_ERR_ARG (the reference exits): ntiles != 6, ncontacts != 12, finer_step < 0, nlat < 2, tiles not N x N.
+ * FG_ERR_BILIN_NOTFOUND: points still unfound after the 10 sweeps (the reference's "global sweep" fallback reads past its
+ * arrays and is not reproduced); fg_last_error() gives the count. */
+typedef struct fg_bilin fg_bilin;
+int  fg_bilin_create(int ntiles, const int *nx, const int *ny, const double *const *lont, const double *const *latt,
+                     int ncontacts, const int *tile1, const int *tile2, const int *istart1, const int *iend1,
+                     const int *jstart1, const int *jend1, const int *istart2, const int *iend2, const int *jstart2,
+                     const int *jend2, int nlon, int nlat, int finer_step, double lonbegin, double lonend,
+                     double latbegin, double latend, int center_y, int device, fg_bilin **out);
+/* the READ branch: index / weight (host, e.g. from fg_bilin_remap_read) instead of the search */
+int  fg_bilin_create_from_weights(int ntiles, const int *nx, const int *ny, const double *const *lont, const double *const *latt,
+                                  int ncontacts, const int *tile1, const int *tile2, const int *istart1, const int *iend1,
+                                  const int *jstart1, const int *jend1, const int *istart2, const int *iend2, const int *jstart2,
+                                  const int *jend2, int nlon, int nlat, int finer_step, double lonbegin, double lonend,
+                                  double latbegin, double latend, int center_y, const int *index, const double *weight,
+                                  int device, fg_bilin **out);
+void fg_bilin_destroy(fg_bilin *h);
+int  fg_bilin_get_index_weight(const fg_bilin *h, int *index, double *weight);   /* host [npts][3], [npts][4]; either may be NULL */
+long fg_bilin_npoints_fine(const fg_bilin *h);
+int  fg_bilin_nlon_fine(const fg_bilin *h);
+int  fg_bilin_nlat_fine(const fg_bilin *h);
+int  fg_bilin_nlon(const fg_bilin *h);
+int  fg_bilin_nlat(const fg_bilin *h);
+long fg_bilin_ncells(const fg_bilin *h);                                          /* 6 * N * N */
+/* nearest-centre comparisons of the search between different distance cosines whose distances were equal or one ulp apart
+ * once correctly rounded: the only
+ * ones the host libm's acos, which is not correctly rounded, could order otherwise (0 for a computed plan that cannot differ
+ * from the reference on that account; 0 for a plan read from weights) */
+long fg_bilin_ambiguous_ties(const fg_bilin *h);
+int  fg_bilin_set_stream(fg_bilin *h, void *stream);
+int  fg_bilin_sync(fg_bilin *h);
+/* src [nz][6*N*N] (tiles back to back, no halo; the halo is read through the contacts) -> out [nz][nlat][nlon], device pointers.
+ * Every level equals a one-level call.  has_missing: a point with any of its four corners equal to missing (a halo corner
+ * counts as 0) gets missing, or with fill_missing the corner of largest weight.  finer_step > 0 coarsens with redu2x, whose
+ * missing-value branch divides the x-swept values by the missing value before the cos(lat) scaling (:1121), as the reference does. */
+int  fg_bilin_apply_scalar(fg_bilin *h, const double *src, int nz, int has_missing, double missing, int fill_missing, double *out);
+/* u, v [nz][6*N*N] eastward / northward components -> u_out, v_out [nz][nlat][nlon]: projected onto x, y, z, interpolated
+ * (missing tested on the projected values) and rotated onto the lat-lon directions (:476-560) */
+int  fg_bilin_apply_vector(fg_bilin *h, const double *u, const double *v, int nz, int has_missing, double missing, int fill_missing,
+                           double *u_out, double *v_out);
+/* fregrid's bilinear remap file (host): dimensions nlon, nlat, three, four; index NC_INT and weight NC_DOUBLE declared
+ * (three|four, nlat, nlon) and holding the point-major arrays as they lie in memory, CDF-2 like fg_remap_write.
+ * fg_bilin_remap_read refuses a file whose nlon / nlat differ from the fine grid's (FG_ERR_ARG). */
+int  fg_bilin_remap_write(const char *path, int nlon_fine, int nlat_fine, const int *index, const double *weight);
+int  fg_bilin_remap_read(const char *path, int nlon_fine, int nlat_fine, int *index, double *weight);
+/* host helpers behind fg_bilin_create (exported for tests): unit_vect_latlon (mosaic_util.c:937) and the fine target grid */
+void fg_unit_vect_latlon(long size, const double *lon, const double *lat, double *vlon, double *vlat);
+void fg_bilin_fine_grid(int nlon, int nlat, int finer_step, double lonbegin, double lonend, double latbegin, double latend,
+                        int center_y, double *lont, double *latt, double *latt1d);
 
 #ifdef __cplusplus
 }
