@@ -706,13 +706,13 @@ double orc_gsum_in(int order, int ntiles_in, const int *nx_in, const int *ny_in,
  * do_scalar_conserve_interp with every branch (conserve_interp.c:507-910): source weight field
  * (weight_exist, :574,:608,:737,:757,:799), cell_methods = sum (:580,:612,:741,:767,:803, final :821-830),
  * cell_measures (:582-588,:614,:743,:769-775,:805, area_missing fatal), the monotone limiter (:617-748) and the
- * --target_grid rescale (:842-869).  Test infrastructure only.  Restated: conserve_interp.c includes mpp_io.h ->
- * <netcdf.h>, so the reference's own object cannot be built here (parity of these branches is UNPINNED against
- * compiled reference code; the plain branch is cross-checked by orc_do_scalar_conserve_interp above, which this
- * function must reproduce bit for bit when all options are off).
+ * --target_grid rescale (:842-869).  Test infrastructure only.  Pinned bit for bit to the reference's own
+ * do_scalar_conserve_interp (oracle/_ref/libconserve_ref.so) by tests/test_conserve_interp_vs_ref.py; it must also
+ * reproduce orc_do_scalar_conserve_interp above bit for bit when all options are off.
  * weight, field_area, cell_area_in: per tile [ny][nx] (NULL pointer = option off; cell_area_in required for
- * sum/measures/target with measures).  Returns 0, -1 (illegal nz combination, :544-546), -2 ("data is not missing
- * but area is missing"), -3 (" xdata is greater than f_bar_max "), -4 (" xdata is less than f_bar_min ").
+ * sum/measures/target with measures).  Returns 0 or the code of the reference's fatal check (tests/orc.py
+ * ORC_APPLY_ERRORS holds its message): -1, -5, -6 (nz > 1 with has_missing, cell_measures, sum; :544-546), -2 ("data is
+ * not missing but area is missing"), -3 (" xdata is greater than f_bar_max "), -4 (" xdata is less than f_bar_min ").
  * Monotone: the reference indexes level 0 only and takes nx1 from the last tile (:648-651); tiles of one mosaic
  * have equal sizes, so nx_in[tile] is used.  One process: the mpp_min/max_double of :672-677 are identities. */
 #define ORC_TOLERANCE 1.e-10                 /* conserve_interp.c:37 */
@@ -735,8 +735,8 @@ int orc_do_scalar_conserve_interp_ex(int order, long nxgrid,
   double missing = -ORC_MAXVAL;
   if (has_missing) missing = missing_in;
   if (nz > 1 && has_missing) return -1;
-  if (nz > 1 && cell_measures) return -1;
-  if (nz > 1 && cell_methods_sum) return -1;
+  if (nz > 1 && cell_measures) return -5;
+  if (nz > 1 && cell_methods_sum) return -6;
   size_t nout = (size_t)nx2 * ny2 * nz;
   double *out_area = (double *)calloc(nout, sizeof(double));
   int *out_miss = (int *)calloc(nout, sizeof(int));

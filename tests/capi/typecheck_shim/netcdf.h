@@ -1,11 +1,13 @@
-/* SHIM, not a netCDF header.  This image has no libnetcdf; tools/libfrencutils/globals.h includes <netcdf.h> only for the
- * `nc_type` typedef (an int in netCDF) of struct members the conservative-interpolation path never reads.  This directory goes on
- * the include path in two places, both of which compile OUR code against the reference's own struct and prototype declarations
- * (globals.h, conserve_interp.h, mpp.h) -- never the reference itself, and never anything used as an oracle:
+/* SHIM, not a netCDF header.  This image has no libnetcdf; it supplies only the `nc_type` typedef (an int in netCDF) and the
+ * NC_* external type codes.  The directory goes on the include path in three places:
  *   tests/test_capi_c.py      gcc -fsyntax-only of integration/conserve_interp_hip.c and integration/field_io_hip.c
  *   oracle/Makefile           oracle/_ref/b2_driver = tests/capi/b2_driver.c + integration/conserve_interp_hip.c
  *                             (+ the reference's mpp.c / mpp_domain.c, which need no netCDF), run by tests/test_gpu_b2_driver.py;
- *                             oracle/_ref/field_io_driver likewise (tests/capi/field_io_driver.c + the two integration objects) */
+ *                             oracle/_ref/field_io_driver likewise (tests/capi/field_io_driver.c + the two integration objects)
+ *   oracle/Makefile           oracle/_ref/libconserve_ref.so, a build of the reference's own tools/fregrid/conserve_interp.c.
+ *                             Its headers name nc_type for struct members that path never reads, and only its WRITE
+ *                             remap-file branch reads NC_INT / NC_DOUBLE; that branch's I/O is stubbed
+ *                             (oracle/conserve_ref_io_stubs.c) and never reached. */
 #ifndef FG_TYPECHECK_NETCDF_SHIM
 #define FG_TYPECHECK_NETCDF_SHIM
 typedef int nc_type;

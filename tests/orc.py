@@ -3,6 +3,8 @@
 * ``oracle/liboracle.so``       our clean-room C restatement (oracle/xgrid_oracle.c)
 * ``oracle/_ref/libfrenc_ref.so`` the reference's own sources compiled in place (oracle/Makefile);
   present in the build container and -- as a prebuilt .so -- on the GPU box.
+* ``oracle/_ref/libconserve_ref.so`` the reference's own conserve_interp.c (setup_conserve_interp,
+  do_scalar_conserve_interp) behind oracle/conserve_ref_adapter.c, built the same way.
 """
 import ctypes as C
 import os
@@ -31,6 +33,7 @@ def f64(a):
 
 _ORACLE = None
 _REF = None
+_CREF = None
 
 
 def oracle():
@@ -129,6 +132,8 @@ def ref():
         L.create_xgrid_2dx2d_order2.restype = C.c_int
         L.conserve_interp.argtypes = [C.c_int] * 4 + [dp] * 7
         L.conserve_interp.restype = None
+        L.conserve_interp_great_circle.argtypes = [C.c_int] * 4 + [dp] * 7
+        L.conserve_interp_great_circle.restype = None
         L.clip_2dx2d_great_circle.argtypes = [dp, dp, dp, C.c_int, dp, dp, dp, C.c_int, dp, dp, dp]
         L.clip_2dx2d_great_circle.restype = C.c_int
         L.great_circle_area.argtypes = [C.c_int, dp, dp, dp]
@@ -310,6 +315,17 @@ def orc_apply_ex(order, x, nx_in, ny_in, data, grad_x, grad_y, grad_mask, has_mi
     return rc, out, gs.value
 
 
+# orc_do_scalar_conserve_interp_ex's error codes -> the message of the reference's fatal check (conserve_interp.c)
+ORC_APPLY_ERRORS = {
+    -1: "conserve_interp: has_missing should be false when nz > 1",
+    -5: "conserve_interp: cell_measures should be false when nz > 1",
+    -6: "conserve_interp: cell_methods should not be sum when nz > 1",
+    -2: "conserve_interp: data is not missing but area is missing",
+    -3: " xdata is greater than f_bar_max ",
+    -4: " xdata is less than f_bar_min ",
+}
+
+
 def orc_create_xgrid_gc(nx1, ny1, nx2, ny2, lon_in, lat_in, lon_out, lat_out, mask=None, j1_beg=0, j1_end=None, capacity=None):
     """create_xgrid_great_circle (oracle restatement); source rows [j1_beg, j1_end)."""
     L = oracle()
@@ -398,6 +414,119 @@ def ref_create_xgrid_box(box_is_src, order, lon_b, lat_b, nxq, nyq, lon_q, lat_q
     if order == 2:
         out["clon"], out["clat"] = cl[:n].copy(), ct[:n].copy()
     return out
+
+
+# ------------------------------------------------------------------------------ the reference's conserve_interp.c
+# option bits (tools/libfrencutils/globals.h)
+CONSERVE_ORDER1, CONSERVE_ORDER2, TARGET, CHECK_CONSERVE, GREAT_CIRCLE, MONOTONIC = 1, 2, 16, 1024, 4096, 16384
+CONSERVE_REF_PATH = os.path.join(ORACLE_DIR, "_ref", "libconserve_ref.so")
+
+
+def conserve_ref_available():
+    return os.path.exists(CONSERVE_REF_PATH)
+
+
+def cref():
+    """oracle/_ref/libconserve_ref.so (None if it has not been built)."""
+    global _CREF
+    if _CREF is None:
+        if not conserve_ref_available():
+            return None
+        L = C.CDLL(CONSERVE_REF_PATH)
+        dpp, ipp = C.POINTER(dp), C.POINTER(ip)
+        L.cref_init.argtypes = []
+        L.cref_init.restype = None
+        L.cref_setup.argtypes = [C.c_uint, C.c_int, ip, ip, dpp, dpp, C.c_int, ip, ip, dpp, dpp, C.c_long, lp] + \
+                                [ip] * 5 + [dp] * 3 + [dpp, dpp]
+        L.cref_setup.restype = C.c_long
+        L.cref_apply.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_int, ip, ip, dpp, C.c_int, ip, ip, dpp, lp] + [ip] * 5 + \
+                                [dp] * 3 + [dpp, dpp, dpp, ipp, C.c_int, C.c_double, dpp, C.c_int, C.c_int, dpp, C.c_double,
+                                            C.c_int, dpp, C.c_char_p, C.c_int]
+        L.cref_apply.restype = C.c_int
+        L.cref_init()
+        _CREF = L
+    return _CREF
+
+
+def cref_setup(order, grids_in, grids_out, great_circle=False, capacity=None):
+    """The reference's setup_conserve_interp (compute branch).  grids_*: lists of (nx, ny, lon, lat) corners.  Returns the
+    dict of orc_setup (exchange cells of every destination tile back to back, xoff) plus the reference caller's
+    cell_area_in / cell_area_out (get_grid_area, or get_grid_great_circle_area with great_circle)."""
+    L = cref()
+    nt, no = len(grids_in), len(grids_out)
+    lon_in = [f64(g[2]).ravel() for g in grids_in]
+    lat_in = [f64(g[3]).ravel() for g in grids_in]
+    lon_out = [f64(g[2]).ravel() for g in grids_out]
+    lat_out = [f64(g[3]).ravel() for g in grids_out]
+    nx_in = np.array([g[0] for g in grids_in], dtype=np.int32)
+    ny_in = np.array([g[1] for g in grids_in], dtype=np.int32)
+    nx_out = np.array([g[0] for g in grids_out], dtype=np.int32)
+    ny_out = np.array([g[1] for g in grids_out], dtype=np.int32)
+    ca_in = [np.empty(g[0] * g[1]) for g in grids_in]
+    ca_out = [np.empty(g[0] * g[1]) for g in grids_out]
+    cap = capacity or 4 * (int(np.sum(nx_in * ny_in)) + int(np.sum(nx_out * ny_out))) * no + 1024
+    xoff = np.zeros(no + 1, dtype=np.int64)
+    t, ii, ji, io, jo = (np.empty(cap, dtype=np.int32) for _ in range(5))
+    a, di, dj = np.empty(cap), np.empty(cap), np.empty(cap)
+    opcode = (CONSERVE_ORDER2 if order == 2 else CONSERVE_ORDER1) | (GREAT_CIRCLE if great_circle else 0)
+    n = L.cref_setup(opcode, nt, _ip(nx_in), _ip(ny_in), _ptr_array(lon_in), _ptr_array(lat_in), no, _ip(nx_out),
+                     _ip(ny_out), _ptr_array(lon_out), _ptr_array(lat_out), cap, xoff.ctypes.data_as(lp),
+                     _ip(t), _ip(ii), _ip(ji), _ip(io), _ip(jo), _dp(a), _dp(di), _dp(dj), _ptr_array(ca_in), _ptr_array(ca_out))
+    if n < 0:
+        raise RuntimeError(f"reference setup: more than {cap} exchange cells")
+    out = dict(n=int(n), xoff=xoff, t_in=t[:n].copy(), i_in=ii[:n].copy(), j_in=ji[:n].copy(), i_out=io[:n].copy(),
+               j_out=jo[:n].copy(), area=a[:n].copy(), cell_area_in=ca_in, cell_area_out=ca_out)
+    if order == 2:
+        out["di"], out["dj"] = di[:n].copy(), dj[:n].copy()
+    return out
+
+
+def cref_apply(order, x, nx_in, ny_in, data, grad_x, grad_y, grad_mask, has_missing, missing, nx2, ny2, nz,
+               weight=None, cell_methods_sum=False, field_area=None, area_missing=-1e20, cell_area_in=None,
+               target_grid=False, cell_area_out=None, monotonic=False, use_volume=False, check_conserve=False):
+    """The reference's do_scalar_conserve_interp, arguments as orc_apply_ex (field_area given = cell_measures).
+    x holds the exchange cells of every destination tile with xoff (a dict without xoff is one tile); nx2 / ny2 /
+    cell_area_out are per destination tile when lists.  Returns (out, printed): out is one array [nz*ny2*nx2] per
+    destination tile (a list when nx2 is a list), printed what the reference wrote to stdout.  A fatal data check of the
+    reference ends the calling process (mpp_error -> exit(1)): run such cases in a child process."""
+    L = cref()
+    multi = isinstance(nx2, (list, tuple, np.ndarray))
+    nx_o = np.asarray(nx2 if multi else [nx2], dtype=np.int32)
+    ny_o = np.asarray(ny2 if multi else [ny2], dtype=np.int32)
+    no = len(nx_o)
+    xoff = np.asarray(x["xoff"], dtype=np.int64) if "xoff" in x else np.array([0, len(x["area"])], dtype=np.int64)
+    assert len(xoff) == no + 1
+    nt = len(nx_in)
+    nxi = np.asarray(nx_in, dtype=np.int32)
+    nyi = np.asarray(ny_in, dtype=np.int32)
+    lst = lambda v: [f64(d).ravel() for d in v] if v is not None else None
+    data, gx, gy, w, fa = lst(data), lst(grad_x), lst(grad_y), lst(weight), lst(field_area)
+    if cell_area_in is None:
+        cell_area_in = [np.ones(int(nxi[t]) * int(nyi[t])) for t in range(nt)]
+    ca = lst(cell_area_in)
+    if cell_area_out is None:
+        cao = [np.ones(int(nx_o[m]) * int(ny_o[m])) for m in range(no)]
+    else:
+        cao = lst(cell_area_out if multi else [cell_area_out])
+    gm = None
+    if order == 2:                     # the monotone branch reads grad_mask whether or not the field has one
+        gm = grad_mask if grad_mask is not None else [np.zeros(int(nxi[t]) * int(nyi[t])) for t in range(nt)]
+        gm = [np.ascontiguousarray(g, dtype=np.int32).ravel() for g in gm]
+    outs = [np.empty(nz * int(nx_o[m]) * int(ny_o[m])) for m in range(no)]
+    ints = [np.ascontiguousarray(x[k], dtype=np.int32) for k in ("t_in", "i_in", "j_in", "i_out", "j_out")]
+    area = f64(x["area"])
+    di = f64(x["di"]) if order == 2 else None
+    dj = f64(x["dj"]) if order == 2 else None
+    pa = lambda v, t=dp: _ptr_array(v, t) if v else None
+    opcode = (TARGET if target_grid else 0) | (MONOTONIC if monotonic else 0) | (CHECK_CONSERVE if check_conserve else 0)
+    msg = C.create_string_buffer(1 << 16)
+    L.cref_apply(opcode, order, nz, nt, _ip(nxi), _ip(nyi), pa(ca), no, _ip(nx_o), _ip(ny_o), pa(cao),
+                 xoff.ctypes.data_as(lp), *[_ip(v) for v in ints], _dp(area), _dp(di), _dp(dj),
+                 pa(data), pa(gx), pa(gy), pa(gm, ip), 1 if has_missing else 0, float(missing), pa(w),
+                 1 if cell_methods_sum else 0, 1 if fa is not None else 0, pa(fa), float(area_missing),
+                 1 if use_volume else 0, pa(outs), msg, len(msg))
+    printed = msg.value.decode(errors="replace")
+    return (outs if multi else outs[0]), printed
 
 
 def host_has_fma():

@@ -139,6 +139,13 @@ def test_conserve_interp_great_circle_b1(fg, gpu_ok):
         ref[d[k]] += data[o["j_in"][k] * ni + o["i_in"][k]] * (o["area"][k] / dst_area[d[k]])
     assert np.max(np.abs(got - ref)) < 1e-12 * np.max(np.abs(ref))
     assert np.count_nonzero(got) == np.count_nonzero(ref) > 0
+    if orc.ref_available():                     # the reference's own conserve_interp_great_circle (interp.c:312)
+        cref = np.empty(nlon * nlat)
+        orc.ref().conserve_interp_great_circle(ni, ni, nlon, nlat, orc._dp(orc.f64(lon[0])), orc._dp(orc.f64(lat[0])),
+                                               orc._dp(orc.f64(lo)), orc._dp(orc.f64(la)), orc._dp(mask), orc._dp(data),
+                                               orc._dp(cref))
+        assert np.max(np.abs(got - cref)) < 1e-12 * np.max(np.abs(cref))
+        assert np.count_nonzero(got) == np.count_nonzero(cref) > 0
 
 
 def test_great_circle_degenerate_cases(fg, gpu_ok):

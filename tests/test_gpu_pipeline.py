@@ -717,6 +717,14 @@ def test_conserve_interp_b1(fg, gpu_ok):
         d = x["j_out"][n] * 20 + x["i_out"][n]
         exp[d] += data[x["j_in"][n] * 36 + x["i_in"][n]] * (x["area"][n] / dst_area[d])
     assert np.max(np.abs(got - exp)) < 1e-12
+    if orc.ref_available():                     # the reference's own conserve_interp (interp.c:262), same operation order
+        ref = np.empty(200)
+        orc.ref().conserve_interp(36, 18, 20, 10, orc._dp(orc.f64(lo1)), orc._dp(orc.f64(la1)), orc._dp(orc.f64(lo2)),
+                                  orc._dp(orc.f64(la2)), orc._dp(np.ones(36 * 18)), orc._dp(data), orc._dp(ref))
+        if orc.host_has_fma():
+            assert np.array_equal(_bits(got), _bits(ref))
+        else:
+            assert np.max(np.abs(got - ref)) < 1e-12
 
 
 def test_polygon_known_answers_on_device(fg, gpu_ok):
