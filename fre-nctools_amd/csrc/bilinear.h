@@ -18,7 +18,7 @@ void fgd_bl_search_iter(const BlGeom &g, int iter, double dlon, double dlat, dou
                         unsigned long long *total, int *found, unsigned long long *key, int *index, unsigned *ties,
                         int pair_blocks, hipStream_t st);
 long fgd_bl_scan_blocks(long ncell);
-void fgd_bl_weight_sides(const BlGeom &g, const int *index, double *angle, double *side_cos, hipStream_t st);
+void fgd_bl_weight_sides(const BlGeom &g, const int *index, double *angle, double *acos_arg, double *side_cos, hipStream_t st);
 void fgd_bl_weight_final(long npts, int N, const int *index, const double *dist, double *weight, hipStream_t st);
 void fgd_bl_corners(const BlGeom &g, const int *index, const int *cell_of, int *elem, int *cell, hipStream_t st);
 void fgd_bl_gather_scalar(long npts, long ncells, int nz, const int *cell, const double *weight, const double *src, int has_missing,

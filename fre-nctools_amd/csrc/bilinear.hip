@@ -19,7 +19,7 @@ void fg_bilin_fine_grid(int nlon, int nlat, int finer_step, double lonbegin, dou
                         int center_y, double *lont, double *latt, double *latt1d);
 void fg_bilin_redu2x_coef(int ny, const double *ylat, double *cosp, double *acosp);
 void fg_bilin_cell_dist(int N, long c0, long c1, const double *x, const double *y, const double *z, double *dist);
-void fg_bilin_dist2side_tail(long n, const double *angle, const double *side_cos, double *dist);
+void fg_bilin_dist2side_tail(long n, const double *angle, const double *acos_arg, const double *side_cos, double *dist);
 }
 
 // host threads for the libm passes (bilinear_host.c); each processes [lo, hi) of an index range
@@ -245,17 +245,20 @@ extern "C" int fg_bilin_create(int ntiles, const int *nx, const int *ny, const d
     return bl_fail(FG_ERR_BILIN_NOTFOUND, "bilinear_interp: %u lat-lon points have no lower-left corner after %d sweeps "
                    "(the reference would start its global sweep here, which reads past its arrays; not reproduced)", left, BL_MAX_ITER);
   }
-  // weights: angles and side cosines on the device, acos / sin / asin with the host libm, the combination on the device
+  // weights: angles, acosl arguments and side cosines on the device, acosl / acos / sin / asin with the host libm, the
+  // combination on the device
   {
     const long n4 = 4 * h->npts;
-    double *dev = h->alloc<double>(2 * n4);
-    std::vector<double> side(2 * n4), dist(n4);
+    double *dev = h->alloc<double>(3 * n4);
+    std::vector<double> side(3 * n4), dist(n4);
     ok = dev != nullptr;
-    if (ok) fgd_bl_weight_sides(g, h->index, dev, dev + n4, st);
+    if (ok) fgd_bl_weight_sides(g, h->index, dev, dev + n4, dev + 2 * n4, st);
     ok = ok && hipGetLastError() == hipSuccess &&
-         hipMemcpyAsync(side.data(), dev, 2 * n4 * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(side.data(), dev, 3 * n4 * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
          hipStreamSynchronize(st) == hipSuccess;
-    if (ok) bl_parallel(n4, [&](long lo, long hi) { fg_bilin_dist2side_tail(hi - lo, side.data() + lo, side.data() + n4 + lo, dist.data() + lo); });
+    if (ok) bl_parallel(n4, [&](long lo, long hi) {
+      fg_bilin_dist2side_tail(hi - lo, side.data() + lo, side.data() + n4 + lo, side.data() + 2 * n4 + lo, dist.data() + lo);
+    });
     ok = ok && hipMemcpyAsync(dev, dist.data(), n4 * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok) fgd_bl_weight_final(h->npts, h->N, h->index, dev, h->weight, st);
     if (ok) fgd_bl_corners(g, h->index, h->cell_of, h->elem, h->cell, st);

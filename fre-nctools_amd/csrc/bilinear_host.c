@@ -99,13 +99,16 @@ void fg_bilin_cell_dist(int N, long c0, long c1, const double *x, const double *
   }
 }
 
-/* the tail of dist2side (:806-815), asin(sin(side) * sin(angle)) with side = acos(side_cos), on n values */
-void fg_bilin_dist2side_tail(long n, const double *angle, const double *side_cos, double *dist)
+/* the tail of dist2side (:806-815), asin(sin(side) * sin(angle)) with side = acos(side_cos), on n values.  angle is
+ * spherical_angle's acosl(acos_arg) rounded to double (mosaic_util.c:834) where acos_arg is not NaN, else the device's angle of
+ * the other branches */
+void fg_bilin_dist2side_tail(long n, const double *angle, const double *acos_arg, const double *side_cos, double *dist)
 {
   long k;
   for (k = 0; k < n; k++) {
     const double side = acos(side_cos[k]);
-    dist[k] = asin(sin(side) * sin(angle[k]));
+    const double a = isnan(acos_arg[k]) ? angle[k] : (double)acosl(acos_arg[k]);
+    dist[k] = asin(sin(side) * sin(a));
   }
 }
 

@@ -19,7 +19,7 @@
 // compares normalize_great_circle_distance values the same way with acos_dd.h's correctly rounded fg_acos_cr as the exact side;
 // where the two correctly rounded distances are equal or one ulp apart -- the only comparisons libm's own rounding could
 // decide otherwise -- a counter is raised (fg_bilin_ambiguous_ties).  The libm acos / sin / asin of the search windows and of
-// the weights are evaluated on the host (bilinear_host.c).  Every double expression keeps the reference's tree
+// the weights (with the acosl of the weights' spherical angles) are evaluated on the host (bilinear_host.c).  Every double expression keeps the reference's tree
 // (-ffp-contract=off).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,11 +38,13 @@
 __device__ __forceinline__ double bl_max(double a, double b) { return a > b ? a : b; }
 __device__ __forceinline__ double bl_min(double a, double b) { return a < b ? a : b; }
 
-// spherical_angle, mosaic_util.c:800-836 (double branch); EXACT: acosl as the reference's x87 build rounds it
+// spherical_angle, mosaic_util.c:800-836 (double branch); EXACT: acosl as the reference's x87 build rounds it.  arg (may be
+// null): the argument handed to acosl, NaN where the angle comes from another branch
 template <bool EXACT>
-__device__ double bl_angle(const double *v1, const double *v2, const double *v3)
+__device__ double bl_angle(const double *v1, const double *v2, const double *v3, double *arg = nullptr)
 {
   double angle, px, py, pz, qx, qy, qz, ddd;
+  if (arg) *arg = __builtin_nan("");
   px = v1[1] * v2[2] - v1[2] * v2[1];
   py = v1[2] * v2[0] - v1[0] * v2[2];
   pz = v1[0] * v2[1] - v1[1] * v2[0];
@@ -56,7 +58,10 @@ __device__ double bl_angle(const double *v1, const double *v2, const double *v3)
     if (fabs(ddd - 1) < BL_EPSLN30) ddd = 1;
     if (fabs(ddd + 1) < BL_EPSLN30) ddd = -1;
     if (ddd > 1. || ddd < -1.) angle = (ddd < 0.) ? BL_PI : 0.;
-    else angle = EXACT ? fg_acosl(ddd) : acos(ddd);
+    else {
+      angle = EXACT ? fg_acosl(ddd) : acos(ddd);
+      if (arg) *arg = ddd;
+    }
   }
   return angle;
 }
@@ -305,16 +310,21 @@ __global__ __launch_bounds__(256) void k_bl_finalize(int N, long npts, int iter,
 }
 
 // weights (:260-406) in two device passes around the host: k_bl_weight_sides writes, for each dist2side call of the point's
-// case (at most 4, in the reference's order), the spherical angle (acosl as the reference's x87 build rounds it) and the
-// cosine normalize_great_circle_distance hands to acos; the host then evaluates asin(sin(acos(cos)) * sin(angle)) with its own
-// libm (bilinear_host.c: fg_bilin_dist2side_tail), and k_bl_weight_final combines the distances.  Unused slots: angle 0, cos 1.
-__device__ __forceinline__ void bl_side(const double *v1, const double *v2, const double *point, double *angle, double *cs)
+// case (at most 4, in the reference's order), the spherical angle, the argument spherical_angle hands to acosl (NaN where
+// the angle comes from another branch) and the cosine normalize_great_circle_distance hands to acos; the host then takes
+// acosl of the argument and evaluates asin(sin(acos(cos)) * sin(angle)) with its own libm (bilinear_host.c:
+// fg_bilin_dist2side_tail), and k_bl_weight_final combines the distances.  Unused slots: angle 0, argument NaN, cos 1.
+// fg_acosl rounds correctly; the reference rounds x87 acosl's long double to double, which differs in the last place at a
+// few arguments, so the weights take acosl from the host like the other libm calls.
+__device__ __forceinline__ void bl_side(const double *v1, const double *v2, const double *point, double *angle, double *arg,
+                                        double *cs)
 {
-  *angle = bl_angle<true>(v1, v2, point);
+  *angle = bl_angle<true>(v1, v2, point, arg);
   *cs = bl_gcd_cos(v1, point);
 }
 
-__global__ __launch_bounds__(256) void k_bl_weight_sides(BlGeom g, long npts, const int *index, double *angle, double *side_cos)
+__global__ __launch_bounds__(256) void k_bl_weight_sides(BlGeom g, long npts, const int *index, double *angle, double *acos_arg,
+                                                         double *side_cos)
 {
   const long n0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (n0 >= npts) return;
@@ -322,23 +332,24 @@ __global__ __launch_bounds__(256) void k_bl_weight_sides(BlGeom g, long npts, co
   const int ic = index[3 * n0], jc = index[3 * n0 + 1], l = index[3 * n0 + 2];
   const long off = (long)l * nxd * nxd;
   const double v0[3] = {g.xo[n0], g.yo[n0], g.zo[n0]};
-  double v1[3], v2[3], v3[3], v4[3], a[4] = {0., 0., 0., 0.}, c[4] = {1., 1., 1., 1.};
+  const double nan = __builtin_nan("");
+  double v1[3], v2[3], v3[3], v4[3], a[4] = {0., 0., 0., 0.}, x[4] = {nan, nan, nan, nan}, c[4] = {1., 1., 1., 1.};
   if (ic == N && jc == N) {
     bl_ld(g, off, jc * nxd + ic, v1); bl_ld(g, off, jc * nxd + ic + 1, v2); bl_ld(g, off, (jc + 1) * nxd + ic, v3);
-    bl_side(v2, v3, v0, &a[0], &c[0]); bl_side(v2, v1, v0, &a[1], &c[1]); bl_side(v1, v3, v0, &a[2], &c[2]);
+    bl_side(v2, v3, v0, &a[0], &x[0], &c[0]); bl_side(v2, v1, v0, &a[1], &x[1], &c[1]); bl_side(v1, v3, v0, &a[2], &x[2], &c[2]);
   } else if (ic == 0 && jc == N) {
     bl_ld(g, off, jc * nxd + ic, v1); bl_ld(g, off, jc * nxd + ic + 1, v2); bl_ld(g, off, (jc + 1) * nxd + ic + 1, v3);
-    bl_side(v3, v2, v0, &a[0], &c[0]); bl_side(v2, v1, v0, &a[1], &c[1]); bl_side(v3, v1, v0, &a[2], &c[2]);
+    bl_side(v3, v2, v0, &a[0], &x[0], &c[0]); bl_side(v2, v1, v0, &a[1], &x[1], &c[1]); bl_side(v3, v1, v0, &a[2], &x[2], &c[2]);
   } else if (jc == 0 && ic == N) {
     bl_ld(g, off, jc * nxd + ic, v1); bl_ld(g, off, (jc + 1) * nxd + ic, v2); bl_ld(g, off, (jc + 1) * nxd + ic + 1, v3);
-    bl_side(v2, v3, v0, &a[0], &c[0]); bl_side(v1, v3, v0, &a[1], &c[1]); bl_side(v1, v2, v0, &a[2], &c[2]);
+    bl_side(v2, v3, v0, &a[0], &x[0], &c[0]); bl_side(v1, v3, v0, &a[1], &x[1], &c[1]); bl_side(v1, v2, v0, &a[2], &x[2], &c[2]);
   } else {
     bl_ld(g, off, jc * nxd + ic, v1); bl_ld(g, off, jc * nxd + ic + 1, v2);
     bl_ld(g, off, (jc + 1) * nxd + ic, v3); bl_ld(g, off, (jc + 1) * nxd + ic + 1, v4);
-    bl_side(v1, v3, v0, &a[0], &c[0]); bl_side(v3, v4, v0, &a[1], &c[1]); bl_side(v4, v2, v0, &a[2], &c[2]);
-    bl_side(v2, v1, v0, &a[3], &c[3]);
+    bl_side(v1, v3, v0, &a[0], &x[0], &c[0]); bl_side(v3, v4, v0, &a[1], &x[1], &c[1]); bl_side(v4, v2, v0, &a[2], &x[2], &c[2]);
+    bl_side(v2, v1, v0, &a[3], &x[3], &c[3]);
   }
-  for (int k = 0; k < 4; k++) { angle[4 * n0 + k] = a[k]; side_cos[4 * n0 + k] = c[k]; }
+  for (int k = 0; k < 4; k++) { angle[4 * n0 + k] = a[k]; acos_arg[4 * n0 + k] = x[k]; side_cos[4 * n0 + k] = c[k]; }
 }
 
 __global__ __launch_bounds__(256) void k_bl_weight_final(long npts, int N, const int *index, const double *dist, double *weight)
@@ -515,10 +526,10 @@ void fgd_bl_search_iter(const BlGeom &g, int iter, double dlon, double dlat, dou
 
 long fgd_bl_scan_blocks(long ncell) { return (ncell + BL_SCAN_B * BL_SCAN_E - 1) / (BL_SCAN_B * BL_SCAN_E); }
 
-void fgd_bl_weight_sides(const BlGeom &g, const int *index, double *angle, double *side_cos, hipStream_t st)
+void fgd_bl_weight_sides(const BlGeom &g, const int *index, double *angle, double *acos_arg, double *side_cos, hipStream_t st)
 {
   const long npts = (long)g.nxo * g.nyo;
-  k_bl_weight_sides<<<bl_nblk(npts, 256), 256, 0, st>>>(g, npts, index, angle, side_cos);
+  k_bl_weight_sides<<<bl_nblk(npts, 256), 256, 0, st>>>(g, npts, index, angle, acos_arg, side_cos);
 }
 
 void fgd_bl_weight_final(long npts, int N, const int *index, const double *dist, double *weight, hipStream_t st)

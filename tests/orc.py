@@ -5,10 +5,13 @@
   present in the build container and -- as a prebuilt .so -- on the GPU box.
 * ``oracle/_ref/libconserve_ref.so`` the reference's own conserve_interp.c (setup_conserve_interp,
   do_scalar_conserve_interp) behind oracle/conserve_ref_adapter.c, built the same way.
+* ``oracle/_ref/libbilinear_ref.so`` the reference's own bilinear_interp.c (setup_bilinear_interp,
+  do_scalar_bilinear_interp, do_vector_bilinear_interp) behind oracle/bilinear_ref_adapter.c, built the same way.
 """
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -34,6 +37,7 @@ def f64(a):
 _ORACLE = None
 _REF = None
 _CREF = None
+_BREF = None
 
 
 def oracle():
@@ -529,6 +533,179 @@ def cref_apply(order, x, nx_in, ny_in, data, grad_x, grad_y, grad_mask, has_miss
     return (outs if multi else outs[0]), printed
 
 
+# ------------------------------------------------------------------------------ the reference's bilinear_interp.c
+BILINEAR_REF_PATH = os.path.join(ORACLE_DIR, "_ref", "libbilinear_ref.so")
+_BREF_GRID = [C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_double] * 4     # N, halo'd centres, target
+
+
+def bilinear_ref_available():
+    return os.path.exists(BILINEAR_REF_PATH)
+
+
+def bref():
+    """oracle/_ref/libbilinear_ref.so (None if it has not been built)."""
+    global _BREF
+    if _BREF is None:
+        if not bilinear_ref_available():
+            return None
+        L = C.CDLL(BILINEAR_REF_PATH)
+        L.bref_init.argtypes = [C.c_int]
+        L.bref_init.restype = None
+        L.bref_setup.argtypes = _BREF_GRID + [ip] + [dp] * 7
+        L.bref_setup.restype = C.c_int
+        target = [C.c_int] * 4 + [ip, dp, dp]
+        L.bref_apply_scalar.argtypes = target + [dp, C.c_int, C.c_double, C.c_int, dp]
+        L.bref_apply_scalar.restype = C.c_int
+        L.bref_apply_vector.argtypes = target + [dp] * 6 + [C.c_int, C.c_double, C.c_int, dp, dp]
+        L.bref_apply_vector.restype = C.c_int
+        L.bref_unit_vect_latlon.argtypes = [C.c_int, dp, dp, dp, dp]
+        L.bref_unit_vect_latlon.restype = None
+        L.bref_cell_dist.argtypes = [C.c_int, dp, dp, dp]
+        L.bref_cell_dist.restype = None
+        L.bref_max_weight_index.argtypes = [C.c_long, dp, ip]
+        L.bref_max_weight_index.restype = None
+        L.normalize_great_circle_distance.argtypes = [dp, dp]
+        L.normalize_great_circle_distance.restype = C.c_double
+        L.max_weight_index.argtypes = [dp, C.c_int]
+        L.max_weight_index.restype = C.c_int
+        L.do_latlon_coarsening.argtypes = [dp, dp, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_double]
+        L.do_latlon_coarsening.restype = None
+        _BREF = L
+    return _BREF
+
+
+def _bref_grid(cfg, lont_h, latt_h):
+    """cfg: dict(N, nlon, nlat, finer_step=0, center_y=False, lonbegin=0, lonend=360, latbegin=-90, latend=90)"""
+    N = int(cfg["N"])
+    lh, ah = f64(lont_h).reshape(-1), f64(latt_h).reshape(-1)
+    assert lh.size == ah.size == 6 * (N + 2) ** 2
+    args = [N, _dp(lh), _dp(ah), int(cfg["nlon"]), int(cfg["nlat"]), int(cfg.get("finer_step", 0)),
+            1 if cfg.get("center_y", False) else 0, float(cfg.get("lonbegin", 0.0)), float(cfg.get("lonend", 360.0)),
+            float(cfg.get("latbegin", -90.0)), float(cfg.get("latend", 90.0))]
+    fs = int(cfg.get("finer_step", 0))
+    nyf, nxf = (2 ** fs) * (int(cfg["nlat"]) - 1) + 1, (2 ** fs) * int(cfg["nlon"])
+    return args, (lh, ah), nxf, nyf
+
+
+def bref_setup(cfg, lont_h, latt_h):
+    """The reference's setup_bilinear_interp (compute branch) in this process.  lont_h / latt_h: halo'd centres [6, N+2, N+2]
+    (radians).  Returns index [n, 3], weight [n, 4] and the fine grid its caller built: lont, latt [n], latt1d [ny_fine],
+    xyz [3, n], vlon, vlat [n, 3].  Only for targets whose ten sweeps are known to find every point: otherwise see
+    bref_setup_child."""
+    L = bref()
+    args, keep, nxf, nyf = _bref_grid(cfg, lont_h, latt_h)
+    n = nxf * nyf
+    out = dict(index=np.empty((n, 3), dtype=np.int32), weight=np.empty((n, 4)), lont=np.empty(n), latt=np.empty(n),
+               latt1d=np.empty(nyf), xyz=np.empty((3, n)), vlon=np.empty((n, 3)), vlat=np.empty((n, 3)))
+    L.bref_setup(*args, _ip(out["index"]), *[_dp(out[k]) for k in ("weight", "lont", "latt", "latt1d", "xyz", "vlon", "vlat")])
+    return out
+
+
+def bref_setup_child(cfg, lont_h, latt_h, workdir, timeout=600):
+    """bref_setup in a child process (its stdout line-buffered).  The reference starts its "global sweep" (bilinear_interp.c:
+    213-259, which reads past its arrays) when the ten sweeps leave a point unfound; the child is stopped at its warning.
+    Returns (result or None, printed text, fell_back).  The child loads only oracle/_ref and numpy."""
+    inp, outp = os.path.join(workdir, "bref_in.npz"), os.path.join(workdir, "bref_out.npz")
+    np.savez(inp, lont_h=f64(lont_h), latt_h=f64(latt_h), cfg=np.array(repr(dict(cfg))))
+    if os.path.exists(outp):
+        os.remove(outp)
+    p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "bref_setup", inp, outp], stdout=subprocess.PIPE,
+                         stderr=subprocess.STDOUT, text=True, cwd=workdir)
+    lines, fell_back = [], False
+    try:
+        for line in p.stdout:
+            lines.append(line)
+            if "global sweep" in line:
+                fell_back = True
+                p.kill()
+                break
+        p.wait(timeout=timeout)
+    finally:
+        if p.poll() is None:
+            p.kill()
+            p.wait()
+        p.stdout.close()
+    printed = "".join(lines)
+    if fell_back:
+        return None, printed, True
+    if p.returncode != 0:
+        raise RuntimeError(f"reference setup child exited with {p.returncode}: {printed[-2000:]}")
+    d = np.load(outp)
+    return {k: d[k] for k in d.files}, printed, False
+
+
+def _bref_setup_main(inp, outp):
+    import ast
+    d = np.load(inp)
+    bref().bref_init(1)
+    out = bref_setup(ast.literal_eval(str(d["cfg"])), d["lont_h"], d["latt_h"])
+    np.savez(outp, **out)
+
+
+def bref_unit_vect_latlon(lon, lat):
+    """the reference's unit_vect_latlon: vlon, vlat [..., 3]"""
+    lon, lat = f64(lon).reshape(-1), f64(lat).reshape(-1)
+    vlo, vla = np.empty((lon.size, 3)), np.empty((lon.size, 3))
+    bref().bref_unit_vect_latlon(lon.size, _dp(lon), _dp(lat), _dp(vlo), _dp(vla))
+    return vlo, vla
+
+
+def _bref_target(cfg, setup):
+    fs = int(cfg.get("finer_step", 0))
+    idx, w = np.ascontiguousarray(setup["index"], dtype=np.int32), f64(setup["weight"])
+    nyf, nxf = (2 ** fs) * (int(cfg["nlat"]) - 1) + 1, (2 ** fs) * int(cfg["nlon"])
+    assert idx.size == 3 * nxf * nyf and w.size == 4 * nxf * nyf and setup["latt1d"].size == nyf
+    return [int(cfg["N"]), int(cfg["nlon"]), int(cfg["nlat"]), fs, _ip(idx), _dp(w), _dp(f64(setup["latt1d"]))], (idx, w)
+
+
+def bref_apply_scalar(cfg, setup, data_h, has_missing=False, missing=0.0, fill_missing=False):
+    """do_scalar_bilinear_interp, one level as fregrid calls it, with the plan of `setup` (bref_setup's dict or one with the
+    same index / weight / latt1d): data_h [6, N+2, N+2] halo'd -> [nlat, nlon]"""
+    args, keep = _bref_target(cfg, setup)
+    d = f64(data_h)
+    assert d.size == 6 * (int(cfg["N"]) + 2) ** 2
+    out = np.empty((int(cfg["nlat"]), int(cfg["nlon"])))
+    bref().bref_apply_scalar(*args, _dp(d), 1 if has_missing else 0, float(missing), 1 if fill_missing else 0, _dp(out))
+    return out
+
+
+def bref_apply_vector(cfg, setup, vlon_in, vlat_in, u_h, v_h, has_missing=False, missing=0.0, fill_missing=False):
+    """do_vector_bilinear_interp, one level: u_h, v_h [6, N+2, N+2] halo'd -> (u_out, v_out) [nlat, nlon].  vlon_in / vlat_in:
+    bref_unit_vect_latlon of the halo'd centres; the fine grid's vlon / vlat come from `setup`."""
+    args, keep = _bref_target(cfg, setup)
+    u, v, vi, wi = f64(u_h), f64(v_h), f64(vlon_in), f64(vlat_in)
+    vo, wo = f64(setup["vlon"]), f64(setup["vlat"])
+    F = 6 * (int(cfg["N"]) + 2) ** 2
+    assert u.size == v.size == F and vi.size == wi.size == 3 * F and vo.size == 3 * len(keep[0])
+    uo, vo_ = np.empty((int(cfg["nlat"]), int(cfg["nlon"]))), np.empty((int(cfg["nlat"]), int(cfg["nlon"])))
+    bref().bref_apply_vector(*args, _dp(vi), _dp(wi), _dp(vo), _dp(wo), _dp(u), _dp(v), 1 if has_missing else 0, float(missing),
+                             1 if fill_missing else 0, _dp(uo), _dp(vo_))
+    return uo, vo_
+
+
+def bref_cell_dist(N, lont_h, latt_h):
+    """normalize_great_circle_distance of each cell's centres (jc, ic) -> (jc+1, ic+1), [6*N*N] in the device's cell order"""
+    lh, ah = f64(lont_h).reshape(-1), f64(latt_h).reshape(-1)
+    out = np.empty(6 * N * N)
+    bref().bref_cell_dist(N, _dp(lh), _dp(ah), _dp(out))
+    return out
+
+
+def bref_max_weight_index(weight):
+    w = f64(weight).reshape(-1, 4)
+    out = np.empty(len(w), dtype=np.int32)
+    bref().bref_max_weight_index(len(w), _dp(w), _ip(out))
+    return out
+
+
+def bref_latlon_coarsening(var, ylat, nlon, nlat, finer_step, has_missing=False, missing=0.0):
+    """do_latlon_coarsening of one level: var [nlat, nlon] fine -> [(nlat-1)/2**fs+1, nlon/2**fs]"""
+    v, y = f64(var).reshape(-1), f64(ylat)
+    out = np.empty(((nlat - 1) // 2 ** finer_step + 1) * (nlon // 2 ** finer_step))
+    bref().do_latlon_coarsening(_dp(v), _dp(y), nlon, nlat, 1, _dp(out), finer_step, 1 if has_missing else 0, float(missing))
+    return out.reshape((nlat - 1) // 2 ** finer_step + 1, nlon // 2 ** finer_step)
+
+
 def host_has_fma():
     """libm's sin()/cos() run their FMA build on an FMA-capable x86-64 host; the device trig emulates that build, so the
     bit-identity assertions of the legacy path hold where the oracle runs on such a host (every box of the GPU pool so far).
@@ -537,3 +714,10 @@ def host_has_fma():
         return " fma " in open("/proc/cpuinfo").read()
     except OSError:
         return True
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "bref_setup":
+        _bref_setup_main(sys.argv[2], sys.argv[3])
+    else:
+        sys.exit(f"usage: {sys.argv[0]} bref_setup IN.npz OUT.npz")

@@ -55,7 +55,7 @@ def close_fields(a, b, missing):
     scale = np.max(np.abs(b[ok])) if ok.any() else 1.0
     assert np.max(np.abs(a[ok] - b[ok])) <= 1e-14 * scale, np.max(np.abs(a[ok] - b[ok]))
     frac = float(np.mean(a.view(np.int64) == b.view(np.int64)))
-    assert frac >= 0.999, frac                  # only points whose weights carry an fg_acosl last-place rounding differ
+    assert frac >= 0.999, frac                  # only points whose weights differ in the last place differ
     return frac
 
 
@@ -67,7 +67,7 @@ def test_index_weights_and_fields_match_reference(fg, path):
         index, weight = p.index_weight()
         assert np.array_equal(index, d["index"])                       # every point, every case
         ties = p.ambiguous_ties
-        # acos / sin / asin come from the host libm as in the reference; what remains is fg_acosl's rare last-place rounding
+        # acosl / acos / sin / asin come from the host libm as in the reference; what remains is a rare last-place rounding
         u = ulps(weight, d["weight"])
         assert u.max() <= 2, u.max()
         frac_w = float(np.mean(u == 0))
