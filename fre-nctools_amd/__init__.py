@@ -11,6 +11,9 @@ mirrors the reference's call signatures:
   -- tools/fregrid/conserve_interp.c:42,507 (compute / READ / WRITE branches; every branch of the sweep: missing values,
      weight field, cell_methods = sum, cell_measures, --target_grid, the monotone limiter)
 
+* ``do_extrapolate`` / ``setup_vertical_interp`` / ``do_vertical_interp``
+  -- tools/fregrid/fregrid_util.c:2662,756,789 (--extrapolate fill of a lat-lon source, --dst_vgrid levels)
+
 There is NO CPU fallback: if the shared library is missing, or no HIP device is visible
 when a compute entry point is called, an exception is raised.
 """
@@ -29,6 +32,8 @@ from . import field_io  # noqa: F401
 from .coupler import coupler_xgrid  # noqa: F401
 from .bilinear import (BilinearPlan, setup_bilinear_interp, do_scalar_bilinear_interp, do_vector_bilinear_interp,  # noqa: F401
                        write_bilinear_remap_file, read_bilinear_remap_file)
+from .extrapolate import (Extrapolator, do_extrapolate, setup_vertical_interp, do_vertical_interp,  # noqa: F401
+                          set_extrap_batch, set_extrap_coef, extrap_coef_host)
 from .parallel import (band_rows, row_cost, allreduce_cell_sums, allreduce_scalar_sum, allreduce_minmax,  # noqa: F401
                        boundary_source_cells, allreduce_cell_sums_sparse, ordered_cell_sums, CellSumExchange)
 from .conserve_interp import (  # noqa: F401
@@ -44,6 +49,7 @@ __all__ = [
     "gnomonic_ed_corners", "latlon_corners", "lib", "lib_path", "FregridHipError",
     "BilinearPlan", "setup_bilinear_interp", "do_scalar_bilinear_interp", "do_vector_bilinear_interp",
     "write_bilinear_remap_file", "read_bilinear_remap_file",
+    "Extrapolator", "do_extrapolate", "setup_vertical_interp", "do_vertical_interp",
 ]
 
 

@@ -51,6 +51,9 @@ EXPORTS = [
     "fg_bilin_nlon_fine", "fg_bilin_nlat_fine", "fg_bilin_nlon", "fg_bilin_nlat", "fg_bilin_ncells", "fg_bilin_set_stream",
     "fg_bilin_sync", "fg_bilin_apply_scalar", "fg_bilin_apply_vector", "fg_bilin_remap_write", "fg_bilin_remap_read",
     "fg_unit_vect_latlon", "fg_bilin_fine_grid", "fg_bilin_ambiguous_ties",
+    "fg_extrap_create", "fg_extrap_destroy", "fg_extrap_set_stream", "fg_extrap_stream", "fg_extrap_run_dev", "fg_extrap_run",
+    "fg_extrap_last_syncs", "fg_extrap_get_coef", "fg_extrap_coef_host", "fg_set_extrap_batch", "fg_set_extrap_coef",
+    "fg_setup_vertical_interp", "fg_dev_vertical_interp",
 ]
 
 
@@ -335,6 +338,32 @@ def lib():
     L.fg_gnomonic_ed_corners.restype = C.c_int
     L.fg_latlon_corners.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp]
     L.fg_latlon_corners.restype = C.c_int
+    L.fg_extrap_create.argtypes = [C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.fg_extrap_create.restype = C.c_int
+    L.fg_extrap_destroy.argtypes = [vp]
+    L.fg_extrap_destroy.restype = None
+    L.fg_extrap_set_stream.argtypes = [vp, vp]
+    L.fg_extrap_set_stream.restype = C.c_int
+    L.fg_extrap_stream.argtypes = [vp]
+    L.fg_extrap_stream.restype = vp
+    L.fg_extrap_run_dev.argtypes = [vp, vp, vp, C.c_int, C.c_long, C.c_double, C.c_double, ip, dp]
+    L.fg_extrap_run_dev.restype = C.c_int
+    L.fg_extrap_run.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.c_double, ip, dp]
+    L.fg_extrap_run.restype = C.c_int
+    L.fg_extrap_last_syncs.argtypes = [vp]
+    L.fg_extrap_last_syncs.restype = C.c_long
+    L.fg_extrap_get_coef.argtypes = [vp, dp, dp, dp, dp]
+    L.fg_extrap_get_coef.restype = C.c_int
+    L.fg_extrap_coef_host.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, dp, dp]
+    L.fg_extrap_coef_host.restype = C.c_int
+    L.fg_set_extrap_batch.argtypes = [C.c_int]
+    L.fg_set_extrap_batch.restype = None
+    L.fg_set_extrap_coef.argtypes = [C.c_int]
+    L.fg_set_extrap_coef.restype = None
+    L.fg_setup_vertical_interp.argtypes = [C.c_int, dp, C.c_int, dp, ip, ip, ip]
+    L.fg_setup_vertical_interp.restype = C.c_int
+    L.fg_dev_vertical_interp.argtypes = [C.c_long, C.c_int, dp, C.c_int, dp, vp, vp]
+    L.fg_dev_vertical_interp.restype = C.c_int
     _LIB = L
     return L
 

@@ -59,7 +59,7 @@ extern "C" {
 #define FG_ERR_IO         (-9)   /* file I/O (fg_nc_*, fg_remap_*)                            */
 #define FG_ERR_NOTFOUND   (-10)  /* attribute / variable not present                          */
 #define FG_ERR_BILIN_NOTFOUND (-11) /* bilinear search: points without a lower-left corner after 10 sweeps (fg_bilin_create) */
-#define FG_ERR_DATA       (-7)   /* the field data hit one of the reference's fatal checks (conserve_interp.c:584,:697,:709) */
+#define FG_ERR_DATA       (-7)   /* the field data hit one of the reference's fatal checks (conserve_interp.c:584,:697,:709; interp.c:366-374) */
 
 /* option bits, same values as tools/libfrencutils/globals.h:46-61 where they exist */
 #define FG_CONSERVE_ORDER1 1
@@ -675,6 +675,48 @@ int  fg_bilin_remap_read(const char *path, int nlon_fine, int nlat_fine, int *in
 void fg_unit_vect_latlon(long size, const double *lon, const double *lat, double *vlon, double *vlat);
 void fg_bilin_fine_grid(int nlon, int nlat, int finer_step, double lonbegin, double lonend, double latbegin, double latend,
                         int center_y, double *lont, double *latt, double *latt1d);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * fregrid --extrapolate and --dst_vgrid (the ocean initial-condition recipe: lat-lon climatology -> tripolar):
+ * do_extrapolate (tools/fregrid/fregrid_util.c:2662-2812) fills the missing points (land) of a lat-lon source field before the
+ * remap -- a relaxed Jacobi iteration of a spherical 5-point Laplacian, per level until the largest residual is <= stop_crit
+ * or 4000 iterations have run; setup_vertical_interp / do_vertical_interp (:756-819, linear_vertical_interp interp.c:360-396)
+ * put the remapped levels onto the --dst_vgrid levels.  Both on the device, bit for bit the reference's arithmetic.
+ *
+ * fg_extrap_create: the grid factors of one source grid (:2676-2720); lon[ni], lat[nj] the T-cell axes in radians (host),
+ * grid_in[].lont1D / latt1D.  The cosines are evaluated with the operation sequence of the reference's build host's libm, on
+ * the host, whatever libm this host has.  One handle serves every field and tile on that grid; it owns a non-blocking stream.
+ * fg_extrap_run_dev: d_in, d_out [nk] levels of [nj][ni], level k at k * level_stride doubles (0 = ni*nj), device pointers; d_out may
+ * equal d_in.  A point is missing where fabs(v - missing) <= 1e-10.  Missing points of level 0 start from 0, those of level k
+ * from the solution of level k-1 (the reference's warm start: the levels are sequential).  iters_out[nk] (host, may be NULL)
+ * receives the 0-based iteration the level stopped after -- the number the reference prints -- and resmax_out[nk] its largest
+ * residual.  Iterations are queued in batches with no host synchronisation inside a batch (one per batch: ceil((iters+1)/batch)
+ * per level); the call returns when d_out is complete.  fg_extrap_run: the same on host arrays [nk][nj][ni]. */
+typedef struct fg_extrap fg_extrap;
+int  fg_extrap_create(int ni, int nj, const double *lon, const double *lat, int is_cyclic, int device, fg_extrap **out);
+void fg_extrap_destroy(fg_extrap *h);
+int  fg_extrap_set_stream(fg_extrap *h, void *stream);      /* queue on the caller's hipStream_t instead */
+void *fg_extrap_stream(fg_extrap *h);
+int  fg_extrap_run_dev(fg_extrap *h, const double *d_in, double *d_out, int nk, long level_stride, double missing,
+                       double stop_crit, int *iters_out, double *resmax_out);
+int  fg_extrap_run(fg_extrap *h, const double *in, double *out, int nk, double missing, double stop_crit,
+                   int *iters_out, double *resmax_out);
+long fg_extrap_last_syncs(const fg_extrap *h);              /* host synchronisations of the last run's iteration loops */
+/* the four coefficient arrays [nj*ni] (host) as the handle uses them / without a handle or a device (cfw, cfe, cfs, cfn of :2710-2718) */
+int  fg_extrap_get_coef(fg_extrap *h, double *cfw, double *cfe, double *cfs, double *cfn);
+int  fg_extrap_coef_host(int ni, int nj, const double *lon, const double *lat, double *cfw, double *cfe, double *cfs, double *cfn);
+/* Test / tuning hooks; results never depend on them.  batch: iterations queued per host synchronisation (default 64, < 1 = default).
+ * coef: 0 (default) the kernel forms the four coefficients of a cell from three row and two column factors on every use,
+ * 1 it reads them from a stored [nj*ni][4] table. */
+void fg_set_extrap_batch(int n);
+void fg_set_extrap_coef(int stored);
+/* setup_vertical_interp: kstart, kend, need_interp of (z1[nk1] source levels, z2[nk2] destination levels); host only. */
+int  fg_setup_vertical_interp(int nk1, const double *z1, int nk2, const double *z2, int *kstart, int *kend, int *need_interp);
+/* do_vertical_interp of a field with a z axis: d_in [nk1][nxy] -> d_out [nk2][nxy] (device, different arrays; z1, z2 host).
+ * Levels above z1[0] take the shallowest source level, levels below z1[nk1-1] the deepest, the others
+ * (1.-w)*upper + w*lower.  need_interp == 0: d_out = d_in.  The reference's fatal checks ("grid1 not monotonic",
+ * "grid2 lies outside grid1", ...) return FG_ERR_DATA with its message.  Synchronous. */
+int  fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int nk2, const double *z2, const double *d_in, double *d_out);
 
 #ifdef __cplusplus
 }

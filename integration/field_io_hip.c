@@ -14,8 +14,11 @@
  *
  * Building it into fregrid without touching the reference's sources: compile fregrid_util.c with
  *     -Dget_input_data=get_input_data_cpu -Dwrite_field_data=write_field_data_cpu
- * and this file with -DFG_HAVE_CPU_FIELD_IO; the cases this file does not serve (--extrapolate, ranks > 1 on the write side, a
- * grid with a halo of its own) are passed to those.  Without that macro they are fatal errors (the test harness).
+ * and this file with -DFG_HAVE_CPU_FIELD_IO; the cases this file does not serve (non-conservative methods, ranks > 1 on the write
+ * side, a grid with a halo of its own) are passed to those.  Without that macro they are fatal errors (the test harness).
+ * --extrapolate with a conservative method is served here: do_extrapolate (:2126-2136) runs on the device copy of each tile's
+ * levels (fg_extrap_run_dev).  That branch is type-checked against the reference's headers but no driver executes it from C yet;
+ * the same library calls are tested bit for bit against the reference through Python (tests/test_gpu_extrapolate.py).
  *
  * The host arrays of Field_config are still malloc'ed -- fregrid.c frees them after every level (:1067-1075) -- but the
  * input arrays are NOT filled (zeros): the data lives on the device.  do_scalar_conserve_interp's CHECK_CONSERVE branch
@@ -137,6 +140,23 @@ static fg_c2l *c2l_for(int ntiles, const Grid_config *grid, int dev)
   return g_c2l;
 }
 
+/* ------------------------------------------------------------------------------------------ extrapolation handles */
+/* one fg_extrap per source tile: the grid factors depend on the tile's lont1D / latt1D / is_cyclic only */
+typedef struct { const Grid_config *key; fg_extrap *h; } ExSlot;
+static ExSlot *g_ex = NULL; static int g_nex = 0;
+
+static fg_extrap *extrap_for(const Grid_config *grid, int dev)
+{
+  int k;
+  for (k = 0; k < g_nex; k++) if (g_ex[k].key == grid) return g_ex[k].h;
+  if (!grid->lont1D || !grid->latt1D) mpp_error("field_io(hip): --extrapolate needs a lat-lon source grid (grid_in[].lont1D / latt1D)");
+  g_ex = (ExSlot *)realloc(g_ex, (size_t)(g_nex + 1) * sizeof(ExSlot));
+  if (!g_ex) mpp_error("field_io(hip): out of memory");
+  g_ex[g_nex].key = grid; g_ex[g_nex].h = NULL;
+  if (fg_extrap_create(grid->nx, grid->ny, grid->lont1D, grid->latt1D, grid->is_cyclic, dev, &g_ex[g_nex].h)) io_fatal("get_input_data");
+  return g_ex[g_nex++].h;
+}
+
 /* ------------------------------------------------------------------------------------------ get_input_data */
 void get_input_data(int ntiles, Field_config *field, Grid_config *grid, Bound_config *bound,
                     int varid, int level_z, int level_n, int level_t, int extrapolate, double stop_crit)
@@ -153,13 +173,13 @@ void get_input_data(int ntiles, Field_config *field, Grid_config *grid, Bound_co
   size_t start[8], nread[8], ncell = 0, fstride = 0, off;
   char *raw, *d_raw;
   FgDevField *slot;
-  (void)bound; (void)stop_crit;
-  if (extrapolate || (interp_method != CONSERVE_ORDER1 && interp_method != CONSERVE_ORDER2)) {
+  (void)bound;
+  if ((interp_method != CONSERVE_ORDER1 && interp_method != CONSERVE_ORDER2)) {
 #ifdef FG_HAVE_CPU_FIELD_IO
     get_input_data_cpu(ntiles, field, grid, bound, varid, level_z, level_n, level_t, extrapolate, stop_crit);
     return;
 #else
-    mpp_error("field_io(hip): --extrapolate and non-conservative methods are served by the reference's get_input_data");
+    mpp_error("field_io(hip): non-conservative methods are served by the reference's get_input_data");
 #endif
   }
   if (!ftype) mpp_error("fregrid_util(get_input_data): field type should be NC_INT, NC_SHORT, NC_FLOAT or NC_DOUBLE");
@@ -220,6 +240,23 @@ void get_input_data(int ntiles, Field_config *field, Grid_config *grid, Bound_co
     if (fg_dev_widen(uptype, (long)(ncell * (size_t)nz), d_raw, field->var[varid].scale, field->var[varid].offset, missing_value, d_src))
       io_fatal("get_input_data");
     fg_dev_free(d_raw);
+    if (extrapolate) {
+      /* do_extrapolate on each tile's levels, in place (:2126-2136): level k of tile n lies at d_src + k*ncell + offset(n) */
+      int *iters = (int *)malloc((size_t)nz * sizeof(int));
+      double *resmax = (double *)malloc((size_t)nz * sizeof(double));
+      int k;
+      if (!iters || !resmax) mpp_error("field_io(hip): out of memory");
+      off = 0;
+      for (n = 0; n < ntiles; n++) {
+        if (fg_extrap_run_dev(extrap_for(&grid[n], dev), d_src + off, d_src + off, nz, (long)ncell, field[n].var[varid].missing,
+                              stop_crit, iters, resmax)) io_fatal("get_input_data");
+        if (mpp_pe() == mpp_root_pe())
+          for (k = 0; k < nz; k++) printf("Stopped after %d iterations, maxres = %g\n", iters[k], resmax[k]);
+        field[n].var[varid].has_missing = 0;
+        off += (size_t)grid[n].nx * grid[n].ny;
+      }
+      free(iters); free(resmax);
+    }
     if (!halo) slot->d_data = d_src;
     else {
       fg_c2l *c2l = c2l_for(ntiles, grid, dev);
