@@ -275,7 +275,9 @@ int fg_halo_map(int ntiles, const int *nx, const int *ny, int ncontacts, const i
   }
   for (int l = 0; l < n2; l++) {
     dir[l] = side_dir(is[l], ie[l], js[l], je[l]);
-    if (dir[l] < 0 || tile[l] < 0 || tile[l] >= ntiles) rc = FG_ERR_ARG;
+    if (dir[l] < 0 || tile[l] < 0 || tile[l] >= ntiles) { rc = FG_ERR_ARG; continue; }
+    /* model indices of a contact lie inside its own tile */
+    if (imin(is[l], ie[l]) < 0 || imax(is[l], ie[l]) > nx[tile[l]] - 1 || imin(js[l], je[l]) < 0 || imax(js[l], je[l]) > ny[tile[l]] - 1) rc = FG_ERR_ARG;
   }
   for (int l = 0; l < n2 && !rc; l++) {
     int n = tile[l], l2 = (l + ncontacts) % n2, m = tile[l2];
@@ -299,9 +301,18 @@ int fg_halo_map(int ntiles, const int *nx, const int *ny, int ncontacts, const i
     if (dir[l] == D_SOUTH && dir[l2] == D_EAST) rotate = -90;
     if (dir[l] == D_NORTH && dir[l2] == D_WEST) rotate = -90;
     if (dir[l] == D_NORTH && dir[l2] == D_NORTH) rotate = 180;
+    /* The reference never checks a strip against the array it indexes, and it places the neighbour's east / north strip
+     * with tile n's size: between tiles of different sizes it reads the wrong column or leaves the array.  Such a mosaic
+     * is refused: the halo strip must lie in tile n's halo'd array, the source strip in tile m's interior, and an east /
+     * north source edge needs nx[m] == nx[n] / ny[m] == ny[n].  Every map entry is then -1 or in [0, map_off[ntiles]),
+     * and every entry written belongs to tile n. */
+    const int nxm = nx[m], nym = ny[m];
+    if (is1 < 0 || ie1 > nxn + 2 * halo - 1 || js1 < 0 || je1 > nyn + 2 * halo - 1 ||
+        is2 < halo || ie2 > nxm + halo - 1 || js2 < halo || je2 > nym + halo - 1 ||
+        (dir[l2] == D_EAST && nxm != nxn) || (dir[l2] == D_NORTH && nym != nyn)) { rc = FG_ERR_ARG; break; }
     int cnt1 = (ie1 - is1 + 1) * (je1 - js1 + 1), cnt2 = (ie2 - is2 + 1) * (je2 - js2 + 1);
     if (cnt1 != cnt2) { rc = FG_ERR_ARG; break; }       /* "size mismatch between the boundary" */
-    int nx2 = nx[m] + 2;
+    int nx2 = nxm + 2;
     int *buf = (int *)malloc(cnt2 * sizeof(int));
     int q = 0;
     if (rotate == 0)        { for (int j = js2; j <= je2; j++) for (int i = is2; i <= ie2; i++) buf[q++] = j * nx2 + i; }

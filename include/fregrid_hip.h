@@ -390,7 +390,10 @@ typedef struct fg_c2l fg_c2l;
 /* Host, once per mosaic.  lonc/latc: corners [(ny+1)][(nx+1)], lont/latt: T-cell centres [ny][nx] (radians, host).
  * Contacts in the convention read_mosaic_contact hands to fregrid (read_mosaic.c:655-777): tile numbers 1-based,
  * 0-based model indices, istart == iend for a west/east edge (0 / nx-1), jstart == jend for south/north.
- * Computes calc_c2l_grid_info (gradient_c2l.c:368) per tile on the host and keeps it in HBM. */
+ * Computes calc_c2l_grid_info (gradient_c2l.c:368) per tile on the host and keeps it in HBM.
+ * Refused with FG_ERR_ARG (fg_halo_map): contact indices outside their tile, and contacts between tiles of different sizes
+ * where setup_boundary (fregrid_util.c:2446-2560), which sizes the neighbour's strip with the receiving tile's nx / ny, would
+ * read another column or leave the array -- the reference does not define those. */
 int  fg_c2l_create(int ntiles, const int *nx, const int *ny, const double *const *lonc, const double *const *latc,
                    const double *const *lont, const double *const *latt,
                    int ncontacts, const int *tile1, const int *tile2,

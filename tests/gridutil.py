@@ -61,3 +61,48 @@ def cell_centres(lonc, latc):
     lon = np.arctan2(ym, xm)
     lon = np.where(lon < 0, lon + 2 * np.pi, lon)
     return lon, np.arcsin(zm / r)
+
+
+def c2l_mosaic(fg, name):
+    """Small mosaics for the order-2 input preparation at sizes that are no multiple of a block, with nx != ny and with
+    unequal tiles: dict(nx, ny, lon, lat [ny+1][nx+1], lont, latt [ny][nx] per tile, contacts).
+      'c9', 'c10'  global cubed sphere, 486 / 600 cells, 12 contacts
+      'patches'    tile 0 of C14 cut 2 x 2 into patches of nx = 7, ny = 5: 4 contacts, outer edges without one
+      'unequal'    low-index corner patches of tiles 0, 1, 2 of C16 with nx = 7, 3, 16 and ny = 5, 11, 2: no contact
+      'single'     the last of those alone
+      'cuboid'     C12 with tile t subsampled [::sy, ::sx]: contacts between tiles of different sizes, which the reference's
+                   setup_boundary does not define (for fg_halo_map's refusal only: never give it to a device)"""
+    A = np.ascontiguousarray
+    if name in ("c9", "c10"):
+        ni = int(name[1:])
+        lon, lat, lont, latt = fg.gnomonic_ed_grid(ni)
+        nx, ny = [ni] * 6, [ni] * 6
+        tiles = [(lon[t], lat[t], lont[t], latt[t]) for t in range(6)]
+    elif name == "patches":
+        lon, lat, lont, latt = fg.gnomonic_ed_grid(14)
+        nx, ny = [7] * 4, [5] * 4
+        tiles = []
+        for pj in range(2):
+            for pi in range(2):
+                c = (slice(pj * 5, (pj + 1) * 5 + 1), slice(pi * 7, (pi + 1) * 7 + 1))
+                m = (slice(pj * 5, (pj + 1) * 5), slice(pi * 7, (pi + 1) * 7))
+                tiles.append((lon[0][c], lat[0][c], lont[0][m], latt[0][m]))
+    elif name in ("unequal", "single"):
+        lon, lat, lont, latt = fg.gnomonic_ed_grid(16)
+        nx, ny = [7, 3, 16], [5, 11, 2]
+        tiles = [(lon[t][:ny[t] + 1, :nx[t] + 1], lat[t][:ny[t] + 1, :nx[t] + 1], lont[t][:ny[t], :nx[t]], latt[t][:ny[t], :nx[t]])
+                 for t in range(3)]
+        if name == "single":
+            nx, ny, tiles = nx[2:], ny[2:], tiles[2:]
+    elif name == "cuboid":
+        lon, lat, lont, latt = fg.gnomonic_ed_grid(12)
+        sub = ((1, 2), (3, 2), (3, 1), (2, 1), (2, 3), (1, 3))
+        nx, ny = [12 // s[0] for s in sub], [12 // s[1] for s in sub]
+        # (the centres are not used by the contact search or the halo map; the subsampled ones only fill the slots)
+        tiles = [(lon[t][::sy, ::sx], lat[t][::sy, ::sx], lont[t][::sy, ::sx], latt[t][::sy, ::sx]) for t, (sx, sy) in enumerate(sub)]
+    else:
+        raise ValueError(name)
+    lonc, latc, lonm, latm = ([A(t[k]) for t in tiles] for k in range(4))
+    for t in range(len(nx)):
+        assert lonc[t].shape == (ny[t] + 1, nx[t] + 1) and lonm[t].shape == (ny[t], nx[t])
+    return dict(nx=nx, ny=ny, lon=lonc, lat=latc, lont=lonm, latt=latm, contacts=fg.find_contacts(nx, ny, lonc, latc))

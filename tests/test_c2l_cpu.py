@@ -136,6 +136,51 @@ def test_halo_map_equals_reference_form_and_is_geometrically_continuous(fg):
             assert np.all(d_h2 > 1.4 * d_ee)               # the halo point lies beyond the edge, not back inside
 
 
+def test_halo_map_stays_inside_the_halo_array_or_refuses(fg):
+    """fg_halo_map restates setup_boundary, which places the neighbour's interior strip with the RECEIVING tile's nx / ny.
+    Between tiles of different sizes that leaves the halo'd array (an entry of 500 in a map of F = 488 elements for the cuboid
+    below), and fg_c2l_create would upload such a map for k_halo_gather / k_c2l_records to read through.  Such contacts are
+    refused; every map that is returned holds only -1 or an index in [0, F)."""
+    bad = gridutil.c2l_mosaic(fg, "cuboid")
+    assert bad["nx"] == [12, 4, 4, 6, 6, 12] and bad["ny"] == [6, 6, 12, 12, 4, 4] and len(bad["contacts"]["tile1"]) == 12
+    with pytest.raises(ValueError):
+        fg.halo_map(bad["nx"], bad["ny"], bad["contacts"])
+    expect = {"c9": (12, 216), "c10": (12, 240), "c12": (12, 288), "patches": (4, 48), "unequal": (0, 0), "single": (0, 0)}
+    for name, (ncontacts, nfilled) in expect.items():
+        if name == "c12":
+            lon, lat = fg.gnomonic_ed_corners(12)
+            nx, ny = [12] * 6, [12] * 6
+            c = fg.find_contacts(nx, ny, lon, lat)
+        else:
+            m = gridutil.c2l_mosaic(fg, name)
+            nx, ny, c = m["nx"], m["ny"], m["contacts"]
+        assert len(c["tile1"]) == ncontacts, name
+        off, mp = fg.halo_map(nx, ny, c)
+        F = sum((a + 2) * (b + 2) for a, b in zip(nx, ny))
+        assert off[-1] == F and mp.shape == (F,)
+        assert mp.min() >= -1 and mp.max() < F, name
+        assert int((mp >= 0).sum()) == nfilled, name
+        for t in range(len(nx)):                          # sources are interior cells, targets halo cells
+            mm = mp[off[t]:off[t + 1]].reshape(ny[t] + 2, nx[t] + 2)
+            assert np.all(mm[1:-1, 1:-1] == -1), name
+        interior = np.zeros(F, dtype=bool)
+        for t in range(len(nx)):
+            interior[off[t]:off[t + 1]].reshape(ny[t] + 2, nx[t] + 2)[1:-1, 1:-1] = True
+        assert np.all(interior[mp[mp >= 0]]), name
+    # a contact whose own indices leave its tile is refused as well: C12, one side of one contact moved along its edge by
+    # one cell (the two strips keep equal lengths, so the reference's size check does not see it)
+    lon, lat = fg.gnomonic_ed_corners(12)
+    good = fg.find_contacts([12] * 6, [12] * 6, lon, lat)
+    for side in ("1", "2"):
+        for shift in (1, -1):
+            c = {k: v.copy() for k, v in good.items()}
+            along = ("istart", "iend") if c["istart" + side][0] != c["iend" + side][0] else ("jstart", "jend")
+            for k in along:
+                c[k + side][0] += shift
+            with pytest.raises(ValueError):
+                fg.halo_map([12] * 6, [12] * 6, c)
+
+
 @needs_ref
 def test_c2l_grid_info_bitwise_vs_reference(fg):
     R = orc.ref()

@@ -21,8 +21,11 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def oracle_prepare(fg, ni, lon, lat, lont, latt, contacts, interior, nz, missing=None):
-    """CPU oracle of the same preparation: halo'd data, grad_x, grad_y, grad_mask per tile."""
+def oracle_prepare(fg, ni, lon, lat, lont, latt, contacts, interior, nz, missing=None, halo_data=None):
+    """CPU oracle of the same preparation: halo'd data, grad_x, grad_y, grad_mask per tile.
+    ni: the size of six ni x ni tiles, or (nx, ny) with one entry per tile of any mosaic.  interior[t] holds [nz][ny][nx];
+    halo_data[t] ([nz][ny+2][nx+2]), when given, replaces it: interiors AND halos as the caller supplies them, the halo cells
+    of a contact still overwritten by the update (fg_c2l_fill_halo with src == NULL)."""
     L = orc.oracle()
     f = L.orc_update_halo
     f.restype = C.c_int
@@ -33,28 +36,33 @@ def oracle_prepare(fg, ni, lon, lat, lont, latt, contacts, interior, nz, missing
     gm = L.orc_grad_mask
     gm.restype = None
     gm.argtypes = [C.c_int, C.c_int, dp, C.c_double, ip]
-    nxa = np.full(6, ni, dtype=np.int32)
-    cs = [np.ascontiguousarray(contacts[k]) for k in KEYS]
+    nx, ny = ([ni] * 6, [ni] * 6) if np.isscalar(ni) else ni
+    nt = len(nx)
+    nxa, nya = np.array(nx, dtype=np.int32), np.array(ny, dtype=np.int32)
+    cs = [np.ascontiguousarray(contacts[k], dtype=np.int32) for k in KEYS]
 
-    def halo(arrs, nlev):
-        tiles = [np.zeros((nlev, ni + 2, ni + 2)) for _ in range(6)]
-        for t in range(6):
-            tiles[t][:, 1:-1, 1:-1] = arrs[t].reshape(nlev, ni, ni)
-        assert f(6, PI(nxa), PI(nxa), len(cs[0]), *[PI(c) for c in cs], nlev, (dp * 6)(*[P(a) for a in tiles])) == 0
+    def halo(arrs, nlev, given=None):
+        if given is not None:
+            tiles = [np.array(given[t], dtype=np.float64).reshape(nlev, ny[t] + 2, nx[t] + 2) for t in range(nt)]
+        else:
+            tiles = [np.zeros((nlev, ny[t] + 2, nx[t] + 2)) for t in range(nt)]
+            for t in range(nt):
+                tiles[t][:, 1:-1, 1:-1] = np.asarray(arrs[t]).reshape(nlev, ny[t], nx[t])
+        assert f(nt, PI(nxa), PI(nya), len(cs[0]), *[PI(c) for c in cs], nlev, (dp * nt)(*[P(a) for a in tiles])) == 0
         return tiles
-    xt = halo([lont[t] for t in range(6)], 1)
-    yt = halo([latt[t] for t in range(6)], 1)
-    data = halo(interior, nz)
-    gx = [np.empty((nz, ni * ni)) for _ in range(6)]
-    gy = [np.empty((nz, ni * ni)) for _ in range(6)]
-    mask = [np.zeros((nz, ni * ni), dtype=np.int32) for _ in range(6)]
-    for t in range(6):
-        info = fg.c2l_grid_info(ni, ni, xt[t][0], yt[t][0], lon[t], lat[t])
+    xt = halo([lont[t] for t in range(nt)], 1)
+    yt = halo([latt[t] for t in range(nt)], 1)
+    data = halo(interior, nz, halo_data)
+    gx = [np.empty((nz, nx[t] * ny[t])) for t in range(nt)]
+    gy = [np.empty((nz, nx[t] * ny[t])) for t in range(nt)]
+    mask = [np.zeros((nz, nx[t] * ny[t]), dtype=np.int32) for t in range(nt)]
+    for t in range(nt):
+        info = fg.c2l_grid_info(nx[t], ny[t], xt[t][0], yt[t][0], lon[t], lat[t])
         for k in range(nz):
             lev = np.ascontiguousarray(data[t][k])
-            g(ni, ni, P(lev), *[P(info[q]) for q in GEOM], P(gx[t][k]), P(gy[t][k]))
+            g(nx[t], ny[t], P(lev), *[P(info[q]) for q in GEOM], P(gx[t][k]), P(gy[t][k]))
             if missing is not None:
-                gm(ni, ni, P(lev), missing, PI(mask[t][k]))
+                gm(nx[t], ny[t], P(lev), missing, PI(mask[t][k]))
     return data, gx, gy, mask, xt, yt
 
 
