@@ -128,3 +128,10 @@ class C2lPrep:
         """unpadded levels [nz, ncells] -> rec [ncells, 3, records_nb(nz)] in one pass (fg_c2l_records): halo values are read
         from the neighbour tiles through the halo map, no halo'd copy is made."""
         check(lib().fg_c2l_records(self._h, C.c_void_p(src_t.data_ptr()), nz, C.c_void_p(rec_t.data_ptr())))
+
+    def records_levels(self, src_t, nz, missing, rec_t, maskbits_t):
+        """unpadded levels [nz, ncells] that carry missing values -> rec [ncells, 3, 8] (eight levels wide whatever nz) and
+        maskbits [ncells] uint8, bit k = the gradient mask of level k (fg_c2l_records_levels); XgridPlan.apply_records_levels
+        sweeps them."""
+        check(lib().fg_c2l_records_levels(self._h, C.c_void_p(src_t.data_ptr()), nz, float(missing), C.c_void_p(rec_t.data_ptr()),
+                                          C.c_void_p(maskbits_t.data_ptr())))

@@ -402,6 +402,29 @@ class XgridPlan:
                                           C.byref(g) if want_gsum else None))
         return g.value if want_gsum else None
 
+    def apply_levels(self, data_t, out_t, nlev, missing, grad_x_t=None, grad_y_t=None, grad_mask_t=None, want_gsum=False):
+        """The level loop of a field with missing values in one call (fg_plan_apply_levels): level k of out [nlev, ndst] is what
+        apply(has_missing=True, nz=1) gives on level k alone.  data [nlev, F], grads [nlev, ncells_in], grad_mask int32
+        [nlev, ncells_in] (order 2 only).  Returns the per-level sums (numpy [nlev]) with want_gsum."""
+        g = np.zeros(nlev, dtype=np.float64)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        check(lib().fg_plan_apply_levels(self._h, ptr(data_t), ptr(grad_x_t), ptr(grad_y_t), ptr(grad_mask_t), float(missing),
+                                         nlev, ptr(out_t), _dp(g) if want_gsum else None))
+        return g if want_gsum else None
+
+    def apply_records_levels(self, nz, rec_t, maskbits_t, out_t, missing, want_gsum=False):
+        """Order-2 sweep of nz <= 8 levels with missing values on what C2lPrep.records_levels wrote (rec [ncells_in, 3, 8],
+        maskbits uint8 [ncells_in]); out [nz, ndst].  Bit-identical to apply_levels()."""
+        g = np.zeros(nz, dtype=np.float64)
+        check(lib().fg_plan_apply_records_levels(self._h, nz, C.c_void_p(rec_t.data_ptr()), C.c_void_p(maskbits_t.data_ptr()),
+                                                 float(missing), C.c_void_p(out_t.data_ptr()), _dp(g) if want_gsum else None))
+        return g if want_gsum else None
+
+    @staticmethod
+    def levels_capacity():
+        """exchange cells apply_levels stages per chunk (fg_plan_levels_capacity)"""
+        return int(lib().fg_plan_levels_capacity())
+
 
 @dataclass
 class InterpConfig:

@@ -246,6 +246,53 @@ __global__ __launch_bounds__(CB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   d_store_records<NB, CB, (NB >= 8 ? 2 : 1)>(row, c < ncells, c0, ncells, rec);
 }
 
+// k_c2l_records for levels with missing values of their own (fg_c2l_records_levels): the same records, always eight levels wide,
+// plus the gradient mask of fregrid_util.c:2203-2215 as one byte per cell -- bit k set where one of the EIGHT neighbours of the
+// cell (not the cell itself) equals `missing` in level k.  The neighbours are the stencil's own values, read through the halo
+// map, so a missing cell of another tile across a cube edge or corner masks its neighbour here; an element no contact fills
+// holds init_halo's 0.0 and is compared like any other value, as k_grad_mask does on the filled halo'd copy.
+template <int CB>
+__global__ __launch_bounds__(CB) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_c2l_records_m(const C2lTile *tiles, int ntiles, long ncells, int nz, const double *src,
+                                                    const int *cell_of, C2lGeom g, double missing, double *rec, unsigned char *gbits)
+{
+  constexpr int NB = 8, R = 3 * NB;
+  const long c0 = (long)blockIdx.x * CB;
+  const long c = c0 + threadIdx.x;
+  double row[R];
+  if (c < ncells) {
+    const C2lTile T = tiles[d_find_tile(tiles, ntiles, c)];
+    const C2lCell cell(T, c, g);
+    int at[3][3];
+#pragma unroll
+    for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+      for (int dx = 0; dx < 3; dx++) at[dy][dx] = cell_of[T.f_off + (long)(cell.j + dy) * (T.nx + 2) + cell.i + dx];
+    unsigned bits = 0;
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+      double f = 0.0, gx = 0.0, gy = 0.0;
+      if (k < nz) {
+        const double *lev = src + (size_t)k * ncells;
+        double v[3][3];
+        bool m = false;
+#pragma unroll
+        for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+          for (int dx = 0; dx < 3; dx++) {
+            v[dy][dx] = (at[dy][dx] >= 0) ? lev[at[dy][dx]] : 0.0;
+            if (!(dy == 1 && dx == 1) && v[dy][dx] == missing) m = true;
+          }
+        f = v[1][1];
+        cell.stencil(v, &gx, &gy);
+        bits |= (m ? 1u : 0u) << k;
+      }
+      row[k] = f; row[NB + k] = gx; row[2 * NB + k] = gy;
+    }
+    gbits[c] = (unsigned char)bits;
+  }
+  d_store_records<NB, CB, 2>(row, c < ncells, c0, ncells, rec);
+}
+
 __global__ __launch_bounds__(256) void k_grad_mask(const C2lTile *tiles, int ntiles, long ncells, long F, int nz,
                                                     const double *data, double missing, int *mask)
 {
@@ -302,6 +349,13 @@ void fgd_c2l_records(const void *tiles, int ntiles, long ncells, int nz, int nb_
   if (nb_pad == 8) k_c2l_records<8, 64><<<nblk(ncells, 64), 64, 0, st>>>(T, ntiles, ncells, nz, src, cell_of, g, rec);
   else if (nb_pad == 4) k_c2l_records<4, 128><<<nblk(ncells, 128), 128, 0, st>>>(T, ntiles, ncells, nz, src, cell_of, g, rec);
   else k_c2l_records<2, 128><<<nblk(ncells, 128), 128, 0, st>>>(T, ntiles, ncells, nz, src, cell_of, g, rec);
+}
+void fgd_c2l_records_levels(const void *tiles, int ntiles, long ncells, int nz, const double *src, const int *cell_of,
+                            const double *const *geom, double missing, double *rec, unsigned char *gbits, hipStream_t st)
+{
+  if (ncells <= 0 || nz <= 0) return;
+  C2lGeom g{geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], geom[6], geom[7], geom[8], geom[9], geom[10]};
+  k_c2l_records_m<64><<<nblk(ncells, 64), 64, 0, st>>>((const C2lTile *)tiles, ntiles, ncells, nz, src, cell_of, g, missing, rec, gbits);
 }
 void fgd_grad_mask(const void *tiles, int ntiles, long ncells, long F, int nz, const double *data, double missing, int *mask, hipStream_t st)
 {

@@ -419,6 +419,7 @@ struct fg_plan {
   long row_sum_cap = 0;
   double *il_f = nullptr, *il_out = nullptr, *il_rs = nullptr;   // [cell][8] scratch (order 1 field, output, row sums)
   double *il_m = nullptr;                                        // order 2: merged records [source cell][3][8] (k_merge3)
+  unsigned char *lv_bits = nullptr;                              // order 2, fg_plan_apply_levels: gradient-mask bits per source cell
   long stats[FG_NSTATS] = {0};
   // monotone limiter scratch (fg_plan_mono_*): limited values per CSR entry, per-source-cell bounds, error word
   double *mono_x = nullptr, *mono_b = nullptr;     // mono_b: [4][nsrc] = f_bar_max | f_bar_min | f_max | f_min
@@ -1829,6 +1830,101 @@ extern "C" int fg_plan_apply_records(fg_plan *pl, int nz, const double *rec, dou
   return 0;
 }
 
+// ------------------------------------------------------------------- levels with missing values of their own
+// The reference's level loop (fregrid.c:1045-1083: do_scalar_conserve_interp(nz = 1, has_missing = 1) per level), eight levels
+// per launch of k_apply_ep8m.  Row sums are kept level-major and reduced level by level with the reduction of the one-level
+// calls, so gsum_out[k] carries the bits fg_plan_apply_ex returns for level k alone.
+extern "C" int fg_plan_levels_capacity(void) { return FG_LEVELS_CAP; }
+int fg_plan_is_finalized(const fg_plan *pl) { return pl && pl->finalized; }      // for sweep.hip
+
+static int levels_scratch(fg_plan *pl, bool want_rs, bool want_il)
+{
+  if (want_il) { int rc = ensure_il_scratch(pl, false); if (rc) return rc; }
+  if (want_il && pl->order == 2 && !pl->lv_bits) {
+    pl->lv_bits = pl->alloc<unsigned char>(pl->nsrc > 0 ? pl->nsrc : 1);
+    if (!pl->lv_bits) return fail(FG_ERR_HIP, "out of device memory");
+  }
+  if (want_rs && !pl->il_rs) {
+    pl->il_rs = pl->alloc<double>((size_t)pl->ndst * 16);
+    if (!pl->il_rs) return fail(FG_ERR_HIP, "out of device memory");
+  }
+  return 0;
+}
+
+// per-level sums of one chunk (il_rs [level][ndst]) -> red_result, handed to the host whenever the 256 result slots are full
+static int levels_gsum(fg_plan *pl, int nbv, int *nred, double **gsum_out, bool last)
+{
+  hipStream_t st = pl->stream;
+  for (int k = 0; k < nbv; k++) fgd_reduce_sum(pl->il_rs + (size_t)k * pl->ndst, pl->ndst, pl->red_partial, pl->red_result + (*nred)++, st);
+  if (*nred + 8 > 256 || last) {
+    HIPCHK(hipMemcpyAsync(*gsum_out, pl->red_result, *nred * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *gsum_out += *nred; *nred = 0;
+  }
+  return 0;
+}
+
+extern "C" int fg_plan_apply_levels(fg_plan *pl, const double *data, const double *grad_x, const double *grad_y,
+                                    const int *grad_mask, double missing, int nlev, double *out, double *gsum_out)
+{
+  if (!pl || !data || !out) return fail(FG_ERR_ARG, "fg_plan_apply_levels: null argument");
+  if (!pl->finalized) return fail(FG_ERR_ARG, "fg_plan_apply_levels: the plan is not finalized (fg_plan_finalize)");
+  if (nlev < 1) return fail(FG_ERR_ARG, "fg_plan_apply_levels: nlev must be >= 1");
+  if (pl->order == 2 && (!grad_x || !grad_y || !grad_mask))
+    return fail(FG_ERR_ARG, "fg_plan_apply_levels: order 2 needs grad_x, grad_y and grad_mask [nlev][ncells_in]");
+  HIPCHK(hipSetDevice(pl->device));
+  { int rc = levels_scratch(pl, gsum_out != nullptr, true); if (rc) return rc; }
+  hipStream_t st = pl->stream;
+  const int ndst = pl->ndst;
+  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, st);
+  pl->apply_pt.begin(PH_APPLY);
+  int nred = 0;
+  for (int k0 = 0; k0 < nlev; k0 += 8) {
+    const int nbv = (nlev - k0 < 8) ? nlev - k0 : 8;
+    const double *f = data + (size_t)k0 * pl->f_stride;
+    double *o = out + (size_t)k0 * ndst;
+    double *rs = gsum_out ? pl->il_rs : nullptr;
+    if (pl->order == 2) {
+      fgd_merge3(8, pl->nsrc, pl->src_idx_f, f, pl->f_stride, grad_x + (size_t)k0 * pl->nsrc, grad_y + (size_t)k0 * pl->nsrc, pl->nsrc,
+                 nbv, pl->il_m, st);
+      fgd_gmask_bits(pl->nsrc, grad_mask + (size_t)k0 * pl->nsrc, pl->nsrc, nbv, pl->lv_bits, st);
+      fgd_apply_levels8(2, ndst, pl->nx, pl->csr, pl->il_m, pl->lv_bits, missing, o, rs, (long)ndst, nbv, st);
+    } else {
+      const double *ins[3] = {f, nullptr, nullptr};
+      double *outs[3] = {pl->il_f, nullptr, nullptr};
+      const long lds[3] = {pl->f_stride, 0, 0}, ns[3] = {pl->f_stride, 0, 0};
+      fgd_interleave3(8, 1, ins, lds, ns, outs, nbv, st);
+      fgd_apply_levels8(1, ndst, pl->nx, pl->csr, pl->il_f, nullptr, missing, o, rs, (long)ndst, nbv, st);
+    }
+    if (gsum_out) { int rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
+  }
+  pl->apply_pt.end();
+  if (pl->apply_pt.on) pl->apply_spans++;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int fg_plan_apply_records_levels(fg_plan *pl, int nz, const double *rec, const unsigned char *maskbits, double missing,
+                                            double *out, double *gsum_out)
+{
+  if (!pl || !rec || !out) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: null argument");
+  if (!pl->finalized) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: the plan is not finalized (fg_plan_finalize)");
+  if (pl->order != 2) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: records carry gradients, the plan is first order");
+  if (!maskbits) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: order 2 needs the gradient-mask bits");
+  if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: 1 to 8 levels per call");
+  HIPCHK(hipSetDevice(pl->device));
+  { int rc = levels_scratch(pl, gsum_out != nullptr, false); if (rc) return rc; }
+  hipStream_t st = pl->stream;
+  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, st);
+  pl->apply_pt.begin(PH_APPLY);
+  fgd_apply_levels8(2, pl->ndst, pl->nx, pl->csr, rec, maskbits, missing, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, st);
+  pl->apply_pt.end();
+  if (pl->apply_pt.on) pl->apply_spans++;
+  if (gsum_out) { int nred = 0; int rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------- the sweep with every option
 static int ex_check(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *gx, const double *gy, int nz, const char *who)
 {
@@ -2702,6 +2798,17 @@ extern "C" int fg_c2l_records(fg_c2l *h, const double *src, int nz, double *rec)
   if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_c2l_records: 1 to 8 levels per call");
   HIPCHK(hipSetDevice(h->device));
   fgd_c2l_records(h->tiles_dev, h->ntiles, h->ncells, nz, records_nb_pad(nz), src, h->cell_of_dev, (const double *const *)h->geom_dev, rec, h->stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int fg_c2l_records_levels(fg_c2l *h, const double *src, int nz, double missing, double *rec, unsigned char *maskbits)
+{
+  if (!h || !src || !rec || !maskbits) return fail(FG_ERR_ARG, "fg_c2l_records_levels: null argument");
+  if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_c2l_records_levels: 1 to 8 levels per call");
+  HIPCHK(hipSetDevice(h->device));
+  fgd_c2l_records_levels(h->tiles_dev, h->ntiles, h->ncells, nz, src, h->cell_of_dev, (const double *const *)h->geom_dev, missing, rec,
+                         maskbits, h->stream);
   HIPCHK(hipGetLastError());
   return 0;
 }

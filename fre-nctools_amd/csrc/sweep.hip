@@ -24,6 +24,7 @@ void fg_set_last_error(const char *msg);         // plan.hip
 // run-scoped use of our compute stream by the plans and the gradient object (plan.hip)
 int fg_plan_borrow_stream(fg_plan *pl, void *stream, void **saved, int *saved_own);
 void fg_plan_return_stream(fg_plan *pl, void *saved, int saved_own);
+int fg_plan_is_finalized(const fg_plan *pl);
 int fg_c2l_borrow_stream(fg_c2l *h, void *stream, void **saved, int *saved_own);
 void fg_c2l_return_stream(fg_c2l *h, void *saved, int saved_own);
 
@@ -112,6 +113,7 @@ struct fg_sweep {
   std::vector<long> ndst, doff;          // cells per plan, offset of the plan's block inside a slot's output (in cells x CHUNK)
   hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;
   double *d_f64 = nullptr, *d_rec = nullptr, *d_tmp = nullptr;   // shared by the chunks (compute stream is in order)
+  unsigned char *d_bits = nullptr;       // order 2, fg_sweep_run_levels: gradient-mask bits of the chunk (fg_c2l_records_levels)
   struct Slot {
     void *d_raw = nullptr, *d_fin = nullptr;     // device: levels as they came from the host; outputs as they go back
     void *pin_in = nullptr, *pin_out = nullptr;  // staging for pageable user memory (allocated on first need)
@@ -144,6 +146,7 @@ extern "C" void fg_sweep_destroy(fg_sweep *sw)
     for (hipEvent_t e : {sl.e_in, sl.e_comp, sl.e_out}) if (e) (void)hipEventDestroy(e);
   }
   for (double *d : {sw->d_f64, sw->d_rec, sw->d_tmp}) if (d) (void)hipFree(d);
+  if (sw->d_bits) (void)hipFree(sw->d_bits);
   for (hipStream_t s : {sw->s_in, sw->s_comp, sw->s_out}) if (s) (void)hipStreamDestroy(s);
   delete sw;
 }
@@ -179,7 +182,8 @@ extern "C" int fg_sweep_create(int nplans, fg_plan *const *plans, fg_c2l *c2l, i
          hipEventCreateWithFlags(&sl.e_out, hipEventDisableTiming) == hipSuccess;
   }
   ok = ok && hipMalloc((void **)&sw->d_f64, nin * 8) == hipSuccess && hipMalloc((void **)&sw->d_tmp, nout * 8) == hipSuccess;
-  if (sw->order == 2) ok = ok && hipMalloc((void **)&sw->d_rec, (size_t)sw->ncin * 3 * 8 * 8) == hipSuccess;
+  if (sw->order == 2) ok = ok && hipMalloc((void **)&sw->d_rec, (size_t)sw->ncin * 3 * 8 * 8) == hipSuccess &&
+                           hipMalloc((void **)&sw->d_bits, (size_t)(sw->ncin > 0 ? sw->ncin : 1)) == hipSuccess;
   if (!ok) { (void)hipGetLastError(); fg_sweep_destroy(sw); return sw_fail(FG_ERR_HIP, "fg_sweep_create: out of device memory (or stream / event creation failed)"); }
   *out = sw;
   return 0;
@@ -198,11 +202,14 @@ static int slot_retire(fg_sweep *sw, fg_sweep::Slot &sl, void *const *host_out)
   return 0;
 }
 
-extern "C" int fg_sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
-                            void *const *host_out)
+// masked: every level carries missing values of its own (fg_sweep_run_levels); else every value is data (fg_sweep_run)
+static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
+                     void *const *host_out, bool masked)
 {
-  if (!sw || !host_in || !host_out || nlev < 1) return sw_fail(FG_ERR_ARG, "fg_sweep_run: null argument");
-  for (size_t p = 0; p < sw->plans.size(); p++) if (!host_out[p]) return sw_fail(FG_ERR_ARG, "fg_sweep_run: null output array");
+  if (!sw || !host_in || !host_out || nlev < 1) return sw_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null argument" : "fg_sweep_run: null argument");
+  for (size_t p = 0; p < sw->plans.size(); p++) if (!host_out[p]) return sw_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null output array" : "fg_sweep_run: null output array");
+  if (masked)
+    for (fg_plan *p : sw->plans) if (!fg_plan_is_finalized(p)) return sw_fail(FG_ERR_ARG, "fg_sweep_run_levels: a plan is not finalized (fg_plan_finalize)");
   SWCHK(hipSetDevice(sw->device));
   // The plans and the gradient object launch on OUR compute stream for the duration of this call only: several fg_sweep objects
   // (one per pair of file types) may share the same plans, a plan may be used directly between two runs, and either may be
@@ -260,10 +267,18 @@ extern "C" int fg_sweep_run(fg_sweep *sw, const void *host_in, long nlev, double
       f64 = sw->d_f64;
     }
     double *res = narrow ? sw->d_tmp : (double *)sl.d_fin;         // [plan block][level][cell]
-    if (sw->order == 2) { int rc = fg_c2l_records(sw->c2l, f64, nl, sw->d_rec); if (rc) return rc; }
+    if (sw->order == 2) {
+      int rc = masked ? fg_c2l_records_levels(sw->c2l, f64, nl, missing, sw->d_rec, sw->d_bits) : fg_c2l_records(sw->c2l, f64, nl, sw->d_rec);
+      if (rc) return rc;
+    }
     for (size_t p = 0; p < sw->plans.size(); p++) {
-      int rc = (sw->order == 2) ? fg_plan_apply_records(sw->plans[p], nl, sw->d_rec, res + sw->doff[p], nullptr)
-                                : fg_plan_apply(sw->plans[p], f64, nullptr, nullptr, nullptr, 0, 0.0, nl, res + sw->doff[p], nullptr);
+      int rc;
+      if (masked)
+        rc = (sw->order == 2) ? fg_plan_apply_records_levels(sw->plans[p], nl, sw->d_rec, sw->d_bits, missing, res + sw->doff[p], nullptr)
+                              : fg_plan_apply_levels(sw->plans[p], f64, nullptr, nullptr, nullptr, missing, nl, res + sw->doff[p], nullptr);
+      else
+        rc = (sw->order == 2) ? fg_plan_apply_records(sw->plans[p], nl, sw->d_rec, res + sw->doff[p], nullptr)
+                              : fg_plan_apply(sw->plans[p], f64, nullptr, nullptr, nullptr, 0, 0.0, nl, res + sw->doff[p], nullptr);
       if (rc) return rc;
     }
     if (narrow) {
@@ -296,4 +311,18 @@ extern "C" int fg_sweep_run(fg_sweep *sw, const void *host_in, long nlev, double
   // drain in chunk order
   for (long c = (chunk > NSLOT ? chunk - NSLOT : 0); c < chunk; c++) { int rc = slot_retire(sw, sw->slot[c % NSLOT], host_out); if (rc) return rc; }
   return 0;
+}
+
+extern "C" int fg_sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
+                            void *const *host_out)
+{
+  return sweep_run(sw, host_in, nlev, scale, offset, missing, host_out, false);
+}
+
+// fg_sweep_run for a variable WITH missing values: per chunk H2D in the file type -> k_widen -> (order 2: records + gradient-mask
+// bits) -> the masked eight-level sweep per plan -> k_narrow -> D2H, on the same three slots, streams and events.
+extern "C" int fg_sweep_run_levels(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
+                                   void *const *host_out)
+{
+  return sweep_run(sw, host_in, nlev, scale, offset, missing, host_out, true);
 }

@@ -238,6 +238,12 @@ void fgd_merge3(int nb_pad, long n, const int *src_idx_f, const double *f, long 
 void fgd_interleave3(int nb_pad, int narr, const double *const *in, const long *ld, const long *n, double *const *out, int nb_valid,
                      hipStream_t st);
 void fgd_deinterleave(int nb_pad, long n, const double *in, long ld, int nb_valid, double *out, hipStream_t st);
+// eight levels with missing values of their own (apply_levels_kernels.hip): rec = merged records (order 2) or the interleaved
+// field (order 1), gbits = gradient-mask bits per source cell (order 2); out and row_sum level-major [level][ld], nb_valid levels
+#define FG_LEVELS_CAP 256     // exchange cells staged per chunk: a longer run of rows is walked in several chunks
+void fgd_apply_levels8(int order, int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing, double *out,
+                       double *row_sum, long ld, int nb_valid, hipStream_t st);
+void fgd_gmask_bits(long n, const int *gmask, long ld, int nb, unsigned char *bits, hipStream_t st);
 void fgd_apply_frac(int ndst, FgCsr csr, const double *data, double *out, hipStream_t st);
 void fgd_reduce_sum(const double *v, long n, double *partial, double *result, hipStream_t st);
 void fgd_xgrid_indices(long nx, const int *x_src, const int *x_dst, const FgTile *tiles_dev, int ntiles, int nx_out,
@@ -336,6 +342,8 @@ void fgd_grad_c2l_rec(const void *tiles, int ntiles, long ncells, long F, int nz
                       const double *const *geom, double *rec, hipStream_t st);
 void fgd_c2l_records(const void *tiles, int ntiles, long ncells, int nz, int nb_pad, const double *src, const int *cell_of,
                      const double *const *geom, double *rec, hipStream_t st);
+void fgd_c2l_records_levels(const void *tiles, int ntiles, long ncells, int nz, const double *src, const int *cell_of,
+                            const double *const *geom, double missing, double *rec, unsigned char *gbits, hipStream_t st);
 void fgd_grad_mask(const void *tiles, int ntiles, long ncells, long F, int nz, const double *data, double missing, int *mask, hipStream_t st);
 size_t fgd_c2l_tile_size(void);
 void fgd_c2l_tile_fill(void *dst, int idx, int nx, int ny, long cell_off, long f_off, long dx_off, long dy_off, long ew_off, long es_off);

@@ -216,10 +216,10 @@ class Sweep:
         """host_in [nlev][ncells_in] of in_dtype; outs[p] [nlev][ndst_p] of out_dtype (numpy arrays, ideally HostBuffer.array).
         `missing` only steers the scale / offset conversion (values equal to it are left alone, fregrid_util.c:2114-2123): the
         streamed remap itself treats every value as data.  A variable that HAS missing values (has_missing: its file carries
-        missing_value / _FillValue, read_field_levels' meta["missing"] is not None) must go level by level through
-        XgridPlan.apply(has_missing=True) -- conserve_interp.c:544 forbids nz > 1 for it -- so that case is refused here."""
+        missing_value / _FillValue, read_field_levels' meta["missing"] is not None) is refused here -- conserve_interp.c:544
+        forbids nz > 1 for it: it goes through run_levels(), which remaps every level with its own mask."""
         if has_missing and host_in.shape[0] > 1:
-            raise ValueError("conserve_interp: has_missing should be false when nz > 1 (a variable with missing values cannot take the streamed sweep)")
+            raise ValueError("conserve_interp: has_missing should be false when nz > 1 (a variable with missing values takes Sweep.run_levels)")
         a = host_in
         assert a.dtype == self.in_dtype and a.flags.c_contiguous and a.shape[1] == self.ncells_in
         nlev = a.shape[0]
@@ -227,6 +227,18 @@ class Sweep:
             assert o.dtype == self.out_dtype and o.flags.c_contiguous and o.shape == (nlev, n)
         ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
         check(lib().fg_sweep_run(self._h, a.ctypes.data_as(C.c_void_p), nlev, float(scale), float(offset), float(missing), ptrs))
+
+    def run_levels(self, host_in, outs, scale=0.0, offset=0.0, missing=-1.0e20):
+        """run() for a variable WITH missing values (fg_sweep_run_levels): every level is remapped as the reference's level loop
+        does it, do_scalar_conserve_interp(nz = 1, has_missing = 1) on that level alone; cells equal to `missing` (after the
+        conversion, which leaves them alone) are left out, destination cells without a valid source come back as `missing`."""
+        a = host_in
+        assert a.dtype == self.in_dtype and a.flags.c_contiguous and a.shape[1] == self.ncells_in
+        nlev = a.shape[0]
+        for o, n in zip(outs, self.ndst):
+            assert o.dtype == self.out_dtype and o.flags.c_contiguous and o.shape == (nlev, n)
+        ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        check(lib().fg_sweep_run_levels(self._h, a.ctypes.data_as(C.c_void_p), nlev, float(scale), float(offset), float(missing), ptrs))
 
     def destroy(self):
         if self._h:

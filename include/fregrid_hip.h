@@ -272,6 +272,36 @@ int fg_plan_apply_interleaved(fg_plan *plan, int nb, const double *data_il, cons
  * while the level-major gradient arrays and the transposition pass are skipped.  gsum_out as in fg_plan_apply. */
 int fg_plan_apply_records(fg_plan *plan, int nz, const double *rec, double *out, double *gsum_out);
 
+/* Levels that each carry missing values of their own, many per call: "the level loop".  The reference takes such a field one
+ * level per call (fregrid.c:1045-1083: get_input_data, do_scalar_conserve_interp(..., 1), write_field_data per level;
+ * conserve_interp.c:544 forbids has_missing with nz > 1), and so do fg_plan_apply / fg_plan_apply_ex, which keep that refusal.
+ * fg_plan_apply_levels is that loop on the device: for k = 0 .. nlev-1, out level k holds the bits
+ * do_scalar_conserve_interp(nz = 1, has_missing = 1) -- and fg_plan_apply(has_missing = 1, nz = 1) -- give on level k alone
+ * (conserve_interp.c:562-591 order 1; :744-783 order 2; :815-839): per destination cell the exchange cells whose source value
+ * differs from `missing` in level k are summed in CSR order; acc / asum where asum > 0, 0.0 where an exchange cell counted but
+ * asum == 0, `missing` otherwise; an exchange cell whose source cell has grad_mask set in level k uses the flat value.  Eight
+ * levels share one launch (every CSR record is read once for them); any nlev >= 1, the last chunk may be partial.
+ *   data       [nlev][F], grad_x / grad_y [nlev][ncells_in] as fg_plan_apply takes them (device pointers)
+ *   grad_mask  int [nlev][ncells_in] as fg_c2l_gradient writes it (fregrid_util.c:2203-2215).  grad_x, grad_y and grad_mask
+ *              are NULL for order 1 and required for order 2
+ *   out        [nlev][ndst] (device); gsum_out: host double[nlev] or NULL, the sum of :815-819 PER LEVEL (what
+ *              fg_plan_apply_ex(has_missing, nz = 1) returns for that level, bit for bit)
+ * Bad arguments -- nlev < 1, NULL buffers, an order-2 plan without gradients or mask, a plan that is not finalized -- return
+ * FG_ERR_ARG, write nothing and leave the plan usable.
+ * Out of scope here, one level per call through fg_plan_apply_ex as before: weight field, cell_measures, cell_methods = sum,
+ * --target_grid and the monotone limiter.  integration/ keeps the reference's per-level loop. */
+int fg_plan_apply_levels(fg_plan *plan, const double *data, const double *grad_x, const double *grad_y,
+                         const int *grad_mask, double missing, int nlev, double *out, double *gsum_out);
+/* The same sweep of 1 <= nz <= 8 levels on the records fg_c2l_records_levels writes: rec [ncells_in][3][8] (always eight
+ * levels wide, zero padded) and maskbits, unsigned char [ncells_in]: bit k set = the cell's gradient is masked in level k (its
+ * exchange cells use the flat value there).  Validity is read from the records themselves (field value == missing).  Order-2
+ * plans only.  out [nz][ndst], gsum_out host double[nz] or NULL; bit-identical to fg_plan_apply_levels. */
+int fg_plan_apply_records_levels(fg_plan *plan, int nz, const double *rec, const unsigned char *maskbits, double missing,
+                                 double *out, double *gsum_out);
+/* Exchange cells the eight-level masked sweep stages per chunk: a tile of destination rows with more of them (fine -> coarse
+ * remaps) is walked in several chunks, the sums carried from chunk to chunk. */
+int fg_plan_levels_capacity(void);
+
 /* The sweep with every remaining option of do_scalar_conserve_interp (conserve_interp.c:507-910).  All pointers are
  * DEVICE pointers over the flattened source cells (tiles back to back, [ny][nx], no halo) or destination cells.
  *   weight          grid_in[].weight (weight_exist, --weight_file/--weight_field), or NULL
@@ -421,6 +451,12 @@ int  fg_c2l_gradient_records(fg_c2l *h, const double *halo_data, int nz, double 
  * neighbour tiles' cells through the halo map instead of materialising the halo'd copy.  Bit-identical to
  * fg_c2l_fill_halo + fg_c2l_gradient_records. */
 int  fg_c2l_records(fg_c2l *h, const double *src, int nz, double *rec);
+/* fg_c2l_records for 1 <= nz <= 8 levels with missing values of their own: rec [ncells][3][8] (eight levels wide whatever nz)
+ * and maskbits, unsigned char [ncells], bit k = grad_mask of level k (fregrid_util.c:2203-2215): one of the cell's EIGHT
+ * neighbours -- not the cell itself -- equals `missing`, neighbours in other tiles read through the halo map, so a missing
+ * cell across a cube edge or corner masks its neighbour.  Same bits as fg_c2l_fill_halo + fg_c2l_gradient(has_missing).
+ * Pair with fg_plan_apply_records_levels.  Device pointers. */
+int  fg_c2l_records_levels(fg_c2l *h, const double *src, int nz, double missing, double *rec, unsigned char *maskbits);
 
 /* Host helpers behind fg_c2l_create, exported for tests and for callers without a mosaic file. */
 int fg_c2l_grid_info(int nx, int ny, const double *xt, const double *yt, const double *xc, const double *yc,
@@ -495,7 +531,13 @@ const char *fg_nc_last_error(void);
  *   conserve_order2 plans (NULL for order 1).  in_type / out_type: FG_NC_SHORT, FG_NC_INT, FG_NC_FLOAT or FG_NC_DOUBLE.
  * fg_sweep_run: host_in [nlev][ncells_in] of in_type (tiles back to back, no halo), host_out[p] [nlev][ndst_p] of out_type.
  *   scale / offset: the variable's scale_factor / add_offset (0 = absent, as the reference treats them); applied to values
- *   != missing.  Levels carry no missing values (conserve_interp.c:544 requires nz == 1 for those: use fg_plan_apply_ex).
+ *   != missing.  fg_sweep_run treats every value as data (conserve_interp.c:544 requires nz == 1 for a variable with missing
+ *   values); such a variable goes through fg_sweep_run_levels.
+ * fg_sweep_run_levels: the same arguments, buffers, slots, streams and events for a variable WITH missing values: every level
+ *   is remapped as do_scalar_conserve_interp(nz = 1, has_missing = 1) would remap it alone (fg_plan_apply_levels; for order 2
+ *   fg_c2l_records_levels + fg_plan_apply_records_levels per chunk), `missing` marking the cells to leave out; it comes back
+ *   as `missing` cast to the output type (write_field_data leaves it alone).  A plan that is not finalized is refused with
+ *   FG_ERR_ARG before anything is copied.
  * Buffers from fg_host_alloc are page-locked: copies go straight from / to them; other host memory is staged through the
  * object's own pinned buffers with one extra host copy.
  * Streams and lifetimes: the plans and the gradient object run on the sweep's compute stream only INSIDE fg_sweep_run (they get
@@ -514,6 +556,8 @@ typedef struct fg_sweep fg_sweep;
 int  fg_sweep_create(int nplans, fg_plan *const *plans, fg_c2l *c2l, int in_type, int out_type, fg_sweep **out);
 int  fg_sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
                   void *const *host_out);
+int  fg_sweep_run_levels(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
+                         void *const *host_out);
 void fg_sweep_destroy(fg_sweep *sw);
 void *fg_host_alloc(size_t bytes);      /* page-locked host memory (hipHostMalloc), NULL on failure */
 void fg_host_free(void *p);
