@@ -249,6 +249,102 @@ __device__ __forceinline__ int d_xcd_block(int b, int nb, int band)
   return ((k / C) * 8 + x) * C + (k % C);
 }
 
+// ------------------------------------------------------------------- the pieces every entry-parallel sweep kernel is made of
+// A tile of ROWS destination rows owns one contiguous run [q0, q1) of CSR records and walks it in chunks of CAP: a chunk is staged
+// in LDS (ep_stage_*), every lane takes its exchange cells' records into registers and issues their gathers in one round, the
+// buffer becomes the table of products, and the lane of each row -- or of each (row, level) -- adds its part of the chunk in CSR
+// order (ep_row_add), carrying its sums from chunk to chunk; apply_finish turns the sums into the output value.
+template <int ORDER> using CsrEntry = typename std::conditional<ORDER == 2, FgCsrEntry2, FgCsrEntry1>::type;
+template <int ORDER> __device__ __forceinline__ const CsrEntry<ORDER> *csr_entries(const FgCsr &csr)
+{
+  if constexpr (ORDER == 2) return csr.e2; else return csr.e1;
+}
+typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+
+// The tile's run of records and this lane's row [b, e): LPR lanes per row, lane t serves row d0 + t / LPR at level t % LPR
+// (LPR = 1: a lane per row); lanes past ROWS * LPR serve none (lane == false, b == e == 0).
+struct EpTile { int q0, q1, d, lev, b, e; bool lane; };
+template <int ROWS, int LPR>
+__device__ __forceinline__ EpTile ep_tile(const FgCsr &csr, int ndst, int tile)
+{
+  EpTile T;
+  const int t = threadIdx.x;
+  const int d0 = tile * ROWS, dl = min(d0 + ROWS, ndst);
+  T.q0 = csr.row_ptr[d0]; T.q1 = csr.row_ptr[dl];
+  T.lane = t < ROWS * LPR;
+  T.d = d0 + t / LPR; T.lev = t % LPR;
+  const int dc = min(T.d, ndst - 1);
+  T.b = 0; T.e = 0;
+  if (T.lane) { T.b = csr.row_ptr[dc]; T.e = csr.row_ptr[dc + 1]; }
+  return T;
+}
+
+// n <= CAP records src[0 .. n) -> sh_e with coalesced 16-byte loads, non-temporal as in k_apply_il (the CSR records are used once
+// per launch).
+// Unrolled form (the one-level kernels): every 16-byte word of the chunk in flight at once (a loop would wait for each load before
+// it issues the next), no branches around the loads.
+template <int TPB, int CAP, typename Entry>
+__device__ __forceinline__ void ep_stage_unrolled(Entry *sh_e, const Entry *src, int n)
+{
+  constexpr int W = sizeof(Entry) / 16, WPL = CAP * W / TPB;
+  const int t = threadIdx.x, nw = n * W;
+  const u4v *g = reinterpret_cast<const u4v *>(src);
+  u4v *l = reinterpret_cast<u4v *>(sh_e);
+  u4v w[WPL];
+#pragma unroll
+  for (int j = 0; j < WPL; j++) w[j] = __builtin_nontemporal_load(g + min(t + TPB * j, nw - 1));
+#pragma unroll
+  for (int j = 0; j < WPL; j++) if (t + TPB * j < nw) l[t + TPB * j] = w[j];
+}
+// Loop form (the 8-level kernels).
+template <int TPB, typename Entry>
+__device__ __forceinline__ void ep_stage_loop(Entry *sh_e, const Entry *src, int n)
+{
+  constexpr int W = sizeof(Entry) / 16;
+  const u4v *g = reinterpret_cast<const u4v *>(src);
+  u4v *l = reinterpret_cast<u4v *>(sh_e);
+  for (int i = threadIdx.x; i < n * W; i += TPB) l[i] = __builtin_nontemporal_load(g + i);
+}
+
+// What one staged exchange cell adds to a row: the product value * area, the area, and whether it counts as touched.  A cell the
+// reference skips with `continue` holds +0.0, +0.0, 0: x + 0.0 == x bit for bit here (no sum is ever -0.0: they start at +0.0).
+struct EpTerm { double p, a; unsigned ok; };
+// The row lane's part of the chunk [c0, c0 + n): the cells of row [b, e) in it, added in CSR order; term(q) reads cell q of the
+// chunk from LDS.
+template <typename F>
+__device__ __forceinline__ void ep_row_add(int b, int e, int c0, int n, double &acc, double &asum, unsigned &touched, F term)
+{
+  const int qa = max(b, c0) - c0, qb = min(e, c0 + n) - c0;
+  int q = qa;
+  for (; q + 8 <= qb; q += 8) {                            // (long rows: eight LDS reads in flight, then the adds in CSR order)
+    EpTerm c[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) c[k] = term(q + k);
+#pragma unroll
+    for (int k = 0; k < 8; k++) { acc += c[k].p; asum += c[k].a; touched |= c[k].ok; }
+  }
+  for (; q < qb; q++) { const EpTerm c = term(q); acc += c.p; asum += c.a; touched |= c.ok; }
+}
+
+// conserve_interp.c:815-839: the row's sums -> its global-sum term (rs) and its output value
+__device__ __forceinline__ double apply_finish(double acc, double asum, bool touched, double missing, double &rs)
+{
+  rs = (asum > 0) ? acc : 0.0;                                 // :815-819
+  if (asum > 0) return acc / asum;                             // :831-839
+  return touched ? 0.0 : missing;
+}
+// the same with cell_methods = sum (:821-830) and --target_grid (asum_t: the plain exchange-cell areas of row d)
+__device__ __forceinline__ double apply_finish_ex(const FgApplyEx &o, int d, double acc, double asum, double asum_t, bool touched, double &rs)
+{
+  if (o.sum) {
+    rs = (asum > 0) ? acc : 0.0;
+    return (asum == 0) ? (touched ? 0.0 : o.missing) : acc;
+  }
+  double r = apply_finish(acc, asum, touched, o.missing, rs);
+  if (o.cell_area_out && r != o.missing) r *= (asum_t / o.cell_area_out[d]);
+  return r;
+}
+
 // Single level, level-major fields (also the has_missing path): one thread per destination cell.
 template <int ORDER, bool MISSING>
 __global__ __launch_bounds__(256) void k_apply1(int ndst, FgCsr csr, const double *f, const double *px, const double *py,
@@ -277,11 +373,9 @@ __global__ __launch_bounds__(256) void k_apply1(int ndst, FgCsr csr, const doubl
     asum += a;
     touched = 1;
   }
-  if (row_sum) row_sum[d] = (asum > 0) ? acc : 0.0;           // conserve_interp.c:815-819
-  double r;                                                   // :831-839
-  if (asum > 0) r = acc / asum;
-  else if (touched) r = 0.0;
-  else r = missing;
+  double rs;
+  const double r = apply_finish(acc, asum, touched != 0, missing, rs);
+  if (row_sum) row_sum[d] = rs;
   out[d] = r;
 }
 
@@ -298,39 +392,20 @@ template <int ORDER, bool MISSING, int TPB, int CAP, int ROWS>
 __global__ __launch_bounds__(TPB) void k_apply_ep1(int ndst, FgCsr csr, const double *f, const double *px, const double *py, const int *gmask,
                                                     double missing, double *out, double *row_sum, int xcd_band)
 {
-  typedef typename std::conditional<ORDER == 2, FgCsrEntry2, FgCsrEntry1>::type Entry;
-  typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-  constexpr int W = sizeof(Entry) / 16, PASS = CAP / TPB;
+  typedef CsrEntry<ORDER> Entry;
+  constexpr int PASS = CAP / TPB;
   static_assert(ROWS <= TPB && CAP % TPB == 0, "tile shape");
   __shared__ __attribute__((aligned(16))) Entry sh_e[CAP];
   double *sh_p = reinterpret_cast<double *>(sh_e), *sh_a = sh_p + CAP;       // the products take the records' place (2 * 8 <= sizeof(Entry))
   __shared__ unsigned char sh_fl[CAP];
   const int t = threadIdx.x;
-  const int d0 = d_xcd_block(blockIdx.x, gridDim.x, xcd_band) * ROWS;
-  const int dl = min(d0 + ROWS, ndst);
-  const int q0 = csr.row_ptr[d0], q1 = csr.row_ptr[dl];
-  const int d = d0 + t, dc = min(d, ndst - 1);
-  int b = 0, e = 0;
-  if (t < ROWS) { b = csr.row_ptr[dc]; e = csr.row_ptr[dc + 1]; }
-  const Entry *src = (ORDER == 2) ? (const Entry *)csr.e2 : (const Entry *)csr.e1;
+  const EpTile T = ep_tile<ROWS, 1>(csr, ndst, d_xcd_block(blockIdx.x, gridDim.x, xcd_band));
   double acc = 0.0, asum = 0.0;
-  int touched = 0;
-  for (int c0 = q0; c0 < q1; c0 += CAP) {                  // (block-uniform)
-    const int n = min(CAP, q1 - c0);
-    if (c0 > q0) __syncthreads();                          // the previous chunk's products have been added
-    {
-      // every 16-byte word of the chunk in flight at once (a loop would wait for each load before it issues the next), no
-      // branches around the loads
-      const u4v *g = reinterpret_cast<const u4v *>(src + c0);
-      u4v *l = reinterpret_cast<u4v *>(sh_e);
-      constexpr int WPL = CAP * W / TPB;
-      const int nw = n * W;
-      u4v w[WPL];
-#pragma unroll
-      for (int j = 0; j < WPL; j++) w[j] = __builtin_nontemporal_load(g + min(t + TPB * j, nw - 1));
-#pragma unroll
-      for (int j = 0; j < WPL; j++) if (t + TPB * j < nw) l[t + TPB * j] = w[j];
-    }
+  unsigned touched = 0;
+  for (int c0 = T.q0; c0 < T.q1; c0 += CAP) {              // (block-uniform)
+    const int n = min(CAP, T.q1 - c0);
+    if (c0 > T.q0) __syncthreads();                        // the previous chunk's products have been added
+    ep_stage_unrolled<TPB, CAP>(sh_e, csr_entries<ORDER>(csr) + c0, n);
     __syncthreads();
     Entry E[PASS];
     double v[PASS], gxv[PASS], gyv[PASS];
@@ -363,28 +438,13 @@ __global__ __launch_bounds__(TPB) void k_apply_ep1(int ndst, FgCsr csr, const do
       }
     }
     __syncthreads();
-    if (t < ROWS) {
-      const int qa = max(b, c0) - c0, qb = min(e, c0 + n) - c0;
-      int q = qa;
-      for (; q + 8 <= qb; q += 8) {                        // (long rows: eight LDS reads in flight, then the adds in CSR order)
-        double pp[8], aa[8];
-        unsigned ff = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) { pp[k] = sh_p[q + k]; aa[k] = sh_a[q + k]; ff |= sh_fl[q + k]; }
-#pragma unroll
-        for (int k = 0; k < 8; k++) { acc += pp[k]; asum += aa[k]; }
-        touched |= (int)ff;
-      }
-      for (; q < qb; q++) { acc += sh_p[q]; asum += sh_a[q]; touched |= sh_fl[q]; }
-    }
+    if (T.lane) ep_row_add(T.b, T.e, c0, n, acc, asum, touched, [&](int q) { return EpTerm{sh_p[q], sh_a[q], sh_fl[q]}; });
   }
-  if (t >= ROWS || d >= ndst) return;
-  if (row_sum) row_sum[d] = (asum > 0) ? acc : 0.0;           // conserve_interp.c:815-819
-  double r;                                                   // :831-839
-  if (asum > 0) r = acc / asum;
-  else if (touched) r = 0.0;
-  else r = missing;
-  out[d] = r;
+  if (!T.lane || T.d >= ndst) return;
+  double rs;
+  const double r = apply_finish(acc, asum, touched != 0, missing, rs);
+  if (row_sum) row_sum[T.d] = rs;
+  out[T.d] = r;
 }
 
 // NB levels at once, fields interleaved [cell][NB]: every CSR entry is read once for NB levels and
@@ -438,16 +498,9 @@ __global__ __launch_bounds__(256) void k_apply_ex(int ndst, FgCsr csr, const dou
     asum += a;
     if (!MONO) touched = 1;
   }
-  if (row_sum) row_sum[d] = (asum > 0) ? acc : 0.0;             // :815-819
-  double r = acc;
-  if (o.sum) {                                                  // :821-830
-    if (asum == 0) r = touched ? 0.0 : o.missing;
-  } else {
-    if (asum > 0) r = acc / asum;                               // :832-839
-    else if (touched) r = 0.0;
-    else r = o.missing;
-    if (o.cell_area_out && r != o.missing) r *= (asum_t / o.cell_area_out[d]);
-  }
+  double rs;
+  const double r = apply_finish_ex(o, d, acc, asum, asum_t, touched != 0, rs);
+  if (row_sum) row_sum[d] = rs;
   out[d] = r;
 }
 
@@ -459,38 +512,21 @@ template <int ORDER, bool MONO, int TPB, int CAP, int ROWS>
 __global__ __launch_bounds__(TPB) void k_apply_epx(int ndst, FgCsr csr, const double *f, const double *px, const double *py,
                                                     FgApplyEx o, double *out, double *row_sum, int *err, int xcd_band)
 {
-  typedef typename std::conditional<ORDER == 2, FgCsrEntry2, FgCsrEntry1>::type Entry;
-  typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-  constexpr int W = sizeof(Entry) / 16, PASS = CAP / TPB;
+  typedef CsrEntry<ORDER> Entry;
+  constexpr int PASS = CAP / TPB;
   static_assert(ROWS <= TPB && CAP % TPB == 0, "tile shape");
   __shared__ __attribute__((aligned(16))) double sh_raw[CAP * 4];     // CSR records (<= 32 B each), then [3][CAP] products
   Entry *sh_e = reinterpret_cast<Entry *>(sh_raw);
   double *sh_t = sh_raw, *sh_p = sh_raw + CAP, *sh_a = sh_raw + 2 * CAP;
   __shared__ unsigned char sh_fl[CAP];
   const int t = threadIdx.x;
-  const int d0 = d_xcd_block(blockIdx.x, gridDim.x, xcd_band) * ROWS;
-  const int dl = min(d0 + ROWS, ndst);
-  const int q0 = csr.row_ptr[d0], q1 = csr.row_ptr[dl];
-  const int d = d0 + t, dc = min(d, ndst - 1);
-  int b = 0, e = 0;
-  if (t < ROWS) { b = csr.row_ptr[dc]; e = csr.row_ptr[dc + 1]; }
-  const Entry *src = (ORDER == 2) ? (const Entry *)csr.e2 : (const Entry *)csr.e1;
+  const EpTile T = ep_tile<ROWS, 1>(csr, ndst, d_xcd_block(blockIdx.x, gridDim.x, xcd_band));
   double acc = 0.0, asum = 0.0, asum_t = 0.0;
   int touched = 0;
-  for (int c0 = q0; c0 < q1; c0 += CAP) {                  // (block-uniform)
-    const int n = min(CAP, q1 - c0);
-    if (c0 > q0) __syncthreads();
-    {
-      const u4v *g = reinterpret_cast<const u4v *>(src + c0);
-      u4v *l = reinterpret_cast<u4v *>(sh_e);
-      constexpr int WPL = CAP * W / TPB;
-      const int nw = n * W;
-      u4v w[WPL];
-#pragma unroll
-      for (int j = 0; j < WPL; j++) w[j] = __builtin_nontemporal_load(g + min(t + TPB * j, nw - 1));
-#pragma unroll
-      for (int j = 0; j < WPL; j++) if (t + TPB * j < nw) l[t + TPB * j] = w[j];
-    }
+  for (int c0 = T.q0; c0 < T.q1; c0 += CAP) {              // (block-uniform)
+    const int n = min(CAP, T.q1 - c0);
+    if (c0 > T.q0) __syncthreads();
+    ep_stage_unrolled<TPB, CAP>(sh_e, csr_entries<ORDER>(csr) + c0, n);
     __syncthreads();
     double tq[PASS], pp[PASS], aa[PASS];
     unsigned char fl[PASS];
@@ -530,23 +566,16 @@ __global__ __launch_bounds__(TPB) void k_apply_epx(int ndst, FgCsr csr, const do
       if (i < n) { sh_t[i] = tq[j]; sh_p[i] = pp[j]; sh_a[i] = aa[j]; sh_fl[i] = fl[j]; }
     }
     __syncthreads();
-    if (t < ROWS) {
-      const int qa = max(b, c0) - c0, qb = min(e, c0 + n) - c0;
+    if (T.lane) {   // three sums, a plain loop: on ep_row_add (8 reads, then 8 adds) the kernel takes 15-20 VGPRs more, ORDER 2 drops to 6 waves
+      const int qa = max(T.b, c0) - c0, qb = min(T.e, c0 + n) - c0;
       for (int q = qa; q < qb; q++) { asum_t += sh_t[q]; acc += sh_p[q]; asum += sh_a[q]; touched |= sh_fl[q]; }
     }
   }
-  if (t >= ROWS || d >= ndst) return;
-  if (row_sum) row_sum[d] = (asum > 0) ? acc : 0.0;             // :815-819
-  double r = acc;
-  if (o.sum) {                                                  // :821-830
-    if (asum == 0) r = touched ? 0.0 : o.missing;
-  } else {
-    if (asum > 0) r = acc / asum;                               // :832-839
-    else if (touched) r = 0.0;
-    else r = o.missing;
-    if (o.cell_area_out && r != o.missing) r *= (asum_t / o.cell_area_out[d]);
-  }
-  out[d] = r;
+  if (!T.lane || T.d >= ndst) return;
+  double rs;
+  const double r = apply_finish_ex(o, T.d, acc, asum, asum_t, touched != 0, rs);
+  if (row_sum) row_sum[T.d] = rs;
+  out[T.d] = r;
 }
 
 // :622-645: bounds of the 3x3 halo'd neighbourhood, ignoring missing values
@@ -745,8 +774,7 @@ template <int TPB, int CAP>
 __global__ __launch_bounds__(TPB) void k_apply_ep8(int ndst, FgCsr csr, const double *rec, double missing, double *out, double *row_sum,
                                                     long out_ld, int nb_valid, int xcd_band)
 {
-  constexpr int NB = 8;
-  constexpr int LPR = NB, LV = 1;                          // sum phase: a lane per (row, level); EP_ROWS * NB <= TPB lanes take part
+  constexpr int NB = 8;                                    // sum phase: a lane per (row, level); EP_ROWS * NB <= TPB lanes take part
   static_assert(EP_ROWS * NB <= TPB, "rows per tile");
   constexpr int EPP = TPB / 2, PASS = CAP / EPP;          // gather phase: a lane pair per exchange cell, EPP cells per pass
   // one buffer: the staged CSR records first, then (once every lane holds its records in registers) the products and areas
@@ -754,23 +782,11 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8(int ndst, FgCsr csr, const do
   FgCsrEntry2 *sh_e = reinterpret_cast<FgCsrEntry2 *>(sh_raw);
   double *sh_p = sh_raw, *sh_a = sh_raw + CAP * NB;
   const int t = threadIdx.x;
-  const int d0 = d_xcd_block(blockIdx.x, gridDim.x, xcd_band) * EP_ROWS;
-  const int dl = min(d0 + EP_ROWS, ndst);
-  const int q0 = csr.row_ptr[d0], q1 = csr.row_ptr[dl];
-  const int d = d0 + t / LPR, lev = (t % LPR) * LV;
-  const int dc = min(d, ndst - 1);
-  const int b = csr.row_ptr[dc], e = csr.row_ptr[dc + 1];
-  const int n = q1 - q0, nst = min(n, CAP);
-  {
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    const u4v *g = reinterpret_cast<const u4v *>(csr.e2 + q0);
-    u4v *l = reinterpret_cast<u4v *>(sh_e);
-    for (int i = t; i < nst * 2; i += TPB) l[i] = __builtin_nontemporal_load(g + i);
-  }
+  const EpTile T = ep_tile<EP_ROWS, NB>(csr, ndst, d_xcd_block(blockIdx.x, gridDim.x, xcd_band));
+  const int q0 = T.q0, n = T.q1 - T.q0, lev = T.lev;
+  ep_stage_loop<TPB>(sh_e, csr.e2 + q0, min(n, CAP));
   __syncthreads();
-  double acc[LV], asum = 0.0;
-#pragma unroll
-  for (int k = 0; k < LV; k++) acc[k] = 0.0;
+  double acc = 0.0, asum = 0.0;
   if (n <= CAP) {
     const int h = (t & 1) * 4;                             // four levels per lane of the pair
     VecD<4> fv[PASS], gxv[PASS], gyv[PASS];
@@ -802,44 +818,24 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8(int ndst, FgCsr csr, const do
       }
     }
     __syncthreads();
-    if (d >= ndst || t >= EP_ROWS * NB) return;
-    for (int q = b - q0; q < e - q0; q++) {
-      const VecD<LV> pv = *reinterpret_cast<const VecD<LV> *>(sh_p + q * NB + lev);
-#pragma unroll
-      for (int k = 0; k < LV; k++) acc[k] += pv.v[k];
-      asum += sh_a[q];
-    }
+    if (T.d >= ndst || !T.lane) return;
+    for (int q = T.b - q0; q < T.e - q0; q++) { acc += sh_p[q * NB + lev]; asum += sh_a[q]; }
   } else {
-    if (d >= ndst || t >= EP_ROWS * NB) return;
-    for (int q = b; q < e; q++) {
+    if (T.d >= ndst || !T.lane) return;
+    for (int q = T.b; q < T.e; q++) {
       const int ql = q - q0;
       const FgCsrEntry2 E = (ql < CAP) ? sh_e[ql] : csr.e2[q];
       const double *pf = rec + (size_t)E.idx_g * (3 * NB) + lev;
-      const VecD<LV> fv = *reinterpret_cast<const VecD<LV> *>(pf);
-      const VecD<LV> gxv = *reinterpret_cast<const VecD<LV> *>(pf + NB);
-      const VecD<LV> gyv = *reinterpret_cast<const VecD<LV> *>(pf + 2 * NB);
-#pragma unroll
-      for (int k = 0; k < LV; k++) {
-        double v = (fv.v[k] + gxv.v[k] * E.di + gyv.v[k] * E.dj);
-        acc[k] += v * E.area;
-      }
+      double v = (pf[0] + pf[NB] * E.di + pf[2 * NB] * E.dj);
+      acc += v * E.area;
       asum += E.area;
     }
   }
-  VecD<LV> r, rs;
-#pragma unroll
-  for (int k = 0; k < LV; k++) {
-    rs.v[k] = (asum > 0) ? acc[k] : 0.0;
-    if (asum > 0) r.v[k] = acc[k] / asum;
-    else if (e > b) r.v[k] = 0.0;
-    else r.v[k] = missing;
-  }
-  if (row_sum) *reinterpret_cast<VecD<LV> *>(row_sum + (size_t)d * NB + lev) = rs;
-  if (out_ld > 0) {
-#pragma unroll
-    for (int k = 0; k < LV; k++) if (lev + k < nb_valid) out[(size_t)(lev + k) * out_ld + d] = r.v[k];
-  } else
-    *reinterpret_cast<VecD<LV> *>(out + (size_t)d * NB + lev) = r;
+  double rs;
+  const double r = apply_finish(acc, asum, T.e > T.b, missing, rs);
+  if (row_sum) row_sum[(size_t)T.d * NB + lev] = rs;
+  if (out_ld > 0) { if (lev < nb_valid) out[(size_t)lev * out_ld + T.d] = r; }
+  else out[(size_t)T.d * NB + lev] = r;
 }
 
 // The same for plans with longer rows (fine -> coarse remaps; k_apply_ep8 above is for rows of a few exchange cells): ROWS rows per
@@ -848,45 +844,47 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8(int ndst, FgCsr csr, const do
 // k_apply_il before: C384 -> 2 deg 0.117 ms per 8 levels on records, now 0.037.)  As a loop the kernel needs more registers than
 // k_apply_ep8 -- with 32 rows per tile on C384 -> 0.25 deg it runs in 0.117 ms against 0.083 -- so short rows keep the kernel above.
 // (ORDER 1: `rec` is the interleaved field [cell][8], a 16-byte CSR record and one 64-byte gather per exchange cell.)
-template <int ORDER, int TPB, int CAP, int ROWS>
-__global__ __launch_bounds__(TPB) void k_apply_ep8g(int ndst, FgCsr csr, const double *rec, double missing, double *out, double *row_sum,
-                                                    long out_ld, int nb_valid, int xcd_band)
+//
+// MASKED: eight levels that each carry their own missing values (fg_plan_apply_levels, fg_plan_apply_records_levels,
+// fg_sweep_run_levels).  The reference takes such a field one level per call (fregrid.c:1045-1083; conserve_interp.c:544 forbids
+// has_missing with nz > 1): level k of the output is do_scalar_conserve_interp(nz = 1, has_missing = 1) on level k alone -- per
+// destination cell the exchange cells whose source value differs from `missing` IN THAT LEVEL are summed in CSR order, the result is
+// acc / asum where asum > 0, 0.0 where an exchange cell counted but asum == 0, else `missing` (:562-591, :744-783, :815-839).
+// Here every CSR record is still read once and every gather is a full 64-byte sector; only the validity differs from level to
+// level: the product table keeps ONE area and an 8-bit validity mask per exchange cell, an invalid (exchange cell, level) holds the
+// product +0.0, and the (row, level) lane carries a touched flag beside its two sums.
+//   gbits (ORDER 2): per source cell, bit k set = level k takes the flat value (fregrid_util.c:2203-2215); k_gmask_bits makes them.
+//   out, row_sum: level-major [level][out_ld], levels < nb_valid only.  The tile mapping is the identity (xcd_band is not read).
+template <int ORDER, bool MASKED, int TPB, int CAP, int ROWS>
+__global__ __launch_bounds__(TPB) void k_apply_ep8g(int ndst, FgCsr csr, const double *rec, const unsigned char *gbits, double missing,
+                                                    double *out, double *row_sum, long out_ld, int nb_valid, int xcd_band)
 {
   constexpr int NB = 8;
   constexpr int EPP = TPB / 2, PASS = CAP / EPP;          // gather phase: a lane pair per exchange cell, EPP cells per pass
-  static_assert(ROWS * NB <= TPB, "a lane per (row, level)");
+  static_assert(ROWS * NB <= TPB && (!MASKED || CAP % EPP == 0), "a lane per (row, level)");
   // one buffer: the staged CSR records first, then (once every lane holds its records in registers) the products and areas
   __shared__ __attribute__((aligned(16))) double sh_raw[CAP * (NB + 1)];
-  typedef typename std::conditional<ORDER == 2, FgCsrEntry2, FgCsrEntry1>::type Entry;
-  constexpr int W = sizeof(Entry) / 16;
+  __shared__ unsigned char sh_vm[MASKED ? CAP * 2 : 1];    // MASKED: validity of levels 0-3 and 4-7 of every staged exchange cell
+  typedef CsrEntry<ORDER> Entry;
   Entry *sh_e = reinterpret_cast<Entry *>(sh_raw);
   double *sh_p = sh_raw, *sh_a = sh_raw + CAP * NB;
   const int t = threadIdx.x;
-  const int d0 = d_xcd_block(blockIdx.x, gridDim.x, xcd_band) * ROWS;
-  const int dl = min(d0 + ROWS, ndst);
-  const int q0 = csr.row_ptr[d0], q1 = csr.row_ptr[dl];
-  const bool sumlane = t < ROWS * NB;                      // lane (row, level) of the sum phase
-  const int d = d0 + t / NB, lev = t % NB;
-  const int dc = min(d, ndst - 1);
-  int b = 0, e = 0;
-  if (sumlane) { b = csr.row_ptr[dc]; e = csr.row_ptr[dc + 1]; }
+  const EpTile T = ep_tile<ROWS, NB>(csr, ndst, MASKED ? (int)blockIdx.x : d_xcd_block(blockIdx.x, gridDim.x, xcd_band));
+  const int lev = T.lev, vsel = lev >> 2, vbit = lev & 3;
   double acc = 0.0, asum = 0.0;
-  for (int c0 = q0; c0 < q1; c0 += CAP) {                  // (block-uniform)
-    const int n = min(CAP, q1 - c0);
-    if (c0 > q0) __syncthreads();                          // the previous chunk's products have been added
-    {
-      typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-      const Entry *src = (ORDER == 2) ? (const Entry *)csr.e2 : (const Entry *)csr.e1;
-      const u4v *g = reinterpret_cast<const u4v *>(src + c0);
-      u4v *l = reinterpret_cast<u4v *>(sh_e);
-      for (int i = t; i < n * W; i += TPB) l[i] = __builtin_nontemporal_load(g + i);
-    }
+  unsigned touched = 0;
+  for (int c0 = T.q0; c0 < T.q1; c0 += CAP) {              // (block-uniform)
+    const int n = min(CAP, T.q1 - c0);
+    if (c0 > T.q0) __syncthreads();                        // the previous chunk's products have been added
+    ep_stage_loop<TPB>(sh_e, csr_entries<ORDER>(csr) + c0, n);
     __syncthreads();
     const int h = (t & 1) * 4;                             // four levels per lane of the pair
     VecD<4> fv[PASS], gxv[PASS], gyv[PASS];
     Entry E[PASS];
+    unsigned gb[PASS];
 #pragma unroll
     for (int j = 0; j < PASS; j++) {
+      gb[j] = 0;
       if (EPP * j < n) {                                   // (block-uniform)
         const int i = min(t / 2 + EPP * j, n - 1);
         E[j] = sh_e[i];
@@ -895,6 +893,7 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8g(int ndst, FgCsr csr, const d
           fv[j] = *reinterpret_cast<const VecD<4> *>(pf);
           gxv[j] = *reinterpret_cast<const VecD<4> *>(pf + NB);
           gyv[j] = *reinterpret_cast<const VecD<4> *>(pf + 2 * NB);
+          if constexpr (MASKED) gb[j] = gbits[E[j].idx_g];
         } else
           fv[j] = *reinterpret_cast<const VecD<4> *>(rec + (size_t)E[j].idx_f * NB + h);
       }
@@ -905,39 +904,47 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8g(int ndst, FgCsr csr, const d
       const int i = t / 2 + EPP * j;
       if (EPP * j < n && i < n) {
         VecD<4> pv;
+        unsigned vm = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           double v = fv[j].v[k];
-          if constexpr (ORDER == 2) v = (v + gxv[j].v[k] * E[j].di + gyv[j].v[k] * E[j].dj);
-          pv.v[k] = v * E[j].area;
+          bool ok = true;
+          if constexpr (MASKED) ok = !(v == missing);      // `if (data == missing) continue`
+          if constexpr (ORDER == 2) { if (!((gb[j] >> (h + k)) & 1u)) v = (v + gxv[j].v[k] * E[j].di + gyv[j].v[k] * E[j].dj); }
+          pv.v[k] = ok ? v * E[j].area : 0.0;
+          vm |= (ok ? 1u : 0u) << k;
         }
         *reinterpret_cast<VecD<4> *>(sh_p + i * NB + h) = pv;
+        if constexpr (MASKED) sh_vm[i * 2 + (t & 1)] = (unsigned char)vm;
         if (h == 0) sh_a[i] = E[j].area;
       }
     }
     __syncthreads();
-    if (sumlane) {
-      const int qa = max(b, c0) - c0, qb = min(e, c0 + n) - c0;
-      int q = qa;
-      for (; q + 8 <= qb; q += 8) {                        // (long rows: eight LDS reads in flight, then the adds in CSR order)
-        double pp[8], aa[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) { pp[k] = sh_p[(q + k) * NB + lev]; aa[k] = sh_a[q + k]; }
-#pragma unroll
-        for (int k = 0; k < 8; k++) { acc += pp[k]; asum += aa[k]; }
-      }
-      for (; q < qb; q++) { acc += sh_p[q * NB + lev]; asum += sh_a[q]; }
-    }
+    if (T.lane)
+      ep_row_add(T.b, T.e, c0, n, acc, asum, touched, [&](int q) {
+        if constexpr (MASKED) {
+          const unsigned ok = (sh_vm[q * 2 + vsel] >> vbit) & 1u;
+          return EpTerm{sh_p[q * NB + lev], ok ? sh_a[q] : 0.0, ok};
+        } else
+          return EpTerm{sh_p[q * NB + lev], sh_a[q], 0u};
+      });
   }
-  if (!sumlane || d >= ndst) return;
-  const double rs = (asum > 0) ? acc : 0.0;
-  double r;
-  if (asum > 0) r = acc / asum;
-  else if (e > b) r = 0.0;
-  else r = missing;
-  if (row_sum) row_sum[(size_t)d * NB + lev] = rs;
-  if (out_ld > 0) { if (lev < nb_valid) out[(size_t)lev * out_ld + d] = r; }
-  else out[(size_t)d * NB + lev] = r;
+  if (!T.lane || T.d >= ndst || (MASKED && lev >= nb_valid)) return;
+  double rs;
+  const double r = apply_finish(acc, asum, MASKED ? touched != 0 : T.e > T.b, missing, rs);
+  if (row_sum) row_sum[MASKED ? (size_t)lev * out_ld + T.d : (size_t)T.d * NB + lev] = rs;
+  if (MASKED || out_ld > 0) { if (lev < nb_valid) out[(size_t)lev * out_ld + T.d] = r; }
+  else out[(size_t)T.d * NB + lev] = r;
+}
+
+// grad_mask int [nb][ncells] (fg_c2l_gradient) -> one byte per source cell, bit k = level k
+__global__ __launch_bounds__(256) void k_gmask_bits(long n, const int *gmask, long ld, int nb, unsigned char *bits)
+{
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n) return;
+  unsigned m = 0;
+  for (int k = 0; k < nb; k++) m |= (gmask[(size_t)k * ld + c] != 0 ? 1u : 0u) << k;
+  bits[c] = (unsigned char)m;
 }
 
 // [nb][n] (level-major, row stride ld) <-> [n][NB] interleaved
@@ -1108,19 +1115,31 @@ void fgd_src_field_index(int order, const FgTile *tiles_dev, int ntiles, int nsr
   if (nsrc > 0) k_src_field_index<<<nblk(nsrc, 256), 256, 0, st>>>(order, tiles_dev, ntiles, nsrc, src_idx_f);
 }
 extern int g_apply_xcd, g_apply_ep;
+// Rows per tile of the chunked entry-parallel kernels by the mean row length m = nx / ndst: R0 rows for rows of a few exchange
+// cells (a tile's cells mostly fit one chunk), fewer rows the longer they are; a single row of any length walks its chunks alone.
+// launch(R) gets the choice as a std::integral_constant.
+template <int V> using Int = std::integral_constant<int, V>;
+template <int R0, int R1, int R2, int R3, typename F>
+static void by_row_length(long m, F launch)
+{
+  if (m <= 6) launch(Int<R0>()); else if (m <= 24) launch(Int<R1>()); else if (m <= 96) launch(Int<R2>()); else launch(Int<R3>());
+}
+// d_xcd_block's mode for the 8-level entry-parallel kernels: the XCD chunks are twice as many tiles as k_apply_il's
+static int xcd_chunk8() { return g_apply_xcd >= 2 ? 2 * g_apply_xcd : g_apply_xcd; }
+
 void fgd_apply1(int order, int ndst, FgCsr csr, const double *f, const double *gx, const double *gy, const int *gmask,
                 int has_missing, double missing, double *out, double *row_sum, hipStream_t st, long nx)
 {
   if (ndst <= 0) return;
   if (g_apply_ep && nx >= 0) {                             // the entry-parallel single-level kernel; rows per tile by the mean row length
-    const long m = nx / ndst;
-    const int xb = g_apply_xcd;
-#define EP1(O_, M_, R_) k_apply_ep1<O_, M_, 256, 512, R_><<<nblk(ndst, R_), 256, 0, st>>>(ndst, csr, f, gx, gy, gmask, missing, out, row_sum, xb)
-#define EP1R(O_, M_) do { if (m <= 6) EP1(O_, M_, 64); else if (m <= 24) EP1(O_, M_, 16); else if (m <= 96) EP1(O_, M_, 4); else EP1(O_, M_, 1); } while (0)
-    if (order == 2) { if (has_missing) EP1R(2, true); else EP1R(2, false); }
-    else            { if (has_missing) EP1R(1, true); else EP1R(1, false); }
-#undef EP1R
-#undef EP1
+    auto ep1 = [&](auto O, auto M) {
+      by_row_length<64, 16, 4, 1>(nx / ndst, [&](auto R) {
+        k_apply_ep1<decltype(O)::value, decltype(M)::value, 256, 512, decltype(R)::value><<<nblk(ndst, decltype(R)::value), 256, 0, st>>>(
+            ndst, csr, f, gx, gy, gmask, missing, out, row_sum, g_apply_xcd);
+      });
+    };
+    if (order == 2) { if (has_missing) ep1(Int<2>(), std::true_type()); else ep1(Int<2>(), std::false_type()); }
+    else            { if (has_missing) ep1(Int<1>(), std::true_type()); else ep1(Int<1>(), std::false_type()); }
     return;
   }
   int grid = nblk(ndst, 256);
@@ -1133,7 +1152,17 @@ void fgd_apply1(int order, int ndst, FgCsr csr, const double *f, const double *g
   }
 }
 
-extern int g_apply_xcd;
+// k_apply_ep8g with R0 / R1 / R2 / R3 rows per tile (the unmasked callers come here with rows longer than 6 only)
+template <int ORDER, bool MASKED, int CAP, int R0, int R1, int R2, int R3>
+static void apply_ep8g(int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing, double *out,
+                       double *row_sum, long out_ld, int nb_valid, int xb, hipStream_t st)
+{
+  by_row_length<R0, R1, R2, R3>(nx / ndst, [&](auto R) {
+    k_apply_ep8g<ORDER, MASKED, 256, CAP, decltype(R)::value><<<nblk(ndst, decltype(R)::value), 256, 0, st>>>(
+        ndst, csr, rec, gbits, missing, out, row_sum, out_ld, nb_valid, xb);
+  });
+}
+
 template <int NB, int V>
 static void apply_il_nb(int order, int ndst, FgCsr csr, const double *f, const double *gx, const double *gy, double missing,
                         double *out, double *row_sum, long out_ld, int nb_valid, hipStream_t st)
@@ -1154,11 +1183,7 @@ void fgd_apply_il(int order, int nb, int ndst, FgCsr csr, const double *f, const
 {
   if (ndst <= 0) return;
   if (order == 1 && nb == 8 && g_apply_ep && nx > 6L * ndst) {   // first order, long rows (fine -> coarse): chunked entry-parallel tiles
-    const long m = nx / ndst;
-    const int xb = g_apply_xcd >= 2 ? 2 * g_apply_xcd : g_apply_xcd;
-#define EP8O1(R_) k_apply_ep8g<1, 256, 256, R_><<<nblk(ndst, R_), 256, 0, st>>>(ndst, csr, f, missing, out, row_sum, out_ld, nb_valid, xb)
-    if (m <= 24) EP8O1(8); else if (m <= 96) EP8O1(2); else EP8O1(1);
-#undef EP8O1
+    apply_ep8g<1, false, 256, 8, 8, 2, 1>(ndst, nx, csr, f, nullptr, missing, out, row_sum, out_ld, nb_valid, xcd_chunk8(), st);
     return;
   }
   const int v = g_apply_vec ? g_apply_vec : (nb >= 8 ? 4 : 2);
@@ -1179,18 +1204,25 @@ void fgd_apply_il_merged(int nb, int ndst, long nx, FgCsr csr, const double *rec
 #define APM(NB_, V_) k_apply_il<2, NB_, V_, true><<<nblk(ndst, 256 / (NB_ / V_)), 256, 0, st>>>(ndst, csr, rec, nullptr, nullptr, missing, out, row_sum, out_ld, nb_valid, g_apply_xcd)
   if (nb == 16) APM(16, 4);
   else if (nb == 8 && g_apply_ep && nx <= 6L * ndst)       // rows of ~4 exchange cells: a tile's cells fit the product table
-    k_apply_ep8<256, 256><<<nblk(ndst, EP_ROWS), 256, 0, st>>>(ndst, csr, rec, missing, out, row_sum, out_ld, nb_valid, g_apply_xcd >= 2 ? 2 * g_apply_xcd : g_apply_xcd);
-  else if (nb == 8 && g_apply_ep) {                        // longer rows: chunked tiles, rows per tile by the mean row length
-    const long m = nx / ndst;
-    const int xb = g_apply_xcd >= 2 ? 2 * g_apply_xcd : g_apply_xcd;
-#define EP8(R_) k_apply_ep8g<2, 256, 256, R_><<<nblk(ndst, R_), 256, 0, st>>>(ndst, csr, rec, missing, out, row_sum, out_ld, nb_valid, xb)
-    if (m <= 24) EP8(8); else if (m <= 96) EP8(2); else EP8(1);
-#undef EP8
-  }
+    k_apply_ep8<256, 256><<<nblk(ndst, EP_ROWS), 256, 0, st>>>(ndst, csr, rec, missing, out, row_sum, out_ld, nb_valid, xcd_chunk8());
+  else if (nb == 8 && g_apply_ep)                          // longer rows: chunked tiles, rows per tile by the mean row length
+    apply_ep8g<2, false, 256, 8, 8, 2, 1>(ndst, nx, csr, rec, nullptr, missing, out, row_sum, out_ld, nb_valid, xcd_chunk8(), st);
   else if (nb == 8) { if (g_apply_vec == 2) APM(8, 2); else APM(8, 4); }   // 4 levels per lane: 0.0875 ms against 0.0936 with 2 (1440x720, 8 levels, chunked tiles)
   else if (nb == 4) APM(4, 2);
   else APM(2, 2);
 #undef APM
+}
+// eight levels with missing values of their own, fields and output as k_apply_ep8g's MASKED form takes them
+void fgd_apply_levels8(int order, int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing, double *out,
+                       double *row_sum, long ld, int nb_valid, hipStream_t st)
+{
+  if (ndst <= 0) return;
+  if (order == 2) apply_ep8g<2, true, FG_LEVELS_CAP, 32, 8, 2, 1>(ndst, nx, csr, rec, gbits, missing, out, row_sum, ld, nb_valid, 0, st);
+  else            apply_ep8g<1, true, FG_LEVELS_CAP, 32, 8, 2, 1>(ndst, nx, csr, rec, gbits, missing, out, row_sum, ld, nb_valid, 0, st);
+}
+void fgd_gmask_bits(long n, const int *gmask, long ld, int nb, unsigned char *bits, hipStream_t st)
+{
+  if (n > 0) k_gmask_bits<<<nblk(n, 256), 256, 0, st>>>(n, gmask, ld, nb, bits);
 }
 void fgd_merge3(int nb_pad, long n, const int *src_idx_f, const double *f, long ld_f, const double *gx, const double *gy, long ld_g,
                 int nb_valid, double *out, hipStream_t st)
@@ -1241,14 +1273,14 @@ void fgd_apply_ex(int order, int ndst, FgCsr csr, const double *f, const double 
 {
   if (ndst <= 0) return;
   if (g_apply_ep && nx >= 0) {                             // entry-parallel; rows per tile by the mean row length
-    const long m = nx / ndst;
-    const int xb = g_apply_xcd;
-#define EPX(O_, M_, R_) k_apply_epx<O_, M_, 256, 512, R_><<<nblk(ndst, R_), 256, 0, st>>>(ndst, csr, f, gx, gy, o, out, row_sum, err, xb)
-#define EPXR(O_, M_) do { if (m <= 6) EPX(O_, M_, 64); else if (m <= 24) EPX(O_, M_, 16); else if (m <= 96) EPX(O_, M_, 4); else EPX(O_, M_, 1); } while (0)
-    if (order == 2) { if (o.xdata) EPXR(2, true); else EPXR(2, false); }
-    else EPXR(1, false);
-#undef EPXR
-#undef EPX
+    auto epx = [&](auto O, auto M) {
+      by_row_length<64, 16, 4, 1>(nx / ndst, [&](auto R) {
+        k_apply_epx<decltype(O)::value, decltype(M)::value, 256, 512, decltype(R)::value><<<nblk(ndst, decltype(R)::value), 256, 0, st>>>(
+            ndst, csr, f, gx, gy, o, out, row_sum, err, g_apply_xcd);
+      });
+    };
+    if (order == 2) { if (o.xdata) epx(Int<2>(), std::true_type()); else epx(Int<2>(), std::false_type()); }
+    else epx(Int<1>(), std::false_type());
     return;
   }
   int grid = nblk(ndst, 256);

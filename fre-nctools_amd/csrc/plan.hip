@@ -1721,6 +1721,32 @@ extern int g_apply_xcd;
 extern "C" void fg_set_apply_xcd(int on) { g_apply_xcd = on < 0 ? 0 : on; }       // tuning hook: tile -> XCD mapping of the sweep (0 identity, 1 banded, C >= 2 chunked)
 extern "C" void fg_set_apply_vec(int v) { g_apply_vec = (v >= 4) ? 4 : (v >= 2 ? 2 : (v == 1 ? 1 : 0)); }   // tuning hook (scripts/)
 
+// ------------------------------------------------------------------- what the apply entry points share
+// the PH_APPLY span of one call's launches on stream st, for fg_plan_phase_ms
+static void apply_span_begin(fg_plan *pl, hipStream_t st)
+{
+  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, st);     // (a long sweep loop must not pile up timing events)
+  pl->apply_pt.begin(PH_APPLY);
+}
+static void apply_span_end(fg_plan *pl)
+{
+  pl->apply_pt.end();
+  if (pl->apply_pt.on) pl->apply_spans++;
+}
+
+// levels per source cell of the interleaved layouts that hold nz <= 8 levels
+static int levels_pad(int nz) { return nz > 4 ? 8 : (nz > 2 ? 4 : 2); }
+
+// row sums of one launch: [cell][16] or [level <= 8][cell]
+static int ensure_il_rs(fg_plan *pl)
+{
+  if (!pl->il_rs) {
+    pl->il_rs = pl->alloc<double>((size_t)pl->ndst * 16);
+    if (!pl->il_rs) return fail(FG_ERR_HIP, "out of device memory");
+  }
+  return 0;
+}
+
 static int ensure_il_scratch(fg_plan *pl, bool want_rs)
 {
   if (!pl->il_out) {
@@ -1729,11 +1755,16 @@ static int ensure_il_scratch(fg_plan *pl, bool want_rs)
     else pl->il_f = pl->alloc<double>((size_t)pl->f_stride * 8);
     if (!pl->il_out || (pl->order == 2 ? !pl->il_m : !pl->il_f)) return fail(FG_ERR_HIP, "out of device memory");
   }
-  if (want_rs && !pl->il_rs) {
-    pl->il_rs = pl->alloc<double>((size_t)pl->ndst * 16);
-    if (!pl->il_rs) return fail(FG_ERR_HIP, "out of device memory");
-  }
-  return 0;
+  return want_rs ? ensure_il_rs(pl) : 0;
+}
+
+// levels [0, nbv) of the first-order field f (level-major, stride f_stride) -> il_f [f_stride][nbp]
+static void interleave_field(fg_plan *pl, const double *f, int nbp, int nbv, hipStream_t st)
+{
+  const double *ins[3] = {f, nullptr, nullptr};
+  double *outs[3] = {pl->il_f, nullptr, nullptr};
+  const long lds[3] = {pl->f_stride, 0, 0}, ns[3] = {pl->f_stride, 0, 0};
+  fgd_interleave3(nbp, 1, ins, lds, ns, outs, nbv, st);
 }
 
 extern "C" int fg_plan_apply(fg_plan *pl, const double *data, const double *grad_x, const double *grad_y,
@@ -1759,8 +1790,7 @@ extern "C" int fg_plan_apply(fg_plan *pl, const double *data, const double *grad
     pl->row_sum_cap = ndst;
   }
   if (nz > 1) { int rc = ensure_il_scratch(pl, gsum_out != nullptr); if (rc) return rc; }
-  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, st);     // (a long sweep loop must not pile up timing events)
-  pl->apply_pt.begin(PH_APPLY);
+  apply_span_begin(pl, st);
   int nred = 0;
   for (int k0 = 0; k0 < nz; k0 += 8) {
     const int nbv = (nz - k0 < 8) ? nz - k0 : 8;
@@ -1772,24 +1802,20 @@ extern "C" int fg_plan_apply(fg_plan *pl, const double *data, const double *grad
       fgd_apply1(pl->order, ndst, pl->csr, f, gx, gy, grad_mask, has_missing, miss, o, gsum_out ? pl->row_sum : nullptr, st, pl->nx);
       if (gsum_out) fgd_reduce_sum(pl->row_sum, ndst, pl->red_partial, pl->red_result + nred++, st);
     } else {
-      const int nbp = nbv > 4 ? 8 : (nbv > 2 ? 4 : 2);
+      const int nbp = levels_pad(nbv);
       double *rs = gsum_out ? pl->il_rs : nullptr;
       if (pl->order == 2) {
         // field + gradients of the chunk -> one record per source cell, then the sweep writes level-major directly
         fgd_merge3(nbp, pl->nsrc, pl->src_idx_f, f, pl->f_stride, gx, gy, pl->nsrc, nbv, pl->il_m, st);
         fgd_apply_il_merged(nbp, ndst, pl->nx, pl->csr, pl->il_m, miss, o, rs, (long)ndst, nbv, st);
       } else {
-        const double *ins[3] = {f, nullptr, nullptr};
-        double *outs[3] = {pl->il_f, nullptr, nullptr};
-        const long lds[3] = {pl->f_stride, 0, 0}, ns[3] = {pl->f_stride, 0, 0};
-        fgd_interleave3(nbp, 1, ins, lds, ns, outs, nbv, st);
+        interleave_field(pl, f, nbp, nbv, st);
         fgd_apply_il(1, nbp, ndst, pl->csr, pl->il_f, nullptr, nullptr, miss, o, rs, (long)ndst, nbv, st, pl->nx);
       }
       if (gsum_out) fgd_reduce_sum(pl->il_rs, (long)ndst * nbp, pl->red_partial, pl->red_result + nred++, st);
     }
   }
-  pl->apply_pt.end();
-  if (pl->apply_pt.on) pl->apply_spans++;
+  apply_span_end(pl);
   if (gsum_out) {
     double parts[256];
     HIPCHK(hipMemcpyAsync(parts, pl->red_result, nred * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1811,17 +1837,12 @@ extern "C" int fg_plan_apply_records(fg_plan *pl, int nz, const double *rec, dou
   if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_plan_apply_records: 1 to 8 levels per call");
   HIPCHK(hipSetDevice(pl->device));
   hipStream_t st = pl->stream;
-  const int ndst = pl->ndst, nbp = nz > 4 ? 8 : (nz > 2 ? 4 : 2);
-  if (gsum_out && !pl->il_rs) {
-    pl->il_rs = pl->alloc<double>((size_t)ndst * 16);
-    if (!pl->il_rs) return fail(FG_ERR_HIP, "out of device memory");
-  }
-  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, st);     // (a long sweep loop must not pile up timing events)
-  pl->apply_pt.begin(PH_APPLY);
+  const int ndst = pl->ndst, nbp = levels_pad(nz);
+  if (gsum_out) { int rc = ensure_il_rs(pl); if (rc) return rc; }
+  apply_span_begin(pl, st);
   fgd_apply_il_merged(nbp, ndst, pl->nx, pl->csr, rec, -1.e20, out, gsum_out ? pl->il_rs : nullptr, (long)ndst, nz, st);
   if (gsum_out) fgd_reduce_sum(pl->il_rs, (long)ndst * nbp, pl->red_partial, pl->red_result, st);
-  pl->apply_pt.end();
-  if (pl->apply_pt.on) pl->apply_spans++;
+  apply_span_end(pl);
   if (gsum_out) {
     HIPCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -1832,7 +1853,7 @@ extern "C" int fg_plan_apply_records(fg_plan *pl, int nz, const double *rec, dou
 
 // ------------------------------------------------------------------- levels with missing values of their own
 // The reference's level loop (fregrid.c:1045-1083: do_scalar_conserve_interp(nz = 1, has_missing = 1) per level), eight levels
-// per launch of k_apply_ep8m.  Row sums are kept level-major and reduced level by level with the reduction of the one-level
+// per launch of k_apply_ep8g<MASKED>.  Row sums are kept level-major and reduced level by level with the reduction of the one-level
 // calls, so gsum_out[k] carries the bits fg_plan_apply_ex returns for level k alone.
 extern "C" int fg_plan_levels_capacity(void) { return FG_LEVELS_CAP; }
 int fg_plan_is_finalized(const fg_plan *pl) { return pl && pl->finalized; }      // for sweep.hip
@@ -1844,11 +1865,7 @@ static int levels_scratch(fg_plan *pl, bool want_rs, bool want_il)
     pl->lv_bits = pl->alloc<unsigned char>(pl->nsrc > 0 ? pl->nsrc : 1);
     if (!pl->lv_bits) return fail(FG_ERR_HIP, "out of device memory");
   }
-  if (want_rs && !pl->il_rs) {
-    pl->il_rs = pl->alloc<double>((size_t)pl->ndst * 16);
-    if (!pl->il_rs) return fail(FG_ERR_HIP, "out of device memory");
-  }
-  return 0;
+  return want_rs ? ensure_il_rs(pl) : 0;
 }
 
 // per-level sums of one chunk (il_rs [level][ndst]) -> red_result, handed to the host whenever the 256 result slots are full
@@ -1876,8 +1893,7 @@ extern "C" int fg_plan_apply_levels(fg_plan *pl, const double *data, const doubl
   { int rc = levels_scratch(pl, gsum_out != nullptr, true); if (rc) return rc; }
   hipStream_t st = pl->stream;
   const int ndst = pl->ndst;
-  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, st);
-  pl->apply_pt.begin(PH_APPLY);
+  apply_span_begin(pl, st);
   int nred = 0;
   for (int k0 = 0; k0 < nlev; k0 += 8) {
     const int nbv = (nlev - k0 < 8) ? nlev - k0 : 8;
@@ -1890,16 +1906,12 @@ extern "C" int fg_plan_apply_levels(fg_plan *pl, const double *data, const doubl
       fgd_gmask_bits(pl->nsrc, grad_mask + (size_t)k0 * pl->nsrc, pl->nsrc, nbv, pl->lv_bits, st);
       fgd_apply_levels8(2, ndst, pl->nx, pl->csr, pl->il_m, pl->lv_bits, missing, o, rs, (long)ndst, nbv, st);
     } else {
-      const double *ins[3] = {f, nullptr, nullptr};
-      double *outs[3] = {pl->il_f, nullptr, nullptr};
-      const long lds[3] = {pl->f_stride, 0, 0}, ns[3] = {pl->f_stride, 0, 0};
-      fgd_interleave3(8, 1, ins, lds, ns, outs, nbv, st);
+      interleave_field(pl, f, 8, nbv, st);
       fgd_apply_levels8(1, ndst, pl->nx, pl->csr, pl->il_f, nullptr, missing, o, rs, (long)ndst, nbv, st);
     }
     if (gsum_out) { int rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
   }
-  pl->apply_pt.end();
-  if (pl->apply_pt.on) pl->apply_spans++;
+  apply_span_end(pl);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1915,11 +1927,9 @@ extern "C" int fg_plan_apply_records_levels(fg_plan *pl, int nz, const double *r
   HIPCHK(hipSetDevice(pl->device));
   { int rc = levels_scratch(pl, gsum_out != nullptr, false); if (rc) return rc; }
   hipStream_t st = pl->stream;
-  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, st);
-  pl->apply_pt.begin(PH_APPLY);
+  apply_span_begin(pl, st);
   fgd_apply_levels8(2, pl->ndst, pl->nx, pl->csr, rec, maskbits, missing, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, st);
-  pl->apply_pt.end();
-  if (pl->apply_pt.on) pl->apply_spans++;
+  apply_span_end(pl);
   if (gsum_out) { int nred = 0; int rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
   HIPCHK(hipGetLastError());
   return 0;
@@ -2085,12 +2095,10 @@ extern "C" int fg_plan_apply_interleaved(fg_plan *pl, int nb, const double *data
   if (pl->order == 2 && (!grad_x_il || !grad_y_il)) return fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
   HIPCHK(hipSetDevice(pl->device));
   if (gsum_out) { int rc = ensure_il_scratch(pl, true); if (rc) return rc; }
-  pl->apply_pt.start(g_profiling != 0 && pl->apply_spans < 256, pl->stream);
-  pl->apply_pt.begin(PH_APPLY);
+  apply_span_begin(pl, pl->stream);
   fgd_apply_il(pl->order, nb, pl->ndst, pl->csr, data_il, grad_x_il, grad_y_il, -1.e20, out_il,
                gsum_out ? pl->il_rs : nullptr, 0, nb, pl->stream, pl->nx);
-  pl->apply_pt.end();
-  if (pl->apply_pt.on) pl->apply_spans++;
+  apply_span_end(pl);
   if (gsum_out) {
     fgd_reduce_sum(pl->il_rs, (long)pl->ndst * nb, pl->red_partial, pl->red_result, pl->stream);
     HIPCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, pl->stream));
@@ -2790,14 +2798,12 @@ extern "C" int fg_c2l_gradient(fg_c2l *h, const double *halo_data, int nz, int h
   return 0;
 }
 
-static int records_nb_pad(int nz) { return nz > 4 ? 8 : (nz > 2 ? 4 : 2); }
-
 extern "C" int fg_c2l_records(fg_c2l *h, const double *src, int nz, double *rec)
 {
   if (!h || !src || !rec) return fail(FG_ERR_ARG, "bad argument");
   if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_c2l_records: 1 to 8 levels per call");
   HIPCHK(hipSetDevice(h->device));
-  fgd_c2l_records(h->tiles_dev, h->ntiles, h->ncells, nz, records_nb_pad(nz), src, h->cell_of_dev, (const double *const *)h->geom_dev, rec, h->stream);
+  fgd_c2l_records(h->tiles_dev, h->ntiles, h->ncells, nz, levels_pad(nz), src, h->cell_of_dev, (const double *const *)h->geom_dev, rec, h->stream);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2818,7 +2824,7 @@ extern "C" int fg_c2l_gradient_records(fg_c2l *h, const double *halo_data, int n
   if (!h || !halo_data || !rec) return fail(FG_ERR_ARG, "bad argument");
   if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_c2l_gradient_records: 1 to 8 levels per call");
   HIPCHK(hipSetDevice(h->device));
-  fgd_grad_c2l_rec(h->tiles_dev, h->ntiles, h->ncells, h->F, nz, records_nb_pad(nz), halo_data, (const double *const *)h->geom_dev, rec, h->stream);
+  fgd_grad_c2l_rec(h->tiles_dev, h->ntiles, h->ncells, h->F, nz, levels_pad(nz), halo_data, (const double *const *)h->geom_dev, rec, h->stream);
   HIPCHK(hipGetLastError());
   return 0;
 }

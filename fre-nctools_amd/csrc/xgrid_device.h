@@ -238,7 +238,7 @@ void fgd_merge3(int nb_pad, long n, const int *src_idx_f, const double *f, long 
 void fgd_interleave3(int nb_pad, int narr, const double *const *in, const long *ld, const long *n, double *const *out, int nb_valid,
                      hipStream_t st);
 void fgd_deinterleave(int nb_pad, long n, const double *in, long ld, int nb_valid, double *out, hipStream_t st);
-// eight levels with missing values of their own (apply_levels_kernels.hip): rec = merged records (order 2) or the interleaved
+// eight levels with missing values of their own (k_apply_ep8g, MASKED): rec = merged records (order 2) or the interleaved
 // field (order 1), gbits = gradient-mask bits per source cell (order 2); out and row_sum level-major [level][ld], nb_valid levels
 #define FG_LEVELS_CAP 256     // exchange cells staged per chunk: a longer run of rows is walked in several chunks
 void fgd_apply_levels8(int order, int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing, double *out,

@@ -8,7 +8,7 @@ oracle's one-level preparation (test_gpu_c2l.oracle_prepare).  Plan and referenc
 comparison is bit for bit where the suite asserts bit identity (orc.host_has_fma), 1e-10 relative otherwise; the equalities
 between device paths are bit for bit everywhere.
 
-Shapes (the smallest that reach each path of k_apply_ep8m):
+Shapes (the smallest that reach each path of the masked k_apply_ep8g):
   short   C9 -> 30 x 15: rows of a few exchange cells, 32 rows per tile, 450 rows = 14 tiles and a partial one
   mid8    C9 -> 12 x 6, mid2: C9 -> 6 x 4: the tiles of 8 and 2 rows
   long    C24 -> 4 x 2: one row per tile, every row longer than the staging capacity (the chunk walk)
