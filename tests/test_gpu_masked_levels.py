@@ -13,7 +13,11 @@ Shapes (the smallest that reach each path of the masked k_apply_ep8g):
   mid8    C9 -> 12 x 6, mid2: C9 -> 6 x 4: the tiles of 8 and 2 rows
   long    C24 -> 4 x 2: one row per tile, every row longer than the staging capacity (the chunk walk)
   empty   tile 1 of C9 alone -> global 30 x 15: most rows are empty
-Masks are integer functions of (tile, j, i, level), see _depth / _missing_at."""
+Masks are integer functions of (tile, j, i, level), see _depth / _missing_at.
+
+No exchange cell of a real grid pair has area 0, so no row here has a counted cell under an area sum of 0: the middle outcome of
+conserve_interp.c:815-839 (0.0 by the `touched` flag, against `missing` where no cell counted) is tested on the hand-made lists of
+tests/sweep_cases.py, in tests/test_gpu_sweep_synthetic.py::test_apply_levels."""
 import ctypes as C
 
 import numpy as np
