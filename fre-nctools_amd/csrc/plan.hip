@@ -325,7 +325,7 @@ struct HandleCache {
     std::lock_guard<std::mutex> lk(mu);
     events[current_device()].push_back(e);
   }
-  // ordering-only events (stream A -> stream B dependencies of the chunked search)
+  // ordering-only events (the plan's stream <-> its second stream in the great-circle clip)
   std::map<int, std::vector<hipEvent_t>> sync_events;
   hipEvent_t get_sync_event()
   {
@@ -384,7 +384,7 @@ struct fg_plan {
   int order = 0, device = 0;
   bool great_circle = false;   // exchange cells from create_xgrid_great_circle semantics (order 1 only)
   hipStream_t stream = nullptr;
-  hipStream_t stream_b = nullptr;   // second stream of the chunked search (always ours)
+  hipStream_t stream_b = nullptr;   // second stream of the three-pass great-circle clip (always ours)
   bool own_stream = true;
   int ntiles = 0;
   std::vector<int> nx_in, ny_in, cell_off;
@@ -407,7 +407,6 @@ struct fg_plan {
   int *x_src = nullptr, *x_dst = nullptr;
   double *x_area = nullptr, *x_c1 = nullptr, *x_c2 = nullptr;
   int *xoff = nullptr;
-  int *x_rowpos = nullptr;       // slot of every exchange cell in its destination row, taken while compacting (search scratch)
   int *perm = nullptr;           // exchange cells grouped by destination row (unsorted inside a row) until fg_plan_finalize
   bool rows_built = false;       // csr.row_ptr and perm come from the search
   bool dist_pending = false;     // order 2: x_c1/x_c2 still hold the centroid integrals after finalize (fg_plan_get_xgrid applies di/dj)
@@ -437,6 +436,16 @@ struct fg_plan {
     if (!p) return;
     for (size_t k = 0; k < owned.size(); k++) if (owned[k] == p) { owned.erase(owned.begin() + k); break; }
     g_pool.put(p);
+  }
+  // Before a search is repeated (plan_search): every block beyond the first `keep` -- those the caller staged -- goes back to the
+  // pool, and so must every pointer into them.  A field that plan_search_core allocates or sets is added HERE as well.
+  void drop_search(size_t keep)
+  {
+    while (owned.size() > keep) { g_pool.put(owned.back()); owned.pop_back(); }
+    tiles_dev = nullptr; mask_dev = nullptr; S = FgCells{}; D = FgCells{};
+    x_src = x_dst = nullptr; x_area = x_c1 = x_c2 = nullptr; xoff = nullptr;
+    perm = nullptr; csr.row_ptr = nullptr; csr.e1 = nullptr; csr.e2 = nullptr; cen = nullptr; src_idx_f = nullptr; sums = nullptr;
+    have_geom = false; rect = false; rect_tab = FgRect{};
   }
 };
 
@@ -545,20 +554,6 @@ static int g_search_finalize = 0;     // fg_set_search_finalize: a search that c
 static int g_gc_split = 1;
 extern "C" void fg_set_gc_split(int on) { g_gc_split = on < 0 ? 0 : on; }      // 2: a task space 64 times too small (tests of the overflow path)
 struct SearchCaps { unsigned long long entries; int regcap, nreg; bool rect; };
-// Chunks of source cells per search (1 = everything on one stream, in sequence; fg_set_search_chunks / FREGRID_HIP_CHUNKS).  Measured at C384 -> 0.25 deg with 4 chunks: the
-// kernels slow each other down by more than the overlap wins (clip 4 x 184 us against 482, step 1.48 ms against 1.30), so the
-// default is ONE chunk; the machinery stays for grids where the balance differs.
-static int g_search_chunks = 0;
-extern "C" void fg_set_search_chunks(int k) { g_search_chunks = k < 0 ? 0 : (k > FG_MAX_CHUNKS ? FG_MAX_CHUNKS : k); }
-static int choose_chunks(int nsrc, int nreg)
-{
-  static const int env_k = getenv("FREGRID_HIP_CHUNKS") ? atoi(getenv("FREGRID_HIP_CHUNKS")) : 0;
-  int k = g_search_chunks ? g_search_chunks : (env_k > 0 ? env_k : 1);
-  if (k > FG_MAX_CHUNKS) k = FG_MAX_CHUNKS;
-  const bool forced = g_search_chunks > 0 || env_k > 0;
-  while (k > 1 && (nreg / k < 1 || (!forced && nsrc / k < 4096))) k--;
-  return k;
-}
 // Rectilinear destination grids (k_rect_tables, xgrid_kernels.hip): 1 = try the index-arithmetic path first and verify the grid on
 // the device in the same stream (default), 0 = always the generic bins path.  A target that fails the check costs the attempt's
 // launches (every kernel leaves at once) and one more synchronisation, ~0.1 ms; callers with host arrays are spared even that by
@@ -585,6 +580,21 @@ static bool host_says_not_rect(int nx, int ny, const double *lon, const double *
   return false;
 }
 #define FG_RETRY (-1000L)
+// Offsets of the parts of one block, handed out in order: the one walk gives every part's place and, at its end, the block's size.
+struct Carve {
+  size_t n = 0;
+  size_t operator()(size_t size) { const size_t at = n; n += size; return at; }
+};
+// Device blocks of one attempt.  keep: stays with the plan; get: scratch of the search, handed back by release().  A block that
+// could not be had clears ok, which the search tests once, before its first launch.
+struct SearchBlocks {
+  fg_plan *pl;
+  bool ok = true;
+  std::vector<void *> scratch;
+  template <typename T> T *keep(size_t count) { T *p = pl->alloc<T>(count); ok = ok && p; return p; }
+  template <typename T> T *get(size_t count) { T *p = keep<T>(count); if (p) scratch.push_back(p); return p; }
+  void release() { for (void *p : scratch) pl->release(p); scratch.clear(); }
+};
 static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const double *const *d_lat_in,
                         const double *const *d_mask_in, const double *d_lon_out, const double *d_lat_out,
                         double mean_dlat, double mean_dlon, const GcXyz *gc_in, const GcXyz *gc_out,
@@ -656,70 +666,73 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   const long nx_alloc = npairs;                       // nxgrid <= candidate pairs <= capacity
 
   if (!alloc_cells(pl, &pl->S, nsrc)) return fail(FG_ERR_HIP, "out of device memory");
-  double *rect_blk = nullptr;
+  SearchBlocks blk{pl};
+  struct { double *hdr, *lat_ax, *lon_ax, *col, *row; } rt{};   // the rectilinear tables, one block (FgRect, xgrid_device.h)
   if (rect) {
     pl->D = FgCells{};
-    pl->D.area = pl->alloc<double>(ndst);
-    rect_blk = pl->alloc<double>(8 + (size_t)(pl->ny_out + 1) + (size_t)(pl->nx_out + 1) + 8 * (size_t)pl->nx_out + 4 * (size_t)(pl->ny_out + 1));
-    if (!pl->D.area || !rect_blk) return fail(FG_ERR_HIP, "out of device memory");
+    pl->D.area = blk.keep<double>(ndst);
+    Carve at;                                         // (in doubles)
+    const size_t o_hdr = at(8), o_lat = at((size_t)pl->ny_out + 1), o_lon = at((size_t)pl->nx_out + 1), o_col = at(8 * (size_t)pl->nx_out),
+                 o_row = at(4 * ((size_t)pl->ny_out + 1));
+    double *rect_blk = blk.keep<double>(at.n);
+    if (!blk.ok) return fail(FG_ERR_HIP, "out of device memory");
+    rt = {rect_blk + o_hdr, rect_blk + o_lat, rect_blk + o_lon, rect_blk + o_col, rect_blk + o_row};
   } else if (!alloc_cells(pl, &pl->D, ndst)) return fail(FG_ERR_HIP, "out of device memory");
   // one zeroed block: [counters | region fill counters | tickets | look-back words of the three scans | bin counts |
-  //                    bin fill cursors | destination-row counts | accepted pairs per source cell]
-  const int K = rect ? 1 : choose_chunks(nsrc, ps.nreg);
-  const long t_bins = fgd_scan_tiles(nslots), t_rows = fgd_scan_tiles(ndst), t_comp = fgd_scan_tiles(nsrc) + K;
-  const size_t zc = (sizeof(FgCounters) + 127) / 128 * 128;
-  const size_t zfill = (size_t)FG_NREG * FG_FILL_STRIDE * sizeof(unsigned);      // (nreg <= FG_NREG)
-  const size_t ztick = 128;
-  const size_t zlb = (size_t)(t_bins + t_rows + t_comp) * sizeof(unsigned long long);
-  const size_t zints = ((size_t)(2 * (nslots + 1) + ndst + 1 + nsrc + 1) * sizeof(int) + 15) / 16 * 16;
-  const size_t zgc = gc ? 2 * (size_t)K * FG_NREG * FG_FILL_STRIDE * sizeof(unsigned) : 0;    // great-circle clip: task counters, then the counters of the walk's pair lists
-  const size_t zbytes = zc + zfill + ztick + zlb + zints + zgc;
-  char *zero_blk = pl->alloc<char>(zbytes);
-  int *bin_start = pl->alloc<int>(nslots + 1);
-  int *heavy_list = pl->alloc<int>(nsrc + 1);
-  int *big_list = pl->alloc<int>(nsrc + 1);
-  int *pair_beg = pl->alloc<int>(nsrc + 1), *pair_cnt = pl->alloc<int>(nsrc + 1);
-  FgBinEntry *bin_entries = pl->alloc<FgBinEntry>(nentries ? nentries : 1);
-  ps.src = pl->alloc<int>(npairs + 1); ps.dst = pl->alloc<int>(npairs + 1);
-  double *tmp_area = pl->alloc<double>(npairs + 1);
-  double *tmp_clon = (order == 2) ? pl->alloc<double>(npairs + 1) : nullptr;
-  double *tmp_clat = (order == 2) ? pl->alloc<double>(npairs + 1) : nullptr;
-  int *defer_list = pl->alloc<int>(npairs + 1);
-  // legacy clip on one chunk: the clip kernels take the destination-row slots, the row scan runs before the compaction and the
-  // compaction stores the row lists itself (no k_csr_fill_pos, no returning atomics in the compaction)
-  const bool early_rows = !gc && !boxm && K == 1;
-  int *tmp_rowpos = early_rows ? pl->alloc<int>(npairs + 1) : nullptr;
-  if (early_rows && !tmp_rowpos) return fail(FG_ERR_HIP, "out of device memory");
+  //                    bin fill cursors | destination-row counts | accepted pairs per source cell | great-circle task counters]
+  const long t_bins = fgd_scan_tiles(nslots), t_rows = fgd_scan_tiles(ndst), t_comp = fgd_scan_tiles(nsrc);
+  const size_t zreg = (size_t)FG_NREG * FG_FILL_STRIDE * sizeof(unsigned);        // a counter per region (nreg <= FG_NREG)
+  Carve z;
+  const size_t z_dc = z((sizeof(FgCounters) + 127) / 128 * 128), z_fill = z(zreg), z_tick = z(128);
+  const size_t z_lb_bins = z(t_bins * sizeof(unsigned long long)), z_lb_rows = z(t_rows * sizeof(unsigned long long)),
+               z_lb_comp = z(t_comp * sizeof(unsigned long long));
+  const size_t z_bin_cnt = z((size_t)(nslots + 1) * sizeof(int)), z_bin_fill = z((size_t)(nslots + 1) * sizeof(int)),
+               z_row_cnt = z((size_t)(ndst + 1) * sizeof(int)), z_nacc = z((size_t)(nsrc + 1) * sizeof(int));
+  z((16 - (z.n - z_bin_cnt) % 16) % 16);              // (the four int arrays together are rounded up to 16 bytes)
+  const size_t z_gc_ntask = z(gc ? zreg : 0), z_gc_ocnt = z(gc ? zreg : 0);   // great-circle clip: task counters, then the counters of the walk's pair lists
+  const size_t zbytes = z.n;
+  char *zero_blk = blk.get<char>(zbytes);
+  int *bin_start = blk.get<int>(nslots + 1);
+  int *heavy_list = blk.get<int>(nsrc + 1);
+  int *big_list = blk.get<int>(nsrc + 1);
+  int *pair_beg = blk.get<int>(nsrc + 1), *pair_cnt = blk.get<int>(nsrc + 1);
+  FgBinEntry *bin_entries = blk.get<FgBinEntry>(nentries ? nentries : 1);
+  ps.src = blk.get<int>(npairs + 1); ps.dst = blk.get<int>(npairs + 1);
+  double *tmp_area = blk.get<double>(npairs + 1);
+  double *tmp_clon = (order == 2) ? blk.get<double>(npairs + 1) : nullptr;
+  double *tmp_clat = (order == 2) ? blk.get<double>(npairs + 1) : nullptr;
+  int *defer_list = blk.get<int>(npairs + 1);
+  // legacy clip: the clip kernels take the destination-row slots, the row scan runs before the compaction and the compaction
+  // stores the row lists itself (no k_csr_fill_pos, no returning atomics in the compaction)
+  const bool early_rows = !gc && !boxm;
+  int *tmp_rowpos = early_rows ? blk.get<int>(npairs + 1) : nullptr;
   // great-circle path, three-pass clip: per-pair words, and 3 tasks (edge pairs to solve) per pair of capacity -- 3.0 per LIVE
   // pair were counted at C384 -> 0.25 deg; pairs whose tasks do not fit go through the one-kernel clip instead
   const bool gc_split = gc && g_gc_split && npairs < (1L << 28);
   const long tcap_want = (g_gc_split == 2) ? npairs / 64 : 3 * npairs;
-  const long tcap_reg = gc_split ? std::min<long>((tcap_want / K / FG_NREG + 255) / 256 * 256, 0x7ffffff0L / (K * FG_NREG)) : 0;   // tasks per region
-  const long tcap_all = tcap_reg * K * FG_NREG;
-  unsigned *gc_meta = gc_split ? pl->alloc<unsigned>(npairs + 1) : nullptr;
-  int *gc_tbase = gc_split ? pl->alloc<int>(npairs + 1) : nullptr;
-  int *gc_order = gc_split ? pl->alloc<int>(npairs + 1) : nullptr;
-  unsigned *gc_task = gc_split ? pl->alloc<unsigned>(tcap_all + 1) : nullptr;
-  double *gc_res = gc_split ? pl->alloc<double>(2 * (size_t)tcap_all + 2) : nullptr;
-  if (gc_split && (!gc_meta || !gc_tbase || !gc_order || !gc_task || !gc_res)) return fail(FG_ERR_HIP, "out of device memory");
-  pl->xoff = pl->alloc<int>(nsrc + 1);
-  pl->x_src = pl->alloc<int>(nx_alloc + 1); pl->x_dst = pl->alloc<int>(nx_alloc + 1);
-  pl->x_area = pl->alloc<double>(nx_alloc + 1);
-  if (order == 2) { pl->x_c1 = pl->alloc<double>(nx_alloc + 1); pl->x_c2 = pl->alloc<double>(nx_alloc + 1); pl->sums = pl->alloc<double>(3 * (size_t)nsrc); }
-  pl->x_rowpos = pl->alloc<int>(nx_alloc + 1);
-  pl->perm = pl->alloc<int>(nx_alloc + 1);
-  pl->csr.row_ptr = pl->alloc<int>(ndst + 1);
-  if (!pl->src_idx_f) pl->src_idx_f = pl->alloc<int>(nsrc + 1);
-  if (!zero_blk || !bin_start || !heavy_list || !big_list || !pair_beg || !pair_cnt || !bin_entries || !ps.src || !ps.dst || !tmp_area ||
-      !defer_list || (order == 2 && (!tmp_clon || !tmp_clat || !pl->x_c1 || !pl->x_c2 || !pl->sums)) || !pl->xoff || !pl->x_src || !pl->x_dst ||
-      !pl->x_area || !pl->x_rowpos || !pl->perm || !pl->csr.row_ptr || !pl->src_idx_f)
-    return fail(FG_ERR_HIP, "out of device memory");
-  FgCounters *dc = (FgCounters *)zero_blk;
-  ps.fill = (unsigned *)(zero_blk + zc);
-  unsigned *tickets = (unsigned *)(zero_blk + zc + zfill);                 // [0] bins [1] rows [2 + k] xoff scan of chunk k
-  unsigned long long *lb_bins = (unsigned long long *)(zero_blk + zc + zfill + ztick), *lb_rows = lb_bins + t_bins, *lb_comp = lb_rows + t_rows;
-  int *bin_cnt = (int *)(zero_blk + zc + zfill + ztick + zlb), *bin_fill = bin_cnt + (nslots + 1), *row_cnt = bin_fill + (nslots + 1);
-  int *nacc = row_cnt + (ndst + 1);
+  const long tcap_reg = gc_split ? std::min<long>((tcap_want / FG_NREG + 255) / 256 * 256, 0x7ffffff0L / FG_NREG) : 0;   // tasks per region
+  const long tcap_all = tcap_reg * FG_NREG;
+  unsigned *gc_meta = gc_split ? blk.get<unsigned>(npairs + 1) : nullptr;
+  int *gc_tbase = gc_split ? blk.get<int>(npairs + 1) : nullptr;
+  int *gc_order = gc_split ? blk.get<int>(npairs + 1) : nullptr;
+  unsigned *gc_task = gc_split ? blk.get<unsigned>(tcap_all + 1) : nullptr;
+  double *gc_res = gc_split ? blk.get<double>(2 * (size_t)tcap_all + 2) : nullptr;
+  pl->xoff = blk.keep<int>(nsrc + 1);
+  pl->x_src = blk.keep<int>(nx_alloc + 1); pl->x_dst = blk.keep<int>(nx_alloc + 1);
+  pl->x_area = blk.keep<double>(nx_alloc + 1);
+  if (order == 2) { pl->x_c1 = blk.keep<double>(nx_alloc + 1); pl->x_c2 = blk.keep<double>(nx_alloc + 1); pl->sums = blk.keep<double>(3 * (size_t)nsrc); }
+  int *x_rowpos = blk.get<int>(nx_alloc + 1);          // slot of every exchange cell in its destination row, where the compaction takes it (!early_rows)
+  pl->perm = blk.keep<int>(nx_alloc + 1);
+  pl->csr.row_ptr = blk.keep<int>(ndst + 1);
+  if (!pl->src_idx_f) pl->src_idx_f = blk.keep<int>(nsrc + 1);
+  if (!blk.ok) return fail(FG_ERR_HIP, "out of device memory");
+  FgCounters *dc = (FgCounters *)(zero_blk + z_dc);
+  ps.fill = (unsigned *)(zero_blk + z_fill);
+  unsigned *tickets = (unsigned *)(zero_blk + z_tick);                     // [0] bins [1] rows [2] xoff scan
+  unsigned long long *lb_bins = (unsigned long long *)(zero_blk + z_lb_bins), *lb_rows = (unsigned long long *)(zero_blk + z_lb_rows),
+                     *lb_comp = (unsigned long long *)(zero_blk + z_lb_comp);
+  int *bin_cnt = (int *)(zero_blk + z_bin_cnt), *bin_fill = (int *)(zero_blk + z_bin_fill), *row_cnt = (int *)(zero_blk + z_row_cnt);
+  int *nacc = (int *)(zero_blk + z_nacc);
   HIPCHK(hipMemsetAsync(zero_blk, 0, zbytes, st));
 
   PhaseTimer pt, ptot;
@@ -736,12 +749,9 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   } else if (rect) {
     // tables + on-device verification of the grid, then the source records, the heavy list and the destination AREAS in one launch
     FgRect &R = pl->rect_tab;
-    R.hdr = rect_blk; R.lat_ax = rect_blk + 8; R.lon_ax = rect_blk + 8 + (pl->ny_out + 1); R.col = rect_blk + 8 + (pl->ny_out + 1) + (pl->nx_out + 1);
-    double *rect_row = rect_blk + 8 + (pl->ny_out + 1) + (pl->nx_out + 1) + 8 * (size_t)pl->nx_out;
-    R.row = rect_row;
+    R.hdr = rt.hdr; R.lat_ax = rt.lat_ax; R.lon_ax = rt.lon_ax; R.col = rt.col; R.row = rt.row;
     R.bad = &dc->rect_bad; R.nx = pl->nx_out; R.ny = pl->ny_out;
-    fgd_rect_tables(d_lon_out, d_lat_out, pl->nx_out, pl->ny_out, rect_blk, rect_blk + 8, rect_blk + 8 + (pl->ny_out + 1),
-                    rect_blk + 8 + (pl->ny_out + 1) + (pl->nx_out + 1), rect_row, &dc->rect_bad, dc->err, st, dst_tlon);
+    fgd_rect_tables(d_lon_out, d_lat_out, pl->nx_out, pl->ny_out, rt.hdr, rt.lat_ax, rt.lon_ax, rt.col, rt.row, &dc->rect_bad, dc->err, st, dst_tlon);
     if (pl->polys.npoly) fgd_polylist_records(pl->polys, pl->S, pl->src_idx_f, pl->sums, &R, heavy_list, &dc->heavy_cnt, dc->err, st);
     fgd_cell_struct2r(ts, pl->tiles_dev, pl->tiles_dev, pl->ntiles, pl->polys.npoly ? 0 : nsrc, ndst, pl->S, pl->D.area, R, pl->mask_dev, order,
                       pl->src_idx_f, pl->sums, dc->err, st, dc->band_keys, (g_search_cull && !pl->polys.npoly) ? 2 : 0, heavy_list, &dc->heavy_cnt);
@@ -768,102 +778,63 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
     pt.end();
   }
 
-  // --- per chunk of source cells: candidates (stream A) -> clip (stream B) -> scan + compaction (stream A again).  The clip of
-  // chunk k is VALU bound, its neighbours in the schedule wait on memory: side by side they fill each other's gaps.
-  hipStream_t sb = st;
-  if (K > 1) {
-    if (!pl->stream_b) pl->stream_b = g_handles.get_stream(pl->device);
-    if (!pl->stream_b) return fail(FG_ERR_HIP, "hipStreamCreate failed");
-    sb = pl->stream_b;
-  }
-  std::vector<hipEvent_t> ev_c(K, nullptr), ev_q(K, nullptr);
+  pt.begin(PH_CANDIDATES);
+  if (rect)
+    fgd_candidates_rect(nsrc, pl->S, pl->mask_dev, pl->rect_tab, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list, &dc->big_cnt, st);
+  else
+    fgd_candidates1(nsrc, pl->S, pl->mask_dev, bins, bin_start, bin_entries, ecap, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list,
+                    &dc->big_cnt, st);
+  pt.end();
+  // --- clip, area, centroid integrals
   hipEvent_t gc_e1 = nullptr, gc_e2 = nullptr;        // great-circle clip: the listed pairs run on stream B beside k_gc_walk
   struct EvReturn {                                   // back to the cache on every way out of this function (HIPCHK / fail returns too)
     hipEvent_t &a, &b;
     ~EvReturn() { g_handles.put_sync_event(a); g_handles.put_sync_event(b); a = b = nullptr; }
   } ev_return{gc_e1, gc_e2};
-  if (gc_split && K == 1) {
-    if (!pl->stream_b) pl->stream_b = g_handles.get_stream(pl->device);
-    gc_e1 = g_handles.get_sync_event(); gc_e2 = g_handles.get_sync_event();
-  }
-  PhaseTimer ptb; ptb.start(g_profiling != 0, sb);
-  int cb[FG_MAX_CHUNKS + 1];
-  for (int k = 0; k <= K; k++) cb[k] = (k == K) ? nsrc : (int)(((long)nsrc * k / K) / 256 * 256);
-  const int nreg_k = ps.nreg / K;                     // regions per chunk (choose_chunks keeps this >= 1)
-  const long pcap_k = (long)nreg_k * ps.regcap;       // pairs per chunk
-  auto chunk_ps = [&](int k) { FgPairSpace q = ps; q.nreg = nreg_k; q.src = ps.src + k * pcap_k; q.dst = ps.dst + k * pcap_k;
-                               q.fill = ps.fill + (size_t)k * nreg_k * FG_FILL_STRIDE; return q; };
-  pt.begin(PH_CANDIDATES);
-  for (int k = 0; k < K; k++) {
-    if (rect)
-      fgd_candidates_rect(nsrc, pl->S, pl->mask_dev, pl->rect_tab, chunk_ps(k), pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list, &dc->big_cnt[k], st);
-    else
-      fgd_candidates1(cb[k], cb[k + 1], pl->S, pl->mask_dev, bins, bin_start, bin_entries, ecap, chunk_ps(k), pair_beg, pair_cnt, heavy_list,
-                      &dc->heavy_cnt, big_list + cb[k], &dc->big_cnt[k], st);
-    if (K > 1) { ev_c[k] = g_handles.get_sync_event(); HIPCHK(hipEventRecord(ev_c[k], st)); }
-  }
-  pt.end();
-  // --- clip, area, centroid integrals
-  for (int k = 0; k < K; k++) {
-    const FgPairSpace q = chunk_ps(k);
-    double *ta = tmp_area + k * pcap_k, *tl = tmp_clon ? tmp_clon + k * pcap_k : nullptr, *tt = tmp_clat ? tmp_clat + k * pcap_k : nullptr;
-    int *dl = defer_list + k * pcap_k;
-    if (K > 1) HIPCHK(hipStreamWaitEvent(sb, ev_c[k], 0));
-    if (boxm) {
-      ptb.begin(PH_CLIP_GENERAL);
-      fgd_clip_box(order, q, boxm->box, th[pl->ntiles], pl->S, pl->D, pl->mask_dev, boxm->mask_quad, ta, tl, tt, nacc, dc->stats, dc->err, sb);
-      ptb.end();
-    } else if (gc) {
-      ptb.begin(PH_CLIP_GENERAL);
-      if (gc_split) {
-        const long tcap_k = tcap_reg * FG_NREG;
-        unsigned *ntask = (unsigned *)(zero_blk + zbytes - zgc) + (size_t)k * FG_NREG * FG_FILL_STRIDE;
-        GcSplit g{gc_meta + k * pcap_k, gc_tbase + k * pcap_k, gc_task + k * tcap_k, gc_res + 2 * k * tcap_k, (unsigned)tcap_reg,
-                  ntask, dl, &dc->defer_cnt[k], &dc->gc_list2_cnt[k], pcap_k,
-                  gc_order + k * pcap_k, ntask + (size_t)K * FG_NREG * FG_FILL_STRIDE};
-        fgd_gc_clip_split(q, pl->S, pl->mask_dev, pl->D, ta, nacc, g, dc->stats, dc->err, sb, K == 1 ? pl->stream_b : nullptr, gc_e1, gc_e2);
-      } else
-        fgd_gc_clip(q, pl->S, pl->mask_dev, pl->D, ta, nacc, dl, &dc->defer_cnt[k], dc->stats, dc->err, sb);
-      ptb.end();
-    } else {
-      ptb.begin(PH_CLIP_QUAD);
-      fgd_clip_quad(order, q, pl->S, pl->mask_dev, pl->D, ta, tl, tt, nacc, dl, &dc->defer_cnt[k], dc->stats, dc->err, sb, rect ? &pl->rect_tab : nullptr,
-                    early_rows ? row_cnt : nullptr, tmp_rowpos);
-      ptb.end();
-      ptb.begin(PH_CLIP_GENERAL);
-      fgd_clip_general(order, q, pl->S, pl->mask_dev, pl->D, ta, tl, tt, nacc, dl, &dc->defer_cnt[k], dc->stats, dc->err, sb, rect ? &pl->rect_tab : nullptr,
-                       early_rows ? row_cnt : nullptr, tmp_rowpos);
-      ptb.end();
-    }
-    if (K > 1) { ev_q[k] = g_handles.get_sync_event(); HIPCHK(hipEventRecord(ev_q[k], sb)); }
-  }
-  // --- compaction into canonical order, per-source-cell sums, destination-row slots
-  long tile0 = 0;
-  for (int k = 0; k < K; k++) {
-    const FgPairSpace q = chunk_ps(k);
-    if (K > 1) HIPCHK(hipStreamWaitEvent(st, ev_q[k], 0));
-    pt.begin(PH_COMPACT);
-    FgCompactIo io{};
-    io.pair_beg = pair_beg; io.pair_cnt = pair_cnt;
-    io.tmp_area = tmp_area + k * pcap_k; io.tmp_clon = tmp_clon ? tmp_clon + k * pcap_k : nullptr; io.tmp_clat = tmp_clat ? tmp_clat + k * pcap_k : nullptr;
-    io.xoff = pl->xoff; io.x_src = pl->x_src; io.x_dst = pl->x_dst; io.x_area = pl->x_area; io.x_c1 = pl->x_c1; io.x_c2 = pl->x_c2;
-    io.row_cnt = row_cnt; io.x_rowpos = pl->x_rowpos; io.sums = pl->sums; io.big_list = big_list + cb[k]; io.big_cnt = &dc->big_cnt[k];
-    io.tmp_rowpos = tmp_rowpos; io.row_ptr = pl->csr.row_ptr; io.perm = pl->perm;
-    io.fill_all = (k == K - 1) ? ps.fill : nullptr; io.nreg_all = nreg_k * K;
-    io.dc = dc; io.xcap = nx_alloc;
-    const int nk = cb[k + 1] - cb[k];
-    if (early_rows)       // accepted pairs per source cell -> xoff, destination-row counts -> row_ptr: one launch
-      fgd_exclusive_scan2(nacc, nk, pl->xoff, lb_comp, &tickets[2], &dc->xtot[0], row_cnt, ndst, pl->csr.row_ptr, lb_rows, &tickets[1], &dc->rows_total, dc->err, st);
-    else
-      fgd_exclusive_scan1(nacc + cb[k], nk, pl->xoff + cb[k], lb_comp + tile0, &tickets[2 + k], &dc->xtot[k], dc->err, st, k ? &dc->xtot[k - 1] : nullptr);
-    tile0 += fgd_scan_tiles(nk);
-    fgd_compact(order, nsrc, q, io, st);
+  if (boxm) {
+    pt.begin(PH_CLIP_GENERAL);
+    fgd_clip_box(order, ps, boxm->box, th[pl->ntiles], pl->S, pl->D, pl->mask_dev, boxm->mask_quad, tmp_area, tmp_clon, tmp_clat, nacc, dc->stats, dc->err, st);
+    pt.end();
+  } else if (gc) {
+    pt.begin(PH_CLIP_GENERAL);
+    if (gc_split) {
+      if (!pl->stream_b) pl->stream_b = g_handles.get_stream(pl->device);
+      gc_e1 = g_handles.get_sync_event(); gc_e2 = g_handles.get_sync_event();
+      GcSplit g{gc_meta, gc_tbase, gc_task, gc_res, (unsigned)tcap_reg, (unsigned *)(zero_blk + z_gc_ntask), defer_list, &dc->defer_cnt,
+                &dc->gc_list2_cnt, npairs, gc_order, (unsigned *)(zero_blk + z_gc_ocnt)};
+      fgd_gc_clip_split(ps, pl->S, pl->mask_dev, pl->D, tmp_area, nacc, g, dc->stats, dc->err, st, pl->stream_b, gc_e1, gc_e2);
+    } else
+      fgd_gc_clip(ps, pl->S, pl->mask_dev, pl->D, tmp_area, nacc, defer_list, &dc->defer_cnt, dc->stats, dc->err, st);
+    pt.end();
+  } else {
+    pt.begin(PH_CLIP_QUAD);
+    fgd_clip_quad(order, ps, pl->S, pl->mask_dev, pl->D, tmp_area, tmp_clon, tmp_clat, nacc, defer_list, &dc->defer_cnt, dc->stats, dc->err, st,
+                  rect ? &pl->rect_tab : nullptr, row_cnt, tmp_rowpos);
+    pt.end();
+    pt.begin(PH_CLIP_GENERAL);
+    fgd_clip_general(order, ps, pl->S, pl->mask_dev, pl->D, tmp_area, tmp_clon, tmp_clat, nacc, defer_list, &dc->defer_cnt, dc->stats, dc->err, st,
+                     rect ? &pl->rect_tab : nullptr, row_cnt, tmp_rowpos);
     pt.end();
   }
+  // --- compaction into canonical order, per-source-cell sums, destination-row slots
+  pt.begin(PH_COMPACT);
+  FgCompactIo io{};
+  io.pair_beg = pair_beg; io.pair_cnt = pair_cnt;
+  io.tmp_area = tmp_area; io.tmp_clon = tmp_clon; io.tmp_clat = tmp_clat;
+  io.xoff = pl->xoff; io.x_src = pl->x_src; io.x_dst = pl->x_dst; io.x_area = pl->x_area; io.x_c1 = pl->x_c1; io.x_c2 = pl->x_c2;
+  io.row_cnt = row_cnt; io.x_rowpos = x_rowpos; io.sums = pl->sums; io.big_list = big_list; io.big_cnt = &dc->big_cnt;
+  io.tmp_rowpos = tmp_rowpos; io.row_ptr = pl->csr.row_ptr; io.perm = pl->perm;
+  io.dc = dc; io.xcap = nx_alloc;
+  if (early_rows)       // accepted pairs per source cell -> xoff, destination-row counts -> row_ptr: one launch
+    fgd_exclusive_scan2(nacc, nsrc, pl->xoff, lb_comp, &tickets[2], &dc->xtot, row_cnt, ndst, pl->csr.row_ptr, lb_rows, &tickets[1], &dc->rows_total, dc->err, st);
+  else
+    fgd_exclusive_scan1(nacc, nsrc, pl->xoff, lb_comp, &tickets[2], &dc->xtot, dc->err, st);
+  fgd_compact(order, nsrc, ps, io, st);
+  pt.end();
   if (!early_rows) {
     pt.begin(PH_ROWS);
     fgd_exclusive_scan1(row_cnt, ndst, pl->csr.row_ptr, lb_rows, &tickets[1], &dc->rows_total, dc->err, st);
-    fgd_csr_fill_pos(nx_alloc, &dc->xtot[K - 1], pl->x_dst, pl->csr.row_ptr, pl->x_rowpos, pl->perm, st);
+    fgd_csr_fill_pos(nx_alloc, &dc->xtot, pl->x_dst, pl->csr.row_ptr, x_rowpos, pl->perm, st);
     pt.end();
   }
   ptot.end();
@@ -892,9 +863,7 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   }
   HIPCHK(hipMemcpyAsync(hc, dc, sizeof(FgCounters), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));                              // the one synchronisation of a search (stream B's work is ordered before it)
-  pt.collect(pl->phase_ms); ptot.collect(pl->phase_ms); ptb.collect(pl->phase_ms);   // (also hands the timing events back on every exit below)
-  for (hipEvent_t e : ev_c) g_handles.put_sync_event(e);
-  for (hipEvent_t e : ev_q) g_handles.put_sync_event(e);
+  pt.collect(pl->phase_ms); ptot.collect(pl->phase_ms);          // (also hands the timing events back on every exit below)
   HIPCHK(hipGetLastError());
   if (rect && hc->rect_bad) { caps->rect = false; return FG_RETRY; }   // not a rectilinear grid after all: every kernel of this attempt left at once
   if (hc->total[0] > nentries) { caps->entries = hc->total[0]; return FG_RETRY; }
@@ -913,24 +882,19 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   if (hc->err[0] & G_ERRBIT_GC_CONVEX2) return fail(FG_ERR_GEOM, "create_xgrid.c(clip_2dx2d_great_circle): grid box 2 is not convex");
   if (hc->err[0] & G_ERRBIT_GC_CLIP) return fail(FG_ERR_GEOM, "%s", gc_clip_error((int)hc->err[1]));
   if (hc->err[0] & G_ERRBIT_LOOKBACK) return fail(FG_ERR_HIP, "single-pass scan: a tile waited too long for its predecessor");
-  pl->nx = (long)hc->xtot[K - 1];
+  pl->nx = (long)hc->xtot;
   pl->stats[FG_STAT_PAIRS] = (long)hc->total[1];
-  pl->stats[FG_STAT_NONEMPTY] = (long)(hc->xtot[K - 1] + hc->stats[FG_STAT_BELOW]);
+  pl->stats[FG_STAT_NONEMPTY] = (long)(hc->xtot + hc->stats[FG_STAT_BELOW]);
   pl->stats[FG_STAT_NXGRID] = pl->nx;
   pl->stats[FG_STAT_BORDERLINE] = (long)hc->stats[FG_STAT_BORDERLINE];
   pl->stats[FG_STAT_BINS] = nbins;
   pl->stats[FG_STAT_BIN_ENTRIES] = (long)hc->total[0];
-  pl->stats[FG_STAT_DEFERRED] = 0;
-  for (int k = 0; k < K; k++) pl->stats[FG_STAT_DEFERRED] += hc->defer_cnt[k] + hc->gc_list2_cnt[k];
+  pl->stats[FG_STAT_DEFERRED] = hc->defer_cnt + hc->gc_list2_cnt;
   pl->stats[FG_STAT_HEAVY] = hc->heavy_cnt;
   pl->stats[FG_STAT_BELOW] = (long)hc->stats[FG_STAT_BELOW];
 
   pl->rect_tab.bad = nullptr;                          // (lives in the scratch block released below; nothing reads it after the search)
-  // scratch no longer needed
-  void *scratch[] = {zero_blk, bin_start, bin_entries, heavy_list, big_list, pair_beg, pair_cnt, ps.src, ps.dst,
-                     tmp_area, tmp_clon, tmp_clat, defer_list, gc_meta, gc_tbase, gc_order, gc_task, gc_res, tmp_rowpos};
-  for (void *p : scratch) pl->release(p);
-  pl->release(pl->x_rowpos); pl->x_rowpos = nullptr;
+  blk.release();                                       // scratch no longer needed
   pl->rows_built = true;
   pl->searched = true;
   if (fuse) {
@@ -979,11 +943,7 @@ static long plan_search(fg_plan *pl, const double *const *d_lon_in, const double
   for (; attempts < 4 && rc == FG_RETRY; attempts++) {
     if (attempts) {
       (void)hipStreamSynchronize(pl->stream);
-      while (pl->owned.size() > keep) { void *p = pl->owned.back(); pl->owned.pop_back(); g_pool.put(p); }
-      pl->tiles_dev = nullptr; pl->mask_dev = nullptr; pl->S = FgCells{}; pl->D = FgCells{};
-      pl->x_src = pl->x_dst = nullptr; pl->x_area = pl->x_c1 = pl->x_c2 = nullptr; pl->xoff = nullptr; pl->x_rowpos = nullptr;
-      pl->perm = nullptr; pl->csr.row_ptr = nullptr; pl->csr.e1 = nullptr; pl->csr.e2 = nullptr; pl->cen = nullptr; pl->src_idx_f = nullptr; pl->sums = nullptr;
-      pl->have_geom = false; pl->rect = false; pl->rect_tab = FgRect{};
+      pl->drop_search(keep);
     }
     rc = plan_search_core(pl, d_lon_in, d_lat_in, d_mask_in, d_lon_out, d_lat_out, mean_dlat, mean_dlon, gc_in, gc_out, boxm, &caps);
   }
@@ -992,106 +952,108 @@ static long plan_search(fg_plan *pl, const double *const *d_lon_in, const double
   return rc;
 }
 
-// mean cell extents from a strided sample of corner arrays (host or device-copied-to-host)
-static void sample_extents(int nx, int ny, const double *lon, const double *lat, double *mdlat, double *mdlon)
+// ----------------------------------------------------------------------------- mean cell extents of the destination grid
+// A strided sample of at most ~4096 cells (sample k = cell k * step), their corners in a compact buffer
+// q[array][sample][4] = SW, SE, NE, NW; the arrays are lon, lat or x, y, z.
+struct CornerSample {
+  int nsamp = 0;
+  std::vector<double> q;
+  const double *corners(int a, int k) const { return &q[((size_t)a * nsamp + k) * 4]; }
+};
+static long sample_step(int nx, int ny, int *nsamp)
+{
+  const long ncell = (long)nx * ny;
+  long step = ncell / 4096; if (step < 1) step = 1;
+  *nsamp = (int)((ncell + step - 1) / step);
+  return step;
+}
+// the corner nodes of sample k in a corner array of nx + 1 columns, in the buffer's order
+__host__ __device__ static inline void sample_nodes(int nx, long step, int k, long n[4])
+{
+  const long c = (long)k * step;
+  const int i = (int)(c % nx), j = (int)(c / nx);
+  n[0] = (long)j * (nx + 1) + i; n[1] = n[0] + 1; n[3] = n[0] + nx + 1; n[2] = n[3] + 1;
+}
+static CornerSample sample_corners_host(int nx, int ny, int narr, const double *const *arr)
+{
+  CornerSample s;
+  const long step = sample_step(nx, ny, &s.nsamp);
+  s.q.resize((size_t)s.nsamp * narr * 4);
+  for (int k = 0; k < s.nsamp; k++) {
+    long n[4];
+    sample_nodes(nx, step, k, n);
+    for (int a = 0; a < narr; a++)
+      for (int v = 0; v < 4; v++) s.q[((size_t)a * s.nsamp + k) * 4 + v] = arr[a][n[v]];
+  }
+  return s;
+}
+// Corner arrays that live on the device: the sampled cells' corners are gathered there, and the compact buffer is copied -- a
+// quarter of a megabyte instead of the whole grid (the whole 0.25-degree target copied into a fresh std::vector took 29 ms,
+// thirty times the search it was preparing).
+__global__ void k_sample_corners(int nx, long step, int nsamp, int narr, const double *a0, const double *a1, const double *a2, double *out)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nsamp) return;
+  long n[4];
+  sample_nodes(nx, step, k, n);
+  const double *arr[3] = {a0, a1, a2};
+  for (int a = 0; a < narr; a++) {
+    double *o = out + ((size_t)a * nsamp + k) * 4;
+    o[0] = arr[a][n[0]]; o[1] = arr[a][n[1]]; o[2] = arr[a][n[2]]; o[3] = arr[a][n[3]];
+  }
+}
+static int sample_corners_dev(fg_plan *pl, int nx, int ny, int narr, const double *d_a0, const double *d_a1, const double *d_a2, CornerSample *s)
+{
+  const long step = sample_step(nx, ny, &s->nsamp);
+  s->q.resize((size_t)s->nsamp * narr * 4);
+  double *d_q = (double *)g_pool.get(pl->device, s->q.size() * sizeof(double));
+  if (!d_q) return fail(FG_ERR_HIP, "out of device memory");
+  k_sample_corners<<<(s->nsamp + 255) / 256, 256, 0, pl->stream>>>(nx, step, s->nsamp, narr, d_a0, d_a1, d_a2, d_q);
+  hipError_t e = hipMemcpyAsync(s->q.data(), d_q, s->q.size() * sizeof(double), hipMemcpyDeviceToHost, pl->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(pl->stream);
+  g_pool.put(d_q);
+  if (e != hipSuccess) return fail(FG_ERR_HIP, "sampling the destination corners failed: %s", hipGetErrorString(e));
+  return 0;
+}
+// sums over cnt representative cells -> the means choose_bins takes
+static void mean_extents(double sl, double sw, long cnt, double *mdlat, double *mdlon)
 {
   const double PI = 3.14159265358979323846;
-  long ncell = (long)nx * ny;
-  long step = ncell / 4096; if (step < 1) step = 1;
+  if (cnt == 0) { *mdlat = PI / 180; *mdlon = PI / 180; return; }
+  *mdlat = sl / cnt; *mdlon = sw / cnt;
+  if (*mdlat < 1e-7) *mdlat = 1e-7;
+  if (*mdlon < 1e-7) *mdlon = 1e-7;
+}
+// lon / lat corners: latitude range and widest edge in longitude of every sampled cell.
+// *curvilinear = 1 if a sampled cell's west / east corners differ in longitude or its south / north corners in latitude (bit
+// patterns, the test k_rect_tables applies to the whole grid): such a target cannot take the rectilinear path, and the search does
+// not spend an attempt on finding that out (a cubed-sphere tile as target: 0.2 ms of kernels and a read-back per plan)
+static void extents_lonlat(const CornerSample &s, double *mdlat, double *mdlon, int *curvilinear)
+{
+  const double PI = 3.14159265358979323846;
+  *curvilinear = 0;
   double sl = 0, sw = 0; long cnt = 0;
-  for (long c = 0; c < ncell; c += step) {
-    int i = (int)(c % nx), j = (int)(c / nx);
-    long n0 = (long)j * (nx + 1) + i, n1 = n0 + 1, n3 = n0 + nx + 1, n2 = n3 + 1;
-    double y[4] = {lat[n0], lat[n1], lat[n2], lat[n3]}, x[4] = {lon[n0], lon[n1], lon[n2], lon[n3]};
+  for (int k = 0; k < s.nsamp; k++) {
+    const double *x = s.corners(0, k), *y = s.corners(1, k);
+    if (memcmp(&x[0], &x[3], 8) || memcmp(&x[1], &x[2], 8) || memcmp(&y[0], &y[1], 8) || memcmp(&y[3], &y[2], 8)) *curvilinear = 1;
     double ymin = y[0], ymax = y[0], w = 0;
-    for (int k = 1; k < 4; k++) { if (y[k] < ymin) ymin = y[k]; if (y[k] > ymax) ymax = y[k]; }
-    for (int k = 0; k < 4; k++) {
-      double d = fabs(x[(k + 1) & 3] - x[k]);              // |remainder(dx, 2 pi)|: the subtraction is exact for pi <= |dx| <= 4 pi (Sterbenz),
+    for (int m = 1; m < 4; m++) { if (y[m] < ymin) ymin = y[m]; if (y[m] > ymax) ymax = y[m]; }
+    for (int m = 0; m < 4; m++) {
+      double d = fabs(x[(m + 1) & 3] - x[m]);              // |remainder(dx, 2 pi)|: the subtraction is exact for pi <= |dx| <= 4 pi (Sterbenz),
       if (d > 3.0 * PI) d = fabs(remainder(d, 2.0 * PI)); else if (d > PI) d = fabs(2.0 * PI - d);   // so the same bits as the library call,
       if (d > w) w = d;                                    // which took 0.12 ms per plan for the 16 k differences of the sample
     }
     if (w > PI / 2) continue;      // polar caps: not representative
     sl += ymax - ymin; sw += w; cnt++;
   }
-  if (cnt == 0) { *mdlat = PI / 180; *mdlon = PI / 180; return; }
-  *mdlat = sl / cnt; *mdlon = sw / cnt;
-  if (*mdlat < 1e-7) *mdlat = 1e-7;
-  if (*mdlon < 1e-7) *mdlon = 1e-7;
+  mean_extents(sl, sw, cnt, mdlat, mdlon);
 }
-
-// The same estimate for corner arrays that live on the device: the sampled cells' corners are gathered into a compact buffer
-// (<= 4096 cells), copied and put through the host routine above -- a quarter of a megabyte instead of the whole grid (the whole
-// 0.25-degree target copied into a fresh std::vector took 29 ms, thirty times the search it was preparing).
-__global__ void k_sample_corners(int nx, int ny, long step, int nsamp, int narr, const double *a0, const double *a1, const double *a2, double *out)
+// unit-vector corners (great-circle plans): the diagonal SW - NE of every sampled cell as its cap-box extent
+static void extents_xyz(const CornerSample &s, double *mdlat, double *mdlon)
 {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= nsamp) return;
-  const long c = (long)k * step;
-  const int i = (int)(c % nx), j = (int)(c / nx);
-  const long n0 = (long)j * (nx + 1) + i, n1 = n0 + 1, n3 = n0 + nx + 1, n2 = n3 + 1;
-  const double *arr[3] = {a0, a1, a2};
-  for (int a = 0; a < narr; a++) {
-    double *o = out + ((size_t)a * nsamp + k) * 4;
-    o[0] = arr[a][n0]; o[1] = arr[a][n1]; o[2] = arr[a][n2]; o[3] = arr[a][n3];
-  }
-}
-// (the buffer holds, per array, the four corners SW, SE, NE, NW of every sampled cell)
-// *curvilinear = 1 if a sampled cell's west / east corners differ in longitude or its south / north corners in latitude (bit
-// patterns, the test k_rect_tables applies to the whole grid): such a target cannot take the rectilinear path, and the search does
-// not spend an attempt on finding that out (a cubed-sphere tile as target: 0.2 ms of kernels and a read-back per plan)
-static int sample_extents_dev(fg_plan *pl, int nx, int ny, const double *d_lon, const double *d_lat, double *mdlat, double *mdlon,
-                              int *curvilinear)
-{
-  *curvilinear = 0;
-  const double PI = 3.14159265358979323846;
-  const long ncell = (long)nx * ny;
-  long step = ncell / 4096; if (step < 1) step = 1;
-  const int nsamp = (int)((ncell + step - 1) / step);
-  double *d_q = (double *)g_pool.get(pl->device, (size_t)nsamp * 8 * sizeof(double));
-  if (!d_q) return fail(FG_ERR_HIP, "out of device memory");
-  std::vector<double> q((size_t)nsamp * 8);
-  k_sample_corners<<<(nsamp + 255) / 256, 256, 0, pl->stream>>>(nx, ny, step, nsamp, 2, d_lon, d_lat, nullptr, d_q);
-  hipError_t e = hipMemcpyAsync(q.data(), d_q, q.size() * sizeof(double), hipMemcpyDeviceToHost, pl->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(pl->stream);
-  g_pool.put(d_q);
-  if (e != hipSuccess) return fail(FG_ERR_HIP, "sampling the destination corners failed: %s", hipGetErrorString(e));
   double sl = 0, sw = 0; long cnt = 0;
-  for (int k = 0; k < nsamp; k++) {
-    const double *x = &q[(size_t)k * 4], *y = &q[((size_t)nsamp + k) * 4];
-    if (memcmp(&x[0], &x[3], 8) || memcmp(&x[1], &x[2], 8) || memcmp(&y[0], &y[1], 8) || memcmp(&y[3], &y[2], 8)) *curvilinear = 1;
-    double ymin = y[0], ymax = y[0], w = 0;
-    for (int m = 1; m < 4; m++) { if (y[m] < ymin) ymin = y[m]; if (y[m] > ymax) ymax = y[m]; }
-    for (int m = 0; m < 4; m++) {                         // |remainder(dx, 2 pi)| without the library call where |dx| <= 3 pi (16 k calls per plan)
-      double d = fabs(x[(m + 1) & 3] - x[m]);
-      if (d > 3.0 * PI) d = fabs(remainder(d, 2.0 * PI)); else if (d > PI) d = fabs(2.0 * PI - d);
-      if (d > w) w = d;
-    }
-    if (w > PI / 2) continue;      // polar caps: not representative
-    sl += ymax - ymin; sw += w; cnt++;
-  }
-  if (cnt == 0) { *mdlat = PI / 180; *mdlon = PI / 180; return 0; }
-  *mdlat = sl / cnt; *mdlon = sw / cnt;
-  if (*mdlat < 1e-7) *mdlat = 1e-7;
-  if (*mdlon < 1e-7) *mdlon = 1e-7;
-  return 0;
-}
-static int sample_extents_xyz_dev(fg_plan *pl, int nx, int ny, const double *d_x, const double *d_y, const double *d_z, double *mdlat, double *mdlon)
-{
-  const double PI = 3.14159265358979323846;
-  const long ncell = (long)nx * ny;
-  long step = ncell / 4096; if (step < 1) step = 1;
-  const int nsamp = (int)((ncell + step - 1) / step);
-  double *d_q = (double *)g_pool.get(pl->device, (size_t)nsamp * 12 * sizeof(double));
-  if (!d_q) return fail(FG_ERR_HIP, "out of device memory");
-  std::vector<double> q((size_t)nsamp * 12);
-  k_sample_corners<<<(nsamp + 255) / 256, 256, 0, pl->stream>>>(nx, ny, step, nsamp, 3, d_x, d_y, d_z, d_q);
-  hipError_t e = hipMemcpyAsync(q.data(), d_q, q.size() * sizeof(double), hipMemcpyDeviceToHost, pl->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(pl->stream);
-  g_pool.put(d_q);
-  if (e != hipSuccess) return fail(FG_ERR_HIP, "sampling the destination corners failed: %s", hipGetErrorString(e));
-  double sl = 0, sw = 0; long cnt = 0;
-  for (int k = 0; k < nsamp; k++) {                        // (corner 0 and the opposite corner 2, as sample_extents_xyz)
-    const double *x = &q[(size_t)k * 4], *y = &q[((size_t)nsamp + k) * 4], *z = &q[((size_t)2 * nsamp + k) * 4];
+  for (int k = 0; k < s.nsamp; k++) {
+    const double *x = s.corners(0, k), *y = s.corners(1, k), *z = s.corners(2, k);
     const double dx = x[0] - x[2], dy = y[0] - y[2], dz = z[0] - z[2];
     const double diag = sqrt(dx * dx + dy * dy + dz * dz);
     const double zc = 0.5 * (z[0] + z[2]);
@@ -1099,11 +1061,14 @@ static int sample_extents_xyz_dev(fg_plan *pl, int nx, int ny, const double *d_x
     if (coslat < 0.2) continue;
     sl += diag; sw += diag / coslat; cnt++;
   }
-  if (cnt == 0) { *mdlat = PI / 180; *mdlon = PI / 180; return 0; }
-  *mdlat = sl / cnt; *mdlon = sw / cnt;
-  if (*mdlat < 1e-7) *mdlat = 1e-7;
-  if (*mdlon < 1e-7) *mdlon = 1e-7;
-  return 0;
+  mean_extents(sl, sw, cnt, mdlat, mdlon);
+}
+// host corner arrays (the callers have host_says_not_rect for the rectilinear question)
+static void sample_extents(int nx, int ny, const double *lon, const double *lat, double *mdlat, double *mdlon)
+{
+  const double *arr[2] = {lon, lat};
+  int curvilinear;
+  extents_lonlat(sample_corners_host(nx, ny, 2, arr), mdlat, mdlon, &curvilinear);
 }
 
 extern "C" long fg_plan_create(int order, int ntiles_in, const int *nx_in, const int *ny_in,
@@ -1166,9 +1131,11 @@ extern "C" long fg_plan_create_dev(int order, int ntiles_in, const int *nx_in, c
   }
   int curvilinear = 0;
   if (!(mean_dlat > 0) || !(mean_dlon > 0)) {
-    if (hipSetDevice(pl->device) != hipSuccess || sample_extents_dev(pl, nx_out, ny_out, d_lon_out, d_lat_out, &mean_dlat, &mean_dlon, &curvilinear)) {
+    CornerSample s;
+    if (hipSetDevice(pl->device) != hipSuccess || sample_corners_dev(pl, nx_out, ny_out, 2, d_lon_out, d_lat_out, nullptr, &s)) {
       fg_plan_destroy(pl); return FG_ERR_HIP;
     }
+    extents_lonlat(s, &mean_dlat, &mean_dlon, &curvilinear);
   }
   long nx = plan_search(pl, d_lon_in, d_lat_in, d_mask_in, d_lon_out, d_lat_out, mean_dlat, mean_dlon, nullptr, nullptr, nullptr, !curvilinear);
   if (nx < 0) { fg_plan_destroy(pl); return nx; }
@@ -1177,29 +1144,6 @@ extern "C" long fg_plan_create_dev(int order, int ntiles_in, const int *nx_in, c
 }
 
 // ------------------------------------------------------------------------------------- great-circle plans
-// typical destination cap-box extent from a strided sample of unit-vector corners (host copies)
-static void sample_extents_xyz(int nx, int ny, const double *x, const double *y, const double *z, double *mdlat, double *mdlon)
-{
-  const double PI = 3.14159265358979323846;
-  long ncell = (long)nx * ny;
-  long step = ncell / 4096; if (step < 1) step = 1;
-  double sl = 0, sw = 0; long cnt = 0;
-  for (long c = 0; c < ncell; c += step) {
-    int i = (int)(c % nx), j = (int)(c / nx);
-    long n0 = (long)j * (nx + 1) + i, n2 = n0 + nx + 2;
-    double dx = x[n0] - x[n2], dy = y[n0] - y[n2], dz = z[n0] - z[n2];
-    double diag = sqrt(dx * dx + dy * dy + dz * dz);
-    double zc = 0.5 * (z[n0] + z[n2]);
-    double coslat = sqrt(fmax(0.0, 1.0 - zc * zc));
-    if (coslat < 0.2) continue;
-    sl += diag; sw += diag / coslat; cnt++;
-  }
-  if (cnt == 0) { *mdlat = PI / 180; *mdlon = PI / 180; return; }
-  *mdlat = sl / cnt; *mdlon = sw / cnt;
-  if (*mdlat < 1e-7) *mdlat = 1e-7;
-  if (*mdlon < 1e-7) *mdlon = 1e-7;
-}
-
 extern "C" long fg_plan_create_great_circle_dev(int ntiles_in, const int *nx_in, const int *ny_in,
                                                 const double *const *d_x_in, const double *const *d_y_in, const double *const *d_z_in,
                                                 const double *const *d_mask_in, int nx_out, int ny_out,
@@ -1216,9 +1160,11 @@ extern "C" long fg_plan_create_great_circle_dev(int ntiles_in, const int *nx_in,
     pl->stream = (hipStream_t)stream; pl->own_stream = false;
   }
   if (!(mean_dlat > 0) || !(mean_dlon > 0)) {
-    if (hipSetDevice(pl->device) != hipSuccess || sample_extents_xyz_dev(pl, nx_out, ny_out, d_x_out, d_y_out, d_z_out, &mean_dlat, &mean_dlon)) {
+    CornerSample s;
+    if (hipSetDevice(pl->device) != hipSuccess || sample_corners_dev(pl, nx_out, ny_out, 3, d_x_out, d_y_out, d_z_out, &s)) {
       fg_plan_destroy(pl); return FG_ERR_HIP;
     }
+    extents_xyz(s, &mean_dlat, &mean_dlon);
   }
   std::vector<GcXyz> gin(ntiles_in);
   for (int m = 0; m < ntiles_in; m++) gin[m] = GcXyz{d_x_in[m], d_y_in[m], d_z_in[m]};
@@ -2622,7 +2568,6 @@ extern "C" int fg_halo_map(int ntiles, const int *nx, const int *ny, int ncontac
 struct fg_c2l {
   int device = 0, ntiles = 0;
   hipStream_t stream = nullptr;
-  hipStream_t stream_b = nullptr;   // second stream of the chunked search (always ours)
   bool own_stream = true;
   long ncells = 0, F = 0;
   std::vector<int> nx, ny;

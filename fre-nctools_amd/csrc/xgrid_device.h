@@ -97,20 +97,17 @@ __device__ __forceinline__ double d_ord_val(unsigned long long k)
 #define FG_TILESET_MAX 8
 struct FgTileSet { FgTile t[FG_TILESET_MAX]; int n; };
 
-// The source cells are searched in up to FG_MAX_CHUNKS chunks so that the VALU-bound clip of one chunk runs (on a second
-// stream) beside the latency-bound candidate scan of the next and the compaction of the previous one.
-#define FG_MAX_CHUNKS 8
 // device-side counters of one search (plan.hip reads them back once)
 struct FgCounters {
   unsigned long long total[4];     // [0] bin-table entries  [1] candidate pairs  [2] (unused)  [3] largest region fill
   unsigned long long rows_total;   // total of the destination-row scan (= nxgrid)
   unsigned long long band_keys[2]; // latitude range of the destination cells as ordered keys (source-cell culling)
-  unsigned long long xtot[FG_MAX_CHUNKS];   // running nxgrid after chunk k of the source cells (the last one is nxgrid)
+  unsigned long long xtot;         // total of the accept-count scan (= nxgrid)
   unsigned err[4];
   int heavy_cnt;
   unsigned rect_bad;               // rectilinear path: != 0 = the destination grid failed the check (k_rect_tables)
-  int defer_cnt[FG_MAX_CHUNKS], big_cnt[FG_MAX_CHUNKS];
-  int gc_list2_cnt[FG_MAX_CHUNKS];           // great-circle path: pairs k_gc_walk handed to the one-kernel clip
+  int defer_cnt, big_cnt;
+  int gc_list2_cnt;                // great-circle path: pairs k_gc_walk handed to the one-kernel clip
   unsigned long long stats[FG_NSTATS];
 };
 #define G_ERRBIT_LOOKBACK 128u     // a single-pass scan waited too long for its predecessor tile (never observed)
@@ -118,9 +115,8 @@ struct FgCounters {
 // single-pass exclusive scan (decoupled look-back): n inputs -> n+1 prefixes (out[n] = total, also 64-bit in *total_dev).
 // status: zeroed words, one per tile of 2048 inputs (fgd_scan_tiles); ticket: zeroed word
 long fgd_scan_tiles(long n);
-// base_dev (may be null): a device value added to every prefix and to the total (chunked scans)
 void fgd_exclusive_scan1(const int *in, long n, int *out, unsigned long long *status, unsigned *ticket,
-                         unsigned long long *total_dev, unsigned *err, hipStream_t st, const unsigned long long *base_dev = nullptr);
+                         unsigned long long *total_dev, unsigned *err, hipStream_t st);
 
 void fgd_exclusive_scan2(const int *in_a, long n_a, int *out_a, unsigned long long *status_a, unsigned *ticket_a, unsigned long long *total_a,
                          const int *in_b, long n_b, int *out_b, unsigned long long *status_b, unsigned *ticket_b, unsigned long long *total_b,
@@ -139,8 +135,7 @@ void fgd_bin_count(int ncells, FgCells c, FgBins b, int *slot_cnt, hipStream_t s
 // bin fill + list of the source cells whose candidate scan gets a whole wave
 void fgd_bin_fill(int ndst, FgCells D, FgBins b, int *slot_fill, const int *slot_start, FgBinEntry *entries, int cap,
                   int nsrc, FgCells S, const double *mask, int *heavy_list, int *heavy_cnt, hipStream_t st);
-// source cells [c0, c1) only (one chunk); ps, pair_beg are the chunk's
-void fgd_candidates1(int c0, int c1, FgCells S, const double *mask, FgBins b, const int *slot_start, const FgBinEntry *entries, int ecap,
+void fgd_candidates1(int nsrc, FgCells S, const double *mask, FgBins b, const int *slot_start, const FgBinEntry *entries, int ecap,
                      FgPairSpace ps, int *pair_beg, int *pair_cnt, const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt,
                      hipStream_t st);
 // A rectilinear destination grid (lon_out a function of the column, lat_out of the row, bit for bit): see k_rect_tables.
@@ -192,11 +187,9 @@ struct FgCompactIo {
   const int *tmp_rowpos;             // != null: row slots per PAIR from the clip kernels; row_ptr is final and perm is stored here
   const int *row_ptr; int *perm;
   double *sums;                      // [3][nsrc] (order 2, zeroed: cells without exchange cells are not visited) or null
-  const int *big_list;               // the chunk's cells with more than CP_SMALL pairs (from the candidate kernel)
+  const int *big_list;               // the cells with more than CP_SMALL pairs (from the candidate kernel)
   const int *big_cnt;
-  const unsigned *fill_all;          // last chunk only: fill counters of ALL regions, summed up into dc->total[1] / [3]; else null
-  int nreg_all;
-  FgCounters *dc;
+  FgCounters *dc;                    // total[1] / [3]: sum and maximum of the pair space's region fill counters, stored here
   long xcap;                         // entries the x_* arrays hold
 };
 void fgd_compact(int order, int nsrc, FgPairSpace ps, const FgCompactIo &io, hipStream_t st);

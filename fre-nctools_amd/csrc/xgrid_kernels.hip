@@ -128,7 +128,7 @@ __device__ inline unsigned long long d_lookback_wave(unsigned long long *status,
 
 // out[i] = exclusive prefix for i in [0, n] (n inputs, n+1 outputs; 32-bit offsets, 64-bit total for the host's checks)
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan1(const int *in, long n, int *out, unsigned long long *status, unsigned *ticket,
-                                                        unsigned long long *total_out, unsigned *err, const unsigned long long *base_in)
+                                                        unsigned long long *total_out, unsigned *err)
 {
   __shared__ unsigned tile[SCAN_CHUNK];
   __shared__ int sh_t;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan1(const int *in, long n, i
   const unsigned inc = block_incl_scan(s, &tot);
   if (threadIdx.x < 64) {
     const unsigned long long e = d_lookback_wave(status, t, (unsigned long long)tot, err);
-    if (threadIdx.x == 0) sh_excl = e + (base_in ? *base_in : 0ull);
+    if (threadIdx.x == 0) sh_excl = e;
   }
   __syncthreads();
   const unsigned long long excl = sh_excl;
@@ -230,11 +230,11 @@ void fgd_exclusive_scan2(const int *in_a, long n_a, int *out_a, unsigned long lo
 }
 
 void fgd_exclusive_scan1(const int *in, long n, int *out, unsigned long long *status, unsigned *ticket,
-                         unsigned long long *total_dev, unsigned *err, hipStream_t st, const unsigned long long *base_dev)
+                         unsigned long long *total_dev, unsigned *err, hipStream_t st)
 {
   if (n < 0) n = 0;
   const int nt = (int)fgd_scan_tiles(n);
-  k_scan1<<<nt, SCAN_THREADS, 0, st>>>(in, n, out, status, nt <= 1024 ? nullptr : ticket, total_dev, err, base_dev);
+  k_scan1<<<nt, SCAN_THREADS, 0, st>>>(in, n, out, status, nt <= 1024 ? nullptr : ticket, total_dev, err);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -752,7 +752,7 @@ __device__ __forceinline__ int d_lane_scan(const SrcQuery &q, int sub, FgBins b,
 // (one wave per block: a block gives its slots back when its slowest wave is done, and the scan lengths vary a lot --
 // measured 256 / 128 / 64 threads: 0.240 / 0.230 / 0.224 ms for the old count pass)
 // The listed cells come FIRST in the grid: their waves run long and should start with the others, not after them.
-__global__ __launch_bounds__(64) void k_candidates1(int c0, int c1, int H, FgCells S, const double *mask, FgBins b, const int *slot_start,
+__global__ __launch_bounds__(64) void k_candidates1(int nsrc, int H, FgCells S, const double *mask, FgBins b, const int *slot_start,
                                                      const FgBinEntry *entries, int ecap, FgPairSpace ps, int *pair_beg, int *pair_cnt,
                                                      const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt)
 {
@@ -761,7 +761,6 @@ __global__ __launch_bounds__(64) void k_candidates1(int c0, int c1, int H, FgCel
     const int nheavy = *heavy_cnt;
     for (int h = blockIdx.x; h < nheavy; h += H) {
       const int s = heavy_list[h];
-      if (s < c0 || s >= c1) continue;                    // another chunk's
       const double lat_in_min = S.lat_min[s], lat_in_max = S.lat_max[s];
       const double lon_in_min = S.lon_min[s], lon_in_max = S.lon_max[s], lon_in_avg = S.lon_avg[s];
       const SrcQuery q = d_src_query(lat_in_min, lat_in_max, lon_in_min, lon_in_max, b);
@@ -784,8 +783,7 @@ __global__ __launch_bounds__(64) void k_candidates1(int c0, int c1, int H, FgCel
   }
   const int bR = (int)blockIdx.x - H;                  // block among the four-lanes-per-cell blocks
   const long t = (long)bR * 64 + lane;
-  const int s = c0 + (int)(t / CAND_G), sub = (int)(t % CAND_G);
-  const int nsrc = c1;
+  const int s = (int)(t / CAND_G), sub = (int)(t % CAND_G);
   int cnt = 0;
   int ids[4] = {-1, -1, -1, -1};
   bool heavy = false;
@@ -1790,9 +1788,9 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
   int *pref = (int *)(lds + RANK_WORDS);                             // [RANK_WORDS]
   double (*sval)[BIG_STAGE] = (double (*)[BIG_STAGE])(lds + RANK_WORDS + RANK_WORDS / 2);   // [3][BIG_STAGE]
   __shared__ int smin, smax;
-  if (io.fill_all && blockIdx.x == 0 && threadIdx.x < 64) {           // candidate totals for the host's capacity checks
+  if (blockIdx.x == 0 && threadIdx.x < 64) {                  // candidate totals for the host's capacity checks
     unsigned long long f = 0; unsigned mx = 0;
-    for (int r = threadIdx.x; r < io.nreg_all; r += 64) { const unsigned v = io.fill_all[r * FG_FILL_STRIDE]; f += v; mx = max(mx, v); }
+    for (int r = threadIdx.x; r < ps.nreg; r += 64) { const unsigned v = ps.fill[r * FG_FILL_STRIDE]; f += v; mx = max(mx, v); }
 #pragma unroll
     for (int o = 32; o; o >>= 1) { f += __shfl_xor(f, o); mx = max(mx, (unsigned)__shfl_xor((int)mx, o)); }
     if (threadIdx.x == 0) { io.dc->total[1] = f; io.dc->total[3] = mx; }
@@ -1993,16 +1991,16 @@ void fgd_bin_fill(int ndst, FgCells D, FgBins b, int *slot_fill, const int *slot
     k_bin_fill<<<nbD + nbS, 256, 0, st>>>(ndst, nbD, D, b, slot_fill, slot_start, entries, cap, nsrc, S, mask, heavy_list, heavy_cnt);
 }
 
-void fgd_candidates1(int c0, int c1, FgCells S, const double *mask, FgBins b, const int *slot_start, const FgBinEntry *entries, int ecap,
+void fgd_candidates1(int nsrc, FgCells S, const double *mask, FgBins b, const int *slot_start, const FgBinEntry *entries, int ecap,
                      FgPairSpace ps, int *pair_beg, int *pair_cnt, const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt,
                      hipStream_t st)
 {
-  if (c1 <= c0) return;
-  const int nbR = nblk((long)(c1 - c0) * CAND_G, 64);
+  if (nsrc <= 0) return;
+  const int nbR = nblk((long)nsrc * CAND_G, 64);
   // (as in fgd_candidates_rect, but up to eight times the waves: a curvilinear target that contains a pole -- a polar tile of a cubed
   // sphere -- lists a fifth of a lat-lon source grid's cells; 0.25 deg -> C384 tile 3: tile 2.8 -> 2.07 ms; 8192 waves: 2.20)
-  const int H = min(8 * HEAVY_BLOCKS, max(64, nblk(c1 - c0, 8)));
-  k_candidates1<<<nbR + H, 64, 0, st>>>(c0, c1, H, S, mask, b, slot_start, entries, ecap, ps, pair_beg, pair_cnt, heavy_list, heavy_cnt, big_list, big_cnt);
+  const int H = min(8 * HEAVY_BLOCKS, max(64, nblk(nsrc, 8)));
+  k_candidates1<<<nbR + H, 64, 0, st>>>(nsrc, H, S, mask, b, slot_start, entries, ecap, ps, pair_beg, pair_cnt, heavy_list, heavy_cnt, big_list, big_cnt);
 }
 
 void fgd_clip_quad(int order, FgPairSpace ps, FgCells S, const double *mask, FgCells D,

@@ -362,10 +362,6 @@ int fg_plan_stats(const fg_plan *plan, long *stats, int n);
  * outgrows a capacity is repeated transparently with the sizes its counters report.  1: size every buffer by counting
  * first (extra passes; smallest plans).  Also selectable with the environment variable FREGRID_HIP_EXACT_SEARCH=1. */
 void fg_set_search_mode(int exact);
-/* Chunks of source cells per search: the clip of one chunk runs on a second stream beside the candidate scan of the next and
- * the compaction of the previous one.  0 (default) = 1: one stream, in sequence -- at C384 -> 0.25 deg the overlapped kernels
- * slow each other down by more than the overlap wins.  Results do not depend on it.  Also FREGRID_HIP_CHUNKS. */
-void fg_set_search_chunks(int chunks);
 /* 1: source cells whose latitude range cannot meet the destination grid are skipped when the per-cell records are built (a
  * rank of a banded multi-GPU job meets a fraction of the source cells); fg_plan_get_cell_area / _cell_struct then return 0 /
  * unspecified values for those cells.  The exchange cells are unchanged.  Default 0. */

@@ -1,7 +1,6 @@
 """Randomised check of the legacy (lon-lat plane) search, order 2: the single-sync search (default: the rectilinear-target path when
 the target is a lat-lon grid, global / regional / stretched / on -180..180) against the exactly sized one (fg_set_search_mode(1)),
-against the GENERIC bins path (fg_set_search_rect(0)), against the generic path in 3 chunks of source cells and against a culling
-search, on pairs of random grids (lat-lon windows and global grids, cubed-sphere
+against the GENERIC bins path (fg_set_search_rect(0)) and against a culling search, on pairs of random grids (lat-lon windows and global grids, cubed-sphere
 faces, tripolar, rotated versions of them); small cases also against the CPU oracle (lists identical, areas / centroid integrals bit
 for bit where the host libm matches).  Both sides stopping with the same reference error counts as agreement.
 usage: python scripts/legacy_fuzz.py [cases] [seed]"""
@@ -58,8 +57,8 @@ def random_grid(small):
     return g
 
 
-def run(a, b, mode, chunks, rect=1, cull=0):
-    fg.lib().fg_set_search_mode(mode); fg.lib().fg_set_search_chunks(chunks); fg.lib().fg_set_search_rect(rect); fg.lib().fg_set_search_cull(cull)
+def run(a, b, mode, rect=1, cull=0):
+    fg.lib().fg_set_search_mode(mode); fg.lib().fg_set_search_rect(rect); fg.lib().fg_set_search_cull(cull)
     try:
         plan = fg.XgridPlan.create(2, [fg.GridConfig(*a)], fg.GridConfig(*b))
         plan.finalize()
@@ -77,7 +76,7 @@ try:
     for ci in range(ncase):
         small = rng.random() < 0.5
         a, b = random_grid(small), random_grid(small)
-        res = [run(a, b, 0, 0), run(a, b, 1, 0), run(a, b, 0, 0, rect=0), run(a, b, 0, 3, rect=0), run(a, b, 0, 0, cull=1)]
+        res = [run(a, b, 0), run(a, b, 1), run(a, b, 0, rect=0), run(a, b, 0, cull=1)]
         x0, e0, s0 = res[0]
         for x, e, s in res[1:]:
             assert e == e0, (ci, e0, e)
@@ -114,7 +113,7 @@ try:
                 tag += " = oracle"
         print(f"case {ci}: {a[0]}x{a[1]} vs {b[0]}x{b[1]}: nxgrid {len(x0['area'])}, pairs {s0['pairs']}, exact_mode {s0['exact_mode']}{tag}", flush=True)
 finally:
-    fg.lib().fg_set_search_mode(0); fg.lib().fg_set_search_chunks(0); fg.lib().fg_set_search_rect(1); fg.lib().fg_set_search_cull(0)
+    fg.lib().fg_set_search_mode(0); fg.lib().fg_set_search_rect(1); fg.lib().fg_set_search_cull(0)
 print(f"legacy_fuzz: {ncase} grid pairs, {ncase - nerr} searched ({nerr} stopped by the same reference error in all variants), {nx_tot} exchange cells, "
-      f"default == exactly sized == generic path == generic in 3 chunks == culling search bit for bit ({nrect} targets took the rectilinear path); "
+      f"default == exactly sized == generic path == culling search bit for bit ({nrect} targets took the rectilinear path); "
       f"{norc} of them also equal to the CPU oracle")

@@ -453,21 +453,49 @@ def generic_path(fg):
     fg.lib().fg_set_search_rect(1)
 
 
-def test_chunked_search_gives_the_same_plan(fg, gpu_ok, generic_path):
-    """Large grids are searched in chunks of source cells (clip of one chunk on a second stream beside the candidate scan of
-    the next): force 1, 3 and 8 chunks on a small case -- exchange cells, order-2 integrals and the sweep must not change."""
+def test_generic_search_of_a_latlon_target_vs_oracle(fg, gpu_ok, generic_path):
+    """C24 -> 72 x 36, order 2, on the generic (bins) path that a lat-lon target does not take by default: exchange cells and
+    order-2 integrals against the oracle."""
     lon, lat = fg.gnomonic_ed_corners(24)
     lo, la = fg.latlon_corners(72, 36)
     gin, gout = [(24, 24, lon[t], lat[t]) for t in range(6)], (72, 36, lo, la)
-    res = []
-    try:
-        for k in (1, 3, 8):
-            fg.lib().fg_set_search_chunks(k)
-            res.append(_plan_vs_oracle(fg, 2, gin, gout))
-    finally:
-        fg.lib().fg_set_search_chunks(0)
-    assert res[0][0] == res[1][0] == res[2][0] > 0
-    assert res[0][1]["pairs"] == res[1][1]["pairs"] == res[2][1]["pairs"]
+    n, st = _plan_vs_oracle(fg, 2, gin, gout)
+    assert n > 0 and st["bins"] > 0 and st["pairs"] >= n
+
+
+def test_sampled_extents_are_the_same_from_host_and_device_corners(fg, gpu_ok):
+    """The mean cell extents that size the bins come from a strided sample of the target's corners, taken by a host loop
+    (XgridPlan.create) or by a kernel (create_dev with mean_dlat = mean_dlon = 0): one estimator, so the same bins, bin records,
+    candidate pairs and exchange cells.  Two generic-path targets with a sampling stride above 1."""
+    import torch
+    dev = "cuda:0"
+    c24, c96 = fg.gnomonic_ed_corners(24), fg.gnomonic_ed_corners(96)
+    lo144, la144 = fg.latlon_corners(144, 90)
+    lo72, la72 = fg.latlon_corners(72, 36)
+    cases = [
+        # 144 x 90 global lat-lon from C24: 12 960 cells, stride 3 (generic path by the hook)
+        ([(24, 24, c24[0][t], c24[1][t]) for t in range(6)], (144, 90, lo144, la144), 0),
+        # one C96 tile from 72 x 36 lat-lon: 9 216 cells, stride 2, curvilinear
+        ([(72, 36, lo72, la72)], (96, 96, c96[0][1], c96[1][1]), 1),
+    ]
+    for gin, gout, rect in cases:
+        assert gout[0] * gout[1] // 4096 > 1
+        fg.lib().fg_set_search_rect(rect)
+        try:
+            ph = fg.XgridPlan.create(1, [fg.GridConfig(*g) for g in gin], fg.GridConfig(*gout))
+            t = [[torch.from_numpy(np.ascontiguousarray(g[k])).to(dev) for g in gin] for k in (2, 3)]
+            lo_t, la_t = (torch.from_numpy(np.ascontiguousarray(gout[k])).to(dev) for k in (2, 3))
+            torch.cuda.synchronize()
+            pd = fg.XgridPlan.create_dev(1, [g[0] for g in gin], [g[1] for g in gin], t[0], t[1], gout[0], gout[1], lo_t, la_t, 0.0, 0.0)
+        finally:
+            fg.lib().fg_set_search_rect(1)
+        sh, sd = ph.stats(), pd.stats()
+        nh, nd = ph.nxgrid, pd.nxgrid
+        ph.destroy(); pd.destroy()
+        assert sh["bins"] > 0 and nh > 0
+        for k in ("bins", "bin_entries", "pairs"):
+            assert sh[k] == sd[k], (k, sh[k], sd[k])
+        assert nh == nd
 
 
 def test_source_cell_culling_keeps_the_plan(fg, gpu_ok):
