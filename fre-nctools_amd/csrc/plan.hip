@@ -603,6 +603,11 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   // Queue order (legacy search, 11 launches + 1 readback; the host synchronises ONCE, at the end):
   //   memset | cell records + bin counts | bin scan | bin fill + heavy list | candidates | quad clip | general clip |
   //   compaction (+ big cells) | row scan | row slots -> perm | counters -> host
+  // Rectilinear target (8 launches): memset | axis tables + check | source records + candidates + destination areas | candidates of
+  //   the listed (heavy) cells | quad clip | general clip | the two scans | compaction | counters -> host
+  //   (no launch fewer than before the record kernel made the candidates: the listed cells keep theirs, now min(2048, nsrc / 8)
+  //   one-wave blocks instead of those + nsrc / 64)
+  //   phase_ms: "cell_struct" covers the tables and the record kernel, candidates included; "candidates" the listed cells' launch
   const bool gc = gc_in != nullptr;
   pl->great_circle = gc;
   hipStream_t st = pl->stream;
@@ -667,16 +672,16 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
 
   if (!alloc_cells(pl, &pl->S, nsrc)) return fail(FG_ERR_HIP, "out of device memory");
   SearchBlocks blk{pl};
-  struct { double *hdr, *lat_ax, *lon_ax, *col, *row; } rt{};   // the rectilinear tables, one block (FgRect, xgrid_device.h)
+  struct { double *hdr, *lat_ax, *lon_ax, *col, *row, *col_min, *col_max, *col_avg; } rt{};   // the rectilinear tables, one block (FgRect, xgrid_device.h)
   if (rect) {
     pl->D = FgCells{};
     pl->D.area = blk.keep<double>(ndst);
     Carve at;                                         // (in doubles)
     const size_t o_hdr = at(8), o_lat = at((size_t)pl->ny_out + 1), o_lon = at((size_t)pl->nx_out + 1), o_col = at(8 * (size_t)pl->nx_out),
-                 o_row = at(4 * ((size_t)pl->ny_out + 1));
+                 o_row = at(4 * ((size_t)pl->ny_out + 1)), o_cmin = at((size_t)pl->nx_out), o_cmax = at((size_t)pl->nx_out), o_cavg = at((size_t)pl->nx_out);
     double *rect_blk = blk.keep<double>(at.n);
     if (!blk.ok) return fail(FG_ERR_HIP, "out of device memory");
-    rt = {rect_blk + o_hdr, rect_blk + o_lat, rect_blk + o_lon, rect_blk + o_col, rect_blk + o_row};
+    rt = {rect_blk + o_hdr, rect_blk + o_lat, rect_blk + o_lon, rect_blk + o_col, rect_blk + o_row, rect_blk + o_cmin, rect_blk + o_cmax, rect_blk + o_cavg};
   } else if (!alloc_cells(pl, &pl->D, ndst)) return fail(FG_ERR_HIP, "out of device memory");
   // one zeroed block: [counters | region fill counters | tickets | look-back words of the three scans | bin counts |
   //                    bin fill cursors | destination-row counts | accepted pairs per source cell | great-circle task counters]
@@ -750,11 +755,14 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
     // tables + on-device verification of the grid, then the source records, the heavy list and the destination AREAS in one launch
     FgRect &R = pl->rect_tab;
     R.hdr = rt.hdr; R.lat_ax = rt.lat_ax; R.lon_ax = rt.lon_ax; R.col = rt.col; R.row = rt.row;
+    R.col_min = rt.col_min; R.col_max = rt.col_max; R.col_avg = rt.col_avg;
     R.bad = &dc->rect_bad; R.nx = pl->nx_out; R.ny = pl->ny_out;
-    fgd_rect_tables(d_lon_out, d_lat_out, pl->nx_out, pl->ny_out, rt.hdr, rt.lat_ax, rt.lon_ax, rt.col, rt.row, &dc->rect_bad, dc->err, st, dst_tlon);
+    fgd_rect_tables(d_lon_out, d_lat_out, pl->nx_out, pl->ny_out, rt.hdr, rt.lat_ax, rt.lon_ax, rt.col, rt.col_min, rt.col_max, rt.col_avg, rt.row,
+                    &dc->rect_bad, dc->err, st, dst_tlon);
     if (pl->polys.npoly) fgd_polylist_records(pl->polys, pl->S, pl->src_idx_f, pl->sums, &R, heavy_list, &dc->heavy_cnt, dc->err, st);
     fgd_cell_struct2r(ts, pl->tiles_dev, pl->tiles_dev, pl->ntiles, pl->polys.npoly ? 0 : nsrc, ndst, pl->S, pl->D.area, R, pl->mask_dev, order,
-                      pl->src_idx_f, pl->sums, dc->err, st, dc->band_keys, (g_search_cull && !pl->polys.npoly) ? 2 : 0, heavy_list, &dc->heavy_cnt);
+                      pl->src_idx_f, pl->sums, dc->err, st, dc->band_keys, (g_search_cull && !pl->polys.npoly) ? 2 : 0, heavy_list, &dc->heavy_cnt,
+                      ps, pair_beg, pair_cnt, big_list, &dc->big_cnt);
   } else if (g_search_cull && !boxm && !pl->polys.npoly) {
     // the destination grid's latitude range from its corners (a 5 us reduction), then ONE record launch in which the source
     // blocks that cannot meet it leave early (round 2 first ran a destination launch, then a source launch: two latency floors)
@@ -780,7 +788,8 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
 
   pt.begin(PH_CANDIDATES);
   if (rect)
-    fgd_candidates_rect(nsrc, pl->S, pl->mask_dev, pl->rect_tab, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list, &dc->big_cnt, st);
+    fgd_candidates_rect(nsrc, pl->S, pl->mask_dev, pl->rect_tab, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list, &dc->big_cnt, st,
+                        pl->polys.npoly ? 0 : 1);         // (the record kernel made the candidates of every cell that is not listed)
   else
     fgd_candidates1(nsrc, pl->S, pl->mask_dev, bins, bin_start, bin_entries, ecap, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list,
                     &dc->big_cnt, st);

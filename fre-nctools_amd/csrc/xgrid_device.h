@@ -145,6 +145,7 @@ struct FgRect {
   const double *lon_ax;   // [nx+1] raw longitude axis (copy of row 0 of lon_out)
   const double *lat_ax;   // [ny+1] compact copy of lat_out[j][0]
   const double *col;      // [nx][8] per column: the four longitudes after fix_lon (SW, SE, NE, NW), lon_min, lon_max, lon_avg, width
+  const double *col_min, *col_max, *col_avg;   // [nx] each: col[i][4], [5], [6] once more as plain arrays, for the candidates' column test
   const double *hdr;      // [8] lon[0], nx / (lon[nx] - lon[0]), lat[0], ny / (lat[ny] - lat[0])
   const double *row;      // [ny+1][4] per latitude-axis value j: sin(lat[j]); and of row j: sin of the mid latitude, sin(dy)/dy of half the
                           // height, 1.0 if the row is flatter than 1e-10 -- what poly_area evaluates on a cell of that row
@@ -152,10 +153,12 @@ struct FgRect {
   int nx, ny;
 };
 void fgd_rect_tables(const double *lon, const double *lat, int nx, int ny, double *hdr, double *lat_ax, double *lon_ax, double *col,
-                     double *row, unsigned *bad, unsigned *err, hipStream_t st, double dst_tlon = 3.14159265358979323846);
+                     double *col_min, double *col_max, double *col_avg, double *row, unsigned *bad, unsigned *err, hipStream_t st,
+                     double dst_tlon = 3.14159265358979323846);
 void fgd_cell_struct2r(const FgTileSet &ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst, FgCells S, double *area_out,
                        FgRect R, const double *mask, int order, int *src_idx_f, double *sums, unsigned *err, hipStream_t st,
-                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt);
+                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt, FgPairSpace ps, int *pair_beg, int *pair_cnt,
+                       int *big_list, int *big_cnt);   // source blocks also make the candidates of their cells (all but the listed ones)
 void fgd_rect_materialize(int ndst, FgRect R, FgCells D, hipStream_t st);
 // Source "cells" given as a list of polygons (<= 8 vertices each, already in the longitude frame they are to be clipped in):
 // fills the source records a search needs (box, vertices, the caller's lon_avg and reference area), the field index, zeroes the
@@ -164,7 +167,7 @@ struct FgPolyList { const int *n; const double *lon, *lat; const double *lon_avg
 void fgd_polylist_records(FgPolyList P, FgCells S, int *src_idx_f, double *sums, const FgRect *rect, int *heavy_list, int *heavy_cnt,
                           unsigned *err, hipStream_t st);
 void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPairSpace ps, int *pair_beg, int *pair_cnt,
-                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st);
+                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only);
 // rect != null: the destination cells come from the rectilinear tables (D holds areas only)
 void fgd_clip_general(int order, FgPairSpace ps, FgCells S, const double *mask, FgCells D,
               double *tmp_area, double *tmp_clon, double *tmp_clat, int *nacc, int *defer_list, int *defer_cnt,

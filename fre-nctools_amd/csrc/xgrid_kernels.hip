@@ -867,7 +867,8 @@ __global__ __launch_bounds__(64) void k_candidates1(int nsrc, int H, FgCells S, 
 #define RECT_HEAVY 48         // rows x window columns above which a source cell's candidates are made by a whole wave
 
 __global__ __launch_bounds__(256) void k_rect_tables(const double *lon, const double *lat, int nx, int ny, double *hdr, double *lat_ax,
-                                                      double *lon_ax, double *col, double *row, unsigned *bad, unsigned *err, double dst_tlon)
+                                                      double *lon_ax, double *col, double *col_min, double *col_max, double *col_avg, double *row,
+                                                      unsigned *bad, unsigned *err, double dst_tlon)
 {
   d_load_trig_table();                                   // (barrier inside)
   const long np = (long)(nx + 1) * (ny + 1);
@@ -904,13 +905,14 @@ __global__ __launch_bounds__(256) void k_rect_tables(const double *lon, const do
     y[0] = 0.0; y[1] = 0.0; y[2] = 0.1; y[3] = 0.1;
     const int n = d_fix_lon(x, y, 4, dst_tlon);
     double *c = col + (size_t)gid * RECT_COLW;
-    if (n != 4) { b = true; for (int k = 0; k < RECT_COLW; k++) c[k] = 0.0; }
+    if (n != 4) { b = true; for (int k = 0; k < RECT_COLW; k++) c[k] = 0.0; col_min[gid] = 0.0; col_max[gid] = 0.0; col_avg[gid] = 0.0; }
     else {
       double xmin = x[0], xmax = x[0], xs = 0;                                                  // as in d_cell_record
       for (int k = 1; k < 4; k++) { if (x[k] < xmin) xmin = x[k]; if (x[k] > xmax) xmax = x[k]; }
       for (int k = 0; k < 4; k++) xs += x[k];
       xs /= 4;
       c[0] = x[0]; c[1] = x[1]; c[2] = x[2]; c[3] = x[3]; c[4] = xmin; c[5] = xmax; c[6] = xs; c[7] = x1 - x0;
+      col_min[gid] = xmin; col_max[gid] = xmax; col_avg[gid] = xs;                              // c[4..6] again, laid out for d_rect_col_pass
     }
   }
   if (gid == 0) {
@@ -940,7 +942,7 @@ struct RectQuery { int j0, j1; int nw; int wa[3], wb[3]; };   // rows [j0, j1]; 
 
 __device__ __forceinline__ RectQuery d_rect_query(const FgRect &R, double lat_in_min, double lat_in_max, double lon_in_min, double lon_in_max)
 {
-  RectQuery q;
+  RectQuery q{};
   const double lon0 = R.hdr[0], inv_lon = R.hdr[1], lat0 = R.hdr[2], inv_lat = R.hdr[3];
   // rows that pass create_xgrid.c:1055: lat[j+1] > lat_in_min && lat[j] < lat_in_max
   q.j0 = max(d_axis_first<true>(R.lat_ax, R.ny + 1, lat_in_min, lat0, inv_lat) - 1, 0);
@@ -958,14 +960,18 @@ __device__ __forceinline__ RectQuery d_rect_query(const FgRect &R, double lat_in
     if (!(axh > lo) || !(axl < hi)) continue;
     const int a = max(d_axis_first<true>(R.lon_ax, R.nx + 1, lo, lon0, inv_lon) - 1, 0);
     const int b = min(d_axis_first<false>(R.lon_ax, R.nx + 1, hi, lon0, inv_lon) - 1, R.nx - 1);
-    if (a <= b && q.nw < 3) { q.wa[q.nw] = a; q.wb[q.nw] = b; q.nw++; }
+    if (a <= b && q.nw < 3) {                          // (no indexing by q.nw: the windows stay in registers)
+      if (q.nw == 0) { q.wa[0] = a; q.wb[0] = b; } else if (q.nw == 1) { q.wa[1] = a; q.wb[1] = b; } else { q.wa[2] = a; q.wb[2] = b; }
+      q.nw++;
+    }
   }
   return q;
 }
 __device__ __forceinline__ int d_rect_ncols(const RectQuery &q)
 {
   int n = 0;
-  for (int w = 0; w < q.nw; w++) n += q.wb[w] - q.wa[w] + 1;
+#pragma unroll
+  for (int w = 0; w < 3; w++) if (w < q.nw) n += q.wb[w] - q.wa[w] + 1;
   return n;
 }
 // "Heavy" = the candidates are made by a whole wave instead of one lane.  Decided from the cell's box and the MEAN axis spacings
@@ -985,11 +991,12 @@ __device__ __forceinline__ int d_rect_col(const RectQuery &q, int k)
   if (q.nw > 1 && k >= l0) { i = q.wa[1] + (k - l0); const int l1 = q.wb[1] - q.wa[1] + 1; if (q.nw > 2 && k - l0 >= l1) i = q.wa[2] + (k - l0 - l1); }
   return i;
 }
-// the reference's longitude reject for column record c (create_xgrid.c:1062-1079)
-__device__ __forceinline__ bool d_rect_col_pass(const double *c, double lon_in_min, double lon_in_max, double lon_in_avg)
+// the reference's longitude reject for column i (create_xgrid.c:1062-1079), from the three plain arrays: lanes that test neighbouring
+// columns read neighbouring doubles (the 64-byte column records gave every lane of a load a cache line of its own)
+__device__ __forceinline__ bool d_rect_col_pass(const FgRect &R, int i, double lon_in_min, double lon_in_max, double lon_in_avg)
 {
-  double lon_out_min = c[4], lon_out_max = c[5];
-  const double dx = c[6] - lon_in_avg;
+  double lon_out_min = R.col_min[i], lon_out_max = R.col_max[i];
+  const double dx = R.col_avg[i] - lon_in_avg;
   if (dx < -G_PI)     { lon_out_min += G_TPI; lon_out_max += G_TPI; }
   else if (dx > G_PI) { lon_out_min -= G_TPI; lon_out_max -= G_TPI; }
   return !(lon_out_min >= lon_in_max || lon_out_max <= lon_in_min);
@@ -1019,15 +1026,133 @@ __device__ __forceinline__ double d_rect_area(const double *c, const double *r)
   return area * G_RADIUS * G_RADIUS;
 }
 
-// Rectilinear twin of k_cell_struct2: source blocks make the full records (and list the cells whose candidates a whole wave
-// will make), destination blocks store the cell AREA only.
-__global__ __launch_bounds__(256) void k_cell_struct2r(FgTileSet ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst,
+// position of the k-th (from 0) set bit of m; k < popcount(m)
+__device__ __forceinline__ int d_kth_set_bit(unsigned long long m, unsigned k)
+{
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w; w >>= 1) {
+    const unsigned c = (unsigned)__popcll(m & ((1ull << w) - 1ull));
+    if (k >= c) { k -= c; m >>= w; pos += w; }
+  }
+  return pos;
+}
+
+// The candidates of one wave of source cells, a lane per cell: called by every thread of the block (barriers inside), by the
+// record kernel with the box it has just made and by k_candidates_rect with the stored one.  Per lane: the query, the exact
+// column test into a bit mask (cmask, nc), cnt = rows x columns; then the wave scan, ONE atomic on the region counter (the
+// region is a hash of the wave's number), pair_beg / pair_cnt, the big-cell list.  The pairs are then written by the whole
+// wave: output slot o of the wave's `total` finds its owner lane in the exclusive scan (kept in LDS with the owner's mask and
+// windows), t = o - excl[owner] gives the row t / nc and the (t % nc)-th set bit of the owner's mask the column -- two stores
+// of 64 consecutive ints per 64 pairs, where a lane writing its own ~5 pairs one by one spread every store over ten lines.
+// A cell's pairs stay contiguous, row-major, in ascending destination index.  A lane whose windows hold more than 64 columns
+// without being listed as heavy (a stretched axis: d_rect_heavy goes by the MEAN spacing) re-tests and writes its own pairs,
+// as every lane did before; its slots are skipped by the others (nc = 0 in LDS).
+// Returns whether the cell is heavy (its candidates are made by a wave of k_candidates_rect instead).
+#define RECT_WL_WORDS 10             // LDS words per lane: excl, nc, cmask lo / hi, j0, wa0, l0, wa1 - l0, l0 + l1, wa2 - l0 - l1
+__device__ __forceinline__ bool d_rect_wave_candidates(const FgRect &R, const FgPairSpace &ps, bool active, int s, int nsrc, unsigned wave_no,
+                                                       double lat_in_min, double lat_in_max, double lon_in_min, double lon_in_max,
+                                                       double lon_in_avg, int *pair_beg, int *pair_cnt, int *big_list, int *big_cnt,
+                                                       unsigned *wl /* [64 * RECT_WL_WORDS], this wave's; in other use until the first barrier */)
+{
+  const int lane = threadIdx.x & 63;
+  int cnt = 0, nr = 0, nwc = 0, nc = 0;
+  unsigned long long cmask = 0ull;
+  RectQuery q{};
+  bool heavy = false;
+  if (active) {
+    heavy = d_rect_heavy(R, lat_in_min, lat_in_max, lon_in_min, lon_in_max);   // listed: a whole wave of k_candidates_rect writes its pairs
+    if (!heavy) {
+      q = d_rect_query(R, lat_in_min, lat_in_max, lon_in_min, lon_in_max);
+      nr = max(q.j1 - q.j0 + 1, 0);
+      nwc = d_rect_ncols(q);
+      if (nr > 0) {
+        // the columns that pass, as a bit mask when the windows are narrow enough (the usual case), else only counted here
+        for (int k = 0; k < nwc; k++)
+          if (d_rect_col_pass(R, d_rect_col(q, k), lon_in_min, lon_in_max, lon_in_avg)) { nc++; if (k < 64) cmask |= 1ull << k; }
+      }
+      cnt = (int)min((long)nr * nc, 0x3fffffffL);
+    }
+  }
+  const unsigned incl = wave_incl_scan((unsigned)cnt, lane);
+  const unsigned total = __shfl(incl, 63);
+  const unsigned excl = incl - (unsigned)cnt;
+  const int r = (int)((wave_no * 2654435761u >> 12) % (unsigned)ps.nreg);
+  unsigned base = 0;
+  if (lane == 0 && total) base = atomicAdd(&ps.fill[r * FG_FILL_STRIDE], total);
+  base = __shfl(base, 0);
+  int n_ok = 0;
+  const unsigned first = base + excl;
+  if (s < nsrc && !heavy) {
+    const int loc0 = (int)min(first, (unsigned)ps.regcap);
+    n_ok = min(cnt, ps.regcap - loc0);
+    pair_beg[s] = r * ps.regcap + loc0;
+    pair_cnt[s] = n_ok;
+  }
+  {
+    const bool bigc = n_ok > CP_SMALL;
+    const unsigned long long bm = __ballot(bigc);
+    if (bm) {
+      int qq = 0;
+      if (lane == 0) qq = atomicAdd(big_cnt, __popcll(bm));
+      qq = __shfl(qq, 0);
+      if (bigc) big_list[qq + __popcll(bm & ((1ull << lane) - 1ull))] = s;
+    }
+  }
+  const bool wide = nwc > 64;
+  const int l0 = q.nw > 1 ? q.wb[0] - q.wa[0] + 1 : 64, l1 = q.nw > 2 ? q.wb[1] - q.wa[1] + 1 : 64;    // (mask bits are below 64)
+  __syncthreads();                                           // the caller's use of the LDS behind wl ends here
+  wl[lane] = excl;
+  wl[64 + lane] = wide ? 0u : (unsigned)nc;
+  wl[2 * 64 + lane] = (unsigned)cmask; wl[3 * 64 + lane] = (unsigned)(cmask >> 32);
+  wl[4 * 64 + lane] = (unsigned)q.j0;
+  wl[5 * 64 + lane] = (unsigned)q.wa[0]; wl[6 * 64 + lane] = (unsigned)l0;
+  wl[7 * 64 + lane] = (unsigned)(q.wa[1] - l0); wl[8 * 64 + lane] = (unsigned)(l0 + l1);
+  wl[9 * 64 + lane] = (unsigned)(q.wa[2] - l0 - l1);
+  __syncthreads();
+  // the wave's slots that lie inside the region: o < lim is the owner's clamp t = o - excl < n_ok
+  const unsigned lim = min(total, (unsigned)ps.regcap - min(base, (unsigned)ps.regcap));
+  int *wsrc = ps.src + (size_t)r * ps.regcap + base, *wdst = ps.dst + (size_t)r * ps.regcap + base;
+  const int s_first = s - lane;
+  for (unsigned ob = 0; ob < lim; ob += 64) {
+    const unsigned o = ob + lane;
+    if (o >= lim || base + o >= (unsigned)ps.regcap) continue;   // (the second test repeats, at the store, what lim holds: an attempt with
+                                                                 //  regcap = 0, the exactly sized search's first, must not write at all)
+    int L = 0;                                               // the last lane whose exclusive prefix is <= o: the one with excl <= o < incl
+#pragma unroll
+    for (int st = 32; st; st >>= 1) if (wl[L + st] <= o) L += st;
+    const unsigned ncL = wl[64 + L];
+    if (!ncL) continue;                                      // (a lane that writes its own pairs, below)
+    const unsigned t = o - wl[L], jr = t / ncL, kc = t - jr * ncL;
+    const int k = d_kth_set_bit((unsigned long long)wl[2 * 64 + L] | ((unsigned long long)wl[3 * 64 + L] << 32), kc);
+    const int i = k + (k < (int)wl[6 * 64 + L] ? (int)wl[5 * 64 + L] : k < (int)wl[8 * 64 + L] ? (int)wl[7 * 64 + L] : (int)wl[9 * 64 + L]);
+    wsrc[o] = s_first + L;
+    wdst[o] = ((int)wl[4 * 64 + L] + (int)jr) * R.nx + i;
+  }
+  if (wide && n_ok > 0) {
+    int *psrc = ps.src + (size_t)r * ps.regcap + first, *pdst = ps.dst + (size_t)r * ps.regcap + first;
+    int w = 0;
+    for (int j = q.j0; j <= q.j1 && w < n_ok; j++)
+      for (int k = 0; k < nwc && w < n_ok; k++) {
+        const int i = d_rect_col(q, k);
+        if (d_rect_col_pass(R, i, lon_in_min, lon_in_max, lon_in_avg)) { psrc[w] = s; pdst[w] = j * R.nx + i; w++; }
+      }
+  }
+  return heavy;
+}
+
+// Rectilinear twin of k_cell_struct2: source blocks make the full records AND, from the box still in registers, the candidates of
+// their cells (d_rect_wave_candidates; the cells whose candidates a whole wave will make are listed for k_candidates_rect);
+// destination blocks store the cell AREA only.
+__global__ __launch_bounds__(256, 4) void k_cell_struct2r(FgTileSet ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst,
                                                         int nbS, FgCells S, double *area_out, FgRect R, const double *mask, int order, int *src_idx_f,
                                                         double *sums, unsigned *err, unsigned long long *band_keys, int cull,
-                                                        int *heavy_list, int *heavy_cnt)
+                                                        int *heavy_list, int *heavy_cnt, FgPairSpace ps, int *pair_beg, int *pair_cnt,
+                                                        int *big_list, int *big_cnt)
 {
   __shared__ double vtile[256 * 17];
   __shared__ FgTile sh_tiles[FG_TILESET_MAX];
+  static_assert(64 * RECT_WL_WORDS * sizeof(unsigned) <= 64 * 17 * sizeof(double), "a wave's share of vtile holds its candidate words");
   if (*R.bad) return;
   if (ts.n && (int)threadIdx.x < ts.n) sh_tiles[threadIdx.x] = ts.t[threadIdx.x];
   const bool isD = (int)blockIdx.x >= nbS;
@@ -1062,6 +1187,7 @@ __global__ __launch_bounds__(256) void k_cell_struct2r(FgTileSet ts, const FgTil
     if (!__syncthreads_or(keep)) {
       if (s < nsrc) {
         S.nv[s] = 0; S.area[s] = 0;
+        pair_beg[s] = 0; pair_cnt[s] = 0;                // (no candidates: what the candidate kernel stored for a cell without a record)
         if (src_idx_f) src_idx_f[s] = idx_f;
         if (sums) { sums[s] = 0.0; sums[nsrc + s] = 0.0; sums[2 * (size_t)nsrc + s] = 0.0; }
       }
@@ -1087,8 +1213,13 @@ __global__ __launch_bounds__(256) void k_cell_struct2r(FgTileSet ts, const FgTil
         src_idx_f[s] = foff + (j + 1) * (tiles[tl].nx + 2) + i + 1;
       }
     }
-    bool heavy = false;
-    if (s < nsrc && nv > 0 && (!mask || mask[s] > 0.5)) heavy = d_rect_heavy(R, box[0], box[1], box[2], box[3]);
+    // the candidates, in the wave's share of vtile (d_cell_record is through with it); wave blockIdx.x * 4 + wave holds the cells
+    // [64 * that, + 64), so the region hash is the one of the stand-alone kernel's block numbers
+    // (lon_avg comes back from the record this lane has just stored: held in registers across d_cell_record it cost the kernel
+    //  its fourth block per CU -- 129 VGPRs -- or, under a launch bound, 12 bytes of scratch)
+    const bool active = s < nsrc && nv > 0 && (!mask || mask[s] > 0.5);
+    const bool heavy = d_rect_wave_candidates(R, ps, active, s, nsrc, (unsigned)(s >> 6), box[0], box[1], box[2], box[3], active ? S.lon_avg[s] : 0.0, pair_beg, pair_cnt,
+                                              big_list, big_cnt, (unsigned *)(vtile + (threadIdx.x >> 6) * (64 * 17)));
     const unsigned long long m = __ballot(heavy);
     if (m) {
       int base = 0;
@@ -1161,7 +1292,8 @@ __global__ __launch_bounds__(256) void k_rect_materialize(int ndst, FgRect R, Fg
 }
 
 // Candidates on a rectilinear destination grid.  Blocks [0, H): a wave per listed source cell (pole caps: every column);
-// blocks [H, ...): one lane per source cell.  Pairs of a cell are contiguous and in ascending destination index.
+// blocks [H, ...): one lane per source cell (d_rect_wave_candidates) -- none when the record kernel has made those candidates
+// itself (k_cell_struct2r), all of them for a polygon-list source.  Pairs of a cell are contiguous and in ascending destination index.
 __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells S, const double *mask, FgRect R, FgPairSpace ps,
                                                          int *pair_beg, int *pair_cnt, const int *heavy_list, const int *heavy_cnt,
                                                          int *big_list, int *big_cnt)
@@ -1180,7 +1312,7 @@ __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells
       int nc = 0;
       for (int kb = 0; kb < nwc; kb += 64) {
         const int k = kb + lane;
-        const bool pass = k < nwc && d_rect_col_pass(R.col + (size_t)d_rect_col(q, k) * RECT_COLW, lon_in_min, lon_in_max, lon_in_avg);
+        const bool pass = k < nwc && d_rect_col_pass(R, d_rect_col(q, k), lon_in_min, lon_in_max, lon_in_avg);
         nc += __popcll(__ballot(pass));
       }
       const long cnt_l = (long)nr * nc;
@@ -1195,7 +1327,7 @@ __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells
       for (int kb = 0; kb < nwc && n_ok > 0; kb += 64) {
         const int k = kb + lane;
         int i = 0; bool pass = false;
-        if (k < nwc) { i = d_rect_col(q, k); pass = d_rect_col_pass(R.col + (size_t)i * RECT_COLW, lon_in_min, lon_in_max, lon_in_avg); }
+        if (k < nwc) { i = d_rect_col(q, k); pass = d_rect_col_pass(R, i, lon_in_min, lon_in_max, lon_in_avg); }
         const unsigned long long m = __ballot(pass);
         const int at = cbase + __popcll(m & ((1ull << lane) - 1ull));
         if (pass)
@@ -1209,73 +1341,13 @@ __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells
     }
     return;
   }
+  __shared__ unsigned wl[64 * RECT_WL_WORDS];
   const int bR = (int)blockIdx.x - H;
   const int s = bR * 64 + lane;
-  int cnt = 0, nr = 0, nwc = 0;
-  unsigned long long cmask = 0ull;
-  RectQuery q{};
-  bool heavy = false;
-  double lon_in_min = 0, lon_in_max = 0, lon_in_avg = 0;
-  if (s < nsrc && d_src_active(S, mask, s)) {
-    const double lat_in_min = S.lat_min[s], lat_in_max = S.lat_max[s];
-    lon_in_min = S.lon_min[s]; lon_in_max = S.lon_max[s]; lon_in_avg = S.lon_avg[s];
-    heavy = d_rect_heavy(R, lat_in_min, lat_in_max, lon_in_min, lon_in_max);   // listed by k_cell_struct2r; a whole wave writes its pairs
-    if (!heavy) {
-      q = d_rect_query(R, lat_in_min, lat_in_max, lon_in_min, lon_in_max);
-      nr = max(q.j1 - q.j0 + 1, 0);
-      nwc = d_rect_ncols(q);
-      int nc = 0;
-      if (nr > 0) {
-        // the columns that pass, as a bit mask when the windows are narrow enough (the usual case), else only counted here and
-        // re-tested row by row below
-        for (int k = 0; k < nwc; k++)
-          if (d_rect_col_pass(R.col + (size_t)d_rect_col(q, k) * RECT_COLW, lon_in_min, lon_in_max, lon_in_avg)) { nc++; if (k < 64) cmask |= 1ull << k; }
-      }
-      cnt = (int)min((long)nr * nc, 0x3fffffffL);
-    }
-  }
-  const unsigned incl = wave_incl_scan((unsigned)cnt, lane);
-  const unsigned total = __shfl(incl, 63);
-  const unsigned excl = incl - (unsigned)cnt;
-  const int r = (int)((((unsigned)bR) * 2654435761u >> 12) % (unsigned)ps.nreg);
-  unsigned base = 0;
-  if (lane == 0 && total) base = atomicAdd(&ps.fill[r * FG_FILL_STRIDE], total);
-  base = __shfl(base, 0);
-  int n_ok = 0;
-  const unsigned first = base + excl;
-  if (s < nsrc && !heavy) {
-    const int loc0 = (int)min(first, (unsigned)ps.regcap);
-    n_ok = min(cnt, ps.regcap - loc0);
-    pair_beg[s] = r * ps.regcap + loc0;
-    pair_cnt[s] = n_ok;
-  }
-  {
-    const bool bigc = n_ok > CP_SMALL;
-    const unsigned long long bm = __ballot(bigc);
-    if (bm) {
-      int qq = 0;
-      if (lane == 0) qq = atomicAdd(big_cnt, __popcll(bm));
-      qq = __shfl(qq, 0);
-      if (bigc) big_list[qq + __popcll(bm & ((1ull << lane) - 1ull))] = s;
-    }
-  }
-  if (n_ok <= 0) return;
-  int *psrc = ps.src + (size_t)r * ps.regcap + first, *pdst = ps.dst + (size_t)r * ps.regcap + first;
-  int w = 0;
-  for (int j = q.j0; j <= q.j1 && w < n_ok; j++) {
-    if (nwc <= 64) {
-      unsigned long long m = cmask;
-      while (m && w < n_ok) {
-        const int k = __ffsll((long long)m) - 1; m &= m - 1ull;
-        psrc[w] = s; pdst[w] = j * R.nx + d_rect_col(q, k);
-        w++;
-      }
-    } else
-      for (int k = 0; k < nwc && w < n_ok; k++) {
-        const int i = d_rect_col(q, k);
-        if (d_rect_col_pass(R.col + (size_t)i * RECT_COLW, lon_in_min, lon_in_max, lon_in_avg)) { psrc[w] = s; pdst[w] = j * R.nx + i; w++; }
-      }
-  }
+  const bool active = s < nsrc && d_src_active(S, mask, s);
+  double b[5] = {0, 0, 0, 0, 0};
+  if (active) { b[0] = S.lat_min[s]; b[1] = S.lat_max[s]; b[2] = S.lon_min[s]; b[3] = S.lon_max[s]; b[4] = S.lon_avg[s]; }
+  (void)d_rect_wave_candidates(R, ps, active, s, nsrc, (unsigned)bR, b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt, wl);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2032,21 +2104,22 @@ void fgd_clip_general(int order, FgPairSpace ps, FgCells S, const double *mask, 
 }
 
 // ---- rectilinear destination grid
-void fgd_rect_tables(const double *lon, const double *lat, int nx, int ny, double *hdr, double *lat_ax, double *lon_ax, double *col, double *row,
-                     unsigned *bad, unsigned *err, hipStream_t st, double dst_tlon)
+void fgd_rect_tables(const double *lon, const double *lat, int nx, int ny, double *hdr, double *lat_ax, double *lon_ax, double *col,
+                     double *col_min, double *col_max, double *col_avg, double *row, unsigned *bad, unsigned *err, hipStream_t st, double dst_tlon)
 {
   const long np = (long)(nx + 1) * (ny + 1);
   const int g = (int)std::min<long>(1024, std::max<long>((np + 255) / 256, (std::max(nx, ny) + 1 + 255) / 256));
-  k_rect_tables<<<std::max(g, 1), 256, 0, st>>>(lon, lat, nx, ny, hdr, lat_ax, lon_ax, col, row, bad, err, dst_tlon);
+  k_rect_tables<<<std::max(g, 1), 256, 0, st>>>(lon, lat, nx, ny, hdr, lat_ax, lon_ax, col, col_min, col_max, col_avg, row, bad, err, dst_tlon);
 }
 void fgd_cell_struct2r(const FgTileSet &ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst, FgCells S, double *area_out,
                        FgRect R, const double *mask, int order, int *src_idx_f, double *sums, unsigned *err, hipStream_t st,
-                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt)
+                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt, FgPairSpace ps, int *pair_beg, int *pair_cnt,
+                       int *big_list, int *big_cnt)
 {
   const int nbS = nblk(nsrc, 256), nbD = nblk(ndst, 256);
   if (nbS + nbD > 0)
     k_cell_struct2r<<<nbS + nbD, 256, 0, st>>>(ts, tiles_in, tiles_out, ntiles, nsrc, ndst, nbS, S, area_out, R, mask, order, src_idx_f, sums, err,
-                                               band_keys, cull, heavy_list, heavy_cnt);
+                                               band_keys, cull, heavy_list, heavy_cnt, ps, pair_beg, pair_cnt, big_list, big_cnt);
 }
 void fgd_polylist_records(FgPolyList P, FgCells S, int *src_idx_f, double *sums, const FgRect *rect, int *heavy_list, int *heavy_cnt,
                           unsigned *err, hipStream_t st)
@@ -2059,10 +2132,10 @@ void fgd_rect_materialize(int ndst, FgRect R, FgCells D, hipStream_t st)
   if (ndst > 0) k_rect_materialize<<<nblk(ndst, 256), 256, 0, st>>>(ndst, R, D);
 }
 void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPairSpace ps, int *pair_beg, int *pair_cnt,
-                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st)
+                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only)
 {
   if (nsrc <= 0) return;
-  const int nbR = nblk(nsrc, 64);
+  const int nbR = listed_only ? 0 : nblk(nsrc, 64);       // listed_only: the record kernel made the candidates of the other cells
   // waves for the listed cells: on a coarse source grid over a fine target EVERY cell is listed (C48 -> 0.25 deg: 13 824 cells; with
   // nsrc / 64 = 216 waves the candidates took 0.24 ms, with nsrc / 8 0.064 -- dealing a cell's (row, column) pairs to all 64 lanes
   // through LDS instead of a lane per column made no difference on top of that)
