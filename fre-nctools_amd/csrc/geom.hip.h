@@ -230,10 +230,25 @@ __device__ inline double d_poly_ctrlon(const double *x, const double *y, int n, 
   return (ctrlon * G_RADIUS * G_RADIUS);
 }
 
+// poly_ctrlon's dphi1 / dphi2: the longitude of a vertex relative to clon, brought into [-pi, pi] (create_xgrid.c:2190-2196)
+__device__ __forceinline__ double d_dphi_clon(double phi, double clon)
+{
+  double d = phi - clon;
+  if (d > G_PI)  d -= 2.0 * G_PI;
+  if (d < -G_PI) d += 2.0 * G_PI;
+  return d;
+}
+
 // Fused area + centroid line integrals over one polygon (order 2): every edge quantity is
 // the same function of the same inputs as in the three separate loops above, evaluated once
 // (sin/cos of the edge mid-latitude, d_sin_lat(half dlat)/(half dlat), sin/cos of the vertex
 // latitudes), so the three results equal the separate evaluations bit for bit.
+// The three loops ask libm for five things per edge -- sincos(lat1) and cos(lat1) of the vertex, sin(avg_y) and then either
+// cos(avg_y) or sincos(avg_y) of the mid-latitude -- and each of them, evaluated on its own, classifies, reduces and looks up
+// its argument again (this kernel is bound by instruction issue).  Here an argument is reduced ONCE:
+// fgs_trig<mask> (sincos_glibc.h) returns all the variants asked of it from one range test, one reduction and one read of
+// the table node.  poly_ctrlat's flat and general forms are both formed from the mid-latitude's four values and picked by a
+// select: a wave holding both kinds of edge used to run a cos() and a sincos() one after the other.
 template <int S>
 __device__ inline void d_poly_area_ctr(const double *x, const double *y, int n, double clon,
                                        double *area_out, double *ctrlon_out, double *ctrlat_out)
@@ -241,19 +256,30 @@ __device__ inline void d_poly_area_ctr(const double *x, const double *y, int n, 
   double area = 0.0, ctrlat = 0.0, ctrlon = 0.0;
   // vertex i is (phi2, lat2); vertex ip is (phi1, lat1).  Per vertex: sincos() for poly_ctrlon's f, plain cos() for
   // poly_ctrlat's cos(lat1) -- the libm entries the reference's object code goes through (see d_poly_ctrlat above).
-  double s2, c2;
-  d_sincos_lat(y[0], &s2, &c2);
-  const double s_first = s2, c_first = c2, cp_first = d_cos_lat(y[0]);
+  // poly_ctrlon's f = (cos*sin + lat) / 2 and the wrapped distance of the vertex from clon are functions of the vertex alone:
+  // formed once per vertex and carried from an edge's second endpoint to the next edge's first.
+  double s0, c0, cp_first;
+  fgs_trig<FGS_COS_F | FGS_SIN_N | FGS_COS_N>(y[0], nullptr, &cp_first, &s0, &c0);
+  const double f_first = 0.5 * (c0 * s0 + y[0]), dphi_first = d_dphi_clon(x[0], clon);
+  double f2 = f_first, dphi2 = dphi_first;
   for (int i = 0; i < n; i++) {
     const bool last = (i + 1 == n);
     int ip = last ? 0 : i + 1;
     double phi1 = x[ip * S], phi2 = x[i * S];
     double lat1 = y[ip * S], lat2 = y[i * S];
-    double s1, c1, cp1;
-    if (last) { s1 = s_first; c1 = c_first; cp1 = cp_first; } else { d_sincos_lat(lat1, &s1, &c1); cp1 = d_cos_lat(lat1); }
+    double f1, dphi1, cp1;
+    if (last) { f1 = f_first; dphi1 = dphi_first; cp1 = cp_first; }
+    else {
+      double s1, c1;
+      fgs_trig<FGS_COS_F | FGS_SIN_N | FGS_COS_N>(lat1, nullptr, &cp1, &s1, &c1);
+      f1 = 0.5 * (c1 * s1 + lat1);
+      dphi1 = d_dphi_clon(phi1, clon);
+    }
     double dx0 = phi1 - phi2;               // x[ip]-x[i]
     double avg_y = (lat1 + lat2) * 0.5;      // == 0.5*(lat1+lat2)
-    const double savg = d_sin_lat(avg_y);    // poly_area: plain sin()
+    // savg: plain sin() (poly_area, ctrlat's flat branch); cavg: plain cos() (flat branch); sa, ca: sincos() (general branch)
+    double savg, cavg, sa, ca;
+    fgs_trig<FGS_ALL>(avg_y, &savg, &cavg, &sa, &ca);
     double dyh = 0.5 * (lat1 - lat2);        // poly_area's dy; ctrlat's hdy == -dyh
     // poly_area tests |lat1-lat2| < 1e-10, poly_ctrlat tests |(lat2-lat1)/2| < 1e-10; the
     // first implies the second, so d_sin_lat(dyh)/dyh is needed exactly when the first fails.
@@ -267,8 +293,7 @@ __device__ inline void d_poly_area_ctr(const double *x, const double *y, int n, 
       if (dx > G_PI)  dx = dx - 2.0 * G_PI;
       if (dx < -G_PI) dx = dx + 2.0 * G_PI;
       if (fabs(dx + G_PI) < G_SMALL || fabs(dx - G_PI) < G_SMALL) area += G_PI;
-      else if (flat) area -= dx * savg;
-      else area -= dx * savg * dat;
+      else area -= dx * savg * dat;             // flat edge: dat = 1.0 and x * 1.0 == x, the reference's dx * sin(avg)
     }
     // ---- poly_ctrlat (create_xgrid.c:2100-2118)
     if (dx0 != 0.0) {
@@ -276,28 +301,16 @@ __device__ inline void d_poly_area_ctr(const double *x, const double *y, int n, 
       if (dx > G_PI)   dx = dx - 2.0 * G_PI;
       if (dx <= -G_PI) dx = dx + 2.0 * G_PI;
       double hdy = (lat2 - lat1) * 0.5;
-      if (fabs(hdy) < G_SMALL)
-        ctrlat -= dx * (2 * d_cos_lat(avg_y) + lat2 * savg - cp1);          // flat branch: separate cos() and sin()
-      else {
-        double sa, ca;
-        d_sincos_lat(avg_y, &sa, &ca);                                      // general branch: sincos(avg_y)
-        const double datc = flat ? d_sin_lat(dyh) / dyh : dat;              // (|hdy| >= 1e-10 > |lat1-lat2| cannot happen)
-        ctrlat -= dx * (datc * (2 * ca + lat2 * sa) - cp1);
-      }
+      // flat branch: separate cos() and sin(); general branch: sincos(avg_y), and |hdy| >= 1e-10 there, so poly_area's
+      // test failed too and dat is sin(hdy)/hdy
+      const double t = (fabs(hdy) < G_SMALL) ? (2 * cavg + lat2 * savg) : dat * (2 * ca + lat2 * sa);
+      ctrlat -= dx * (t - cp1);
     }
     // ---- poly_ctrlon (create_xgrid.c:2176-2214)
     if (dx0 != 0.0) {
       double dphi = dx0;
-      double f1 = 0.5 * (c1 * s1 + lat1);
-      double f2 = 0.5 * (c2 * s2 + lat2);
       if (dphi > G_PI)  dphi = dphi - 2.0 * G_PI;
       if (dphi < -G_PI) dphi = dphi + 2.0 * G_PI;
-      double dphi1 = phi1 - clon;
-      if (dphi1 > G_PI)  dphi1 -= 2.0 * G_PI;
-      if (dphi1 < -G_PI) dphi1 += 2.0 * G_PI;
-      double dphi2 = phi2 - clon;
-      if (dphi2 > G_PI)  dphi2 -= 2.0 * G_PI;
-      if (dphi2 < -G_PI) dphi2 += 2.0 * G_PI;
       if (fabs(dphi2 - dphi1) < G_PI) {
         ctrlon -= dphi * (dphi1 * f1 + dphi2 * f2) / 2.0;
       } else {
@@ -307,7 +320,7 @@ __device__ inline void d_poly_area_ctr(const double *x, const double *y, int n, 
                   + 0.5 * fac * (dphi1 + dphi2) * fint;
       }
     }
-    s2 = s1; c2 = c1;
+    f2 = f1; dphi2 = dphi1;
   }
   *area_out = (area < 0) ? -area * G_RADIUS * G_RADIUS : area * G_RADIUS * G_RADIUS;
   *ctrlat_out = ctrlat * G_RADIUS * G_RADIUS;

@@ -2495,11 +2495,12 @@ extern "C" int fg_clip_2dx2d_batch(int npoly, const double *lon1, const double *
   return 0;
 }
 
-// op 0 poly_area, 1 poly_ctrlon(clon), 2 poly_ctrlat, 3 fix_lon(tlon = clon) in place (lon/lat/n updated).
+// op 0 poly_area, 1 poly_ctrlon(clon), 2 poly_ctrlat, 3 fix_lon(tlon = clon) in place (lon/lat/n updated);
+// 4, 5, 6: area, ctrlon(clon), ctrlat as the clip kernels' fused integrals routine computes them.
 extern "C" int fg_poly_op_batch(int op, int npoly, double *lon, double *lat, int *n, const double *clon, double *result)
 {
-  if (op < 0 || op > 3 || npoly < 0 || !lon || !lat || !n) return fail(FG_ERR_ARG, "bad argument");
-  if ((op == 1 || op == 3) && !clon) return fail(FG_ERR_ARG, "clon/tlon array required");
+  if (op < 0 || op > 6 || npoly < 0 || !lon || !lat || !n) return fail(FG_ERR_ARG, "bad argument");
+  if ((op == 1 || op == 3 || op == 5) && !clon) return fail(FG_ERR_ARG, "clon/tlon array required");
   if (op != 3 && !result) return fail(FG_ERR_ARG, "result array required");
   if (npoly == 0) return 0;
   HIPCHK(hipSetDevice(b1_device()));

@@ -81,6 +81,8 @@ __global__ __launch_bounds__(64) void k_poly_clip(int npoly, const double *lon1,
 }
 
 // op 0: poly_area, 1: poly_ctrlon (clon[p]), 2: poly_ctrlat, 3: fix_lon in place (tlon = clon[p]; n updated)
+// op 4, 5, 6: the area, ctrlon (clon[p]) and ctrlat that the clip kernels' fused d_poly_area_ctr returns -- a probe: each must
+// equal op 0, 1, 2 bit for bit
 __global__ __launch_bounds__(64) void k_poly_op(int op, int npoly, double *lon, double *lat, int *n, const double *clon,
                                                  double *result)
 {
@@ -93,7 +95,11 @@ __global__ __launch_bounds__(64) void k_poly_op(int op, int npoly, double *lon, 
   if (op == 0) result[p] = d_poly_area<1>(x, y, m);
   else if (op == 1) result[p] = d_poly_ctrlon<1>(x, y, m, clon[p]);
   else if (op == 2) result[p] = d_poly_ctrlat<1>(x, y, m);
-  else {
+  else if (op >= 4) {
+    double pa, pclon, pclat;
+    d_poly_area_ctr<1>(x, y, m, op == 5 ? clon[p] : 0.0, &pa, &pclon, &pclat);
+    result[p] = (op == 4) ? pa : (op == 5) ? pclon : pclat;
+  } else {
     int mm = d_fix_lon(x, y, m, clon[p]);
     n[p] = mm;
     for (int k = 0; k < PB_CAP; k++) {

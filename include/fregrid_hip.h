@@ -402,7 +402,9 @@ void fg_set_apply_xcd(int on);
  * inputs have at most 12 vertices (8 for fix_lon).  fg_clip_2dx2d_batch: n_out[p] = vertex count,
  * 0 = empty, -1 = parallel edges (fatal in the reference), -2 = more than 24 vertices.
  * fg_poly_op_batch: op 0 poly_area, 1 poly_ctrlon (clon[p]), 2 poly_ctrlat -> result[p];
- * op 3 fix_lon with tlon = clon[p], in place (lon/lat/n updated). */
+ * op 3 fix_lon with tlon = clon[p], in place (lon/lat/n updated);
+ * op 4, 5, 6: area, ctrlon (clon[p]) and ctrlat again, from the fused routine the order-2 clip kernels integrate with (one pass
+ * over the edges for all three) -- a probe for tests: they equal ops 0, 1, 2 bit for bit. */
 int fg_clip_2dx2d_batch(int npoly, const double *lon1, const double *lat1, const int *n1,
                         const double *lon2, const double *lat2, const int *n2,
                         double *lon_out, double *lat_out, int *n_out);
