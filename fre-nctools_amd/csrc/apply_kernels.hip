@@ -78,7 +78,57 @@ __device__ __forceinline__ void d_rank_count(const int *keys, int n, const int (
   }
 }
 
-template <int ORDER, int RPW, bool DIST, int BT>
+// The records of a block's run of perm (nq entries from q0; STAGED: sorted in LDS, else in perm itself): G entries per lane and
+// pass, so that a wave has G gathers in flight in each of the two dependent rounds (by exchange cell, then by its source cell)
+// instead of one.  Entries past the run's end repeat the pass's first one and store nothing.  Per entry the operations are
+// those of a one-entry loop, in the same order.  (STAGED is a template constant: chosen per load, LDS or global memory, the
+// index reads become flat loads, which are waited for one by one.)
+template <int ORDER, bool DIST, int BT, int G, bool STAGED>
+__device__ __forceinline__ void d_csr_records(const int *sh, const int *perm, int q0, int nq, const int *x_src, const double *x_area,
+                                              const double *x_c1, const double *x_c2, const int *src_idx_f, const double *cen, int nsrc,
+                                              const FgCsr &csr)
+{
+  for (int i0 = threadIdx.x; i0 < nq; i0 += BT * G) {
+    int n[G], s[G], idx[G];
+    double ar[G], c1[G], c2[G], cl[G], ct[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) { const int i = i0 + BT * g, ic = (i < nq) ? i : i0; n[g] = STAGED ? sh[ic] : perm[q0 + ic]; }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      s[g] = x_src[n[g]]; ar[g] = x_area[n[g]];
+      if (ORDER == 2) { c1[g] = x_c1[n[g]]; c2[g] = x_c2[n[g]]; }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      idx[g] = src_idx_f[s[g]];
+      if (ORDER == 2 && DIST) { cl[g] = cen[s[g]]; ct[g] = cen[nsrc + s[g]]; }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      const int i = i0 + BT * g;
+      if (ORDER == 2) {
+        FgCsrEntry2 E;
+        E.idx_f = idx[g]; E.idx_g = s[g]; E.area = ar[g];
+        if (DIST) {
+          double di = c1[g] / E.area, dj = c2[g] / E.area;
+          di -= cl[g]; dj -= ct[g];
+          E.di = di; E.dj = dj;
+        } else { E.di = c1[g]; E.dj = c2[g]; }
+        if (i < nq) csr.e2[q0 + i] = E;
+      } else {
+        FgCsrEntry1 E;
+        E.idx_f = idx[g]; E.pad = 0; E.area = ar[g];
+        if (i < nq) csr.e1[q0 + i] = E;
+      }
+    }
+  }
+}
+
+// entries per lane and pass of the record loop.  2 and 4 take the same time on C384 -> 0.25 deg (113.4 / 113.1 us, 117.9 with
+// one); 4 costs the DIST kernels 76 registers (6 waves per SIMD instead of 8) and the finalize of a coarse -> fine plan 4-7 us
+// (C96 -> 0.25 deg: 54 us with 2, 62 with 4, 59 with one): profiles/compact_finalize_loads_summary.md
+#define SG_GROUP 2
+template <int ORDER, int RPW, bool DIST, int BT, int G>
 __global__ __launch_bounds__(BT) void k_csr_sortgather(int ndst, int *perm, const int *x_src, const double *x_area, const double *x_c1,
                                                         const double *x_c2, const int *src_idx_f, const double *cen, int nsrc, FgCsr csr,
                                                         int *tmp, long ntmp)
@@ -190,24 +240,8 @@ __global__ __launch_bounds__(BT) void k_csr_sortgather(int ndst, int *perm, cons
     }
     __syncthreads();
   }
-  for (int i = threadIdx.x; i < nq; i += BT) {
-    const int n = staged ? sh[i] : perm[q0 + i];
-    const int s = x_src[n];
-    if (ORDER == 2) {
-      FgCsrEntry2 E;
-      E.idx_f = src_idx_f[s]; E.idx_g = s; E.area = x_area[n];
-      if (DIST) {
-        double di = x_c1[n] / E.area, dj = x_c2[n] / E.area;
-        di -= cen[s]; dj -= cen[nsrc + s];
-        E.di = di; E.dj = dj;
-      } else { E.di = x_c1[n]; E.dj = x_c2[n]; }
-      csr.e2[q0 + i] = E;
-    } else {
-      FgCsrEntry1 E;
-      E.idx_f = src_idx_f[s]; E.pad = 0; E.area = x_area[n];
-      csr.e1[q0 + i] = E;
-    }
-  }
+  if (staged) d_csr_records<ORDER, DIST, BT, G, true>(sh, perm, q0, nq, x_src, x_area, x_c1, x_c2, src_idx_f, cen, nsrc, csr);
+  else        d_csr_records<ORDER, DIST, BT, G, false>(sh, perm, q0, nq, x_src, x_area, x_c1, x_c2, src_idx_f, cen, nsrc, csr);
 }
 
 // index of source cell s inside one level of the field array: order 1 fields have no halo
@@ -1103,7 +1137,7 @@ void fgd_csr_sortgather(int order, int ndst, long nx, const int *perm, const int
   // rows per block: 64 short rows for one wave; 16 long ones, or a single very long one (fine -> very coarse), for four waves
   // (long_rows: the caller knows of a region of long rows under a short mean -- the cells round the pole of a curvilinear target)
   const int mode = nx > 256 * (long)ndst ? 2 : ((nx > 8 * (long)ndst || long_rows) ? 1 : 0);
-#define SG(O_, R_, D_) k_csr_sortgather<O_, R_, D_, (R_ >= 64 ? 64 : 256)><<<nblk(ndst, R_), (R_ >= 64 ? 64 : 256), 0, st>>>(ndst, pm, x_src, x_area, x_c1, x_c2, src_idx_f, cen, nsrc, csr, tmp, ntmp)
+#define SG(O_, R_, D_) k_csr_sortgather<O_, R_, D_, (R_ >= 64 ? 64 : 256), SG_GROUP><<<nblk(ndst, R_), (R_ >= 64 ? 64 : 256), 0, st>>>(ndst, pm, x_src, x_area, x_c1, x_c2, src_idx_f, cen, nsrc, csr, tmp, ntmp)
 #define SGM(O_, D_) do { if (mode == 2) SG(O_, 1, D_); else if (mode == 1) SG(O_, 16, D_); else SG(O_, 64, D_); } while (0)
   if (order == 2) { if (cen) SGM(2, true); else SGM(2, false); }
   else SGM(1, false);

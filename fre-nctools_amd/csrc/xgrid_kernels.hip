@@ -1776,7 +1776,7 @@ __global__ __launch_bounds__(GEN_THREADS) void k_clip_general(const int *defer_l
 #define CP_SPAN (256 + CP_SMALL)
 static_assert(CP_SMALL % 64 == 0 && CP_SMALL <= 256, "the halo lanes of k_compact are whole waves of its 256-lane block");
 
-struct CpPair { int s, d, beg, cnt, li, p; long x0; int na; double a, l, t; bool mine; };
+struct CpPair { int s, d, beg, cnt, row; long x0; int na; double a, l, t; bool mine; };    // row: the cell's place in perm (early row slots)
 
 // Slot of an exchange cell in its destination row: atomicAdd(&row_cnt[d], 1) for every lane with take -- or, where many lanes of
 // the wave share a destination cell (a coarse target: value-returning atomics on one address queue up), one atomic per group of
@@ -1810,23 +1810,47 @@ __device__ __forceinline__ int d_row_slot(int *row_cnt, bool take, int d, int la
   return slot;
 }
 
-template <int ORDER>
-__device__ __forceinline__ CpPair d_cp_load(const FgPairSpace &ps, const FgCompactIo &io, int p, int p0, unsigned live_end, bool halo)
+// A lane's pair of the block's 256 (c) and, for the first CP_SMALL lanes (HALO), its pair of the halo (h): everything the ranking
+// and the stores need, in rounds of loads that are each issued together -- (A) what the pair index alone addresses, (B) what needs
+// the pair's source and destination cell (xoff too: it waits for no answer about whose cell it is), (C) the area and centroid
+// integrals of a halo pair once it is known to be this block's (with (A) they were reads for other blocks' pairs: FETCH_SIZE
+// 179 MB against 154 MB, and 4 us slower).  Loads go out ahead of their guards, from clamped indices (pair p0 is live; row 0 for a
+// rejected pair), and a value loaded for nothing is dropped: a pair beyond the region's end keeps d = -1 and mine = false,
+// and d_cp_place reads the values of its own accepted pairs only.
+// (A lane used to finish the main pair, four dependent rounds, before it began the same four for the halo pair.)
+template <int ORDER, bool HALO>
+__device__ __forceinline__ void d_cp_load(const FgPairSpace &ps, const FgCompactIo &io, int p0, int tid, unsigned live_end, CpPair &c, CpPair &h)
 {
-  CpPair c;
-  c.s = 0; c.d = -1; c.beg = 0; c.cnt = 0; c.x0 = 0; c.na = 0; c.a = 0; c.l = 0; c.t = 0; c.mine = false; c.li = p - p0; c.p = p;
-  if ((unsigned)p < live_end) {
-    c.s = ps.src[p]; c.d = ps.dst[p];
-    c.beg = io.pair_beg[c.s]; c.cnt = io.pair_cnt[c.s];
-    // this block's cell: its first pair is one of the block's 256 (halo lanes: ... and it is not a big cell's)
-    c.mine = c.cnt <= CP_SMALL && c.beg >= p0 && c.beg < p0 + 256;
-    if (c.mine) {
-      c.x0 = io.xoff[c.s]; c.na = io.xoff[c.s + 1] - (int)c.x0;
-      if (c.d >= 0) { c.a = io.tmp_area[p]; if (ORDER == 2) { c.l = io.tmp_clon[p]; c.t = io.tmp_clat[p]; } }
-    }
+  constexpr int N = HALO ? 2 : 1;
+  const int *const rowpos = io.tmp_rowpos ? io.tmp_rowpos : ps.dst;   // (no slots from the clip kernels: row is not used)
+  int p[N], pc[N], s[N], d[N], rp[N], beg[N], cnt[N], rb[N], x0[N], x1[N];
+  bool ok[N];
+  double a[N], l[N], t[N];
+#pragma unroll
+  for (int k = 0; k < N; k++) { p[k] = p0 + 256 * k + tid; ok[k] = (unsigned)p[k] < live_end; pc[k] = ok[k] ? p[k] : p0; }
+#pragma unroll
+  for (int k = 0; k < N; k++) {                            // round A
+    s[k] = ps.src[pc[k]]; d[k] = ps.dst[pc[k]]; rp[k] = rowpos[pc[k]];
+    if (k == 0) { a[k] = io.tmp_area[pc[k]]; if (ORDER == 2) { l[k] = io.tmp_clon[pc[k]]; t[k] = io.tmp_clat[pc[k]]; } }
   }
-  (void)halo;
-  return c;
+#pragma unroll
+  for (int k = 0; k < N; k++) {                            // round B
+    beg[k] = io.pair_beg[s[k]]; cnt[k] = io.pair_cnt[s[k]]; rb[k] = io.row_ptr[max(d[k], 0)];
+    x0[k] = io.xoff[s[k]]; x1[k] = io.xoff[s[k] + 1];
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    // this block's cell: its first pair is one of the block's 256 (halo lanes: ... and it is not a big cell's)
+    const bool mine = ok[k] && cnt[k] <= CP_SMALL && beg[k] >= p0 && beg[k] < p0 + 256;
+    if (k == 1) {                                          // round C, the halo pair's values: few halo pairs are this block's
+      a[k] = 0; l[k] = 0; t[k] = 0;
+      if (mine && d[k] >= 0) { a[k] = io.tmp_area[p[k]]; if (ORDER == 2) { l[k] = io.tmp_clon[p[k]]; t[k] = io.tmp_clat[p[k]]; } }
+    }
+    CpPair &o = k ? h : c;
+    o.s = ok[k] ? s[k] : 0; o.d = ok[k] ? d[k] : -1; o.beg = ok[k] ? beg[k] : 0; o.cnt = ok[k] ? cnt[k] : 0;
+    o.mine = mine; o.x0 = mine ? x0[k] : 0; o.na = mine ? x1[k] - x0[k] : 0; o.row = (int)((unsigned)rb[k] + (unsigned)rp[k]);
+    o.a = a[k]; o.l = (ORDER == 2) ? l[k] : 0.0; o.t = (ORDER == 2) ? t[k] : 0.0;
+  }
 }
 
 // returns the exchange cell's position if its row slot is still to be taken (no slots from the clip kernels), else -1
@@ -1840,7 +1864,7 @@ __device__ __forceinline__ long d_cp_place(const FgCompactIo &io, const CpPair &
   const long pos = c.x0 + rank;
   io.x_src[pos] = c.s; io.x_dst[pos] = c.d; io.x_area[pos] = c.a;
   if (ORDER == 2) { io.x_c1[pos] = c.l; io.x_c2[pos] = c.t; sh_v[0][lb + rank] = c.a; sh_v[1][lb + rank] = c.l; sh_v[2][lb + rank] = c.t; }
-  if (io.tmp_rowpos) io.perm[io.row_ptr[c.d] + io.tmp_rowpos[c.p]] = (int)pos;        // the row slot was taken by the clip kernel
+  if (io.tmp_rowpos) io.perm[c.row] = (int)pos;           // the row slot was taken by the clip kernel: row_ptr[d] + tmp_rowpos[p]
   else return pos;
   return -1;
 }
@@ -1904,11 +1928,23 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
     // exchange cells to their places; order 2: the values also go to LDS in rank order, BIG_STAGE ranks at a time, where three
     // lanes (one array each) add them up in exchange-cell order -- hundreds to thousands of ordered additions per cell, which
     // from global memory (even with the loads 16 ahead) set the duration of the whole compaction
+    // A cell that fits one stage (every cell of a coarse -> fine remap) takes a pair's values and row slot along with its
+    // destination index, and row_ptr as soon as that is back, ahead of the rank: two rounds of loads per pair instead of
+    // four.  A cell of several stages (great-circle search) passes over its pairs once per stage and loads only what the
+    // stage stores.
+    const bool ahead = na <= BIG_STAGE;                    // (block-uniform)
+    const int *const rowpos = io.tmp_rowpos ? io.tmp_rowpos : ps.dst;
     double acc = 0;
     for (int c0 = 0; c0 < max(na, 1); c0 += BIG_STAGE) {
       for (int k = threadIdx.x; k < c; k += 256) {
         const int p = o + k;
         const int d = ps.dst[p];
+        double a = 0, l = 0, t = 0;
+        int row = 0;
+        if (ahead) {
+          a = io.tmp_area[p]; if (ORDER == 2) { l = io.tmp_clon[p]; t = io.tmp_clat[p]; }
+          row = (int)((unsigned)rowpos[p] + (unsigned)io.row_ptr[max(d, 0)]);
+        }
         if (d < 0) continue;
         int rank;
         if (bitmap) { const int w = (d - dmin) >> 6, b = (d - dmin) & 63; rank = pref[w] + __popcll(bits[w] & ((1ull << b) - 1ull)); }
@@ -1916,14 +1952,16 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
         if (rank < c0 || rank >= c0 + BIG_STAGE) continue;
         const long pos = x0 + rank;
         if (pos >= io.xcap) continue;
-        const double a = io.tmp_area[p];
+        if (!ahead) {
+          a = io.tmp_area[p]; if (ORDER == 2) { l = io.tmp_clon[p]; t = io.tmp_clat[p]; }
+          if (io.tmp_rowpos) row = io.row_ptr[d] + io.tmp_rowpos[p];
+        }
         io.x_src[pos] = s; io.x_dst[pos] = d; io.x_area[pos] = a;
         if (ORDER == 2) {
-          const double l = io.tmp_clon[p], t = io.tmp_clat[p];
           io.x_c1[pos] = l; io.x_c2[pos] = t;
           sval[0][rank - c0] = a; sval[1][rank - c0] = l; sval[2][rank - c0] = t;
         }
-        if (io.tmp_rowpos) io.perm[io.row_ptr[d] + io.tmp_rowpos[p]] = (int)pos;
+        if (io.tmp_rowpos) io.perm[row] = (int)pos;
         else io.x_rowpos[pos] = atomicAdd(&io.row_cnt[d], 1);
       }
       __syncthreads();
@@ -1961,9 +1999,9 @@ __global__ __launch_bounds__(256) void k_compact(int nsrc, FgPairSpace ps, FgCom
   const unsigned rfill = ps.fill[r * FG_FILL_STRIDE];
   const unsigned live_end = r * (unsigned)ps.regcap + (rfill < (unsigned)ps.regcap ? rfill : (unsigned)ps.regcap);   // end of the region's pairs
   if ((unsigned)p0 >= live_end) return;
-  const CpPair c = d_cp_load<ORDER>(ps, io, p0 + tid, p0, live_end, false);
-  CpPair h; h.mine = false; h.d = -1;
-  if (tid < CP_SMALL) { h = d_cp_load<ORDER>(ps, io, p0 + 256 + tid, p0, live_end, true); sh_d[256 + tid] = h.d; }
+  CpPair c, h; h.mine = false; h.d = -1;
+  if (tid < CP_SMALL) { d_cp_load<ORDER, true>(ps, io, p0, tid, live_end, c, h); sh_d[256 + tid] = h.d; }   // (whole waves)
+  else d_cp_load<ORDER, false>(ps, io, p0, tid, live_end, c, h);
   sh_d[tid] = c.d;
   __syncthreads();
   const bool first = (unsigned)(p0 + tid) < live_end && p0 + tid == c.beg;
