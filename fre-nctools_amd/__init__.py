@@ -159,6 +159,24 @@ def latlon2xyz(lon, lat):
     return x, y, z
 
 
+def latlon2xyz_dev(lon_t, lat_t, stream=None):
+    """latlon2xyz on the device (fg_dev_latlon2xyz): torch float64 tensors on a GPU in, (x, y, z) tensors of the same shape out,
+    with the bits of ``latlon2xyz``.  Queued on ``stream`` (a raw HIP stream handle) or on torch's current stream, not
+    synchronised.  A point outside the domain (non-finite, |lat| >= 2.4262, |lon| > 1024 rad) comes back as NaN."""
+    import torch
+    _lib.require_gpu()
+    assert lon_t.is_cuda and lat_t.is_cuda and lon_t.dtype == lat_t.dtype == torch.float64 and lon_t.shape == lat_t.shape
+    lon_t, lat_t = lon_t.contiguous(), lat_t.contiguous()
+    x, y, z = (torch.empty_like(lon_t) for _ in range(3))
+    dev = lon_t.device.index or 0
+    if stream is None:
+        stream = torch.cuda.current_stream(lon_t.device).cuda_stream
+    vp = C.c_void_p
+    _lib.check(lib().fg_dev_latlon2xyz(lon_t.numel(), vp(lon_t.data_ptr()), vp(lat_t.data_ptr()), vp(x.data_ptr()), vp(y.data_ptr()),
+                                       vp(z.data_ptr()), dev, vp(int(stream))))
+    return x, y, z
+
+
 def gc_clip_batch(a, b, device=0):
     """clip_2dx2d_great_circle on npairs quadrilateral pairs: a, b [npairs, 4, 3] unit vectors (clockwise).
     Returns (n_out [npairs], vertices [npairs, 16, 3], area [npairs])."""

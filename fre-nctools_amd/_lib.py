@@ -54,6 +54,7 @@ EXPORTS = [
     "fg_extrap_create", "fg_extrap_destroy", "fg_extrap_set_stream", "fg_extrap_stream", "fg_extrap_run_dev", "fg_extrap_run",
     "fg_extrap_last_syncs", "fg_extrap_get_coef", "fg_extrap_coef_host", "fg_set_extrap_batch", "fg_set_extrap_coef",
     "fg_setup_vertical_interp", "fg_dev_vertical_interp",
+    "fg_dev_latlon2xyz", "fg_plan_create_great_circle_lonlat", "fg_plan_create_great_circle_lonlat_dev",
 ]
 
 
@@ -195,6 +196,13 @@ def lib():
     L.fg_plan_create_great_circle_dev.restype = C.c_long
     L.fg_latlon2xyz.argtypes = [C.c_long, dp, dp, dp, dp, dp]
     L.fg_latlon2xyz.restype = None
+    L.fg_dev_latlon2xyz.argtypes = [C.c_long, vp, vp, vp, vp, vp, C.c_int, vp]
+    L.fg_dev_latlon2xyz.restype = C.c_int
+    L.fg_plan_create_great_circle_lonlat.argtypes = L.fg_plan_create_great_circle.argtypes
+    L.fg_plan_create_great_circle_lonlat.restype = C.c_long
+    L.fg_plan_create_great_circle_lonlat_dev.argtypes = [C.c_int, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int,
+                                                         vp, vp, C.c_double, C.c_double, C.c_int, vp, C.c_int, C.POINTER(vp)]
+    L.fg_plan_create_great_circle_lonlat_dev.restype = C.c_long
     cip = C.POINTER(C.c_int)
     L.create_xgrid_great_circle.argtypes = [cip] * 4 + [dp] * 5 + [ip] * 4 + [dp] * 3
     L.create_xgrid_great_circle.restype = C.c_int

@@ -206,6 +206,57 @@ class XgridPlan:
         return cls(h.value, 1, device, True)
 
     @classmethod
+    def create_great_circle_lonlat(cls, grids_in, grid_out, masks=None, device=0):
+        """create_great_circle with the unit vectors formed on the device (fg_plan_create_great_circle_lonlat): lon / lat are
+        uploaded, no host trig.  The plan is the one create_great_circle builds."""
+        _lib.require_gpu()
+        L = lib()
+        nt = len(grids_in)
+        nx = (C.c_int * nt)(*[g.nx for g in grids_in])
+        ny = (C.c_int * nt)(*[g.ny for g in grids_in])
+        keep = []
+        dpt = C.POINTER(C.c_double)
+
+        def arr(a, n):
+            a = _f64(a).reshape(-1)
+            assert a.size == n, (a.size, n)
+            keep.append(a)
+            return _dp(a)
+
+        lon = (dpt * nt)(*[arr(g.lonc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
+        lat = (dpt * nt)(*[arr(g.latc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
+        msk = None
+        if masks is not None:
+            msk = (dpt * nt)(*[arr(m, g.nx * g.ny) if m is not None else dpt() for m, g in zip(masks, grids_in)])
+        lo = arr(grid_out.lonc, (grid_out.nx + 1) * (grid_out.ny + 1))
+        la = arr(grid_out.latc, (grid_out.nx + 1) * (grid_out.ny + 1))
+        h = C.c_void_p()
+        check(L.fg_plan_create_great_circle_lonlat(nt, nx, ny, lon, lat, msk, grid_out.nx, grid_out.ny, lo, la, device, C.byref(h)))
+        return cls(h.value, 1, device, True)
+
+    @classmethod
+    def create_great_circle_lonlat_dev(cls, nx_in, ny_in, lon_in_t, lat_in_t, nx_out, ny_out, lon_out_t, lat_out_t,
+                                       mean_dlat=0.0, mean_dlon=0.0, device=0, stream=None, masks_t=None):
+        """Great-circle search on lon / lat corner arrays already on the device (torch float64 tensors, radians); the unit
+        vectors are formed there, in buffers the plan owns for the duration of the search."""
+        L = lib()
+        nt = len(nx_in)
+        nx = (C.c_int * nt)(*nx_in)
+        ny = (C.c_int * nt)(*ny_in)
+        lon = (C.c_void_p * nt)(*[t.data_ptr() for t in lon_in_t])
+        lat = (C.c_void_p * nt)(*[t.data_ptr() for t in lat_in_t])
+        msk = None
+        if masks_t is not None:
+            msk = (C.c_void_p * nt)(*[(t.data_ptr() if t is not None else None) for t in masks_t])
+        h = C.c_void_p()
+        use = 0 if stream is None else 1
+        sptr = C.c_void_p(0 if stream is None else int(stream))
+        check(L.fg_plan_create_great_circle_lonlat_dev(nt, nx, ny, lon, lat, msk, nx_out, ny_out,
+                                                       C.c_void_p(lon_out_t.data_ptr()), C.c_void_p(lat_out_t.data_ptr()),
+                                                       float(mean_dlat), float(mean_dlon), device, sptr, use, C.byref(h)))
+        return cls(h.value, 1, device, True)
+
+    @classmethod
     def create_empty(cls, order, nx_in, ny_in, nx_out, ny_out, device=0):
         _lib.require_gpu()
         nt = len(nx_in)

@@ -424,6 +424,7 @@ struct fg_plan {
   double *mono_x = nullptr, *mono_b = nullptr;     // mono_b: [4][nsrc] = f_bar_max | f_bar_min | f_max | f_min
   int *xerr = nullptr;
   bool mono_open = false;
+  unsigned *ll_err = nullptr;    // error word of a latlon2xyz conversion queued ahead of the search (great-circle plans from lon / lat)
 
   template <typename T> T *alloc(size_t count)
   {
@@ -739,6 +740,7 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   int *bin_cnt = (int *)(zero_blk + z_bin_cnt), *bin_fill = (int *)(zero_blk + z_bin_fill), *row_cnt = (int *)(zero_blk + z_row_cnt);
   int *nacc = (int *)(zero_blk + z_nacc);
   HIPCHK(hipMemsetAsync(zero_blk, 0, zbytes, st));
+  if (pl->ll_err) HIPCHK(hipMemcpyAsync(&dc->err[2], pl->ll_err, sizeof(unsigned), hipMemcpyDeviceToDevice, st));   // rides on the one readback
 
   PhaseTimer pt, ptot;
   pt.start(g_profiling != 0, st); ptot.start(g_profiling != 0, st);
@@ -882,6 +884,8 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
     caps->regcap = (int)((hc->total[3] + FG_REG_ALIGN - 1) / FG_REG_ALIGN * FG_REG_ALIGN);
     return FG_RETRY;
   }
+  if (hc->err[2] & G_ERRBIT_LL2X) return fail(FG_ERR_ARG, "latlon2xyz: a grid corner is not finite, or its latitude (|lat| >= 2.4262) or longitude "
+                                                          "(|lon| > 1024) lies outside the range of the device trig (radians expected)");
   if (hc->err[0] & 8u) return fail(FG_ERR_ARG, "a grid corner latitude lies outside [-pi/2, pi/2] (radians expected)");
   if (hc->err[0] & 1u) return fail(FG_ERR_MAXV, "create_xgrid.c: n2_in is greater than MAX_V");
   if (hc->err[0] & 2u) return fail(FG_ERR_PARALLEL, "the line between <x1_0,y1_0> and  <x1_1,y1_1> should not parallel to "
@@ -1233,6 +1237,120 @@ extern "C" long fg_plan_create_great_circle(int ntiles_in, const int *nx_in, con
   long nx = fg_plan_create_great_circle_dev(ntiles_in, nx_in, ny_in, xs.data(), ys.data(), zs.data(), mask_in ? dmask.data() : nullptr,
                                             nx_out, ny_out, gout.x, gout.y, gout.z, mdlat, mdlon, device, nullptr, 0, plan_out);
   cleanup();
+  return nx;
+}
+
+// ------------------------------------------------------------------------------------- great-circle plans from lon / lat
+// latlon2xyz on the device (latlon2xyz_kernels.hip): the unit vectors carry the bits of the reference's host libm, so nothing of
+// the great-circle path is left to the host.
+
+extern "C" int fg_dev_latlon2xyz(long n, const double *d_lon, const double *d_lat, double *d_x, double *d_y, double *d_z, int device, void *stream)
+{
+  if (n < 0 || (n > 0 && (!d_lon || !d_lat || !d_x || !d_y || !d_z))) return fail(FG_ERR_ARG, "fg_dev_latlon2xyz: bad size or null pointer");
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(device));
+  const FgLl2xGrid g{d_lon, d_lat, d_x, d_y, d_z, n};
+  fgd_latlon2xyz(&g, 1, nullptr, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// pl: from plan_base, its stream settled.  Takes the unit-vector buffers from the plan's pool, queues the conversion of every
+// grid (one launch) and the search behind it on the plan's stream, and hands the buffers back: after the search nothing reads
+// the corner arrays any more (the cell records hold the corners; fg_plan_get_polygons works from those), which is also how long
+// fg_plan_create_great_circle_dev needs its caller's arrays.  Destroys the plan on failure.
+static long gc_lonlat_search(fg_plan *pl, const double *const *d_lon_in, const double *const *d_lat_in, const double *const *d_mask_in,
+                             const double *d_lon_out, const double *d_lat_out, double mean_dlat, double mean_dlon)
+{
+  const int nt = pl->ntiles;
+  std::vector<FgLl2xGrid> jobs(nt + 1);
+  std::vector<GcXyz> gxyz(nt + 1);                  // [nt] = the destination grid
+  std::vector<void *> blocks;
+  for (int m = 0; m <= nt; m++) {
+    const size_t np = m < nt ? (size_t)(pl->nx_in[m] + 1) * (pl->ny_in[m] + 1) : (size_t)(pl->nx_out + 1) * (pl->ny_out + 1);
+    double *d = pl->alloc<double>(3 * np);          // x | y | z
+    if (!d) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "out of device memory"); }
+    blocks.push_back(d);
+    jobs[m] = FgLl2xGrid{m < nt ? d_lon_in[m] : d_lon_out, m < nt ? d_lat_in[m] : d_lat_out, d, d + np, d + 2 * np, (long)np};
+    gxyz[m] = GcXyz{d, d + np, d + 2 * np};
+  }
+  pl->ll_err = pl->alloc<unsigned>(1);
+  if (!pl->ll_err) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "out of device memory"); }
+  blocks.push_back(pl->ll_err);
+  hipError_t e = hipSetDevice(pl->device);
+  if (e == hipSuccess) e = hipMemsetAsync(pl->ll_err, 0, sizeof(unsigned), pl->stream);
+  if (e == hipSuccess) { fgd_latlon2xyz(jobs.data(), nt + 1, pl->ll_err, pl->stream); e = hipGetLastError(); }
+  if (e != hipSuccess) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "latlon2xyz: %s", hipGetErrorString(e)); }
+  if (!(mean_dlat > 0) || !(mean_dlon > 0)) {
+    CornerSample s;
+    if (sample_corners_dev(pl, pl->nx_out, pl->ny_out, 3, gxyz[nt].x, gxyz[nt].y, gxyz[nt].z, &s)) { fg_plan_destroy(pl); return FG_ERR_HIP; }
+    extents_xyz(s, &mean_dlat, &mean_dlon);
+  }
+  const long nx = plan_search(pl, nullptr, nullptr, d_mask_in, nullptr, nullptr, mean_dlat, mean_dlon, gxyz.data(), &gxyz[nt]);
+  if (nx < 0) { fg_plan_destroy(pl); return nx; }
+  for (void *p : blocks) pl->release(p);
+  pl->ll_err = nullptr;
+  return nx;
+}
+
+extern "C" long fg_plan_create_great_circle_lonlat_dev(int ntiles_in, const int *nx_in, const int *ny_in,
+                                                       const double *const *d_lon_in, const double *const *d_lat_in,
+                                                       const double *const *d_mask_in, int nx_out, int ny_out,
+                                                       const double *d_lon_out, const double *d_lat_out,
+                                                       double mean_dlat, double mean_dlon, int device, void *stream, int use_caller_stream,
+                                                       fg_plan **plan_out)
+{
+  if (!d_lon_in || !d_lat_in || !d_lon_out || !d_lat_out) return fail(FG_ERR_ARG, "null grid pointer");
+  for (int m = 0; m < ntiles_in; m++) if (!d_lon_in[m] || !d_lat_in[m]) return fail(FG_ERR_ARG, "null grid pointer");
+  fg_plan *pl = nullptr;
+  int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
+  if (rc) return rc;
+  if (use_caller_stream) {
+    g_handles.put_stream(pl->device, pl->stream);
+    pl->stream = (hipStream_t)stream; pl->own_stream = false;
+  }
+  const long nx = gc_lonlat_search(pl, d_lon_in, d_lat_in, d_mask_in, d_lon_out, d_lat_out, mean_dlat, mean_dlon);
+  if (nx >= 0) *plan_out = pl;
+  return nx;
+}
+
+// host corner arrays: lon / lat go up through the transfer pool (16 bytes per vertex), the rest is the entry above
+extern "C" long fg_plan_create_great_circle_lonlat(int ntiles_in, const int *nx_in, const int *ny_in,
+                                                   const double *const *lon_in, const double *const *lat_in, const double *const *mask_in,
+                                                   int nx_out, int ny_out, const double *lon_out, const double *lat_out,
+                                                   int device, fg_plan **plan_out)
+{
+  if (!lon_in || !lat_in || !lon_out || !lat_out) return fail(FG_ERR_ARG, "null grid pointer");
+  for (int m = 0; m < ntiles_in; m++) if (!lon_in[m] || !lat_in[m]) return fail(FG_ERR_ARG, "null grid pointer");
+  fg_plan *pl = nullptr;
+  int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
+  if (rc) return rc;
+  std::vector<const double *> dlon(ntiles_in), dlat(ntiles_in), dmask(ntiles_in, nullptr);
+  std::vector<void *> staged;
+  std::vector<XferJob> up_jobs;
+  auto up = [&](const double *h, size_t n) -> const double * {
+    double *d = pl->alloc<double>(n);
+    if (!d) return nullptr;
+    up_jobs.push_back(XferJob{(void *)h, d, n * sizeof(double), false});
+    staged.push_back(d);
+    return d;
+  };
+  bool ok = true;
+  for (int m = 0; m < ntiles_in && ok; m++) {
+    const size_t np = (size_t)(nx_in[m] + 1) * (ny_in[m] + 1);
+    dlon[m] = up(lon_in[m], np); dlat[m] = up(lat_in[m], np);
+    if (mask_in && mask_in[m]) { dmask[m] = up(mask_in[m], (size_t)nx_in[m] * ny_in[m]); ok = ok && dmask[m]; }
+    ok = ok && dlon[m] && dlat[m];
+  }
+  const size_t npo = (size_t)(nx_out + 1) * (ny_out + 1);
+  const double *dlo = ok ? up(lon_out, npo) : nullptr, *dla = ok ? up(lat_out, npo) : nullptr;
+  if (!ok || !dlo || !dla || !xfer_pool().run(device, up_jobs)) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)"); }
+  double mdlat, mdlon;
+  sample_extents(nx_out, ny_out, lon_out, lat_out, &mdlat, &mdlon);      // (as fg_plan_create_great_circle: from the host arrays, no read-back)
+  const long nx = gc_lonlat_search(pl, dlon.data(), dlat.data(), mask_in ? dmask.data() : nullptr, dlo, dla, mdlat, mdlon);
+  if (nx < 0) return nx;
+  for (void *p : staged) pl->release(p);
+  *plan_out = pl;
   return nx;
 }
 

@@ -10,6 +10,7 @@
 // (they differ in the last place for 0.07 % of arguments).  geom.hip.h uses each where the compiled reference does.
 // Nothing is taken on trust: tests/test_sincos_host.py compiles this header for the host and requires bit-identical
 // results to libm's sin(), cos() and sincos() on tens of millions of arguments across the range.
+// The end of the file adds the next branch of the same routine (longitudes, up to 1024 rad) and latlon2xyz's vertex on top of it.
 // The library itself is built with -ffp-contract=off: the only fused operations are the explicit fma() calls here.
 #pragma once
 #include <stdint.h>
@@ -284,4 +285,98 @@ FG_HD void fgs_trig(double x, double *sin_f, double *cos_f, double *sin_n, doubl
     if (ky != k) { sn = FGS_TAB(ky, 0); ssn = FGS_TAB(ky, 1); cs = FGS_TAB(ky, 2); ccs = FGS_TAB(ky, 3); }
     *sin_f = copysign(fgs_cos_core<true>(ry, y < 0 ? -FGS_HP1 : FGS_HP1, sn, ssn, cs, ccs), x);
   }
+}
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * libm sin() / cos() beyond 2.426265 (longitudes): the next branch of s_sin.c, reduce_sincos + do_sincos, with the contractions
+ * of the multiarch FMA build written out.  x is reduced by the nearest multiple n * pi/2 -- pi/2 split into mp1 + mp2 + pp3 + pp4,
+ * the subtraction carried as a + da -- and the quadrant picks do_cos or do_sin (glibc 2.35's do_sincos: the sine is Taylor below |a| = 0.126, as in do_sin itself).
+ * glibc takes this branch up to 105414350; here it ends at FGS_WIDE_MAX = 1024 rad, far outside any longitude frame and the
+ * range tests/test_sincos_wide_host.py pins against the host libm.  Beyond it, and for a non-finite argument, the result is
+ * NaN (glibc's huge-argument reduction, __branred, is not restated).  Below 2.426265 the results are fgs_sin / fgs_cos. */
+#define FGS_WIDE_MIN 0x1.368fdp+1            /* s_sin.c compares the high word with 0x400368fd: 2.42626476..., its "2.426265" */
+#define FGS_WIDE_MAX 1024.0
+#define FGS_HPINV 0x1.45F306DC9C883p-1       /* 2/pi */
+#define FGS_TOINT 0x1.8p52
+#define FGS_MP1 0x1.921FB58p0
+#define FGS_MP2 (-0x1.DDE973Cp-27)
+#define FGS_PP3 (-0x1.CB3B398p-55)
+#define FGS_PP4 (-0x1.d747f23e32ed7p-83)
+
+/* x - n * pi/2 = a + da; returns n mod 4 */
+FG_HD int fgs_reduce_wide(double x, double *a, double *da)
+{
+  const double t = fma(x, FGS_HPINV, FGS_TOINT);
+  const double xn = t - FGS_TOINT;
+  union { double d; uint64_t b; } c; c.d = t;
+  const double y = fma(-xn, FGS_MP2, fma(-xn, FGS_MP1, x));
+  const double t2 = fma(-xn, FGS_PP3, y);
+  double db = fma(-xn, FGS_PP3, y - t2);
+  const double b = fma(-xn, FGS_PP4, t2);
+  db += fma(-xn, FGS_PP4, t2 - b);
+  *a = b; *da = db;
+  return (int)(c.b & 3u);
+}
+/* do_sincos: q = n for the sine, n + 1 for the cosine; odd = do_cos, even = do_sin */
+FG_HD double fgs_quadrant(double a, double da, int q)
+{
+  const double r = (q & 1) ? fgs_do_cos<true, false>(a, da) : fgs_do_sin<true, false>(a, da);
+  return (q & 2) ? -r : r;
+}
+FG_HD double fgs_sin_wide(double x)
+{
+  const double ax = fabs(x);
+  if (ax < FGS_WIDE_MIN) return fgs_sin(x);
+  if (!(ax <= FGS_WIDE_MAX)) return (double)NAN;
+  double a, da;
+  const int n = fgs_reduce_wide(x, &a, &da);
+  return fgs_quadrant(a, da, n);
+}
+FG_HD double fgs_cos_wide(double x)
+{
+  const double ax = fabs(x);
+  if (ax < FGS_WIDE_MIN) return fgs_cos(x);
+  if (!(ax <= FGS_WIDE_MAX)) return (double)NAN;
+  double a, da;
+  const int n = fgs_reduce_wide(x, &a, &da);
+  return fgs_quadrant(a, da, n + 1);
+}
+/* both of one argument: one (a, da, n), one table node.  Of q = n and q = n + 1 one is odd -- do_cos(a, da) -- and one even --
+ * the sine of (a, da) -- so each is evaluated once and the quadrant deals them out. */
+FG_HD void fgs_sincos_wide_f(double x, double *sinx, double *cosx)
+{
+  const double ax = fabs(x);
+  if (ax < FGS_WIDE_MIN) { fgs_trig<FGS_SIN_F | FGS_COS_F>(x, sinx, cosx, nullptr, nullptr); return; }
+  if (!(ax <= FGS_WIDE_MAX)) { *sinx = *cosx = (double)NAN; return; }
+  double a, da;
+  const int n = fgs_reduce_wide(x, &a, &da);
+  const double aw = fabs(a);
+  const double u = FGS_BIG + aw;
+  const double r = aw - (u - FGS_BIG);
+  const int k = fgs_index(u);
+  const double sn = FGS_TAB(k, 0), ssn = FGS_TAB(k, 1), cs = FGS_TAB(k, 2), ccs = FGS_TAB(k, 3);
+  const double dw = a < 0 ? -da : da;        /* do_sin flips on a <= 0, but a = 0 is its Taylor path: one sign for both */
+  const double co = fgs_cos_core<true>(r, dw, sn, ssn, cs, ccs);
+  const double si = aw < 0.126 ? fgs_taylor_sin<true>(a * a, a, da) : copysign(fgs_sin_core<true>(r, dw, sn, ssn, cs, ccs), a);
+  const double rs = (n & 1) ? co : si, rc = (n & 1) ? si : co;
+  *sinx = (n & 2) ? -rs : rs;
+  *cosx = ((n + 1) & 2) ? -rc : rc;
+}
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * One vertex of latlon2xyz (mosaic_util.c:212-222): x = cos(lat) * cos(lon), y = cos(lat) * sin(lon), z = sin(lat), each
+ * function libm's sin() / cos() (the reference's loop stores between the calls, so gcc does not pair them into sincos()).
+ * The latitude is one fgs_trig (cos(lat) is the same value both times), the longitude one fused wide evaluation; the two
+ * products are plain multiplies.  Outside the domain -- a non-finite coordinate, |lat| >= 2.426265, |lon| > FGS_WIDE_MAX --
+ * the vertex is NaN and the return value false. */
+FG_HD bool fgs_latlon2xyz_vertex(double lon, double lat, double *x, double *y, double *z)
+{
+  const bool ok = fabs(lat) < FGS_WIDE_MIN && fabs(lon) <= FGS_WIDE_MAX;     /* (false for NaN) */
+  double sl = 0.0, cl = 0.0, so, co;
+  fgs_trig<FGS_SIN_F | FGS_COS_F>(lat, &sl, &cl, nullptr, nullptr);
+  fgs_sincos_wide_f(lon, &so, &co);
+  *x = ok ? cl * co : (double)NAN;
+  *y = ok ? cl * so : (double)NAN;
+  *z = ok ? sl : (double)NAN;
+  return ok;
 }

@@ -97,13 +97,21 @@ __device__ __forceinline__ double d_ord_val(unsigned long long k)
 #define FG_TILESET_MAX 8
 struct FgTileSet { FgTile t[FG_TILESET_MAX]; int n; };
 
+// latlon2xyz on the device (latlon2xyz_kernels.hip): one grid's corners, lon / lat in, unit vectors out (n vertices each);
+// a launch converts up to FG_TILESET_MAX grids, the descriptors travel as a kernel argument.  err (may be null) gets
+// G_ERRBIT_LL2X when a vertex lies outside the domain of the device trig (such a vertex becomes NaN).
+struct FgLl2xGrid { const double *lon, *lat; double *x, *y, *z; long n; };
+struct FgLl2xSet { FgLl2xGrid g[FG_TILESET_MAX]; int n; };
+#define G_ERRBIT_LL2X 256u
+void fgd_latlon2xyz(const FgLl2xGrid *grids, int ngrids, unsigned *err, hipStream_t st);
+
 // device-side counters of one search (plan.hip reads them back once)
 struct FgCounters {
   unsigned long long total[4];     // [0] bin-table entries  [1] candidate pairs  [2] (unused)  [3] largest region fill
   unsigned long long rows_total;   // total of the destination-row scan (= nxgrid)
   unsigned long long band_keys[2]; // latitude range of the destination cells as ordered keys (source-cell culling)
   unsigned long long xtot;         // total of the accept-count scan (= nxgrid)
-  unsigned err[4];
+  unsigned err[4];                 // [0] G_ERRBIT_* of the search's kernels  [1] great-circle clip code  [2] bits of a conversion queued ahead of the search
   int heavy_cnt;
   unsigned rect_bad;               // rectilinear path: != 0 = the destination grid failed the check (k_rect_tables)
   int defer_cnt, big_cnt;

@@ -595,6 +595,29 @@ long fg_plan_create_great_circle_dev(int ntiles_in, const int *nx_in, const int 
                                      fg_plan **plan);
 /* latlon2xyz (mosaic_util.c:212-222) with the host libm, threaded */
 void fg_latlon2xyz(long size, const double *lon, const double *lat, double *x, double *y, double *z);
+/* latlon2xyz on the device: d_lon, d_lat [n] in, d_x, d_y, d_z [n] out, all DEVICE pointers; queued on `stream` of `device`, no
+ * synchronisation.  The results carry the bits of fg_latlon2xyz on an FMA-capable x86-64 host (glibc 2.35's sin() / cos(),
+ * restated in csrc/sincos_glibc.h).  Domain: finite coordinates, |lat| < 2.4262 (libm's first three branches) and
+ * |lon| <= 1024 rad; a point outside it becomes NaN in all three outputs.  Returns 0 or FG_ERR_*. */
+int fg_dev_latlon2xyz(long n, const double *d_lon, const double *d_lat, double *d_x, double *d_y, double *d_z, int device, void *stream);
+/* Great-circle plans from lon / lat corner arrays (radians) with the conversion above on the device -- no host trig.
+ * fg_plan_create_great_circle_lonlat_dev: the argument list of fg_plan_create_great_circle_dev with DEVICE lon / lat arrays in
+ * place of the unit vectors.  The plan takes the unit-vector buffers from its pool, queues the conversion of every grid (one
+ * launch) ahead of the search on its stream and hands the buffers back when the search is done; the caller's arrays are not
+ * read after the call returns.  mean_dlat / mean_dlon <= 0: derived from a sample of the converted destination corners.
+ * fg_plan_create_great_circle_lonlat: the argument list of fg_plan_create_great_circle; uploads lon / lat (16 bytes per corner
+ * instead of 24) and takes the same path.  A corner outside the conversion's domain gives FG_ERR_ARG (found at the search's
+ * one read-back).  The unit vectors are the ones fg_plan_create_great_circle forms on the host, so the plans are identical. */
+long fg_plan_create_great_circle_lonlat(int ntiles_in, const int *nx_in, const int *ny_in,
+                                        const double *const *lon_in, const double *const *lat_in, const double *const *mask_in,
+                                        int nx_out, int ny_out, const double *lon_out, const double *lat_out,
+                                        int device, fg_plan **plan);
+long fg_plan_create_great_circle_lonlat_dev(int ntiles_in, const int *nx_in, const int *ny_in,
+                                            const double *const *d_lon_in, const double *const *d_lat_in,
+                                            const double *const *d_mask_in, int nx_out, int ny_out,
+                                            const double *d_lon_out, const double *d_lat_out,
+                                            double mean_dlat, double mean_dlon, int device, void *stream, int use_caller_stream,
+                                            fg_plan **plan);
 /* B1 drop-ins (create_xgrid.h): same prototypes as the reference */
 int create_xgrid_great_circle(const int *nlon_in, const int *nlat_in, const int *nlon_out, const int *nlat_out,
                               const double *lon_in, const double *lat_in, const double *lon_out, const double *lat_out,
