@@ -94,6 +94,47 @@ class FieldConfig:
     var: List[VarConfig] = field(default_factory=lambda: [VarConfig()])
 
 
+def _host_grid_args(grids_in, grid_out, masks):
+    """ctypes arguments of a plan entry that takes host corner arrays -- (nt, nx, ny, lon, lat, masks, nx_out, ny_out, lon_out,
+    lat_out) -- and the list of arrays that must stay alive for the call."""
+    nt = len(grids_in)
+    keep = []
+    dpt = C.POINTER(C.c_double)
+
+    def arr(a, n):
+        a = _f64(a).reshape(-1)
+        assert a.size == n, (a.size, n)
+        keep.append(a)
+        return _dp(a)
+
+    def corners(g, a):
+        return arr(a, (g.nx + 1) * (g.ny + 1))
+
+    nx = (C.c_int * nt)(*[g.nx for g in grids_in])
+    ny = (C.c_int * nt)(*[g.ny for g in grids_in])
+    lon = (dpt * nt)(*[corners(g, g.lonc) for g in grids_in])
+    lat = (dpt * nt)(*[corners(g, g.latc) for g in grids_in])
+    msk = None
+    if masks is not None:
+        msk = (dpt * nt)(*[arr(m, g.nx * g.ny) if m is not None else dpt() for m, g in zip(masks, grids_in)])
+    args = (nt, nx, ny, lon, lat, msk, grid_out.nx, grid_out.ny, corners(grid_out, grid_out.lonc), corners(grid_out, grid_out.latc))
+    return args, keep
+
+
+def _dev_grid_args(nx_in, ny_in, tables_t, masks_t, nx_out, ny_out, out_t, mean_dlat, mean_dlon, device, stream):
+    """ctypes arguments of a ``_dev`` plan entry, up to the plan handle: tables_t holds one list of torch tensors (an entry per
+    source tile) for every pointer table of the entry, out_t the destination's tensors; stream None = a stream of the plan's own."""
+    nt = len(nx_in)
+    tables = [(C.c_void_p * nt)(*[t.data_ptr() for t in tab]) for tab in tables_t]
+    msk = None
+    if masks_t is not None:
+        msk = (C.c_void_p * nt)(*[(t.data_ptr() if t is not None else None) for t in masks_t])
+    use = 0 if stream is None else 1
+    sptr = C.c_void_p(0 if stream is None else int(stream))
+    return (nt, (C.c_int * nt)(*nx_in), (C.c_int * nt)(*ny_in), *tables, msk, nx_out, ny_out, *[C.c_void_p(t.data_ptr()) for t in out_t],
+            float(mean_dlat), float(mean_dlon), device, sptr, use)
+
+
 class XgridPlan:
     """RAII wrapper of an ``fg_plan`` (include/fregrid_hip.h)."""
 
@@ -108,101 +149,37 @@ class XgridPlan:
     def create(cls, order, grids_in, grid_out, masks=None, device=0):
         """Search with host corner arrays (copied to the device)."""
         _lib.require_gpu()
-        L = lib()
-        nt = len(grids_in)
-        nx = (C.c_int * nt)(*[g.nx for g in grids_in])
-        ny = (C.c_int * nt)(*[g.ny for g in grids_in])
-        keep = []
-        dpt = C.POINTER(C.c_double)
-
-        def arr(a, n):
-            a = _f64(a).reshape(-1)
-            assert a.size == n, (a.size, n)
-            keep.append(a)
-            return _dp(a)
-
-        lon = (dpt * nt)(*[arr(g.lonc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
-        lat = (dpt * nt)(*[arr(g.latc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
-        if masks is None:
-            msk = None
-        else:
-            msk = (dpt * nt)(*[arr(m, g.nx * g.ny) if m is not None else dpt() for m, g in zip(masks, grids_in)])
-        lo = arr(grid_out.lonc, (grid_out.nx + 1) * (grid_out.ny + 1))
-        la = arr(grid_out.latc, (grid_out.nx + 1) * (grid_out.ny + 1))
+        args, keep = _host_grid_args(grids_in, grid_out, masks)
         h = C.c_void_p()
-        check(L.fg_plan_create(order, nt, nx, ny, lon, lat, msk, grid_out.nx, grid_out.ny, lo, la, device, C.byref(h)))
+        check(lib().fg_plan_create(order, *args, device, C.byref(h)))
         return cls(h.value, order, device)
 
     @classmethod
     def create_dev(cls, order, nx_in, ny_in, lon_in_t, lat_in_t, nx_out, ny_out, lon_out_t, lat_out_t,
                    mean_dlat=0.0, mean_dlon=0.0, device=0, stream=None, masks_t=None):
         """Search with corner arrays already on the device (torch float64 CUDA tensors)."""
-        L = lib()
-        nt = len(nx_in)
-        nx = (C.c_int * nt)(*nx_in)
-        ny = (C.c_int * nt)(*ny_in)
-        lon = (C.c_void_p * nt)(*[t.data_ptr() for t in lon_in_t])
-        lat = (C.c_void_p * nt)(*[t.data_ptr() for t in lat_in_t])
-        msk = None
-        if masks_t is not None:
-            msk = (C.c_void_p * nt)(*[(t.data_ptr() if t is not None else None) for t in masks_t])
         h = C.c_void_p()
-        use = 0 if stream is None else 1
-        sptr = C.c_void_p(0 if stream is None else int(stream))
-        check(L.fg_plan_create_dev(order, nt, nx, ny, lon, lat, msk, nx_out, ny_out,
-                                   C.c_void_p(lon_out_t.data_ptr()), C.c_void_p(lat_out_t.data_ptr()),
-                                   float(mean_dlat), float(mean_dlon), device, sptr, use, C.byref(h)))
+        check(lib().fg_plan_create_dev(order, *_dev_grid_args(nx_in, ny_in, (lon_in_t, lat_in_t), masks_t, nx_out, ny_out,
+                                                              (lon_out_t, lat_out_t), mean_dlat, mean_dlon, device, stream), C.byref(h)))
         return cls(h.value, order, device)
 
     @classmethod
     def create_great_circle(cls, grids_in, grid_out, masks=None, device=0):
         """Great-circle search (create_xgrid_great_circle semantics) with host corner arrays; first order."""
         _lib.require_gpu()
-        L = lib()
-        nt = len(grids_in)
-        nx = (C.c_int * nt)(*[g.nx for g in grids_in])
-        ny = (C.c_int * nt)(*[g.ny for g in grids_in])
-        keep = []
-        dpt = C.POINTER(C.c_double)
-
-        def arr(a, n):
-            a = _f64(a).reshape(-1)
-            assert a.size == n, (a.size, n)
-            keep.append(a)
-            return _dp(a)
-
-        lon = (dpt * nt)(*[arr(g.lonc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
-        lat = (dpt * nt)(*[arr(g.latc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
-        msk = None
-        if masks is not None:
-            msk = (dpt * nt)(*[arr(m, g.nx * g.ny) if m is not None else dpt() for m, g in zip(masks, grids_in)])
-        lo = arr(grid_out.lonc, (grid_out.nx + 1) * (grid_out.ny + 1))
-        la = arr(grid_out.latc, (grid_out.nx + 1) * (grid_out.ny + 1))
+        args, keep = _host_grid_args(grids_in, grid_out, masks)
         h = C.c_void_p()
-        check(L.fg_plan_create_great_circle(nt, nx, ny, lon, lat, msk, grid_out.nx, grid_out.ny, lo, la, device, C.byref(h)))
+        check(lib().fg_plan_create_great_circle(*args, device, C.byref(h)))
         return cls(h.value, 1, device, True)
 
     @classmethod
     def create_great_circle_dev(cls, nx_in, ny_in, xyz_in_t, nx_out, ny_out, xyz_out_t, mean_dlat=0.0, mean_dlon=0.0,
                                 device=0, stream=None, masks_t=None):
         """Great-circle search on unit vectors already on the device: xyz_in_t[m] = (x, y, z) torch tensors."""
-        L = lib()
-        nt = len(nx_in)
-        nx = (C.c_int * nt)(*nx_in)
-        ny = (C.c_int * nt)(*ny_in)
-        xs = (C.c_void_p * nt)(*[t[0].data_ptr() for t in xyz_in_t])
-        ys = (C.c_void_p * nt)(*[t[1].data_ptr() for t in xyz_in_t])
-        zs = (C.c_void_p * nt)(*[t[2].data_ptr() for t in xyz_in_t])
-        msk = None
-        if masks_t is not None:
-            msk = (C.c_void_p * nt)(*[(t.data_ptr() if t is not None else None) for t in masks_t])
         h = C.c_void_p()
-        use = 0 if stream is None else 1
-        sptr = C.c_void_p(0 if stream is None else int(stream))
-        check(L.fg_plan_create_great_circle_dev(nt, nx, ny, xs, ys, zs, msk, nx_out, ny_out,
-                                                C.c_void_p(xyz_out_t[0].data_ptr()), C.c_void_p(xyz_out_t[1].data_ptr()),
-                                                C.c_void_p(xyz_out_t[2].data_ptr()), float(mean_dlat), float(mean_dlon),
-                                                device, sptr, use, C.byref(h)))
+        tables = [[t[k] for t in xyz_in_t] for k in range(3)]
+        check(lib().fg_plan_create_great_circle_dev(*_dev_grid_args(nx_in, ny_in, tables, masks_t, nx_out, ny_out, [xyz_out_t[k] for k in range(3)],
+                                                                    mean_dlat, mean_dlon, device, stream), C.byref(h)))
         return cls(h.value, 1, device, True)
 
     @classmethod
@@ -210,28 +187,9 @@ class XgridPlan:
         """create_great_circle with the unit vectors formed on the device (fg_plan_create_great_circle_lonlat): lon / lat are
         uploaded, no host trig.  The plan is the one create_great_circle builds."""
         _lib.require_gpu()
-        L = lib()
-        nt = len(grids_in)
-        nx = (C.c_int * nt)(*[g.nx for g in grids_in])
-        ny = (C.c_int * nt)(*[g.ny for g in grids_in])
-        keep = []
-        dpt = C.POINTER(C.c_double)
-
-        def arr(a, n):
-            a = _f64(a).reshape(-1)
-            assert a.size == n, (a.size, n)
-            keep.append(a)
-            return _dp(a)
-
-        lon = (dpt * nt)(*[arr(g.lonc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
-        lat = (dpt * nt)(*[arr(g.latc, (g.nx + 1) * (g.ny + 1)) for g in grids_in])
-        msk = None
-        if masks is not None:
-            msk = (dpt * nt)(*[arr(m, g.nx * g.ny) if m is not None else dpt() for m, g in zip(masks, grids_in)])
-        lo = arr(grid_out.lonc, (grid_out.nx + 1) * (grid_out.ny + 1))
-        la = arr(grid_out.latc, (grid_out.nx + 1) * (grid_out.ny + 1))
+        args, keep = _host_grid_args(grids_in, grid_out, masks)
         h = C.c_void_p()
-        check(L.fg_plan_create_great_circle_lonlat(nt, nx, ny, lon, lat, msk, grid_out.nx, grid_out.ny, lo, la, device, C.byref(h)))
+        check(lib().fg_plan_create_great_circle_lonlat(*args, device, C.byref(h)))
         return cls(h.value, 1, device, True)
 
     @classmethod
@@ -239,21 +197,10 @@ class XgridPlan:
                                        mean_dlat=0.0, mean_dlon=0.0, device=0, stream=None, masks_t=None):
         """Great-circle search on lon / lat corner arrays already on the device (torch float64 tensors, radians); the unit
         vectors are formed there, in buffers the plan owns for the duration of the search."""
-        L = lib()
-        nt = len(nx_in)
-        nx = (C.c_int * nt)(*nx_in)
-        ny = (C.c_int * nt)(*ny_in)
-        lon = (C.c_void_p * nt)(*[t.data_ptr() for t in lon_in_t])
-        lat = (C.c_void_p * nt)(*[t.data_ptr() for t in lat_in_t])
-        msk = None
-        if masks_t is not None:
-            msk = (C.c_void_p * nt)(*[(t.data_ptr() if t is not None else None) for t in masks_t])
         h = C.c_void_p()
-        use = 0 if stream is None else 1
-        sptr = C.c_void_p(0 if stream is None else int(stream))
-        check(L.fg_plan_create_great_circle_lonlat_dev(nt, nx, ny, lon, lat, msk, nx_out, ny_out,
-                                                       C.c_void_p(lon_out_t.data_ptr()), C.c_void_p(lat_out_t.data_ptr()),
-                                                       float(mean_dlat), float(mean_dlon), device, sptr, use, C.byref(h)))
+        check(lib().fg_plan_create_great_circle_lonlat_dev(*_dev_grid_args(nx_in, ny_in, (lon_in_t, lat_in_t), masks_t, nx_out, ny_out,
+                                                                           (lon_out_t, lat_out_t), mean_dlat, mean_dlon, device, stream),
+                                                           C.byref(h)))
         return cls(h.value, 1, device, True)
 
     @classmethod

@@ -532,6 +532,21 @@ struct GcXyz { const double *x, *y, *z; };
 // 1-D x 2-D variants: the "source" tile of the search is the box grid expanded to corner arrays (d_lon_in[0]/d_lat_in[0]),
 // the "destination" the quads; box holds the 1-D bounds the pair kernel clips against.
 struct BoxMode { FgBox box; const double *mask_quad; int no_adjust; };
+// What one search works on; every pointer is a device pointer, and a caller names the fields it has.  A legacy search takes
+// lon_in / lat_in [ntiles] and lon_out / lat_out, a great-circle search gc_in [ntiles] and gc_out instead.  mask_in: null, or
+// [ntiles] with null entries for unmasked tiles.  mean_dlat / mean_dlon size the bins (choose_bins).  rect_hint 0: the caller has
+// seen that the destination is not rectilinear, so no attempt is spent on finding that out.
+struct SearchIn {
+  const double *const *lon_in = nullptr, *const *lat_in = nullptr, *const *mask_in = nullptr;
+  const double *lon_out = nullptr, *lat_out = nullptr;
+  const GcXyz *gc_in = nullptr, *gc_out = nullptr;
+  const BoxMode *boxm = nullptr;
+  double mean_dlat = 0, mean_dlon = 0;
+  int rect_hint = 1;
+};
+// What steers a search: the values of the process-wide setters (fg_set_search_*, fg_set_gc_split, fg_set_profiling) as
+// plan_search found them when the plan-creating call started.  Every attempt of that search gets the same ones.
+struct SearchOpts { bool exact, cull, finalize, rect, dst_frame; int gc_split; bool profile; };
 static const char *gc_clip_error(int code)
 {
   switch (code) {
@@ -596,10 +611,7 @@ struct SearchBlocks {
   template <typename T> T *get(size_t count) { T *p = keep<T>(count); if (p) scratch.push_back(p); return p; }
   void release() { for (void *p : scratch) pl->release(p); scratch.clear(); }
 };
-static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const double *const *d_lat_in,
-                        const double *const *d_mask_in, const double *d_lon_out, const double *d_lat_out,
-                        double mean_dlat, double mean_dlon, const GcXyz *gc_in, const GcXyz *gc_out,
-                        const BoxMode *boxm, SearchCaps *caps)
+static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &opt, SearchCaps *caps)
 {
   // Queue order (legacy search, 11 launches + 1 readback; the host synchronises ONCE, at the end):
   //   memset | cell records + bin counts | bin scan | bin fill + heavy list | candidates | quad clip | general clip |
@@ -609,7 +621,8 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   //   (no launch fewer than before the record kernel made the candidates: the listed cells keep theirs, now min(2048, nsrc / 8)
   //   one-wave blocks instead of those + nsrc / 64)
   //   phase_ms: "cell_struct" covers the tables and the record kernel, candidates included; "candidates" the listed cells' launch
-  const bool gc = gc_in != nullptr;
+  const bool gc = in.gc_in != nullptr;
+  const BoxMode *const boxm = in.boxm;
   pl->great_circle = gc;
   hipStream_t st = pl->stream;
   const int nsrc = pl->nsrc, ndst = pl->ndst, order = pl->order;
@@ -619,8 +632,8 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   // tile descriptors: source tiles + the destination tile as entry [ntiles]
   std::vector<FgTile> &th = pl->tiles_host;  // owned by the plan: an async upload needs no sync
   th.resize(pl->ntiles + 1);
-  for (int m = 0; m < pl->ntiles; m++) th[m] = FgTile{gc ? nullptr : d_lon_in[m], gc ? nullptr : d_lat_in[m], pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
-  th[pl->ntiles] = FgTile{d_lon_out, d_lat_out, pl->nx_out, pl->ny_out, 0};
+  for (int m = 0; m < pl->ntiles; m++) th[m] = FgTile{gc ? nullptr : in.lon_in[m], gc ? nullptr : in.lat_in[m], pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
+  th[pl->ntiles] = FgTile{in.lon_out, in.lat_out, pl->nx_out, pl->ny_out, 0};
   pl->tiles_dev = pl->alloc<FgTile>(pl->ntiles + 1);
   if (!pl->tiles_dev) return fail(FG_ERR_HIP, "out of device memory");
   FgTileSet ts; ts.n = 0;
@@ -631,22 +644,22 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   std::vector<FgTileXyz> gct;                       // must outlive the async upload: synchronised at the readback
   if (gc) {
     gct.resize(pl->ntiles + 1);
-    for (int m = 0; m < pl->ntiles; m++) gct[m] = FgTileXyz{gc_in[m].x, gc_in[m].y, gc_in[m].z, pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
-    gct[pl->ntiles] = FgTileXyz{gc_out->x, gc_out->y, gc_out->z, pl->nx_out, pl->ny_out, 0};
+    for (int m = 0; m < pl->ntiles; m++) gct[m] = FgTileXyz{in.gc_in[m].x, in.gc_in[m].y, in.gc_in[m].z, pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
+    gct[pl->ntiles] = FgTileXyz{in.gc_out->x, in.gc_out->y, in.gc_out->z, pl->nx_out, pl->ny_out, 0};
     gct_dev = pl->alloc<FgTileXyz>(pl->ntiles + 1);
     if (!gct_dev) return fail(FG_ERR_HIP, "out of device memory");
     HIPCHK(hipMemcpyAsync(gct_dev, gct.data(), sizeof(FgTileXyz) * gct.size(), hipMemcpyHostToDevice, st));
   }
 
   bool any_mask = false;
-  if (d_mask_in) for (int m = 0; m < pl->ntiles; m++) if (d_mask_in[m]) any_mask = true;
+  if (in.mask_in) for (int m = 0; m < pl->ntiles; m++) if (in.mask_in[m]) any_mask = true;
   if (any_mask) {
     pl->mask_dev = pl->alloc<double>(nsrc);
     if (!pl->mask_dev) return fail(FG_ERR_HIP, "out of device memory");
     std::vector<double> ones;
     for (int m = 0; m < pl->ntiles; m++) {
       size_t nc = (size_t)pl->nx_in[m] * pl->ny_in[m];
-      if (d_mask_in[m]) HIPCHK(hipMemcpyAsync(pl->mask_dev + pl->cell_off[m], d_mask_in[m], nc * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (in.mask_in[m]) HIPCHK(hipMemcpyAsync(pl->mask_dev + pl->cell_off[m], in.mask_in[m], nc * sizeof(double), hipMemcpyDeviceToDevice, st));
       else {
         ones.assign(nc, 1.0);
         HIPCHK(hipMemcpyAsync(pl->mask_dev + pl->cell_off[m], ones.data(), nc * sizeof(double), hipMemcpyHostToDevice, st));
@@ -658,9 +671,9 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   // --- sizes known up front
   const bool rect = caps->rect && !gc && !boxm;
   pl->rect = rect;
-  const double dst_tlon = g_dst_frame ? (double)NAN : 3.14159265358979323846;
+  const double dst_tlon = opt.dst_frame ? (double)NAN : 3.14159265358979323846;
   FgBins bins;
-  choose_bins(pl, mean_dlat, mean_dlon, &bins);
+  choose_bins(pl, in.mean_dlat, in.mean_dlon, &bins);
   if (rect) { bins.nblat = 0; bins.nblon = 0; }       // no bins on the rectilinear path
   const long nbins = (long)bins.nblat * bins.nblon;
   const long nslots = nbins + bins.nblat;             // regular bins + one wide list per bin row
@@ -714,8 +727,8 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   int *tmp_rowpos = early_rows ? blk.get<int>(npairs + 1) : nullptr;
   // great-circle path, three-pass clip: per-pair words, and 3 tasks (edge pairs to solve) per pair of capacity -- 3.0 per LIVE
   // pair were counted at C384 -> 0.25 deg; pairs whose tasks do not fit go through the one-kernel clip instead
-  const bool gc_split = gc && g_gc_split && npairs < (1L << 28);
-  const long tcap_want = (g_gc_split == 2) ? npairs / 64 : 3 * npairs;
+  const bool gc_split = gc && opt.gc_split && npairs < (1L << 28);
+  const long tcap_want = (opt.gc_split == 2) ? npairs / 64 : 3 * npairs;
   const long tcap_reg = gc_split ? std::min<long>((tcap_want / FG_NREG + 255) / 256 * 256, 0x7ffffff0L / FG_NREG) : 0;   // tasks per region
   const long tcap_all = tcap_reg * FG_NREG;
   unsigned *gc_meta = gc_split ? blk.get<unsigned>(npairs + 1) : nullptr;
@@ -743,15 +756,15 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   if (pl->ll_err) HIPCHK(hipMemcpyAsync(&dc->err[2], pl->ll_err, sizeof(unsigned), hipMemcpyDeviceToDevice, st));   // rides on the one readback
 
   PhaseTimer pt, ptot;
-  pt.start(g_profiling != 0, st); ptot.start(g_profiling != 0, st);
+  pt.start(opt.profile, st); ptot.start(opt.profile, st);
   for (int k = 0; k < PH_COUNT; k++) pl->phase_ms[k] = 0;
   ptot.begin(PH_SEARCH_TOTAL);
   pt.begin(PH_CELL_STRUCT);
   if (gc) {
     // destination cells first: a culling search (a rank's band of the target) folds their latitude ranges into band_keys, and
     // the source launch drops the cells that cannot meet that range before their (expensive) spherical-excess area
-    fgd_gc_cell_struct(gct_dev + pl->ntiles, 1, ndst, pl->D, st, g_search_cull ? dc->band_keys : nullptr, 1);
-    fgd_gc_cell_struct(gct_dev, pl->ntiles, nsrc, pl->S, st, g_search_cull ? dc->band_keys : nullptr, 2);
+    fgd_gc_cell_struct(gct_dev + pl->ntiles, 1, ndst, pl->D, st, opt.cull ? dc->band_keys : nullptr, 1);
+    fgd_gc_cell_struct(gct_dev, pl->ntiles, nsrc, pl->S, st, opt.cull ? dc->band_keys : nullptr, 2);
     fgd_src_field_index(order, pl->tiles_dev, pl->ntiles, nsrc, pl->src_idx_f, st);
   } else if (rect) {
     // tables + on-device verification of the grid, then the source records, the heavy list and the destination AREAS in one launch
@@ -759,16 +772,16 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
     R.hdr = rt.hdr; R.lat_ax = rt.lat_ax; R.lon_ax = rt.lon_ax; R.col = rt.col; R.row = rt.row;
     R.col_min = rt.col_min; R.col_max = rt.col_max; R.col_avg = rt.col_avg;
     R.bad = &dc->rect_bad; R.nx = pl->nx_out; R.ny = pl->ny_out;
-    fgd_rect_tables(d_lon_out, d_lat_out, pl->nx_out, pl->ny_out, rt.hdr, rt.lat_ax, rt.lon_ax, rt.col, rt.col_min, rt.col_max, rt.col_avg, rt.row,
+    fgd_rect_tables(in.lon_out, in.lat_out, pl->nx_out, pl->ny_out, rt.hdr, rt.lat_ax, rt.lon_ax, rt.col, rt.col_min, rt.col_max, rt.col_avg, rt.row,
                     &dc->rect_bad, dc->err, st, dst_tlon);
     if (pl->polys.npoly) fgd_polylist_records(pl->polys, pl->S, pl->src_idx_f, pl->sums, &R, heavy_list, &dc->heavy_cnt, dc->err, st);
     fgd_cell_struct2r(ts, pl->tiles_dev, pl->tiles_dev, pl->ntiles, pl->polys.npoly ? 0 : nsrc, ndst, pl->S, pl->D.area, R, pl->mask_dev, order,
-                      pl->src_idx_f, pl->sums, dc->err, st, dc->band_keys, (g_search_cull && !pl->polys.npoly) ? 2 : 0, heavy_list, &dc->heavy_cnt,
+                      pl->src_idx_f, pl->sums, dc->err, st, dc->band_keys, (opt.cull && !pl->polys.npoly) ? 2 : 0, heavy_list, &dc->heavy_cnt,
                       ps, pair_beg, pair_cnt, big_list, &dc->big_cnt);
-  } else if (g_search_cull && !boxm && !pl->polys.npoly) {
+  } else if (opt.cull && !boxm && !pl->polys.npoly) {
     // the destination grid's latitude range from its corners (a 5 us reduction), then ONE record launch in which the source
     // blocks that cannot meet it leave early (round 2 first ran a destination launch, then a source launch: two latency floors)
-    fgd_band_keys(d_lat_out, (long)(pl->nx_out + 1) * (pl->ny_out + 1), dc->band_keys, st);
+    fgd_band_keys(in.lat_out, (long)(pl->nx_out + 1) * (pl->ny_out + 1), dc->band_keys, st);
     fgd_cell_struct2(ts, pl->tiles_dev, pl->tiles_dev, pl->ntiles, nsrc, ndst, pl->S, pl->D, bins, bin_cnt, order, pl->src_idx_f, pl->sums, dc->err, st, dc->band_keys, 2, dst_tlon);
   } else if (pl->polys.npoly) {
     fgd_polylist_records(pl->polys, pl->S, pl->src_idx_f, pl->sums, nullptr, nullptr, nullptr, dc->err, st);
@@ -854,7 +867,7 @@ static long plan_search_core(fg_plan *pl, const double *const *d_lon_in, const d
   // totals) then has no host round trip and no idle GPU between its search and its finalize (25-30 us of a 0.9 ms step; rocprofv3
   // kernel timeline, scripts/band_trace.sh).  The records are sized by the capacity of the exchange-cell arrays (the count is
   // not known yet); an attempt that has to be repeated drops them with everything else.
-  const bool fuse = g_search_finalize && early_rows && !pl->polys.npoly;
+  const bool fuse = opt.finalize && early_rows && !pl->polys.npoly;
   int *fused_tmp = nullptr;
   if (fuse) {
     pt.begin(PH_FINALIZE);
@@ -930,26 +943,25 @@ extern "C" void fg_set_search_mode(int exact) { g_search_exact = exact; }
 // a fraction of the source cells); fg_plan_get_cell_area then returns 0 for them.  Results are unchanged.
 extern "C" void fg_set_search_cull(int on) { g_search_cull = on ? 1 : 0; }
 extern "C" void fg_set_search_finalize(int on) { g_search_finalize = on ? 1 : 0; }
-static long plan_search(fg_plan *pl, const double *const *d_lon_in, const double *const *d_lat_in,
-                        const double *const *d_mask_in, const double *d_lon_out, const double *d_lat_out,
-                        double mean_dlat, double mean_dlon, const GcXyz *gc_in = nullptr, const GcXyz *gc_out = nullptr,
-                        const BoxMode *boxm = nullptr, int rect_hint = 1)
+static long plan_search(fg_plan *pl, const SearchIn &in)
 {
   static const bool env_exact = getenv("FREGRID_HIP_EXACT_SEARCH") && atoi(getenv("FREGRID_HIP_EXACT_SEARCH")) != 0;
-  const bool exact = g_search_exact || env_exact;
+  // the setters' variables are read HERE and nowhere below: a repeated attempt runs under the options of the first
+  const SearchOpts opt{.exact = g_search_exact || env_exact, .cull = g_search_cull != 0, .finalize = g_search_finalize != 0,
+                       .rect = g_search_rect != 0, .dst_frame = g_dst_frame != 0, .gc_split = g_gc_split, .profile = g_profiling != 0};
   const long big = std::max((long)pl->nsrc, (long)pl->ndst);
   // 32-bit prefixes (bin starts, exchange-cell offsets, CSR rows): the bin table holds up to 3 records per destination cell
   // (+ the wide lists) and the pair list 8 per cell, so grids beyond 2^28 cells could wrap an int before the host sees a
   // counter -- refused up front rather than guarded in every kernel
   if (big > (1L << 28)) return fail(FG_ERR_CAPACITY, "grid of %ld cells: more than 2^28 cells per search are not supported", big);
   SearchCaps caps;
-  caps.entries = exact ? 0ull : 3ull * (unsigned long long)pl->ndst + 4096ull;
+  caps.entries = opt.exact ? 0ull : 3ull * (unsigned long long)pl->ndst + 4096ull;
   const unsigned long long cap_pairs = std::min<unsigned long long>(8ull * (unsigned long long)big + 65536ull, 2000000000ull);
   // regions of the pair list: a run of 256 source cells appends to one region; at least four such runs per region on average, so
   // that small grids do not pile their pairs into a few small regions
   caps.nreg = (int)std::max(1L, std::min((long)FG_NREG, ((long)pl->nsrc + 1023) / 1024));
-  caps.regcap = exact ? 0 : (int)((cap_pairs / caps.nreg + FG_REG_ALIGN - 1) / FG_REG_ALIGN * FG_REG_ALIGN);
-  caps.rect = g_search_rect && rect_hint && !gc_in && !boxm && pl->nx_out <= 8192 && pl->nx_out >= 2;
+  caps.regcap = opt.exact ? 0 : (int)((cap_pairs / caps.nreg + FG_REG_ALIGN - 1) / FG_REG_ALIGN * FG_REG_ALIGN);
+  caps.rect = opt.rect && in.rect_hint && !in.gc_in && !in.boxm && pl->nx_out <= 8192 && pl->nx_out >= 2;
   const size_t keep = pl->owned.size();              // blocks the caller staged before the search stay
   long rc = FG_RETRY;
   int attempts = 0;
@@ -958,7 +970,7 @@ static long plan_search(fg_plan *pl, const double *const *d_lon_in, const double
       (void)hipStreamSynchronize(pl->stream);
       pl->drop_search(keep);
     }
-    rc = plan_search_core(pl, d_lon_in, d_lat_in, d_mask_in, d_lon_out, d_lat_out, mean_dlat, mean_dlon, gc_in, gc_out, boxm, &caps);
+    rc = plan_search_core(pl, in, opt, &caps);
   }
   if (rc == FG_RETRY) return fail(FG_ERR_CAPACITY, "exchange-grid search: capacities did not settle");
   if (rc >= 0) pl->stats[FG_STAT_EXACT] = (attempts > 1) ? 1 : 0;
@@ -1076,12 +1088,102 @@ static void extents_xyz(const CornerSample &s, double *mdlat, double *mdlon)
   }
   mean_extents(sl, sw, cnt, mdlat, mdlon);
 }
-// host corner arrays (the callers have host_says_not_rect for the rectilinear question)
-static void sample_extents(int nx, int ny, const double *lon, const double *lat, double *mdlat, double *mdlon)
+// What a search takes from the destination grid before it starts: the mean extents and the rectilinear hint (SearchIn).
+struct DstExtents { double dlat = 0, dlon = 0; int rect_hint = 1; };
+// host corner arrays: the sample for the extents, a look at a few corners for the hint
+static DstExtents dst_extents_host(int nx, int ny, const double *lon, const double *lat)
 {
   const double *arr[2] = {lon, lat};
+  DstExtents x;
   int curvilinear;
-  extents_lonlat(sample_corners_host(nx, ny, 2, arr), mdlat, mdlon, &curvilinear);
+  extents_lonlat(sample_corners_host(nx, ny, 2, arr), &x.dlat, &x.dlon, &curvilinear);
+  x.rect_hint = host_says_not_rect(nx, ny, lon, lat) ? 0 : 1;
+  return x;
+}
+// device corner arrays, lon / lat (d_a2 null) or x / y / z: a no-op when the caller gave positive extents, otherwise the sample
+// is gathered on the plan's stream and read back (one synchronisation); the lon / lat form also gives the hint
+static int dst_extents_dev(fg_plan *pl, const double *d_a0, const double *d_a1, const double *d_a2, DstExtents *x)
+{
+  if (x->dlat > 0 && x->dlon > 0) return 0;
+  CornerSample s;
+  HIPCHK(hipSetDevice(pl->device));
+  if (sample_corners_dev(pl, pl->nx_out, pl->ny_out, d_a2 ? 3 : 2, d_a0, d_a1, d_a2, &s)) return FG_ERR_HIP;
+  int curvilinear = 0;
+  if (d_a2) extents_xyz(s, &x->dlat, &x->dlon);
+  else extents_lonlat(s, &x->dlat, &x->dlon, &curvilinear);
+  x->rect_hint = !curvilinear;
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- plan creation: the steps the entries share
+// Ownership: a static helper that fails returns the error and leaves the plan alone.  Every extern "C" entry holds the plan it
+// got from plan_base in a PlanGuard, which destroys it on every way out but one: hand_over passes the entry's result through
+// and gives the plan to the caller when that is no error, so *plan_out is written on success only.
+struct PlanGuard {
+  fg_plan *pl = nullptr;
+  ~PlanGuard() { fg_plan_destroy(pl); }
+  long hand_over(long rc, fg_plan **plan_out) { if (rc >= 0) { *plan_out = pl; pl = nullptr; } return rc; }
+};
+// The grid-pointer check of every entry, host or device arrays alike: the tables themselves, the destination arrays, and every
+// tile's corner arrays (a tile's mask may be null).  ntiles is the plan's, i.e. plan_base has seen it.
+static int check_grid_ptrs(int ntiles, std::initializer_list<const double *const *> tables, std::initializer_list<const double *> dst)
+{
+  bool ok = true;
+  for (const double *const *t : tables) ok = ok && t;
+  for (const double *p : dst) ok = ok && p;
+  if (ok) for (const double *const *t : tables) for (int m = 0; m < ntiles; m++) ok = ok && t[m];
+  return ok ? 0 : fail(FG_ERR_ARG, "null grid pointer");
+}
+namespace {
+// Host arrays into plan-owned blocks, all in one batch of the transfer pool; done() hands back the blocks, for a caller whose
+// search has run and needs none of them any more.
+struct HostUpload {
+  fg_plan *pl = nullptr;
+  bool ok = true;
+  std::vector<XferJob> jobs;
+  std::vector<void *> blocks;
+  template <typename T> T *put(const T *h, size_t n)
+  {
+    T *d = pl->alloc<T>(n);
+    ok = ok && d;
+    if (d) { jobs.push_back(XferJob{(void *)h, d, n * sizeof(T), false}); blocks.push_back(d); }
+    return d;
+  }
+  bool run() { return ok && xfer_pool().run(pl->device, jobs); }
+  void done() { for (void *p : blocks) pl->release(p); blocks.clear(); }
+};
+// The staging of host lon / lat: every source tile's corner arrays and mask (where given) and the destination's corner arrays.
+// lon / lat / mask are the device pointer tables a SearchIn takes.
+struct StagedGrids {
+  HostUpload up;
+  std::vector<const double *> lon, lat, mask;
+  const double *lon_out = nullptr, *lat_out = nullptr;
+  bool has_masks = false;
+  explicit StagedGrids(fg_plan *pl) : up{pl}, lon(pl->ntiles), lat(pl->ntiles), mask(pl->ntiles, nullptr) {}
+  const double *const *masks() const { return has_masks ? mask.data() : nullptr; }
+};
+}  // namespace
+static int stage_host_grids(fg_plan *pl, const double *const *lon_in, const double *const *lat_in, const double *const *mask_in,
+                            const double *lon_out, const double *lat_out, StagedGrids *s)
+{
+  if (int rc = check_grid_ptrs(pl->ntiles, {lon_in, lat_in}, {lon_out, lat_out})) return rc;     // (before anything touches the device)
+  HostUpload &up = s->up;
+  s->has_masks = mask_in != nullptr;
+  for (int m = 0; m < pl->ntiles && up.ok; m++) {
+    const size_t np = (size_t)(pl->nx_in[m] + 1) * (pl->ny_in[m] + 1);
+    s->lon[m] = up.put(lon_in[m], np); s->lat[m] = up.put(lat_in[m], np);
+    if (mask_in && mask_in[m]) s->mask[m] = up.put(mask_in[m], (size_t)pl->nx_in[m] * pl->ny_in[m]);
+  }
+  const size_t npo = (size_t)(pl->nx_out + 1) * (pl->ny_out + 1);
+  if (up.ok) { s->lon_out = up.put(lon_out, npo); s->lat_out = up.put(lat_out, npo); }
+  if (!up.run()) return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)");
+  return 0;
+}
+// The plan runs on the caller's stream from here on and never owns it; a stream of its own goes back to the cache.
+static void adopt_stream(fg_plan *pl, void *stream)
+{
+  if (pl->own_stream && pl->stream) g_handles.put_stream(pl->device, pl->stream);
+  pl->stream = (hipStream_t)stream; pl->own_stream = false;
 }
 
 extern "C" long fg_plan_create(int order, int ntiles_in, const int *nx_in, const int *ny_in,
@@ -1090,38 +1192,15 @@ extern "C" long fg_plan_create(int order, int ntiles_in, const int *nx_in, const
                                int nx_out, int ny_out, const double *lon_out, const double *lat_out,
                                int device, fg_plan **plan_out)
 {
-  if (!lon_in || !lat_in || !lon_out || !lat_out) return fail(FG_ERR_ARG, "null grid pointer");
-  fg_plan *pl = nullptr;
-  int rc = plan_base(order, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
-  if (rc) return rc;
-  std::vector<const double *> dlon(ntiles_in), dlat(ntiles_in), dmask(ntiles_in, nullptr);
-  std::vector<void *> staged;
-  std::vector<XferJob> up_jobs;
-  auto up = [&](const double *h, size_t n) -> const double * {
-    double *d = pl->alloc<double>(n);
-    if (!d) return nullptr;
-    up_jobs.push_back(XferJob{(void *)h, d, n * sizeof(double), false});
-    staged.push_back(d);
-    return d;
-  };
-  bool ok = true;
-  for (int m = 0; m < ntiles_in && ok; m++) {
-    size_t np = (size_t)(nx_in[m] + 1) * (ny_in[m] + 1);
-    dlon[m] = up(lon_in[m], np); dlat[m] = up(lat_in[m], np);
-    if (mask_in && mask_in[m]) { dmask[m] = up(mask_in[m], (size_t)nx_in[m] * ny_in[m]); ok = ok && dmask[m]; }
-    ok = ok && dlon[m] && dlat[m];
-  }
-  size_t npo = (size_t)(nx_out + 1) * (ny_out + 1);
-  const double *dlo = ok ? up(lon_out, npo) : nullptr, *dla = ok ? up(lat_out, npo) : nullptr;
-  if (!ok || !dlo || !dla || !xfer_pool().run(device, up_jobs)) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)"); }
-  double mdlat, mdlon;
-  sample_extents(nx_out, ny_out, lon_out, lat_out, &mdlat, &mdlon);
-  long nx = plan_search(pl, dlon.data(), dlat.data(), mask_in ? dmask.data() : nullptr, dlo, dla, mdlat, mdlon, nullptr, nullptr, nullptr,
-                        host_says_not_rect(nx_out, ny_out, lon_out, lat_out) ? 0 : 1);
-  if (nx < 0) { fg_plan_destroy(pl); return nx; }
-  for (void *p : staged) pl->release(p);
-  *plan_out = pl;
-  return nx;
+  PlanGuard g;
+  if (int rc = plan_base(order, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  StagedGrids s(g.pl);
+  if (int rc = stage_host_grids(g.pl, lon_in, lat_in, mask_in, lon_out, lat_out, &s)) return rc;
+  const DstExtents x = dst_extents_host(nx_out, ny_out, lon_out, lat_out);
+  const long nx = plan_search(g.pl, SearchIn{.lon_in = s.lon.data(), .lat_in = s.lat.data(), .mask_in = s.masks(), .lon_out = s.lon_out,
+                                             .lat_out = s.lat_out, .mean_dlat = x.dlat, .mean_dlon = x.dlon, .rect_hint = x.rect_hint});
+  if (nx >= 0) s.up.done();
+  return g.hand_over(nx, plan_out);
 }
 
 // Same as fg_plan_create but every grid pointer is a DEVICE pointer (inputs already in HBM).
@@ -1134,29 +1213,28 @@ extern "C" long fg_plan_create_dev(int order, int ntiles_in, const int *nx_in, c
                                    double mean_dlat, double mean_dlon, int device, void *stream,
                                    int use_caller_stream, fg_plan **plan_out)
 {
-  if (!d_lon_in || !d_lat_in || !d_lon_out || !d_lat_out) return fail(FG_ERR_ARG, "null grid pointer");
-  fg_plan *pl = nullptr;
-  int rc = plan_base(order, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
-  if (rc) return rc;
-  if (use_caller_stream) {
-    g_handles.put_stream(pl->device, pl->stream);
-    pl->stream = (hipStream_t)stream; pl->own_stream = false;
-  }
-  int curvilinear = 0;
-  if (!(mean_dlat > 0) || !(mean_dlon > 0)) {
-    CornerSample s;
-    if (hipSetDevice(pl->device) != hipSuccess || sample_corners_dev(pl, nx_out, ny_out, 2, d_lon_out, d_lat_out, nullptr, &s)) {
-      fg_plan_destroy(pl); return FG_ERR_HIP;
-    }
-    extents_lonlat(s, &mean_dlat, &mean_dlon, &curvilinear);
-  }
-  long nx = plan_search(pl, d_lon_in, d_lat_in, d_mask_in, d_lon_out, d_lat_out, mean_dlat, mean_dlon, nullptr, nullptr, nullptr, !curvilinear);
-  if (nx < 0) { fg_plan_destroy(pl); return nx; }
-  *plan_out = pl;
-  return nx;
+  PlanGuard g;
+  if (int rc = plan_base(order, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  if (int rc = check_grid_ptrs(ntiles_in, {d_lon_in, d_lat_in}, {d_lon_out, d_lat_out})) return rc;
+  if (use_caller_stream) adopt_stream(g.pl, stream);
+  DstExtents x{mean_dlat, mean_dlon};
+  if (int rc = dst_extents_dev(g.pl, d_lon_out, d_lat_out, nullptr, &x)) return rc;
+  const long nx = plan_search(g.pl, SearchIn{.lon_in = d_lon_in, .lat_in = d_lat_in, .mask_in = d_mask_in, .lon_out = d_lon_out,
+                                             .lat_out = d_lat_out, .mean_dlat = x.dlat, .mean_dlon = x.dlon, .rect_hint = x.rect_hint});
+  return g.hand_over(nx, plan_out);
 }
 
 // ------------------------------------------------------------------------------------- great-circle plans
+// The tail of every great-circle entry.  gxyz: the corner unit vectors on the device, [ntiles] source tiles and the destination
+// grid as entry [ntiles]; x: the caller's extents, derived from the destination's unit vectors where not positive.  After the
+// search nothing reads the corner arrays any more (the cell records hold the corners; fg_plan_get_polygons works from those).
+static long gc_search(fg_plan *pl, const GcXyz *gxyz, const double *const *d_mask_in, DstExtents x)
+{
+  const GcXyz *out = &gxyz[pl->ntiles];
+  if (int rc = dst_extents_dev(pl, out->x, out->y, out->z, &x)) return rc;
+  return plan_search(pl, SearchIn{.mask_in = d_mask_in, .gc_in = gxyz, .gc_out = out, .mean_dlat = x.dlat, .mean_dlon = x.dlon});
+}
+
 extern "C" long fg_plan_create_great_circle_dev(int ntiles_in, const int *nx_in, const int *ny_in,
                                                 const double *const *d_x_in, const double *const *d_y_in, const double *const *d_z_in,
                                                 const double *const *d_mask_in, int nx_out, int ny_out,
@@ -1164,80 +1242,50 @@ extern "C" long fg_plan_create_great_circle_dev(int ntiles_in, const int *nx_in,
                                                 double mean_dlat, double mean_dlon, int device, void *stream, int use_caller_stream,
                                                 fg_plan **plan_out)
 {
-  if (!d_x_in || !d_y_in || !d_z_in || !d_x_out || !d_y_out || !d_z_out) return fail(FG_ERR_ARG, "null grid pointer");
-  fg_plan *pl = nullptr;
-  int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
-  if (rc) return rc;
-  if (use_caller_stream) {
-    g_handles.put_stream(pl->device, pl->stream);
-    pl->stream = (hipStream_t)stream; pl->own_stream = false;
-  }
-  if (!(mean_dlat > 0) || !(mean_dlon > 0)) {
-    CornerSample s;
-    if (hipSetDevice(pl->device) != hipSuccess || sample_corners_dev(pl, nx_out, ny_out, 3, d_x_out, d_y_out, d_z_out, &s)) {
-      fg_plan_destroy(pl); return FG_ERR_HIP;
-    }
-    extents_xyz(s, &mean_dlat, &mean_dlon);
-  }
-  std::vector<GcXyz> gin(ntiles_in);
-  for (int m = 0; m < ntiles_in; m++) gin[m] = GcXyz{d_x_in[m], d_y_in[m], d_z_in[m]};
-  GcXyz gout{d_x_out, d_y_out, d_z_out};
-  long nx = plan_search(pl, nullptr, nullptr, d_mask_in, nullptr, nullptr, mean_dlat, mean_dlon, gin.data(), &gout);
-  if (nx < 0) { fg_plan_destroy(pl); return nx; }
-  *plan_out = pl;
-  return nx;
+  PlanGuard g;
+  if (int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  if (int rc = check_grid_ptrs(ntiles_in, {d_x_in, d_y_in, d_z_in}, {d_x_out, d_y_out, d_z_out})) return rc;
+  if (use_caller_stream) adopt_stream(g.pl, stream);
+  std::vector<GcXyz> gxyz(ntiles_in + 1);
+  for (int m = 0; m < ntiles_in; m++) gxyz[m] = GcXyz{d_x_in[m], d_y_in[m], d_z_in[m]};
+  gxyz[ntiles_in] = GcXyz{d_x_out, d_y_out, d_z_out};
+  const long nx = gc_search(g.pl, gxyz.data(), d_mask_in, DstExtents{mean_dlat, mean_dlon});
+  return g.hand_over(nx, plan_out);
 }
 
+// host corner arrays, unit vectors on the host (libm, as the reference), then one synchronous upload per grid
 extern "C" long fg_plan_create_great_circle(int ntiles_in, const int *nx_in, const int *ny_in,
                                             const double *const *lon_in, const double *const *lat_in, const double *const *mask_in,
                                             int nx_out, int ny_out, const double *lon_out, const double *lat_out,
                                             int device, fg_plan **plan_out)
 {
-  if (!lon_in || !lat_in || !lon_out || !lat_out || !nx_in || !ny_in) return fail(FG_ERR_ARG, "null grid pointer");
-  if (ntiles_in < 1 || nx_out < 1 || ny_out < 1) return fail(FG_ERR_ARG, "bad grid sizes");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  if (device < 0 || device >= ndev) return fail(FG_ERR_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-  HIPCHK(hipSetDevice(device));
-  // unit vectors on the host (libm, as the reference), then one upload per array
-  std::vector<double *> dev_ptrs;
-  auto cleanup = [&]() { for (double *p : dev_ptrs) g_pool.put(p); };
-  auto to_dev_xyz = [&](int nx, int ny, const double *lon, const double *lat, GcXyz *out) -> bool {
-    const size_t np = (size_t)(nx + 1) * (ny + 1);
-    std::vector<double> h(3 * np);
-    fg_latlon2xyz((long)np, lon, lat, h.data(), h.data() + np, h.data() + 2 * np);
-    double *d = (double *)g_pool.get(device, 3 * np * sizeof(double));
-    if (!d) return false;
-    dev_ptrs.push_back(d);
-    if (hipMemcpy(d, h.data(), 3 * np * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return false;
-    out->x = d; out->y = d + np; out->z = d + 2 * np;
-    return true;
+  PlanGuard g;
+  if (int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  if (int rc = check_grid_ptrs(ntiles_in, {lon_in, lat_in}, {lon_out, lat_out})) return rc;
+  fg_plan *pl = g.pl;
+  std::vector<GcXyz> gxyz(ntiles_in + 1);           // [ntiles_in] = the destination grid
+  std::vector<const double *> dmask(ntiles_in, nullptr);
+  std::vector<void *> blocks;
+  std::vector<double> h;
+  auto upload = [&](const double *src, size_t n) -> double * {
+    double *d = pl->alloc<double>(n);
+    if (d) blocks.push_back(d);
+    return d && hipMemcpy(d, src, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? d : nullptr;
   };
-  std::vector<GcXyz> gin(ntiles_in);
-  std::vector<const double *> xs(ntiles_in), ys(ntiles_in), zs(ntiles_in), dmask(ntiles_in, nullptr);
-  bool ok = true;
-  for (int m = 0; m < ntiles_in && ok; m++) {
-    if (nx_in[m] < 1 || ny_in[m] < 1) { cleanup(); return fail(FG_ERR_ARG, "bad source tile size"); }
-    ok = to_dev_xyz(nx_in[m], ny_in[m], lon_in[m], lat_in[m], &gin[m]);
-    xs[m] = gin[m].x; ys[m] = gin[m].y; zs[m] = gin[m].z;
-    if (ok && mask_in && mask_in[m]) {
-      const size_t nc = (size_t)nx_in[m] * ny_in[m];
-      double *d = (double *)g_pool.get(device, nc * sizeof(double));
-      ok = d && hipMemcpy(d, mask_in[m], nc * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-      if (d) dev_ptrs.push_back(d);
-      dmask[m] = d;
-    }
+  for (int m = 0; m <= ntiles_in; m++) {
+    const bool src = m < ntiles_in;
+    const size_t np = src ? (size_t)(nx_in[m] + 1) * (ny_in[m] + 1) : (size_t)(nx_out + 1) * (ny_out + 1);
+    h.resize(3 * np);                               // x | y | z
+    fg_latlon2xyz((long)np, src ? lon_in[m] : lon_out, src ? lat_in[m] : lat_out, h.data(), h.data() + np, h.data() + 2 * np);
+    const double *d = upload(h.data(), 3 * np);
+    bool ok = d != nullptr;
+    if (ok && src && mask_in && mask_in[m]) ok = (dmask[m] = upload(mask_in[m], (size_t)nx_in[m] * ny_in[m])) != nullptr;
+    if (!ok) return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)");
+    gxyz[m] = GcXyz{d, d + np, d + 2 * np};
   }
-  GcXyz gout{};
-  ok = ok && to_dev_xyz(nx_out, ny_out, lon_out, lat_out, &gout);
-  if (!ok) { cleanup(); return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)"); }
-  double mdlat, mdlon;
-  sample_extents(nx_out, ny_out, lon_out, lat_out, &mdlat, &mdlon);
-  long nx = fg_plan_create_great_circle_dev(ntiles_in, nx_in, ny_in, xs.data(), ys.data(), zs.data(), mask_in ? dmask.data() : nullptr,
-                                            nx_out, ny_out, gout.x, gout.y, gout.z, mdlat, mdlon, device, nullptr, 0, plan_out);
-  cleanup();
-  return nx;
+  const long nx = gc_search(pl, gxyz.data(), mask_in ? dmask.data() : nullptr, dst_extents_host(nx_out, ny_out, lon_out, lat_out));
+  if (nx >= 0) for (void *p : blocks) pl->release(p);
+  return g.hand_over(nx, plan_out);
 }
 
 // ------------------------------------------------------------------------------------- great-circle plans from lon / lat
@@ -1256,11 +1304,9 @@ extern "C" int fg_dev_latlon2xyz(long n, const double *d_lon, const double *d_la
 }
 
 // pl: from plan_base, its stream settled.  Takes the unit-vector buffers from the plan's pool, queues the conversion of every
-// grid (one launch) and the search behind it on the plan's stream, and hands the buffers back: after the search nothing reads
-// the corner arrays any more (the cell records hold the corners; fg_plan_get_polygons works from those), which is also how long
-// fg_plan_create_great_circle_dev needs its caller's arrays.  Destroys the plan on failure.
+// grid (one launch) and its error word ahead of the search on the plan's stream, runs gc_search and hands the buffers back.
 static long gc_lonlat_search(fg_plan *pl, const double *const *d_lon_in, const double *const *d_lat_in, const double *const *d_mask_in,
-                             const double *d_lon_out, const double *d_lat_out, double mean_dlat, double mean_dlon)
+                             const double *d_lon_out, const double *d_lat_out, DstExtents x)
 {
   const int nt = pl->ntiles;
   std::vector<FgLl2xGrid> jobs(nt + 1);
@@ -1269,25 +1315,20 @@ static long gc_lonlat_search(fg_plan *pl, const double *const *d_lon_in, const d
   for (int m = 0; m <= nt; m++) {
     const size_t np = m < nt ? (size_t)(pl->nx_in[m] + 1) * (pl->ny_in[m] + 1) : (size_t)(pl->nx_out + 1) * (pl->ny_out + 1);
     double *d = pl->alloc<double>(3 * np);          // x | y | z
-    if (!d) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "out of device memory"); }
+    if (!d) return fail(FG_ERR_HIP, "out of device memory");
     blocks.push_back(d);
     jobs[m] = FgLl2xGrid{m < nt ? d_lon_in[m] : d_lon_out, m < nt ? d_lat_in[m] : d_lat_out, d, d + np, d + 2 * np, (long)np};
     gxyz[m] = GcXyz{d, d + np, d + 2 * np};
   }
   pl->ll_err = pl->alloc<unsigned>(1);
-  if (!pl->ll_err) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "out of device memory"); }
+  if (!pl->ll_err) return fail(FG_ERR_HIP, "out of device memory");
   blocks.push_back(pl->ll_err);
   hipError_t e = hipSetDevice(pl->device);
   if (e == hipSuccess) e = hipMemsetAsync(pl->ll_err, 0, sizeof(unsigned), pl->stream);
   if (e == hipSuccess) { fgd_latlon2xyz(jobs.data(), nt + 1, pl->ll_err, pl->stream); e = hipGetLastError(); }
-  if (e != hipSuccess) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "latlon2xyz: %s", hipGetErrorString(e)); }
-  if (!(mean_dlat > 0) || !(mean_dlon > 0)) {
-    CornerSample s;
-    if (sample_corners_dev(pl, pl->nx_out, pl->ny_out, 3, gxyz[nt].x, gxyz[nt].y, gxyz[nt].z, &s)) { fg_plan_destroy(pl); return FG_ERR_HIP; }
-    extents_xyz(s, &mean_dlat, &mean_dlon);
-  }
-  const long nx = plan_search(pl, nullptr, nullptr, d_mask_in, nullptr, nullptr, mean_dlat, mean_dlon, gxyz.data(), &gxyz[nt]);
-  if (nx < 0) { fg_plan_destroy(pl); return nx; }
+  if (e != hipSuccess) return fail(FG_ERR_HIP, "latlon2xyz: %s", hipGetErrorString(e));
+  const long nx = gc_search(pl, gxyz.data(), d_mask_in, x);
+  if (nx < 0) return nx;
   for (void *p : blocks) pl->release(p);
   pl->ll_err = nullptr;
   return nx;
@@ -1300,58 +1341,29 @@ extern "C" long fg_plan_create_great_circle_lonlat_dev(int ntiles_in, const int 
                                                        double mean_dlat, double mean_dlon, int device, void *stream, int use_caller_stream,
                                                        fg_plan **plan_out)
 {
-  if (!d_lon_in || !d_lat_in || !d_lon_out || !d_lat_out) return fail(FG_ERR_ARG, "null grid pointer");
-  for (int m = 0; m < ntiles_in; m++) if (!d_lon_in[m] || !d_lat_in[m]) return fail(FG_ERR_ARG, "null grid pointer");
-  fg_plan *pl = nullptr;
-  int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
-  if (rc) return rc;
-  if (use_caller_stream) {
-    g_handles.put_stream(pl->device, pl->stream);
-    pl->stream = (hipStream_t)stream; pl->own_stream = false;
-  }
-  const long nx = gc_lonlat_search(pl, d_lon_in, d_lat_in, d_mask_in, d_lon_out, d_lat_out, mean_dlat, mean_dlon);
-  if (nx >= 0) *plan_out = pl;
-  return nx;
+  PlanGuard g;
+  if (int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  if (int rc = check_grid_ptrs(ntiles_in, {d_lon_in, d_lat_in}, {d_lon_out, d_lat_out})) return rc;
+  if (use_caller_stream) adopt_stream(g.pl, stream);
+  const long nx = gc_lonlat_search(g.pl, d_lon_in, d_lat_in, d_mask_in, d_lon_out, d_lat_out, DstExtents{mean_dlat, mean_dlon});
+  return g.hand_over(nx, plan_out);
 }
 
-// host corner arrays: lon / lat go up through the transfer pool (16 bytes per vertex), the rest is the entry above
+// host corner arrays: lon / lat go up through the transfer pool (16 bytes per vertex), the rest is the entry above; the extents
+// come from the host arrays, as in fg_plan_create_great_circle (no read-back)
 extern "C" long fg_plan_create_great_circle_lonlat(int ntiles_in, const int *nx_in, const int *ny_in,
                                                    const double *const *lon_in, const double *const *lat_in, const double *const *mask_in,
                                                    int nx_out, int ny_out, const double *lon_out, const double *lat_out,
                                                    int device, fg_plan **plan_out)
 {
-  if (!lon_in || !lat_in || !lon_out || !lat_out) return fail(FG_ERR_ARG, "null grid pointer");
-  for (int m = 0; m < ntiles_in; m++) if (!lon_in[m] || !lat_in[m]) return fail(FG_ERR_ARG, "null grid pointer");
-  fg_plan *pl = nullptr;
-  int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
-  if (rc) return rc;
-  std::vector<const double *> dlon(ntiles_in), dlat(ntiles_in), dmask(ntiles_in, nullptr);
-  std::vector<void *> staged;
-  std::vector<XferJob> up_jobs;
-  auto up = [&](const double *h, size_t n) -> const double * {
-    double *d = pl->alloc<double>(n);
-    if (!d) return nullptr;
-    up_jobs.push_back(XferJob{(void *)h, d, n * sizeof(double), false});
-    staged.push_back(d);
-    return d;
-  };
-  bool ok = true;
-  for (int m = 0; m < ntiles_in && ok; m++) {
-    const size_t np = (size_t)(nx_in[m] + 1) * (ny_in[m] + 1);
-    dlon[m] = up(lon_in[m], np); dlat[m] = up(lat_in[m], np);
-    if (mask_in && mask_in[m]) { dmask[m] = up(mask_in[m], (size_t)nx_in[m] * ny_in[m]); ok = ok && dmask[m]; }
-    ok = ok && dlon[m] && dlat[m];
-  }
-  const size_t npo = (size_t)(nx_out + 1) * (ny_out + 1);
-  const double *dlo = ok ? up(lon_out, npo) : nullptr, *dla = ok ? up(lat_out, npo) : nullptr;
-  if (!ok || !dlo || !dla || !xfer_pool().run(device, up_jobs)) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)"); }
-  double mdlat, mdlon;
-  sample_extents(nx_out, ny_out, lon_out, lat_out, &mdlat, &mdlon);      // (as fg_plan_create_great_circle: from the host arrays, no read-back)
-  const long nx = gc_lonlat_search(pl, dlon.data(), dlat.data(), mask_in ? dmask.data() : nullptr, dlo, dla, mdlat, mdlon);
-  if (nx < 0) return nx;
-  for (void *p : staged) pl->release(p);
-  *plan_out = pl;
-  return nx;
+  PlanGuard g;
+  if (int rc = plan_base(FG_CONSERVE_ORDER1, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  StagedGrids s(g.pl);
+  if (int rc = stage_host_grids(g.pl, lon_in, lat_in, mask_in, lon_out, lat_out, &s)) return rc;
+  const long nx = gc_lonlat_search(g.pl, s.lon.data(), s.lat.data(), s.masks(), s.lon_out, s.lat_out,
+                                   dst_extents_host(nx_out, ny_out, lon_out, lat_out));
+  if (nx >= 0) s.up.done();
+  return g.hand_over(nx, plan_out);
 }
 
 // A search whose SOURCE cells are a list of polygons (<= 8 vertices each), e.g. the atmosphere x land cells of a coupler mosaic
@@ -1364,31 +1376,23 @@ extern "C" long fg_plan_create_polylist(int order, int npoly, const int *n, cons
                                         int device, fg_plan **plan_out)
 {
   if (npoly < 1 || !n || !lon || !lat || !lon_avg || !area_ref || !lon_out || !lat_out) return fail(FG_ERR_ARG, "null argument");
-  fg_plan *pl = nullptr;
+  PlanGuard g;
   const int one = 1;
-  int rc = plan_base(order, 1, &npoly, &one, nx_out, ny_out, device, &pl);
-  if (rc) return rc;
+  if (int rc = plan_base(order, 1, &npoly, &one, nx_out, ny_out, device, &g.pl)) return rc;
+  fg_plan *pl = g.pl;
   if (order == 2) pl->f_stride = npoly;                  // (no halo: the "field" of a polygon list is one value per polygon)
   const size_t npo = (size_t)(nx_out + 1) * (ny_out + 1);
-  int *d_n = pl->alloc<int>(npoly);
-  double *d_lon = pl->alloc<double>((size_t)npoly * 8), *d_lat = pl->alloc<double>((size_t)npoly * 8);
-  double *d_avg = pl->alloc<double>(npoly), *d_area = pl->alloc<double>(npoly), *d_lo = pl->alloc<double>(npo), *d_la = pl->alloc<double>(npo);
-  std::vector<XferJob> jobs = {{(void *)n, d_n, (size_t)npoly * sizeof(int), false}, {(void *)lon, d_lon, (size_t)npoly * 64, false},
-                               {(void *)lat, d_lat, (size_t)npoly * 64, false}, {(void *)lon_avg, d_avg, (size_t)npoly * 8, false},
-                               {(void *)area_ref, d_area, (size_t)npoly * 8, false}, {(void *)lon_out, d_lo, npo * 8, false}, {(void *)lat_out, d_la, npo * 8, false}};
-  if (!d_n || !d_lon || !d_lat || !d_avg || !d_area || !d_lo || !d_la || !xfer_pool().run(device, jobs)) {
-    fg_plan_destroy(pl); return fail(FG_ERR_HIP, "polygon upload failed (out of device memory?)");
-  }
-  pl->polys = FgPolyList{d_n, d_lon, d_lat, d_avg, d_area, npoly};
-  double mdlat, mdlon;
-  sample_extents(nx_out, ny_out, lon_out, lat_out, &mdlat, &mdlon);
+  HostUpload up{pl};
+  pl->polys = FgPolyList{up.put(n, npoly), up.put(lon, (size_t)npoly * 8), up.put(lat, (size_t)npoly * 8), up.put(lon_avg, npoly),
+                         up.put(area_ref, npoly), npoly};
+  double *d_lo = up.put(lon_out, npo), *d_la = up.put(lat_out, npo);
+  if (!up.run()) return fail(FG_ERR_HIP, "polygon upload failed (out of device memory?)");
+  const DstExtents x = dst_extents_host(nx_out, ny_out, lon_out, lat_out);
   const double *none[1] = {nullptr};
-  long nx = plan_search(pl, none, none, nullptr, d_lo, d_la, mdlat, mdlon, nullptr, nullptr, nullptr,
-                        host_says_not_rect(nx_out, ny_out, lon_out, lat_out) ? 0 : 1);
-  if (nx < 0) { fg_plan_destroy(pl); return nx; }
-  pl->release(d_lo); pl->release(d_la);
-  *plan_out = pl;
-  return nx;
+  const long nx = plan_search(pl, SearchIn{.lon_in = none, .lat_in = none, .lon_out = d_lo, .lat_out = d_la, .mean_dlat = x.dlat,
+                                           .mean_dlon = x.dlon, .rect_hint = x.rect_hint});
+  if (nx >= 0) { pl->release(d_lo); pl->release(d_la); }     // (the list stays with the plan)
+  return g.hand_over(nx, plan_out);
 }
 
 extern "C" int fg_plan_set_stream(fg_plan *pl, void *stream)
@@ -1396,8 +1400,7 @@ extern "C" int fg_plan_set_stream(fg_plan *pl, void *stream)
   if (!pl) return fail(FG_ERR_ARG, "null plan");
   HIPCHK(hipSetDevice(pl->device));
   HIPCHK(hipStreamSynchronize(pl->stream));
-  if (pl->own_stream && pl->stream) g_handles.put_stream(pl->device, pl->stream);
-  pl->stream = (hipStream_t)stream; pl->own_stream = false;
+  adopt_stream(pl, stream);
   return 0;
 }
 
@@ -1423,17 +1426,15 @@ void fg_plan_return_stream(fg_plan *pl, void *saved, int saved_own)
 extern "C" int fg_plan_create_empty(int order, int ntiles_in, const int *nx_in, const int *ny_in,
                                     int nx_out, int ny_out, int device, fg_plan **plan_out)
 {
-  fg_plan *pl = nullptr;
-  int rc = plan_base(order, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &pl);
-  if (rc) return rc;
+  PlanGuard g;
+  if (int rc = plan_base(order, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  fg_plan *pl = g.pl;
   std::vector<FgTile> th(pl->ntiles);
   for (int m = 0; m < pl->ntiles; m++) th[m] = FgTile{nullptr, nullptr, pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
   pl->tiles_dev = pl->alloc<FgTile>(pl->ntiles + 1);
-  if (!pl->tiles_dev || hipMemcpy(pl->tiles_dev, th.data(), sizeof(FgTile) * th.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    fg_plan_destroy(pl); return fail(FG_ERR_HIP, "out of device memory");
-  }
-  *plan_out = pl;
-  return 0;
+  if (!pl->tiles_dev || hipMemcpy(pl->tiles_dev, th.data(), sizeof(FgTile) * th.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(FG_ERR_HIP, "out of device memory");
+  return (int)g.hand_over(0, plan_out);
 }
 
 // The search sizes the exchange-cell arrays by capacity (8*max(nsrc, ndst) entries), about twice what a remap between grids of
@@ -2202,17 +2203,23 @@ static int b1_device(void)
   return e ? atoi(e) : 0;
 }
 
-extern "C" void get_grid_area(const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
+// get_grid_area / get_grid_great_circle_area: the source records of a plan against a 1x1 dummy destination, which keeps the plan
+// machinery uniform
+static void b1_grid_area(bool great_circle, const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
 {
-  // a 1x1 dummy destination keeps the plan machinery uniform; only the source records are used
   int nx = *nlon, ny = *nlat, one = 1;
   const double dl[4] = {0, 0.01, 0, 0.01}, da[4] = {0, 0, 0.01, 0.01};
   const double *lons[1] = {lon}, *lats[1] = {lat};
   fg_plan *pl = nullptr;
-  long rc = fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, b1_device(), &pl);
+  long rc = great_circle ? fg_plan_create_great_circle(1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, b1_device(), &pl)
+                         : fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, b1_device(), &pl);
   if (rc < 0) fatal(fg_last_error());
   if (fg_plan_get_cell_area(pl, area, nullptr)) fatal(fg_last_error());
   fg_plan_destroy(pl);
+}
+extern "C" void get_grid_area(const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
+{
+  b1_grid_area(false, nlon, nlat, lon, lat, area);
 }
 extern "C" void get_grid_area_(const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
 {
@@ -2246,14 +2253,7 @@ extern "C" int create_xgrid_great_circle_(const int *nlon_in, const int *nlat_in
 
 extern "C" void get_grid_great_circle_area(const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
 {
-  int nx = *nlon, ny = *nlat, one = 1;
-  const double dl[4] = {0, 0.01, 0, 0.01}, da[4] = {0, 0, 0.01, 0.01};      // dummy 1x1 destination
-  const double *lons[1] = {lon}, *lats[1] = {lat};
-  fg_plan *pl = nullptr;
-  long rc = fg_plan_create_great_circle(1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, b1_device(), &pl);
-  if (rc < 0) fatal(fg_last_error());
-  if (fg_plan_get_cell_area(pl, area, nullptr)) fatal(fg_last_error());
-  fg_plan_destroy(pl);
+  b1_grid_area(true, nlon, nlat, lon, lat, area);
 }
 extern "C" void get_grid_great_circle_area_(const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
 {
@@ -2378,9 +2378,9 @@ static int b1_create_xgrid_box(int box_is_src, int order, int nxb, int nyb, cons
   bm.mask_quad = box_is_src ? nullptr : d_mask;
   bm.no_adjust = (box_is_src && order == 1 && !(nxb > 1)) ? 1 : 0;
   const double *lons[1] = {d_tx}, *lats[1] = {d_ty}, *masks[1] = {box_is_src ? d_mask : nullptr};
-  double mdlat, mdlon;
-  sample_extents(nxq, nyq, lon_q, lat_q, &mdlat, &mdlon);
-  long nx = plan_search(pl, lons, lats, box_is_src ? masks : nullptr, d_lq, d_aq, mdlat, mdlon, nullptr, nullptr, &bm);
+  const DstExtents x = dst_extents_host(nxq, nyq, lon_q, lat_q);
+  long nx = plan_search(pl, SearchIn{.lon_in = lons, .lat_in = lats, .mask_in = box_is_src ? masks : nullptr, .lon_out = d_lq, .lat_out = d_aq,
+                                     .boxm = &bm, .mean_dlat = x.dlat, .mean_dlon = x.dlon});
   if (nx < 0) fatal(fg_last_error());
   if (nx > (long)MAXXGRID) fatal("nxgrid is greater than MAXXGRID, increase MAXXGRID");
   std::vector<int> bi(nx), bj(nx), qi(nx), qj(nx);
@@ -2536,16 +2536,19 @@ static int plan_apply_frac(fg_plan *pl, const double *data, double *out)
   return 0;
 }
 
-// interp.c:262-305: first-order remap with weights xarea / (sum of xarea over the destination cell)
-extern "C" void conserve_interp(int nx_src, int ny_src, int nx_dst, int ny_dst, const double *x_src,
-                                const double *y_src, const double *x_dst, const double *y_dst,
-                                const double *mask_src, const double *data_src, double *data_dst)
+// interp.c:262-305: first-order remap with weights xarea / (sum of xarea over the destination cell); interp.c:312: the same
+// with the great-circle exchange grid
+static void b1_conserve_interp(bool great_circle, int nx_src, int ny_src, int nx_dst, int ny_dst, const double *x_src,
+                               const double *y_src, const double *x_dst, const double *y_dst,
+                               const double *mask_src, const double *data_src, double *data_dst)
 {
   const double *lons[1] = {x_src}, *lats[1] = {y_src}, *masks[1] = {mask_src};
   fg_plan *pl = nullptr;
-  long nx = fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, b1_device(), &pl);
+  long nx = great_circle ? fg_plan_create_great_circle(1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, b1_device(), &pl)
+                         : fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, b1_device(), &pl);
   if (nx < 0) fatal(fg_last_error());
-  if (nx >= (long)MAXXGRID)
+  if (great_circle && nx > (long)MAXXGRID) fatal("nxgrid is greater than MAXXGRID, increase MAXXGRID");
+  if (!great_circle && nx >= (long)MAXXGRID)
     fatal("The xgrid size is too large for resources.\n nxgrid is greater than MAXXGRID/nthreads; increase MAXXGRID,\n"
           " decrease nthreads, or increase number of MPI ranks.");
   if (fg_plan_finalize(pl, nullptr)) fatal(fg_last_error());
@@ -2558,26 +2561,17 @@ extern "C" void conserve_interp(int nx_src, int ny_src, int nx_dst, int ny_dst, 
   (void)hipFree(dsrc); (void)hipFree(ddst);
   fg_plan_destroy(pl);
 }
-
-// interp.c:312 -- the same with the great-circle exchange grid
+extern "C" void conserve_interp(int nx_src, int ny_src, int nx_dst, int ny_dst, const double *x_src,
+                                const double *y_src, const double *x_dst, const double *y_dst,
+                                const double *mask_src, const double *data_src, double *data_dst)
+{
+  b1_conserve_interp(false, nx_src, ny_src, nx_dst, ny_dst, x_src, y_src, x_dst, y_dst, mask_src, data_src, data_dst);
+}
 extern "C" void conserve_interp_great_circle(int nx_src, int ny_src, int nx_dst, int ny_dst, const double *x_src,
                                              const double *y_src, const double *x_dst, const double *y_dst,
                                              const double *mask_src, const double *data_src, double *data_dst)
 {
-  const double *lons[1] = {x_src}, *lats[1] = {y_src}, *masks[1] = {mask_src};
-  fg_plan *pl = nullptr;
-  long nx = fg_plan_create_great_circle(1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, b1_device(), &pl);
-  if (nx < 0) fatal(fg_last_error());
-  if (nx > (long)MAXXGRID) fatal("nxgrid is greater than MAXXGRID, increase MAXXGRID");
-  if (fg_plan_finalize(pl, nullptr)) fatal(fg_last_error());
-  size_t ns = (size_t)nx_src * ny_src, nd = (size_t)nx_dst * ny_dst;
-  double *dsrc = nullptr, *ddst = nullptr;
-  if (hipMalloc(&dsrc, ns * sizeof(double)) != hipSuccess || hipMalloc(&ddst, nd * sizeof(double)) != hipSuccess) fatal("hipMalloc failed");
-  if (hipMemcpy(dsrc, data_src, ns * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) fatal("hipMemcpy failed");
-  if (plan_apply_frac(pl, dsrc, ddst)) fatal(fg_last_error());
-  if (hipMemcpy(data_dst, ddst, nd * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) fatal("hipMemcpy failed");
-  (void)hipFree(dsrc); (void)hipFree(ddst);
-  fg_plan_destroy(pl);
+  b1_conserve_interp(true, nx_src, ny_src, nx_dst, ny_dst, x_src, y_src, x_dst, y_dst, mask_src, data_src, data_dst);
 }
 
 // ----------------------------------------------------------------------------- polygon primitives

@@ -358,6 +358,8 @@ int  fg_plan_phase_ms(fg_plan *plan, float *ms, int n);   /* [9] = mean over the
  * [2]=nxgrid, [3]=pairs whose area ratio is within 1e-9 (relative) of the 1e-6 threshold,
  * [4]=bins, [5]=bin entries.  n = capacity of stats. */
 int fg_plan_stats(const fg_plan *plan, long *stats, int n);
+/* The search switches (fg_set_search_*, fg_set_gc_split, and fg_set_profiling for the search phases) are process-wide, are read
+ * once when a plan-creating call starts, and do not affect a search already running. */
 /* Search mode.  0 (default): every buffer of the search is sized by capacity (bin records 3*ndst, candidate pairs and
  * exchange cells 8*max(nsrc, ndst)), counts stay on the device and the host synchronises once, at the end; a search that
  * outgrows a capacity is repeated transparently with the sizes its counters report.  1: size every buffer by counting
