@@ -13,6 +13,8 @@ mirrors the reference's call signatures:
 
 * ``do_extrapolate`` / ``setup_vertical_interp`` / ``do_vertical_interp``
   -- tools/fregrid/fregrid_util.c:2662,756,789 (--extrapolate fill of a lat-lon source, --dst_vgrid levels)
+* ``RunoffRegrid`` / ``nearest_unmasked`` / ``runoff_input_grid`` / ``runoff_output_grid``
+  -- tools/runoff_regrid/runoff_regrid.c:430,626,708,243,322 (setup_remap, process_data's arithmetic, nearest, the grids)
 
 There is NO CPU fallback: if the shared library is missing, or no HIP device is visible
 when a compute entry point is called, an exception is raised.
@@ -34,6 +36,8 @@ from .bilinear import (BilinearPlan, setup_bilinear_interp, do_scalar_bilinear_i
                        write_bilinear_remap_file, read_bilinear_remap_file)
 from .extrapolate import (Extrapolator, do_extrapolate, setup_vertical_interp, do_vertical_interp,  # noqa: F401
                           set_extrap_batch, set_extrap_coef, extrap_coef_host)
+from .runoff import (RunoffRegrid, nearest_unmasked, runoff_input_grid, runoff_output_grid,  # noqa: F401
+                     set_runoff_prune, runoff_tile)
 from .parallel import (band_rows, row_cost, allreduce_cell_sums, allreduce_scalar_sum, allreduce_minmax,  # noqa: F401
                        boundary_source_cells, allreduce_cell_sums_sparse, ordered_cell_sums, CellSumExchange)
 from .conserve_interp import (  # noqa: F401
@@ -50,6 +54,7 @@ __all__ = [
     "BilinearPlan", "setup_bilinear_interp", "do_scalar_bilinear_interp", "do_vector_bilinear_interp",
     "write_bilinear_remap_file", "read_bilinear_remap_file",
     "Extrapolator", "do_extrapolate", "setup_vertical_interp", "do_vertical_interp",
+    "RunoffRegrid", "nearest_unmasked", "runoff_input_grid", "runoff_output_grid",
 ]
 
 

@@ -55,6 +55,9 @@ EXPORTS = [
     "fg_extrap_last_syncs", "fg_extrap_get_coef", "fg_extrap_coef_host", "fg_set_extrap_batch", "fg_set_extrap_coef",
     "fg_setup_vertical_interp", "fg_dev_vertical_interp",
     "fg_dev_latlon2xyz", "fg_plan_create_great_circle_lonlat", "fg_plan_create_great_circle_lonlat_dev",
+    "fg_runoff_create", "fg_runoff_create_from_xgrid", "fg_runoff_destroy", "fg_runoff_nxgrid", "fg_runoff_get_xgrid",
+    "fg_runoff_get_maps", "fg_runoff_get_xyz", "fg_runoff_search_stats", "fg_runoff_phase_ms", "fg_runoff_stream", "fg_runoff_apply", "fg_runoff_apply_dev",
+    "fg_nearest_unmasked", "fg_set_runoff_prune", "fg_runoff_tile",
 ]
 
 
@@ -379,6 +382,37 @@ def lib():
     L.fg_setup_vertical_interp.restype = C.c_int
     L.fg_dev_vertical_interp.argtypes = [C.c_long, C.c_int, dp, C.c_int, dp, vp, vp]
     L.fg_dev_vertical_interp.restype = C.c_int
+    L.fg_runoff_create.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_int, C.c_int] + [dp] * 6 + [C.c_int, C.POINTER(vp)]
+    L.fg_runoff_create.restype = C.c_int
+    L.fg_runoff_create_from_xgrid.argtypes = [C.c_int, C.c_int, dp, dp, C.c_int, C.c_int] + [dp] * 4 + [C.c_long] + [ip] * 4 + \
+        [dp, C.c_int, C.POINTER(vp)]
+    L.fg_runoff_create_from_xgrid.restype = C.c_int
+    L.fg_runoff_destroy.argtypes = [vp]
+    L.fg_runoff_destroy.restype = None
+    L.fg_runoff_nxgrid.argtypes = [vp]
+    L.fg_runoff_nxgrid.restype = C.c_long
+    L.fg_runoff_get_xgrid.argtypes = [vp] + [ip] * 4 + [dp]
+    L.fg_runoff_get_xgrid.restype = C.c_int
+    L.fg_runoff_get_maps.argtypes = [vp, ip, ip]
+    L.fg_runoff_get_maps.restype = C.c_int
+    L.fg_runoff_get_xyz.argtypes = [vp, dp, dp, dp]
+    L.fg_runoff_get_xyz.restype = C.c_int
+    L.fg_runoff_search_stats.argtypes = [vp, C.POINTER(C.c_long)]
+    L.fg_runoff_search_stats.restype = C.c_int
+    L.fg_runoff_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    L.fg_runoff_phase_ms.restype = C.c_int
+    L.fg_runoff_stream.argtypes = [vp]
+    L.fg_runoff_stream.restype = vp
+    L.fg_runoff_apply.argtypes = [vp, dp, dp, dp]
+    L.fg_runoff_apply.restype = C.c_int
+    L.fg_runoff_apply_dev.argtypes = [vp, vp, vp, dp]
+    L.fg_runoff_apply_dev.restype = C.c_int
+    L.fg_nearest_unmasked.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_int, ip, ip, ip]
+    L.fg_nearest_unmasked.restype = C.c_int
+    L.fg_set_runoff_prune.argtypes = [C.c_int]
+    L.fg_set_runoff_prune.restype = None
+    L.fg_runoff_tile.argtypes = []
+    L.fg_runoff_tile.restype = C.c_int
     _LIB = L
     return L
 

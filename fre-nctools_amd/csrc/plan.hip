@@ -2349,21 +2349,22 @@ extern "C" int clip_2dx2d_great_circle(const double x1_in[], const double y1_in[
   return n_out;
 }
 
-// create_xgrid_1dx2d_order1/2 and create_xgrid_2dx1d_order1/2 (create_xgrid.c:208-591) through the shared search pipeline
-static int b1_create_xgrid_box(int box_is_src, int order, int nxb, int nyb, const double *lon_b, const double *lat_b,
-                               int nxq, int nyq, const double *lon_q, const double *lat_q, const double *mask,
-                               int *i_in, int *j_in, int *i_out, int *j_out, double *xgrid_area, double *xgrid_clon, double *xgrid_clat)
+// create_xgrid_1dx2d_order1/2 and create_xgrid_2dx1d_order1/2 (create_xgrid.c:208-591) through the shared search pipeline.
+// fg_box_xgrid_lists is the part that can fail with a code (runoff.hip calls it on its own device); lists as (box i, box j, quad i, quad j).
+long fg_box_xgrid_lists(int dev, int box_is_src, int order, int nxb, int nyb, const double *lon_b, const double *lat_b,
+                        int nxq, int nyq, const double *lon_q, const double *lat_q, const double *mask,
+                        std::vector<int> idx[4], std::vector<double> &area, std::vector<double> *clon, std::vector<double> *clat)
 {
-  const int dev = b1_device();
-  if (nxb < 1 || nyb < 1 || nxq < 1 || nyq < 1) fatal("create_xgrid: bad grid sizes");
+  if (nxb < 1 || nyb < 1 || nxq < 1 || nyq < 1) return fail(FG_ERR_ARG, "create_xgrid: bad grid sizes");
   fg_plan *pl = nullptr;
-  if (plan_base(order, 1, &nxb, &nyb, nxq, nyq, dev, &pl)) fatal(fg_last_error());
+  int rc = plan_base(order, 1, &nxb, &nyb, nxq, nyq, dev, &pl);
+  if (rc) return rc;
   const size_t npb = (size_t)(nxb + 1) * (nyb + 1), npq = (size_t)(nxq + 1) * (nyq + 1);
   std::vector<double> tx(npb), ty(npb);                                  // the reference's tmpx/tmpy, :229-236
   for (int j = 0; j <= nyb; j++) for (int i = 0; i <= nxb; i++) { tx[(size_t)j * (nxb + 1) + i] = lon_b[i]; ty[(size_t)j * (nxb + 1) + i] = lat_b[j]; }
   const size_t nmask = box_is_src ? (size_t)nxb * nyb : (size_t)nxq * nyq;
   double *d = pl->alloc<double>(2 * npb + 2 * npq + (nxb + 1) + (nyb + 1) + nmask);
-  if (!d) fatal("out of device memory");
+  if (!d) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "out of device memory"); }
   double *d_tx = d, *d_ty = d_tx + npb, *d_lq = d_ty + npb, *d_aq = d_lq + npq, *d_lb = d_aq + npq, *d_ab = d_lb + (nxb + 1), *d_mask = d_ab + (nyb + 1);
   bool ok = hipMemcpy(d_tx, tx.data(), npb * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(d_ty, ty.data(), npb * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
@@ -2372,7 +2373,7 @@ static int b1_create_xgrid_box(int box_is_src, int order, int nxb, int nyb, cons
             hipMemcpy(d_lb, lon_b, (nxb + 1) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(d_ab, lat_b, (nyb + 1) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(d_mask, mask, nmask * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) fatal("grid upload failed");
+  if (!ok) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "grid upload failed"); }
   BoxMode bm;
   bm.box = FgBox{d_lb, d_ab, nxb, nyb};
   bm.mask_quad = box_is_src ? nullptr : d_mask;
@@ -2381,16 +2382,30 @@ static int b1_create_xgrid_box(int box_is_src, int order, int nxb, int nyb, cons
   const DstExtents x = dst_extents_host(nxq, nyq, lon_q, lat_q);
   long nx = plan_search(pl, SearchIn{.lon_in = lons, .lat_in = lats, .mask_in = box_is_src ? masks : nullptr, .lon_out = d_lq, .lat_out = d_aq,
                                      .boxm = &bm, .mean_dlat = x.dlat, .mean_dlon = x.dlon});
-  if (nx < 0) fatal(fg_last_error());
-  if (nx > (long)MAXXGRID) fatal("nxgrid is greater than MAXXGRID, increase MAXXGRID");
-  std::vector<int> bi(nx), bj(nx), qi(nx), qj(nx);
-  if (fg_plan_get_xgrid(pl, nullptr, bi.data(), bj.data(), qi.data(), qj.data(), xgrid_area, order == 2 ? xgrid_clon : nullptr,
-                        order == 2 ? xgrid_clat : nullptr)) fatal(fg_last_error());
-  for (long k = 0; k < nx; k++) {
-    if (box_is_src) { i_in[k] = bi[k]; j_in[k] = bj[k]; i_out[k] = qi[k]; j_out[k] = qj[k]; }
-    else { i_in[k] = qi[k]; j_in[k] = qj[k]; i_out[k] = bi[k]; j_out[k] = bj[k]; }
-  }
+  if (nx < 0) { fg_plan_destroy(pl); return nx; }
+  if (nx > (long)MAXXGRID) { fg_plan_destroy(pl); return fail(FG_ERR_CAPACITY, "nxgrid is greater than MAXXGRID, increase MAXXGRID"); }
+  for (int k = 0; k < 4; k++) idx[k].resize(nx);
+  area.resize(nx);
+  if (order == 2) { clon->resize(nx); clat->resize(nx); }
+  rc = fg_plan_get_xgrid(pl, nullptr, idx[0].data(), idx[1].data(), idx[2].data(), idx[3].data(), area.data(),
+                         order == 2 ? clon->data() : nullptr, order == 2 ? clat->data() : nullptr);
   fg_plan_destroy(pl);
+  return rc ? rc : nx;
+}
+
+static int b1_create_xgrid_box(int box_is_src, int order, int nxb, int nyb, const double *lon_b, const double *lat_b,
+                               int nxq, int nyq, const double *lon_q, const double *lat_q, const double *mask,
+                               int *i_in, int *j_in, int *i_out, int *j_out, double *xgrid_area, double *xgrid_clon, double *xgrid_clat)
+{
+  std::vector<int> idx[4];
+  std::vector<double> area, clon, clat;
+  const long nx = fg_box_xgrid_lists(b1_device(), box_is_src, order, nxb, nyb, lon_b, lat_b, nxq, nyq, lon_q, lat_q, mask, idx, area, &clon, &clat);
+  if (nx < 0) fatal(fg_last_error());
+  const size_t ni = (size_t)nx * sizeof(int), nd = (size_t)nx * sizeof(double);
+  memcpy(box_is_src ? i_in : i_out, idx[0].data(), ni); memcpy(box_is_src ? j_in : j_out, idx[1].data(), ni);
+  memcpy(box_is_src ? i_out : i_in, idx[2].data(), ni); memcpy(box_is_src ? j_out : j_in, idx[3].data(), ni);
+  memcpy(xgrid_area, area.data(), nd);
+  if (order == 2) { memcpy(xgrid_clon, clon.data(), nd); memcpy(xgrid_clat, clat.data(), nd); }
   return (int)nx;
 }
 

@@ -380,3 +380,38 @@ FG_HD bool fgs_latlon2xyz_vertex(double lon, double lat, double *x, double *y, d
   *z = ok ? sl : (double)NAN;
   return ok;
 }
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * libm sincos() beyond 2.426265: the same branch of s_sincos.c (reduce_sincos + do_sincos twice, q = n and n + 1) WITHOUT
+ * contraction -- every product and sum rounded on its own, as fgs_sincos is below the hand-over.  On the hosts the fixtures
+ * come from, libm's sincos() is the uncontracted build on this branch too (tests/test_runoff_cpu.py pins it against the host,
+ * bit for bit).  The compiled runoff_regrid.c calls sincos() for every sin/cos pair of distance(), longitudes included.
+ * Same range as the siblings above: |x| <= FGS_WIDE_MAX, NaN beyond and for a non-finite argument. */
+FG_HD int fgs_reduce_wide_n(double x, double *a, double *da)
+{
+  const double t = x * FGS_HPINV + FGS_TOINT;
+  const double xn = t - FGS_TOINT;
+  union { double d; uint64_t b; } c; c.d = t;
+  const double y = (x - xn * FGS_MP1) - xn * FGS_MP2;
+  double t1 = xn * FGS_PP3;
+  const double t2 = y - t1;
+  double db = (y - t2) - t1;
+  t1 = xn * FGS_PP4;
+  const double b = t2 - t1;
+  db += (t2 - b) - t1;
+  *a = b; *da = db;
+  return (int)(c.b & 3u);
+}
+FG_HD void fgs_sincos_wide(double x, double *sinx, double *cosx)
+{
+  const double ax = fabs(x);
+  if (ax < FGS_WIDE_MIN) { fgs_sincos(x, sinx, cosx); return; }
+  if (!(ax <= FGS_WIDE_MAX)) { *sinx = *cosx = (double)NAN; return; }
+  double a, da;
+  const int n = fgs_reduce_wide_n(x, &a, &da);
+  const double co = fgs_do_cos<false, false>(a, da);      /* the odd quadrant of the pair */
+  const double si = fgs_do_sin<false, false>(a, da);      /* the even one (Taylor below |a| = 0.126, signed like a) */
+  const double rs = (n & 1) ? co : si, rc = (n & 1) ? si : co;
+  *sinx = (n & 2) ? -rs : rs;
+  *cosx = ((n + 1) & 2) ? -rc : rc;
+}

@@ -789,6 +789,44 @@ int  fg_setup_vertical_interp(int nk1, const double *z1, int nk2, const double *
  * "grid2 lies outside grid1", ...) return FG_ERR_DATA with its message.  Synchronous. */
 int  fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int nk2, const double *z2, const double *d_in, double *d_out);
 
+/* ---- runoff_regrid on the device (tools/runoff_regrid/runoff_regrid.c: setup_remap :430, process_data :626-675, nearest :708) ----
+ * All angles in radians, as setup_remap receives them.  The exchange list is create_xgrid_1dx2d_order1's; the nearest ocean
+ * point (mask_out != 0) of every land point (mask_out == 0) is the reference's, bit for bit: the first point in row-major order
+ * among those with the smallest rounded distance() r, r < distance(0, pi/2, 0, -pi/2) strictly; imap = jmap = -1 on ocean
+ * points and where no ocean point qualifies.  A mask_out without an ocean point is FG_ERR_ARG (the reference indexes with -1). */
+typedef struct fg_runoff fg_runoff;
+int  fg_runoff_create(int nx_in, int ny_in, const double *lonb_in, const double *latb_in, const double *mask_in,
+                      int nx_out, int ny_out, const double *xc, const double *yc, const double *xt, const double *yt,
+                      const double *mask_out, const double *area_out, int device, fg_runoff **out);
+/* the same with a given exchange list (the analogue of fg_plan_set_xgrid); mask_in, area_in [ny_in*nx_in] serve the input total */
+int  fg_runoff_create_from_xgrid(int nx_in, int ny_in, const double *mask_in, const double *area_in, int nx_out, int ny_out,
+                                 const double *xt, const double *yt, const double *mask_out, const double *area_out,
+                                 long nxgrid, const int *i_in, const int *j_in, const int *i_out, const int *j_out,
+                                 const double *xgrid_area, int device, fg_runoff **out);
+void fg_runoff_destroy(fg_runoff *h);
+long fg_runoff_nxgrid(const fg_runoff *h);
+int  fg_runoff_get_xgrid(const fg_runoff *h, int *i_in, int *j_in, int *i_out, int *j_out, double *xgrid_area);   /* any may be NULL */
+int  fg_runoff_get_maps(const fg_runoff *h, int *imap, int *jmap);          /* [ny_out*nx_out] */
+int  fg_runoff_get_xyz(fg_runoff *h, double *x, double *y, double *z);      /* distance()'s point triples [ny_out*nx_out] (tests) */
+/* queries, tiles, tiles visited over all queries, most tiles visited by one query -- of the handle's search */
+int  fg_runoff_search_stats(const fg_runoff *h, long *stats4);
+/* wall time of the handle's setup in ms (the first n of 5): exchange list with the input areas (fg_runoff_create only), point
+ * conversion, nearest search (compaction, balls, kernel, read-back), its kernel alone (events), host sorts and uploads */
+int  fg_runoff_phase_ms(const fg_runoff *h, float *ms, int n);
+void *fg_runoff_stream(fg_runoff *h);
+/* One time level: remap sum in list order, runoff move (ascending land index onto the target's own value; a value <= 0 stays),
+ * division by area_out.  totals (may be NULL): sum of in*area_in over mask_in > 0, sum of out*area_out, each summed by 1024
+ * strided partial sums and a binary tree over them.  _dev: device pointers (different arrays), on the handle's stream; it
+ * synchronises only when totals is given. */
+int  fg_runoff_apply(fg_runoff *h, const double *in, double *out, double *totals);
+int  fg_runoff_apply_dev(fg_runoff *h, const double *d_in, double *d_out, double *totals);
+/* nearest() alone for the grid points qindex[nq] (row-major indices): host pointers, device FREGRID_HIP_DEVICE or 0 */
+int  fg_nearest_unmasked(int nlon, int nlat, const double *mask, const double *lon, const double *lat, int nq,
+                         const int *qindex, int *iout, int *jout);
+/* Test hook; results never depend on it.  1 (default): tiles are skipped by their bounding balls; 0: every tile is visited. */
+void fg_set_runoff_prune(int on);
+int  fg_runoff_tile(void);                                                  /* compacted ocean points per tile */
+
 #ifdef __cplusplus
 }
 #endif
