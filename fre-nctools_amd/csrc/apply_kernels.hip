@@ -24,12 +24,14 @@ __global__ __launch_bounds__(256) void k_csr_count(long nx, const int *x_dst, in
 // Slot of every exchange cell in its destination row.  Exchange cells are ordered by source cell, so in a fine -> coarse remap
 // long runs of consecutive cells fall into the same row (C768 -> 1 deg: ~8): one atomic per run of equal rows within a wave
 // instead of one per cell (the per-cell version spent 0.4 ms there on same-address atomics); the cells of a run take
-// consecutive slots in ascending order.
-__global__ __launch_bounds__(256) void k_csr_fill(long nx, const int *x_dst, const int *row_ptr, int *row_fill, int *perm)
+// consecutive slots in ascending order.  The entry stored is the pair {exchange cell, its source cell} (x_src[n], read here
+// beside x_dst[n]: coalesced).
+__global__ __launch_bounds__(256) void k_csr_fill(long nx, const int *x_src, const int *x_dst, const int *row_ptr, int *row_fill, FgRowEnt *perm)
 {
   const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const int d = (n < nx) ? x_dst[n] : -1;
+  const int s = (n < nx) ? x_src[n] : 0;
   const int prev = __shfl_up(d, 1);
   const bool head = (lane == 0) || (d != prev);
   const unsigned long long heads = __ballot(head);
@@ -39,25 +41,29 @@ __global__ __launch_bounds__(256) void k_csr_fill(long nx, const int *x_dst, con
   int base = 0;
   if (lane == start && d >= 0) base = atomicAdd(&row_fill[d], end - start);
   base = __shfl(base, start);
-  if (d >= 0) perm[row_ptr[d] + base + (lane - start)] = (int)n;
+  if (d >= 0) perm[row_ptr[d] + base + (lane - start)] = FgRowEnt{(int)n, s};
 }
 
 // the same with slots already taken while the search compacted its exchange cells (k_compact): no atomics.  Launched for
 // the capacity of the exchange-cell arrays when the host does not know the count yet (nx_dev)
-__global__ __launch_bounds__(256) void k_csr_fill_pos(long nx, const unsigned long long *nx_dev, const int *x_dst, const int *row_ptr,
-                                                       const int *x_rowpos, int *perm)
+__global__ __launch_bounds__(256) void k_csr_fill_pos(long nx, const unsigned long long *nx_dev, const int *x_src, const int *x_dst,
+                                                       const int *row_ptr, const int *x_rowpos, FgRowEnt *perm)
 {
   if (nx_dev) { const unsigned long long nd = *nx_dev; if (nd < (unsigned long long)nx) nx = (long)nd; }
   const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n < nx) perm[row_ptr[x_dst[n]] + x_rowpos[n]] = (int)n;
+  if (n < nx) { const int s = x_src[n]; perm[row_ptr[x_dst[n]] + x_rowpos[n]] = FgRowEnt{(int)n, s}; }
 }
 
-// Rows of `perm` into ascending exchange-cell order, then the packed CSR records -- one kernel.  A block owns RPW consecutive
-// rows, i.e. one contiguous run of perm: it is staged in LDS, every lane sorts its own row there by insertion (rows are short
-// when the grids are of similar resolution, ~4 entries); rows longer than SHORT (fine -> coarse remaps: 50-1000 entries) are
-// sorted by the whole wave, every lane placing its elements at their rank (the exchange-cell numbers are distinct).  The
-// records then leave in one coalesced sweep over the run.  RPW = 64 when rows are short, 16 when the mean row is long, so that
-// four times as many waves are in flight.  Runs beyond the staging capacity are sorted in place in global memory.
+// Rows of `perm` into ascending exchange-cell order, then the packed CSR records -- one kernel.  An entry of perm is the pair
+// {exchange cell n, its source cell s}: the rows are ordered by n and s moves with it, so that the record loop knows both
+// addresses of an entry at once.  A block owns RPW consecutive rows, i.e. one contiguous run of perm: it is staged in LDS (the
+// exchange cells in sh, the source cells in shs), every lane sorts its own row there by insertion (rows are short when the grids
+// are of similar resolution, ~4 entries); rows longer than SHORT (fine -> coarse remaps: 50-1000 entries) are sorted by the whole
+// wave, every lane placing its elements at their rank (the exchange-cell numbers are distinct).  The lanes hold their elements
+// in registers while the ranks are counted, so after a barrier the placement goes back into sh / shs themselves: no landing
+// buffer, and the LDS a block needs is what it was when the lists held the exchange cell alone.  The records then leave in one
+// coalesced sweep over the run.  RPW = 64 when rows are short, 16 when the mean row is long, so that four times as many waves
+// are in flight.  Runs beyond the staging capacity are sorted in place in global memory.
 // DIST (order 2): x_c1/x_c2 still hold the centroid integrals; di = clon/area - cen_lon, dj = clat/area - cen_lat
 // (conserve_interp.c:256-257,355-356) are formed here, the operations k_distances applies to the arrays themselves.
 // rank[k] += number of keys[0..n) below v[k]: one walk over the keys (LDS) for N values -- a walk per value waits for LDS once
@@ -78,30 +84,46 @@ __device__ __forceinline__ void d_rank_count(const int *keys, int n, const int (
   }
 }
 
+// A packed CSR record to its place with non-temporal 16-byte stores.  The finalize writes every record once and reads none, while
+// the lines of x_area / x_c1 / x_c2 are shared by the gathers of neighbouring rows: at C384 -> 0.25 deg (133 MB of records)
+// k_csr_sortgather takes 103.4 us with ordinary stores and 96.7 us with these (profiles/csr_row_pairs_summary.md).
+template <typename E>
+__device__ __forceinline__ void d_store_stream(E *dst, const E &e)
+{
+  typedef int v4i __attribute__((ext_vector_type(4)));
+  static_assert(sizeof(E) % 16 == 0 && alignof(E) >= 8, "records are whole 16-byte words");
+  v4i w[sizeof(E) / 16];
+  __builtin_memcpy(w, &e, sizeof(E));
+#pragma unroll
+  for (unsigned k = 0; k < sizeof(E) / 16; k++) __builtin_nontemporal_store(w[k], (v4i *)dst + k);
+}
+
 // The records of a block's run of perm (nq entries from q0; STAGED: sorted in LDS, else in perm itself): G entries per lane and
-// pass, so that a wave has G gathers in flight in each of the two dependent rounds (by exchange cell, then by its source cell)
-// instead of one.  Entries past the run's end repeat the pass's first one and store nothing.  Per entry the operations are
-// those of a one-entry loop, in the same order.  (STAGED is a template constant: chosen per load, LDS or global memory, the
-// index reads become flat loads, which are waited for one by one.)
+// pass.  An entry names its exchange cell and its source cell, so all its loads go out in ONE round: area (order 2: and the two
+// integrals) by exchange cell; the field index and (DIST) the centroid record of k_centroids by source cell.  Entries past the
+// run's end repeat the pass's first one and store nothing.  Per entry the operations are those of a one-entry loop, in the same
+// order.  (STAGED is a template constant: chosen per load, LDS or global memory, the index reads become flat loads, which are
+// waited for one by one.)
 template <int ORDER, bool DIST, int BT, int G, bool STAGED>
-__device__ __forceinline__ void d_csr_records(const int *sh, const int *perm, int q0, int nq, const int *x_src, const double *x_area,
-                                              const double *x_c1, const double *x_c2, const int *src_idx_f, const double *cen, int nsrc,
+__device__ __forceinline__ void d_csr_records(const int *sh, const int *shs, const FgRowEnt *perm, int q0, int nq, const double *x_area,
+                                              const double *x_c1, const double *x_c2, const int *src_idx_f, const FgSrcRec *cen,
                                               const FgCsr &csr)
 {
   for (int i0 = threadIdx.x; i0 < nq; i0 += BT * G) {
     int n[G], s[G], idx[G];
     double ar[G], c1[G], c2[G], cl[G], ct[G];
 #pragma unroll
-    for (int g = 0; g < G; g++) { const int i = i0 + BT * g, ic = (i < nq) ? i : i0; n[g] = STAGED ? sh[ic] : perm[q0 + ic]; }
-#pragma unroll
     for (int g = 0; g < G; g++) {
-      s[g] = x_src[n[g]]; ar[g] = x_area[n[g]];
-      if (ORDER == 2) { c1[g] = x_c1[n[g]]; c2[g] = x_c2[n[g]]; }
+      const int i = i0 + BT * g, ic = (i < nq) ? i : i0;
+      if (STAGED) { n[g] = sh[ic]; s[g] = shs[ic]; }
+      else { const FgRowEnt p = perm[q0 + ic]; n[g] = p.n; s[g] = p.s; }
     }
 #pragma unroll
     for (int g = 0; g < G; g++) {
+      ar[g] = x_area[n[g]];
+      if (ORDER == 2) { c1[g] = x_c1[n[g]]; c2[g] = x_c2[n[g]]; }
       idx[g] = src_idx_f[s[g]];
-      if (ORDER == 2 && DIST) { cl[g] = cen[s[g]]; ct[g] = cen[nsrc + s[g]]; }
+      if (ORDER == 2 && DIST) { const FgSrcRec r = cen[s[g]]; cl[g] = r.cen_lon; ct[g] = r.cen_lat; }
     }
 #pragma unroll
     for (int g = 0; g < G; g++) {
@@ -114,29 +136,40 @@ __device__ __forceinline__ void d_csr_records(const int *sh, const int *perm, in
           di -= cl[g]; dj -= ct[g];
           E.di = di; E.dj = dj;
         } else { E.di = c1[g]; E.dj = c2[g]; }
-        if (i < nq) csr.e2[q0 + i] = E;
+        if (i < nq) d_store_stream(&csr.e2[q0 + i], E);
       } else {
         FgCsrEntry1 E;
         E.idx_f = idx[g]; E.pad = 0; E.area = ar[g];
-        if (i < nq) csr.e1[q0 + i] = E;
+        if (i < nq) d_store_stream(&csr.e1[q0 + i], E);
       }
     }
   }
 }
 
-// entries per lane and pass of the record loop.  2 and 4 take the same time on C384 -> 0.25 deg (113.4 / 113.1 us, 117.9 with
-// one); 4 costs the DIST kernels 76 registers (6 waves per SIMD instead of 8) and the finalize of a coarse -> fine plan 4-7 us
-// (C96 -> 0.25 deg: 54 us with 2, 62 with 4, 59 with one): profiles/compact_finalize_loads_summary.md
+// lane-serial insertion of the row [b, e) of perm (global memory), ordered by exchange cell
+__device__ __forceinline__ void d_row_insertion(FgRowEnt *perm, int b, int e)
+{
+  for (int i = b + 1; i < e; i++) {
+    const FgRowEnt v = perm[i];
+    int j = i - 1;
+    while (j >= b && perm[j].n > v.n) { perm[j + 1] = perm[j]; j--; }
+    perm[j + 1] = v;
+  }
+}
+
+// entries per lane and pass of the record loop.  2 and 4 take the same time on C384 -> 0.25 deg, with an entry's loads in two
+// dependent rounds (113.4 / 113.1 us, 117.9 with one: profiles/compact_finalize_loads_summary.md) and in one (101.3 / 102.1 us:
+// profiles/csr_row_pairs_summary.md); 4 costs the DIST kernels registers and cost the finalize of a coarse -> fine plan 4-7 us
+// (C96 -> 0.25 deg: 54 us with 2, 62 with 4, 59 with one)
 #define SG_GROUP 2
 template <int ORDER, int RPW, bool DIST, int BT, int G>
-__global__ __launch_bounds__(BT) void k_csr_sortgather(int ndst, int *perm, const int *x_src, const double *x_area, const double *x_c1,
-                                                        const double *x_c2, const int *src_idx_f, const double *cen, int nsrc, FgCsr csr,
-                                                        int *tmp, long ntmp)
+__global__ __launch_bounds__(BT) void k_csr_sortgather(int ndst, FgRowEnt *perm, const double *x_area, const double *x_c1, const double *x_c2,
+                                                        const int *src_idx_f, const FgSrcRec *cen, FgCsr csr, int *tmp, long ntmp)
 {
   constexpr int SHORT = 12, CAP = (RPW >= 64) ? 512 : 2048;                // 4 KB of LDS per wave in the short-row case
-  // (BT: 64 lanes for 64 short rows; 256 for 16 long rows -- their ~1000 records leave through three dependent gathers each, and
-  // with one wave that was 18 rounds of them per block: C384 -> 2 deg finalize 0.186 ms)
-  __shared__ int sh[CAP], sh2[CAP];
+  // (BT: 64 lanes for 64 short rows; 256 for 16 long rows -- their ~1000 records leave through gathers, and with one wave that
+  // was 18 rounds of them per block: C384 -> 2 deg finalize 0.186 ms)
+  __shared__ int sh[CAP], shs[CAP];                        // exchange cells (the sort key) and their source cells
   __shared__ int long_b[RPW], long_n[RPW];
   __shared__ int nlong;
   if (threadIdx.x == 0) nlong = 0;
@@ -148,78 +181,80 @@ __global__ __launch_bounds__(BT) void k_csr_sortgather(int ndst, int *perm, cons
   int b = 0, e = 0;
   if ((int)threadIdx.x < RPW && d < ndst) { b = csr.row_ptr[d]; e = csr.row_ptr[d + 1]; }
   if (staged) {
-    for (int i = threadIdx.x; i < nq; i += BT) sh[i] = perm[q0 + i];
+    for (int i = threadIdx.x; i < nq; i += BT) { const FgRowEnt p = perm[q0 + i]; sh[i] = p.n; shs[i] = p.s; }
     __syncthreads();
     if (e - b > SHORT) { const int q = atomicAdd(&nlong, 1); long_b[q] = b - q0; long_n[q] = e - b; }
     else
       for (int i = b - q0 + 1; i < e - q0; i++) {
-        int v = sh[i], j = i - 1;
-        while (j >= b - q0 && sh[j] > v) { sh[j + 1] = sh[j]; j--; }
-        sh[j + 1] = v;
+        const int v = sh[i], w = shs[i];
+        int j = i - 1;
+        while (j >= b - q0 && sh[j] > v) { sh[j + 1] = sh[j]; shs[j + 1] = shs[j]; j--; }
+        sh[j + 1] = v; shs[j + 1] = w;
       }
     __syncthreads();
     const int nl = nlong;
     for (int q = 0; q < nl; q++) {
       const int rb = long_b[q], n = long_n[q];
       // every lane ranks up to CAP / BT = 8 elements of the row in ONE walk over its keys (a walk per element waits for LDS
-      // once per comparison: 0.82 ms for the 1 850-entry rows of C384 -> 10 deg)
+      // once per comparison: 0.82 ms for the 1 850-entry rows of C384 -> 10 deg).  The elements stay in registers over the
+      // barrier that ends every lane's walk; then they go to their ranks in the row itself.
       constexpr int OWN = CAP / BT;
       if (n <= BT) {                                       // (block-uniform) one element per lane at most
-        if ((int)threadIdx.x < n) {
-          const int v = sh[rb + threadIdx.x];
-          int rank = 0;
+        const bool own = (int)threadIdx.x < n;
+        int v = 0, w = 0, rank = 0;
+        if (own) {
+          v = sh[rb + threadIdx.x]; w = shs[rb + threadIdx.x];
           for (int j = 0; j < n; j++) rank += (sh[rb + j] < v) ? 1 : 0;
-          sh2[rb + rank] = v;
         }
+        __syncthreads();
+        if (own) { sh[rb + rank] = v; shs[rb + rank] = w; }
       } else {
-        int v[OWN], rank[OWN];
+        int v[OWN], w[OWN], rank[OWN];
 #pragma unroll
-        for (int k = 0; k < OWN; k++) { const int i = threadIdx.x + BT * k; v[k] = (i < n) ? sh[rb + i] : 0x7fffffff; rank[k] = 0; }
+        for (int k = 0; k < OWN; k++) {
+          const int i = threadIdx.x + BT * k;
+          v[k] = (i < n) ? sh[rb + i] : 0x7fffffff; w[k] = (i < n) ? shs[rb + i] : 0; rank[k] = 0;
+        }
         d_rank_count<OWN>(sh + rb, n, v, rank);
+        __syncthreads();
 #pragma unroll
-        for (int k = 0; k < OWN; k++) if ((int)threadIdx.x + BT * k < n) sh2[rb + rank[k]] = v[k];
+        for (int k = 0; k < OWN; k++) if ((int)threadIdx.x + BT * k < n) { sh[rb + rank[k]] = v[k]; shs[rb + rank[k]] = w[k]; }
       }
-      __syncthreads();
-      for (int i = threadIdx.x; i < n; i += BT) sh[rb + i] = sh2[rb + i];
       __syncthreads();
     }
   } else {
     // beyond the staging capacity: per row in global memory (lane-serial insertion, or the wave through LDS for long rows)
     if (e - b > SHORT) { const int q = atomicAdd(&nlong, 1); long_b[q] = b; long_n[q] = e - b; }
-    else
-      for (int i = b + 1; i < e; i++) {
-        int v = perm[i], j = i - 1;
-        while (j >= b && perm[j] > v) { perm[j + 1] = perm[j]; j--; }
-        perm[j + 1] = v;
-      }
+    else d_row_insertion(perm, b, e);
     __syncthreads();
     const int nl = nlong;
     for (int q = 0; q < nl; q++) {
       const int rb = long_b[q], n = long_n[q];
       if (n <= CAP) {
-        for (int i = threadIdx.x; i < n; i += BT) sh[i] = perm[rb + i];
+        for (int i = threadIdx.x; i < n; i += BT) { const FgRowEnt p = perm[rb + i]; sh[i] = p.n; shs[i] = p.s; }
         __syncthreads();
         for (int i = threadIdx.x; i < n; i += BT) {
           const int v = sh[i];
           int rank = 0;
           for (int j = 0; j < n; j++) rank += (sh[j] < v) ? 1 : 0;
-          perm[rb + rank] = v;
+          perm[rb + rank] = FgRowEnt{v, shs[i]};
         }
         __syncthreads();
       } else if (tmp) {
         // a row longer than the staging buffer (C384 -> 10 deg: 1 850 exchange cells): its keys pass through LDS a buffer-full at
-        // a time, every element counts the smaller keys of each tile into its rank (kept in tmp), then the row is written out in
-        // rank order (second half of tmp) and copied back.  (Until round 3 one lane sorted such a row by insertion, in global
-        // memory: 1.9 SECONDS for that remap's finalize.)
-        int *rk = tmp + rb, *srt = tmp + ntmp + rb;
+        // a time, every element counts the smaller keys of each tile into its rank (kept in the last third of tmp), then the
+        // row's pairs are written out in rank order (first two thirds of tmp) and copied back.  (Until round 3 one lane sorted
+        // such a row by insertion, in global memory: 1.9 SECONDS for that remap's finalize.)
+        FgRowEnt *srt = (FgRowEnt *)tmp + rb;
+        int *rk = tmp + 2 * ntmp + rb;
         for (int t0 = 0; t0 < n; t0 += CAP) {
           const int m = min(CAP, n - t0);
-          for (int j = threadIdx.x; j < m; j += BT) sh[j] = perm[rb + t0 + j];
+          for (int j = threadIdx.x; j < m; j += BT) sh[j] = perm[rb + t0 + j].n;
           __syncthreads();
           for (int i0 = threadIdx.x; i0 < n; i0 += 8 * BT) {           // eight elements per lane and walk over the tile
             int v[8], r[8];
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const int i = i0 + BT * k; v[k] = (i < n) ? perm[rb + i] : 0x7fffffff; r[k] = (i < n && t0) ? rk[i] : 0; }
+            for (int k = 0; k < 8; k++) { const int i = i0 + BT * k; v[k] = (i < n) ? perm[rb + i].n : 0x7fffffff; r[k] = (i < n && t0) ? rk[i] : 0; }
             d_rank_count<8>(sh, m, v, r);
 #pragma unroll
             for (int k = 0; k < 8; k++) { const int i = i0 + BT * k; if (i < n) rk[i] = r[k]; }
@@ -230,18 +265,12 @@ __global__ __launch_bounds__(BT) void k_csr_sortgather(int ndst, int *perm, cons
         __syncthreads();
         for (int i = threadIdx.x; i < n; i += BT) perm[rb + i] = srt[i];
         __syncthreads();
-      } else if (threadIdx.x == 0) {                       // serial, as a last resort (no scratch: the plan's mean row is short)
-        for (int i = rb + 1; i < rb + n; i++) {
-          int v = perm[i], j = i - 1;
-          while (j >= rb && perm[j] > v) { perm[j + 1] = perm[j]; j--; }
-          perm[j + 1] = v;
-        }
-      }
+      } else if (threadIdx.x == 0) d_row_insertion(perm, rb, rb + n);   // serial, as a last resort (no scratch: the plan's mean row is short)
     }
     __syncthreads();
   }
-  if (staged) d_csr_records<ORDER, DIST, BT, G, true>(sh, perm, q0, nq, x_src, x_area, x_c1, x_c2, src_idx_f, cen, nsrc, csr);
-  else        d_csr_records<ORDER, DIST, BT, G, false>(sh, perm, q0, nq, x_src, x_area, x_c1, x_c2, src_idx_f, cen, nsrc, csr);
+  if (staged) d_csr_records<ORDER, DIST, BT, G, true>(sh, shs, perm, q0, nq, x_area, x_c1, x_c2, src_idx_f, cen, csr);
+  else        d_csr_records<ORDER, DIST, BT, G, false>(sh, shs, perm, q0, nq, x_area, x_c1, x_c2, src_idx_f, cen, csr);
 }
 
 // index of source cell s inside one level of the field array: order 1 fields have no halo
@@ -1119,25 +1148,25 @@ void fgd_csr_count(long nx, const int *x_dst, int *row_cnt, hipStream_t st)
 {
   if (nx > 0) k_csr_count<<<nblk(nx, 256), 256, 0, st>>>(nx, x_dst, row_cnt);
 }
-void fgd_csr_fill(long nx, const int *x_dst, const int *row_ptr, int *row_fill, int *perm, hipStream_t st)
+void fgd_csr_fill(long nx, const int *x_src, const int *x_dst, const int *row_ptr, int *row_fill, FgRowEnt *perm, hipStream_t st)
 {
-  if (nx > 0) k_csr_fill<<<nblk(nx, 256), 256, 0, st>>>(nx, x_dst, row_ptr, row_fill, perm);
+  if (nx > 0) k_csr_fill<<<nblk(nx, 256), 256, 0, st>>>(nx, x_src, x_dst, row_ptr, row_fill, perm);
 }
-void fgd_csr_fill_pos(long nx_cap, const unsigned long long *nx_dev, const int *x_dst, const int *row_ptr, const int *x_rowpos, int *perm,
+void fgd_csr_fill_pos(long nx_cap, const unsigned long long *nx_dev, const int *x_src, const int *x_dst, const int *row_ptr, const int *x_rowpos, FgRowEnt *perm,
                       hipStream_t st)
 {
-  if (nx_cap > 0) k_csr_fill_pos<<<nblk(nx_cap, 256), 256, 0, st>>>(nx_cap, nx_dev, x_dst, row_ptr, x_rowpos, perm);
+  if (nx_cap > 0) k_csr_fill_pos<<<nblk(nx_cap, 256), 256, 0, st>>>(nx_cap, nx_dev, x_src, x_dst, row_ptr, x_rowpos, perm);
 }
-void fgd_csr_sortgather(int order, int ndst, long nx, const int *perm, const int *x_src, const double *x_area, const double *x_c1,
-                        const double *x_c2, const int *src_idx_f, const double *cen, int nsrc, FgCsr csr, hipStream_t st, int *tmp, long ntmp,
+void fgd_csr_sortgather(int order, int ndst, long nx, const FgRowEnt *perm, const double *x_area, const double *x_c1, const double *x_c2,
+                        const int *src_idx_f, const FgSrcRec *cen, FgCsr csr, hipStream_t st, int *tmp, long ntmp,
                         int long_rows)
 {
   if (ndst <= 0) return;
-  int *pm = const_cast<int *>(perm);                       // sorted in place only for runs beyond the LDS staging capacity
+  FgRowEnt *pm = const_cast<FgRowEnt *>(perm);                     // sorted in place only for runs beyond the LDS staging capacity
   // rows per block: 64 short rows for one wave; 16 long ones, or a single very long one (fine -> very coarse), for four waves
   // (long_rows: the caller knows of a region of long rows under a short mean -- the cells round the pole of a curvilinear target)
   const int mode = nx > 256 * (long)ndst ? 2 : ((nx > 8 * (long)ndst || long_rows) ? 1 : 0);
-#define SG(O_, R_, D_) k_csr_sortgather<O_, R_, D_, (R_ >= 64 ? 64 : 256), SG_GROUP><<<nblk(ndst, R_), (R_ >= 64 ? 64 : 256), 0, st>>>(ndst, pm, x_src, x_area, x_c1, x_c2, src_idx_f, cen, nsrc, csr, tmp, ntmp)
+#define SG(O_, R_, D_) k_csr_sortgather<O_, R_, D_, (R_ >= 64 ? 64 : 256), SG_GROUP><<<nblk(ndst, R_), (R_ >= 64 ? 64 : 256), 0, st>>>(ndst, pm, x_area, x_c1, x_c2, src_idx_f, cen, csr, tmp, ntmp)
 #define SGM(O_, D_) do { if (mode == 2) SG(O_, 1, D_); else if (mode == 1) SG(O_, 16, D_); else SG(O_, 64, D_); } while (0)
   if (order == 2) { if (cen) SGM(2, true); else SGM(2, false); }
   else SGM(1, false);

@@ -407,10 +407,11 @@ struct fg_plan {
   int *x_src = nullptr, *x_dst = nullptr;
   double *x_area = nullptr, *x_c1 = nullptr, *x_c2 = nullptr;
   int *xoff = nullptr;
-  int *perm = nullptr;           // exchange cells grouped by destination row (unsorted inside a row) until fg_plan_finalize
+  FgRowEnt *perm = nullptr;      // {exchange cell, its source cell} grouped by destination row (unsorted inside a row) until fg_plan_finalize
   bool rows_built = false;       // csr.row_ptr and perm come from the search
   bool dist_pending = false;     // order 2: x_c1/x_c2 still hold the centroid integrals after finalize (fg_plan_get_xgrid applies di/dj)
-  double *sums = nullptr, *cen = nullptr;
+  double *sums = nullptr;
+  FgSrcRec *cen = nullptr;       // order 2, from the finalize on: the centroid of every source cell
   // sweep
   FgCsr csr{};
   int *src_idx_f = nullptr;
@@ -741,7 +742,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   pl->x_area = blk.keep<double>(nx_alloc + 1);
   if (order == 2) { pl->x_c1 = blk.keep<double>(nx_alloc + 1); pl->x_c2 = blk.keep<double>(nx_alloc + 1); pl->sums = blk.keep<double>(3 * (size_t)nsrc); }
   int *x_rowpos = blk.get<int>(nx_alloc + 1);          // slot of every exchange cell in its destination row, where the compaction takes it (!early_rows)
-  pl->perm = blk.keep<int>(nx_alloc + 1);
+  pl->perm = blk.keep<FgRowEnt>(nx_alloc + 1);
   pl->csr.row_ptr = blk.keep<int>(ndst + 1);
   if (!pl->src_idx_f) pl->src_idx_f = blk.keep<int>(nsrc + 1);
   if (!blk.ok) return fail(FG_ERR_HIP, "out of device memory");
@@ -858,7 +859,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   if (!early_rows) {
     pt.begin(PH_ROWS);
     fgd_exclusive_scan1(row_cnt, ndst, pl->csr.row_ptr, lb_rows, &tickets[1], &dc->rows_total, dc->err, st);
-    fgd_csr_fill_pos(nx_alloc, &dc->xtot, pl->x_dst, pl->csr.row_ptr, x_rowpos, pl->perm, st);
+    fgd_csr_fill_pos(nx_alloc, &dc->xtot, pl->x_src, pl->x_dst, pl->csr.row_ptr, x_rowpos, pl->perm, st);
     pt.end();
   }
   ptot.end();
@@ -872,16 +873,16 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   if (fuse) {
     pt.begin(PH_FINALIZE);
     if (order == 2) {
-      pl->cen = pl->alloc<double>(2 * (size_t)nsrc);
+      pl->cen = pl->alloc<FgSrcRec>((size_t)nsrc + 1);
       if (!pl->cen) return fail(FG_ERR_HIP, "out of device memory");
       fgd_centroids(nsrc, pl->S, pl->sums, pl->cen, st);
       pl->csr.e2 = pl->alloc<FgCsrEntry2>(nx_alloc + 1);
     } else pl->csr.e1 = pl->alloc<FgCsrEntry1>(nx_alloc + 1);
     if (!pl->csr.e1 && !pl->csr.e2) return fail(FG_ERR_HIP, "out of device memory");
     // (the row-length heuristic of the record kernel wants the exchange-cell count: nsrc + ndst is within a factor of it)
-    int *sg_tmp = pl->alloc<int>(2 * (size_t)(nx_alloc + 1));   // (scratch for rows beyond the LDS staging; null = the serial last resort)
-    fgd_csr_sortgather(order, ndst, (long)nsrc + ndst, pl->perm, pl->x_src, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f,
-                       order == 2 ? pl->cen : nullptr, nsrc, pl->csr, st, sg_tmp, nx_alloc + 1);
+    int *sg_tmp = pl->alloc<int>(3 * (size_t)(nx_alloc + 1));   // (scratch for rows beyond the LDS staging; null = the serial last resort)
+    fgd_csr_sortgather(order, ndst, (long)nsrc + ndst, pl->perm, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f,
+                       order == 2 ? pl->cen : nullptr, pl->csr, st, sg_tmp, nx_alloc + 1);
     fused_tmp = sg_tmp;
     pt.end();
   }
@@ -1521,7 +1522,7 @@ extern "C" int fg_plan_stats(const fg_plan *pl, long *stats, int n)
 // Destination-row CSR.  A searched plan arrives with row_ptr and perm (rows grouped, unsorted inside a row) already built on
 // the device by the search; a plan loaded from a remap file (fg_plan_set_xgrid) counts and fills its rows here.
 // cen != null: order 2, x_c1/x_c2 hold the centroid integrals and di/dj are formed while the records are packed.
-static int build_csr(fg_plan *pl, const double *cen)
+static int build_csr(fg_plan *pl, const FgSrcRec *cen)
 {
   hipStream_t st = pl->stream;
   const int ndst = pl->ndst;
@@ -1537,7 +1538,7 @@ static int build_csr(fg_plan *pl, const double *cen)
     const long t_rows = fgd_scan_tiles(ndst);
     const size_t zb = 256 + (size_t)t_rows * sizeof(unsigned long long) + 2 * ((size_t)ndst + 1) * sizeof(int);
     char *z = pl->alloc<char>(zb);                                    // [ticket, total, err | look-back words | counts | fill cursors]
-    pl->perm = pl->alloc<int>(nx + 1);
+    pl->perm = pl->alloc<FgRowEnt>(nx + 1);
     pl->csr.row_ptr = pl->alloc<int>(ndst + 1);
     if (!z || !pl->perm || !pl->csr.row_ptr) return fail(FG_ERR_HIP, "out of device memory");
     HIPCHK(hipMemsetAsync(z, 0, zb, st));
@@ -1545,7 +1546,7 @@ static int build_csr(fg_plan *pl, const double *cen)
     int *row_cnt = (int *)(z + 256 + (size_t)t_rows * sizeof(unsigned long long));
     fgd_csr_count(nx, pl->x_dst, row_cnt, st);
     fgd_exclusive_scan1(row_cnt, ndst, pl->csr.row_ptr, lb, (unsigned *)z, (unsigned long long *)(z + 8), (unsigned *)(z + 16), st);
-    fgd_csr_fill(nx, pl->x_dst, pl->csr.row_ptr, row_cnt + ndst + 1, pl->perm, st);
+    fgd_csr_fill(nx, pl->x_src, pl->x_dst, pl->csr.row_ptr, row_cnt + ndst + 1, pl->perm, st);
     scratch = z;
   }
   if (pl->order == 2) pl->csr.e2 = pl->alloc<FgCsrEntry2>(nx + 1);
@@ -1554,13 +1555,13 @@ static int build_csr(fg_plan *pl, const double *cen)
   // rows longer than the kernel's LDS staging are sorted through this -- also in plans whose MEAN row is short: the cells around a
   // pole of a cubed-sphere target hold a whole row of a lat-lon source each (1 440 exchange cells: a lane sorting that by insertion
   // took 17 ms)
-  int *sg_tmp = pl->alloc<int>(2 * (size_t)(nx + 1));
+  int *sg_tmp = pl->alloc<int>(3 * (size_t)(nx + 1));
   // a curvilinear target with cells that went to the general clip (pole vertices): its rows round the pole are long -- hundreds of
   // exchange cells -- under a mean of 6.6, and the 64-rows-per-wave mode ranks them one after another (0.25 deg -> C384 tile 3:
   // 0.23 ms of the tile's 1.1); the 16-rows-per-block mode costs the short rows of such a tile little
   const int long_rows = !pl->rect && !pl->great_circle && pl->stats[FG_STAT_DEFERRED] > 0 && nx > 4 * (long)ndst;
-  fgd_csr_sortgather(pl->order, ndst, nx, pl->perm, pl->x_src, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f, cen, pl->nsrc, pl->csr, st,
-                     sg_tmp, nx + 1, long_rows);
+  fgd_csr_sortgather(pl->order, ndst, nx, pl->perm, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f, cen, pl->csr, st, sg_tmp, nx + 1,
+                     long_rows);
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   pl->release(scratch); pl->release(pl->perm); pl->perm = nullptr; pl->release(sg_tmp);
@@ -1581,7 +1582,7 @@ extern "C" int fg_plan_finalize(fg_plan *pl, const double *total_cell_sums_dev)
   PhaseTimer pt; pt.start(g_profiling != 0, pl->stream);
   pt.begin(PH_FINALIZE);
   if (pl->order == 2) {
-    pl->cen = pl->alloc<double>(2 * (size_t)pl->nsrc);
+    pl->cen = pl->alloc<FgSrcRec>((size_t)pl->nsrc + 1);
     if (!pl->cen) return fail(FG_ERR_HIP, "out of device memory");
     const double *tot = total_cell_sums_dev ? total_cell_sums_dev : pl->sums;
     fgd_centroids(pl->nsrc, pl->S, tot, pl->cen, pl->stream);
@@ -1625,7 +1626,7 @@ extern "C" int fg_plan_get_xgrid(const fg_plan *pl, int *t_in, int *i_in, int *j
   if (nx == 0) return 0;
   if (pl->dist_pending) {                     // di = clon/area - centroid (conserve_interp.c:256-257,355-356), on first use
     fg_plan *m = const_cast<fg_plan *>(pl);
-    fgd_distances(nx, pl->nsrc, pl->x_src, pl->x_area, pl->cen, m->x_c1, m->x_c2, pl->stream);
+    fgd_distances(nx, pl->x_src, pl->x_area, pl->cen, m->x_c1, m->x_c2, pl->stream);
     HIPCHK(hipStreamSynchronize(pl->stream));
     m->dist_pending = false;
   }

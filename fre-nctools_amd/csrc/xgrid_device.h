@@ -186,6 +186,13 @@ void fgd_clip_quad(int order, FgPairSpace ps, FgCells S, const double *mask, FgC
               double *tmp_area, double *tmp_clon, double *tmp_clat, int *nacc, int *defer_list, int *defer_cnt,
               unsigned long long *stats, unsigned *err, hipStream_t st, const FgRect *rect = nullptr, int *row_cnt = nullptr,
               int *tmp_rowpos = nullptr);
+// An entry of a destination row's list (perm) before the CSR records exist: the exchange cell n and its source cell s, stored by
+// whoever places the exchange cell (s is in a register there), so that the record kernel does not fetch x_src[n] to learn it
+struct alignas(8) FgRowEnt { int n, s; };
+// The centroid of a source cell (order 2, conserve_interp.c:327-348), both coordinates in one 16-byte record: one gather per
+// exchange cell where two arrays took two.  (A 32-byte record that also held the cell's field index was measured: the record
+// kernel took the same time, the centroid pass 6 us longer for writing twice as much: profiles/csr_row_pairs_summary.md.)
+struct alignas(16) FgSrcRec { double cen_lon, cen_lat; };
 // accepted pairs -> exchange cells in canonical order (xoff = scan of the clip kernels' nacc), per-source-cell sums,
 // destination-row sizes and slots
 struct FgCompactIo {
@@ -196,7 +203,7 @@ struct FgCompactIo {
   double *x_area, *x_c1, *x_c2;
   int *row_cnt, *x_rowpos;
   const int *tmp_rowpos;             // != null: row slots per PAIR from the clip kernels; row_ptr is final and perm is stored here
-  const int *row_ptr; int *perm;
+  const int *row_ptr; FgRowEnt *perm;
   double *sums;                      // [3][nsrc] (order 2, zeroed: cells without exchange cells are not visited) or null
   const int *big_list;               // the cells with more than CP_SMALL pairs (from the candidate kernel)
   const int *big_cnt;
@@ -204,9 +211,9 @@ struct FgCompactIo {
   long xcap;                         // entries the x_* arrays hold
 };
 void fgd_compact(int order, int nsrc, FgPairSpace ps, const FgCompactIo &io, hipStream_t st);
-void fgd_centroids(int nsrc, FgCells S, const double *sums, double *cen, hipStream_t st);
-void fgd_distances(long nx, int nsrc, const int *x_src, const double *x_area, const double *cen, double *x_c1,
-                   double *x_c2, hipStream_t st);
+// cen[s] for every source cell: its centroid from the sums (zero where the cell has no exchange cell or was culled)
+void fgd_centroids(int nsrc, FgCells S, const double *sums, FgSrcRec *cen, hipStream_t st);
+void fgd_distances(long nx, const int *x_src, const double *x_area, const FgSrcRec *cen, double *x_c1, double *x_c2, hipStream_t st);
 
 // ---- sweep (apply_kernels.hip) ----
 // CSR by destination cell: row_ptr[ndst+1]; per entry: index of the source value in the
@@ -220,15 +227,16 @@ struct FgCsr {
   FgCsrEntry2 *e2;
 };
 void fgd_csr_count(long nx, const int *x_dst, int *row_cnt, hipStream_t st);
-void fgd_csr_fill(long nx, const int *x_dst, const int *row_ptr, int *row_fill, int *perm, hipStream_t st);
+void fgd_csr_fill(long nx, const int *x_src, const int *x_dst, const int *row_ptr, int *row_fill, FgRowEnt *perm, hipStream_t st);
 // nx_cap threads; the true count is read from *nx_dev (null: nx_cap is the count)
-void fgd_csr_fill_pos(long nx_cap, const unsigned long long *nx_dev, const int *x_dst, const int *row_ptr, const int *x_rowpos, int *perm,
-                      hipStream_t st);
-// rows of perm into ascending exchange-cell order, then the packed CSR records; cen != null (order 2): x_c1/x_c2 still hold the
-// centroid integrals and di/dj are formed here (conserve_interp.c:256-257,355-356), else they are taken as they are
-void fgd_csr_sortgather(int order, int ndst, long nx, const int *perm, const int *x_src, const double *x_area, const double *x_c1,
-                        const double *x_c2, const int *src_idx_f, const double *cen, int nsrc, FgCsr csr, hipStream_t st, int *tmp = nullptr, long ntmp = 0,
-                        int long_rows = 0);   // tmp: 2 * ntmp ints of scratch for rows beyond the LDS staging (ntmp > exchange cells), or null
+void fgd_csr_fill_pos(long nx_cap, const unsigned long long *nx_dev, const int *x_src, const int *x_dst, const int *row_ptr, const int *x_rowpos,
+                      FgRowEnt *perm, hipStream_t st);
+// rows of perm into ascending exchange-cell order (the source cell moves with it), then the packed CSR records; cen != null
+// (order 2): x_c1/x_c2 still hold the centroid integrals and di/dj are formed here (conserve_interp.c:256-257,355-356), else
+// they are taken as they are
+void fgd_csr_sortgather(int order, int ndst, long nx, const FgRowEnt *perm, const double *x_area, const double *x_c1, const double *x_c2,
+                        const int *src_idx_f, const FgSrcRec *cen, FgCsr csr, hipStream_t st, int *tmp = nullptr, long ntmp = 0,
+                        int long_rows = 0);   // tmp: 3 * ntmp ints of scratch for rows beyond the LDS staging (ntmp > exchange cells), or null
 void fgd_src_field_index(int order, const FgTile *tiles_dev, int ntiles, int nsrc, int *src_idx_f, hipStream_t st);
 void fgd_apply1(int order, int ndst, FgCsr csr, const double *f, const double *gx, const double *gy, const int *gmask,
                 int has_missing, double missing, double *out, double *row_sum, hipStream_t st, long nx = -1);

@@ -1864,7 +1864,7 @@ __device__ __forceinline__ long d_cp_place(const FgCompactIo &io, const CpPair &
   const long pos = c.x0 + rank;
   io.x_src[pos] = c.s; io.x_dst[pos] = c.d; io.x_area[pos] = c.a;
   if (ORDER == 2) { io.x_c1[pos] = c.l; io.x_c2[pos] = c.t; sh_v[0][lb + rank] = c.a; sh_v[1][lb + rank] = c.l; sh_v[2][lb + rank] = c.t; }
-  if (io.tmp_rowpos) io.perm[c.row] = (int)pos;           // the row slot was taken by the clip kernel: row_ptr[d] + tmp_rowpos[p]
+  if (io.tmp_rowpos) io.perm[c.row] = FgRowEnt{(int)pos, c.s};   // the row slot was taken by the clip kernel: row_ptr[d] + tmp_rowpos[p]
   else return pos;
   return -1;
 }
@@ -1961,7 +1961,7 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
           io.x_c1[pos] = l; io.x_c2[pos] = t;
           sval[0][rank - c0] = a; sval[1][rank - c0] = l; sval[2][rank - c0] = t;
         }
-        if (io.tmp_rowpos) io.perm[row] = (int)pos;
+        if (io.tmp_rowpos) io.perm[row] = FgRowEnt{(int)pos, s};
         else io.x_rowpos[pos] = atomicAdd(&io.row_cnt[d], 1);
       }
       __syncthreads();
@@ -2025,46 +2025,54 @@ __global__ __launch_bounds__(256) void k_compact(int nsrc, FgPairSpace ps, FgCom
 // ---------------------------------------------------------------------------------------
 // order-2 centroid pass
 // ---------------------------------------------------------------------------------------
-// cen[0][s], cen[1][s] = centroid lon/lat of source cell s (conserve_interp.c:327-348)
-__global__ __launch_bounds__(256) void k_centroids(int nsrc, FgCells S, const double *sums, double *cen)
+// cen[s] = centroid lon/lat of source cell s (conserve_interp.c:327-348), one 16-byte record: the record kernel of the finalize
+// (k_csr_sortgather) and k_distances fetch both coordinates with one gather
+__global__ __launch_bounds__(256) void k_centroids(int nsrc, FgCells S, const double *sums, FgSrcRec *cen)
 {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   double a = 0, ca = 1, cl = 0, ct = 0;
+  int nv = 0;
   bool whole = false;                                      // the cell's own integrals are needed (covered area off by >= 1e-3)
   // (a source cell a culling search left out -- nv = 0 -- has no exchange cell on this rank: its centroid is never read, though
   // the totals handed over by the other ranks are there)
-  if (s < nsrc && (a = sums[s]) > 0 && S.nv[s] > 0) {
-    ca = S.area[s];
-    if (fabs(a - ca) / ca < 1.e-3) {
-      cl = sums[nsrc + s] / a;
-      ct = sums[2 * (size_t)nsrc + s] / a;
-    } else whole = true;
+  // A cell without exchange cells (most cells of a rank's band) costs one load; for the others the vertex count, the cell's
+  // area and the two integrals go out together (they were two more dependent round trips)
+  if (s < nsrc && (a = sums[s]) > 0) {
+    const double sl = sums[nsrc + s], st = sums[2 * (size_t)nsrc + s], sa = S.area[s];
+    nv = S.nv[s];
+    if (nv > 0) {
+      ca = sa;
+      if (fabs(a - ca) / ca < 1.e-3) {
+        cl = sl / a;
+        ct = st / a;
+      } else whole = true;
+    }
   }
   // the sine table (3.5 KB into LDS, a barrier) only for blocks that hold such a cell: none in a global remap of similar grids
   if (__syncthreads_or(whole)) {
     d_load_trig_table();
     if (whole) {
       double x[G_MAXV], y[G_MAXV];
-      int n = S.nv[s];
+      int n = nv;
       const double *vp = S.verts + (size_t)s * 16;
       for (int k = 0; k < G_MAXV; k++) { x[k] = vp[k]; y[k] = vp[8 + k]; }
       cl = d_poly_ctrlon<1>(x, y, n, S.lon_avg[s]) / ca;
       ct = d_poly_ctrlat<1>(x, y, n) / ca;
     }
   }
-  if (s < nsrc) { cen[s] = cl; cen[nsrc + s] = ct; }
+  if (s < nsrc) cen[s] = FgSrcRec{cl, ct};
 }
 
 // di = clon/area - cen_lon, dj = clat/area - cen_lat (conserve_interp.c:256-257,355-356)
-__global__ __launch_bounds__(256) void k_distances(long nx, int nsrc, const int *x_src, const double *x_area,
-                                                    const double *cen, double *x_c1, double *x_c2)
+__global__ __launch_bounds__(256) void k_distances(long nx, const int *x_src, const double *x_area, const FgSrcRec *cen, double *x_c1,
+                                                    double *x_c2)
 {
   long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= nx) return;
   int s = x_src[n];
   double a = x_area[n];
   double di = x_c1[n] / a, dj = x_c2[n] / a;
-  di -= cen[s]; dj -= cen[nsrc + s];
+  di -= cen[s].cen_lon; dj -= cen[s].cen_lat;
   x_c1[n] = di; x_c2[n] = dj;
 }
 
@@ -2189,15 +2197,14 @@ void fgd_compact(int order, int nsrc, FgPairSpace ps, const FgCompactIo &io, hip
   else            k_compact<1><<<BIG_BLOCKS + nblk(np, 256), 256, 0, st>>>(nsrc, ps, io);
 }
 
-void fgd_centroids(int nsrc, FgCells S, const double *sums, double *cen, hipStream_t st)
+void fgd_centroids(int nsrc, FgCells S, const double *sums, FgSrcRec *cen, hipStream_t st)
 {
   if (nsrc > 0) k_centroids<<<nblk(nsrc, 256), 256, 0, st>>>(nsrc, S, sums, cen);
 }
 
-void fgd_distances(long nx, int nsrc, const int *x_src, const double *x_area, const double *cen, double *x_c1,
-                   double *x_c2, hipStream_t st)
+void fgd_distances(long nx, const int *x_src, const double *x_area, const FgSrcRec *cen, double *x_c1, double *x_c2, hipStream_t st)
 {
-  if (nx > 0) k_distances<<<nblk(nx, 256), 256, 0, st>>>(nx, nsrc, x_src, x_area, cen, x_c1, x_c2);
+  if (nx > 0) k_distances<<<nblk(nx, 256), 256, 0, st>>>(nx, x_src, x_area, cen, x_c1, x_c2);
 }
 
 // total[3][nsrc] += this plan's exchange cells, cell by cell in exchange-cell order, CONTINUING from the value already there:
