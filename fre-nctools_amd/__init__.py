@@ -15,6 +15,8 @@ mirrors the reference's call signatures:
   -- tools/fregrid/fregrid_util.c:2662,756,789 (--extrapolate fill of a lat-lon source, --dst_vgrid levels)
 * ``RunoffRegrid`` / ``nearest_unmasked`` / ``runoff_input_grid`` / ``runoff_output_grid``
   -- tools/runoff_regrid/runoff_regrid.c:430,626,708,243,322 (setup_remap, process_data's arithmetic, nearest, the grids)
+* ``LandNearest``
+  -- tools/remap_land/remap_land.c:2520,2569 (full_search_nearest, search_nearest_sface)
 
 There is NO CPU fallback: if the shared library is missing, or no HIP device is visible
 when a compute entry point is called, an exception is raised.
@@ -38,6 +40,7 @@ from .extrapolate import (Extrapolator, do_extrapolate, setup_vertical_interp, d
                           set_extrap_batch, set_extrap_coef, extrap_coef_host)
 from .runoff import (RunoffRegrid, nearest_unmasked, runoff_input_grid, runoff_output_grid,  # noqa: F401
                      set_runoff_prune, runoff_tile)
+from .remap_land import LandNearest, set_rland_prune, rland_tile  # noqa: F401
 from .parallel import (band_rows, row_cost, allreduce_cell_sums, allreduce_scalar_sum, allreduce_minmax,  # noqa: F401
                        boundary_source_cells, allreduce_cell_sums_sparse, ordered_cell_sums, CellSumExchange)
 from .conserve_interp import (  # noqa: F401
@@ -55,6 +58,7 @@ __all__ = [
     "write_bilinear_remap_file", "read_bilinear_remap_file",
     "Extrapolator", "do_extrapolate", "setup_vertical_interp", "do_vertical_interp",
     "RunoffRegrid", "nearest_unmasked", "runoff_input_grid", "runoff_output_grid",
+    "LandNearest",
 ]
 
 

@@ -58,6 +58,8 @@ EXPORTS = [
     "fg_runoff_create", "fg_runoff_create_from_xgrid", "fg_runoff_destroy", "fg_runoff_nxgrid", "fg_runoff_get_xgrid",
     "fg_runoff_get_maps", "fg_runoff_get_xyz", "fg_runoff_search_stats", "fg_runoff_phase_ms", "fg_runoff_stream", "fg_runoff_apply", "fg_runoff_apply_dev",
     "fg_nearest_unmasked", "fg_set_runoff_prune", "fg_runoff_tile",
+    "fg_rland_create", "fg_rland_destroy", "fg_rland_stream", "fg_rland_search", "fg_rland_search_sface", "fg_rland_stats",
+    "fg_rland_phase_ms", "fg_set_rland_prune", "fg_rland_tile",
 ]
 
 
@@ -413,6 +415,24 @@ def lib():
     L.fg_set_runoff_prune.restype = None
     L.fg_runoff_tile.argtypes = []
     L.fg_runoff_tile.restype = C.c_int
+    L.fg_rland_create.argtypes = [C.c_int, C.c_int, dp, dp, C.POINTER(vp)]
+    L.fg_rland_create.restype = C.c_int
+    L.fg_rland_destroy.argtypes = [vp]
+    L.fg_rland_destroy.restype = None
+    L.fg_rland_stream.argtypes = [vp]
+    L.fg_rland_stream.restype = vp
+    L.fg_rland_search.argtypes = [vp, ip, C.c_int, C.c_int, vp, vp, ip, ip, ip]
+    L.fg_rland_search.restype = C.c_int
+    L.fg_rland_search_sface.argtypes = [vp, ip, C.c_int, vp, vp, ip, ip, ip, C.c_int, ip]
+    L.fg_rland_search_sface.restype = C.c_int
+    L.fg_rland_stats.argtypes = [vp, C.POINTER(C.c_long), C.c_int]
+    L.fg_rland_stats.restype = C.c_int
+    L.fg_rland_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    L.fg_rland_phase_ms.restype = C.c_int
+    L.fg_set_rland_prune.argtypes = [C.c_int]
+    L.fg_set_rland_prune.restype = None
+    L.fg_rland_tile.argtypes = []
+    L.fg_rland_tile.restype = C.c_int
     _LIB = L
     return L
 

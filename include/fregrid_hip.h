@@ -827,6 +827,40 @@ int  fg_nearest_unmasked(int nlon, int nlat, const double *mask, const double *l
 void fg_set_runoff_prune(int on);
 int  fg_runoff_tile(void);                                                  /* compacted ocean points per tile */
 
+/* ---- remap_land's nearest-point search on the device (tools/remap_land/remap_land.c:2520-2607) ----
+ * All angles in radians.  Masks are int, non-zero = present, as the tool's *_count_* arrays are.  The answer for a destination
+ * point is the reference's, bit for bit: the first source point in scan order (flat index l = face * npts_src + i) among those
+ * with the smallest great_circle_distance as gcc -O2 and the host libm evaluate it.  The device finds the source points whose
+ * chord to the query is within 2^-40 of the smallest; the host decides among them with the reference's expression; queries
+ * that argument does not cover (nearest point more than a quarter turn away, first point at the antipode, coordinates outside
+ * |lon| <= 8, |lat| <= the double pi/2 = 1.5707963267948966, where cos(lat) is still >= 0) take the reference's loop on the host.
+ * fg_rland_create converts and orders the nface_src * npts_src source points once (device FREGRID_HIP_DEVICE or 0).
+ * lon_dst / lat_dst may be host or device memory; every other array is the host's. */
+typedef struct fg_rland fg_rland;
+int  fg_rland_create(int nface_src, int npts_src, const double *lon_src, const double *lat_src, fg_rland **out);
+void fg_rland_destroy(fg_rland *h);
+void *fg_rland_stream(fg_rland *h);
+/* full_search_nearest (:2520).  face: -1 all faces, else that face's points only.  idx_map = face_map = -1 where mask_dst == 0.
+ * No unmasked source point while a destination point is unmasked: FG_ERR_ARG, "... no nearest point is found". */
+int  fg_rland_search(fg_rland *h, const int *mask_src, int face, int npts_dst, const void *lon_dst, const void *lat_dst,
+                     const int *mask_dst, int *idx_map, int *face_map);
+/* search_nearest_sface (:2569): idx_map_sf = idx_map where face_map == iface_dst, else the nearest unmasked point of face
+ * iface_dst, searched for those points only (the error above applies only if there is such a point); -1 where mask_dst == 0. */
+int  fg_rland_search_sface(fg_rland *h, const int *mask_src, int npts_dst, const void *lon_dst, const void *lat_dst,
+                           const int *mask_dst, const int *idx_map, const int *face_map, int iface_dst, int *idx_map_sf);
+/* of the last search call (the first n of 8), in this order: [0] queries, [1] tiles, [2] tiles visited in phase 1 (smallest
+ * chord) and [3] in phase 2 (survivors) over all queries, [4] survivors in all, [5] queries decided on the host among several
+ * survivors, [6] queries that took the reference's loop, [7] queries with more survivors than the 4 slots (second launch,
+ * exact size).  There are two visited counts, so [4]..[7] sit one place later than in a list with a single one. */
+int  fg_rland_stats(const fg_rland *h, long *stats, int n);
+/* wall time in ms (the first n of 8): create's conversion and ordering; of the last search call: the destination points'
+ * copy and conversion, compaction with balls, phase 1 and phase 2 (events), overflow pass, host finish.  The handle's device
+ * buffers only grow, so a search allocates nothing once the handle has seen its sizes. */
+int  fg_rland_phase_ms(const fg_rland *h, float *ms, int n);
+/* Test hook; results never depend on it.  1 (default): tiles are skipped by their bounding balls; 0: every tile is visited. */
+void fg_set_rland_prune(int on);
+int  fg_rland_tile(void);                                                   /* compacted source points per tile */
+
 #ifdef __cplusplus
 }
 #endif
