@@ -1389,6 +1389,10 @@ __device__ __forceinline__ void d_finish_pair(const double *px, const double *py
 // cutting quad lives in registers.  Returns -1 if the pair must go to the general kernel (more than 4 vertices on a side, or
 // more than 8 in an intermediate polygon); otherwise the vertex count of the clipped polygon left in column tid (0: empty).
 // RECT: the destination cell is four values of its column record and two of the latitude axis (FgRect) -- D holds areas only.
+// The pass runs at four waves per SIMD and is bound by instruction issue, with a third of its wave cycles spent waiting: what
+// was measured on its round trips to memory and LDS and on its exec-masked regions, kept or not, is in
+// profiles/clip_edges_summary.md (kept: the pair's loads asked for in one round; the cutting edges unrolled together with the
+// polygon's slots read in one round, neither of which pays alone).
 template <bool RECT, int T>
 __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int tid, const int s, const int d,
                                               const FgCells &S, const FgCells &D, const FgRect &R, unsigned *err)
@@ -1396,25 +1400,40 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
   // RECT: the cutting cell is always a quad, so source cells of up to 8 vertices (the pole-fixed ones) fit this kernel too --
   // the general kernel then only sees the rare pair whose intermediate polygon outgrows 8 vertices
   constexpr int NV1 = RECT ? CLIP_SLOTS : 4;
-  const int n1 = S.nv[s], n2 = RECT ? 4 : D.nv[d];
-  if (n1 > NV1 || n2 > 4) return -1;
-
+  // Everything the pair needs from memory is asked for here in one round, ahead of the vertex-count test: the counts, the source
+  // cell's sixteen coordinates whatever its count (a cell record always has them; those from n1 on are not used) and the cutting
+  // quad.  Asked for one after the other -- the count, then the quad, then the vertices beyond the fourth under k < n1 -- each
+  // was a round trip of its own that a wave sat out.
+  // (The empty asm statements keep the compiler from moving the loads back below the test.)
   const double *sv = S.verts + (size_t)s * 16;
-  const double lon_in_avg = S.lon_avg[s];
   double x1[NV1], y1[NV1], x2[4], y2[4];
   double lon_out_avg;
+  int n1 = S.nv[s], n2 = RECT ? 4 : D.nv[d];
+  double lon_in_avg = S.lon_avg[s];
+#pragma unroll
+  for (int k = 0; k < NV1; k++) { x1[k] = sv[k]; y1[k] = sv[8 + k]; }
   if (RECT) {
     const int j = d / R.nx, i = d - j * R.nx;
     const double *c = R.col + (size_t)i * RECT_COLW;
-    const double ya = R.lat_ax[j], yb = R.lat_ax[j + 1];
+    double ya = R.lat_ax[j], yb = R.lat_ax[j + 1];
     x2[0] = c[0]; x2[1] = c[1]; x2[2] = c[2]; x2[3] = c[3]; lon_out_avg = c[6];
+    asm volatile("" : "+v"(ya), "+v"(yb));
     y2[0] = ya; y2[1] = ya; y2[2] = yb; y2[3] = yb;
   } else {
     const double *dv = D.verts + (size_t)d * 16;
 #pragma unroll
     for (int k = 0; k < 4; k++) { x2[k] = dv[k]; y2[k] = dv[8 + k]; }
     lon_out_avg = D.lon_avg[d];
+#pragma unroll
+    for (int k = 0; k < 4; k++) asm volatile("" : "+v"(y2[k]));
+    asm volatile("" : "+v"(n2));
   }
+#pragma unroll
+  for (int k = 0; k < NV1; k++) asm volatile("" : "+v"(x1[k]), "+v"(y1[k]));
+#pragma unroll
+  for (int k = 0; k < 4; k++) asm volatile("" : "+v"(x2[k]));
+  asm volatile("" : "+v"(n1), "+v"(lon_in_avg), "+v"(lon_out_avg));
+  if (n1 > NV1 || n2 > 4) return -1;
   double shift = 0.0;
   {
     double dx = lon_out_avg - lon_in_avg;            // create_xgrid.c:1064-1074
@@ -1423,7 +1442,7 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
   bool wrap = false;
 #pragma unroll
   for (int k = 0; k < NV1; k++) {
-    if (k < 4 || k < n1) { x1[k] = sv[k]; y1[k] = sv[8 + k]; } else { x1[k] = 0.0; y1[k] = 0.0; }
+    if (!(k < 4 || k < n1)) { x1[k] = 0.0; y1[k] = 0.0; }
     if (k < n1 && (x1[k] > G_TPI || x1[k] < 0.0)) wrap = true;  // create_xgrid.c:1282
   }
 #pragma unroll
@@ -1438,7 +1457,8 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
   for (int k = 0; k < NV1; k++) if (k < 4 || k < n1) sh_poly[k][tid] = make_double2(x1[k], y1[k]);
   // the cutting quad stays in registers; its vertex e is picked with selects (n2 <= 4)
   // vertex e of the cutting quad, picked with bit masks (a ?: chain on e is turned into a scratch-memory
-  // table by the optimizer)
+  // table by the optimizer).  Where e is a constant -- every copy of the unrolled loop below, and n2 - 1 in the rectilinear
+  // kernel -- the masks fold and the pick costs nothing.
   const long long b0x = __double_as_longlong(x2[0]), b1x = __double_as_longlong(x2[1]);
   const long long b2x = __double_as_longlong(x2[2]), b3x = __double_as_longlong(x2[3]);
   const long long b0y = __double_as_longlong(y2[0]), b1y = __double_as_longlong(y2[1]);
@@ -1459,21 +1479,26 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
   int n_cur = n1;
   bool overflow = false, parallel = false;
   double2 e0 = cut(n2 - 1);
+  // The loop over the cutting edges is unrolled (a quad has at most four; the generic instantiation leaves at e == n2), so
+  // that e is a constant in every copy and cut(e) is a pick of registers, not sixteen selects.  All CLIP_SLOTS columns of the
+  // polygon are read in one round at the head of an edge -- slots from n_cur on hold stale vertices or nothing, and only their
+  // contribution to inmask is predicated -- instead of one read, wait and test per slot, each behind its own k < n_cur.
 #if FG_EXP == 2
   for (int e = 0; e < 0; e++) {
 #else
-  for (int e = 0; e < n2 && n_cur > 0; e++) {
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    if ((!RECT && e >= n2) || n_cur <= 0) break;
 #endif
     double2 e1 = cut(e);
     const double x2_0 = e0.x, y2_0 = e0.y, x2_1 = e1.x, y2_1 = e1.y;
     double2 c[CLIP_SLOTS];
     unsigned inmask = 0u;
 #pragma unroll
+    for (int k = 0; k < CLIP_SLOTS; k++) c[k] = sh_poly[k][tid];
+#pragma unroll
     for (int k = 0; k < CLIP_SLOTS; k++)
-      if (k < n_cur) {
-        c[k] = sh_poly[k][tid];
-        inmask |= (unsigned)d_inside_edge(x2_0, y2_0, x2_1, y2_1, c[k].x, c[k].y) << k;
-      }
+      if (k < n_cur) inmask |= (unsigned)d_inside_edge(x2_0, y2_0, x2_1, y2_1, c[k].x, c[k].y) << k;
     const unsigned full = (1u << n_cur) - 1u;
     const unsigned prevmask = ((inmask << 1) | (inmask >> (n_cur - 1))) & full;     // bit k: vertex k-1 (cyclic) is inside
     const unsigned tmask = inmask ^ prevmask;                                        // bit k: edge (k-1, k) crosses the line
@@ -1545,19 +1570,32 @@ __global__ __launch_bounds__(CLIP_THREADS) __attribute__((amdgpu_waves_per_eu(CL
   __shared__ unsigned char sh_n[T];
   __shared__ int sh_wtot[T / 64];
 #endif
-  if (RECT && *R.bad) return;
-  {                                                   // the launch covers the regions' CAPACITY: blocks beyond a region's fill leave at once
-    const unsigned first = blockIdx.x * T, r = first / (unsigned)ps.regcap;
-    if (first - r * (unsigned)ps.regcap >= ps.fill[r * FG_FILL_STRIDE]) return;
-  }
-  d_load_trig_table();
   const int tid = threadIdx.x, lane = tid & 63;
   const int p0 = blockIdx.x * T;
+  // The head of a block in three steps, not a chain of ten loads each waited for on its own (profiles/clip_edges_summary.md
+  // counts them in the ISA).  Step 1, two scalar loads and one test: the rectilinear check's verdict and the region's fill
+  // -- the launch covers the regions' CAPACITY, and under culling and bands most of its blocks lie beyond their region's
+  // fill and leave here, at the cost they always had.  Round 2, for a block that stays:
+  // its lanes' pairs and its share of the trig table, asked for together (the empty asm keeps the compiler from moving the
+  // pair's loads below the barrier).  Round 3 is the pair's cells, in d_clip_quad_sh.  Read where they are used -- verdict,
+  // test, fill, test, table, table, barrier, fill again, src, count, ... -- each was a round trip that the wave sat out.
+  // The fill is kept for the lane test below, and src / dst for the second half of the kernel.
+  const unsigned first = blockIdx.x * T, reg = first / (unsigned)ps.regcap;
+  const unsigned fill = ps.fill[reg * FG_FILL_STRIDE];
+  const unsigned bad = RECT ? *R.bad : 0u;
+  if ((RECT && bad != 0u) | (first - reg * (unsigned)ps.regcap >= fill)) return;
+  static_assert(2 * T >= 112 * 4, "at most two table values per lane");
+  const int t0 = min(tid, 112 * 4 - 1), t1 = min(tid + T, 112 * 4 - 1);       // (a lane past the end repeats the last value)
+  int s_in = ps.src[p0 + tid], d_in = ps.dst[p0 + tid];
+  double tab0 = FG_SINCOS_TAB[t0 >> 2][t0 & 3], tab1 = FG_SINCOS_TAB[t1 >> 2][t1 & 3];
+  asm volatile("" : "+v"(s_in), "+v"(d_in), "+v"(tab0), "+v"(tab1));
+  fgs_lds_tab[t0] = tab0; fgs_lds_tab[t1] = tab1;
+  __syncthreads();
   // ---- first half: clip.  Lane = candidate pair; 4 of 10 pairs of a cubed-sphere x lat-lon job come out empty.
   bool defer = false;
   int n_cur = 0;
-  if (d_pair_live(ps, p0 + tid)) {
-    n_cur = d_clip_quad_sh<RECT, T>(sh_poly, tid, ps.src[p0 + tid], ps.dst[p0 + tid], S, D, R, err);
+  if ((unsigned)(p0 + tid) - reg * (unsigned)ps.regcap < min(fill, (unsigned)ps.regcap)) {      // d_pair_live
+    n_cur = d_clip_quad_sh<RECT, T>(sh_poly, tid, s_in, d_in, S, D, R, err);
     if (n_cur < 0) { defer = true; n_cur = 0; }        // rare; the general kernel finishes this pair
     else if (n_cur == 0) ps.dst[p0 + tid] = -1;
   }
@@ -1585,8 +1623,8 @@ __global__ __launch_bounds__(CLIP_THREADS) __attribute__((amdgpu_waves_per_eu(CL
   int s = -1, d_acc = -1;
   if (n_cur > 0) {
     const int p = p0 + src;
-    s = ps.src[p];
-    const int d = ps.dst[p];
+    s = CLIP_COMPACT ? ps.src[p] : s_in;               // (a pair that reaches this point still has the dst it came with)
+    const int d = CLIP_COMPACT ? ps.dst[p] : d_in;
     ClipOut o; o.area = -1.0; o.clon = 0; o.clat = 0;
     const double *px = (const double *)&sh_poly[0][src];
 #if FG_EXP == 1
