@@ -17,6 +17,9 @@ mirrors the reference's call signatures:
   -- tools/runoff_regrid/runoff_regrid.c:430,626,708,243,322 (setup_remap, process_data's arithmetic, nearest, the grids)
 * ``LandNearest``
   -- tools/remap_land/remap_land.c:2520,2569 (full_search_nearest, search_nearest_sface)
+* ``RiverRegrid`` / ``river_source_grid`` / ``river_land_frac``
+  -- tools/river_regrid/river_regrid.c:694,880,991,1298,1180,352,544 (calc_max_subA, calc_tocell, calc_river_data, sort_basin,
+     check_river_data, the source bounds, the land fraction thresholds)
 
 There is NO CPU fallback: if the shared library is missing, or no HIP device is visible
 when a compute entry point is called, an exception is raised.
@@ -41,6 +44,8 @@ from .extrapolate import (Extrapolator, do_extrapolate, setup_vertical_interp, d
 from .runoff import (RunoffRegrid, nearest_unmasked, runoff_input_grid, runoff_output_grid,  # noqa: F401
                      set_runoff_prune, runoff_tile)
 from .remap_land import LandNearest, set_rland_prune, rland_tile  # noqa: F401
+from .river import (RiverRegrid, river_source_grid, river_land_frac, set_river_prune, river_qsort_index,  # noqa: F401
+                    river_sort_basin)
 from .parallel import (band_rows, row_cost, allreduce_cell_sums, allreduce_scalar_sum, allreduce_minmax,  # noqa: F401
                        boundary_source_cells, allreduce_cell_sums_sparse, ordered_cell_sums, CellSumExchange)
 from .conserve_interp import (  # noqa: F401
@@ -59,6 +64,7 @@ __all__ = [
     "Extrapolator", "do_extrapolate", "setup_vertical_interp", "do_vertical_interp",
     "RunoffRegrid", "nearest_unmasked", "runoff_input_grid", "runoff_output_grid",
     "LandNearest",
+    "RiverRegrid", "river_source_grid", "river_land_frac",
 ]
 
 

@@ -60,6 +60,8 @@ EXPORTS = [
     "fg_nearest_unmasked", "fg_set_runoff_prune", "fg_runoff_tile",
     "fg_rland_create", "fg_rland_destroy", "fg_rland_stream", "fg_rland_search", "fg_rland_search_sface", "fg_rland_stats",
     "fg_rland_phase_ms", "fg_set_rland_prune", "fg_rland_tile",
+    "fg_river_create", "fg_river_destroy", "fg_river_stream", "fg_river_run", "fg_river_get", "fg_river_get_max_suba",
+    "fg_river_stats", "fg_river_phase_ms", "fg_set_river_prune", "fg_river_qsort_index",
 ]
 
 
@@ -433,6 +435,26 @@ def lib():
     L.fg_set_rland_prune.restype = None
     L.fg_rland_tile.argtypes = []
     L.fg_rland_tile.restype = C.c_int
+    L.fg_river_create.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, C.c_int, ip, ip, C.c_int] + [dpp] * 6 + [C.c_double, C.c_int, C.POINTER(vp)]
+    L.fg_river_create.restype = C.c_int
+    L.fg_river_destroy.argtypes = [vp]
+    L.fg_river_destroy.restype = None
+    L.fg_river_stream.argtypes = [vp]
+    L.fg_river_stream.restype = vp
+    L.fg_river_run.argtypes = [vp]
+    L.fg_river_run.restype = C.c_int
+    L.fg_river_get.argtypes = [vp, C.c_int, dp, ip, ip, ip, dp, dp]
+    L.fg_river_get.restype = C.c_int
+    L.fg_river_get_max_suba.argtypes = [vp, C.c_int, dp]
+    L.fg_river_get_max_suba.restype = C.c_int
+    L.fg_river_stats.argtypes = [vp, C.POINTER(C.c_long), C.c_int]
+    L.fg_river_stats.restype = C.c_int
+    L.fg_river_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    L.fg_river_phase_ms.restype = C.c_int
+    L.fg_set_river_prune.argtypes = [C.c_int]
+    L.fg_set_river_prune.restype = None
+    L.fg_river_qsort_index.argtypes = [dp, C.c_int, ip]
+    L.fg_river_qsort_index.restype = C.c_int
     _LIB = L
     return L
 

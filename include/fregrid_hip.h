@@ -861,6 +861,45 @@ int  fg_rland_phase_ms(const fg_rland *h, float *ms, int n);
 void fg_set_rland_prune(int on);
 int  fg_rland_tile(void);                                                   /* compacted source points per tile */
 
+/* ---- river_regrid on the device (tools/river_regrid/river_regrid.c: calc_max_subA :694, calc_tocell :880, calc_river_data
+ * :991, sort_basin :1298, check_river_data :1180) ----
+ * The arrays are those get_source_data and get_mosaic_grid leave in river_type; reading the files, the land fractions from
+ * the exchange grids and write_river_data are the caller's.  Every output carries the reference's bits.
+ * Source: xb_r [nx_in+1], yb_r [ny_in+1] (radians), subA_in [ny_in*nx_in]; missing6: the missing values of subA, tocell, travel,
+ * basin, cellarea, celllength as the file gives them (doubles).  Limits: subA's must fit an int (init_river_data keeps it in
+ * one); those of tocell, travel and basin must be negative integers (the reference's sweeps take any value >= 0 for data).
+ * Mosaic: ntiles tiles of nx[n] x ny[n] cells, all equal; opcode = 1 (x cyclic) | 2 (y cyclic) | 4 (cubic grid, 6 tiles); per
+ * tile xb, yb [(ny+1)*(nx+1)] (radians), xt, yt [(ny+2)*(nx+2)] (degrees: interior given, the halo is filled here by
+ * update_halo_double's rule, what that rule never writes stays as given), area [ny*nx], landfrac [ny*nx] (thresholded, in [0, 1]).
+ * Errors of the reference come back as FG_ERR_ARG with its message text, never as an abort. */
+typedef struct fg_river fg_river;
+int  fg_river_create(int nx_in, int ny_in, const double *xb_r, const double *yb_r, const double *subA_in, const double *missing6,
+                     int ntiles, const int *nx, const int *ny, int opcode, const double *const *xb, const double *const *yb,
+                     const double *const *xt, const double *const *yt, const double *const *area, const double *const *landfrac,
+                     double suba_cutoff, int device, fg_river **out);
+void fg_river_destroy(fg_river *h);
+void *fg_river_stream(fg_river *h);
+/* all five stages; the handle may be run again */
+int  fg_river_run(fg_river *h);
+/* the interior [ny*nx] of a tile, as write_river_data copies it; any pointer may be NULL */
+int  fg_river_get(const fg_river *h, int tile, double *subA, int *tocell, int *travel, int *basin, double *cellarea, double *celllength);
+/* calc_max_subA's result with its halo [(ny+2)*(nx+2)], as calc_tocell reads it (tests) */
+int  fg_river_get_max_suba(const fg_river *h, int tile, double *out);
+/* of the last run (the first n of 7): [0] maximum travel, [1] maximum basin, [2] coast points that are full land, [3] sink
+ * points (check_river_data's counts), [4] full-land cells (those the search runs for), [5] source cells the search visited,
+ * [6] kernel launches */
+int  fg_river_stats(const fg_river *h, long *stats, int n);
+/* wall time in ms (the first n of 5): create; of the last run: max subA; tocell, outlets, travel and basin; accumulated subA;
+ * sort_basin and check_river_data on the host */
+int  fg_river_phase_ms(const fg_river *h, float *ms, int n);
+/* Test hook; results never depend on it.  1 (default): only the adjust_lon calls that change the longitudes are replayed and
+ * only the source cells between them that can overlap are visited; 0: every land cell walks every source cell in the
+ * reference's order.  A source grid whose bounds do not ascend always takes the second path. */
+void fg_set_river_prune(int on);
+/* qsort_index (:1538) on the host: sorts array [n] ascending in place and carries index [n] along, with the reference's order
+ * among equal values (sort_basin's ids depend on it) */
+int  fg_river_qsort_index(double *array, int n, int *index);
+
 #ifdef __cplusplus
 }
 #endif
