@@ -2,16 +2,13 @@
 // (tools/fregrid/bilinear_interp.c:72-434) and do_scalar / do_vector_bilinear_interp (:436-560) on the device.
 // Kernels: bilinear_kernels.hip.  Host arithmetic that must round like the reference: bilinear_host.c, c2l_host.c.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <string>
 #include <thread>
 #include <vector>
 #include "bilinear.h"
-#include "fregrid_hip.h"
-
-void fg_set_last_error(const char *msg);
+#include "fg_host.h"
 
 extern "C" {
 void fg_unit_vect_latlon(long size, const double *lon, const double *lat, double *vlon, double *vlat);
@@ -37,16 +34,6 @@ template <typename F> static void bl_parallel(long n, F fn)
   fn(0L, chunk < n ? chunk : n);
   for (std::thread &x : w) x.join();
 }
-
-static int bl_fail(int code, const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  fg_set_last_error(buf);
-  return code;
-}
-#define BLCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return bl_fail(FG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 #define BL_MAX_ITER 10                    // setup_bilinear_interp's max_iter (:76)
 
@@ -107,22 +94,18 @@ static int bl_prepare(int ntiles, const int *nx, const int *ny, const double *co
                       double lonbegin, double lonend, double latbegin, double latend, int center_y, int device, fg_bilin **out,
                       std::vector<double> *lat_fine_out)
 {
-  if (!out) return bl_fail(FG_ERR_ARG, "fg_bilin: null output handle");
+  if (!out) return fg_fail(FG_ERR_ARG, "fg_bilin: null output handle");
   *out = nullptr;
-  if (ntiles != 6) return bl_fail(FG_ERR_ARG, "bilinear_interp: source mosaic should be cubic mosaic and have six tiles when using bilinear option");
-  if (ncontacts != 12) return bl_fail(FG_ERR_ARG, "bilinear_interp: a cubic mosaic has 12 contacts, got %d", ncontacts);
-  if (finer_step < 0) return bl_fail(FG_ERR_ARG, "bilinear_interp: finer_step must be >= 0");
-  if (nlat < 2) return bl_fail(FG_ERR_ARG, "bilinear_interp: nlat must be >= 2");
-  if (nlon < 1 || finer_step > 10) return bl_fail(FG_ERR_ARG, "bilinear_interp: bad nlon / finer_step");
-  if (!nx || !ny || !lont || !latt || !tile1 || !tile2) return bl_fail(FG_ERR_ARG, "fg_bilin: null argument");
+  if (ntiles != 6) return fg_fail(FG_ERR_ARG, "bilinear_interp: source mosaic should be cubic mosaic and have six tiles when using bilinear option");
+  if (ncontacts != 12) return fg_fail(FG_ERR_ARG, "bilinear_interp: a cubic mosaic has 12 contacts, got %d", ncontacts);
+  if (finer_step < 0) return fg_fail(FG_ERR_ARG, "bilinear_interp: finer_step must be >= 0");
+  if (nlat < 2) return fg_fail(FG_ERR_ARG, "bilinear_interp: nlat must be >= 2");
+  if (nlon < 1 || finer_step > 10) return fg_fail(FG_ERR_ARG, "bilinear_interp: bad nlon / finer_step");
+  if (!nx || !ny || !lont || !latt || !tile1 || !tile2) return fg_fail(FG_ERR_ARG, "fg_bilin: null argument");
   for (int t = 0; t < 6; t++)
     if (nx[t] != nx[0] || ny[t] != nx[0] || nx[t] < 2 || nx[t] > 8191 || !lont[t] || !latt[t])
-      return bl_fail(FG_ERR_ARG, "bilinear_interp: the six tiles must be N x N with the same 2 <= N <= 8191");
-  int ndev = 0;
-  BLCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return bl_fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  if (device < 0 || device >= ndev) return bl_fail(FG_ERR_ARG, "device out of range");
-  BLCHK(hipSetDevice(device));
+      return fg_fail(FG_ERR_ARG, "bilinear_interp: the six tiles must be N x N with the same 2 <= N <= 8191");
+  if (int rc = fg_use_device("fg_bilin", device)) return rc;
 
   const int N = nx[0], nxd = N + 2;
   const long T = (long)nxd * nxd, F = 6 * T, ncells = 6L * N * N;
@@ -131,7 +114,7 @@ static int bl_prepare(int ntiles, const int *nx, const int *ny, const double *co
   std::vector<int> map(F);
   int rc = fg_halo_map(6, nx, ny, ncontacts, tile1, tile2, istart1, iend1, jstart1, jend1, istart2, iend2, jstart2, jend2,
                        map_off.data(), map.data());
-  if (rc) return bl_fail(rc, "fregrid_util: inconsistent contact description (size mismatch between the boundary)");
+  if (rc) return fg_fail(rc, "fregrid_util: inconsistent contact description (size mismatch between the boundary)");
   std::vector<double> lh(2 * F, 0.0);
   std::vector<int> cell_of(F, -1);
   for (int t = 0; t < 6; t++)
@@ -159,7 +142,7 @@ static int bl_prepare(int ntiles, const int *nx, const int *ny, const double *co
   fg_bilin *h = new fg_bilin();
   h->device = device; h->N = N; h->nlon = nlon; h->nlat = nlat; h->finer_step = finer_step;
   h->nxo = nxo; h->nyo = nyo; h->npts = npts; h->ncells = ncells; h->F = F;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return bl_fail(FG_ERR_HIP, "hipStreamCreate failed"); }
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fg_fail(FG_ERR_HIP, "hipStreamCreate failed"); }
   h->own_stream = true;
   h->xt = h->alloc<double>(3 * F); h->lont = h->alloc<double>(2 * F);
   h->vlon_in = h->alloc<double>(3 * F); h->vlat_in = h->alloc<double>(3 * F);
@@ -182,7 +165,7 @@ static int bl_prepare(int ntiles, const int *nx, const int *ny, const double *co
     h->cosp.push_back(dc); h->acosp.push_back(da);
     ny_s = (ny_s - 1) / 2 + 1;
   }
-  if (!ok) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: out of device memory or upload failed"); }
+  if (!ok) { fg_bilin_destroy(h); return fg_fail(FG_ERR_HIP, "fg_bilin: out of device memory or upload failed"); }
   if (lat_fine_out) *lat_fine_out = la1;
   *out = h;
   return 0;
@@ -220,7 +203,7 @@ extern "C" int fg_bilin_create(int ntiles, const int *nx, const int *ny, const d
   unsigned long long *key = h->alloc<unsigned long long>(h->npts);
   int *found = h->alloc<int>(h->npts);
   unsigned *unfound = h->alloc<unsigned>(BL_MAX_ITER + 2);      // [BL_MAX_ITER + 1]: ambiguous ties
-  if (!win || !cnt || !off || !bsum || !total || !key || !found || !unfound) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: out of device memory"); }
+  if (!win || !cnt || !off || !bsum || !total || !key || !found || !unfound) { fg_bilin_destroy(h); return fg_fail(FG_ERR_HIP, "fg_bilin: out of device memory"); }
   hipStream_t st = h->stream;
   bool ok = hipMemsetAsync(key, 0xff, h->npts * sizeof(unsigned long long), st) == hipSuccess &&
             hipMemsetAsync(found, 0, h->npts * sizeof(int), st) == hipSuccess &&
@@ -239,10 +222,10 @@ extern "C" int fg_bilin_create(int ntiles, const int *nx, const int *ny, const d
        hipStreamSynchronize(st) == hipSuccess;
   const unsigned left = left2[0];
   h->ambiguous_ties = left2[1];
-  if (!ok) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: search kernels failed"); }
+  if (!ok) { fg_bilin_destroy(h); return fg_fail(FG_ERR_HIP, "fg_bilin: search kernels failed"); }
   if (left) {
     fg_bilin_destroy(h);
-    return bl_fail(FG_ERR_BILIN_NOTFOUND, "bilinear_interp: %u lat-lon points have no lower-left corner after %d sweeps "
+    return fg_fail(FG_ERR_BILIN_NOTFOUND, "bilinear_interp: %u lat-lon points have no lower-left corner after %d sweeps "
                    "(the reference would start its global sweep here, which reads past its arrays; not reproduced)", left, BL_MAX_ITER);
   }
   // weights: angles, acosl arguments and side cosines on the device, acosl / acos / sin / asin with the host libm, the
@@ -269,7 +252,7 @@ extern "C" int fg_bilin_create(int ntiles, const int *nx, const int *ny, const d
   for (void *p : {(void *)win, (void *)cnt, (void *)off, (void *)bsum, (void *)total, (void *)key, (void *)found, (void *)unfound}) {
     for (size_t k = 0; k < h->owned.size(); k++) if (h->owned[k] == p) { (void)hipFree(p); h->owned.erase(h->owned.begin() + k); break; }
   }
-  if (!ok) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "fg_bilin: weight kernel failed"); }
+  if (!ok) { fg_bilin_destroy(h); return fg_fail(FG_ERR_HIP, "fg_bilin: weight kernel failed"); }
   *out = h;
   return 0;
 }
@@ -281,7 +264,7 @@ extern "C" int fg_bilin_create_from_weights(int ntiles, const int *nx, const int
                                             int nlat, int finer_step, double lonbegin, double lonend, double latbegin, double latend,
                                             int center_y, const int *index, const double *weight, int device, fg_bilin **out)
 {
-  if (!index || !weight) return bl_fail(FG_ERR_ARG, "fg_bilin_create_from_weights: null index / weight");
+  if (!index || !weight) return fg_fail(FG_ERR_ARG, "fg_bilin_create_from_weights: null index / weight");
   fg_bilin *h = nullptr;
   int rc = bl_prepare(ntiles, nx, ny, lont, latt, ncontacts, tile1, tile2, istart1, iend1, jstart1, jend1, istart2, iend2, jstart2,
                       jend2, nlon, nlat, finer_step, lonbegin, lonend, latbegin, latend, center_y, device, &h, nullptr);
@@ -290,22 +273,22 @@ extern "C" int fg_bilin_create_from_weights(int ntiles, const int *nx, const int
     if (index[3 * n] < 0 || index[3 * n] > h->N || index[3 * n + 1] < 0 || index[3 * n + 1] > h->N || index[3 * n + 2] < 0 ||
         index[3 * n + 2] > 5) {
       fg_bilin_destroy(h);
-      return bl_fail(FG_ERR_ARG, "fg_bilin_create_from_weights: index of point %ld out of range", n);
+      return fg_fail(FG_ERR_ARG, "fg_bilin_create_from_weights: index of point %ld out of range", n);
     }
-  if (!up(h->index, index, 3 * h->npts) || !up(h->weight, weight, 4 * h->npts)) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "upload failed"); }
+  if (!up(h->index, index, 3 * h->npts) || !up(h->weight, weight, 4 * h->npts)) { fg_bilin_destroy(h); return fg_fail(FG_ERR_HIP, "upload failed"); }
   fgd_bl_corners(h->geom(), h->index, h->cell_of, h->elem, h->cell, h->stream);
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { fg_bilin_destroy(h); return bl_fail(FG_ERR_HIP, "corner kernel failed"); }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { fg_bilin_destroy(h); return fg_fail(FG_ERR_HIP, "corner kernel failed"); }
   *out = h;
   return 0;
 }
 
 extern "C" int fg_bilin_get_index_weight(const fg_bilin *h, int *index, double *weight)
 {
-  if (!h) return bl_fail(FG_ERR_ARG, "null handle");
-  BLCHK(hipSetDevice(h->device));
-  BLCHK(hipStreamSynchronize(h->stream));
-  if (index) BLCHK(hipMemcpy(index, h->index, 3 * h->npts * sizeof(int), hipMemcpyDeviceToHost));
-  if (weight) BLCHK(hipMemcpy(weight, h->weight, 4 * h->npts * sizeof(double), hipMemcpyDeviceToHost));
+  if (!h) return fg_fail(FG_ERR_ARG, "null handle");
+  FGCHK(hipSetDevice(h->device));
+  FGCHK(hipStreamSynchronize(h->stream));
+  if (index) FGCHK(hipMemcpy(index, h->index, 3 * h->npts * sizeof(int), hipMemcpyDeviceToHost));
+  if (weight) FGCHK(hipMemcpy(weight, h->weight, 4 * h->npts * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -319,18 +302,18 @@ extern "C" long fg_bilin_ambiguous_ties(const fg_bilin *h) { return h ? (long)h-
 
 extern "C" int fg_bilin_set_stream(fg_bilin *h, void *stream)
 {
-  if (!h) return bl_fail(FG_ERR_ARG, "null handle");
-  BLCHK(hipSetDevice(h->device));
-  BLCHK(hipStreamSynchronize(h->stream));
-  if (h->own_stream) BLCHK(hipStreamDestroy(h->stream));
+  if (!h) return fg_fail(FG_ERR_ARG, "null handle");
+  FGCHK(hipSetDevice(h->device));
+  FGCHK(hipStreamSynchronize(h->stream));
+  if (h->own_stream) FGCHK(hipStreamDestroy(h->stream));
   h->stream = (hipStream_t)stream; h->own_stream = false;
   return 0;
 }
 extern "C" int fg_bilin_sync(fg_bilin *h)
 {
-  if (!h) return bl_fail(FG_ERR_ARG, "null handle");
-  BLCHK(hipSetDevice(h->device));
-  BLCHK(hipStreamSynchronize(h->stream));
+  if (!h) return fg_fail(FG_ERR_ARG, "null handle");
+  FGCHK(hipSetDevice(h->device));
+  FGCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -360,38 +343,38 @@ static void bl_coarsen(fg_bilin *h, double *fine, double *b, double *tmp, int nz
 extern "C" int fg_bilin_apply_scalar(fg_bilin *h, const double *src, int nz, int has_missing, double missing, int fill_missing,
                                      double *out)
 {
-  if (!h || !src || !out || nz < 1) return bl_fail(FG_ERR_ARG, "fg_bilin_apply_scalar: bad argument");
-  BLCHK(hipSetDevice(h->device));
+  if (!h || !src || !out || nz < 1) return fg_fail(FG_ERR_ARG, "fg_bilin_apply_scalar: bad argument");
+  FGCHK(hipSetDevice(h->device));
   const size_t nf = (size_t)nz * h->npts;
   if (h->finer_step == 0) {
     fgd_bl_gather_scalar(h->npts, h->ncells, nz, h->cell, h->weight, src, has_missing, missing, fill_missing, out, h->stream);
   } else {
     double *ws = bl_workspace(h, 3 * nf);
-    if (!ws) return bl_fail(FG_ERR_HIP, "fg_bilin_apply_scalar: out of device memory");
+    if (!ws) return fg_fail(FG_ERR_HIP, "fg_bilin_apply_scalar: out of device memory");
     fgd_bl_gather_scalar(h->npts, h->ncells, nz, h->cell, h->weight, src, has_missing, missing, fill_missing, ws, h->stream);
     bl_coarsen(h, ws, ws + nf, ws + 2 * nf, nz, has_missing, missing, out);
   }
-  BLCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int fg_bilin_apply_vector(fg_bilin *h, const double *u, const double *v, int nz, int has_missing, double missing,
                                      int fill_missing, double *u_out, double *v_out)
 {
-  if (!h || !u || !v || !u_out || !v_out || nz < 1) return bl_fail(FG_ERR_ARG, "fg_bilin_apply_vector: bad argument");
-  BLCHK(hipSetDevice(h->device));
+  if (!h || !u || !v || !u_out || !v_out || nz < 1) return fg_fail(FG_ERR_ARG, "fg_bilin_apply_vector: bad argument");
+  FGCHK(hipSetDevice(h->device));
   const size_t nf = (size_t)nz * h->npts;
   if (h->finer_step == 0) {
     fgd_bl_gather_vector(h->npts, h->ncells, nz, h->elem, h->cell, h->weight, h->vlon_in, h->vlat_in, h->vlon_o, h->vlat_o, u, v,
                          has_missing, missing, fill_missing, u_out, v_out, h->stream);
   } else {
     double *ws = bl_workspace(h, 4 * nf);
-    if (!ws) return bl_fail(FG_ERR_HIP, "fg_bilin_apply_vector: out of device memory");
+    if (!ws) return fg_fail(FG_ERR_HIP, "fg_bilin_apply_vector: out of device memory");
     fgd_bl_gather_vector(h->npts, h->ncells, nz, h->elem, h->cell, h->weight, h->vlon_in, h->vlat_in, h->vlon_o, h->vlat_o, u, v,
                          has_missing, missing, fill_missing, ws, ws + nf, h->stream);
     bl_coarsen(h, ws, ws + 2 * nf, ws + 3 * nf, nz, has_missing, missing, u_out);
     bl_coarsen(h, ws + nf, ws + 2 * nf, ws + 3 * nf, nz, has_missing, missing, v_out);
   }
-  BLCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }

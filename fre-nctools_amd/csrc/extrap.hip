@@ -10,26 +10,13 @@
 // stopping iteration; the launches behind it were no-ops, so the buffer iteration n wrote holds the answer.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <atomic>
 #include <vector>
 #include "extrap.h"
-#include "fregrid_hip.h"
+#include "fg_host.h"
 #include "sincos_glibc.h"
-
-void fg_set_last_error(const char *msg);
-
-static int ex_fail(int code, const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  fg_set_last_error(buf);
-  return code;
-}
-#define EXCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return ex_fail(FG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 #define EX_DEFAULT_BATCH 64
 static std::atomic<int> g_batch{EX_DEFAULT_BATCH};
@@ -66,11 +53,11 @@ static void ex_factors(int ni, int nj, const double *lon, const double *lat, dou
 
 static int ex_check_grid(int ni, int nj, const double *lon, const double *lat)
 {
-  if (ni < 2 || nj < 2) return ex_fail(FG_ERR_ARG, "fg_extrap: the grid must be at least 2 x 2 (ni = %d, nj = %d)", ni, nj);
-  if ((long)ni * nj > 0x7fffffffL / 4) return ex_fail(FG_ERR_ARG, "fg_extrap: grid too large");
-  if (!lon || !lat) return ex_fail(FG_ERR_ARG, "fg_extrap: null axis");
+  if (ni < 2 || nj < 2) return fg_fail(FG_ERR_ARG, "fg_extrap: the grid must be at least 2 x 2 (ni = %d, nj = %d)", ni, nj);
+  if ((long)ni * nj > 0x7fffffffL / 4) return fg_fail(FG_ERR_ARG, "fg_extrap: grid too large");
+  if (!lon || !lat) return fg_fail(FG_ERR_ARG, "fg_extrap: null axis");
   for (int j = 0; j < nj; j++)
-    if (!(fabs(lat[j]) < 2.4)) return ex_fail(FG_ERR_ARG, "fg_extrap: latitude %d (%g) is not in radians", j, lat[j]);
+    if (!(fabs(lat[j]) < 2.4)) return fg_fail(FG_ERR_ARG, "fg_extrap: latitude %d (%g) is not in radians", j, lat[j]);
   return 0;
 }
 
@@ -78,7 +65,7 @@ extern "C" int fg_extrap_coef_host(int ni, int nj, const double *lon, const doub
 {
   int rc_ = ex_check_grid(ni, nj, lon, lat);
   if (rc_) return rc_;
-  if (!cfw || !cfe || !cfs || !cfn) return ex_fail(FG_ERR_ARG, "fg_extrap_coef_host: null output");
+  if (!cfw || !cfe || !cfs || !cfn) return fg_fail(FG_ERR_ARG, "fg_extrap_coef_host: null output");
   std::vector<double> rn(nj), rs(nj), rc(nj), ce(ni), cw(ni);
   ex_factors(ni, nj, lon, lat, rn.data(), rs.data(), rc.data(), ce.data(), cw.data());
   for (int j = 0; j < nj; j++) for (int i = 0; i < ni; i++) {
@@ -117,33 +104,31 @@ extern "C" void fg_extrap_destroy(fg_extrap *h)
 static int ex_create(int ni, int nj, const double *lon, const double *lat, int is_cyclic, int device, fg_extrap *h)
 {
   const long ncell = (long)ni * nj;
-  EXCHK(hipSetDevice(device));
+  FGCHK(hipSetDevice(device));
   h->device = device; h->ni = ni; h->nj = nj; h->is_cyclic = is_cyclic ? 1 : 0;
   h->h_fac.resize(3 * (size_t)nj + 2 * (size_t)ni);
   double *f = h->h_fac.data();
   ex_factors(ni, nj, lon, lat, f, f + nj, f + 2 * nj, f + 3 * nj, f + 3 * nj + ni);
-  EXCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  FGCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   h->own_stream = true;
-  EXCHK(hipMalloc((void **)&h->fac, h->h_fac.size() * sizeof(double)));
-  EXCHK(hipMemcpy(h->fac, f, h->h_fac.size() * sizeof(double), hipMemcpyHostToDevice));
-  EXCHK(hipMalloc((void **)&h->buf[0], ncell * sizeof(double)));
-  EXCHK(hipMalloc((void **)&h->buf[1], ncell * sizeof(double)));
-  EXCHK(hipMalloc((void **)&h->sorbits, ((ncell + 63) / 64) * sizeof(unsigned long long)));
-  EXCHK(hipMalloc((void **)&h->slots, EX_MAX_ITER * sizeof(unsigned long long)));
-  EXCHK(hipHostMalloc((void **)&h->h_slots, EX_MAX_ITER * sizeof(unsigned long long)));
+  FGCHK(hipMalloc((void **)&h->fac, h->h_fac.size() * sizeof(double)));
+  FGCHK(hipMemcpy(h->fac, f, h->h_fac.size() * sizeof(double), hipMemcpyHostToDevice));
+  FGCHK(hipMalloc((void **)&h->buf[0], ncell * sizeof(double)));
+  FGCHK(hipMalloc((void **)&h->buf[1], ncell * sizeof(double)));
+  FGCHK(hipMalloc((void **)&h->sorbits, ((ncell + 63) / 64) * sizeof(unsigned long long)));
+  FGCHK(hipMalloc((void **)&h->slots, EX_MAX_ITER * sizeof(unsigned long long)));
+  FGCHK(hipHostMalloc((void **)&h->h_slots, EX_MAX_ITER * sizeof(unsigned long long)));
   return 0;
 }
 
 extern "C" int fg_extrap_create(int ni, int nj, const double *lon, const double *lat, int is_cyclic, int device, fg_extrap **out)
 {
-  if (!out) return ex_fail(FG_ERR_ARG, "fg_extrap_create: null output handle");
+  if (!out) return fg_fail(FG_ERR_ARG, "fg_extrap_create: null output handle");
   *out = nullptr;
   int rc = ex_check_grid(ni, nj, lon, lat);
   if (rc) return rc;
-  int ndev = 0;
-  EXCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return ex_fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  if (device < 0 || device >= ndev) return ex_fail(FG_ERR_ARG, "fg_extrap_create: device out of range");
+  rc = fg_use_device("fg_extrap_create", device);
+  if (rc) return rc;
   fg_extrap *h = new fg_extrap;
   rc = ex_create(ni, nj, lon, lat, is_cyclic, device, h);
   if (rc) { fg_extrap_destroy(h); return rc; }
@@ -153,9 +138,9 @@ extern "C" int fg_extrap_create(int ni, int nj, const double *lon, const double 
 
 extern "C" int fg_extrap_set_stream(fg_extrap *h, void *stream)
 {
-  if (!h) return ex_fail(FG_ERR_ARG, "fg_extrap_set_stream: null handle");
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_extrap_set_stream: null handle");
   (void)hipSetDevice(h->device);
-  if (h->stream) EXCHK(hipStreamSynchronize(h->stream));
+  if (h->stream) FGCHK(hipStreamSynchronize(h->stream));
   if (h->own_stream) (void)hipStreamDestroy(h->stream);
   h->stream = (hipStream_t)stream;
   h->own_stream = false;
@@ -166,7 +151,7 @@ extern "C" long fg_extrap_last_syncs(const fg_extrap *h) { return h ? h->syncs :
 
 extern "C" int fg_extrap_get_coef(fg_extrap *h, double *cfw, double *cfe, double *cfs, double *cfn)
 {
-  if (!h || !cfw || !cfe || !cfs || !cfn) return ex_fail(FG_ERR_ARG, "fg_extrap_get_coef: null argument");
+  if (!h || !cfw || !cfe || !cfs || !cfn) return fg_fail(FG_ERR_ARG, "fg_extrap_get_coef: null argument");
   const double *f = h->h_fac.data();
   const int ni = h->ni, nj = h->nj;
   for (int j = 0; j < nj; j++) for (int i = 0; i < ni; i++) {
@@ -187,20 +172,20 @@ static int ex_stored_coef(fg_extrap *h)
     double *q = &c[4 * ((size_t)j * ni + i)];
     ex_cell_coef(f[j], f[nj + j], f[2 * nj + j], f[3 * nj + i], f[3 * nj + ni + i], q[0], q[1], q[2], q[3]);
   }
-  EXCHK(hipMalloc((void **)&h->coef, c.size() * sizeof(double)));
-  EXCHK(hipMemcpy(h->coef, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice));
+  FGCHK(hipMalloc((void **)&h->coef, c.size() * sizeof(double)));
+  FGCHK(hipMemcpy(h->coef, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
 
 extern "C" int fg_extrap_run_dev(fg_extrap *h, const double *d_in, double *d_out, int nk, long level_stride, double missing,
                                  double stop_crit, int *iters_out, double *resmax_out)
 {
-  if (!h) return ex_fail(FG_ERR_ARG, "fg_extrap_run_dev: null handle");
-  if (nk < 1 || !d_in || !d_out) return ex_fail(FG_ERR_ARG, "fg_extrap_run_dev: bad argument");
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_extrap_run_dev: null handle");
+  if (nk < 1 || !d_in || !d_out) return fg_fail(FG_ERR_ARG, "fg_extrap_run_dev: bad argument");
   const long ncell = (long)h->ni * h->nj;
   if (level_stride == 0) level_stride = ncell;
-  if (level_stride < ncell) return ex_fail(FG_ERR_ARG, "fg_extrap_run_dev: level_stride smaller than a level");
-  EXCHK(hipSetDevice(h->device));
+  if (level_stride < ncell) return fg_fail(FG_ERR_ARG, "fg_extrap_run_dev: level_stride smaller than a level");
+  FGCHK(hipSetDevice(h->device));
   const int batch = g_batch;
   ExGrid g;
   g.ni = h->ni; g.nj = h->nj; g.is_cyclic = h->is_cyclic;
@@ -218,15 +203,15 @@ extern "C" int fg_extrap_run_dev(fg_extrap *h, const double *d_in, double *d_out
     // valid points take this level's data, missing ones keep the level above's solution (:2734-2745)
     fgd_ex_prepare(g, d_in + (long)k * level_stride, missing, k ? h->buf[cur] : nullptr, h->buf[0], h->sorbits, st);
     cur = 0;
-    EXCHK(hipMemsetAsync(h->slots, 0, EX_MAX_ITER * sizeof(unsigned long long), st));
+    FGCHK(hipMemsetAsync(h->slots, 0, EX_MAX_ITER * sizeof(unsigned long long), st));
     int stop = -1;
     for (int n0 = 0; n0 < EX_MAX_ITER && stop < 0; n0 += batch) {
       const int n1 = n0 + batch < EX_MAX_ITER ? n0 + batch : EX_MAX_ITER;
       for (int n = n0; n < n1; n++)                                   // iteration n: buf[n & 1] -> buf[(n + 1) & 1]
         fgd_ex_iterate(g, h->buf[n & 1], h->buf[(n + 1) & 1], h->sorbits, stop_crit, n ? h->slots + n - 1 : nullptr, h->slots + n, st);
-      EXCHK(hipGetLastError());
-      EXCHK(hipMemcpyAsync(h->h_slots + n0, h->slots + n0, (size_t)(n1 - n0) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      EXCHK(hipStreamSynchronize(st));
+      FGCHK(hipGetLastError());
+      FGCHK(hipMemcpyAsync(h->h_slots + n0, h->slots + n0, (size_t)(n1 - n0) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      FGCHK(hipStreamSynchronize(st));
       h->syncs++;
       for (int n = n0; n < n1; n++) {
         double r;
@@ -237,21 +222,21 @@ extern "C" int fg_extrap_run_dev(fg_extrap *h, const double *d_in, double *d_out
     cur = (stop + 1) & 1;
     if (iters_out) iters_out[k] = stop;
     if (resmax_out) memcpy(&resmax_out[k], &h->h_slots[stop], sizeof(double));
-    EXCHK(hipMemcpyAsync(d_out + (long)k * level_stride, h->buf[cur], ncell * sizeof(double), hipMemcpyDeviceToDevice, st));
+    FGCHK(hipMemcpyAsync(d_out + (long)k * level_stride, h->buf[cur], ncell * sizeof(double), hipMemcpyDeviceToDevice, st));
   }
-  EXCHK(hipStreamSynchronize(st));
+  FGCHK(hipStreamSynchronize(st));
   return 0;
 }
 
 extern "C" int fg_extrap_run(fg_extrap *h, const double *in, double *out, int nk, double missing, double stop_crit,
                              int *iters_out, double *resmax_out)
 {
-  if (!h) return ex_fail(FG_ERR_ARG, "fg_extrap_run: null handle");
-  if (nk < 1 || !in || !out) return ex_fail(FG_ERR_ARG, "fg_extrap_run: bad argument");
-  EXCHK(hipSetDevice(h->device));
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_extrap_run: null handle");
+  if (nk < 1 || !in || !out) return fg_fail(FG_ERR_ARG, "fg_extrap_run: bad argument");
+  FGCHK(hipSetDevice(h->device));
   const size_t bytes = (size_t)h->ni * h->nj * (size_t)nk * sizeof(double);
   double *d = nullptr;
-  EXCHK(hipMalloc((void **)&d, bytes));
+  FGCHK(hipMalloc((void **)&d, bytes));
   int rc = 0;
   hipError_t e = hipMemcpy(d, in, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
@@ -259,7 +244,7 @@ extern "C" int fg_extrap_run(fg_extrap *h, const double *in, double *out, int nk
     if (!rc) e = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
   }
   (void)hipFree(d);
-  if (e != hipSuccess) return ex_fail(FG_ERR_HIP, "fg_extrap_run: copy failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fg_fail(FG_ERR_HIP, "fg_extrap_run: copy failed: %s", hipGetErrorString(e));
   return rc;
 }
 
@@ -267,7 +252,7 @@ extern "C" int fg_extrap_run(fg_extrap *h, const double *in, double *out, int nk
 extern "C" int fg_setup_vertical_interp(int nk1, const double *z1, int nk2, const double *z2, int *kstart_out, int *kend_out,
                                         int *need_interp_out)
 {
-  if (nk1 < 1 || nk2 < 1 || !z1 || !z2) return ex_fail(FG_ERR_ARG, "fg_setup_vertical_interp: bad argument");
+  if (nk1 < 1 || nk2 < 1 || !z1 || !z2) return fg_fail(FG_ERR_ARG, "fg_setup_vertical_interp: bad argument");
   int kstart, kend, need = 1;
   for (kstart = 0; kstart < nk2; kstart++) if (z2[kstart] >= z1[0]) break;            // fregrid_util.c:764-769
   for (kend = nk2 - 1; kend >= 0; kend--) if (z2[kend] <= z1[nk1 - 1]) break;
@@ -293,24 +278,24 @@ static int ex_nearest_index(double value, const double *array, int ia)          
 
 extern "C" int fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int nk2, const double *z2, const double *d_in, double *d_out)
 {
-  if (nxy < 1 || !d_in || !d_out) return ex_fail(FG_ERR_ARG, "fg_dev_vertical_interp: bad argument");
-  if (nk2 > 65535) return ex_fail(FG_ERR_ARG, "fg_dev_vertical_interp: more than 65535 destination levels");
+  if (nxy < 1 || !d_in || !d_out) return fg_fail(FG_ERR_ARG, "fg_dev_vertical_interp: bad argument");
+  if (nk2 > 65535) return fg_fail(FG_ERR_ARG, "fg_dev_vertical_interp: more than 65535 destination levels");
   int kstart, kend, need;
   int rc = fg_setup_vertical_interp(nk1, z1, nk2, z2, &kstart, &kend, &need);
   if (rc) return rc;
   if (!need) {                                                                        // do_vertical_interp leaves the field alone (:794)
-    if (d_in != d_out) EXCHK(hipMemcpy(d_out, d_in, (size_t)nxy * nk1 * sizeof(double), hipMemcpyDeviceToDevice));
+    if (d_in != d_out) FGCHK(hipMemcpy(d_out, d_in, (size_t)nxy * nk1 * sizeof(double), hipMemcpyDeviceToDevice));
     return 0;
   }
-  if (d_in == d_out) return ex_fail(FG_ERR_ARG, "fg_dev_vertical_interp: in and out must be different arrays");
+  if (d_in == d_out) return fg_fail(FG_ERR_ARG, "fg_dev_vertical_interp: in and out must be different arrays");
   const int nk = kend - kstart + 1;
-  if (nk < 1) return ex_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
+  if (nk < 1) return fg_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
   const double *g1 = z1, *g2 = z2 + kstart;
   // linear_vertical_interp's fatal checks (interp.c:366-374), nearest_index's (mosaic_util.c:86-89)
-  for (int k = 1; k < nk1; k++) if (g1[k] <= g1[k - 1]) return ex_fail(FG_ERR_DATA, "interp.c: grid1 not monotonic");
-  for (int k = 1; k < nk; k++) if (g2[k] <= g2[k - 1]) return ex_fail(FG_ERR_DATA, "interp.c: grid2 not monotonic");
-  if (g1[0] > g2[0]) return ex_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
-  if (g1[nk1 - 1] < g2[nk - 1]) return ex_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
+  for (int k = 1; k < nk1; k++) if (g1[k] <= g1[k - 1]) return fg_fail(FG_ERR_DATA, "interp.c: grid1 not monotonic");
+  for (int k = 1; k < nk; k++) if (g2[k] <= g2[k - 1]) return fg_fail(FG_ERR_DATA, "interp.c: grid2 not monotonic");
+  if (g1[0] > g2[0]) return fg_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
+  if (g1[nk1 - 1] < g2[nk - 1]) return fg_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
   std::vector<ExVLevel> lev(nk2);
   for (int k = 0; k < nk2; k++) {
     ExVLevel &L = lev[k];
@@ -324,7 +309,7 @@ extern "C" int fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int n
     else { L.interp = 1; L.a = n - 1; L.b = n; L.w = (v - g1[n - 1]) / (g1[n] - g1[n - 1]); }
   }
   ExVLevel *d_lev = nullptr;
-  EXCHK(hipMalloc((void **)&d_lev, lev.size() * sizeof(ExVLevel)));
+  FGCHK(hipMalloc((void **)&d_lev, lev.size() * sizeof(ExVLevel)));
   hipError_t e = hipMemcpy(d_lev, lev.data(), lev.size() * sizeof(ExVLevel), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     fgd_ex_vertical(nxy, nk2, d_lev, d_in, d_out, nullptr);
@@ -332,6 +317,6 @@ extern "C" int fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int n
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   }
   (void)hipFree(d_lev);
-  if (e != hipSuccess) return ex_fail(FG_ERR_HIP, "fg_dev_vertical_interp: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fg_fail(FG_ERR_HIP, "fg_dev_vertical_interp: %s", hipGetErrorString(e));
   return 0;
 }

@@ -7,7 +7,6 @@
 // pay hipMalloc/hipFree.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -17,29 +16,19 @@
 #include <string>
 #include <type_traits>
 #include <vector>
-#include "fregrid_hip.h"
+#include "fg_host.h"
 #include "xgrid_device.h"
 
 // ----------------------------------------------------------------------------- errors
 static thread_local std::string g_err;
-static int fail(int code, const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  g_err = buf;
-  return code;
-}
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return fail(FG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
 extern "C" const char *fg_last_error(void) { return g_err.c_str(); }
-void fg_set_last_error(const char *msg) { g_err = msg ? msg : ""; }      // for the other translation units (sweep.hip)
+void fg_set_last_error(const char *msg) { g_err = msg ? msg : ""; }      // what fg_host.h's fg_fail writes, in every translation unit
 
 extern "C" int fg_device_count(void)
 {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) { fail(FG_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e)); return FG_ERR_HIP; }
+  if (e != hipSuccess) { fg_fail(FG_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e)); return FG_ERR_HIP; }
   return n;
 }
 
@@ -111,22 +100,22 @@ extern "C" void fg_pool_release(void) { g_pool.release_all(); }
 // from the plans' caching pool; copies are synchronous.
 extern "C" void *fg_dev_alloc(size_t bytes, int device)
 {
-  if (hipSetDevice(device) != hipSuccess) { fail(FG_ERR_HIP, "fg_dev_alloc: no such HIP device %d", device); return nullptr; }
+  if (hipSetDevice(device) != hipSuccess) { fg_fail(FG_ERR_HIP, "fg_dev_alloc: no such HIP device %d", device); return nullptr; }
   void *p = g_pool.get(device, bytes);
-  if (!p) fail(FG_ERR_HIP, "fg_dev_alloc: out of device memory (%zu bytes)", bytes);
+  if (!p) fg_fail(FG_ERR_HIP, "fg_dev_alloc: out of device memory (%zu bytes)", bytes);
   return p;
 }
 extern "C" void fg_dev_free(void *p) { g_pool.put(p); }
 extern "C" int fg_dev_upload(void *dst_dev, const void *src_host, size_t bytes)
 {
-  if (bytes && (!dst_dev || !src_host)) return fail(FG_ERR_ARG, "fg_dev_upload: null pointer");
-  if (bytes) HIPCHK(hipMemcpy(dst_dev, src_host, bytes, hipMemcpyHostToDevice));
+  if (bytes && (!dst_dev || !src_host)) return fg_fail(FG_ERR_ARG, "fg_dev_upload: null pointer");
+  if (bytes) FGCHK(hipMemcpy(dst_dev, src_host, bytes, hipMemcpyHostToDevice));
   return 0;
 }
 extern "C" int fg_dev_download(void *dst_host, const void *src_dev, size_t bytes)
 {
-  if (bytes && (!dst_host || !src_dev)) return fail(FG_ERR_ARG, "fg_dev_download: null pointer");
-  if (bytes) HIPCHK(hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
+  if (bytes && (!dst_host || !src_dev)) return fg_fail(FG_ERR_ARG, "fg_dev_download: null pointer");
+  if (bytes) FGCHK(hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 // dst_dev[i] = src_dev[idx_dev[i]] / dst_dev[idx_dev[i]] = src_dev[i], i < n: moving a short list of source cells in and out of the
@@ -139,11 +128,11 @@ __global__ __launch_bounds__(256) void k_gather_f64(long n, double *dst, const d
 }
 static int dev_gather(double *dst_dev, const double *src_dev, const int *idx_dev, long n, int scatter)
 {
-  if (n < 0 || (n > 0 && (!dst_dev || !src_dev || !idx_dev))) return fail(FG_ERR_ARG, "fg_dev_gather_f64 / fg_dev_scatter_f64: bad argument");
+  if (n < 0 || (n > 0 && (!dst_dev || !src_dev || !idx_dev))) return fg_fail(FG_ERR_ARG, "fg_dev_gather_f64 / fg_dev_scatter_f64: bad argument");
   if (n == 0) return 0;
   k_gather_f64<<<(unsigned)((n + 255) / 256), 256>>>(n, dst_dev, src_dev, idx_dev, scatter);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
+  FGCHK(hipGetLastError());
+  FGCHK(hipDeviceSynchronize());
   return 0;
 }
 extern "C" int fg_dev_gather_f64(double *dst_dev, const double *src_dev, const int *idx_dev, long n) { return dev_gather(dst_dev, src_dev, idx_dev, n, 0); }
@@ -464,27 +453,23 @@ static bool alloc_cells(fg_plan *pl, FgCells *c, size_t n)
 static int plan_base(int order, int ntiles_in, const int *nx_in, const int *ny_in, int nx_out, int ny_out,
                      int device, fg_plan **out)
 {
-  if (order != FG_CONSERVE_ORDER1 && order != FG_CONSERVE_ORDER2) return fail(FG_ERR_ARG, "order must be 1 or 2");
-  if (ntiles_in < 1 || !nx_in || !ny_in || nx_out < 1 || ny_out < 1 || !out) return fail(FG_ERR_ARG, "bad grid sizes");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  if (device < 0 || device >= ndev) return fail(FG_ERR_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-  HIPCHK(hipSetDevice(device));
+  if (order != FG_CONSERVE_ORDER1 && order != FG_CONSERVE_ORDER2) return fg_fail(FG_ERR_ARG, "order must be 1 or 2");
+  if (ntiles_in < 1 || !nx_in || !ny_in || nx_out < 1 || ny_out < 1 || !out) return fg_fail(FG_ERR_ARG, "bad grid sizes");
+  if (int rc = fg_use_device("fg_plan", device)) return rc;
   fg_plan *pl = new fg_plan();
   pl->order = order; pl->device = device; pl->ntiles = ntiles_in;
   long off = 0, foff = 0;
   for (int m = 0; m < ntiles_in; m++) {
-    if (nx_in[m] < 1 || ny_in[m] < 1) { delete pl; return fail(FG_ERR_ARG, "bad source tile size"); }
+    if (nx_in[m] < 1 || ny_in[m] < 1) { delete pl; return fg_fail(FG_ERR_ARG, "bad source tile size"); }
     pl->nx_in.push_back(nx_in[m]); pl->ny_in.push_back(ny_in[m]); pl->cell_off.push_back((int)off);
     off += (long)nx_in[m] * ny_in[m];
     foff += (order == 2) ? (long)(nx_in[m] + 2) * (ny_in[m] + 2) : (long)nx_in[m] * ny_in[m];
   }
-  if (off > 2000000000L || (long)nx_out * ny_out > 2000000000L) { delete pl; return fail(FG_ERR_ARG, "grid too large for 32-bit cell indices"); }
+  if (off > 2000000000L || (long)nx_out * ny_out > 2000000000L) { delete pl; return fg_fail(FG_ERR_ARG, "grid too large for 32-bit cell indices"); }
   pl->nsrc = (int)off; pl->f_stride = foff;
   pl->nx_out = nx_out; pl->ny_out = ny_out; pl->ndst = nx_out * ny_out;
   pl->stream = g_handles.get_stream(device);
-  if (!pl->stream) { delete pl; return fail(FG_ERR_HIP, "hipStreamCreate failed"); }
+  if (!pl->stream) { delete pl; return fg_fail(FG_ERR_HIP, "hipStreamCreate failed"); }
   *out = pl;
   return 0;
 }
@@ -628,7 +613,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   hipStream_t st = pl->stream;
   const int nsrc = pl->nsrc, ndst = pl->ndst, order = pl->order;
   FgCounters *hc = pinned_counters();
-  if (!hc) return fail(FG_ERR_HIP, "hipHostMalloc failed");
+  if (!hc) return fg_fail(FG_ERR_HIP, "hipHostMalloc failed");
 
   // tile descriptors: source tiles + the destination tile as entry [ntiles]
   std::vector<FgTile> &th = pl->tiles_host;  // owned by the plan: an async upload needs no sync
@@ -636,11 +621,11 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   for (int m = 0; m < pl->ntiles; m++) th[m] = FgTile{gc ? nullptr : in.lon_in[m], gc ? nullptr : in.lat_in[m], pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
   th[pl->ntiles] = FgTile{in.lon_out, in.lat_out, pl->nx_out, pl->ny_out, 0};
   pl->tiles_dev = pl->alloc<FgTile>(pl->ntiles + 1);
-  if (!pl->tiles_dev) return fail(FG_ERR_HIP, "out of device memory");
+  if (!pl->tiles_dev) return fg_fail(FG_ERR_HIP, "out of device memory");
   FgTileSet ts; ts.n = 0;
   const bool by_value = !gc && pl->ntiles + 1 <= FG_TILESET_MAX;        // descriptors travel as a kernel argument
   if (by_value) { ts.n = pl->ntiles + 1; for (int m = 0; m <= pl->ntiles; m++) ts.t[m] = th[m]; }
-  else HIPCHK(hipMemcpyAsync(pl->tiles_dev, th.data(), sizeof(FgTile) * th.size(), hipMemcpyHostToDevice, st));
+  else FGCHK(hipMemcpyAsync(pl->tiles_dev, th.data(), sizeof(FgTile) * th.size(), hipMemcpyHostToDevice, st));
   FgTileXyz *gct_dev = nullptr;
   std::vector<FgTileXyz> gct;                       // must outlive the async upload: synchronised at the readback
   if (gc) {
@@ -648,23 +633,23 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
     for (int m = 0; m < pl->ntiles; m++) gct[m] = FgTileXyz{in.gc_in[m].x, in.gc_in[m].y, in.gc_in[m].z, pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
     gct[pl->ntiles] = FgTileXyz{in.gc_out->x, in.gc_out->y, in.gc_out->z, pl->nx_out, pl->ny_out, 0};
     gct_dev = pl->alloc<FgTileXyz>(pl->ntiles + 1);
-    if (!gct_dev) return fail(FG_ERR_HIP, "out of device memory");
-    HIPCHK(hipMemcpyAsync(gct_dev, gct.data(), sizeof(FgTileXyz) * gct.size(), hipMemcpyHostToDevice, st));
+    if (!gct_dev) return fg_fail(FG_ERR_HIP, "out of device memory");
+    FGCHK(hipMemcpyAsync(gct_dev, gct.data(), sizeof(FgTileXyz) * gct.size(), hipMemcpyHostToDevice, st));
   }
 
   bool any_mask = false;
   if (in.mask_in) for (int m = 0; m < pl->ntiles; m++) if (in.mask_in[m]) any_mask = true;
   if (any_mask) {
     pl->mask_dev = pl->alloc<double>(nsrc);
-    if (!pl->mask_dev) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->mask_dev) return fg_fail(FG_ERR_HIP, "out of device memory");
     std::vector<double> ones;
     for (int m = 0; m < pl->ntiles; m++) {
       size_t nc = (size_t)pl->nx_in[m] * pl->ny_in[m];
-      if (in.mask_in[m]) HIPCHK(hipMemcpyAsync(pl->mask_dev + pl->cell_off[m], in.mask_in[m], nc * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (in.mask_in[m]) FGCHK(hipMemcpyAsync(pl->mask_dev + pl->cell_off[m], in.mask_in[m], nc * sizeof(double), hipMemcpyDeviceToDevice, st));
       else {
         ones.assign(nc, 1.0);
-        HIPCHK(hipMemcpyAsync(pl->mask_dev + pl->cell_off[m], ones.data(), nc * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
+        FGCHK(hipMemcpyAsync(pl->mask_dev + pl->cell_off[m], ones.data(), nc * sizeof(double), hipMemcpyHostToDevice, st));
+        FGCHK(hipStreamSynchronize(st));
       }
     }
   }
@@ -685,7 +670,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   const long npairs = fgd_pairs_total(ps);            // capacity of the pair list
   const long nx_alloc = npairs;                       // nxgrid <= candidate pairs <= capacity
 
-  if (!alloc_cells(pl, &pl->S, nsrc)) return fail(FG_ERR_HIP, "out of device memory");
+  if (!alloc_cells(pl, &pl->S, nsrc)) return fg_fail(FG_ERR_HIP, "out of device memory");
   SearchBlocks blk{pl};
   struct { double *hdr, *lat_ax, *lon_ax, *col, *row, *col_min, *col_max, *col_avg; } rt{};   // the rectilinear tables, one block (FgRect, xgrid_device.h)
   if (rect) {
@@ -695,9 +680,9 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
     const size_t o_hdr = at(8), o_lat = at((size_t)pl->ny_out + 1), o_lon = at((size_t)pl->nx_out + 1), o_col = at(8 * (size_t)pl->nx_out),
                  o_row = at(4 * ((size_t)pl->ny_out + 1)), o_cmin = at((size_t)pl->nx_out), o_cmax = at((size_t)pl->nx_out), o_cavg = at((size_t)pl->nx_out);
     double *rect_blk = blk.keep<double>(at.n);
-    if (!blk.ok) return fail(FG_ERR_HIP, "out of device memory");
+    if (!blk.ok) return fg_fail(FG_ERR_HIP, "out of device memory");
     rt = {rect_blk + o_hdr, rect_blk + o_lat, rect_blk + o_lon, rect_blk + o_col, rect_blk + o_row, rect_blk + o_cmin, rect_blk + o_cmax, rect_blk + o_cavg};
-  } else if (!alloc_cells(pl, &pl->D, ndst)) return fail(FG_ERR_HIP, "out of device memory");
+  } else if (!alloc_cells(pl, &pl->D, ndst)) return fg_fail(FG_ERR_HIP, "out of device memory");
   // one zeroed block: [counters | region fill counters | tickets | look-back words of the three scans | bin counts |
   //                    bin fill cursors | destination-row counts | accepted pairs per source cell | great-circle task counters]
   const long t_bins = fgd_scan_tiles(nslots), t_rows = fgd_scan_tiles(ndst), t_comp = fgd_scan_tiles(nsrc);
@@ -745,7 +730,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   pl->perm = blk.keep<FgRowEnt>(nx_alloc + 1);
   pl->csr.row_ptr = blk.keep<int>(ndst + 1);
   if (!pl->src_idx_f) pl->src_idx_f = blk.keep<int>(nsrc + 1);
-  if (!blk.ok) return fail(FG_ERR_HIP, "out of device memory");
+  if (!blk.ok) return fg_fail(FG_ERR_HIP, "out of device memory");
   FgCounters *dc = (FgCounters *)(zero_blk + z_dc);
   ps.fill = (unsigned *)(zero_blk + z_fill);
   unsigned *tickets = (unsigned *)(zero_blk + z_tick);                     // [0] bins [1] rows [2] xoff scan
@@ -753,8 +738,8 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
                      *lb_comp = (unsigned long long *)(zero_blk + z_lb_comp);
   int *bin_cnt = (int *)(zero_blk + z_bin_cnt), *bin_fill = (int *)(zero_blk + z_bin_fill), *row_cnt = (int *)(zero_blk + z_row_cnt);
   int *nacc = (int *)(zero_blk + z_nacc);
-  HIPCHK(hipMemsetAsync(zero_blk, 0, zbytes, st));
-  if (pl->ll_err) HIPCHK(hipMemcpyAsync(&dc->err[2], pl->ll_err, sizeof(unsigned), hipMemcpyDeviceToDevice, st));   // rides on the one readback
+  FGCHK(hipMemsetAsync(zero_blk, 0, zbytes, st));
+  if (pl->ll_err) FGCHK(hipMemcpyAsync(&dc->err[2], pl->ll_err, sizeof(unsigned), hipMemcpyDeviceToDevice, st));   // rides on the one readback
 
   PhaseTimer pt, ptot;
   pt.start(opt.profile, st); ptot.start(opt.profile, st);
@@ -812,7 +797,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   pt.end();
   // --- clip, area, centroid integrals
   hipEvent_t gc_e1 = nullptr, gc_e2 = nullptr;        // great-circle clip: the listed pairs run on stream B beside k_gc_walk
-  struct EvReturn {                                   // back to the cache on every way out of this function (HIPCHK / fail returns too)
+  struct EvReturn {                                   // back to the cache on every way out of this function (FGCHK / fg_fail returns too)
     hipEvent_t &a, &b;
     ~EvReturn() { g_handles.put_sync_event(a); g_handles.put_sync_event(b); a = b = nullptr; }
   } ev_return{gc_e1, gc_e2};
@@ -874,11 +859,11 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
     pt.begin(PH_FINALIZE);
     if (order == 2) {
       pl->cen = pl->alloc<FgSrcRec>((size_t)nsrc + 1);
-      if (!pl->cen) return fail(FG_ERR_HIP, "out of device memory");
+      if (!pl->cen) return fg_fail(FG_ERR_HIP, "out of device memory");
       fgd_centroids(nsrc, pl->S, pl->sums, pl->cen, st);
       pl->csr.e2 = pl->alloc<FgCsrEntry2>(nx_alloc + 1);
     } else pl->csr.e1 = pl->alloc<FgCsrEntry1>(nx_alloc + 1);
-    if (!pl->csr.e1 && !pl->csr.e2) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->csr.e1 && !pl->csr.e2) return fg_fail(FG_ERR_HIP, "out of device memory");
     // (the row-length heuristic of the record kernel wants the exchange-cell count: nsrc + ndst is within a factor of it)
     int *sg_tmp = pl->alloc<int>(3 * (size_t)(nx_alloc + 1));   // (scratch for rows beyond the LDS staging; null = the serial last resort)
     fgd_csr_sortgather(order, ndst, (long)nsrc + ndst, pl->perm, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f,
@@ -886,29 +871,29 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
     fused_tmp = sg_tmp;
     pt.end();
   }
-  HIPCHK(hipMemcpyAsync(hc, dc, sizeof(FgCounters), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));                              // the one synchronisation of a search (stream B's work is ordered before it)
+  FGCHK(hipMemcpyAsync(hc, dc, sizeof(FgCounters), hipMemcpyDeviceToHost, st));
+  FGCHK(hipStreamSynchronize(st));                              // the one synchronisation of a search (stream B's work is ordered before it)
   pt.collect(pl->phase_ms); ptot.collect(pl->phase_ms);          // (also hands the timing events back on every exit below)
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   if (rect && hc->rect_bad) { caps->rect = false; return FG_RETRY; }   // not a rectilinear grid after all: every kernel of this attempt left at once
   if (hc->total[0] > nentries) { caps->entries = hc->total[0]; return FG_RETRY; }
-  if (hc->total[0] > 2000000000ull) return fail(FG_ERR_ARG, "bin table too large");
+  if (hc->total[0] > 2000000000ull) return fg_fail(FG_ERR_ARG, "bin table too large");
   if (hc->total[3] > (unsigned long long)ps.regcap) {
-    if (hc->total[3] > 2000000000ull / (unsigned long long)ps.nreg) return fail(FG_ERR_CAPACITY, "candidate pair list exceeds 2^31 entries");
+    if (hc->total[3] > 2000000000ull / (unsigned long long)ps.nreg) return fg_fail(FG_ERR_CAPACITY, "candidate pair list exceeds 2^31 entries");
     caps->regcap = (int)((hc->total[3] + FG_REG_ALIGN - 1) / FG_REG_ALIGN * FG_REG_ALIGN);
     return FG_RETRY;
   }
-  if (hc->err[2] & G_ERRBIT_LL2X) return fail(FG_ERR_ARG, "latlon2xyz: a grid corner is not finite, or its latitude (|lat| >= 2.4262) or longitude "
+  if (hc->err[2] & G_ERRBIT_LL2X) return fg_fail(FG_ERR_ARG, "latlon2xyz: a grid corner is not finite, or its latitude (|lat| >= 2.4262) or longitude "
                                                           "(|lon| > 1024) lies outside the range of the device trig (radians expected)");
-  if (hc->err[0] & 8u) return fail(FG_ERR_ARG, "a grid corner latitude lies outside [-pi/2, pi/2] (radians expected)");
-  if (hc->err[0] & 1u) return fail(FG_ERR_MAXV, "create_xgrid.c: n2_in is greater than MAX_V");
-  if (hc->err[0] & 2u) return fail(FG_ERR_PARALLEL, "the line between <x1_0,y1_0> and  <x1_1,y1_1> should not parallel to "
+  if (hc->err[0] & 8u) return fg_fail(FG_ERR_ARG, "a grid corner latitude lies outside [-pi/2, pi/2] (radians expected)");
+  if (hc->err[0] & 1u) return fg_fail(FG_ERR_MAXV, "create_xgrid.c: n2_in is greater than MAX_V");
+  if (hc->err[0] & 2u) return fg_fail(FG_ERR_PARALLEL, "the line between <x1_0,y1_0> and  <x1_1,y1_1> should not parallel to "
                                                     "the line between <x2_0,y2_0> and  <x2_1,y2_1>");
-  if (hc->err[0] & 4u) return fail(FG_ERR_MAXV, "clipped polygon exceeds 16 vertices");
-  if (hc->err[0] & G_ERRBIT_GC_CONVEX1) return fail(FG_ERR_GEOM, "create_xgrid.c(clip_2dx2d_great_circle): grid box 1 is not convex");
-  if (hc->err[0] & G_ERRBIT_GC_CONVEX2) return fail(FG_ERR_GEOM, "create_xgrid.c(clip_2dx2d_great_circle): grid box 2 is not convex");
-  if (hc->err[0] & G_ERRBIT_GC_CLIP) return fail(FG_ERR_GEOM, "%s", gc_clip_error((int)hc->err[1]));
-  if (hc->err[0] & G_ERRBIT_LOOKBACK) return fail(FG_ERR_HIP, "single-pass scan: a tile waited too long for its predecessor");
+  if (hc->err[0] & 4u) return fg_fail(FG_ERR_MAXV, "clipped polygon exceeds 16 vertices");
+  if (hc->err[0] & G_ERRBIT_GC_CONVEX1) return fg_fail(FG_ERR_GEOM, "create_xgrid.c(clip_2dx2d_great_circle): grid box 1 is not convex");
+  if (hc->err[0] & G_ERRBIT_GC_CONVEX2) return fg_fail(FG_ERR_GEOM, "create_xgrid.c(clip_2dx2d_great_circle): grid box 2 is not convex");
+  if (hc->err[0] & G_ERRBIT_GC_CLIP) return fg_fail(FG_ERR_GEOM, "%s", gc_clip_error((int)hc->err[1]));
+  if (hc->err[0] & G_ERRBIT_LOOKBACK) return fg_fail(FG_ERR_HIP, "single-pass scan: a tile waited too long for its predecessor");
   pl->nx = (long)hc->xtot;
   pl->stats[FG_STAT_PAIRS] = (long)hc->total[1];
   pl->stats[FG_STAT_NONEMPTY] = (long)(hc->xtot + hc->stats[FG_STAT_BELOW]);
@@ -927,7 +912,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   if (fuse) {
     pl->release(pl->perm); pl->perm = nullptr; pl->release(fused_tmp);
     if (!pl->red_partial) { pl->red_partial = pl->alloc<double>(1024); pl->red_result = pl->alloc<double>(260); }
-    if (!pl->red_partial || !pl->red_result) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->red_partial || !pl->red_result) return fg_fail(FG_ERR_HIP, "out of device memory");
     pl->dist_pending = (order == 2);
     pl->finalized = true; pl->fused = true;
   }
@@ -954,7 +939,7 @@ static long plan_search(fg_plan *pl, const SearchIn &in)
   // 32-bit prefixes (bin starts, exchange-cell offsets, CSR rows): the bin table holds up to 3 records per destination cell
   // (+ the wide lists) and the pair list 8 per cell, so grids beyond 2^28 cells could wrap an int before the host sees a
   // counter -- refused up front rather than guarded in every kernel
-  if (big > (1L << 28)) return fail(FG_ERR_CAPACITY, "grid of %ld cells: more than 2^28 cells per search are not supported", big);
+  if (big > (1L << 28)) return fg_fail(FG_ERR_CAPACITY, "grid of %ld cells: more than 2^28 cells per search are not supported", big);
   SearchCaps caps;
   caps.entries = opt.exact ? 0ull : 3ull * (unsigned long long)pl->ndst + 4096ull;
   const unsigned long long cap_pairs = std::min<unsigned long long>(8ull * (unsigned long long)big + 65536ull, 2000000000ull);
@@ -973,7 +958,7 @@ static long plan_search(fg_plan *pl, const SearchIn &in)
     }
     rc = plan_search_core(pl, in, opt, &caps);
   }
-  if (rc == FG_RETRY) return fail(FG_ERR_CAPACITY, "exchange-grid search: capacities did not settle");
+  if (rc == FG_RETRY) return fg_fail(FG_ERR_CAPACITY, "exchange-grid search: capacities did not settle");
   if (rc >= 0) pl->stats[FG_STAT_EXACT] = (attempts > 1) ? 1 : 0;
   return rc;
 }
@@ -1033,12 +1018,12 @@ static int sample_corners_dev(fg_plan *pl, int nx, int ny, int narr, const doubl
   const long step = sample_step(nx, ny, &s->nsamp);
   s->q.resize((size_t)s->nsamp * narr * 4);
   double *d_q = (double *)g_pool.get(pl->device, s->q.size() * sizeof(double));
-  if (!d_q) return fail(FG_ERR_HIP, "out of device memory");
+  if (!d_q) return fg_fail(FG_ERR_HIP, "out of device memory");
   k_sample_corners<<<(s->nsamp + 255) / 256, 256, 0, pl->stream>>>(nx, step, s->nsamp, narr, d_a0, d_a1, d_a2, d_q);
   hipError_t e = hipMemcpyAsync(s->q.data(), d_q, s->q.size() * sizeof(double), hipMemcpyDeviceToHost, pl->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(pl->stream);
   g_pool.put(d_q);
-  if (e != hipSuccess) return fail(FG_ERR_HIP, "sampling the destination corners failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fg_fail(FG_ERR_HIP, "sampling the destination corners failed: %s", hipGetErrorString(e));
   return 0;
 }
 // sums over cnt representative cells -> the means choose_bins takes
@@ -1107,7 +1092,7 @@ static int dst_extents_dev(fg_plan *pl, const double *d_a0, const double *d_a1, 
 {
   if (x->dlat > 0 && x->dlon > 0) return 0;
   CornerSample s;
-  HIPCHK(hipSetDevice(pl->device));
+  FGCHK(hipSetDevice(pl->device));
   if (sample_corners_dev(pl, pl->nx_out, pl->ny_out, d_a2 ? 3 : 2, d_a0, d_a1, d_a2, &s)) return FG_ERR_HIP;
   int curvilinear = 0;
   if (d_a2) extents_xyz(s, &x->dlat, &x->dlon);
@@ -1133,7 +1118,7 @@ static int check_grid_ptrs(int ntiles, std::initializer_list<const double *const
   for (const double *const *t : tables) ok = ok && t;
   for (const double *p : dst) ok = ok && p;
   if (ok) for (const double *const *t : tables) for (int m = 0; m < ntiles; m++) ok = ok && t[m];
-  return ok ? 0 : fail(FG_ERR_ARG, "null grid pointer");
+  return ok ? 0 : fg_fail(FG_ERR_ARG, "null grid pointer");
 }
 namespace {
 // Host arrays into plan-owned blocks, all in one batch of the transfer pool; done() hands back the blocks, for a caller whose
@@ -1177,7 +1162,7 @@ static int stage_host_grids(fg_plan *pl, const double *const *lon_in, const doub
   }
   const size_t npo = (size_t)(pl->nx_out + 1) * (pl->ny_out + 1);
   if (up.ok) { s->lon_out = up.put(lon_out, npo); s->lat_out = up.put(lat_out, npo); }
-  if (!up.run()) return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)");
+  if (!up.run()) return fg_fail(FG_ERR_HIP, "grid upload failed (out of device memory?)");
   return 0;
 }
 // The plan runs on the caller's stream from here on and never owns it; a stream of its own goes back to the cache.
@@ -1281,7 +1266,7 @@ extern "C" long fg_plan_create_great_circle(int ntiles_in, const int *nx_in, con
     const double *d = upload(h.data(), 3 * np);
     bool ok = d != nullptr;
     if (ok && src && mask_in && mask_in[m]) ok = (dmask[m] = upload(mask_in[m], (size_t)nx_in[m] * ny_in[m])) != nullptr;
-    if (!ok) return fail(FG_ERR_HIP, "grid upload failed (out of device memory?)");
+    if (!ok) return fg_fail(FG_ERR_HIP, "grid upload failed (out of device memory?)");
     gxyz[m] = GcXyz{d, d + np, d + 2 * np};
   }
   const long nx = gc_search(pl, gxyz.data(), mask_in ? dmask.data() : nullptr, dst_extents_host(nx_out, ny_out, lon_out, lat_out));
@@ -1295,12 +1280,12 @@ extern "C" long fg_plan_create_great_circle(int ntiles_in, const int *nx_in, con
 
 extern "C" int fg_dev_latlon2xyz(long n, const double *d_lon, const double *d_lat, double *d_x, double *d_y, double *d_z, int device, void *stream)
 {
-  if (n < 0 || (n > 0 && (!d_lon || !d_lat || !d_x || !d_y || !d_z))) return fail(FG_ERR_ARG, "fg_dev_latlon2xyz: bad size or null pointer");
+  if (n < 0 || (n > 0 && (!d_lon || !d_lat || !d_x || !d_y || !d_z))) return fg_fail(FG_ERR_ARG, "fg_dev_latlon2xyz: bad size or null pointer");
   if (n == 0) return 0;
-  HIPCHK(hipSetDevice(device));
+  FGCHK(hipSetDevice(device));
   const FgLl2xGrid g{d_lon, d_lat, d_x, d_y, d_z, n};
   fgd_latlon2xyz(&g, 1, nullptr, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
@@ -1316,18 +1301,18 @@ static long gc_lonlat_search(fg_plan *pl, const double *const *d_lon_in, const d
   for (int m = 0; m <= nt; m++) {
     const size_t np = m < nt ? (size_t)(pl->nx_in[m] + 1) * (pl->ny_in[m] + 1) : (size_t)(pl->nx_out + 1) * (pl->ny_out + 1);
     double *d = pl->alloc<double>(3 * np);          // x | y | z
-    if (!d) return fail(FG_ERR_HIP, "out of device memory");
+    if (!d) return fg_fail(FG_ERR_HIP, "out of device memory");
     blocks.push_back(d);
     jobs[m] = FgLl2xGrid{m < nt ? d_lon_in[m] : d_lon_out, m < nt ? d_lat_in[m] : d_lat_out, d, d + np, d + 2 * np, (long)np};
     gxyz[m] = GcXyz{d, d + np, d + 2 * np};
   }
   pl->ll_err = pl->alloc<unsigned>(1);
-  if (!pl->ll_err) return fail(FG_ERR_HIP, "out of device memory");
+  if (!pl->ll_err) return fg_fail(FG_ERR_HIP, "out of device memory");
   blocks.push_back(pl->ll_err);
   hipError_t e = hipSetDevice(pl->device);
   if (e == hipSuccess) e = hipMemsetAsync(pl->ll_err, 0, sizeof(unsigned), pl->stream);
   if (e == hipSuccess) { fgd_latlon2xyz(jobs.data(), nt + 1, pl->ll_err, pl->stream); e = hipGetLastError(); }
-  if (e != hipSuccess) return fail(FG_ERR_HIP, "latlon2xyz: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fg_fail(FG_ERR_HIP, "latlon2xyz: %s", hipGetErrorString(e));
   const long nx = gc_search(pl, gxyz.data(), d_mask_in, x);
   if (nx < 0) return nx;
   for (void *p : blocks) pl->release(p);
@@ -1376,7 +1361,7 @@ extern "C" long fg_plan_create_polylist(int order, int npoly, const int *n, cons
                                         const double *area_ref, int nx_out, int ny_out, const double *lon_out, const double *lat_out,
                                         int device, fg_plan **plan_out)
 {
-  if (npoly < 1 || !n || !lon || !lat || !lon_avg || !area_ref || !lon_out || !lat_out) return fail(FG_ERR_ARG, "null argument");
+  if (npoly < 1 || !n || !lon || !lat || !lon_avg || !area_ref || !lon_out || !lat_out) return fg_fail(FG_ERR_ARG, "null argument");
   PlanGuard g;
   const int one = 1;
   if (int rc = plan_base(order, 1, &npoly, &one, nx_out, ny_out, device, &g.pl)) return rc;
@@ -1387,7 +1372,7 @@ extern "C" long fg_plan_create_polylist(int order, int npoly, const int *n, cons
   pl->polys = FgPolyList{up.put(n, npoly), up.put(lon, (size_t)npoly * 8), up.put(lat, (size_t)npoly * 8), up.put(lon_avg, npoly),
                          up.put(area_ref, npoly), npoly};
   double *d_lo = up.put(lon_out, npo), *d_la = up.put(lat_out, npo);
-  if (!up.run()) return fail(FG_ERR_HIP, "polygon upload failed (out of device memory?)");
+  if (!up.run()) return fg_fail(FG_ERR_HIP, "polygon upload failed (out of device memory?)");
   const DstExtents x = dst_extents_host(nx_out, ny_out, lon_out, lat_out);
   const double *none[1] = {nullptr};
   const long nx = plan_search(pl, SearchIn{.lon_in = none, .lat_in = none, .lon_out = d_lo, .lat_out = d_la, .mean_dlat = x.dlat,
@@ -1398,9 +1383,9 @@ extern "C" long fg_plan_create_polylist(int order, int npoly, const int *n, cons
 
 extern "C" int fg_plan_set_stream(fg_plan *pl, void *stream)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipStreamSynchronize(pl->stream));
   adopt_stream(pl, stream);
   return 0;
 }
@@ -1410,9 +1395,9 @@ extern "C" int fg_plan_set_stream(fg_plan *pl, void *stream)
 // give back: the caller has synchronised `stream`.  The plan never owns a borrowed stream.
 int fg_plan_borrow_stream(fg_plan *pl, void *stream, void **saved, int *saved_own)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipStreamSynchronize(pl->stream));
   *saved = (void *)pl->stream; *saved_own = pl->own_stream ? 1 : 0;
   pl->stream = (hipStream_t)stream; pl->own_stream = false;
   return 0;
@@ -1434,7 +1419,7 @@ extern "C" int fg_plan_create_empty(int order, int ntiles_in, const int *nx_in, 
   for (int m = 0; m < pl->ntiles; m++) th[m] = FgTile{nullptr, nullptr, pl->nx_in[m], pl->ny_in[m], pl->cell_off[m]};
   pl->tiles_dev = pl->alloc<FgTile>(pl->ntiles + 1);
   if (!pl->tiles_dev || hipMemcpy(pl->tiles_dev, th.data(), sizeof(FgTile) * th.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(FG_ERR_HIP, "out of device memory");
+    return fg_fail(FG_ERR_HIP, "out of device memory");
   return (int)g.hand_over(0, plan_out);
 }
 
@@ -1443,19 +1428,19 @@ extern "C" int fg_plan_create_empty(int order, int ntiles_in, const int *nx_in, 
 // the arrays are re-allocated at nxgrid entries (device-to-device copies, ~0.1 ms at C384 -> 0.25 deg).
 extern "C" int fg_plan_trim(fg_plan *pl)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  if (!pl->searched) return fail(FG_ERR_STATE, "fg_plan_trim: plan holds no exchange cells");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  if (!pl->searched) return fg_fail(FG_ERR_STATE, "fg_plan_trim: plan holds no exchange cells");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipStreamSynchronize(pl->stream));
   const size_t n = (size_t)pl->nx + 1;
   auto shrink = [&](auto *&ptr) -> int {
     if (!ptr) return 0;
     typedef typename std::remove_reference<decltype(*ptr)>::type T;
     T *q = pl->alloc<T>(n);
-    if (!q) return fail(FG_ERR_HIP, "out of device memory");
-    if (hipMemcpyAsync(q, ptr, n * sizeof(T), hipMemcpyDeviceToDevice, pl->stream) != hipSuccess) return fail(FG_ERR_HIP, "device copy failed");
+    if (!q) return fg_fail(FG_ERR_HIP, "out of device memory");
+    if (hipMemcpyAsync(q, ptr, n * sizeof(T), hipMemcpyDeviceToDevice, pl->stream) != hipSuccess) return fg_fail(FG_ERR_HIP, "device copy failed");
     void *old = ptr; ptr = q;
-    HIPCHK(hipStreamSynchronize(pl->stream));
+    FGCHK(hipStreamSynchronize(pl->stream));
     pl->release(old);
     return 0;
   };
@@ -1473,11 +1458,11 @@ extern "C" int fg_plan_device(const fg_plan *pl) { return pl ? pl->device : FG_E
 extern "C" double *fg_plan_cell_sums_dev(fg_plan *pl) { return (pl && pl->order == 2) ? pl->sums : nullptr; }
 extern "C" int fg_plan_copy_cell_sums(fg_plan *pl, double *dst_dev)
 {
-  if (!pl || !dst_dev) return fail(FG_ERR_ARG, "null argument");
-  if (pl->order != 2 || !pl->sums) return fail(FG_ERR_STATE, "plan holds no order-2 cell sums");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipMemcpyAsync(dst_dev, pl->sums, 3 * (size_t)pl->nsrc * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl || !dst_dev) return fg_fail(FG_ERR_ARG, "null argument");
+  if (pl->order != 2 || !pl->sums) return fg_fail(FG_ERR_STATE, "plan holds no order-2 cell sums");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipMemcpyAsync(dst_dev, pl->sums, 3 * (size_t)pl->nsrc * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+  FGCHK(hipStreamSynchronize(pl->stream));
   return 0;
 }
 // total_dev[3][ncells_in] (sum of area, of the clon integral, of the clat integral per source cell) += this plan's exchange cells,
@@ -1485,14 +1470,14 @@ extern "C" int fg_plan_copy_cell_sums(fg_plan *pl, double *dst_dev)
 // of source cells.  Before fg_plan_finalize only.
 static int accumulate_cell_sums(fg_plan *pl, double *total_dev, const int *cells_dev, int ncells, bool sync)
 {
-  if (!pl || !total_dev) return fail(FG_ERR_ARG, "null argument");
+  if (!pl || !total_dev) return fg_fail(FG_ERR_ARG, "null argument");
   if (pl->order != 2 || !pl->searched || pl->finalized || !pl->xoff)
-    return fail(FG_ERR_STATE, "fg_plan_accumulate_cell_sums: needs a searched, not yet finalized order-2 plan");
-  HIPCHK(hipSetDevice(pl->device));
+    return fg_fail(FG_ERR_STATE, "fg_plan_accumulate_cell_sums: needs a searched, not yet finalized order-2 plan");
+  FGCHK(hipSetDevice(pl->device));
   if (pl->nx > 0)
     fgd_accumulate_cell_sums(cells_dev ? ncells : pl->nsrc, cells_dev, pl->nsrc, pl->xoff, pl->x_area, pl->x_c1, pl->x_c2, total_dev, pl->stream);
-  if (sync) HIPCHK(hipStreamSynchronize(pl->stream));
-  HIPCHK(hipGetLastError());
+  if (sync) FGCHK(hipStreamSynchronize(pl->stream));
+  FGCHK(hipGetLastError());
   return 0;
 }
 extern "C" int fg_plan_accumulate_cell_sums(fg_plan *pl, double *total_dev, const int *cells_dev, int ncells)
@@ -1508,13 +1493,13 @@ extern "C" int fg_plan_accumulate_cell_sums_async(fg_plan *pl, double *total_dev
 extern "C" void *fg_plan_stream(fg_plan *pl) { return pl ? (void *)pl->stream : nullptr; }
 extern "C" int fg_plan_sync(fg_plan *pl)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  FGCHK(hipStreamSynchronize(pl->stream));
   return 0;
 }
 extern "C" int fg_plan_stats(const fg_plan *pl, long *stats, int n)
 {
-  if (!pl || !stats) return fail(FG_ERR_ARG, "null argument");
+  if (!pl || !stats) return fg_fail(FG_ERR_ARG, "null argument");
   for (int k = 0; k < n && k < FG_NSTATS; k++) stats[k] = pl->stats[k];
   return 0;
 }
@@ -1527,10 +1512,10 @@ static int build_csr(fg_plan *pl, const FgSrcRec *cen)
   hipStream_t st = pl->stream;
   const int ndst = pl->ndst;
   const long nx = pl->nx;
-  HIPCHK(hipSetDevice(pl->device));
+  FGCHK(hipSetDevice(pl->device));
   if (!pl->src_idx_f) {
     pl->src_idx_f = pl->alloc<int>(pl->nsrc + 1);
-    if (!pl->src_idx_f) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->src_idx_f) return fg_fail(FG_ERR_HIP, "out of device memory");
     fgd_src_field_index(pl->order, pl->tiles_dev, pl->ntiles, pl->nsrc, pl->src_idx_f, st);
   }
   void *scratch = nullptr;
@@ -1540,8 +1525,8 @@ static int build_csr(fg_plan *pl, const FgSrcRec *cen)
     char *z = pl->alloc<char>(zb);                                    // [ticket, total, err | look-back words | counts | fill cursors]
     pl->perm = pl->alloc<FgRowEnt>(nx + 1);
     pl->csr.row_ptr = pl->alloc<int>(ndst + 1);
-    if (!z || !pl->perm || !pl->csr.row_ptr) return fail(FG_ERR_HIP, "out of device memory");
-    HIPCHK(hipMemsetAsync(z, 0, zb, st));
+    if (!z || !pl->perm || !pl->csr.row_ptr) return fg_fail(FG_ERR_HIP, "out of device memory");
+    FGCHK(hipMemsetAsync(z, 0, zb, st));
     unsigned long long *lb = (unsigned long long *)(z + 256);
     int *row_cnt = (int *)(z + 256 + (size_t)t_rows * sizeof(unsigned long long));
     fgd_csr_count(nx, pl->x_dst, row_cnt, st);
@@ -1551,7 +1536,7 @@ static int build_csr(fg_plan *pl, const FgSrcRec *cen)
   }
   if (pl->order == 2) pl->csr.e2 = pl->alloc<FgCsrEntry2>(nx + 1);
   else pl->csr.e1 = pl->alloc<FgCsrEntry1>(nx + 1);
-  if (!pl->csr.e1 && !pl->csr.e2) return fail(FG_ERR_HIP, "out of device memory");
+  if (!pl->csr.e1 && !pl->csr.e2) return fg_fail(FG_ERR_HIP, "out of device memory");
   // rows longer than the kernel's LDS staging are sorted through this -- also in plans whose MEAN row is short: the cells around a
   // pole of a cubed-sphere target hold a whole row of a lat-lon source each (1 440 exchange cells: a lane sorting that by insertion
   // took 17 ms)
@@ -1562,28 +1547,28 @@ static int build_csr(fg_plan *pl, const FgSrcRec *cen)
   const int long_rows = !pl->rect && !pl->great_circle && pl->stats[FG_STAT_DEFERRED] > 0 && nx > 4 * (long)ndst;
   fgd_csr_sortgather(pl->order, ndst, nx, pl->perm, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f, cen, pl->csr, st, sg_tmp, nx + 1,
                      long_rows);
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(st));
+  FGCHK(hipGetLastError());
   pl->release(scratch); pl->release(pl->perm); pl->perm = nullptr; pl->release(sg_tmp);
   if (!pl->red_partial) { pl->red_partial = pl->alloc<double>(1024); pl->red_result = pl->alloc<double>(260); }
-  if (!pl->red_partial || !pl->red_result) return fail(FG_ERR_HIP, "out of device memory");
+  if (!pl->red_partial || !pl->red_result) return fg_fail(FG_ERR_HIP, "out of device memory");
   return 0;
 }
 
 extern "C" int fg_plan_finalize(fg_plan *pl, const double *total_cell_sums_dev)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  if (!pl->searched) return fail(FG_ERR_STATE, "fg_plan_finalize: plan holds no search result");
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  if (!pl->searched) return fg_fail(FG_ERR_STATE, "fg_plan_finalize: plan holds no search result");
   if (pl->finalized && pl->fused && !total_cell_sums_dev) return 0;         // its search did it (fg_set_search_finalize)
-  if (pl->finalized) return fail(FG_ERR_STATE, pl->fused ? "fg_plan_finalize: the plan was finalized by its search (fg_set_search_finalize) from its own "
+  if (pl->finalized) return fg_fail(FG_ERR_STATE, pl->fused ? "fg_plan_finalize: the plan was finalized by its search (fg_set_search_finalize) from its own "
                                                           "per-cell sums; totals over several plans need the two-step sequence"
                                                          : "fg_plan_finalize: already finalized");
-  HIPCHK(hipSetDevice(pl->device));
+  FGCHK(hipSetDevice(pl->device));
   PhaseTimer pt; pt.start(g_profiling != 0, pl->stream);
   pt.begin(PH_FINALIZE);
   if (pl->order == 2) {
     pl->cen = pl->alloc<FgSrcRec>((size_t)pl->nsrc + 1);
-    if (!pl->cen) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->cen) return fg_fail(FG_ERR_HIP, "out of device memory");
     const double *tot = total_cell_sums_dev ? total_cell_sums_dev : pl->sums;
     fgd_centroids(pl->nsrc, pl->S, tot, pl->cen, pl->stream);
     pl->dist_pending = true;                 // the CSR records get di/dj now; the exchange-cell arrays when somebody asks for them
@@ -1591,7 +1576,7 @@ extern "C" int fg_plan_finalize(fg_plan *pl, const double *total_cell_sums_dev)
   int rc = build_csr(pl, pl->order == 2 ? pl->cen : nullptr);
   if (rc) return rc;
   pt.end();
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  FGCHK(hipStreamSynchronize(pl->stream));
   pl->phase_ms[PH_FINALIZE] = 0; pt.collect(pl->phase_ms);
   pl->finalized = true;
   return 0;
@@ -1602,10 +1587,10 @@ extern "C" int fg_plan_finalize(fg_plan *pl, const double *total_cell_sums_dev)
 // [6] destination rows [7] whole search (device span) [8] finalize [9] last apply
 extern "C" int fg_plan_phase_ms(fg_plan *pl, float *ms, int n)
 {
-  if (!pl || !ms) return fail(FG_ERR_ARG, "null argument");
+  if (!pl || !ms) return fg_fail(FG_ERR_ARG, "null argument");
   if (pl->apply_spans > 0) {               // sweeps are timed without a sync; average them now
-    HIPCHK(hipSetDevice(pl->device));
-    HIPCHK(hipStreamSynchronize(pl->stream));
+    FGCHK(hipSetDevice(pl->device));
+    FGCHK(hipStreamSynchronize(pl->stream));
     float acc[PH_COUNT] = {0};
     pl->apply_pt.collect(acc);
     pl->phase_ms[PH_APPLY] = acc[PH_APPLY] / pl->apply_spans;
@@ -1618,16 +1603,16 @@ extern "C" int fg_plan_phase_ms(fg_plan *pl, float *ms, int n)
 extern "C" int fg_plan_get_xgrid(const fg_plan *pl, int *t_in, int *i_in, int *j_in, int *i_out, int *j_out,
                                  double *area, double *c1, double *c2)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  if (!pl->searched) return fail(FG_ERR_STATE, "plan holds no exchange cells");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  if (!pl->searched) return fg_fail(FG_ERR_STATE, "plan holds no exchange cells");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipStreamSynchronize(pl->stream));
   const long nx = pl->nx;
   if (nx == 0) return 0;
   if (pl->dist_pending) {                     // di = clon/area - centroid (conserve_interp.c:256-257,355-356), on first use
     fg_plan *m = const_cast<fg_plan *>(pl);
     fgd_distances(nx, pl->x_src, pl->x_area, pl->cen, m->x_c1, m->x_c2, pl->stream);
-    HIPCHK(hipStreamSynchronize(pl->stream));
+    FGCHK(hipStreamSynchronize(pl->stream));
     m->dist_pending = false;
   }
   std::vector<XferJob> jobs;
@@ -1636,10 +1621,10 @@ extern "C" int fg_plan_get_xgrid(const fg_plan *pl, int *t_in, int *i_in, int *j
   if (t_in || i_in || j_in || i_out || j_out) {
     // index decomposition on the device (the host loop with two divisions per exchange cell took longer than the transfer)
     idx = (int *)g_pool.get(pl->device, 5 * (size_t)nx * sizeof(int));
-    if (!idx) return fail(FG_ERR_HIP, "out of device memory");
+    if (!idx) return fg_fail(FG_ERR_HIP, "out of device memory");
     fgd_xgrid_indices(nx, pl->x_src, pl->x_dst, pl->tiles_dev, pl->ntiles, pl->nx_out, idx, idx + nx, idx + 2 * nx, idx + 3 * nx,
                       idx + 4 * nx, pl->stream);
-    HIPCHK(hipStreamSynchronize(pl->stream));
+    FGCHK(hipStreamSynchronize(pl->stream));
     int *dst[5] = {t_in, i_in, j_in, i_out, j_out};
     for (int q = 0; q < 5; q++) if (dst[q]) jobs.push_back(XferJob{dst[q], idx + (size_t)q * nx, (size_t)nx * sizeof(int), true});
   }
@@ -1648,7 +1633,7 @@ extern "C" int fg_plan_get_xgrid(const fg_plan *pl, int *t_in, int *i_in, int *j
     if (c1) jobs.push_back(XferJob{c1, pl->x_c1, (size_t)nx * sizeof(double), true});
     if (c2) jobs.push_back(XferJob{c2, pl->x_c2, (size_t)nx * sizeof(double), true});
   }
-  if (!xfer_pool().run(pl->device, jobs)) return fail(FG_ERR_HIP, "fg_plan_get_xgrid: device -> host copy failed");
+  if (!xfer_pool().run(pl->device, jobs)) return fg_fail(FG_ERR_HIP, "fg_plan_get_xgrid: device -> host copy failed");
   return 0;
 }
 
@@ -1657,12 +1642,12 @@ extern "C" int fg_plan_get_xgrid(const fg_plan *pl, int *t_in, int *i_in, int *j
 // clip_2dx2d_great_circle returned for the pair inside create_xgrid (make_coupler_mosaic.c:1560-1577 keeps exactly these).
 extern "C" int fg_plan_get_polygons(const fg_plan *pl, int maxv, int *n_out, double *v0, double *v1, double *v2)
 {
-  if (!pl || !n_out || !v0 || !v1) return fail(FG_ERR_ARG, "null argument");
-  if (!pl->searched || !pl->have_geom || !pl->x_src) return fail(FG_ERR_STATE, "fg_plan_get_polygons: needs a plan from a search (cell records)");
-  if (pl->great_circle && !v2) return fail(FG_ERR_ARG, "fg_plan_get_polygons: a great-circle plan returns x, y, z");
-  if (maxv < 3 || maxv > 64) return fail(FG_ERR_ARG, "fg_plan_get_polygons: maxv must be 3..64");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl || !n_out || !v0 || !v1) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->searched || !pl->have_geom || !pl->x_src) return fg_fail(FG_ERR_STATE, "fg_plan_get_polygons: needs a plan from a search (cell records)");
+  if (pl->great_circle && !v2) return fg_fail(FG_ERR_ARG, "fg_plan_get_polygons: a great-circle plan returns x, y, z");
+  if (maxv < 3 || maxv > 64) return fg_fail(FG_ERR_ARG, "fg_plan_get_polygons: maxv must be 3..64");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipStreamSynchronize(pl->stream));
   const long nx = pl->nx, CH = 1L << 20;
   const int dev = pl->device;
   for (long k0 = 0; k0 < nx; k0 += CH) {
@@ -1671,39 +1656,39 @@ extern "C" int fg_plan_get_polygons(const fg_plan *pl, int maxv, int *n_out, dou
     int *d_n = (int *)g_pool.get(dev, n * sizeof(int));
     double *d_v = (double *)g_pool.get(dev, 3 * nv * sizeof(double));
     struct Put { void *a, *b; ~Put() { g_pool.put(a); g_pool.put(b); } } put{d_n, d_v};
-    if (!d_n || !d_v) return fail(FG_ERR_HIP, "out of device memory");
+    if (!d_n || !d_v) return fg_fail(FG_ERR_HIP, "out of device memory");
     std::vector<XferJob> jobs;
     if (pl->great_circle) {
       double *a = (double *)g_pool.get(dev, (size_t)n * 12 * 8), *b = (double *)g_pool.get(dev, (size_t)n * 12 * 8);
       double *o = (double *)g_pool.get(dev, (size_t)n * FG_GC_POLY_CAP * 3 * 8), *ar = (double *)g_pool.get(dev, (size_t)n * 8);
       struct Put4 { void *p[4]; ~Put4() { for (void *q : p) g_pool.put(q); } } put4{{a, b, o, ar}};
-      if (!a || !b || !o || !ar) return fail(FG_ERR_HIP, "out of device memory");
+      if (!a || !b || !o || !ar) return fg_fail(FG_ERR_HIP, "out of device memory");
       fgd_xgrid_gather_gc(n, pl->x_src + k0, pl->x_dst + k0, pl->S, pl->D, a, b, pl->stream);
       fgd_gc_clip_batch((int)n, a, b, o, d_n, ar, pl->stream);
       fgd_split_xyz(n, maxv, o, d_v, d_v + nv, d_v + 2 * nv, pl->stream);
-      HIPCHK(hipStreamSynchronize(pl->stream));
+      FGCHK(hipStreamSynchronize(pl->stream));
       jobs.push_back(XferJob{v2 + (size_t)k0 * maxv, d_v + 2 * nv, nv * sizeof(double), true});
     } else {
       fgd_xgrid_polygons(n, pl->x_src + k0, pl->x_dst + k0, pl->S, pl->D, pl->rect ? &pl->rect_tab : nullptr, maxv, d_n, d_v, d_v + nv, pl->stream);
-      HIPCHK(hipStreamSynchronize(pl->stream));
+      FGCHK(hipStreamSynchronize(pl->stream));
     }
-    HIPCHK(hipGetLastError());
+    FGCHK(hipGetLastError());
     jobs.push_back(XferJob{n_out + k0, d_n, (size_t)n * sizeof(int), true});
     jobs.push_back(XferJob{v0 + (size_t)k0 * maxv, d_v, nv * sizeof(double), true});
     jobs.push_back(XferJob{v1 + (size_t)k0 * maxv, d_v + nv, nv * sizeof(double), true});
-    if (!xfer_pool().run(dev, jobs)) return fail(FG_ERR_HIP, "fg_plan_get_polygons: device -> host copy failed");
+    if (!xfer_pool().run(dev, jobs)) return fg_fail(FG_ERR_HIP, "fg_plan_get_polygons: device -> host copy failed");
   }
   return 0;
 }
 
 extern "C" int fg_plan_get_cell_area(const fg_plan *pl, double *area_in, double *area_out)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  if (!pl->have_geom) return fail(FG_ERR_STATE, "plan holds no cell records");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipStreamSynchronize(pl->stream));
-  if (area_in) HIPCHK(hipMemcpy(area_in, pl->S.area, (size_t)pl->nsrc * sizeof(double), hipMemcpyDeviceToHost));
-  if (area_out) HIPCHK(hipMemcpy(area_out, pl->D.area, (size_t)pl->ndst * sizeof(double), hipMemcpyDeviceToHost));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  if (!pl->have_geom) return fg_fail(FG_ERR_STATE, "plan holds no cell records");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipStreamSynchronize(pl->stream));
+  if (area_in) FGCHK(hipMemcpy(area_in, pl->S.area, (size_t)pl->nsrc * sizeof(double), hipMemcpyDeviceToHost));
+  if (area_out) FGCHK(hipMemcpy(area_out, pl->D.area, (size_t)pl->ndst * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1712,10 +1697,10 @@ extern "C" int fg_plan_get_cell_area(const fg_plan *pl, double *area_in, double 
 extern "C" int fg_plan_get_cell_struct(const fg_plan *pl, int which, double *lat_min, double *lat_max, double *lon_min,
                                        double *lon_max, double *lon_avg, int *nvert, double *vlon, double *vlat)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  if (!pl->have_geom) return fail(FG_ERR_STATE, "plan holds no cell records");
-  HIPCHK(hipSetDevice(pl->device));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  if (!pl->have_geom) return fg_fail(FG_ERR_STATE, "plan holds no cell records");
+  FGCHK(hipSetDevice(pl->device));
+  FGCHK(hipStreamSynchronize(pl->stream));
   FgCells tmp{};
   std::vector<void *> tmp_blocks;
   struct Free { std::vector<void *> &v; ~Free() { for (void *p : v) g_pool.put(p); } } free_tmp{tmp_blocks};
@@ -1725,22 +1710,22 @@ extern "C" int fg_plan_get_cell_struct(const fg_plan *pl, int which, double *lat
     tmp.lat_min = (double *)get(nd * 8); tmp.lat_max = (double *)get(nd * 8); tmp.lon_min = (double *)get(nd * 8);
     tmp.lon_max = (double *)get(nd * 8); tmp.lon_avg = (double *)get(nd * 8); tmp.nv = (int *)get(nd * 4); tmp.verts = (double *)get(nd * 128);
     tmp.area = pl->D.area;
-    if (tmp_blocks.size() != 7) return fail(FG_ERR_HIP, "out of device memory");
+    if (tmp_blocks.size() != 7) return fg_fail(FG_ERR_HIP, "out of device memory");
     FgRect R = pl->rect_tab;
     fgd_rect_materialize(pl->ndst, R, tmp, pl->stream);
-    HIPCHK(hipStreamSynchronize(pl->stream));
+    FGCHK(hipStreamSynchronize(pl->stream));
   }
   const FgCells &c = which ? (pl->rect ? tmp : pl->D) : pl->S;
   size_t n = which ? pl->ndst : pl->nsrc;
-  if (lat_min) HIPCHK(hipMemcpy(lat_min, c.lat_min, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (lat_max) HIPCHK(hipMemcpy(lat_max, c.lat_max, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (lon_min) HIPCHK(hipMemcpy(lon_min, c.lon_min, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (lon_max) HIPCHK(hipMemcpy(lon_max, c.lon_max, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (lon_avg) HIPCHK(hipMemcpy(lon_avg, c.lon_avg, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (nvert) HIPCHK(hipMemcpy(nvert, c.nv, n * sizeof(int), hipMemcpyDeviceToHost));
+  if (lat_min) FGCHK(hipMemcpy(lat_min, c.lat_min, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (lat_max) FGCHK(hipMemcpy(lat_max, c.lat_max, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (lon_min) FGCHK(hipMemcpy(lon_min, c.lon_min, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (lon_max) FGCHK(hipMemcpy(lon_max, c.lon_max, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (lon_avg) FGCHK(hipMemcpy(lon_avg, c.lon_avg, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (nvert) FGCHK(hipMemcpy(nvert, c.nv, n * sizeof(int), hipMemcpyDeviceToHost));
   if (vlon || vlat) {
     std::vector<double> v(n * 16);
-    HIPCHK(hipMemcpy(v.data(), c.verts, n * 16 * sizeof(double), hipMemcpyDeviceToHost));
+    FGCHK(hipMemcpy(v.data(), c.verts, n * 16 * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < n; k++)
       for (int l = 0; l < 8; l++) {
         if (vlon) vlon[k * 8 + l] = v[k * 16 + l];
@@ -1754,17 +1739,17 @@ extern "C" int fg_plan_set_xgrid(fg_plan *pl, long nxgrid, const int *t_in, cons
                                  const int *i_out, const int *j_out, const double *area,
                                  const double *di_in, const double *dj_in)
 {
-  if (!pl) return fail(FG_ERR_ARG, "null plan");
-  if (nxgrid < 0 || (nxgrid > 0 && (!t_in || !i_in || !j_in || !i_out || !j_out || !area))) return fail(FG_ERR_ARG, "null exchange-cell array");
-  if (pl->order == 2 && nxgrid > 0 && (!di_in || !dj_in)) return fail(FG_ERR_ARG, "order 2 needs di_in/dj_in");
-  if (pl->finalized || pl->searched) return fail(FG_ERR_STATE, "fg_plan_set_xgrid needs a plan from fg_plan_create_empty");
-  HIPCHK(hipSetDevice(pl->device));
+  if (!pl) return fg_fail(FG_ERR_ARG, "null plan");
+  if (nxgrid < 0 || (nxgrid > 0 && (!t_in || !i_in || !j_in || !i_out || !j_out || !area))) return fg_fail(FG_ERR_ARG, "null exchange-cell array");
+  if (pl->order == 2 && nxgrid > 0 && (!di_in || !dj_in)) return fg_fail(FG_ERR_ARG, "order 2 needs di_in/dj_in");
+  if (pl->finalized || pl->searched) return fg_fail(FG_ERR_STATE, "fg_plan_set_xgrid needs a plan from fg_plan_create_empty");
+  FGCHK(hipSetDevice(pl->device));
   std::vector<int> s(nxgrid), d(nxgrid);
   for (long k = 0; k < nxgrid; k++) {
     int m = t_in[k];
     if (m < 0 || m >= pl->ntiles || i_in[k] < 0 || i_in[k] >= pl->nx_in[m] || j_in[k] < 0 || j_in[k] >= pl->ny_in[m] ||
         i_out[k] < 0 || i_out[k] >= pl->nx_out || j_out[k] < 0 || j_out[k] >= pl->ny_out)
-      return fail(FG_ERR_ARG, "exchange cell %ld has an index outside its grid", k);
+      return fg_fail(FG_ERR_ARG, "exchange cell %ld has an index outside its grid", k);
     s[k] = pl->cell_off[m] + j_in[k] * pl->nx_in[m] + i_in[k];
     d[k] = j_out[k] * pl->nx_out + i_out[k];
   }
@@ -1772,14 +1757,14 @@ extern "C" int fg_plan_set_xgrid(fg_plan *pl, long nxgrid, const int *t_in, cons
   pl->x_src = pl->alloc<int>(nxgrid + 1); pl->x_dst = pl->alloc<int>(nxgrid + 1);
   pl->x_area = pl->alloc<double>(nxgrid + 1);
   if (pl->order == 2) { pl->x_c1 = pl->alloc<double>(nxgrid + 1); pl->x_c2 = pl->alloc<double>(nxgrid + 1); }
-  if (!pl->x_src || !pl->x_dst || !pl->x_area || (pl->order == 2 && (!pl->x_c1 || !pl->x_c2))) return fail(FG_ERR_HIP, "out of device memory");
+  if (!pl->x_src || !pl->x_dst || !pl->x_area || (pl->order == 2 && (!pl->x_c1 || !pl->x_c2))) return fg_fail(FG_ERR_HIP, "out of device memory");
   if (nxgrid > 0) {
-    HIPCHK(hipMemcpy(pl->x_src, s.data(), nxgrid * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pl->x_dst, d.data(), nxgrid * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pl->x_area, area, nxgrid * sizeof(double), hipMemcpyHostToDevice));
+    FGCHK(hipMemcpy(pl->x_src, s.data(), nxgrid * sizeof(int), hipMemcpyHostToDevice));
+    FGCHK(hipMemcpy(pl->x_dst, d.data(), nxgrid * sizeof(int), hipMemcpyHostToDevice));
+    FGCHK(hipMemcpy(pl->x_area, area, nxgrid * sizeof(double), hipMemcpyHostToDevice));
     if (pl->order == 2) {
-      HIPCHK(hipMemcpy(pl->x_c1, di_in, nxgrid * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(pl->x_c2, dj_in, nxgrid * sizeof(double), hipMemcpyHostToDevice));
+      FGCHK(hipMemcpy(pl->x_c1, di_in, nxgrid * sizeof(double), hipMemcpyHostToDevice));
+      FGCHK(hipMemcpy(pl->x_c2, dj_in, nxgrid * sizeof(double), hipMemcpyHostToDevice));
     }
   }
   pl->searched = true;
@@ -1817,7 +1802,7 @@ static int ensure_il_rs(fg_plan *pl)
 {
   if (!pl->il_rs) {
     pl->il_rs = pl->alloc<double>((size_t)pl->ndst * 16);
-    if (!pl->il_rs) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->il_rs) return fg_fail(FG_ERR_HIP, "out of device memory");
   }
   return 0;
 }
@@ -1828,7 +1813,7 @@ static int ensure_il_scratch(fg_plan *pl, bool want_rs)
     pl->il_out = pl->alloc<double>((size_t)pl->ndst * 8);
     if (pl->order == 2) pl->il_m = pl->alloc<double>((size_t)pl->nsrc * 24);
     else pl->il_f = pl->alloc<double>((size_t)pl->f_stride * 8);
-    if (!pl->il_out || (pl->order == 2 ? !pl->il_m : !pl->il_f)) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->il_out || (pl->order == 2 ? !pl->il_m : !pl->il_f)) return fg_fail(FG_ERR_HIP, "out of device memory");
   }
   return want_rs ? ensure_il_rs(pl) : 0;
 }
@@ -1846,22 +1831,22 @@ extern "C" int fg_plan_apply(fg_plan *pl, const double *data, const double *grad
                              const int *grad_mask, int has_missing, double missing, int nz,
                              double *out, double *gsum_out)
 {
-  if (!pl || !data || !out) return fail(FG_ERR_ARG, "null argument");
-  if (!pl->finalized) return fail(FG_ERR_STATE, "fg_plan_apply: call fg_plan_finalize first");
-  if (nz < 1) return fail(FG_ERR_ARG, "nz must be >= 1");
-  if (nz > 1 && has_missing) return fail(FG_ERR_ARG, "conserve_interp: has_missing should be false when nz > 1");
-  if (pl->order == 2 && (!grad_x || !grad_y)) return fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
-  if (pl->order == 2 && has_missing && !grad_mask) return fail(FG_ERR_ARG, "order 2 with missing values needs grad_mask");
-  HIPCHK(hipSetDevice(pl->device));
+  if (!pl || !data || !out) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->finalized) return fg_fail(FG_ERR_STATE, "fg_plan_apply: call fg_plan_finalize first");
+  if (nz < 1) return fg_fail(FG_ERR_ARG, "nz must be >= 1");
+  if (nz > 1 && has_missing) return fg_fail(FG_ERR_ARG, "conserve_interp: has_missing should be false when nz > 1");
+  if (pl->order == 2 && (!grad_x || !grad_y)) return fg_fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
+  if (pl->order == 2 && has_missing && !grad_mask) return fg_fail(FG_ERR_ARG, "order 2 with missing values needs grad_mask");
+  FGCHK(hipSetDevice(pl->device));
   hipStream_t st = pl->stream;
   const double miss = has_missing ? missing : -1.e20;            // conserve_interp.c:541-542
   const int ndst = pl->ndst;
   const int nchunk = (nz + 7) / 8;
-  if (nchunk > 256) return fail(FG_ERR_ARG, "nz too large for one call (max 2048 levels)");
+  if (nchunk > 256) return fg_fail(FG_ERR_ARG, "nz too large for one call (max 2048 levels)");
   if (gsum_out && pl->row_sum_cap < ndst) {
     pl->release(pl->row_sum);
     pl->row_sum = pl->alloc<double>(ndst);
-    if (!pl->row_sum) { pl->row_sum_cap = 0; return fail(FG_ERR_HIP, "out of device memory"); }
+    if (!pl->row_sum) { pl->row_sum_cap = 0; return fg_fail(FG_ERR_HIP, "out of device memory"); }
     pl->row_sum_cap = ndst;
   }
   if (nz > 1) { int rc = ensure_il_scratch(pl, gsum_out != nullptr); if (rc) return rc; }
@@ -1893,24 +1878,24 @@ extern "C" int fg_plan_apply(fg_plan *pl, const double *data, const double *grad
   apply_span_end(pl);
   if (gsum_out) {
     double parts[256];
-    HIPCHK(hipMemcpyAsync(parts, pl->red_result, nred * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    FGCHK(hipMemcpyAsync(parts, pl->red_result, nred * sizeof(double), hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));
     double g = 0;
     for (int k = 0; k < nred; k++) g += parts[k];
     *gsum_out = g;
   }
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
 // The order-2 sweep on records made by fg_c2l_gradient_records: no level-major detour, no merge pass.
 extern "C" int fg_plan_apply_records(fg_plan *pl, int nz, const double *rec, double *out, double *gsum_out)
 {
-  if (!pl || !rec || !out) return fail(FG_ERR_ARG, "null argument");
-  if (!pl->finalized) return fail(FG_ERR_STATE, "fg_plan_apply_records: call fg_plan_finalize first");
-  if (pl->order != 2) return fail(FG_ERR_ARG, "fg_plan_apply_records: records carry gradients, the plan is first order");
-  if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_plan_apply_records: 1 to 8 levels per call");
-  HIPCHK(hipSetDevice(pl->device));
+  if (!pl || !rec || !out) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->finalized) return fg_fail(FG_ERR_STATE, "fg_plan_apply_records: call fg_plan_finalize first");
+  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records: records carry gradients, the plan is first order");
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records: 1 to 8 levels per call");
+  FGCHK(hipSetDevice(pl->device));
   hipStream_t st = pl->stream;
   const int ndst = pl->ndst, nbp = levels_pad(nz);
   if (gsum_out) { int rc = ensure_il_rs(pl); if (rc) return rc; }
@@ -1919,10 +1904,10 @@ extern "C" int fg_plan_apply_records(fg_plan *pl, int nz, const double *rec, dou
   if (gsum_out) fgd_reduce_sum(pl->il_rs, (long)ndst * nbp, pl->red_partial, pl->red_result, st);
   apply_span_end(pl);
   if (gsum_out) {
-    HIPCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    FGCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));
   }
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
@@ -1938,7 +1923,7 @@ static int levels_scratch(fg_plan *pl, bool want_rs, bool want_il)
   if (want_il) { int rc = ensure_il_scratch(pl, false); if (rc) return rc; }
   if (want_il && pl->order == 2 && !pl->lv_bits) {
     pl->lv_bits = pl->alloc<unsigned char>(pl->nsrc > 0 ? pl->nsrc : 1);
-    if (!pl->lv_bits) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->lv_bits) return fg_fail(FG_ERR_HIP, "out of device memory");
   }
   return want_rs ? ensure_il_rs(pl) : 0;
 }
@@ -1949,8 +1934,8 @@ static int levels_gsum(fg_plan *pl, int nbv, int *nred, double **gsum_out, bool 
   hipStream_t st = pl->stream;
   for (int k = 0; k < nbv; k++) fgd_reduce_sum(pl->il_rs + (size_t)k * pl->ndst, pl->ndst, pl->red_partial, pl->red_result + (*nred)++, st);
   if (*nred + 8 > 256 || last) {
-    HIPCHK(hipMemcpyAsync(*gsum_out, pl->red_result, *nred * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    FGCHK(hipMemcpyAsync(*gsum_out, pl->red_result, *nred * sizeof(double), hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));
     *gsum_out += *nred; *nred = 0;
   }
   return 0;
@@ -1959,12 +1944,12 @@ static int levels_gsum(fg_plan *pl, int nbv, int *nred, double **gsum_out, bool 
 extern "C" int fg_plan_apply_levels(fg_plan *pl, const double *data, const double *grad_x, const double *grad_y,
                                     const int *grad_mask, double missing, int nlev, double *out, double *gsum_out)
 {
-  if (!pl || !data || !out) return fail(FG_ERR_ARG, "fg_plan_apply_levels: null argument");
-  if (!pl->finalized) return fail(FG_ERR_ARG, "fg_plan_apply_levels: the plan is not finalized (fg_plan_finalize)");
-  if (nlev < 1) return fail(FG_ERR_ARG, "fg_plan_apply_levels: nlev must be >= 1");
+  if (!pl || !data || !out) return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: null argument");
+  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: the plan is not finalized (fg_plan_finalize)");
+  if (nlev < 1) return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: nlev must be >= 1");
   if (pl->order == 2 && (!grad_x || !grad_y || !grad_mask))
-    return fail(FG_ERR_ARG, "fg_plan_apply_levels: order 2 needs grad_x, grad_y and grad_mask [nlev][ncells_in]");
-  HIPCHK(hipSetDevice(pl->device));
+    return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: order 2 needs grad_x, grad_y and grad_mask [nlev][ncells_in]");
+  FGCHK(hipSetDevice(pl->device));
   { int rc = levels_scratch(pl, gsum_out != nullptr, true); if (rc) return rc; }
   hipStream_t st = pl->stream;
   const int ndst = pl->ndst;
@@ -1987,68 +1972,68 @@ extern "C" int fg_plan_apply_levels(fg_plan *pl, const double *data, const doubl
     if (gsum_out) { int rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
   }
   apply_span_end(pl);
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int fg_plan_apply_records_levels(fg_plan *pl, int nz, const double *rec, const unsigned char *maskbits, double missing,
                                             double *out, double *gsum_out)
 {
-  if (!pl || !rec || !out) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: null argument");
-  if (!pl->finalized) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: the plan is not finalized (fg_plan_finalize)");
-  if (pl->order != 2) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: records carry gradients, the plan is first order");
-  if (!maskbits) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: order 2 needs the gradient-mask bits");
-  if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_plan_apply_records_levels: 1 to 8 levels per call");
-  HIPCHK(hipSetDevice(pl->device));
+  if (!pl || !rec || !out) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: null argument");
+  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: the plan is not finalized (fg_plan_finalize)");
+  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: records carry gradients, the plan is first order");
+  if (!maskbits) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: order 2 needs the gradient-mask bits");
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: 1 to 8 levels per call");
+  FGCHK(hipSetDevice(pl->device));
   { int rc = levels_scratch(pl, gsum_out != nullptr, false); if (rc) return rc; }
   hipStream_t st = pl->stream;
   apply_span_begin(pl, st);
   fgd_apply_levels8(2, pl->ndst, pl->nx, pl->csr, rec, maskbits, missing, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, st);
   apply_span_end(pl);
   if (gsum_out) { int nred = 0; int rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
 // ------------------------------------------------------------------- the sweep with every option
 static int ex_check(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *gx, const double *gy, int nz, const char *who)
 {
-  if (!pl || !o || !data) return fail(FG_ERR_ARG, "%s: null argument", who);
-  if (!pl->finalized) return fail(FG_ERR_STATE, "%s: call fg_plan_finalize first", who);
-  if (nz < 1) return fail(FG_ERR_ARG, "nz must be >= 1");
-  if (nz > 1 && o->has_missing) return fail(FG_ERR_ARG, "conserve_interp: has_missing should be false when nz > 1");
-  if (nz > 1 && o->field_area) return fail(FG_ERR_ARG, "conserve_interp: cell_measures should be false when nz > 1");
-  if (nz > 1 && o->cell_methods_sum) return fail(FG_ERR_ARG, "conserve_interp: cell_methods should not be sum when nz > 1");
-  if (pl->order == 2 && (!gx || !gy)) return fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
+  if (!pl || !o || !data) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!pl->finalized) return fg_fail(FG_ERR_STATE, "%s: call fg_plan_finalize first", who);
+  if (nz < 1) return fg_fail(FG_ERR_ARG, "nz must be >= 1");
+  if (nz > 1 && o->has_missing) return fg_fail(FG_ERR_ARG, "conserve_interp: has_missing should be false when nz > 1");
+  if (nz > 1 && o->field_area) return fg_fail(FG_ERR_ARG, "conserve_interp: cell_measures should be false when nz > 1");
+  if (nz > 1 && o->cell_methods_sum) return fg_fail(FG_ERR_ARG, "conserve_interp: cell_methods should not be sum when nz > 1");
+  if (pl->order == 2 && (!gx || !gy)) return fg_fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
   if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
-    return fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
+    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
   return 0;
 }
 
 static int ex_error_word(fg_plan *pl)
 {
   int e = 0;
-  HIPCHK(hipMemcpyAsync(&e, pl->xerr, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
-  HIPCHK(hipStreamSynchronize(pl->stream));
-  if (e & FG_XERR_AREA_MISSING) return fail(FG_ERR_DATA, "conserve_interp: data is not missing but area is missing");
-  if (e & FG_XERR_ABOVE) return fail(FG_ERR_DATA, " xdata is greater than f_bar_max ");
-  if (e & FG_XERR_BELOW) return fail(FG_ERR_DATA, " xdata is less than f_bar_min ");
+  FGCHK(hipMemcpyAsync(&e, pl->xerr, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
+  FGCHK(hipStreamSynchronize(pl->stream));
+  if (e & FG_XERR_AREA_MISSING) return fg_fail(FG_ERR_DATA, "conserve_interp: data is not missing but area is missing");
+  if (e & FG_XERR_ABOVE) return fg_fail(FG_ERR_DATA, " xdata is greater than f_bar_max ");
+  if (e & FG_XERR_BELOW) return fg_fail(FG_ERR_DATA, " xdata is less than f_bar_min ");
   return 0;
 }
 
 static int ex_scratch(fg_plan *pl, bool mono)
 {
-  if (!pl->xerr) { pl->xerr = pl->alloc<int>(4); if (!pl->xerr) return fail(FG_ERR_HIP, "out of device memory"); }
+  if (!pl->xerr) { pl->xerr = pl->alloc<int>(4); if (!pl->xerr) return fg_fail(FG_ERR_HIP, "out of device memory"); }
   if (pl->row_sum_cap < pl->ndst) {
     pl->release(pl->row_sum);
     pl->row_sum = pl->alloc<double>(pl->ndst);
-    if (!pl->row_sum) { pl->row_sum_cap = 0; return fail(FG_ERR_HIP, "out of device memory"); }
+    if (!pl->row_sum) { pl->row_sum_cap = 0; return fg_fail(FG_ERR_HIP, "out of device memory"); }
     pl->row_sum_cap = pl->ndst;
   }
   if (mono && !pl->mono_x) {
     pl->mono_x = pl->alloc<double>(pl->nx > 0 ? pl->nx : 1);
     pl->mono_b = pl->alloc<double>((size_t)pl->nsrc * 4);
-    if (!pl->mono_x || !pl->mono_b) return fail(FG_ERR_HIP, "out of device memory");
+    if (!pl->mono_x || !pl->mono_b) return fg_fail(FG_ERR_HIP, "out of device memory");
   }
   return 0;
 }
@@ -2069,23 +2054,23 @@ extern "C" int fg_plan_mono_begin(fg_plan *pl, const fg_apply_opts *o, const dou
 {
   int rc = ex_check(pl, o, data, grad_x, grad_y, 1, "fg_plan_mono_begin");
   if (rc) return rc;
-  if (pl->order != 2) return fail(FG_ERR_ARG, "the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)");
-  HIPCHK(hipSetDevice(pl->device));
+  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)");
+  FGCHK(hipSetDevice(pl->device));
   if ((rc = ex_scratch(pl, true))) return rc;
   const double miss = o->has_missing ? o->missing : -1.e20;
   double *b = pl->mono_b;
   const size_t n = pl->nsrc;
-  HIPCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
+  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
   fgd_mono_bounds(pl->tiles_dev, pl->ntiles, pl->nsrc, pl->src_idx_f, data, miss, b, b + n, b + 2 * n, b + 3 * n, pl->stream);
   fgd_mono_xdata(pl->nx, pl->csr, data, grad_x, grad_y, grad_mask, miss, pl->mono_x, b + 2 * n, b + 3 * n, pl->stream);
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   pl->mono_open = true;
   return 0;
 }
 
 extern "C" int fg_plan_mono_minmax_dev(fg_plan *pl, double **f_min, double **f_max)
 {
-  if (!pl || !pl->mono_open) return fail(FG_ERR_STATE, "fg_plan_mono_minmax_dev: call fg_plan_mono_begin first");
+  if (!pl || !pl->mono_open) return fg_fail(FG_ERR_STATE, "fg_plan_mono_minmax_dev: call fg_plan_mono_begin first");
   if (f_max) *f_max = pl->mono_b + 2 * (size_t)pl->nsrc;
   if (f_min) *f_min = pl->mono_b + 3 * (size_t)pl->nsrc;
   return 0;
@@ -2093,21 +2078,21 @@ extern "C" int fg_plan_mono_minmax_dev(fg_plan *pl, double **f_min, double **f_m
 
 extern "C" int fg_plan_mono_copy_minmax(fg_plan *pl, int to_plan, double *f_min, double *f_max)
 {
-  if (!pl || !pl->mono_open || !f_min || !f_max) return fail(FG_ERR_STATE, "fg_plan_mono_copy_minmax: call fg_plan_mono_begin first");
-  HIPCHK(hipSetDevice(pl->device));
+  if (!pl || !pl->mono_open || !f_min || !f_max) return fg_fail(FG_ERR_STATE, "fg_plan_mono_copy_minmax: call fg_plan_mono_begin first");
+  FGCHK(hipSetDevice(pl->device));
   double *mx = pl->mono_b + 2 * (size_t)pl->nsrc, *mn = pl->mono_b + 3 * (size_t)pl->nsrc;
   const size_t bytes = (size_t)pl->nsrc * sizeof(double);
-  HIPCHK(hipMemcpyAsync(to_plan ? mn : f_min, to_plan ? f_min : mn, bytes, hipMemcpyDeviceToDevice, pl->stream));
-  HIPCHK(hipMemcpyAsync(to_plan ? mx : f_max, to_plan ? f_max : mx, bytes, hipMemcpyDeviceToDevice, pl->stream));
-  HIPCHK(hipStreamSynchronize(pl->stream));
+  FGCHK(hipMemcpyAsync(to_plan ? mn : f_min, to_plan ? f_min : mn, bytes, hipMemcpyDeviceToDevice, pl->stream));
+  FGCHK(hipMemcpyAsync(to_plan ? mx : f_max, to_plan ? f_max : mx, bytes, hipMemcpyDeviceToDevice, pl->stream));
+  FGCHK(hipStreamSynchronize(pl->stream));
   return 0;
 }
 
 extern "C" int fg_plan_mono_end(fg_plan *pl, const fg_apply_opts *o, const double *data, double *out, double *gsum_out)
 {
-  if (!pl || !o || !data || !out) return fail(FG_ERR_ARG, "null argument");
-  if (!pl->mono_open) return fail(FG_ERR_STATE, "fg_plan_mono_end: call fg_plan_mono_begin first");
-  HIPCHK(hipSetDevice(pl->device));
+  if (!pl || !o || !data || !out) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->mono_open) return fg_fail(FG_ERR_STATE, "fg_plan_mono_end: call fg_plan_mono_begin first");
+  FGCHK(hipSetDevice(pl->device));
   pl->mono_open = false;
   const double miss = o->has_missing ? o->missing : -1.e20;
   double *b = pl->mono_b;
@@ -2118,9 +2103,9 @@ extern "C" int fg_plan_mono_end(fg_plan *pl, const fg_apply_opts *o, const doubl
   fgd_apply_ex(2, pl->ndst, pl->csr, data, nullptr, nullptr, x, out, gsum_out ? pl->row_sum : nullptr, pl->xerr, pl->stream, pl->nx);
   if (gsum_out) {
     fgd_reduce_sum(pl->row_sum, pl->ndst, pl->red_partial, pl->red_result, pl->stream);
-    HIPCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+    FGCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, pl->stream));
   }
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return ex_error_word(pl);
 }
 
@@ -2129,17 +2114,17 @@ extern "C" int fg_plan_apply_ex(fg_plan *pl, const fg_apply_opts *o, const doubl
 {
   int rc = ex_check(pl, o, data, grad_x, grad_y, nz, "fg_plan_apply_ex");
   if (rc) return rc;
-  if (!out) return fail(FG_ERR_ARG, "null argument");
+  if (!out) return fg_fail(FG_ERR_ARG, "null argument");
   if (o->monotonic && pl->order == 2) {
-    if (nz != 1) return fail(FG_ERR_ARG, "the monotone limiter works on one level per call (conserve_interp.c:648-651 index level 0 only)");
+    if (nz != 1) return fg_fail(FG_ERR_ARG, "the monotone limiter works on one level per call (conserve_interp.c:648-651 index level 0 only)");
     if ((rc = fg_plan_mono_begin(pl, o, data, grad_x, grad_y, grad_mask))) return rc;
     return fg_plan_mono_end(pl, o, data, out, gsum_out);
   }
-  HIPCHK(hipSetDevice(pl->device));
+  FGCHK(hipSetDevice(pl->device));
   if ((rc = ex_scratch(pl, false))) return rc;
-  if (nz > 256) return fail(FG_ERR_ARG, "nz too large for one call (max 256 levels)");
+  if (nz > 256) return fg_fail(FG_ERR_ARG, "nz too large for one call (max 256 levels)");
   hipStream_t st = pl->stream;
-  HIPCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
+  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
   FgApplyEx x = ex_pack(pl, o, grad_mask);
   for (int k = 0; k < nz; k++) {
     fgd_apply_ex(pl->order, pl->ndst, pl->csr, data + (size_t)k * pl->f_stride, grad_x ? grad_x + (size_t)k * pl->nsrc : nullptr,
@@ -2147,11 +2132,11 @@ extern "C" int fg_plan_apply_ex(fg_plan *pl, const fg_apply_opts *o, const doubl
                  gsum_out ? pl->row_sum : nullptr, pl->xerr, st, pl->nx);
     if (gsum_out) fgd_reduce_sum(pl->row_sum, pl->ndst, pl->red_partial, pl->red_result + k, st);
   }
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   if (gsum_out) {
     double parts[256];
-    HIPCHK(hipMemcpyAsync(parts, pl->red_result, nz * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    FGCHK(hipMemcpyAsync(parts, pl->red_result, nz * sizeof(double), hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));
     double g = 0;
     for (int k = 0; k < nz; k++) g += parts[k];
     *gsum_out = g;
@@ -2164,11 +2149,11 @@ extern "C" int fg_plan_apply_ex(fg_plan *pl, const fg_apply_opts *o, const doubl
 extern "C" int fg_plan_apply_interleaved(fg_plan *pl, int nb, const double *data_il, const double *grad_x_il,
                                          const double *grad_y_il, double *out_il, double *gsum_out)
 {
-  if (!pl || !data_il || !out_il) return fail(FG_ERR_ARG, "null argument");
-  if (!pl->finalized) return fail(FG_ERR_STATE, "fg_plan_apply_interleaved: call fg_plan_finalize first");
-  if (nb != 2 && nb != 4 && nb != 8 && nb != 16) return fail(FG_ERR_ARG, "nb must be 2, 4, 8 or 16");
-  if (pl->order == 2 && (!grad_x_il || !grad_y_il)) return fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
-  HIPCHK(hipSetDevice(pl->device));
+  if (!pl || !data_il || !out_il) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->finalized) return fg_fail(FG_ERR_STATE, "fg_plan_apply_interleaved: call fg_plan_finalize first");
+  if (nb != 2 && nb != 4 && nb != 8 && nb != 16) return fg_fail(FG_ERR_ARG, "nb must be 2, 4, 8 or 16");
+  if (pl->order == 2 && (!grad_x_il || !grad_y_il)) return fg_fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
+  FGCHK(hipSetDevice(pl->device));
   if (gsum_out) { int rc = ensure_il_scratch(pl, true); if (rc) return rc; }
   apply_span_begin(pl, pl->stream);
   fgd_apply_il(pl->order, nb, pl->ndst, pl->csr, data_il, grad_x_il, grad_y_il, -1.e20, out_il,
@@ -2176,10 +2161,10 @@ extern "C" int fg_plan_apply_interleaved(fg_plan *pl, int nb, const double *data
   apply_span_end(pl);
   if (gsum_out) {
     fgd_reduce_sum(pl->il_rs, (long)pl->ndst * nb, pl->red_partial, pl->red_result, pl->stream);
-    HIPCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, pl->stream));
-    HIPCHK(hipStreamSynchronize(pl->stream));
+    FGCHK(hipMemcpyAsync(gsum_out, pl->red_result, sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+    FGCHK(hipStreamSynchronize(pl->stream));
   }
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
@@ -2198,12 +2183,6 @@ static void fatal(const char *msg)
 extern "C" int get_maxxgrid(void) { return MAXXGRID; }
 extern "C" int get_maxxgrid_(void) { return get_maxxgrid(); }
 
-static int b1_device(void)
-{
-  const char *e = getenv("FREGRID_HIP_DEVICE");
-  return e ? atoi(e) : 0;
-}
-
 // get_grid_area / get_grid_great_circle_area: the source records of a plan against a 1x1 dummy destination, which keeps the plan
 // machinery uniform
 static void b1_grid_area(bool great_circle, const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
@@ -2212,8 +2191,8 @@ static void b1_grid_area(bool great_circle, const int *nlon, const int *nlat, co
   const double dl[4] = {0, 0.01, 0, 0.01}, da[4] = {0, 0, 0.01, 0.01};
   const double *lons[1] = {lon}, *lats[1] = {lat};
   fg_plan *pl = nullptr;
-  long rc = great_circle ? fg_plan_create_great_circle(1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, b1_device(), &pl)
-                         : fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, b1_device(), &pl);
+  long rc = great_circle ? fg_plan_create_great_circle(1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, fg_env_device(), &pl)
+                         : fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx, &ny, lons, lats, nullptr, one, one, dl, da, fg_env_device(), &pl);
   if (rc < 0) fatal(fg_last_error());
   if (fg_plan_get_cell_area(pl, area, nullptr)) fatal(fg_last_error());
   fg_plan_destroy(pl);
@@ -2235,7 +2214,7 @@ extern "C" int create_xgrid_great_circle(const int *nlon_in, const int *nlat_in,
   int nx1 = *nlon_in, ny1 = *nlat_in;
   const double *lons[1] = {lon_in}, *lats[1] = {lat_in}, *masks[1] = {mask_in};
   fg_plan *pl = nullptr;
-  long nx = fg_plan_create_great_circle(1, &nx1, &ny1, lons, lats, masks, *nlon_out, *nlat_out, lon_out, lat_out, b1_device(), &pl);
+  long nx = fg_plan_create_great_circle(1, &nx1, &ny1, lons, lats, masks, *nlon_out, *nlat_out, lon_out, lat_out, fg_env_device(), &pl);
   if (nx < 0) fatal(fg_last_error());
   if (nx > (long)MAXXGRID) fatal("nxgrid is greater than MAXXGRID, increase MAXXGRID");      // create_xgrid.c:1444
   if (fg_plan_get_xgrid(pl, nullptr, i_in, j_in, i_out, j_out, xgrid_area, nullptr, nullptr)) fatal(fg_last_error());
@@ -2263,16 +2242,13 @@ extern "C" void get_grid_great_circle_area_(const int *nlon, const int *nlat, co
 
 extern "C" int fg_gc_clip_batch(int npairs, const double *a, const double *b, double *out, int *n_out, double *area, int device)
 {
-  if (npairs < 0 || !a || !b || !out || !n_out || !area) return fail(FG_ERR_ARG, "null argument");
+  if (npairs < 0 || !a || !b || !out || !n_out || !area) return fg_fail(FG_ERR_ARG, "null argument");
   if (npairs == 0) return 0;
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  HIPCHK(hipSetDevice(device));
+  if (int rc = fg_use_device("fg_gc_clip_batch", device)) return rc;
   const size_t na = (size_t)npairs * 12, no = (size_t)npairs * FG_GC_POLY_CAP * 3;
   double *d_a = (double *)g_pool.get(device, (2 * na + no + npairs) * sizeof(double));
   int *d_n = (int *)g_pool.get(device, (size_t)npairs * sizeof(int));
-  if (!d_a || !d_n) { if (d_a) g_pool.put(d_a); if (d_n) g_pool.put(d_n); return fail(FG_ERR_HIP, "out of device memory"); }
+  if (!d_a || !d_n) { if (d_a) g_pool.put(d_a); if (d_n) g_pool.put(d_n); return fg_fail(FG_ERR_HIP, "out of device memory"); }
   double *d_b = d_a + na, *d_o = d_b + na, *d_ar = d_o + no;
   int rc = 0;
   if (hipMemcpy(d_a, a, na * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
@@ -2284,7 +2260,7 @@ extern "C" int fg_gc_clip_batch(int npairs, const double *a, const double *b, do
         hipMemcpy(area, d_ar, (size_t)npairs * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = FG_ERR_HIP;
   }
   g_pool.put(d_a); g_pool.put(d_n);
-  if (rc) return fail(rc, "fg_gc_clip_batch: HIP copy/launch failed: %s", hipGetErrorString(hipGetLastError()));
+  if (rc) return fg_fail(rc, "fg_gc_clip_batch: HIP copy/launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;
 }
 
@@ -2293,8 +2269,8 @@ extern "C" double great_circle_area(int n, const double *x, const double *y, con
   if (n < 1 || n > 64) fatal("great_circle_area (HIP): 1 <= n <= 64");
   double h[64 * 3], area = 0;
   for (int k = 0; k < n; k++) { h[k * 3] = x[k]; h[k * 3 + 1] = y[k]; h[k * 3 + 2] = z[k]; }
-  if (hipSetDevice(b1_device()) != hipSuccess) fatal("no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  double *d = (double *)g_pool.get(b1_device(), (64 * 3 + 2) * sizeof(double));
+  if (hipSetDevice(fg_env_device()) != hipSuccess) fatal("no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
+  double *d = (double *)g_pool.get(fg_env_device(), (64 * 3 + 2) * sizeof(double));
   if (!d) fatal("out of device memory");
   int *dn = (int *)(d + 64 * 3 + 1);
   bool ok = hipMemcpy(d, h, n * 3 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
@@ -2311,14 +2287,11 @@ extern "C" double great_circle_area(int n, const double *x, const double *y, con
 // sin / cos of n host values with the device's latitude trig (sincos_glibc.h): parity probe for the tests
 extern "C" int fg_sincos_batch(long n, const double *x, double *s, double *c, int device)
 {
-  if (n < 0 || !x || !s || !c) return fail(FG_ERR_ARG, "null argument");
+  if (n < 0 || !x || !s || !c) return fg_fail(FG_ERR_ARG, "null argument");
   if (n == 0) return 0;
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  HIPCHK(hipSetDevice(device));
+  if (int rc = fg_use_device("fg_sincos_batch", device)) return rc;
   double *d = (double *)g_pool.get(device, 3 * (size_t)n * sizeof(double));
-  if (!d) return fail(FG_ERR_HIP, "out of device memory");
+  if (!d) return fg_fail(FG_ERR_HIP, "out of device memory");
   bool ok = hipMemcpy(d, x, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok) {
     fgd_sincos_probe(n, d, d + n, d + 2 * n, nullptr);
@@ -2326,7 +2299,7 @@ extern "C" int fg_sincos_batch(long n, const double *x, double *s, double *c, in
          hipMemcpy(c, d + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
   }
   g_pool.put(d);
-  if (!ok) return fail(FG_ERR_HIP, "fg_sincos_batch: HIP copy/launch failed");
+  if (!ok) return fg_fail(FG_ERR_HIP, "fg_sincos_batch: HIP copy/launch failed");
   return 0;
 }
 
@@ -2342,7 +2315,7 @@ extern "C" int clip_2dx2d_great_circle(const double x1_in[], const double y1_in[
     a[k * 3] = x1_in[k]; a[k * 3 + 1] = y1_in[k]; a[k * 3 + 2] = z1_in[k];
     b[k * 3] = x2_in[k]; b[k * 3 + 1] = y2_in[k]; b[k * 3 + 2] = z2_in[k];
   }
-  if (fg_gc_clip_batch(1, a, b, out, &n_out, &area, b1_device())) fatal(fg_last_error());
+  if (fg_gc_clip_batch(1, a, b, out, &n_out, &area, fg_env_device())) fatal(fg_last_error());
   if (n_out == -1) fatal("create_xgrid.c(clip_2dx2d_great_circle): grid box 1 is not convex");
   if (n_out == -2) fatal("create_xgrid.c(clip_2dx2d_great_circle): grid box 2 is not convex");
   if (n_out < 0) fatal(gc_clip_error(-n_out));
@@ -2356,7 +2329,7 @@ long fg_box_xgrid_lists(int dev, int box_is_src, int order, int nxb, int nyb, co
                         int nxq, int nyq, const double *lon_q, const double *lat_q, const double *mask,
                         std::vector<int> idx[4], std::vector<double> &area, std::vector<double> *clon, std::vector<double> *clat)
 {
-  if (nxb < 1 || nyb < 1 || nxq < 1 || nyq < 1) return fail(FG_ERR_ARG, "create_xgrid: bad grid sizes");
+  if (nxb < 1 || nyb < 1 || nxq < 1 || nyq < 1) return fg_fail(FG_ERR_ARG, "create_xgrid: bad grid sizes");
   fg_plan *pl = nullptr;
   int rc = plan_base(order, 1, &nxb, &nyb, nxq, nyq, dev, &pl);
   if (rc) return rc;
@@ -2365,7 +2338,7 @@ long fg_box_xgrid_lists(int dev, int box_is_src, int order, int nxb, int nyb, co
   for (int j = 0; j <= nyb; j++) for (int i = 0; i <= nxb; i++) { tx[(size_t)j * (nxb + 1) + i] = lon_b[i]; ty[(size_t)j * (nxb + 1) + i] = lat_b[j]; }
   const size_t nmask = box_is_src ? (size_t)nxb * nyb : (size_t)nxq * nyq;
   double *d = pl->alloc<double>(2 * npb + 2 * npq + (nxb + 1) + (nyb + 1) + nmask);
-  if (!d) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "out of device memory"); }
+  if (!d) { fg_plan_destroy(pl); return fg_fail(FG_ERR_HIP, "out of device memory"); }
   double *d_tx = d, *d_ty = d_tx + npb, *d_lq = d_ty + npb, *d_aq = d_lq + npq, *d_lb = d_aq + npq, *d_ab = d_lb + (nxb + 1), *d_mask = d_ab + (nyb + 1);
   bool ok = hipMemcpy(d_tx, tx.data(), npb * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(d_ty, ty.data(), npb * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
@@ -2374,7 +2347,7 @@ long fg_box_xgrid_lists(int dev, int box_is_src, int order, int nxb, int nyb, co
             hipMemcpy(d_lb, lon_b, (nxb + 1) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(d_ab, lat_b, (nyb + 1) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(d_mask, mask, nmask * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { fg_plan_destroy(pl); return fail(FG_ERR_HIP, "grid upload failed"); }
+  if (!ok) { fg_plan_destroy(pl); return fg_fail(FG_ERR_HIP, "grid upload failed"); }
   BoxMode bm;
   bm.box = FgBox{d_lb, d_ab, nxb, nyb};
   bm.mask_quad = box_is_src ? nullptr : d_mask;
@@ -2384,7 +2357,7 @@ long fg_box_xgrid_lists(int dev, int box_is_src, int order, int nxb, int nyb, co
   long nx = plan_search(pl, SearchIn{.lon_in = lons, .lat_in = lats, .mask_in = box_is_src ? masks : nullptr, .lon_out = d_lq, .lat_out = d_aq,
                                      .boxm = &bm, .mean_dlat = x.dlat, .mean_dlon = x.dlon});
   if (nx < 0) { fg_plan_destroy(pl); return nx; }
-  if (nx > (long)MAXXGRID) { fg_plan_destroy(pl); return fail(FG_ERR_CAPACITY, "nxgrid is greater than MAXXGRID, increase MAXXGRID"); }
+  if (nx > (long)MAXXGRID) { fg_plan_destroy(pl); return fg_fail(FG_ERR_CAPACITY, "nxgrid is greater than MAXXGRID, increase MAXXGRID"); }
   for (int k = 0; k < 4; k++) idx[k].resize(nx);
   area.resize(nx);
   if (order == 2) { clon->resize(nx); clat->resize(nx); }
@@ -2400,7 +2373,7 @@ static int b1_create_xgrid_box(int box_is_src, int order, int nxb, int nyb, cons
 {
   std::vector<int> idx[4];
   std::vector<double> area, clon, clat;
-  const long nx = fg_box_xgrid_lists(b1_device(), box_is_src, order, nxb, nyb, lon_b, lat_b, nxq, nyq, lon_q, lat_q, mask, idx, area, &clon, &clat);
+  const long nx = fg_box_xgrid_lists(fg_env_device(), box_is_src, order, nxb, nyb, lon_b, lat_b, nxq, nyq, lon_q, lat_q, mask, idx, area, &clon, &clat);
   if (nx < 0) fatal(fg_last_error());
   const size_t ni = (size_t)nx * sizeof(int), nd = (size_t)nx * sizeof(double);
   memcpy(box_is_src ? i_in : i_out, idx[0].data(), ni); memcpy(box_is_src ? j_in : j_out, idx[1].data(), ni);
@@ -2415,7 +2388,7 @@ extern "C" int clip(const double lon_in[], const double lat_in[], int n_in, doub
                     double lon_out[], double lat_out[])
 {
   if (n_in < 1 || n_in > 12) fatal("clip (HIP): 1 <= n_in <= 12");
-  const int dev = b1_device();
+  const int dev = fg_env_device();
   if (hipSetDevice(dev) != hipSuccess) fatal("no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
   double *d = (double *)g_pool.get(dev, (4 * 16 + 2) * sizeof(double));
   if (!d) fatal("out of device memory");
@@ -2437,7 +2410,7 @@ extern "C" int clip(const double lon_in[], const double lat_in[], int n_in, doub
 
 static void b1_box_ctr(double ll_lon, double ll_lat, double ur_lon, double ur_lat, double clon, double out[2])
 {
-  const int dev = b1_device();
+  const int dev = fg_env_device();
   if (hipSetDevice(dev) != hipSuccess) fatal("no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
   double *d = (double *)g_pool.get(dev, 2 * sizeof(double));
   if (!d) fatal("out of device memory");
@@ -2457,7 +2430,7 @@ extern "C" double box_ctrlon(double ll_lon, double ll_lat, double ur_lon, double
 
 extern "C" void get_grid_area_no_adjust(const int *nlon, const int *nlat, const double *lon, const double *lat, double *area)
 {
-  const int nx = *nlon, ny = *nlat, dev = b1_device();
+  const int nx = *nlon, ny = *nlat, dev = fg_env_device();
   if (nx < 1 || ny < 1) fatal("get_grid_area_no_adjust: bad grid sizes");
   if (hipSetDevice(dev) != hipSuccess) fatal("no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
   const size_t np = (size_t)(nx + 1) * (ny + 1), nc = (size_t)nx * ny;
@@ -2508,7 +2481,7 @@ static int b1_create_xgrid(int order, const int *nlon_in, const int *nlat_in, co
   int nx1 = *nlon_in, ny1 = *nlat_in;
   const double *lons[1] = {lon_in}, *lats[1] = {lat_in}, *masks[1] = {mask_in};
   fg_plan *pl = nullptr;
-  long nx = fg_plan_create(order, 1, &nx1, &ny1, lons, lats, masks, *nlon_out, *nlat_out, lon_out, lat_out, b1_device(), &pl);
+  long nx = fg_plan_create(order, 1, &nx1, &ny1, lons, lats, masks, *nlon_out, *nlat_out, lon_out, lat_out, fg_env_device(), &pl);
   if (nx < 0) fatal(fg_last_error());
   if (nx >= (long)MAXXGRID)                                     // create_xgrid.c:1087-1088
     fatal("nxgrid is greater than MAXXGRID/nthreads, increase MAXXGRID, decrease nthreads, or increase number of MPI ranks");
@@ -2547,8 +2520,8 @@ extern "C" int create_xgrid_2dx2d_order2_(const int *a, const int *b, const int 
 static int plan_apply_frac(fg_plan *pl, const double *data, double *out)
 {
   fgd_apply_frac(pl->ndst, pl->csr, data, out, pl->stream);
-  HIPCHK(hipStreamSynchronize(pl->stream));
-  HIPCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(pl->stream));
+  FGCHK(hipGetLastError());
   return 0;
 }
 
@@ -2560,8 +2533,8 @@ static void b1_conserve_interp(bool great_circle, int nx_src, int ny_src, int nx
 {
   const double *lons[1] = {x_src}, *lats[1] = {y_src}, *masks[1] = {mask_src};
   fg_plan *pl = nullptr;
-  long nx = great_circle ? fg_plan_create_great_circle(1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, b1_device(), &pl)
-                         : fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, b1_device(), &pl);
+  long nx = great_circle ? fg_plan_create_great_circle(1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, fg_env_device(), &pl)
+                         : fg_plan_create(FG_CONSERVE_ORDER1, 1, &nx_src, &ny_src, lons, lats, masks, nx_dst, ny_dst, x_dst, y_dst, fg_env_device(), &pl);
   if (nx < 0) fatal(fg_last_error());
   if (great_circle && nx > (long)MAXXGRID) fatal("nxgrid is greater than MAXXGRID, increase MAXXGRID");
   if (!great_circle && nx >= (long)MAXXGRID)
@@ -2606,20 +2579,20 @@ extern "C" int fg_clip_2dx2d_batch(int npoly, const double *lon1, const double *
                                    const double *lon2, const double *lat2, const int *n2,
                                    double *lon_out, double *lat_out, int *n_out)
 {
-  if (npoly < 0 || !lon1 || !lat1 || !n1 || !lon2 || !lat2 || !n2 || !lon_out || !lat_out || !n_out) return fail(FG_ERR_ARG, "null argument");
+  if (npoly < 0 || !lon1 || !lat1 || !n1 || !lon2 || !lat2 || !n2 || !lon_out || !lat_out || !n_out) return fg_fail(FG_ERR_ARG, "null argument");
   if (npoly == 0) return 0;
-  HIPCHK(hipSetDevice(b1_device()));
+  FGCHK(hipSetDevice(fg_env_device()));
   size_t nb = (size_t)npoly * FG_POLY_STRIDE * sizeof(double), ni = (size_t)npoly * sizeof(int);
   DevBuf a(nb), b(nb), c(nb), d(nb), xo(nb), yo(nb), m1(ni), m2(ni), mo(ni);
-  if (!a.p || !b.p || !c.p || !d.p || !xo.p || !yo.p || !m1.p || !m2.p || !mo.p) return fail(FG_ERR_HIP, "out of device memory");
-  HIPCHK(hipMemcpy(a.p, lon1, nb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(b.p, lat1, nb, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(c.p, lon2, nb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d.p, lat2, nb, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(m1.p, n1, ni, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(m2.p, n2, ni, hipMemcpyHostToDevice));
+  if (!a.p || !b.p || !c.p || !d.p || !xo.p || !yo.p || !m1.p || !m2.p || !mo.p) return fg_fail(FG_ERR_HIP, "out of device memory");
+  FGCHK(hipMemcpy(a.p, lon1, nb, hipMemcpyHostToDevice)); FGCHK(hipMemcpy(b.p, lat1, nb, hipMemcpyHostToDevice));
+  FGCHK(hipMemcpy(c.p, lon2, nb, hipMemcpyHostToDevice)); FGCHK(hipMemcpy(d.p, lat2, nb, hipMemcpyHostToDevice));
+  FGCHK(hipMemcpy(m1.p, n1, ni, hipMemcpyHostToDevice)); FGCHK(hipMemcpy(m2.p, n2, ni, hipMemcpyHostToDevice));
   fgd_poly_clip(npoly, (double *)a.p, (double *)b.p, (int *)m1.p, (double *)c.p, (double *)d.p, (int *)m2.p,
                 (double *)xo.p, (double *)yo.p, (int *)mo.p, 0);
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(lon_out, xo.p, nb, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(lat_out, yo.p, nb, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(n_out, mo.p, ni, hipMemcpyDeviceToHost));
+  FGCHK(hipDeviceSynchronize());
+  FGCHK(hipMemcpy(lon_out, xo.p, nb, hipMemcpyDeviceToHost)); FGCHK(hipMemcpy(lat_out, yo.p, nb, hipMemcpyDeviceToHost));
+  FGCHK(hipMemcpy(n_out, mo.p, ni, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2627,23 +2600,23 @@ extern "C" int fg_clip_2dx2d_batch(int npoly, const double *lon1, const double *
 // 4, 5, 6: area, ctrlon(clon), ctrlat as the clip kernels' fused integrals routine computes them.
 extern "C" int fg_poly_op_batch(int op, int npoly, double *lon, double *lat, int *n, const double *clon, double *result)
 {
-  if (op < 0 || op > 6 || npoly < 0 || !lon || !lat || !n) return fail(FG_ERR_ARG, "bad argument");
-  if ((op == 1 || op == 3 || op == 5) && !clon) return fail(FG_ERR_ARG, "clon/tlon array required");
-  if (op != 3 && !result) return fail(FG_ERR_ARG, "result array required");
+  if (op < 0 || op > 6 || npoly < 0 || !lon || !lat || !n) return fg_fail(FG_ERR_ARG, "bad argument");
+  if ((op == 1 || op == 3 || op == 5) && !clon) return fg_fail(FG_ERR_ARG, "clon/tlon array required");
+  if (op != 3 && !result) return fg_fail(FG_ERR_ARG, "result array required");
   if (npoly == 0) return 0;
-  HIPCHK(hipSetDevice(b1_device()));
+  FGCHK(hipSetDevice(fg_env_device()));
   size_t nb = (size_t)npoly * FG_POLY_STRIDE * sizeof(double), ni = (size_t)npoly * sizeof(int), nd = (size_t)npoly * sizeof(double);
   DevBuf a(nb), b(nb), m(ni), cl(nd), r(nd);
-  if (!a.p || !b.p || !m.p || !cl.p || !r.p) return fail(FG_ERR_HIP, "out of device memory");
-  HIPCHK(hipMemcpy(a.p, lon, nb, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(b.p, lat, nb, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(m.p, n, ni, hipMemcpyHostToDevice));
-  if (clon) HIPCHK(hipMemcpy(cl.p, clon, nd, hipMemcpyHostToDevice));
+  if (!a.p || !b.p || !m.p || !cl.p || !r.p) return fg_fail(FG_ERR_HIP, "out of device memory");
+  FGCHK(hipMemcpy(a.p, lon, nb, hipMemcpyHostToDevice)); FGCHK(hipMemcpy(b.p, lat, nb, hipMemcpyHostToDevice));
+  FGCHK(hipMemcpy(m.p, n, ni, hipMemcpyHostToDevice));
+  if (clon) FGCHK(hipMemcpy(cl.p, clon, nd, hipMemcpyHostToDevice));
   fgd_poly_op(op, npoly, (double *)a.p, (double *)b.p, (int *)m.p, (double *)cl.p, (double *)r.p, 0);
-  HIPCHK(hipDeviceSynchronize());
+  FGCHK(hipDeviceSynchronize());
   if (op == 3) {
-    HIPCHK(hipMemcpy(lon, a.p, nb, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(lat, b.p, nb, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(n, m.p, ni, hipMemcpyDeviceToHost));
-  } else HIPCHK(hipMemcpy(result, r.p, nd, hipMemcpyDeviceToHost));
+    FGCHK(hipMemcpy(lon, a.p, nb, hipMemcpyDeviceToHost)); FGCHK(hipMemcpy(lat, b.p, nb, hipMemcpyDeviceToHost));
+    FGCHK(hipMemcpy(n, m.p, ni, hipMemcpyDeviceToHost));
+  } else FGCHK(hipMemcpy(result, r.p, nd, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2735,18 +2708,14 @@ extern "C" int fg_c2l_create(int ntiles, const int *nx, const int *ny, const dou
                              const int *istart2, const int *iend2, const int *jstart2, const int *jend2,
                              int device, fg_c2l **out)
 {
-  if (ntiles < 1 || !nx || !ny || !lonc || !latc || !lont || !latt || !out) return fail(FG_ERR_ARG, "null argument");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  if (device < 0 || device >= ndev) return fail(FG_ERR_ARG, "device out of range");
-  HIPCHK(hipSetDevice(device));
+  if (ntiles < 1 || !nx || !ny || !lonc || !latc || !lont || !latt || !out) return fg_fail(FG_ERR_ARG, "null argument");
+  if (int rc = fg_use_device("fg_c2l_create", device)) return rc;
   fg_c2l *h = new fg_c2l();
   h->device = device; h->ntiles = ntiles;
   std::vector<long> cell_off(ntiles + 1), f_off(ntiles + 1), dx_off(ntiles + 1), dy_off(ntiles + 1), ew_off(ntiles + 1), es_off(ntiles + 1);
   long co = 0, fo = 0, xo = 0, yo = 0, wo = 0, so = 0;
   for (int t = 0; t < ntiles; t++) {
-    if (nx[t] < 2 || ny[t] < 2) { delete h; return fail(FG_ERR_ARG, "tiles need at least 2x2 cells for the gradient"); }
+    if (nx[t] < 2 || ny[t] < 2) { delete h; return fg_fail(FG_ERR_ARG, "tiles need at least 2x2 cells for the gradient"); }
     h->nx.push_back(nx[t]); h->ny.push_back(ny[t]);
     cell_off[t] = co; f_off[t] = fo; dx_off[t] = xo; dy_off[t] = yo; ew_off[t] = wo; es_off[t] = so;
     co += (long)nx[t] * ny[t]; fo += (long)(nx[t] + 2) * (ny[t] + 2);
@@ -2758,7 +2727,7 @@ extern "C" int fg_c2l_create(int ntiles, const int *nx, const int *ny, const dou
   std::vector<int> map(fo);
   int rc = fg_halo_map(ntiles, nx, ny, ncontacts, tile1, tile2, istart1, iend1, jstart1, jend1, istart2, iend2, jstart2, jend2,
                        map_off.data(), map.data());
-  if (rc) { delete h; return fail(rc, "fregrid_util: inconsistent contact description (size mismatch between the boundary)"); }
+  if (rc) { delete h; return fg_fail(rc, "fregrid_util: inconsistent contact description (size mismatch between the boundary)"); }
   // halo'd cell centres: interior copy, zero halo (init_halo), then the same halo update as the data
   h->lont_halo.assign(fo, 0.0); h->latt_halo.assign(fo, 0.0);
   for (int t = 0; t < ntiles; t++)
@@ -2783,10 +2752,10 @@ extern "C" int fg_c2l_create(int ntiles, const int *nx, const int *ny, const dou
     for (int t = 1; t < ntiles; t++) workers.emplace_back(one, t);
     one(0);
     for (std::thread &w : workers) w.join();
-    for (int t = 0; t < ntiles; t++) if (rcs[t]) { rc = rcs[t]; delete h; return fail(rc, "fg_c2l_grid_info failed"); }
+    for (int t = 0; t < ntiles; t++) if (rcs[t]) { rc = rcs[t]; delete h; return fg_fail(rc, "fg_c2l_grid_info failed"); }
   }
   h->stream = g_handles.get_stream(device);
-  if (!h->stream) { delete h; return fail(FG_ERR_HIP, "hipStreamCreate failed"); }
+  if (!h->stream) { delete h; return fg_fail(FG_ERR_HIP, "hipStreamCreate failed"); }
   std::vector<char> th(fgd_c2l_tile_size() * ntiles);
   for (int t = 0; t < ntiles; t++) fgd_c2l_tile_fill(th.data(), t, nx[t], ny[t], cell_off[t], f_off[t], dx_off[t], dy_off[t], ew_off[t], es_off[t]);
   const std::vector<double> *src[11] = {&dx, &dy, &area, &ew, &ee, &es, &en, &enn, &ene, &vlon, &vlat};
@@ -2801,11 +2770,11 @@ extern "C" int fg_c2l_create(int ntiles, const int *nx, const int *ny, const dou
   for (long e = 0; e < fo; e++) if (map[e] >= 0) cell_of[e] = cell_of[map[e]];     // sources are interior elements
   ok = ok && hipMemcpy(h->cell_of_dev, cell_of.data(), fo * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
   for (int k = 0; k < 11 && ok; k++) { h->geom_dev[k] = h->alloc<double>(src[k]->size()); ok = ok && h->geom_dev[k]; }
-  if (!ok) { fg_c2l_destroy(h); return fail(FG_ERR_HIP, "out of device memory"); }
+  if (!ok) { fg_c2l_destroy(h); return fg_fail(FG_ERR_HIP, "out of device memory"); }
   ok = ok && hipMemcpy(h->tiles_dev, th.data(), th.size(), hipMemcpyHostToDevice) == hipSuccess;
   ok = ok && hipMemcpy(h->map_dev, map.data(), fo * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
   for (int k = 0; k < 11 && ok; k++) ok = hipMemcpy(h->geom_dev[k], src[k]->data(), src[k]->size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { fg_c2l_destroy(h); return fail(FG_ERR_HIP, "upload of the gradient geometry failed"); }
+  if (!ok) { fg_c2l_destroy(h); return fg_fail(FG_ERR_HIP, "upload of the gradient geometry failed"); }
   *out = h;
   return 0;
 }
@@ -2814,18 +2783,18 @@ extern "C" long fg_c2l_ncells(const fg_c2l *h) { return h ? h->ncells : FG_ERR_A
 extern "C" long fg_c2l_halo_size(const fg_c2l *h) { return h ? h->F : FG_ERR_ARG; }
 extern "C" int fg_c2l_set_stream(fg_c2l *h, void *stream)
 {
-  if (!h) return fail(FG_ERR_ARG, "null handle");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!h) return fg_fail(FG_ERR_ARG, "null handle");
+  FGCHK(hipSetDevice(h->device));
+  FGCHK(hipStreamSynchronize(h->stream));
   if (h->own_stream) g_handles.put_stream(h->device, h->stream);
   h->stream = (hipStream_t)stream; h->own_stream = false;
   return 0;
 }
 int fg_c2l_borrow_stream(fg_c2l *h, void *stream, void **saved, int *saved_own)      // (see fg_plan_borrow_stream)
 {
-  if (!h) return fail(FG_ERR_ARG, "null handle");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!h) return fg_fail(FG_ERR_ARG, "null handle");
+  FGCHK(hipSetDevice(h->device));
+  FGCHK(hipStreamSynchronize(h->stream));
   *saved = (void *)h->stream; *saved_own = h->own_stream ? 1 : 0;
   h->stream = (hipStream_t)stream; h->own_stream = false;
   return 0;
@@ -2837,14 +2806,14 @@ void fg_c2l_return_stream(fg_c2l *h, void *saved, int saved_own)
 }
 extern "C" int fg_c2l_sync(fg_c2l *h)
 {
-  if (!h) return fail(FG_ERR_ARG, "null handle");
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!h) return fg_fail(FG_ERR_ARG, "null handle");
+  FGCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 // host copies of the halo'd cell-centre arrays [F] (for tests)
 extern "C" int fg_c2l_get_centres(const fg_c2l *h, double *lont_halo, double *latt_halo)
 {
-  if (!h) return fail(FG_ERR_ARG, "null handle");
+  if (!h) return fg_fail(FG_ERR_ARG, "null handle");
   if (lont_halo) memcpy(lont_halo, h->lont_halo.data(), h->F * sizeof(double));
   if (latt_halo) memcpy(latt_halo, h->latt_halo.data(), h->F * sizeof(double));
   return 0;
@@ -2854,14 +2823,14 @@ extern "C" int fg_c2l_get_centres(const fg_c2l *h, double *lont_halo, double *la
 // src == NULL: halo_data already holds the interiors, only the halo is filled.  Device pointers.
 extern "C" int fg_c2l_fill_halo(fg_c2l *h, const double *src, double *halo_data, int nz)
 {
-  if (!h || !halo_data || nz < 1) return fail(FG_ERR_ARG, "bad argument");
-  HIPCHK(hipSetDevice(h->device));
+  if (!h || !halo_data || nz < 1) return fg_fail(FG_ERR_ARG, "bad argument");
+  FGCHK(hipSetDevice(h->device));
   if (src) {
-    HIPCHK(hipMemsetAsync(halo_data, 0, (size_t)nz * h->F * sizeof(double), h->stream));   // init_halo (corners stay 0)
+    FGCHK(hipMemsetAsync(halo_data, 0, (size_t)nz * h->F * sizeof(double), h->stream));   // init_halo (corners stay 0)
     fgd_pack_interior(h->tiles_dev, h->ntiles, h->ncells, h->F, nz, src, halo_data, h->stream);
   }
   fgd_halo_gather(h->F, nz, h->map_dev, halo_data, h->stream);
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
@@ -2870,44 +2839,44 @@ extern "C" int fg_c2l_fill_halo(fg_c2l *h, const double *src, double *halo_data,
 extern "C" int fg_c2l_gradient(fg_c2l *h, const double *halo_data, int nz, int has_missing, double missing,
                                double *grad_x, double *grad_y, int *grad_mask)
 {
-  if (!h || !halo_data || !grad_x || !grad_y || nz < 1) return fail(FG_ERR_ARG, "bad argument");
-  HIPCHK(hipSetDevice(h->device));
+  if (!h || !halo_data || !grad_x || !grad_y || nz < 1) return fg_fail(FG_ERR_ARG, "bad argument");
+  FGCHK(hipSetDevice(h->device));
   fgd_grad_c2l(h->tiles_dev, h->ntiles, h->ncells, h->F, nz, halo_data, (const double *const *)h->geom_dev, grad_x, grad_y, h->stream);
   if (grad_mask) {
     if (has_missing) fgd_grad_mask(h->tiles_dev, h->ntiles, h->ncells, h->F, nz, halo_data, missing, grad_mask, h->stream);
-    else HIPCHK(hipMemsetAsync(grad_mask, 0, (size_t)nz * h->ncells * sizeof(int), h->stream));
+    else FGCHK(hipMemsetAsync(grad_mask, 0, (size_t)nz * h->ncells * sizeof(int), h->stream));
   }
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int fg_c2l_records(fg_c2l *h, const double *src, int nz, double *rec)
 {
-  if (!h || !src || !rec) return fail(FG_ERR_ARG, "bad argument");
-  if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_c2l_records: 1 to 8 levels per call");
-  HIPCHK(hipSetDevice(h->device));
+  if (!h || !src || !rec) return fg_fail(FG_ERR_ARG, "bad argument");
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "fg_c2l_records: 1 to 8 levels per call");
+  FGCHK(hipSetDevice(h->device));
   fgd_c2l_records(h->tiles_dev, h->ntiles, h->ncells, nz, levels_pad(nz), src, h->cell_of_dev, (const double *const *)h->geom_dev, rec, h->stream);
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int fg_c2l_records_levels(fg_c2l *h, const double *src, int nz, double missing, double *rec, unsigned char *maskbits)
 {
-  if (!h || !src || !rec || !maskbits) return fail(FG_ERR_ARG, "fg_c2l_records_levels: null argument");
-  if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_c2l_records_levels: 1 to 8 levels per call");
-  HIPCHK(hipSetDevice(h->device));
+  if (!h || !src || !rec || !maskbits) return fg_fail(FG_ERR_ARG, "fg_c2l_records_levels: null argument");
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "fg_c2l_records_levels: 1 to 8 levels per call");
+  FGCHK(hipSetDevice(h->device));
   fgd_c2l_records_levels(h->tiles_dev, h->ntiles, h->ncells, nz, src, h->cell_of_dev, (const double *const *)h->geom_dev, missing, rec,
                          maskbits, h->stream);
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int fg_c2l_gradient_records(fg_c2l *h, const double *halo_data, int nz, double *rec)
 {
-  if (!h || !halo_data || !rec) return fail(FG_ERR_ARG, "bad argument");
-  if (nz < 1 || nz > 8) return fail(FG_ERR_ARG, "fg_c2l_gradient_records: 1 to 8 levels per call");
-  HIPCHK(hipSetDevice(h->device));
+  if (!h || !halo_data || !rec) return fg_fail(FG_ERR_ARG, "bad argument");
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "fg_c2l_gradient_records: 1 to 8 levels per call");
+  FGCHK(hipSetDevice(h->device));
   fgd_grad_c2l_rec(h->tiles_dev, h->ntiles, h->ncells, h->F, nz, levels_pad(nz), halo_data, (const double *const *)h->geom_dev, rec, h->stream);
-  HIPCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   return 0;
 }

@@ -8,56 +8,18 @@
 // level for the accumulated subA, then sort_basin and check_river_data on the host.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
-#include <chrono>
 #include <utility>
 #include <vector>
 #include "river.h"
 #include "xgrid_device.h"
-#include "fregrid_hip.h"
-
-void fg_set_last_error(const char *msg);
-
-static int rv_fail(int code, const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  fg_set_last_error(buf);
-  return code;
-}
-#define RVCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return rv_fail(FG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
-static double rv_now_ms(void)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+#include "fg_host.h"
 
 static std::atomic<int> g_prune{1};
 extern "C" void fg_set_river_prune(int on) { g_prune = on ? 1 : 0; }
-
-// device memory that is released when the owner goes out of scope
-struct RvDev {
-  std::vector<void *> ptrs;
-  ~RvDev() { for (void *p : ptrs) (void)hipFree(p); }
-  template <typename T> T *get(size_t n)
-  {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-  template <typename T> T *put(const std::vector<T> &v)
-  {
-    T *p = get<T>(v.size());
-    if (p && !v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return p;
-  }
-};
 
 // qsort_index (:1538): the reference's own quicksort, whose order among equal values sort_basin's ids depend on.  The same
 // exchanges in the same order within a range; the two halves are disjoint, so the smaller one recurses and the larger one loops.
@@ -88,7 +50,7 @@ static void rv_qsort_index(double *a, int start, int end, int *idx)
 }
 extern "C" int fg_river_qsort_index(double *array, int n, int *index)
 {
-  if (n < 0 || (n > 0 && (!array || !index))) return rv_fail(FG_ERR_ARG, "fg_river_qsort_index: bad argument");
+  if (n < 0 || (n > 0 && (!array || !index))) return fg_fail(FG_ERR_ARG, "fg_river_qsort_index: bad argument");
   rv_qsort_index(array, 0, n - 1, index);
   return 0;
 }
@@ -134,7 +96,7 @@ struct fg_river {
   double subA_missing = 0, cellarea_missing = 0, celllength_missing = 0;
   int tocell_missing = 0, travel_missing = 0, basin_missing = 0;
   hipStream_t stream = nullptr;
-  RvDev dev;
+  FgDev dev;
   RvSource src;
   RvGrid grid;
   int nland = 0;
@@ -169,32 +131,32 @@ extern "C" int fg_river_create(int nx_in, int ny_in, const double *xb_r, const d
                                const double *const *xt, const double *const *yt, const double *const *area, const double *const *landfrac,
                                double suba_cutoff, int device, fg_river **out)
 {
-  if (!out) return rv_fail(FG_ERR_ARG, "fg_river_create: null output handle");
+  if (!out) return fg_fail(FG_ERR_ARG, "fg_river_create: null output handle");
   *out = nullptr;
   if (nx_in < 1 || ny_in < 1 || (long)nx_in * ny_in > 0x3fffffffL || !xb_r || !yb_r || !subA_in || !missing6)
-    return rv_fail(FG_ERR_ARG, "fg_river_create: bad source grid argument");
-  if (ntiles < 1 || !nx_t || !ny_t || !xb || !yb || !xt || !yt || !area || !landfrac) return rv_fail(FG_ERR_ARG, "fg_river_create: bad mosaic argument");
+    return fg_fail(FG_ERR_ARG, "fg_river_create: bad source grid argument");
+  if (ntiles < 1 || !nx_t || !ny_t || !xb || !yb || !xt || !yt || !area || !landfrac) return fg_fail(FG_ERR_ARG, "fg_river_create: bad mosaic argument");
   for (int n = 0; n < ntiles; n++) {
-    if (nx_t[n] != nx_t[0] || ny_t[n] != ny_t[0]) return rv_fail(FG_ERR_ARG, "river_regrid: all the tiles should have the same grid size");
-    if (!xb[n] || !yb[n] || !xt[n] || !yt[n] || !area[n] || !landfrac[n]) return rv_fail(FG_ERR_ARG, "fg_river_create: null tile array");
+    if (nx_t[n] != nx_t[0] || ny_t[n] != ny_t[0]) return fg_fail(FG_ERR_ARG, "river_regrid: all the tiles should have the same grid size");
+    if (!xb[n] || !yb[n] || !xt[n] || !yt[n] || !area[n] || !landfrac[n]) return fg_fail(FG_ERR_ARG, "fg_river_create: null tile array");
   }
   const int nx = nx_t[0], ny = ny_t[0];
-  if (nx < 1 || ny < 1 || (double)ntiles * (nx + 2) * (ny + 2) > 0x3fffffff) return rv_fail(FG_ERR_ARG, "fg_river_create: bad tile size %d x %d", nx, ny);
-  if (opcode & ~7) return rv_fail(FG_ERR_ARG, "fg_river_create: opcode %d is not a sum of 1 (x cyclic), 2 (y cyclic), 4 (cubic grid)", opcode);
-  if ((opcode & RV_CUBIC_GRID) && ntiles != 6) return rv_fail(FG_ERR_ARG, "river_regrid: the mosaic must be a 6-tile cubic grid for 12 contacts.");
-  if ((opcode & RV_CUBIC_GRID) && nx != ny) return rv_fail(FG_ERR_ARG, "fg_river_create: the tiles of a cubic grid must be square");
-  if ((opcode & (RV_X_CYCLIC | RV_Y_CYCLIC)) && ntiles != 1) return rv_fail(FG_ERR_ARG, "river_regrid: number of tiles must be 1 for single contact");
+  if (nx < 1 || ny < 1 || (double)ntiles * (nx + 2) * (ny + 2) > 0x3fffffff) return fg_fail(FG_ERR_ARG, "fg_river_create: bad tile size %d x %d", nx, ny);
+  if (opcode & ~7) return fg_fail(FG_ERR_ARG, "fg_river_create: opcode %d is not a sum of 1 (x cyclic), 2 (y cyclic), 4 (cubic grid)", opcode);
+  if ((opcode & RV_CUBIC_GRID) && ntiles != 6) return fg_fail(FG_ERR_ARG, "river_regrid: the mosaic must be a 6-tile cubic grid for 12 contacts.");
+  if ((opcode & RV_CUBIC_GRID) && nx != ny) return fg_fail(FG_ERR_ARG, "fg_river_create: the tiles of a cubic grid must be square");
+  if ((opcode & (RV_X_CYCLIC | RV_Y_CYCLIC)) && ntiles != 1) return fg_fail(FG_ERR_ARG, "river_regrid: number of tiles must be 1 for single contact");
   // update_halo_double's y-cyclic loop runs to ny along a row of nx + 2: with ny > nx it would write into the next rows
-  if ((opcode & RV_Y_CYCLIC) && ny > nx) return rv_fail(FG_ERR_ARG, "fg_river_create: a y-cyclic grid with ny > nx is not supported (the reference's halo update runs its rows to ny)");
+  if ((opcode & RV_Y_CYCLIC) && ny > nx) return fg_fail(FG_ERR_ARG, "fg_river_create: a y-cyclic grid with ny > nx is not supported (the reference's halo update runs its rows to ny)");
   fg_river *h = new fg_river;
   struct Guard { fg_river *&h; bool keep = false; ~Guard() { if (!keep) fg_river_destroy(h); } } guard{h};
   h->device = device; h->nx_in = nx_in; h->ny_in = ny_in; h->ntiles = ntiles; h->nx = nx; h->ny = ny; h->opcode = opcode; h->suba_cutoff = suba_cutoff;
   // init_river_data (:652-657) passes subA's missing value through an int; the three int fields take theirs from a double.  The
   // sweeps of calc_river_data and the outlet test take any value >= 0 for data, so those three must be negative.
-  if (!(fabs(missing6[0]) < 2147483648.0)) return rv_fail(FG_ERR_ARG, "fg_river_create: subA's missing value %g does not fit the int that init_river_data keeps it in", missing6[0]);
+  if (!(fabs(missing6[0]) < 2147483648.0)) return fg_fail(FG_ERR_ARG, "fg_river_create: subA's missing value %g does not fit the int that init_river_data keeps it in", missing6[0]);
   h->subA_missing = (double)(int)missing6[0];
   if (!rv_int_missing(missing6[1], &h->tocell_missing) || !rv_int_missing(missing6[2], &h->travel_missing) || !rv_int_missing(missing6[3], &h->basin_missing))
-    return rv_fail(FG_ERR_ARG, "fg_river_create: the missing values of tocell, travel and basin must be negative integers (the reference's sweeps would take them for data)");
+    return fg_fail(FG_ERR_ARG, "fg_river_create: the missing values of tocell, travel and basin must be negative integers (the reference's sweeps would take them for data)");
   h->cellarea_missing = missing6[4]; h->celllength_missing = missing6[5];
   const long per = (long)nx * ny, perh = (long)(nx + 2) * (ny + 2), perb = (long)(nx + 1) * (ny + 1);
   h->ncell = per * ntiles; h->nhalo = perh * ntiles;
@@ -209,16 +171,10 @@ extern "C" int fg_river_create(int nx_in, int ny_in, const double *xb_r, const d
     memcpy(&ytv[n * perh], yt[n], perh * sizeof(double));
   }
   for (long c = 0; c < h->ncell; c++)
-    if (h->landfrac[c] > 1 || h->landfrac[c] < 0 || h->landfrac[c] != h->landfrac[c]) return rv_fail(FG_ERR_ARG, "river_regrid: land_frac should be between 0 or 1");
-  {
-    int ndev = 0;
-    RVCHK(hipGetDeviceCount(&ndev));
-    if (ndev < 1) return rv_fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-    if (device < 0 || device >= ndev) return rv_fail(FG_ERR_ARG, "fg_river_create: device out of range");
-    RVCHK(hipSetDevice(device));
-  }
-  const double t0 = rv_now_ms();
-  RVCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (h->landfrac[c] > 1 || h->landfrac[c] < 0 || h->landfrac[c] != h->landfrac[c]) return fg_fail(FG_ERR_ARG, "river_regrid: land_frac should be between 0 or 1");
+  if (int rc = fg_use_device("fg_river_create", device)) return rc;
+  const double t0 = fg_now_ms();
+  FGCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   // the halo of xt, yt (get_mosaic_grid :631): filled indices from their interior cell, the others as the caller gave them
   h->hmap = rv_halo_map(ntiles, nx, ny, opcode);
   {
@@ -246,7 +202,7 @@ extern "C" int fg_river_create(int nx_in, int ny_in, const double *xb_r, const d
   h->maxsub_init.assign(h->ncell, RV_LARGE);
   for (long c = 0; c < h->ncell; c++) if (!(h->landfrac[c] < 1)) { land.push_back((int)c); h->maxsub_init[c] = h->subA_missing; }
   h->nland = (int)land.size();
-  RvDev &dev = h->dev;
+  FgDev &dev = h->dev;
   RvSource &s = h->src;
   s.xb = dev.put(sx); s.yb = dev.put(sy); s.tlon = dev.put(tlon); s.subA = dev.put(ssub); s.next = dev.put(next);
   s.nx = nx_in; s.ny = ny_in; s.missing = h->subA_missing;
@@ -256,8 +212,8 @@ extern "C" int fg_river_create(int nx_in, int ny_in, const double *xb_r, const d
   g.hmap = dev.put(h->hmap);
   h->d_land = dev.put(land);
   if (!s.xb || !s.yb || !s.tlon || !s.subA || !s.next || !g.xb || !g.yb || !g.xt || !g.yt || !g.area || !g.landfrac || !g.hmap || !h->d_land)
-    return rv_fail(FG_ERR_HIP, "fg_river_create: device allocation or upload failed");
-  h->ms[0] = (float)(rv_now_ms() - t0);
+    return fg_fail(FG_ERR_HIP, "fg_river_create: device allocation or upload failed");
+  h->ms[0] = (float)(fg_now_ms() - t0);
   guard.keep = true;
   *out = h;
   return 0;
@@ -274,17 +230,17 @@ static int rv_sort_basin(fg_river *h, const std::vector<int> &outlet)
   for (int n = 0; n < nb; n++) indx[n] = n;
   for (long c = 0; c < h->ncell; c++) if (outlet[c]) {
     const int b = h->basin[c];
-    if (b > maxbasin || b < 1) return rv_fail(FG_ERR_ARG, "river_regrid: basin should be between 1 and maxbasin");
+    if (b > maxbasin || b < 1) return fg_fail(FG_ERR_ARG, "river_regrid: basin should be between 1 and maxbasin");
     maxsuba[b - 1] = h->subA[c];
   }
-  for (int n = 0; n < nb; n++) if (maxsuba[n] == h->subA_missing) return rv_fail(FG_ERR_ARG, "river_regrid: maxsuba is not assigned for some basin");
+  for (int n = 0; n < nb; n++) if (maxsuba[n] == h->subA_missing) return fg_fail(FG_ERR_ARG, "river_regrid: maxsuba is not assigned for some basin");
   rv_qsort_index(maxsuba.data(), 0, nb - 1, indx.data());
   for (int n = 0; n < nb; n++) rank[indx[n]] = n;
-  for (int n = 0; n < nb; n++) if (rank[n] < 0) return rv_fail(FG_ERR_ARG, "river_regrid: rank should be no less than 0");
+  for (int n = 0; n < nb; n++) if (rank[n] < 0) return fg_fail(FG_ERR_ARG, "river_regrid: rank should be no less than 0");
   for (long c = 0; c < h->ncell; c++) {
     const int b = h->basin[c];
     if (b != h->basin_missing) {
-      if (b > maxbasin || b < 1) return rv_fail(FG_ERR_ARG, "river_regrid: basin should be a positive integer no larger than maxbasin");
+      if (b > maxbasin || b < 1) return fg_fail(FG_ERR_ARG, "river_regrid: basin should be a positive integer no larger than maxbasin");
       h->basin[c] = maxbasin - rank[b - 1];
     }
   }
@@ -304,9 +260,9 @@ static int rv_check(fg_river *h, const std::vector<int> &outlet)
     const double subA = h->subA[c];
     if (h->landfrac[c] == 0) {
       if (tocell != h->tocell_missing || travel != h->travel_missing || basin != h->basin_missing || subA != h->subA_missing)
-        return rv_fail(FG_ERR_ARG, "river_regrid, subA, tocell, travel, or basin is not missing value for some ocean points");
+        return fg_fail(FG_ERR_ARG, "river_regrid, subA, tocell, travel, or basin is not missing value for some ocean points");
     } else if (tocell == h->tocell_missing || travel == h->travel_missing || basin == h->basin_missing || subA == h->subA_missing)
-      return rv_fail(FG_ERR_ARG, "river_regrid, subA, tocell, travel, or basin is missing value for some river points");
+      return fg_fail(FG_ERR_ARG, "river_regrid, subA, tocell, travel, or basin is missing value for some river points");
     if (h->landfrac[c] == 1 && tocell == 0) {
       const long n = c / per, r = c % per, j = r / nx, i = r % nx;
       bool coast = false;
@@ -324,8 +280,8 @@ static int rv_check(fg_river *h, const std::vector<int> &outlet)
     if (b >= 1 && b <= maxbasin) ++cnt[b - 1];
   }
   for (int n = 0; n < maxbasin; n++) {
-    if (cnt[n] <= 0) return rv_fail(FG_ERR_ARG, "river_regrid: some river has no point with travel = 0");
-    if (cnt[n] > 1) return rv_fail(FG_ERR_ARG, "river_regrid: some river has more than one point with travel = 0");
+    if (cnt[n] <= 0) return fg_fail(FG_ERR_ARG, "river_regrid: some river has no point with travel = 0");
+    if (cnt[n] > 1) return fg_fail(FG_ERR_ARG, "river_regrid: some river has more than one point with travel = 0");
   }
   h->stats[0] = maxtravel; h->stats[1] = maxbasin; h->stats[2] = ncoast; h->stats[3] = nsink;
   return 0;
@@ -333,13 +289,13 @@ static int rv_check(fg_river *h, const std::vector<int> &outlet)
 
 extern "C" int fg_river_run(fg_river *h)
 {
-  if (!h) return rv_fail(FG_ERR_ARG, "fg_river_run: null handle");
-  RVCHK(hipSetDevice(h->device));
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_river_run: null handle");
+  FGCHK(hipSetDevice(h->device));
   h->done = false;
   const long nc = h->ncell;
   hipStream_t st = h->stream;
   const RvGrid &g = h->grid;
-  RvDev t;
+  FgDev t;
   long launches = 0;
   const long ntile_scan = fgd_scan_tiles(nc);
   double *d_maxsub = t.put(h->maxsub_init), *d_cellarea = t.get<double>(nc), *d_celllength = t.get<double>(nc), *d_subA = t.get<double>(nc);
@@ -350,22 +306,22 @@ extern "C" int fg_river_run(fg_river *h)
   unsigned long long *d_z = t.get<unsigned long long>(4 + ntile_scan);
   if (!d_maxsub || !d_cellarea || !d_celllength || !d_subA || !d_tocell || !d_dir || !d_flag || !d_trav0 || !d_prefix || !d_succ[0] || !d_succ[1] ||
       !d_hops[0] || !d_hops[1] || !d_travel || !d_basin || !d_cells || !d_z)
-    return rv_fail(FG_ERR_HIP, "fg_river_run: device allocation or upload failed");
-  RVCHK(hipMemsetAsync(d_z, 0, (4 + ntile_scan) * sizeof(unsigned long long), st));
+    return fg_fail(FG_ERR_HIP, "fg_river_run: device allocation or upload failed");
+  FGCHK(hipMemsetAsync(d_z, 0, (4 + ntile_scan) * sizeof(unsigned long long), st));
   unsigned *d_ticket = (unsigned *)(d_z + 2), *d_err = d_ticket + 1;
   int *d_changed = (int *)(d_z + 3);
 
   // 1. max subA (:719-762)
-  double t0 = rv_now_ms();
+  double t0 = fg_now_ms();
   const int prune = g_prune && h->pruned_ok;
   fgd_rv_max_suba(h->src, g, h->nland, h->d_land, d_maxsub, d_z, prune, st); launches += h->nland > 0;
-  RVCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   h->maxsub.resize(nc);
   unsigned long long visited = 0;
-  RVCHK(hipMemcpyAsync(h->maxsub.data(), d_maxsub, nc * sizeof(double), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(&visited, d_z, sizeof visited, hipMemcpyDeviceToHost, st));
-  RVCHK(hipStreamSynchronize(st));
-  double t1 = rv_now_ms();
+  FGCHK(hipMemcpyAsync(h->maxsub.data(), d_maxsub, nc * sizeof(double), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(&visited, d_z, sizeof visited, hipMemcpyDeviceToHost, st));
+  FGCHK(hipStreamSynchronize(st));
+  double t1 = fg_now_ms();
   h->ms[1] = (float)(t1 - t0);
 
   // 3, 4, 6. tocell; outlets with their numbers; cellarea, celllength
@@ -374,37 +330,37 @@ extern "C" int fg_river_run(fg_river *h)
                  d_cellarea, d_celllength, st);
   fgd_exclusive_scan1(d_flag, nc, d_prefix, d_z + 4, d_ticket, d_z + 1, d_err, st);
   launches += 3;
-  RVCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   // 5. travel and basin: pointer jumping, the number of rounds is the logarithm of the longest river
   int cur = 0;
   for (int round = 0;; round++) {
-    if (round > 40) return rv_fail(FG_ERR_ARG, "fg_river_run: the flow directions form a cycle");
+    if (round > 40) return fg_fail(FG_ERR_ARG, "fg_river_run: the flow directions form a cycle");
     int changed = 0;
-    RVCHK(hipMemsetAsync(d_changed, 0, sizeof(int), st));
+    FGCHK(hipMemsetAsync(d_changed, 0, sizeof(int), st));
     fgd_rv_jump(nc, d_succ[cur], d_hops[cur], d_succ[cur ^ 1], d_hops[cur ^ 1], d_changed, st); launches++;
-    RVCHK(hipGetLastError());
-    RVCHK(hipMemcpyAsync(&changed, d_changed, sizeof(int), hipMemcpyDeviceToHost, st));
-    RVCHK(hipStreamSynchronize(st));
+    FGCHK(hipGetLastError());
+    FGCHK(hipMemcpyAsync(&changed, d_changed, sizeof(int), hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));
     cur ^= 1;
     if (!changed) break;
   }
   fgd_rv_finish(nc, d_tocell, h->tocell_missing, d_succ[cur], d_hops[cur], d_trav0, d_prefix, h->travel_missing, h->basin_missing, d_travel, d_basin, st);
   launches++;
-  RVCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   h->tocell.resize(nc); h->travel.resize(nc); h->basin.resize(nc); h->cellarea.resize(nc); h->celllength.resize(nc); h->subA.resize(nc);
   std::vector<int> outlet(nc), dirv(nc);
   unsigned scan_err = 0;
-  RVCHK(hipMemcpyAsync(h->tocell.data(), d_tocell, nc * sizeof(int), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(dirv.data(), d_dir, nc * sizeof(int), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(h->travel.data(), d_travel, nc * sizeof(int), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(h->basin.data(), d_basin, nc * sizeof(int), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(outlet.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(h->cellarea.data(), d_cellarea, nc * sizeof(double), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(h->celllength.data(), d_celllength, nc * sizeof(double), hipMemcpyDeviceToHost, st));
-  RVCHK(hipMemcpyAsync(&scan_err, d_err, sizeof scan_err, hipMemcpyDeviceToHost, st));
-  RVCHK(hipStreamSynchronize(st));
-  if (scan_err) return rv_fail(FG_ERR_HIP, "fg_river_run: the outlet scan failed (error bits %u)", scan_err);
-  t0 = rv_now_ms();
+  FGCHK(hipMemcpyAsync(h->tocell.data(), d_tocell, nc * sizeof(int), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(dirv.data(), d_dir, nc * sizeof(int), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(h->travel.data(), d_travel, nc * sizeof(int), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(h->basin.data(), d_basin, nc * sizeof(int), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(outlet.data(), d_flag, nc * sizeof(int), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(h->cellarea.data(), d_cellarea, nc * sizeof(double), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(h->celllength.data(), d_celllength, nc * sizeof(double), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(&scan_err, d_err, sizeof scan_err, hipMemcpyDeviceToHost, st));
+  FGCHK(hipStreamSynchronize(st));
+  if (scan_err) return fg_fail(FG_ERR_HIP, "fg_river_run: the outlet scan failed (error bits %u)", scan_err);
+  t0 = fg_now_ms();
   h->ms[2] = (float)(t0 - t1);
 
   // The reference's sweeps (:1095-1117) stop after the first one that assigns nothing.  Rivers that end in a cell next to the
@@ -417,7 +373,7 @@ extern "C" int fg_river_run(fg_river *h)
     if (!outlet[c] && dirv[c] >= 0) { upstream++; level1 += h->travel[c] == 1; }
   }
   if (upstream > 0 && level1 == 0)
-    return rv_fail(FG_ERR_ARG, "river_regrid, subA, tocell, travel, or basin is missing value for some river points");
+    return fg_fail(FG_ERR_ARG, "river_regrid, subA, tocell, travel, or basin is missing value for some river points");
   // 7. accumulated subA by travel level, maxtravel down to 0 (:1130-1166)
   std::vector<int> start(maxtravel + 2, 0), cells(nc);
   for (long c = 0; c < nc; c++) if (h->travel[c] >= 0) start[h->travel[c] + 1]++;
@@ -426,20 +382,20 @@ extern "C" int fg_river_run(fg_river *h)
     std::vector<int> fill(start.begin(), start.end() - 1);
     for (long c = 0; c < nc; c++) if (h->travel[c] >= 0) cells[fill[h->travel[c]]++] = (int)c;
   }
-  RVCHK(hipMemcpyAsync(d_cells, cells.data(), nc * sizeof(int), hipMemcpyHostToDevice, st));
+  FGCHK(hipMemcpyAsync(d_cells, cells.data(), nc * sizeof(int), hipMemcpyHostToDevice, st));
   {
     std::vector<double> miss(nc, h->subA_missing);
-    RVCHK(hipMemcpyAsync(d_subA, miss.data(), nc * sizeof(double), hipMemcpyHostToDevice, st));
-    RVCHK(hipStreamSynchronize(st));
+    FGCHK(hipMemcpyAsync(d_subA, miss.data(), nc * sizeof(double), hipMemcpyHostToDevice, st));
+    FGCHK(hipStreamSynchronize(st));
   }
   for (int l = maxtravel; l >= 0; l--) {
     const int count = start[l + 1] - start[l];
     fgd_rv_level(g, l, count, d_cells + start[l], d_dir, d_travel, d_cellarea, h->subA_missing, d_subA, st); launches += count > 0;
   }
-  RVCHK(hipGetLastError());
-  RVCHK(hipMemcpyAsync(h->subA.data(), d_subA, nc * sizeof(double), hipMemcpyDeviceToHost, st));
-  RVCHK(hipStreamSynchronize(st));
-  t1 = rv_now_ms();
+  FGCHK(hipGetLastError());
+  FGCHK(hipMemcpyAsync(h->subA.data(), d_subA, nc * sizeof(double), hipMemcpyDeviceToHost, st));
+  FGCHK(hipStreamSynchronize(st));
+  t1 = fg_now_ms();
   h->ms[3] = (float)(t1 - t0);
 
   // 8, 9. sort_basin, check_river_data
@@ -448,15 +404,15 @@ extern "C" int fg_river_run(fg_river *h)
   rc = rv_check(h, outlet);
   if (rc) return rc;
   h->stats[4] = h->nland; h->stats[5] = (long)visited; h->stats[6] = launches;
-  h->ms[4] = (float)(rv_now_ms() - t1);
+  h->ms[4] = (float)(fg_now_ms() - t1);
   h->done = true;
   return 0;
 }
 
 extern "C" int fg_river_get(const fg_river *h, int tile, double *subA, int *tocell, int *travel, int *basin, double *cellarea, double *celllength)
 {
-  if (!h || tile < 0 || tile >= h->ntiles) return rv_fail(FG_ERR_ARG, "fg_river_get: bad handle or tile");
-  if (!h->done) return rv_fail(FG_ERR_ARG, "fg_river_get: fg_river_run has not completed on this handle");
+  if (!h || tile < 0 || tile >= h->ntiles) return fg_fail(FG_ERR_ARG, "fg_river_get: bad handle or tile");
+  if (!h->done) return fg_fail(FG_ERR_ARG, "fg_river_get: fg_river_run has not completed on this handle");
   const size_t per = (size_t)h->nx * h->ny, o = per * tile;
   if (subA) memcpy(subA, &h->subA[o], per * sizeof(double));
   if (tocell) memcpy(tocell, &h->tocell[o], per * sizeof(int));
@@ -469,8 +425,8 @@ extern "C" int fg_river_get(const fg_river *h, int tile, double *subA, int *toce
 
 extern "C" int fg_river_get_max_suba(const fg_river *h, int tile, double *out)
 {
-  if (!h || !out || tile < 0 || tile >= h->ntiles) return rv_fail(FG_ERR_ARG, "fg_river_get_max_suba: bad argument");
-  if (h->maxsub.empty()) return rv_fail(FG_ERR_ARG, "fg_river_get_max_suba: fg_river_run has not searched on this handle");
+  if (!h || !out || tile < 0 || tile >= h->ntiles) return fg_fail(FG_ERR_ARG, "fg_river_get_max_suba: bad argument");
+  if (h->maxsub.empty()) return fg_fail(FG_ERR_ARG, "fg_river_get_max_suba: fg_river_run has not searched on this handle");
   const size_t perh = (size_t)(h->nx + 2) * (h->ny + 2);
   for (size_t k = 0; k < perh; k++) { const int m = h->hmap[perh * tile + k]; out[k] = m >= 0 ? h->maxsub[m] : h->subA_missing; }
   return 0;
@@ -478,14 +434,14 @@ extern "C" int fg_river_get_max_suba(const fg_river *h, int tile, double *out)
 
 extern "C" int fg_river_stats(const fg_river *h, long *s, int n)
 {
-  if (!h || !s || n < 0) return rv_fail(FG_ERR_ARG, "fg_river_stats: bad argument");
+  if (!h || !s || n < 0) return fg_fail(FG_ERR_ARG, "fg_river_stats: bad argument");
   for (int k = 0; k < n && k < 7; k++) s[k] = h->stats[k];
   return 0;
 }
 
 extern "C" int fg_river_phase_ms(const fg_river *h, float *ms, int n)
 {
-  if (!h || !ms || n < 0) return rv_fail(FG_ERR_ARG, "fg_river_phase_ms: bad argument");
+  if (!h || !ms || n < 0) return fg_fail(FG_ERR_ARG, "fg_river_phase_ms: bad argument");
   for (int k = 0; k < n && k < 5; k++) ms[k] = h->ms[k];
   return 0;
 }

@@ -9,9 +9,9 @@
 #pragma once
 #include "runoff.h"
 
-#define RL_TILE RO_TILE            /* compacted unmasked points per tile (fg_rland_tile); fgd_ro_compact / fgd_ro_balls are reused */
+#define RL_TILE RO_TILE            /* compacted unmasked points per tile (fg_rland_tile); fgd_ro_tiles is reused */
 #define RL_GROUP RO_GROUP          /* tiles per group: one ballot step */
-#define RL_WAVES 4                 /* queries (waves) per block */
+#define RL_WAVES RO_WAVES          /* queries (waves) per block: ball_walk.hip.h's launch shape */
 #define RL_K 4                     /* survivor slots per query; a query with more goes to the exact-size overflow pass */
 /* Two points whose computed chords differ by more than RL_M have computed d that differ strictly the same way (DESIGN.md 3.10:
  * the argument needs 2^-45.3; the rest is room). */

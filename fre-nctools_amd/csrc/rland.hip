@@ -8,34 +8,15 @@
 // reference's own expression on those few points.  Queries the proof does not cover take the reference's loop on the host.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <vector>
 #include "rland.h"
-#include "fregrid_hip.h"
-
-void fg_set_last_error(const char *msg);
-
-static int rl_fail(int code, const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  fg_set_last_error(buf);
-  return code;
-}
-#define RLCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return rl_fail(FG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
-static double rl_now_ms(void)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+#include "fg_host.h"
 
 static std::atomic<int> g_prune{1};
 extern "C" void fg_set_rland_prune(int on) { g_prune = on ? 1 : 0; }
@@ -112,48 +93,44 @@ extern "C" void fg_rland_destroy(fg_rland *h)
 static int rl_create(fg_rland *h, const double *lon_src, const double *lat_src)
 {
   const long n = h->n;
-  RLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  double t0 = rl_now_ms();
+  FGCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  double t0 = fg_now_ms();
   h->lon.assign(lon_src, lon_src + n); h->lat.assign(lat_src, lat_src + n);
   for (long l = 0; l < n; l++) if (!rl_in_range(lon_src[l], lat_src[l])) { h->in_range = false; break; }
   h->d_xyz = h->b_xyz.need<double>(3 * (size_t)n);
   double *d_ll = h->b_ll.need<double>(2 * (size_t)n);      // the searches reuse it for the destination points
-  if (!h->d_xyz || !d_ll) return rl_fail(FG_ERR_HIP, "fg_rland_create: out of device memory");
+  if (!h->d_xyz || !d_ll) return fg_fail(FG_ERR_HIP, "fg_rland_create: out of device memory");
   std::vector<double> xyz(3 * (size_t)n);
-  RLCHK(hipMemcpy(d_ll, lon_src, n * sizeof(double), hipMemcpyHostToDevice));
-  RLCHK(hipMemcpy(d_ll + n, lat_src, n * sizeof(double), hipMemcpyHostToDevice));
+  FGCHK(hipMemcpy(d_ll, lon_src, n * sizeof(double), hipMemcpyHostToDevice));
+  FGCHK(hipMemcpy(d_ll + n, lat_src, n * sizeof(double), hipMemcpyHostToDevice));
   fgd_ro_xyz(n, d_ll, d_ll + n, h->d_xyz, h->d_xyz + n, h->d_xyz + 2 * n, h->stream);
-  RLCHK(hipGetLastError());
-  RLCHK(hipMemcpyAsync(xyz.data(), h->d_xyz, xyz.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  RLCHK(hipStreamSynchronize(h->stream));
-  double t1 = rl_now_ms();
+  FGCHK(hipGetLastError());
+  FGCHK(hipMemcpyAsync(xyz.data(), h->d_xyz, xyz.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  FGCHK(hipStreamSynchronize(h->stream));
+  double t1 = fg_now_ms();
   h->ms[RL_MS_CONVERT] = (float)(t1 - t0);
   std::vector<std::pair<uint64_t, int>> keyed((size_t)n);
   for (long l = 0; l < n; l++) keyed[l] = {rl_key(xyz[l], xyz[n + l], xyz[2 * n + l]), (int)l};
   std::sort(keyed.begin(), keyed.end());
   h->order.resize((size_t)n);
   for (long k = 0; k < n; k++) h->order[k] = keyed[k].second;
-  h->ms[RL_MS_ORDER] = (float)(rl_now_ms() - t1);
+  h->ms[RL_MS_ORDER] = (float)(fg_now_ms() - t1);
   return 0;
 }
 
 extern "C" int fg_rland_create(int nface_src, int npts_src, const double *lon_src, const double *lat_src, fg_rland **out)
 {
-  if (!out) return rl_fail(FG_ERR_ARG, "fg_rland_create: null output handle");
+  if (!out) return fg_fail(FG_ERR_ARG, "fg_rland_create: null output handle");
   *out = nullptr;
   if (nface_src < 1 || npts_src < 1 || (long)nface_src * npts_src > 0x7fffffffL / RL_TILE)
-    return rl_fail(FG_ERR_ARG, "fg_rland_create: bad source size %d x %d", nface_src, npts_src);
-  if (!lon_src || !lat_src) return rl_fail(FG_ERR_ARG, "fg_rland_create: null grid argument");
-  const char *e = getenv("FREGRID_HIP_DEVICE");
-  const int device = e ? atoi(e) : 0;
-  int ndev = 0;
-  RLCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return rl_fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  if (device < 0 || device >= ndev) return rl_fail(FG_ERR_ARG, "fg_rland_create: device out of range");
-  RLCHK(hipSetDevice(device));
+    return fg_fail(FG_ERR_ARG, "fg_rland_create: bad source size %d x %d", nface_src, npts_src);
+  if (!lon_src || !lat_src) return fg_fail(FG_ERR_ARG, "fg_rland_create: null grid argument");
+  const int device = fg_env_device();
+  int rc = fg_use_device("fg_rland_create", device);
+  if (rc) return rc;
   fg_rland *h = new fg_rland;
   h->device = device; h->nface = nface_src; h->npts = npts_src; h->n = (long)nface_src * npts_src;
-  const int rc = rl_create(h, lon_src, lat_src);
+  rc = rl_create(h, lon_src, lat_src);
   if (rc) { fg_rland_destroy(h); return rc; }
   *out = h;
   return 0;
@@ -170,20 +147,20 @@ struct RlQueries {
 static int rl_queries(fg_rland *h, int npts_dst, const void *lon_dst, const void *lat_dst, RlQueries &qs)
 {
   const size_t n = (size_t)npts_dst;
-  const double t0 = rl_now_ms();
+  const double t0 = fg_now_ms();
   qs.npts = npts_dst;
   qs.lon.resize(n); qs.lat.resize(n);
   double *d_ll = h->b_ll.need<double>(2 * n);
   qs.d_xyz = h->b_qxyz.need<double>(3 * n);
-  if (!d_ll || !qs.d_xyz) return rl_fail(FG_ERR_HIP, "fg_rland_search: out of device memory");
-  RLCHK(hipMemcpy(qs.lon.data(), lon_dst, n * sizeof(double), hipMemcpyDefault));
-  RLCHK(hipMemcpy(qs.lat.data(), lat_dst, n * sizeof(double), hipMemcpyDefault));
-  RLCHK(hipMemcpy(d_ll, qs.lon.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  RLCHK(hipMemcpy(d_ll + n, qs.lat.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  if (!d_ll || !qs.d_xyz) return fg_fail(FG_ERR_HIP, "fg_rland_search: out of device memory");
+  FGCHK(hipMemcpy(qs.lon.data(), lon_dst, n * sizeof(double), hipMemcpyDefault));
+  FGCHK(hipMemcpy(qs.lat.data(), lat_dst, n * sizeof(double), hipMemcpyDefault));
+  FGCHK(hipMemcpy(d_ll, qs.lon.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  FGCHK(hipMemcpy(d_ll + n, qs.lat.data(), n * sizeof(double), hipMemcpyHostToDevice));
   fgd_ro_xyz((long)n, d_ll, d_ll + n, qs.d_xyz, qs.d_xyz + n, qs.d_xyz + 2 * n, h->stream);
-  RLCHK(hipGetLastError());
-  RLCHK(hipStreamSynchronize(h->stream));
-  h->ms[RL_MS_QUERIES] += (float)(rl_now_ms() - t0);
+  FGCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(h->stream));
+  h->ms[RL_MS_QUERIES] += (float)(fg_now_ms() - t0);
   return 0;
 }
 
@@ -195,28 +172,28 @@ static int rl_search(fg_rland *h, const int *mask_src, int m0, int m1, const RlQ
   h->stats[RL_ST_QUERIES] += nq;
   if (nq < 1) return 0;
   hipStream_t st = h->stream;
-  double t0 = rl_now_ms();
+  double t0 = fg_now_ms();
   const long l0 = (long)m0 * npts, l1 = (long)m1 * npts;
   std::vector<int> oidx;
   for (long k = 0; k < h->n; k++) { const int l = h->order[k]; if (l >= l0 && l < l1 && mask_src[l] != 0) oidx.push_back(l); }
   const int nsrc = (int)oidx.size();
-  if (nsrc == 0) return rl_fail(FG_ERR_ARG, "remap_land(full_search_nearest): no nearest point is found");
+  if (nsrc == 0) return fg_fail(FG_ERR_ARG, "remap_land(full_search_nearest): no nearest point is found");
   long first = l0;
   while (mask_src[first] == 0) first++;
-  const int ntiles = (nsrc + RL_TILE - 1) / RL_TILE, ngroups = (ntiles + RL_GROUP - 1) / RL_GROUP;
+  const RoTiles tl = ro_tiles_of(nsrc);
+  const int ntiles = tl.ntiles, ngroups = tl.ngroups;
   h->stats[RL_ST_TILES] = ntiles;
   int *d_oidx = h->b_oidx.put(oidx.data(), oidx.size()), *d_q = h->b_q.put(qlist.data(), (size_t)nq);
   RoPoint *d_pts = h->b_pts.need<RoPoint>((size_t)ntiles * RL_TILE);
   RoBall *d_ball = h->b_ball.need<RoBall>(ntiles), *d_gball = h->b_gball.need<RoBall>(ngroups);
   double *d_c = h->b_c.need<double>(2 * (size_t)nq);
   int *d_i = h->b_i.need<int>((size_t)nq * (3 + RL_K));
-  if (!d_oidx || !d_q || !d_pts || !d_ball || !d_gball || !d_c || !d_i) return rl_fail(FG_ERR_HIP, "fg_rland_search: device allocation or upload failed");
+  if (!d_oidx || !d_q || !d_pts || !d_ball || !d_gball || !d_c || !d_i) return fg_fail(FG_ERR_HIP, "fg_rland_search: device allocation or upload failed");
   const long n = h->n;
-  fgd_ro_compact(nsrc, ntiles, d_oidx, h->d_xyz, h->d_xyz + n, h->d_xyz + 2 * n, d_pts, st);
-  fgd_ro_balls(ntiles, ngroups, d_pts, d_ball, d_gball, st);
-  RLCHK(hipGetLastError());
-  RLCHK(hipStreamSynchronize(st));
-  double t1 = rl_now_ms();
+  fgd_ro_tiles(nsrc, d_oidx, h->d_xyz, h->d_xyz + n, h->d_xyz + 2 * n, d_pts, d_ball, d_gball, st);
+  FGCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(st));
+  double t1 = fg_now_ms();
   h->ms[RL_MS_TILES] += (float)(t1 - t0);
   RlSearch p;
   p.pts = d_pts; p.ball = d_ball; p.gball = d_gball;
@@ -227,22 +204,22 @@ static int rl_search(fg_rland *h, const int *mask_src, int m0, int m1, const RlQ
   p.nq = nq; p.ntiles = ntiles; p.ngroups = ngroups;
   struct Events { hipEvent_t e[3] = {nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } evs;
   hipEvent_t *ev = evs.e;
-  for (int k = 0; k < 3; k++) RLCHK(hipEventCreate(&ev[k]));
-  RLCHK(hipEventRecord(ev[0], st));
+  for (int k = 0; k < 3; k++) FGCHK(hipEventCreate(&ev[k]));
+  FGCHK(hipEventRecord(ev[0], st));
   fgd_rl_cmin(p, prune, st);
-  RLCHK(hipGetLastError());
-  RLCHK(hipEventRecord(ev[1], st));
+  FGCHK(hipGetLastError());
+  FGCHK(hipEventRecord(ev[1], st));
   fgd_rl_survivors(p, prune, st);
-  RLCHK(hipGetLastError());
-  RLCHK(hipEventRecord(ev[2], st));
+  FGCHK(hipGetLastError());
+  FGCHK(hipEventRecord(ev[2], st));
   std::vector<double> c(2 * (size_t)nq);
   std::vector<int> iv((size_t)nq * (3 + RL_K));
-  RLCHK(hipMemcpyAsync(c.data(), d_c, c.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  RLCHK(hipMemcpyAsync(iv.data(), d_i, iv.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  RLCHK(hipStreamSynchronize(st));
+  FGCHK(hipMemcpyAsync(c.data(), d_c, c.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  FGCHK(hipMemcpyAsync(iv.data(), d_i, iv.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  FGCHK(hipStreamSynchronize(st));
   float ms1 = 0, ms2 = 0;
-  RLCHK(hipEventElapsedTime(&ms1, ev[0], ev[1]));
-  RLCHK(hipEventElapsedTime(&ms2, ev[1], ev[2]));
+  FGCHK(hipEventElapsedTime(&ms1, ev[0], ev[1]));
+  FGCHK(hipEventElapsedTime(&ms2, ev[1], ev[2]));
   h->ms[RL_MS_PHASE1] += ms1; h->ms[RL_MS_PHASE2] += ms2;
   const int *count = iv.data(), *visited = iv.data() + nq, *slots = iv.data() + 3 * (size_t)nq;
   for (int q = 0; q < nq; q++) { h->stats[RL_ST_VISITED] += visited[q]; h->stats[RL_ST_VISITED2] += visited[nq + q]; }
@@ -254,21 +231,21 @@ static int rl_search(fg_rland *h, const int *mask_src, int m0, int m1, const RlQ
     scan[q] = !h->in_range || count[q] < 1 || rl_needs_scan(c[q], c[(size_t)nq + q], qs.lon[i], qs.lat[i]);
     if (!scan[q] && count[q] > RL_K) { ovq.push_back(q); ovptr.push_back(ovptr.back() + count[q]); }
   }
-  t0 = rl_now_ms();
+  t0 = fg_now_ms();
   std::vector<int> ovout((size_t)ovptr.back());
   const int nov = (int)ovq.size();
   if (nov > 0) {
     int *d_ovq = h->b_ovq.put(ovq.data(), ovq.size()), *d_ovptr = h->b_ovptr.put(ovptr.data(), ovptr.size());
     int *d_ovout = h->b_ovout.need<int>(ovout.size());
-    if (!d_ovq || !d_ovptr || !d_ovout) return rl_fail(FG_ERR_HIP, "fg_rland_search: device allocation or upload failed");
-    RLCHK(hipMemsetAsync(d_ovout, 0xff, ovout.size() * sizeof(int), st));
+    if (!d_ovq || !d_ovptr || !d_ovout) return fg_fail(FG_ERR_HIP, "fg_rland_search: device allocation or upload failed");
+    FGCHK(hipMemsetAsync(d_ovout, 0xff, ovout.size() * sizeof(int), st));
     fgd_rl_overflow(p, nov, d_ovq, d_ovptr, d_ovout, prune, st);
-    RLCHK(hipGetLastError());
-    RLCHK(hipMemcpyAsync(ovout.data(), d_ovout, ovout.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    RLCHK(hipStreamSynchronize(st));
-    for (int v : ovout) if (v < 0 || v >= n) return rl_fail(FG_ERR_HIP, "fg_rland_search: the overflow pass did not reproduce the survivor counts");
+    FGCHK(hipGetLastError());
+    FGCHK(hipMemcpyAsync(ovout.data(), d_ovout, ovout.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));
+    for (int v : ovout) if (v < 0 || v >= n) return fg_fail(FG_ERR_HIP, "fg_rland_search: the overflow pass did not reproduce the survivor counts");
   }
-  t1 = rl_now_ms();
+  t1 = fg_now_ms();
   h->ms[RL_MS_OVERFLOW] += (float)(t1 - t0);
   h->stats[RL_ST_OVERFLOW] += nov;
   const double *slon = h->lon.data(), *slat = h->lat.data();
@@ -285,16 +262,16 @@ static int rl_search(fg_rland *h, const int *mask_src, int m0, int m1, const RlQ
     if (count[q] <= RL_K) answer[q] = rl_finish(count[q], slots + (size_t)q * RL_K, slon, slat, qs.lon[i], qs.lat[i]);
     else { answer[q] = rl_finish(count[q], ovout.data() + ovptr[ko], slon, slat, qs.lon[i], qs.lat[i]); ko++; }
   }
-  h->ms[RL_MS_FINISH] += (float)(rl_now_ms() - t1);
+  h->ms[RL_MS_FINISH] += (float)(fg_now_ms() - t1);
   return 0;
 }
 
 static int rl_check_search(const char *who, fg_rland *h, const int *mask_src, int npts_dst, const void *lon_dst, const void *lat_dst,
                            const int *mask_dst)
 {
-  if (!h) return rl_fail(FG_ERR_ARG, "%s: null handle", who);
-  if (npts_dst < 0 || !mask_src || (npts_dst > 0 && (!lon_dst || !lat_dst || !mask_dst))) return rl_fail(FG_ERR_ARG, "%s: bad argument", who);
-  RLCHK(hipSetDevice(h->device));
+  if (!h) return fg_fail(FG_ERR_ARG, "%s: null handle", who);
+  if (npts_dst < 0 || !mask_src || (npts_dst > 0 && (!lon_dst || !lat_dst || !mask_dst))) return fg_fail(FG_ERR_ARG, "%s: bad argument", who);
+  FGCHK(hipSetDevice(h->device));
   memset(h->stats, 0, sizeof h->stats);
   for (int k = RL_MS_QUERIES; k < RL_NMS; k++) h->ms[k] = 0;
   return 0;
@@ -305,8 +282,8 @@ extern "C" int fg_rland_search(fg_rland *h, const int *mask_src, int face, int n
 {
   int rc = rl_check_search("fg_rland_search", h, mask_src, npts_dst, lon_dst, lat_dst, mask_dst);
   if (rc) return rc;
-  if (face < -1 || face >= h->nface) return rl_fail(FG_ERR_ARG, "fg_rland_search: face %d of %d", face, h->nface);
-  if (npts_dst > 0 && (!idx_map || !face_map)) return rl_fail(FG_ERR_ARG, "fg_rland_search: null output");
+  if (face < -1 || face >= h->nface) return fg_fail(FG_ERR_ARG, "fg_rland_search: face %d of %d", face, h->nface);
+  if (npts_dst > 0 && (!idx_map || !face_map)) return fg_fail(FG_ERR_ARG, "fg_rland_search: null output");
   std::vector<int> qlist;
   for (int i = 0; i < npts_dst; i++) { idx_map[i] = face_map[i] = -1; if (mask_dst[i] != 0) qlist.push_back(i); }
   if (qlist.empty()) return 0;
@@ -325,8 +302,8 @@ extern "C" int fg_rland_search_sface(fg_rland *h, const int *mask_src, int npts_
 {
   int rc = rl_check_search("fg_rland_search_sface", h, mask_src, npts_dst, lon_dst, lat_dst, mask_dst);
   if (rc) return rc;
-  if (iface_dst < 0 || iface_dst >= h->nface) return rl_fail(FG_ERR_ARG, "fg_rland_search_sface: face %d of %d", iface_dst, h->nface);
-  if (npts_dst > 0 && (!idx_map || !face_map || !idx_map_sf)) return rl_fail(FG_ERR_ARG, "fg_rland_search_sface: null map");
+  if (iface_dst < 0 || iface_dst >= h->nface) return fg_fail(FG_ERR_ARG, "fg_rland_search_sface: face %d of %d", iface_dst, h->nface);
+  if (npts_dst > 0 && (!idx_map || !face_map || !idx_map_sf)) return fg_fail(FG_ERR_ARG, "fg_rland_search_sface: null map");
   std::vector<int> qlist;
   for (int i = 0; i < npts_dst; i++) {
     if (mask_dst[i] == 0) idx_map_sf[i] = -1;
@@ -346,14 +323,14 @@ extern "C" int fg_rland_search_sface(fg_rland *h, const int *mask_src, int npts_
 
 extern "C" int fg_rland_stats(const fg_rland *h, long *stats, int n)
 {
-  if (!h || !stats || n < 0) return rl_fail(FG_ERR_ARG, "fg_rland_stats: bad argument");
+  if (!h || !stats || n < 0) return fg_fail(FG_ERR_ARG, "fg_rland_stats: bad argument");
   for (int k = 0; k < n && k < RL_NSTAT; k++) stats[k] = h->stats[k];
   return 0;
 }
 
 extern "C" int fg_rland_phase_ms(const fg_rland *h, float *ms, int n)
 {
-  if (!h || !ms || n < 0) return rl_fail(FG_ERR_ARG, "fg_rland_phase_ms: bad argument");
+  if (!h || !ms || n < 0) return fg_fail(FG_ERR_ARG, "fg_rland_phase_ms: bad argument");
   for (int k = 0; k < n && k < RL_NMS; k++) ms[k] = h->ms[k];
   return 0;
 }

@@ -73,8 +73,17 @@ struct RoSearch {
   double r0;
 };
 void fgd_ro_xyz(long n, const double *lon, const double *lat, double *x, double *y, double *z, hipStream_t st);
-void fgd_ro_compact(int nocean, int ntiles, const int *oidx, const double *x, const double *y, const double *z, RoPoint *pts, hipStream_t st);
-void fgd_ro_balls(int ntiles, int ngroups, const RoPoint *pts, RoBall *ball, RoBall *gball, hipStream_t st);
+/* the tiles and groups of npoints compacted points: pts holds ntiles * RO_TILE records, ball ntiles, gball ngroups */
+struct RoTiles { int ntiles, ngroups; };
+static inline RoTiles ro_tiles_of(int npoints)
+{
+  RoTiles t;
+  t.ntiles = (npoints + RO_TILE - 1) / RO_TILE; t.ngroups = (t.ntiles + RO_GROUP - 1) / RO_GROUP;
+  return t;
+}
+/* the tile build: the points oidx[0 .. npoints) of x, y, z into pts in that order, then the tile balls and the group balls */
+void fgd_ro_tiles(int npoints, const int *oidx, const double *x, const double *y, const double *z, RoPoint *pts, RoBall *ball,
+                  RoBall *gball, hipStream_t st);
 void fgd_ro_nearest(const RoSearch &p, int prune, hipStream_t st);
 struct RoApply {
   const int *rowptr, *src; const double *xarea;      /* exchange list by destination cell, list order within a cell */

@@ -6,68 +6,21 @@
 // the land points by their ocean target.  A time level is then three launches without atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
-#include <chrono>
 #include <vector>
 #include "runoff.h"
-#include "fregrid_hip.h"
+#include "fg_host.h"
 
-void fg_set_last_error(const char *msg);
 long fg_box_xgrid_lists(int dev, int box_is_src, int order, int nxb, int nyb, const double *lon_b, const double *lat_b,
                         int nxq, int nyq, const double *lon_q, const double *lat_q, const double *mask,
                         std::vector<int> idx[4], std::vector<double> &area, std::vector<double> *clon, std::vector<double> *clat);
 
-static int ro_fail(int code, const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-  fg_set_last_error(buf);
-  return code;
-}
-#define ROCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return ro_fail(FG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
-static double ro_now_ms(void)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 static std::atomic<int> g_prune{1};
 extern "C" void fg_set_runoff_prune(int on) { g_prune = on ? 1 : 0; }
 extern "C" int fg_runoff_tile(void) { return RO_TILE; }
-
-// device memory that is released when the owner goes out of scope
-struct RoDev {
-  std::vector<void *> ptrs;
-  ~RoDev() { for (void *p : ptrs) (void)hipFree(p); }
-  template <typename T> T *get(size_t n)
-  {
-    void *p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-    ptrs.push_back(p);
-    return (T *)p;
-  }
-  template <typename T> T *put(const T *src, size_t n)
-  {
-    T *p = get<T>(n);
-    if (p && n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return p;
-  }
-};
-
-static int ro_check_device(int device)
-{
-  int ndev = 0;
-  ROCHK(hipGetDeviceCount(&ndev));
-  if (ndev < 1) return ro_fail(FG_ERR_HIP, "no HIP device visible: libfregrid_hip needs an MI355X-class GPU");
-  if (device < 0 || device >= ndev) return ro_fail(FG_ERR_ARG, "fg_runoff: device out of range");
-  ROCHK(hipSetDevice(device));
-  return 0;
-}
 
 // nearest() for nq points of the grid itself.  d_xyz: the converted points [3][n] on the device.  stats (may be null):
 // queries, tiles, tiles visited in all, most tiles visited by one query.
@@ -80,17 +33,17 @@ static int ro_search(hipStream_t st, int nlon, int nlat, const double *mask, con
   orank[n] = (int)oidx.size();
   const int nocean = (int)oidx.size();
   if (stats) { stats[0] = nq; stats[1] = stats[2] = stats[3] = 0; }
-  if (nocean == 0) return ro_fail(FG_ERR_ARG, "fg_runoff: mask has no ocean point (every value is 0): there is nothing to map the land points to");
+  if (nocean == 0) return fg_fail(FG_ERR_ARG, "fg_runoff: mask has no ocean point (every value is 0): there is nothing to map the land points to");
   if (nq < 1) return 0;
-  const int ntiles = (nocean + RO_TILE - 1) / RO_TILE, ngroups = (ntiles + RO_GROUP - 1) / RO_GROUP;
-  RoDev dev;
+  const RoTiles tl = ro_tiles_of(nocean);
+  const int ntiles = tl.ntiles, ngroups = tl.ngroups;
+  FgDev dev;
   int *d_oidx = dev.put(oidx.data(), oidx.size()), *d_orank = dev.put(orank.data(), orank.size()), *d_q = dev.put(qindex, (size_t)nq);
   RoPoint *d_pts = dev.get<RoPoint>((size_t)ntiles * RO_TILE);
   RoBall *d_ball = dev.get<RoBall>(ntiles), *d_gball = dev.get<RoBall>(ngroups);
   int *d_out = dev.get<int>(3 * (size_t)nq);
-  if (!d_oidx || !d_orank || !d_q || !d_pts || !d_ball || !d_gball || !d_out) return ro_fail(FG_ERR_HIP, "fg_runoff: device allocation or upload failed");
-  fgd_ro_compact(nocean, ntiles, d_oidx, d_xyz, d_xyz + n, d_xyz + 2 * n, d_pts, st);
-  fgd_ro_balls(ntiles, ngroups, d_pts, d_ball, d_gball, st);
+  if (!d_oidx || !d_orank || !d_q || !d_pts || !d_ball || !d_gball || !d_out) return fg_fail(FG_ERR_HIP, "fg_runoff: device allocation or upload failed");
+  fgd_ro_tiles(nocean, d_oidx, d_xyz, d_xyz + n, d_xyz + 2 * n, d_pts, d_ball, d_gball, st);
   RoSearch p;
   p.x = d_xyz; p.y = d_xyz + n; p.z = d_xyz + 2 * n;
   p.pts = d_pts; p.ball = d_ball; p.gball = d_gball; p.orank = d_orank; p.qindex = d_q;
@@ -98,14 +51,14 @@ static int ro_search(hipStream_t st, int nlon, int nlat, const double *mask, con
   p.n = (int)n; p.nlon = nlon; p.nq = nq; p.ntiles = ntiles; p.ngroups = ngroups;
   p.r0 = ro_r0();
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernel_ms) { ROCHK(hipEventCreate(&e0)); ROCHK(hipEventCreate(&e1)); ROCHK(hipEventRecord(e0, st)); }
+  if (kernel_ms) { FGCHK(hipEventCreate(&e0)); FGCHK(hipEventCreate(&e1)); FGCHK(hipEventRecord(e0, st)); }
   fgd_ro_nearest(p, g_prune, st);
-  ROCHK(hipGetLastError());
-  if (kernel_ms) ROCHK(hipEventRecord(e1, st));
+  FGCHK(hipGetLastError());
+  if (kernel_ms) FGCHK(hipEventRecord(e1, st));
   std::vector<int> out(3 * (size_t)nq);
-  ROCHK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  ROCHK(hipStreamSynchronize(st));
-  if (kernel_ms) { ROCHK(hipEventElapsedTime(kernel_ms, e0, e1)); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+  FGCHK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  FGCHK(hipStreamSynchronize(st));
+  if (kernel_ms) { FGCHK(hipEventElapsedTime(kernel_ms, e0, e1)); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
   memcpy(iout, out.data(), (size_t)nq * sizeof(int));
   memcpy(jout, out.data() + nq, (size_t)nq * sizeof(int));
   if (stats) {
@@ -117,8 +70,8 @@ static int ro_search(hipStream_t st, int nlon, int nlat, const double *mask, con
 
 static int ro_check_grid(const char *who, int nlon, int nlat, const double *mask, const double *lon, const double *lat)
 {
-  if (nlon < 1 || nlat < 1 || (long)nlon * nlat > 0x7fffffffL / RO_TILE) return ro_fail(FG_ERR_ARG, "%s: bad grid size %d x %d", who, nlon, nlat);
-  if (!mask || !lon || !lat) return ro_fail(FG_ERR_ARG, "%s: null grid argument", who);
+  if (nlon < 1 || nlat < 1 || (long)nlon * nlat > 0x7fffffffL / RO_TILE) return fg_fail(FG_ERR_ARG, "%s: bad grid size %d x %d", who, nlon, nlat);
+  if (!mask || !lon || !lat) return fg_fail(FG_ERR_ARG, "%s: null grid argument", who);
   return 0;
 }
 
@@ -128,16 +81,15 @@ extern "C" int fg_nearest_unmasked(int nlon, int nlat, const double *mask, const
   int rc = ro_check_grid("fg_nearest_unmasked", nlon, nlat, mask, lon, lat);
   if (rc) return rc;
   const long n = (long)nlon * nlat;
-  if (nq < 0 || (nq > 0 && (!qindex || !iout || !jout))) return ro_fail(FG_ERR_ARG, "fg_nearest_unmasked: bad query arguments");
-  for (int q = 0; q < nq; q++) if (qindex[q] < 0 || qindex[q] >= n) return ro_fail(FG_ERR_ARG, "fg_nearest_unmasked: query %d (%d) is outside the grid", q, qindex[q]);
-  const char *e = getenv("FREGRID_HIP_DEVICE");
-  rc = ro_check_device(e ? atoi(e) : 0);
+  if (nq < 0 || (nq > 0 && (!qindex || !iout || !jout))) return fg_fail(FG_ERR_ARG, "fg_nearest_unmasked: bad query arguments");
+  for (int q = 0; q < nq; q++) if (qindex[q] < 0 || qindex[q] >= n) return fg_fail(FG_ERR_ARG, "fg_nearest_unmasked: query %d (%d) is outside the grid", q, qindex[q]);
+  rc = fg_use_device("fg_nearest_unmasked", fg_env_device());
   if (rc) return rc;
-  RoDev dev;
+  FgDev dev;
   double *d_ll = dev.get<double>(2 * (size_t)n), *d_xyz = dev.get<double>(3 * (size_t)n);
-  if (!d_ll || !d_xyz) return ro_fail(FG_ERR_HIP, "fg_nearest_unmasked: out of device memory");
-  ROCHK(hipMemcpy(d_ll, lon, n * sizeof(double), hipMemcpyHostToDevice));
-  ROCHK(hipMemcpy(d_ll + n, lat, n * sizeof(double), hipMemcpyHostToDevice));
+  if (!d_ll || !d_xyz) return fg_fail(FG_ERR_HIP, "fg_nearest_unmasked: out of device memory");
+  FGCHK(hipMemcpy(d_ll, lon, n * sizeof(double), hipMemcpyHostToDevice));
+  FGCHK(hipMemcpy(d_ll + n, lat, n * sizeof(double), hipMemcpyHostToDevice));
   fgd_ro_xyz(n, d_ll, d_ll + n, d_xyz, d_xyz + n, d_xyz + 2 * n, nullptr);
   return ro_search(nullptr, nlon, nlat, mask, d_xyz, nq, qindex, iout, jout, nullptr, nullptr);
 }
@@ -145,7 +97,7 @@ extern "C" int fg_nearest_unmasked(int nlon, int nlat, const double *mask, const
 struct fg_runoff {
   int device = 0, nx_in = 0, ny_in = 0, nx_out = 0, ny_out = 0;
   hipStream_t stream = nullptr;
-  RoDev dev;
+  FgDev dev;
   double *d_xyz = nullptr, *d_tmp = nullptr, *d_totals = nullptr;
   RoApply a;
   std::vector<int> xi[4];                    // i_in, j_in, i_out, j_out
@@ -169,30 +121,30 @@ static int ro_setup(fg_runoff *h, const double *mask_in, const double *area_in, 
 {
   const int nx = h->nx_out, ny = h->ny_out;
   const long n = (long)nx * ny, n_in = (long)h->nx_in * h->ny_in, nxg = (long)h->xarea.size();
-  ROCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  RoDev &dev = h->dev;
+  FGCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  FgDev &dev = h->dev;
   h->d_xyz = dev.get<double>(3 * (size_t)n);
   h->d_tmp = dev.get<double>((size_t)n);
   h->d_totals = dev.get<double>(2);
-  if (!h->d_xyz || !h->d_tmp || !h->d_totals) return ro_fail(FG_ERR_HIP, "fg_runoff: out of device memory");
-  double t0 = ro_now_ms();
+  if (!h->d_xyz || !h->d_tmp || !h->d_totals) return fg_fail(FG_ERR_HIP, "fg_runoff: out of device memory");
+  double t0 = fg_now_ms();
   {
-    RoDev t;
+    FgDev t;
     double *d_lon = t.put(xt, (size_t)n), *d_lat = t.put(yt, (size_t)n);
-    if (!d_lon || !d_lat) return ro_fail(FG_ERR_HIP, "fg_runoff: grid upload failed");
+    if (!d_lon || !d_lat) return fg_fail(FG_ERR_HIP, "fg_runoff: grid upload failed");
     fgd_ro_xyz(n, d_lon, d_lat, h->d_xyz, h->d_xyz + n, h->d_xyz + 2 * n, h->stream);
-    ROCHK(hipGetLastError());
-    ROCHK(hipStreamSynchronize(h->stream));
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(h->stream));
   }
   std::vector<int> qindex;
   for (long i = 0; i < n; i++) if (mask_out[i] == 0.0) qindex.push_back((int)i);             // :517
   const int nq = (int)qindex.size();
   std::vector<int> qi(nq), qj(nq);
-  double t1 = ro_now_ms();
+  double t1 = fg_now_ms();
   h->ms[1] = (float)(t1 - t0);
   int rc = ro_search(h->stream, nx, ny, mask_out, h->d_xyz, nq, qindex.data(), qi.data(), qj.data(), h->stats, &h->ms[3]);
   if (rc) return rc;
-  t0 = ro_now_ms();
+  t0 = fg_now_ms();
   h->ms[2] = (float)(t0 - t1);
   h->imap.assign(n, -1); h->jmap.assign(n, -1);
   for (int q = 0; q < nq; q++) { h->imap[qindex[q]] = qi[q]; h->jmap[qindex[q]] = qj[q]; }
@@ -213,7 +165,7 @@ static int ro_setup(fg_runoff *h, const double *mask_in, const double *area_in, 
   for (long l = 0; l < nxg; l++) {
     const int i1 = h->xi[0][l], j1 = h->xi[1][l], i2 = h->xi[2][l], j2 = h->xi[3][l];
     if (i1 < 0 || i1 >= h->nx_in || j1 < 0 || j1 >= h->ny_in || i2 < 0 || i2 >= nx || j2 < 0 || j2 >= ny)
-      return ro_fail(FG_ERR_ARG, "fg_runoff: exchange entry %ld lies outside the grids", l);
+      return fg_fail(FG_ERR_ARG, "fg_runoff: exchange entry %ld lies outside the grids", l);
     rowptr[(long)j2 * nx + i2 + 1]++;
   }
   for (long c = 0; c < n; c++) rowptr[c + 1] += rowptr[c];
@@ -231,24 +183,24 @@ static int ro_setup(fg_runoff *h, const double *mask_in, const double *area_in, 
   a.area_out = dev.put(area_out, (size_t)n); a.area_in = dev.put(area_in, (size_t)n_in); a.mask_in = dev.put(mask_in, (size_t)n_in);
   a.ncell_out = (int)n; a.ncell_in = (int)n_in;
   if (!a.rowptr || !a.src || !a.xarea || !a.tptr || !a.tsrc || !a.land || !a.area_out || !a.area_in || !a.mask_in)
-    return ro_fail(FG_ERR_HIP, "fg_runoff: device allocation or upload failed");
-  h->ms[4] = (float)(ro_now_ms() - t0);
+    return fg_fail(FG_ERR_HIP, "fg_runoff: device allocation or upload failed");
+  h->ms[4] = (float)(fg_now_ms() - t0);
   return 0;
 }
 
 static int ro_new(const char *who, int nx_in, int ny_in, int nx_out, int ny_out, const double *xt, const double *yt,
                   const double *mask_out, const double *area_out, int device, fg_runoff **out, fg_runoff **h)
 {
-  if (!out) return ro_fail(FG_ERR_ARG, "%s: null output handle", who);
+  if (!out) return fg_fail(FG_ERR_ARG, "%s: null output handle", who);
   *out = nullptr;
-  if (nx_in < 1 || ny_in < 1 || (long)nx_in * ny_in > 0x7fffffffL) return ro_fail(FG_ERR_ARG, "%s: bad input grid size", who);
+  if (nx_in < 1 || ny_in < 1 || (long)nx_in * ny_in > 0x7fffffffL) return fg_fail(FG_ERR_ARG, "%s: bad input grid size", who);
   int rc = ro_check_grid(who, nx_out, ny_out, mask_out, xt, yt);
   if (rc) return rc;
-  if (!area_out) return ro_fail(FG_ERR_ARG, "%s: null area_out", who);
+  if (!area_out) return fg_fail(FG_ERR_ARG, "%s: null area_out", who);
   long nocean = 0;
   for (long i = 0; i < (long)nx_out * ny_out; i++) nocean += !(mask_out[i] == 0.0);
-  if (nocean == 0) return ro_fail(FG_ERR_ARG, "%s: mask_out has no ocean point (every value is 0): there is nothing to map the land points to", who);
-  rc = ro_check_device(device);
+  if (nocean == 0) return fg_fail(FG_ERR_ARG, "%s: mask_out has no ocean point (every value is 0): there is nothing to map the land points to", who);
+  rc = fg_use_device(who, device);
   if (rc) return rc;
   *h = new fg_runoff;
   (*h)->device = device; (*h)->nx_in = nx_in; (*h)->ny_in = ny_in; (*h)->nx_out = nx_out; (*h)->ny_out = ny_out;
@@ -265,7 +217,7 @@ extern "C" int fg_runoff_create_from_xgrid(int nx_in, int ny_in, const double *m
   if (rc) return rc;
   if (!mask_in || !area_in || nxgrid < 0 || (nxgrid > 0 && (!i_in || !j_in || !i_out || !j_out || !xgrid_area))) {
     fg_runoff_destroy(h);
-    return ro_fail(FG_ERR_ARG, "fg_runoff_create_from_xgrid: null argument");
+    return fg_fail(FG_ERR_ARG, "fg_runoff_create_from_xgrid: null argument");
   }
   const int *lists[4] = {i_in, j_in, i_out, j_out};
   for (int k = 0; k < 4; k++) h->xi[k].assign(lists[k], lists[k] + nxgrid);
@@ -283,8 +235,8 @@ extern "C" int fg_runoff_create(int nx_in, int ny_in, const double *lonb_in, con
   fg_runoff *h = nullptr;
   int rc = ro_new("fg_runoff_create", nx_in, ny_in, nx_out, ny_out, xt, yt, mask_out, area_out, device, out, &h);
   if (rc) return rc;
-  if (!lonb_in || !latb_in || !mask_in || !xc || !yc) { fg_runoff_destroy(h); return ro_fail(FG_ERR_ARG, "fg_runoff_create: null argument"); }
-  const double t0 = ro_now_ms();
+  if (!lonb_in || !latb_in || !mask_in || !xc || !yc) { fg_runoff_destroy(h); return fg_fail(FG_ERR_ARG, "fg_runoff_create: null argument"); }
+  const double t0 = fg_now_ms();
   // setup_remap :472: the box grid is the source, the list comes back as (box i, box j, quad i, quad j) = (i_in, j_in, i_out, j_out)
   const long nx = fg_box_xgrid_lists(device, 1, FG_CONSERVE_ORDER1, nx_in, ny_in, lonb_in, latb_in, nx_out, ny_out, xc, yc, mask_in,
                                      h->xi, h->xarea, nullptr, nullptr);
@@ -299,7 +251,7 @@ extern "C" int fg_runoff_create(int nx_in, int ny_in, const double *lonb_in, con
   if (prc >= 0) prc = fg_plan_get_cell_area(pl, area_in.data(), nullptr);
   if (pl) fg_plan_destroy(pl);
   if (prc < 0) { fg_runoff_destroy(h); return (int)prc; }
-  h->ms[0] = (float)(ro_now_ms() - t0);
+  h->ms[0] = (float)(fg_now_ms() - t0);
   rc = ro_setup(h, mask_in, area_in.data(), xt, yt, mask_out, area_out);
   if (rc) { fg_runoff_destroy(h); return rc; }
   *out = h;
@@ -311,7 +263,7 @@ extern "C" void *fg_runoff_stream(fg_runoff *h) { return h ? (void *)h->stream :
 
 extern "C" int fg_runoff_get_xgrid(const fg_runoff *h, int *i_in, int *j_in, int *i_out, int *j_out, double *xgrid_area)
 {
-  if (!h) return ro_fail(FG_ERR_ARG, "fg_runoff_get_xgrid: null handle");
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_runoff_get_xgrid: null handle");
   int *dst[4] = {i_in, j_in, i_out, j_out};
   for (int k = 0; k < 4; k++) if (dst[k]) memcpy(dst[k], h->xi[k].data(), h->xi[k].size() * sizeof(int));
   if (xgrid_area) memcpy(xgrid_area, h->xarea.data(), h->xarea.size() * sizeof(double));
@@ -320,7 +272,7 @@ extern "C" int fg_runoff_get_xgrid(const fg_runoff *h, int *i_in, int *j_in, int
 
 extern "C" int fg_runoff_get_maps(const fg_runoff *h, int *imap, int *jmap)
 {
-  if (!h || !imap || !jmap) return ro_fail(FG_ERR_ARG, "fg_runoff_get_maps: null argument");
+  if (!h || !imap || !jmap) return fg_fail(FG_ERR_ARG, "fg_runoff_get_maps: null argument");
   memcpy(imap, h->imap.data(), h->imap.size() * sizeof(int));
   memcpy(jmap, h->jmap.data(), h->jmap.size() * sizeof(int));
   return 0;
@@ -328,55 +280,55 @@ extern "C" int fg_runoff_get_maps(const fg_runoff *h, int *imap, int *jmap)
 
 extern "C" int fg_runoff_get_xyz(fg_runoff *h, double *x, double *y, double *z)
 {
-  if (!h || !x || !y || !z) return ro_fail(FG_ERR_ARG, "fg_runoff_get_xyz: null argument");
+  if (!h || !x || !y || !z) return fg_fail(FG_ERR_ARG, "fg_runoff_get_xyz: null argument");
   const size_t n = (size_t)h->nx_out * h->ny_out;
-  ROCHK(hipSetDevice(h->device));
-  ROCHK(hipMemcpy(x, h->d_xyz, n * sizeof(double), hipMemcpyDeviceToHost));
-  ROCHK(hipMemcpy(y, h->d_xyz + n, n * sizeof(double), hipMemcpyDeviceToHost));
-  ROCHK(hipMemcpy(z, h->d_xyz + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost));
+  FGCHK(hipSetDevice(h->device));
+  FGCHK(hipMemcpy(x, h->d_xyz, n * sizeof(double), hipMemcpyDeviceToHost));
+  FGCHK(hipMemcpy(y, h->d_xyz + n, n * sizeof(double), hipMemcpyDeviceToHost));
+  FGCHK(hipMemcpy(z, h->d_xyz + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int fg_runoff_search_stats(const fg_runoff *h, long *stats)
 {
-  if (!h || !stats) return ro_fail(FG_ERR_ARG, "fg_runoff_search_stats: null argument");
+  if (!h || !stats) return fg_fail(FG_ERR_ARG, "fg_runoff_search_stats: null argument");
   memcpy(stats, h->stats, sizeof h->stats);
   return 0;
 }
 
 extern "C" int fg_runoff_phase_ms(const fg_runoff *h, float *ms, int n)
 {
-  if (!h || !ms || n < 0) return ro_fail(FG_ERR_ARG, "fg_runoff_phase_ms: bad argument");
+  if (!h || !ms || n < 0) return fg_fail(FG_ERR_ARG, "fg_runoff_phase_ms: bad argument");
   for (int k = 0; k < n && k < 5; k++) ms[k] = h->ms[k];
   return 0;
 }
 
 extern "C" int fg_runoff_apply_dev(fg_runoff *h, const double *d_in, double *d_out, double *totals)
 {
-  if (!h || !d_in || !d_out) return ro_fail(FG_ERR_ARG, "fg_runoff_apply_dev: null argument");
-  if (d_in == d_out) return ro_fail(FG_ERR_ARG, "fg_runoff_apply_dev: in and out must be different arrays");
-  ROCHK(hipSetDevice(h->device));
+  if (!h || !d_in || !d_out) return fg_fail(FG_ERR_ARG, "fg_runoff_apply_dev: null argument");
+  if (d_in == d_out) return fg_fail(FG_ERR_ARG, "fg_runoff_apply_dev: in and out must be different arrays");
+  FGCHK(hipSetDevice(h->device));
   fgd_ro_apply(h->a, d_in, h->d_tmp, d_out, h->d_totals, h->stream);
-  ROCHK(hipGetLastError());
+  FGCHK(hipGetLastError());
   if (totals) {
-    ROCHK(hipMemcpyAsync(totals, h->d_totals, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    ROCHK(hipStreamSynchronize(h->stream));
+    FGCHK(hipMemcpyAsync(totals, h->d_totals, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    FGCHK(hipStreamSynchronize(h->stream));
   }
   return 0;
 }
 
 extern "C" int fg_runoff_apply(fg_runoff *h, const double *in, double *out, double *totals)
 {
-  if (!h || !in || !out) return ro_fail(FG_ERR_ARG, "fg_runoff_apply: null argument");
-  ROCHK(hipSetDevice(h->device));
+  if (!h || !in || !out) return fg_fail(FG_ERR_ARG, "fg_runoff_apply: null argument");
+  FGCHK(hipSetDevice(h->device));
   const size_t n_in = (size_t)h->nx_in * h->ny_in, n = (size_t)h->nx_out * h->ny_out;
-  RoDev t;
+  FgDev t;
   double *d_in = t.put(in, n_in), *d_out = t.get<double>(n);
-  if (!d_in || !d_out) return ro_fail(FG_ERR_HIP, "fg_runoff_apply: device allocation or upload failed");
+  if (!d_in || !d_out) return fg_fail(FG_ERR_HIP, "fg_runoff_apply: device allocation or upload failed");
   double tot[2];
   int rc = fg_runoff_apply_dev(h, d_in, d_out, tot);                 // synchronises the handle's stream
   if (rc) return rc;
-  ROCHK(hipMemcpy(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost));
+  FGCHK(hipMemcpy(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost));
   if (totals) { totals[0] = tot[0]; totals[1] = tot[1]; }
   return 0;
 }

@@ -4,12 +4,14 @@
 //
 // k_ro_xyz       lon, lat -> the point triple of distance(), once per point (the reference forms it once per PAIR)
 // k_ro_compact   the ocean points' triples and indices, gathered in row-major order into tiles of RO_TILE
-// k_ro_balls     a bounding ball per tile and per group of RO_GROUP tiles
-// k_ro_nearest   one wave per land query: the lexicographic minimum of (r, index) over the ocean points with r < r0
+// k_ro_tile_balls / k_ro_group_balls   a bounding ball per tile and per group of RO_GROUP tiles
+// k_ro_nearest   one wave per land query: the lexicographic minimum of (r, index) over the ocean points with r < r0; the
+//                walk over the balls is ball_walk.hip.h's, shared with rland_kernels.hip
 // k_ro_remap / k_ro_move / k_ro_totals   process_data's three loops and its two sums
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "runoff.h"
+#include "ball_walk.hip.h"
 
 __global__ void __launch_bounds__(256) k_ro_xyz(long n, const double *__restrict__ lon, const double *__restrict__ lat,
                                                  double *__restrict__ x, double *__restrict__ y, double *__restrict__ z)
@@ -67,15 +69,6 @@ __global__ void __launch_bounds__(256) k_ro_group_balls(int ntiles, int ngroups,
   gball[g] = b;
 }
 
-// true: no member of the ball can reach (r, any index).  d - rad is a lower bound of every member's chord up to 2^-47 in all
-// (the roundings of d, of the difference and of the member's own r); the margin makes the comparison strict with room to
-// spare, so a member with r == best.r is never discarded.  NaN anywhere gives false.
-__device__ __forceinline__ bool ro_skip(const RoBall &b, double qx, double qy, double qz, double rbest)
-{
-  const double d = sqrt(ro_sumsq(qx, qy, qz, b.x, b.y, b.z));
-  return (d - b.rad) - RO_MARGIN > rbest;
-}
-
 // all lanes leave with the wave's minimum of (r, idx)
 __device__ __forceinline__ void ro_wave_min(RoBest &b)
 {
@@ -90,63 +83,44 @@ __device__ __forceinline__ void ro_wave_min(RoBest &b)
 template <bool PRUNE>
 __global__ void __launch_bounds__(64 * RO_WAVES) k_ro_nearest(RoSearch p)
 {
-  const int q = (blockIdx.x * (64 * RO_WAVES) + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  const BwLane l = bw_lane();
+  const int q = l.wave;
   if (q >= p.nq) return;                                   // whole waves leave: no block-wide barrier below
   const int qi = p.qindex[q];
   const double qx = p.x[qi], qy = p.y[qi], qz = p.z[qi];
-  const int sub = lane / RO_TILE, e = lane % RO_TILE;      // a visit takes 64 / RO_TILE tiles, one per lane group
-  constexpr int NSUB = 64 / RO_TILE;
   RoBest b = ro_best_init(p.r0);
   int nvis = 0;
   bool dirty = false;                                      // this lane's minimum changed since the last ro_wave_min
   auto visit = [&](int t) {                                // t < 0: this lane group idles
     if (t >= 0) {
-      const RoPoint pt = p.pts[(size_t)t * RO_TILE + e];
+      const RoPoint pt = p.pts[(size_t)t * RO_TILE + l.e];
       const int was = b.idx;
       ro_consider(b, ro_sumsq(qx, qy, qz, pt.x, pt.y, pt.z), pt.idx);
       dirty |= b.idx != was;                               // a new minimum is another point
     }
   };
+  auto settle = [&]() {                                    // the lanes agree again: true if some lane's minimum had changed
+    if (!__any(dirty)) return false;
+    ro_wave_min(b);
+    dirty = false;
+    return true;
+  };
   if (PRUNE) {
     // Seed: the tiles around the query's own rank in the compacted list, and around the ranks of its northern and southern
-    // neighbours' indices.  The scan below visits every tile the bound does not exclude, these again if need be, so the seed
-    // only makes the bound tight from the start.
+    // neighbours' indices.  The walk visits every tile the bound does not exclude, these again if need be, so the seed only
+    // makes the bound tight from the start.
     for (int k = -1; k <= 1; k++) {
       long g = (long)qi + (long)k * p.nlon;
       g = g < 0 ? 0 : (g > p.n ? p.n : g);
-      const int t = min(p.orank[g] / RO_TILE, p.ntiles - 1) - 1 + sub;
-      visit(sub < 3 && t >= 0 && t < p.ntiles ? t : -1);
+      const int t = min(p.orank[g] / RO_TILE, p.ntiles - 1) - 1 + l.sub;
+      visit(l.sub < 3 && t >= 0 && t < p.ntiles ? t : -1);
       nvis += 3;
     }
     ro_wave_min(b);
     dirty = false;
-    for (int g0 = 0; g0 < p.ngroups; g0 += 64) {
-      const int g = g0 + lane;
-      unsigned long long gm = __ballot(g < p.ngroups && !ro_skip(p.gball[g], qx, qy, qz, b.r));
-      bool improved = false;                                          // since this ballot (uniform)
-      while (gm) {
-        const int gg = g0 + __builtin_ctzll(gm);
-        gm &= gm - 1;
-        if (improved && ro_skip(p.gball[gg], qx, qy, qz, b.r)) continue;
-        const int t = gg * RO_GROUP + lane;
-        unsigned long long tm = __ballot(t < p.ntiles && !ro_skip(p.ball[t], qx, qy, qz, b.r));
-        if (!tm) continue;
-        while (tm) {
-          int mine = -1;
-#pragma unroll
-          for (int k = 0; k < NSUB; k++)
-            if (tm) { const int bit = __builtin_ctzll(tm); tm &= tm - 1; nvis++; if (sub == k) mine = gg * RO_GROUP + bit; }
-          visit(mine);
-        }
-        if (__any(dirty)) { ro_wave_min(b); dirty = false; improved = true; }   // the lanes agree again before the next bound test
-      }
-    }
-  } else {
-    for (int t0 = 0; t0 < p.ntiles; t0 += NSUB) visit(t0 + sub < p.ntiles ? t0 + sub : -1);
-    nvis = p.ntiles;
-    ro_wave_min(b);
   }
-  if (lane == 0) {
+  nvis += bw_walk<PRUNE>(p.gball, p.ball, p.ngroups, p.ntiles, qx, qy, qz, l, [&]() { return b.r; }, visit, settle);
+  if (l.lane == 0) {
     p.iout[q] = b.idx < 0 ? -1 : b.idx % p.nlon;
     p.jout[q] = b.idx < 0 ? -1 : b.idx / p.nlon;
     p.visited[q] = nvis;
@@ -192,22 +166,18 @@ void fgd_ro_xyz(long n, const double *lon, const double *lat, double *x, double 
 {
   if (n > 0) hipLaunchKernelGGL(k_ro_xyz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, lon, lat, x, y, z);
 }
-void fgd_ro_compact(int nocean, int ntiles, const int *oidx, const double *x, const double *y, const double *z, RoPoint *pts, hipStream_t st)
+void fgd_ro_tiles(int npoints, const int *oidx, const double *x, const double *y, const double *z, RoPoint *pts, RoBall *ball,
+                  RoBall *gball, hipStream_t st)
 {
-  const int npad = ntiles * RO_TILE;
-  hipLaunchKernelGGL(k_ro_compact, dim3((npad + 255) / 256), dim3(256), 0, st, nocean, npad, oidx, x, y, z, pts);
-}
-void fgd_ro_balls(int ntiles, int ngroups, const RoPoint *pts, RoBall *ball, RoBall *gball, hipStream_t st)
-{
-  hipLaunchKernelGGL(k_ro_tile_balls, dim3((ntiles + 255) / 256), dim3(256), 0, st, ntiles, pts, ball);
-  hipLaunchKernelGGL(k_ro_group_balls, dim3((ngroups + 255) / 256), dim3(256), 0, st, ntiles, ngroups, ball, gball);
+  const RoTiles t = ro_tiles_of(npoints);
+  const int npad = t.ntiles * RO_TILE;
+  hipLaunchKernelGGL(k_ro_compact, dim3((npad + 255) / 256), dim3(256), 0, st, npoints, npad, oidx, x, y, z, pts);
+  hipLaunchKernelGGL(k_ro_tile_balls, dim3((t.ntiles + 255) / 256), dim3(256), 0, st, t.ntiles, pts, ball);
+  hipLaunchKernelGGL(k_ro_group_balls, dim3((t.ngroups + 255) / 256), dim3(256), 0, st, t.ntiles, t.ngroups, ball, gball);
 }
 void fgd_ro_nearest(const RoSearch &p, int prune, hipStream_t st)
 {
-  if (p.nq < 1) return;
-  const dim3 grid((p.nq + RO_WAVES - 1) / RO_WAVES), block(64 * RO_WAVES);
-  if (prune) hipLaunchKernelGGL(k_ro_nearest<true>, grid, block, 0, st, p);
-  else hipLaunchKernelGGL(k_ro_nearest<false>, grid, block, 0, st, p);
+  bw_launch(k_ro_nearest<true>, k_ro_nearest<false>, prune, p.nq, st, p);
 }
 void fgd_ro_apply(const RoApply &a, const double *in, double *tmp, double *out, double *totals, hipStream_t st)
 {

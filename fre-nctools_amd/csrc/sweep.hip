@@ -15,22 +15,17 @@
 #include <string.h>
 #include <string>
 #include <vector>
-#include "fregrid_hip.h"
+#include "fg_host.h"
 
 extern "C" int fg_plan_order(const fg_plan *pl);
 extern "C" long fg_plan_ncells_out(const fg_plan *pl);
 extern "C" int fg_plan_device(const fg_plan *pl);
-void fg_set_last_error(const char *msg);         // plan.hip
 // run-scoped use of our compute stream by the plans and the gradient object (plan.hip)
 int fg_plan_borrow_stream(fg_plan *pl, void *stream, void **saved, int *saved_own);
 void fg_plan_return_stream(fg_plan *pl, void *saved, int saved_own);
 int fg_plan_is_finalized(const fg_plan *pl);
 int fg_c2l_borrow_stream(fg_c2l *h, void *stream, void **saved, int *saved_own);
 void fg_c2l_return_stream(fg_c2l *h, void *saved, int saved_own);
-
-static int sw_fail(int code, const char *msg) { fg_set_last_error(msg); return code; }
-#define SWCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { char b_[256]; \
-  snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return sw_fail(FG_ERR_HIP, b_); } } while (0)
 
 namespace {
 constexpr int NSLOT = 3;       // buffer slots in flight
@@ -75,7 +70,7 @@ bool is_pinned(const void *p)
 // (integration/field_io_hip.c).  Synchronous (null stream + device sync).
 extern "C" int fg_dev_widen(int nc_type, long n, const void *raw_dev, double scale, double offset, double missing, double *out_dev)
 {
-  if (n < 0 || (n > 0 && (!raw_dev || !out_dev)) || !type_size(nc_type)) return sw_fail(FG_ERR_ARG, "fg_dev_widen: bad argument");
+  if (n < 0 || (n > 0 && (!raw_dev || !out_dev)) || !type_size(nc_type)) return fg_fail(FG_ERR_ARG, "fg_dev_widen: bad argument");
   if (n == 0) return 0;
   const int grid = (int)((n + 255) / 256);
   switch (nc_type) {
@@ -84,13 +79,13 @@ extern "C" int fg_dev_widen(int nc_type, long n, const void *raw_dev, double sca
     case FG_NC_FLOAT: k_widen<float><<<grid, 256>>>(n, (const float *)raw_dev, scale, offset, missing, out_dev); break;
     default: k_widen<double><<<grid, 256>>>(n, (const double *)raw_dev, scale, offset, missing, out_dev); break;
   }
-  SWCHK(hipGetLastError());
-  SWCHK(hipDeviceSynchronize());
+  FGCHK(hipGetLastError());
+  FGCHK(hipDeviceSynchronize());
   return 0;
 }
 extern "C" int fg_dev_narrow(int nc_type, long n, const double *in_dev, double scale, double offset, double missing, void *out_dev)
 {
-  if (n < 0 || (n > 0 && (!in_dev || !out_dev)) || !type_size(nc_type)) return sw_fail(FG_ERR_ARG, "fg_dev_narrow: bad argument");
+  if (n < 0 || (n > 0 && (!in_dev || !out_dev)) || !type_size(nc_type)) return fg_fail(FG_ERR_ARG, "fg_dev_narrow: bad argument");
   if (n == 0) return 0;
   const int grid = (int)((n + 255) / 256);
   switch (nc_type) {
@@ -99,8 +94,8 @@ extern "C" int fg_dev_narrow(int nc_type, long n, const double *in_dev, double s
     case FG_NC_FLOAT: k_narrow<float><<<grid, 256>>>(n, in_dev, scale, offset, missing, (float *)out_dev); break;
     default: k_narrow<double><<<grid, 256>>>(n, in_dev, scale, offset, missing, (double *)out_dev); break;
   }
-  SWCHK(hipGetLastError());
-  SWCHK(hipDeviceSynchronize());
+  FGCHK(hipGetLastError());
+  FGCHK(hipDeviceSynchronize());
   return 0;
 }
 
@@ -153,24 +148,24 @@ extern "C" void fg_sweep_destroy(fg_sweep *sw)
 
 extern "C" int fg_sweep_create(int nplans, fg_plan *const *plans, fg_c2l *c2l, int in_type, int out_type, fg_sweep **out)
 {
-  if (nplans < 1 || !plans || !out) return sw_fail(FG_ERR_ARG, "fg_sweep_create: null argument");
-  if (!type_size(in_type) || !type_size(out_type)) return sw_fail(FG_ERR_ARG, "fg_sweep_create: types must be FG_NC_SHORT, FG_NC_INT, FG_NC_FLOAT or FG_NC_DOUBLE");
+  if (nplans < 1 || !plans || !out) return fg_fail(FG_ERR_ARG, "fg_sweep_create: null argument");
+  if (!type_size(in_type) || !type_size(out_type)) return fg_fail(FG_ERR_ARG, "fg_sweep_create: types must be FG_NC_SHORT, FG_NC_INT, FG_NC_FLOAT or FG_NC_DOUBLE");
   fg_sweep *sw = new fg_sweep();
   sw->in_type = in_type; sw->out_type = out_type; sw->in_sz = type_size(in_type); sw->out_sz = type_size(out_type);
   sw->order = fg_plan_order(plans[0]); sw->device = fg_plan_device(plans[0]); sw->ncin = fg_plan_ncells_in(plans[0]);
   for (int p = 0; p < nplans; p++) {
     if (!plans[p] || fg_plan_order(plans[p]) != sw->order || fg_plan_ncells_in(plans[p]) != sw->ncin || fg_plan_device(plans[p]) != sw->device) {
-      delete sw; return sw_fail(FG_ERR_ARG, "fg_sweep_create: the plans must share order, source grid and device");
+      delete sw; return fg_fail(FG_ERR_ARG, "fg_sweep_create: the plans must share order, source grid and device");
     }
     sw->plans.push_back(plans[p]);
     sw->doff.push_back(sw->ndst_total * CHUNK);
     sw->ndst.push_back(fg_plan_ncells_out(plans[p]));
     sw->ndst_total += sw->ndst.back();
   }
-  if (sw->order == 2 && !c2l) { delete sw; return sw_fail(FG_ERR_ARG, "fg_sweep_create: conserve_order2 plans need the gradient object (fg_c2l)"); }
-  if (sw->order == 2 && fg_c2l_ncells(c2l) != sw->ncin) { delete sw; return sw_fail(FG_ERR_ARG, "fg_sweep_create: the gradient object belongs to another grid"); }
+  if (sw->order == 2 && !c2l) { delete sw; return fg_fail(FG_ERR_ARG, "fg_sweep_create: conserve_order2 plans need the gradient object (fg_c2l)"); }
+  if (sw->order == 2 && fg_c2l_ncells(c2l) != sw->ncin) { delete sw; return fg_fail(FG_ERR_ARG, "fg_sweep_create: the gradient object belongs to another grid"); }
   sw->c2l = (sw->order == 2) ? c2l : nullptr;
-  if (hipSetDevice(sw->device) != hipSuccess) { delete sw; return sw_fail(FG_ERR_HIP, "hipSetDevice failed"); }
+  if (hipSetDevice(sw->device) != hipSuccess) { delete sw; return fg_fail(FG_ERR_HIP, "hipSetDevice failed"); }
   bool ok = hipStreamCreateWithFlags(&sw->s_in, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithFlags(&sw->s_comp, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithFlags(&sw->s_out, hipStreamNonBlocking) == hipSuccess;
@@ -184,7 +179,7 @@ extern "C" int fg_sweep_create(int nplans, fg_plan *const *plans, fg_c2l *c2l, i
   ok = ok && hipMalloc((void **)&sw->d_f64, nin * 8) == hipSuccess && hipMalloc((void **)&sw->d_tmp, nout * 8) == hipSuccess;
   if (sw->order == 2) ok = ok && hipMalloc((void **)&sw->d_rec, (size_t)sw->ncin * 3 * 8 * 8) == hipSuccess &&
                            hipMalloc((void **)&sw->d_bits, (size_t)(sw->ncin > 0 ? sw->ncin : 1)) == hipSuccess;
-  if (!ok) { (void)hipGetLastError(); fg_sweep_destroy(sw); return sw_fail(FG_ERR_HIP, "fg_sweep_create: out of device memory (or stream / event creation failed)"); }
+  if (!ok) { (void)hipGetLastError(); fg_sweep_destroy(sw); return fg_fail(FG_ERR_HIP, "fg_sweep_create: out of device memory (or stream / event creation failed)"); }
   *out = sw;
   return 0;
 }
@@ -193,7 +188,7 @@ extern "C" int fg_sweep_create(int nplans, fg_plan *const *plans, fg_c2l *c2l, i
 static int slot_retire(fg_sweep *sw, fg_sweep::Slot &sl, void *const *host_out)
 {
   if (!sl.busy) return 0;
-  SWCHK(hipEventSynchronize(sl.e_out));
+  FGCHK(hipEventSynchronize(sl.e_out));
   if (sl.staged_out)
     for (size_t p = 0; p < sw->plans.size(); p++)
       memcpy((char *)host_out[p] + (size_t)sl.l0 * sw->ndst[p] * sw->out_sz, (char *)sl.pin_out + (size_t)sw->doff[p] * sw->out_sz,
@@ -206,11 +201,11 @@ static int slot_retire(fg_sweep *sw, fg_sweep::Slot &sl, void *const *host_out)
 static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
                      void *const *host_out, bool masked)
 {
-  if (!sw || !host_in || !host_out || nlev < 1) return sw_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null argument" : "fg_sweep_run: null argument");
-  for (size_t p = 0; p < sw->plans.size(); p++) if (!host_out[p]) return sw_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null output array" : "fg_sweep_run: null output array");
+  if (!sw || !host_in || !host_out || nlev < 1) return fg_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null argument" : "fg_sweep_run: null argument");
+  for (size_t p = 0; p < sw->plans.size(); p++) if (!host_out[p]) return fg_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null output array" : "fg_sweep_run: null output array");
   if (masked)
-    for (fg_plan *p : sw->plans) if (!fg_plan_is_finalized(p)) return sw_fail(FG_ERR_ARG, "fg_sweep_run_levels: a plan is not finalized (fg_plan_finalize)");
-  SWCHK(hipSetDevice(sw->device));
+    for (fg_plan *p : sw->plans) if (!fg_plan_is_finalized(p)) return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels: a plan is not finalized (fg_plan_finalize)");
+  FGCHK(hipSetDevice(sw->device));
   // The plans and the gradient object launch on OUR compute stream for the duration of this call only: several fg_sweep objects
   // (one per pair of file types) may share the same plans, a plan may be used directly between two runs, and either may be
   // destroyed before the other.  On every way out -- errors included -- the three streams are drained, the borrowed streams
@@ -246,14 +241,14 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
     const size_t bytes_in = (size_t)nl * sw->ncin * sw->in_sz;
     const char *src = (const char *)host_in + (size_t)l0 * sw->ncin * sw->in_sz;
     if (!in_pinned) {
-      if (!sl.pin_in) SWCHK(hipHostMalloc(&sl.pin_in, nin * sw->in_sz, hipHostMallocDefault));
+      if (!sl.pin_in) FGCHK(hipHostMalloc(&sl.pin_in, nin * sw->in_sz, hipHostMallocDefault));
       memcpy(sl.pin_in, src, bytes_in);
       src = (const char *)sl.pin_in;
     }
-    SWCHK(hipMemcpyAsync(sl.d_raw, src, bytes_in, hipMemcpyHostToDevice, sw->s_in));
-    SWCHK(hipEventRecord(sl.e_in, sw->s_in));
+    FGCHK(hipMemcpyAsync(sl.d_raw, src, bytes_in, hipMemcpyHostToDevice, sw->s_in));
+    FGCHK(hipEventRecord(sl.e_in, sw->s_in));
     // --- widen, (gradients,) sweep, narrow (compute stream)
-    SWCHK(hipStreamWaitEvent(sw->s_comp, sl.e_in, 0));
+    FGCHK(hipStreamWaitEvent(sw->s_comp, sl.e_in, 0));
     const long n_in = (long)nl * sw->ncin;
     const double *f64 = (const double *)sl.d_raw;
     if (widen) {
@@ -295,17 +290,17 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
         }
       }
     }
-    SWCHK(hipGetLastError());
-    SWCHK(hipEventRecord(sl.e_comp, sw->s_comp));
+    FGCHK(hipGetLastError());
+    FGCHK(hipEventRecord(sl.e_comp, sw->s_comp));
     // --- download (copy-out stream)
-    SWCHK(hipStreamWaitEvent(sw->s_out, sl.e_comp, 0));
-    if (!out_pinned && !sl.pin_out) SWCHK(hipHostMalloc(&sl.pin_out, nout * sw->out_sz, hipHostMallocDefault));
+    FGCHK(hipStreamWaitEvent(sw->s_out, sl.e_comp, 0));
+    if (!out_pinned && !sl.pin_out) FGCHK(hipHostMalloc(&sl.pin_out, nout * sw->out_sz, hipHostMallocDefault));
     for (size_t p = 0; p < sw->plans.size(); p++) {
       const size_t b = (size_t)nl * sw->ndst[p] * sw->out_sz;
       char *dst = out_pinned ? (char *)host_out[p] + (size_t)l0 * sw->ndst[p] * sw->out_sz : (char *)sl.pin_out + (size_t)sw->doff[p] * sw->out_sz;
-      SWCHK(hipMemcpyAsync(dst, (const char *)sl.d_fin + (size_t)sw->doff[p] * sw->out_sz, b, hipMemcpyDeviceToHost, sw->s_out));
+      FGCHK(hipMemcpyAsync(dst, (const char *)sl.d_fin + (size_t)sw->doff[p] * sw->out_sz, b, hipMemcpyDeviceToHost, sw->s_out));
     }
-    SWCHK(hipEventRecord(sl.e_out, sw->s_out));
+    FGCHK(hipEventRecord(sl.e_out, sw->s_out));
     sl.busy = true; sl.l0 = l0; sl.nl = nl; sl.staged_out = !out_pinned;
   }
   // drain in chunk order

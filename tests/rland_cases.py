@@ -194,7 +194,7 @@ def hostcheck(tmpdir, c):
 
 
 def thinned_source(nsrc, n=1200, seed=11):
-    """1200 points over the sphere in 3 faces of 400 with exactly `nsrc` unmasked, chosen by a seeded permutation"""
+    """`n` points (1200) over the sphere in 3 faces of n / 3 with exactly `nsrc` unmasked, chosen by a seeded permutation"""
     lon, lat = sphere_points(n, 0.25)
     mask = np.zeros(n, dtype=np.int32)
     mask[np.random.default_rng(seed).permutation(n)[:nsrc]] = 1

@@ -63,12 +63,15 @@ def test_maps_equal_the_reference(fg, fixtures, host, name, prune):
 
 def test_tile_edges_pruned_equals_brute_force_equals_host_build(fg, gpu_ok, tmp_path):
     """unmasked source counts 1, T-1, T, T+1, 2T+1 and 64T+1 (one past a full ballot step) on 1200 points in three faces; 173
-    queries over the whole sphere, no multiple of the four queries of a block"""
+    queries over the whole sphere, no multiple of the four queries of a block.  Then (64 * 64 + 64) T + 1 of 66900 points: one
+    tile past 65 groups, so the walk's group ballot runs a second time, over one full group and one group of a single one-point
+    tile."""
     T = fg.rland_tile()
-    assert 64 * T + 1 < 1200
+    big = (64 * 64 + 64) * T + 1
+    assert 64 * T + 1 < 1200 and big < 66900
     qlon, qlat = rc.sphere_points(173, 0.7)
-    for nsrc in (1, T - 1, T, T + 1, 2 * T + 1, 64 * T + 1):
-        lon, lat, mask = rc.thinned_source(nsrc)
+    for nsrc, n in [(k, 1200) for k in (1, T - 1, T, T + 1, 2 * T + 1, 64 * T + 1)] + [(big, 66900)]:
+        lon, lat, mask = rc.thinned_source(nsrc, n=n)
         c = dict(lon_src=lon, lat_src=lat, mask_src=mask, lon_dst=qlon, lat_dst=qlat, mask_dst=np.ones(173, dtype=np.int32), iface_dst=-1)
         ref = rc.hostcheck(tmp_path, c)
         got = {}
@@ -80,6 +83,8 @@ def test_tile_edges_pruned_equals_brute_force_equals_host_build(fg, gpu_ok, tmp_
                 assert st["tiles"] == -(-nsrc // T) and st["fallback"] == ref["fallback"], (nsrc, prune, st)
                 if prune:
                     assert st["tiles_visited_survivors"] <= st["queries"] * st["tiles"]
+                if prune and nsrc == big:
+                    assert st["tiles"] > 64 * 64 and st["tiles_visited"] < st["queries"] * st["tiles"], st
         for prune in (1, 0):
             assert np.array_equal(got[prune][0], ref["idx_map"]) and np.array_equal(got[prune][1], ref["face_map"]), (nsrc, prune)
         assert np.all(mask[got[1][1], got[1][0]] != 0)

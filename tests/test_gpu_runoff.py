@@ -30,10 +30,11 @@ def _xgrid(fx):
 
 
 def _regular(mask):
-    """a handle on the 40 x 30 regular grid with the given mask and an empty exchange list"""
-    x, y = np.meshgrid((np.arange(NX) + 0.5) * (2 * np.pi / NX), -np.pi / 2 + (np.arange(NY) + 0.5) * (np.pi / NY))
+    """a handle on the regular grid of the mask's shape with the given mask and an empty exchange list"""
+    ny, nx = mask.shape
+    x, y = np.meshgrid((np.arange(nx) + 0.5) * (2 * np.pi / nx), -np.pi / 2 + (np.arange(ny) + 0.5) * (np.pi / ny))
     gi = dict(nx=2, ny=2, mask=np.ones((2, 2)), area=np.ones((2, 2)))
-    go = dict(nx=NX, ny=NY, xt=x, yt=y, mask=mask, area=np.ones((NY, NX)))
+    go = dict(nx=nx, ny=ny, xt=x, yt=y, mask=mask, area=np.ones((ny, nx)))
     e = np.zeros(0, dtype=np.int32)
     return gi, go, (e, e, e, e, np.zeros(0))
 
@@ -69,11 +70,14 @@ def test_maps_equal_the_reference(fg, fixtures, name, prune):
 
 def test_tile_edges_pruned_equals_brute_force_equals_numpy(fg, gpu_ok):
     """ocean counts 1, T-1, T, T+1, 2T+1 and 64T+1 (one past a full ballot step) on 1200 cells; the land counts 1199, 1185, 1183,
-    1167 and 175 are no multiples of the four queries of a block, 1184 is."""
+    1167 and 175 are no multiples of the four queries of a block, 1184 is.  Then (64 * 64 + 64) T + 1 ocean cells of 300 x 223:
+    one tile past 65 groups, so the walk's group ballot runs a second time, over one full group and one group of a single
+    one-point tile; 339 land queries at T = 16."""
     T = fg.runoff_tile()
-    assert 64 * T + 1 < NX * NY
-    for nocean in (1, T - 1, T, T + 1, 2 * T + 1, 64 * T + 1):
-        mask = rc.thinned_mask(nocean, NX, NY)
+    big = (64 * 64 + 64) * T + 1
+    assert 64 * T + 1 < NX * NY and big < 300 * 223
+    for nocean, nx, ny in [(k, NX, NY) for k in (1, T - 1, T, T + 1, 2 * T + 1, 64 * T + 1)] + [(big, 300, 223)]:
+        mask = rc.thinned_mask(nocean, nx, ny)
         gi, go, xg = _regular(mask)
         got = {}
         for prune in (1, 0):
@@ -81,7 +85,10 @@ def test_tile_edges_pruned_equals_brute_force_equals_numpy(fg, gpu_ok):
             with fg.RunoffRegrid(gi, go, xgrid=xg) as h:
                 got[prune] = h.maps()
                 xyz = h.xyz()
-                assert h.search_stats()["tiles"] == -(-nocean // T)
+                st = h.search_stats()
+                assert st["tiles"] == -(-nocean // T)
+                if prune and nocean == big:
+                    assert st["tiles"] > 64 * 64 and st["tiles_visited"] < st["queries"] * st["tiles"], st
         assert np.array_equal(got[1][0], got[0][0]) and np.array_equal(got[1][1], got[0][1]), nocean
         ref = _numpy_nearest(*xyz, mask)
         assert np.array_equal(got[1][0], ref[0]) and np.array_equal(got[1][1], ref[1]), nocean
