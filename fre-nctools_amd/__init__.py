@@ -20,6 +20,8 @@ mirrors the reference's call signatures:
 * ``RiverRegrid`` / ``river_source_grid`` / ``river_land_frac``
   -- tools/river_regrid/river_regrid.c:694,880,991,1298,1180,352,544 (calc_max_subA, calc_tocell, calc_river_data, sort_basin,
      check_river_data, the source bounds, the land fraction thresholds)
+* ``Topog`` / ``create_realistic_topog`` / ``zw_from_zeta``
+  -- tools/make_topog/topog.c:355,551,687,830,878,987 (create_realistic_topog with filter_topo, process_topo and its adjustments)
 
 There is NO CPU fallback: if the shared library is missing, or no HIP device is visible
 when a compute entry point is called, an exception is raised.
@@ -46,6 +48,7 @@ from .runoff import (RunoffRegrid, nearest_unmasked, runoff_input_grid, runoff_o
 from .remap_land import LandNearest, set_rland_prune, rland_tile  # noqa: F401
 from .river import (RiverRegrid, river_source_grid, river_land_frac, set_river_prune, river_qsort_index,  # noqa: F401
                     river_sort_basin)
+from .topog import Topog, create_realistic_topog, zw_from_zeta, topog_source_rows, set_topog_sweep  # noqa: F401
 from .parallel import (band_rows, row_cost, allreduce_cell_sums, allreduce_scalar_sum, allreduce_minmax,  # noqa: F401
                        boundary_source_cells, allreduce_cell_sums_sparse, ordered_cell_sums, CellSumExchange)
 from .conserve_interp import (  # noqa: F401
@@ -65,6 +68,7 @@ __all__ = [
     "RunoffRegrid", "nearest_unmasked", "runoff_input_grid", "runoff_output_grid",
     "LandNearest",
     "RiverRegrid", "river_source_grid", "river_land_frac",
+    "Topog", "create_realistic_topog", "zw_from_zeta",
 ]
 
 

@@ -62,7 +62,20 @@ EXPORTS = [
     "fg_rland_phase_ms", "fg_set_rland_prune", "fg_rland_tile",
     "fg_river_create", "fg_river_destroy", "fg_river_stream", "fg_river_run", "fg_river_get", "fg_river_get_max_suba",
     "fg_river_stats", "fg_river_phase_ms", "fg_set_river_prune", "fg_river_qsort_index",
+    "fg_topog_default_opts", "fg_topog_create", "fg_topog_destroy", "fg_topog_stream", "fg_topog_set_source", "fg_topog_get_source",
+    "fg_topog_remap", "fg_topog_filter", "fg_topog_process", "fg_topog_run", "fg_topog_set_depth", "fg_topog_get", "fg_topog_stats",
+    "fg_topog_phase_ms", "fg_plan_apply_frac_dev", "fg_set_topog_sweep",
 ]
+
+
+class TopogOpts(C.Structure):
+    """fg_topog_opts (include/fregrid_hip.h): every switch of create_realistic_topog"""
+    _fields_ = [("scale_factor", C.c_double)] + \
+        [(k, C.c_int) for k in ("tripolar_grid", "cyclic_x", "cyclic_y", "fill_first_row", "filter_topog", "num_filter_pass",
+                                "smooth_topo_allow_deepening", "round_shallow", "fill_shallow", "deepen_shallow", "full_cell", "flat_bottom",
+                                "adjust_topo", "fill_isolated_cells", "dont_change_landmask", "kmt_min")] + \
+        [("min_thickness", C.c_double), ("open_very_this_cell", C.c_int), ("fraction_full_cell", C.c_double),
+         ("use_great_circle_algorithm", C.c_int), ("on_grid", C.c_int)]
 
 
 class ApplyOpts(C.Structure):
@@ -455,6 +468,37 @@ def lib():
     L.fg_set_river_prune.restype = None
     L.fg_river_qsort_index.argtypes = [dp, C.c_int, ip]
     L.fg_river_qsort_index.restype = C.c_int
+    top = C.POINTER(TopogOpts)
+    L.fg_topog_default_opts.argtypes = [top]
+    L.fg_topog_default_opts.restype = None
+    L.fg_topog_create.argtypes = [C.c_int, C.c_int, dp, dp, top, C.c_int, C.POINTER(vp)]
+    L.fg_topog_create.restype = C.c_int
+    L.fg_topog_destroy.argtypes = [vp]
+    L.fg_topog_destroy.restype = None
+    L.fg_topog_stream.argtypes = [vp]
+    L.fg_topog_stream.restype = vp
+    L.fg_topog_set_source.argtypes = [vp, C.c_int, C.c_int, dp, dp, vp, C.c_int, C.c_double]
+    L.fg_topog_set_source.restype = C.c_int
+    L.fg_topog_get_source.argtypes = [vp, dp, dp, dp, dp]
+    L.fg_topog_get_source.restype = C.c_int
+    for f in (L.fg_topog_remap, L.fg_topog_filter):
+        f.argtypes = [vp]
+        f.restype = C.c_int
+    for f in (L.fg_topog_process, L.fg_topog_run):
+        f.argtypes = [vp, C.c_int, dp]
+        f.restype = C.c_int
+    L.fg_topog_set_depth.argtypes = [vp, dp]
+    L.fg_topog_set_depth.restype = C.c_int
+    L.fg_topog_get.argtypes = [vp, dp, ip]
+    L.fg_topog_get.restype = C.c_int
+    L.fg_topog_stats.argtypes = [vp, C.POINTER(C.c_long), dp, C.c_int]
+    L.fg_topog_stats.restype = C.c_int
+    L.fg_topog_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    L.fg_topog_phase_ms.restype = C.c_int
+    L.fg_set_topog_sweep.argtypes = [C.c_int]
+    L.fg_set_topog_sweep.restype = None
+    L.fg_plan_apply_frac_dev.argtypes = [vp, vp, vp]
+    L.fg_plan_apply_frac_dev.restype = C.c_int
     _LIB = L
     return L
 

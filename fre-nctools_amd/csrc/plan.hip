@@ -2525,6 +2525,14 @@ static int plan_apply_frac(fg_plan *pl, const double *data, double *out)
   return 0;
 }
 
+extern "C" int fg_plan_apply_frac_dev(fg_plan *pl, const double *data_dev, double *out_dev)
+{
+  if (!pl || !data_dev || !out_dev) return fg_fail(FG_ERR_ARG, "fg_plan_apply_frac_dev: null argument");
+  if (!pl->finalized || pl->order != 1) return fg_fail(FG_ERR_STATE, "fg_plan_apply_frac_dev: needs a finalized first-order plan");
+  FGCHK(hipSetDevice(pl->device));
+  return plan_apply_frac(pl, data_dev, out_dev);
+}
+
 // interp.c:262-305: first-order remap with weights xarea / (sum of xarea over the destination cell); interp.c:312: the same
 // with the great-circle exchange grid
 static void b1_conserve_interp(bool great_circle, int nx_src, int ny_src, int nx_dst, int ny_dst, const double *x_src,

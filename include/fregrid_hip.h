@@ -900,6 +900,68 @@ void fg_set_river_prune(int on);
  * among equal values (sort_basin's ids depend on it) */
 int  fg_river_qsort_index(double *array, int n, int *index);
 
+/* ---- make_topog --topog_type realistic on the device (tools/make_topog/topog.c: create_realistic_topog :355, process_topo :551,
+ * filter_topo :687, remove_isolated_cells :830, restrict_partial_cells :878, show_deepest :945, enforce_min_depth :987) ----
+ * The arrays are those the tool reads from the topography file, the vertical grid and the model grid; the tool's netCDF and
+ * mosaic handling, its domain decomposition and the idealised topographies are the caller's.  The depth stays in device memory
+ * from the remap to the last adjustment and carries the reference's bits; with use_great_circle_algorithm the
+ * remap agrees to rounding, as the great-circle plans do.  Errors of the reference come back as FG_ERR_ARG with its message
+ * text, never as an abort.  A source too large for one plan is the plan's error. */
+typedef struct fg_topog fg_topog;
+typedef struct fg_topog_opts {          /* every switch create_realistic_topog takes, in its order */
+  double scale_factor;
+  int tripolar_grid, cyclic_x, cyclic_y, fill_first_row, filter_topog, num_filter_pass, smooth_topo_allow_deepening;
+  int round_shallow, fill_shallow, deepen_shallow, full_cell, flat_bottom, adjust_topo, fill_isolated_cells, dont_change_landmask;
+  int kmt_min;
+  double min_thickness;
+  int open_very_this_cell;
+  double fraction_full_cell;
+  int use_great_circle_algorithm, on_grid;
+} fg_topog_opts;
+/* make_topog.c:297-323: scale_factor 1, num_filter_pass 1, adjust_topo 1, fill_isolated_cells 1, kmt_min 2, min_thickness 0.1,
+ * open_very_this_cell 1, fraction_full_cell 0.2, everything else 0 */
+void fg_topog_default_opts(fg_topog_opts *opts);
+/* x_dst, y_dst [(ny_dst+1)*(nx_dst+1)]: the model grid's corners in DEGREES, as the tool holds them.  opts NULL: the defaults. */
+int  fg_topog_create(int nx_dst, int ny_dst, const double *x_dst, const double *y_dst, const fg_topog_opts *opts, int device, fg_topog **out);
+void fg_topog_destroy(fg_topog *h);
+void *fg_topog_stream(fg_topog *h);
+/* xt_src [nx_src], yt_src [ny_src]: the cell-centre axes of the file in degrees; data [ny_src*nx_src] in the file's type, dtype the
+ * nc_type code 4 (NC_INT, int32), 5 (NC_FLOAT) or 6 (NC_DOUBLE); missing: the file's missing_value.  Forms the bounds (:416-427),
+ * trims the rows to the model grid's latitudes (:437-449), uploads those rows in their narrow type, and on the device widens,
+ * masks and scales them (:492-502; `missing` is tested before scaling, <= 0 after it is masked) and expands the two axes to the
+ * corner arrays.  May be called again: the new source replaces the old one.  on_grid: the trimmed source must have nx_dst*ny_dst cells. */
+int  fg_topog_set_source(fg_topog *h, int nx_src, int ny_src, const double *xt_src, const double *yt_src, const void *data, int dtype, double missing);
+/* what set_source left on the device (tests): x_src, y_src [(ny_now+1)*(nx_src+1)] radians, depth_src, mask_src [ny_now*nx_src],
+ * ny_now = jend - jstart + 1 (fg_topog_stats); any pointer may be NULL */
+int  fg_topog_get_source(const fg_topog *h, double *x_src, double *y_src, double *depth_src, double *mask_src);
+/* The stages, each leaving its result on the device.  remap: conserve_interp / conserve_interp_great_circle (interp.c:262-356), or
+ * with on_grid the copy of :503-511 (only `missing` becomes 0, negative scaled values are kept).  filter: filter_topo, whatever
+ * opts.filter_topog says.  process: process_topo with nk levels zw [nk].  run: :512-536, i.e. remap, filter if filter_topog, the
+ * deepest depth, fill_first_row, process if nk > 0 (nk == 0: no vertical grid, no levels).  zw is checked where the stage begins
+ * (the reference finds a non-monotone zw at the first ocean cell, and nk < kmt_min in enforce_min_depth). */
+int  fg_topog_remap(fg_topog *h);
+int  fg_topog_filter(fg_topog *h);
+int  fg_topog_process(fg_topog *h, int nk, const double *zw);
+int  fg_topog_run(fg_topog *h, int nk, const double *zw);
+/* Test hook: overwrites the device depth [ny_dst*nx_dst], so that a stage can be fed the reference's intermediate. */
+int  fg_topog_set_depth(fg_topog *h, const double *depth);
+/* depth [ny_dst*nx_dst], num_levels [ny_dst*nx_dst] (after process; NULL to skip) */
+int  fg_topog_get(const fg_topog *h, double *depth, int *num_levels);
+/* the first n of 9: [0] jstart, [1] jend, [2] nxgrid of the last remap (0 for on_grid), [3] isolated cells filled, [4] partial
+ * cells restricted, [5] shallow cells modified (the counts the reference prints under debug), [6] show_deepest's verdict: 0 the
+ * topography is deeper than the grid by more than 1 m, 1 fewer levels would do, 2 the grid fits, -1 no vertical grid was given,
+ * [7] launches of the isolated-cell sweep, [8] ny_now.  *deepest (may be NULL): the deepest non-zero depth after the filter stage. */
+int  fg_topog_stats(const fg_topog *h, long *stats, double *deepest, int n);
+/* wall time in ms (the first n of 5): create; set_source; remap; filter; process */
+int  fg_topog_phase_ms(const fg_topog *h, float *ms, int n);
+/* Test hook; results never depend on it (the sweep's result does not depend on its order, for depths without
+ * NaN).  1 (default): remove_isolated_cells is evaluated for every cell at once on the arrays process_topo left, inside the last
+ * kernel; 0: it runs as the reference's in-place sweep, one launch per anti-diagonal 2j + i. */
+void fg_set_topog_sweep(int fused);
+/* out_dev [ncells_out] = conserve_interp's area-fraction sweep (interp.c:283-294) of data_dev [ncells_in] over a finalized
+ * first-order plan; device pointers, queued on the plan's stream and waited for */
+int  fg_plan_apply_frac_dev(fg_plan *plan, const double *data_dev, double *out_dev);
+
 #ifdef __cplusplus
 }
 #endif
