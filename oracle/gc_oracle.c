@@ -34,6 +34,23 @@
 #define GC_MASK_THRESH 0.5
 #define GC_CAP 40
 
+/* This file is compiled twice into liboracle.so (oracle/Makefile).  The plain build is the one pinned to the reference:
+ * no suffix, acosl is libm's (the x87 fpatan, then one rounding to double).  The second build (-DGC_ORC_SUFFIX=_cr
+ * -DGC_ACOSL=orc_fg_acosl) exports every orc_* below as orc_*_cr and takes the arc cosine from the host build of csrc/fp80.h's
+ * fg_acosl (oracle/gc_acos_cr.cpp), the correctly rounded one the device calls: the oracle that rounds the way the device does.
+ * tests/test_gc_oracle_cr_cpu.py accounts for every value in which the two differ. */
+#ifndef GC_ORC_SUFFIX
+#define GC_ORC_SUFFIX
+#endif
+#define GC_CAT_(a, b) a##b
+#define GC_CAT(a, b) GC_CAT_(a, b)
+#define ORC(name) GC_CAT(name, GC_ORC_SUFFIX)
+#ifdef GC_ACOSL
+double GC_ACOSL(double x);
+#else
+#define GC_ACOSL acosl
+#endif
+
 typedef struct { double x, y, z, u, u_clip; int intersect, inbound, inside, subj_index, clip_index; } GcNode;
 typedef struct { int n; GcNode v[GC_CAP]; } GcList;
 
@@ -55,7 +72,7 @@ static int add_end(GcList *l, double x, double y, double z, int intersect, doubl
   return 0;
 }
 
-double orc_spherical_angle(const double *v1, const double *v2, const double *v3)
+double ORC(orc_spherical_angle)(const double *v1, const double *v2, const double *v3)
 {                                                           /* mosaic_util.c:799-836, double branch */
   double angle, px, py, pz, qx, qy, qz, ddd;
   px = v1[1] * v2[2] - v1[2] * v2[1];
@@ -74,19 +91,19 @@ double orc_spherical_angle(const double *v1, const double *v2, const double *v3)
       if (ddd < 0.) angle = M_PI;
       else angle = 0.;
     } else
-      angle = acosl(ddd);
+      angle = GC_ACOSL(ddd);
   }
   return angle;
 }
 
-double orc_great_circle_area(int n, const double *x, const double *y, const double *z)
+double ORC(orc_great_circle_area)(int n, const double *x, const double *y, const double *z)
 {                                                           /* mosaic_util.c:763-787 */
   double pnt0[3], pnt1[3], pnt2[3], sum = 0.0;
   for (int i = 0; i < n; i++) {
     pnt0[0] = x[i]; pnt0[1] = y[i]; pnt0[2] = z[i];
     pnt1[0] = x[(i + 1) % n]; pnt1[1] = y[(i + 1) % n]; pnt1[2] = z[(i + 1) % n];
     pnt2[0] = x[(i + 2) % n]; pnt2[1] = y[(i + 2) % n]; pnt2[2] = z[(i + 2) % n];
-    sum += orc_spherical_angle(pnt1, pnt2, pnt0);
+    sum += ORC(orc_spherical_angle)(pnt1, pnt2, pnt0);
   }
   return (sum - (n - 2.) * M_PI) * GC_RADIUS * GC_RADIUS;
 }
@@ -95,7 +112,7 @@ static double list_area(const GcList *l)                    /* gridArea, mosaic_
 {
   double x[GC_CAP], y[GC_CAP], z[GC_CAP];
   for (int k = 0; k < l->n; k++) { x[k] = l->v[k].x; y[k] = l->v[k].y; z[k] = l->v[k].z; }
-  return orc_great_circle_area(l->n, x, y, z);
+  return ORC(orc_great_circle_area)(l->n, x, y, z);
 }
 
 static int inside_polygon(const GcNode *node, const GcList *l)   /* mosaic_util.c:1546-1589 */
@@ -106,7 +123,7 @@ static int inside_polygon(const GcNode *node, const GcList *l)   /* mosaic_util.
     pnt1[0] = l->v[k].x; pnt1[1] = l->v[k].y; pnt1[2] = l->v[k].z;
     pnt2[0] = l->v[kn].x; pnt2[1] = l->v[kn].y; pnt2[2] = l->v[kn].z;
     if (same_point(pnt0[0], pnt0[1], pnt0[2], pnt1[0], pnt1[1], pnt1[2])) return 1;
-    anglesum += orc_spherical_angle(pnt0, pnt2, pnt1);
+    anglesum += ORC(orc_spherical_angle)(pnt0, pnt2, pnt1);
   }
   return fabs(anglesum - 2 * M_PI) < GC_EPSLN8;
 }
@@ -139,7 +156,7 @@ static void cross3(const double *p1, const double *p2, double *e)
 static double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 static double metric3(const double *p) { return sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]); }
 
-int orc_line_intersect_2D_3D(const double *a1, const double *a2, const double *q1, const double *q2, const double *q3,
+int ORC(orc_line_intersect_2D_3D)(const double *a1, const double *a2, const double *q1, const double *q2, const double *q3,
                              double *intersect, double *u_a, double *u_q, int *inbound)
 {                                                           /* create_xgrid.c:1919-2081 */
   double u, p1[3], v1[3], v2[3], c1[3], c2[3], c3[3], coincident, sense, norm;
@@ -265,7 +282,7 @@ static int add_node(GcList *l, const GcNode *nd) { return add_end(l, nd->x, nd->
 static double minv(int n, const double *d) { double m = d[0]; for (int k = 1; k < n; k++) if (d[k] < m) m = d[k]; return m; }
 static double maxv(int n, const double *d) { double m = d[0]; for (int k = 1; k < n; k++) if (d[k] > m) m = d[k]; return m; }
 
-int orc_clip_2dx2d_great_circle(const double x1_in[], const double y1_in[], const double z1_in[], int n1_in,
+int ORC(orc_clip_2dx2d_great_circle)(const double x1_in[], const double y1_in[], const double z1_in[], int n1_in,
                                 const double x2_in[], const double y2_in[], const double z2_in[], int n2_in,
                                 double x_out[], double y_out[], double z_out[])
 {
@@ -298,7 +315,7 @@ int orc_clip_2dx2d_great_circle(const double x1_in[], const double y1_in[], cons
     for (int i2 = 0; i2 < npts2; i2++) {
       int i2p = (i2 + 1) % npts2, i2p2 = (i2 + 2) % npts2, inbound, rc;
       double *p2_0 = pt2[i2], *p2_1 = pt2[i2p], *p2_2 = pt2[i2p2], I[3], u1, u2;
-      if (orc_line_intersect_2D_3D(p1_0, p1_1, p2_0, p2_1, p2_2, I, &u1, &u2, &inbound)) {
+      if (ORC(orc_line_intersect_2D_3D)(p1_0, p1_1, p2_0, p2_1, p2_2, I, &u1, &u2, &inbound)) {
         rc = add_intersect(&il, I[0], I[1], I[2], u1, u2, inbound, i1, i1p, i2, i2p);
         if (rc < 0) return rc;
         if (rc) {
@@ -395,7 +412,7 @@ int orc_clip_2dx2d_great_circle(const double x1_in[], const double y1_in[], cons
   return n_out;
 }
 
-void orc_latlon2xyz(int size, const double *lon, const double *lat, double *x, double *y, double *z)
+void ORC(orc_latlon2xyz)(int size, const double *lon, const double *lat, double *x, double *y, double *z)
 {                                                           /* mosaic_util.c:212-222 */
   for (int n = 0; n < size; n++) {
     x[n] = cos(lat[n]) * cos(lon[n]);
@@ -413,12 +430,12 @@ static void cell_xyz(const double *x, const double *y, const double *z, int nxp,
   cx[3] = x[n3]; cy[3] = y[n3]; cz[3] = z[n3];
 }
 
-void orc_get_grid_great_circle_area(int nx, int ny, const double *lon, const double *lat, double *area)
+void ORC(orc_get_grid_great_circle_area)(int nx, int ny, const double *lon, const double *lat, double *area)
 {                                                           /* create_xgrid.c:98-137 */
   const int nxp = nx + 1, nyp = ny + 1;
   double *x = (double *)malloc((size_t)nxp * nyp * sizeof(double)), *y = (double *)malloc((size_t)nxp * nyp * sizeof(double)),
          *z = (double *)malloc((size_t)nxp * nyp * sizeof(double));
-  orc_latlon2xyz(nxp * nyp, lon, lat, x, y, z);
+  ORC(orc_latlon2xyz)(nxp * nyp, lon, lat, x, y, z);
   for (int j = 0; j < ny; j++)
     for (int i = 0; i < nx; i++) {
       double cx[4], cy[4], cz[4];
@@ -433,7 +450,7 @@ void orc_get_grid_great_circle_area(int nx, int ny, const double *lon, const dou
 /* create_xgrid_great_circle restricted to source rows [j1_begin, j1_end) (the whole call is rows [0, ny1)), with a
  * capacity instead of MAXXGRID.  Returns nxgrid, or -(100 + code) if the clip hit one of the reference's fatal errors,
  * or -99 on capacity. */
-long orc_create_xgrid_great_circle_rows(int nx1, int ny1, int nx2, int ny2, const double *lon_in, const double *lat_in,
+long ORC(orc_create_xgrid_great_circle_rows)(int nx1, int ny1, int nx2, int ny2, const double *lon_in, const double *lat_in,
                                         const double *lon_out, const double *lat_out, const double *mask_in,
                                         int j1_begin, int j1_end, long capacity,
                                         int *i_in, int *j_in, int *i_out, int *j_out,
@@ -444,10 +461,10 @@ long orc_create_xgrid_great_circle_rows(int nx1, int ny1, int nx2, int ny2, cons
   double *x1 = (double *)malloc((size_t)nx1p * ny1p * 3 * sizeof(double)), *y1 = x1 + (size_t)nx1p * ny1p, *z1 = y1 + (size_t)nx1p * ny1p;
   double *x2 = (double *)malloc((size_t)nx2p * ny2p * 3 * sizeof(double)), *y2 = x2 + (size_t)nx2p * ny2p, *z2 = y2 + (size_t)nx2p * ny2p;
   double *area1 = (double *)malloc((size_t)nx1 * ny1 * sizeof(double)), *area2 = (double *)malloc((size_t)nx2 * ny2 * sizeof(double));
-  orc_latlon2xyz(nx1p * ny1p, lon_in, lat_in, x1, y1, z1);
-  orc_latlon2xyz(nx2p * ny2p, lon_out, lat_out, x2, y2, z2);
-  orc_get_grid_great_circle_area(nx1, ny1, lon_in, lat_in, area1);
-  orc_get_grid_great_circle_area(nx2, ny2, lon_out, lat_out, area2);
+  ORC(orc_latlon2xyz)(nx1p * ny1p, lon_in, lat_in, x1, y1, z1);
+  ORC(orc_latlon2xyz)(nx2p * ny2p, lon_out, lat_out, x2, y2, z2);
+  ORC(orc_get_grid_great_circle_area)(nx1, ny1, lon_in, lat_in, area1);
+  ORC(orc_get_grid_great_circle_area)(nx2, ny2, lon_out, lat_out, area2);
   /* per-destination-cell boxes so the brute-force scan only pays six comparisons for far pairs -- the same six the
    * reference's clip starts with (create_xgrid.c:1508-1528), hoisted */
   double *bb = (double *)malloc((size_t)nx2 * ny2 * 6 * sizeof(double));
@@ -467,10 +484,10 @@ long orc_create_xgrid_great_circle_rows(int nx1, int ny1, int nx2, int ny2, cons
           a4 >= b[5] + GC_RANGE_CHECK || b[4] >= a5 + GC_RANGE_CHECK) continue;
       double x2_in[4], y2_in[4], z2_in[4], x_out[GC_CAP], y_out[GC_CAP], z_out[GC_CAP];
       cell_xyz(x2, y2, z2, nx2p, i2, j2, x2_in, y2_in, z2_in);
-      int n_out = orc_clip_2dx2d_great_circle(x1_in, y1_in, z1_in, 4, x2_in, y2_in, z2_in, 4, x_out, y_out, z_out);
+      int n_out = ORC(orc_clip_2dx2d_great_circle)(x1_in, y1_in, z1_in, 4, x2_in, y2_in, z2_in, 4, x_out, y_out, z_out);
       if (n_out < 0) { rc_err = -(100 - n_out); break; }
       if (n_out > 0) {
-        double xarea = orc_great_circle_area(n_out, x_out, y_out, z_out) * mask_in[j1 * nx1 + i1];
+        double xarea = ORC(orc_great_circle_area)(n_out, x_out, y_out, z_out) * mask_in[j1 * nx1 + i1];
         double min_area = area1[j1 * nx1 + i1] < area2[j2 * nx2 + i2] ? area1[j1 * nx1 + i1] : area2[j2 * nx2 + i2];
         if (xarea / min_area > GC_AREA_RATIO_THRESH) {
           if (nxgrid >= capacity) { rc_err = -99; break; }

@@ -1,6 +1,7 @@
 """ctypes access to the CPU checkers used by the tests (never by the product):
 
-* ``oracle/liboracle.so``       our clean-room C restatement (oracle/xgrid_oracle.c)
+* ``oracle/liboracle.so``       our clean-room C restatement (oracle/xgrid_oracle.c); gc_oracle.c is in it twice, plain
+  (libm's acosl, pinned to the reference) and as orc_*_cr (the device's correctly rounded arc cosine): ``cr=True`` below
 * ``oracle/_ref/libfrenc_ref.so`` the reference's own sources compiled in place (oracle/Makefile);
   present in the build container and -- as a prebuilt .so -- on the GPU box.
 * ``oracle/_ref/libconserve_ref.so`` the reference's own conserve_interp.c (setup_conserve_interp,
@@ -91,6 +92,13 @@ def oracle():
         L.orc_latlon2xyz.restype = None
         L.orc_create_xgrid_great_circle_rows.argtypes = [C.c_int] * 4 + [dp] * 5 + [C.c_int, C.c_int, C.c_long] + [ip] * 4 + [dp] * 3
         L.orc_create_xgrid_great_circle_rows.restype = C.c_long
+        L.orc_spherical_angle.argtypes = [dp, dp, dp]
+        L.orc_spherical_angle.restype = C.c_double
+        # gc_oracle.c's second build: the same text with the device's arc cosine (csrc/fp80.h's fg_acosl)
+        for nm in ("orc_clip_2dx2d_great_circle", "orc_great_circle_area", "orc_get_grid_great_circle_area",
+                   "orc_create_xgrid_great_circle_rows", "orc_spherical_angle"):
+            getattr(L, nm + "_cr").argtypes = getattr(L, nm).argtypes
+            getattr(L, nm + "_cr").restype = getattr(L, nm).restype
         L.orc_clip.argtypes = [dp, dp, C.c_int] + [C.c_double] * 4 + [dp, dp]
         L.orc_clip.restype = C.c_int
         L.orc_box_ctrlat.argtypes = [C.c_double] * 4
@@ -330,20 +338,70 @@ ORC_APPLY_ERRORS = {
 }
 
 
-def orc_create_xgrid_gc(nx1, ny1, nx2, ny2, lon_in, lat_in, lon_out, lat_out, mask=None, j1_beg=0, j1_end=None, capacity=None):
-    """create_xgrid_great_circle (oracle restatement); source rows [j1_beg, j1_end)."""
+def _gc(name, cr):
+    """gc_oracle.c's function `name`: the plain build (libm's acosl, pinned to the reference) or, with cr, the build whose
+    arc cosine is the device's correctly rounded fg_acosl"""
+    return getattr(oracle(), name + ("_cr" if cr else ""))
+
+
+def orc_spherical_angle(v1, v2, v3, cr=False):
+    return _gc("orc_spherical_angle", cr)(_dp(f64(v1)), _dp(f64(v2)), _dp(f64(v3)))
+
+
+def orc_great_circle_area(x, y, z, cr=False):
+    x, y, z = f64(x), f64(y), f64(z)
+    return _gc("orc_great_circle_area", cr)(len(x), _dp(x), _dp(y), _dp(z))
+
+
+def orc_clip_gc(a, b, cr=False):
+    """clip_2dx2d_great_circle of two polygons given as [n, 3] unit vectors: (n_out, vertices [n_out, 3])"""
+    a, b = f64(a), f64(b)
+    aa = [np.ascontiguousarray(a[:, ax]) for ax in range(3)]
+    bb = [np.ascontiguousarray(b[:, ax]) for ax in range(3)]
+    oo = [np.zeros(50) for _ in range(3)]
+    n = _gc("orc_clip_2dx2d_great_circle", cr)(*[_dp(v) for v in aa], len(a), *[_dp(v) for v in bb], len(b), *[_dp(v) for v in oo])
+    return n, np.stack([v[:max(n, 0)] for v in oo], axis=1)
+
+
+def orc_create_xgrid_gc(nx1, ny1, nx2, ny2, lon_in, lat_in, lon_out, lat_out, mask=None, j1_beg=0, j1_end=None, capacity=None,
+                        cr=False):
+    """create_xgrid_great_circle (oracle restatement); source rows [j1_beg, j1_end).  cr: the build that rounds like the device."""
     L = oracle()
     lon_in, lat_in, lon_out, lat_out = f64(lon_in).ravel(), f64(lat_in).ravel(), f64(lon_out).ravel(), f64(lat_out).ravel()
     mask = f64(np.ones(nx1 * ny1) if mask is None else mask).ravel()
     cap = capacity or 8 * (nx1 * ny1 + nx2 * ny2) + 1024
     ii, ji, io, jo = (np.empty(cap, dtype=np.int32) for _ in range(4))
     a, cl, ct = np.empty(cap), np.empty(cap), np.empty(cap)
-    n = L.orc_create_xgrid_great_circle_rows(nx1, ny1, nx2, ny2, _dp(lon_in), _dp(lat_in), _dp(lon_out), _dp(lat_out),
-                                             _dp(mask), j1_beg, ny1 if j1_end is None else j1_end, cap,
-                                             _ip(ii), _ip(ji), _ip(io), _ip(jo), _dp(a), _dp(cl), _dp(ct))
+    n = _gc("orc_create_xgrid_great_circle_rows", cr)(nx1, ny1, nx2, ny2, _dp(lon_in), _dp(lat_in), _dp(lon_out), _dp(lat_out),
+                                                      _dp(mask), j1_beg, ny1 if j1_end is None else j1_end, cap,
+                                                      _ip(ii), _ip(ji), _ip(io), _ip(jo), _dp(a), _dp(cl), _dp(ct))
     if n < 0:
         raise RuntimeError(f"oracle create_xgrid_great_circle failed: {n}")
     return dict(n=int(n), i_in=ii[:n].copy(), j_in=ji[:n].copy(), i_out=io[:n].copy(), j_out=jo[:n].copy(), area=a[:n].copy())
+
+
+def orc_gc_pair_areas(nx1, lon_in, lat_in, nx2, lon_out, lat_out, i_in, j_in, i_out, j_out, cr=False):
+    """The areas create_xgrid_great_circle gives the listed (source cell, destination cell) pairs with a mask of ones:
+    great_circle_area of clip_2dx2d_great_circle of the two cells (create_xgrid.c:1413-1447), pair by pair -- for lists whose
+    brute-force search is too long to run a second time.  A pair that does not clip to a polygon comes back as NaN."""
+    L = oracle()
+    lon_in, lat_in, lon_out, lat_out = f64(lon_in).ravel(), f64(lat_in).ravel(), f64(lon_out).ravel(), f64(lat_out).ravel()
+
+    def cells(lon, lat, nxp, i, j):
+        i, j = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64)
+        idx = np.stack([j * nxp + i, (j + 1) * nxp + i, (j + 1) * nxp + i + 1, j * nxp + i + 1], axis=1).ravel()
+        lo, la = np.ascontiguousarray(lon[idx]), np.ascontiguousarray(lat[idx])
+        x, y, z = (np.empty(idx.size) for _ in range(3))
+        L.orc_latlon2xyz(idx.size, _dp(lo), _dp(la), _dp(x), _dp(y), _dp(z))
+        return np.stack([x, y, z], axis=1).reshape(-1, 4, 3)
+
+    a, b = cells(lon_in, lat_in, nx1 + 1, i_in, j_in), cells(lon_out, lat_out, nx2 + 1, i_out, j_out)
+    out = np.full(len(a), np.nan)
+    for k in range(len(a)):
+        n, v = orc_clip_gc(a[k], b[k], cr=cr)
+        if n > 0:
+            out[k] = orc_great_circle_area(v[:, 0], v[:, 1], v[:, 2], cr=cr)
+    return out
 
 
 def ref_create_xgrid_gc(nx1, ny1, nx2, ny2, lon_in, lat_in, lon_out, lat_out, mask=None):
@@ -359,10 +417,10 @@ def ref_create_xgrid_gc(nx1, ny1, nx2, ny2, lon_in, lat_in, lon_out, lat_out, ma
     return dict(n=n, i_in=ii[:n].copy(), j_in=ji[:n].copy(), i_out=io[:n].copy(), j_out=jo[:n].copy(), area=a[:n].copy())
 
 
-def orc_get_grid_gc_area(nx, ny, lon, lat):
+def orc_get_grid_gc_area(nx, ny, lon, lat, cr=False):
     lon, lat = f64(lon).ravel(), f64(lat).ravel()
     a = np.empty(nx * ny)
-    oracle().orc_get_grid_great_circle_area(nx, ny, _dp(lon), _dp(lat), _dp(a))
+    _gc("orc_get_grid_great_circle_area", cr)(nx, ny, _dp(lon), _dp(lat), _dp(a))
     return a
 
 

@@ -60,21 +60,22 @@ SETUP_CASES = [(name, order) for name in ("c24_to_72x36", "c24_to_regional", "la
                                           "c12_to_0.5deg", "c48_to_10deg") for order in (1, 2)]
 
 
-def orc_setup_gc(gin, gout):
+def orc_setup_gc(gin, gout, cr=False):
     """The restatement's great-circle setup, composed the way conserve_interp.c:164-168 searches: whole source tiles, one
-    create_xgrid_great_circle per (destination tile, source tile), t_in = source tile."""
+    create_xgrid_great_circle per (destination tile, source tile), t_in = source tile.  cr: gc_oracle.c's build with the device's
+    arc cosine."""
     keys = ("t_in", "i_in", "j_in", "i_out", "j_out", "area")
     parts, xoff = {k: [] for k in keys}, [0]
     for (nx2, ny2, lo2, la2) in gout:
         for m, (nx1, ny1, lo1, la1) in enumerate(gin):
-            x = orc.orc_create_xgrid_gc(nx1, ny1, nx2, ny2, lo1, la1, lo2, la2)
+            x = orc.orc_create_xgrid_gc(nx1, ny1, nx2, ny2, lo1, la1, lo2, la2, cr=cr)
             x["t_in"] = np.full(x["n"], m, dtype=np.int32)
             for k in keys:
                 parts[k].append(x[k])
         xoff.append(sum(len(a) for a in parts["area"]))
     out = {k: np.concatenate(v) for k, v in parts.items()}
-    out.update(n=xoff[-1], xoff=np.array(xoff), cell_area_in=[orc.orc_get_grid_gc_area(*g) for g in gin],
-               cell_area_out=[orc.orc_get_grid_gc_area(*g) for g in gout])
+    out.update(n=xoff[-1], xoff=np.array(xoff), cell_area_in=[orc.orc_get_grid_gc_area(*g, cr=cr) for g in gin],
+               cell_area_out=[orc.orc_get_grid_gc_area(*g, cr=cr) for g in gout])
     return out
 
 

@@ -4,14 +4,15 @@ do_scalar_conserve_interp (device sweep) against the reference's setup_conserve_
 grids of tests/test_conserve_interp_vs_ref.py and one case per sweep branch.
 
 Tolerances are the suite's: the legacy path is bit-identical where the host libm runs its FMA build (orc.host_has_fma),
-1e-10 relative otherwise.  The great-circle path has identical index lists and areas within 1e-10 (a few carry
-last-place differences from glibc's acosl, see test_gpu_great_circle.py); a remapped value is bit-identical unless one of
-its exchange cells has such an area, and then within the same 1e-10."""
+1e-10 relative otherwise.  The great-circle path has identical index lists and areas within 1e-10 of the reference's (a few
+carry last-place differences from glibc's acosl, see test_gpu_great_circle.py); a remapped value is bit-identical unless one of
+its exchange cells has such an area, and then within the same 1e-10.  Against the oracle that rounds like the device
+(gc_oracle.c's _cr build, pinned in tests/test_gc_oracle_cr_cpu.py) every great-circle area and cell area is bit-identical."""
 import numpy as np
 import pytest
 
 import orc
-from test_conserve_interp_vs_ref import Case, _id, grids, sweep_inputs
+from test_conserve_interp_vs_ref import Case, _id, grids, orc_setup_gc, sweep_inputs
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not orc.conserve_ref_available(), reason="oracle/_ref/libconserve_ref.so not built")]
@@ -88,6 +89,18 @@ def test_setup_great_circle_vs_reference(fg, gpu_ok, name):
     r = orc.cref_setup(1, gin, gout, great_circle=True)
     grid_in, grid_out, interp = mirror_setup(fg, 1, gin, gout, great_circle=True)
     check_setup(fg, 1, gin, gout, r, grid_in, grid_out, interp, great_circle=True)
+    # against the oracle that rounds like the device (gc_oracle.c's _cr build), tile by tile: every area and cell area in bits
+    ocr = orc_setup_gc(gin, gout, cr=True)
+    assert np.array_equal(ocr["xoff"], r["xoff"])
+    for n, ic in enumerate(interp):
+        s = slice(int(ocr["xoff"][n]), int(ocr["xoff"][n + 1]))
+        assert np.array_equal(ic.t_in, ocr["t_in"][s]) and np.array_equal(ic.i_in, ocr["i_in"][s]) and np.array_equal(ic.j_out, ocr["j_out"][s])
+        nd = int(np.count_nonzero(_bits(ic.area) != _bits(ocr["area"][s])))
+        assert nd == 0, f"destination tile {n}: {nd} of {ic.nxgrid} exchange-cell areas differ from the _cr oracle"
+    for which, gs, areas in (("source", grid_in, ocr["cell_area_in"]), ("destination", grid_out, ocr["cell_area_out"])):
+        for t, (g, a) in enumerate(zip(gs, areas)):
+            nd = int(np.count_nonzero(_bits(g.cell_area) != _bits(a)))
+            assert nd == 0, f"{which} tile {t}: {nd} of {a.size} cell areas differ from the _cr oracle"
     # a field through the mirror's great-circle sweep against the reference's sweep over the reference's own lists
     _, _, _, kw = sweep_inputs(fg, Case(1, missing="pattern", grid=name))
     ref, _ = orc.cref_apply(1, r, kw["nx_in"], kw["ny_in"], kw["data"], None, None, None, True, kw["missing"],

@@ -1,5 +1,6 @@
 """BASELINE.json configs 4 and 5 at full size on the device, checked through size-independent properties plus oracle
-parity on sampled source rows (the brute-force oracle cannot finish these sizes):
+parity on sampled source rows (the brute-force oracle cannot finish these sizes; great-circle areas of those rows to 1e-10 and
+98 % in bits against the plain oracle, all of them in bits against the oracle's _cr build, see test_gpu_great_circle.py):
   config 4a  C768 -> 2880x1440, great-circle clip, first order, write the remap file (order 2 + great circle is rejected
              by the reference itself, fregrid.c:763 -- SURVEY §8d)
   config 4b  C768 -> 2880x1440, legacy clip, second order (the order-2 half of config 4)
@@ -54,6 +55,12 @@ def test_config4_c768_great_circle_full_size(fg, gpu_ok, tmp_path):
             assert np.array_equal(x[k][sel], o[k]), k
         assert np.max(np.abs(x["area"][sel] - o["area"]) / o["area"]) < 1e-10
         assert np.mean(_bits(x["area"][sel]) == _bits(o["area"])) > 0.98
+        # every area of the row in bits against the oracle that rounds like the device (gc_oracle.c's _cr build).  The lists are
+        # the plain build's (asserted above, and the two builds' lists are identical), so the _cr build clips the listed pairs
+        # one by one: a second brute-force search of the row costs 50 s of CPU, these a fraction of a second
+        acr = orc.orc_gc_pair_areas(ni, lon[t], lat[t], nlon, lo, la, o["i_in"], o["j_in"], o["i_out"], o["j_out"], cr=True)
+        nd = int(np.count_nonzero(_bits(x["area"][sel]) != _bits(acr)))
+        assert nd == 0, f"tile {t} row {j0}: {nd} of {o['n']} exchange-cell areas differ from the _cr oracle"
     # first-order sweep on the great-circle plan: constants preserved, conservation
     dev = "cuda:0"
     data = torch.full((2, 6 * ni * ni), 3.25, dtype=torch.float64, device=dev)

@@ -1,10 +1,14 @@
-"""GPU parity of the great-circle path (create_xgrid_great_circle semantics) against the oracle
-(gc_oracle.c, itself pinned bit for bit to the compiled reference): exchange-cell lists identical, areas within 1e-10
-relative -- and in fact bit-identical except where the x87 fpatan inside glibc's acosl rounds differently from the
-device's correctly rounded replacement (csrc/fp80.h), which the tests quantify."""
+"""GPU parity of the great-circle path (create_xgrid_great_circle semantics) against two builds of the
+oracle (gc_oracle.c):
+* the plain one, pinned bit for bit to the compiled reference: exchange-cell lists identical, areas within 1e-10 relative and
+  more than 98 % of them bit-identical -- the allowance for the x87 fpatan inside glibc's acosl, which rounds an angle
+  differently from the device's correctly rounded replacement (csrc/fp80.h's fg_acosl) once in a few thousand;
+* the _cr one, the same text with fg_acosl, pinned to the plain one with every differing value accounted for
+  (tests/test_gc_oracle_cr_cpu.py): ALL areas bit-identical, no tolerance and no allowed fraction."""
 import numpy as np
 import pytest
 
+import gc_cases
 import orc
 
 pytestmark = pytest.mark.gpu
@@ -15,17 +19,14 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def _cases(fg):
-    c24 = fg.gnomonic_ed_corners(24)
-    c12 = fg.gnomonic_ed_corners(12)
-    return {
-        "c24_tile1_144x90": (24, 24, 144, 90, c24[0][0], c24[1][0]) + fg.latlon_corners(144, 90),
-        "c24_tile3_polar_144x90": (24, 24, 144, 90, c24[0][2], c24[1][2]) + fg.latlon_corners(144, 90),
-        "latlon_aligned_2x": (36, 18, 72, 36) + fg.latlon_corners(36, 18) + fg.latlon_corners(72, 36),
-        "latlon_regional_offset": (30, 20, 45, 33) + fg.latlon_corners(30, 20, 10., 70., -30., 30.) + fg.latlon_corners(45, 33, 0., 90., -40., 40.),
-        "latlon_to_cubed_polar": (40, 20, 12, 12) + fg.latlon_corners(40, 20) + (c12[0][5], c12[1][5]),
-        "tripolar_to_cubed": (45, 27, 12, 12) + fg.tripolar_corners(45, 27) + (c12[0][2], c12[1][2]),
-    }
+def _nbits(a, b):
+    """how many values differ in bits"""
+    a, b = _bits(a), _bits(b)
+    assert a.shape == b.shape
+    return int(np.count_nonzero(a != b))
+
+
+_cases = gc_cases.grid_cases
 
 
 @pytest.mark.parametrize("name", ["c24_tile1_144x90", "c24_tile3_polar_144x90", "latlon_aligned_2x", "latlon_regional_offset",
@@ -41,11 +42,18 @@ def test_create_xgrid_great_circle_vs_oracle(fg, gpu_ok, name):
     assert rel.max() < RTOL
     same = np.mean(_bits(area) == _bits(o["area"]))
     assert same > 0.98, same                       # the rest: one final double rounding of an angle (fpatan vs exact)
+    ocr = orc.orc_create_xgrid_gc(*args, cr=True)  # the oracle that rounds like the device: every value
+    assert ocr["n"] == n
+    nd = _nbits(area, ocr["area"])
+    assert nd == 0, f"{nd} of {n} exchange-cell areas differ from the _cr oracle"
     assert not clon.any() and not clat.any()       # create_xgrid.c:1446-1447
     ca = fg.get_grid_great_circle_area(args[0], args[1], args[4], args[5])
     cref = orc.orc_get_grid_gc_area(args[0], args[1], args[4], args[5])
     assert np.max(np.abs(ca - cref) / np.abs(cref)) < RTOL
     assert np.mean(_bits(ca) == _bits(cref)) > 0.98
+    for nx, ny, lo, la in (args[0:2] + args[4:6], args[2:4] + args[6:8]):
+        nd = _nbits(fg.get_grid_great_circle_area(nx, ny, lo, la), orc.orc_get_grid_gc_area(nx, ny, lo, la, cr=True))
+        assert nd == 0, f"{nd} of {nx * ny} grid-cell areas differ from the _cr oracle"
 
 
 def test_clip_vertices_bitwise(fg, gpu_ok):
@@ -66,7 +74,7 @@ def test_clip_vertices_bitwise(fg, gpu_ok):
     a = np.stack([np.stack([cell(v, 25, int(gc["i_in"][k]), int(gc["j_in"][k])) for v in (x1, y1, z1)], axis=1) for k in idx])
     b = np.stack([np.stack([cell(v, 145, int(gc["i_out"][k]), int(gc["j_out"][k])) for v in (x2, y2, z2)], axis=1) for k in idx])
     n_out, verts, area = fg.gc_clip_batch(a, b)
-    nbad_area = 0
+    nbad_area = nbad_cr = 0
     for q, k in enumerate(idx):
         aa = [np.ascontiguousarray(a[q][:, ax]) for ax in range(3)]
         bb = [np.ascontiguousarray(b[q][:, ax]) for ax in range(3)]
@@ -78,7 +86,9 @@ def test_clip_vertices_bitwise(fg, gpu_ok):
         ar = O.orc_great_circle_area(no, *[orc._dp(v) for v in oo])
         assert abs(ar - area[q]) <= RTOL * abs(ar)
         nbad_area += ar != area[q]
+        nbad_cr += _nbits(O.orc_great_circle_area_cr(no, *[orc._dp(v) for v in oo]), area[q])
     assert nbad_area < 0.02 * len(idx)
+    assert nbad_cr == 0, f"{nbad_cr} of {len(idx)} areas differ from the _cr oracle"
     # an antipodal cell (whose edge planes do cross the first cell's chords) is rejected by the reference's bounding box
     # (create_xgrid.c:1508-1528) and so it is here
     anti = -a[0][::-1]
@@ -102,12 +112,17 @@ def test_setup_conserve_interp_great_circle_and_sweep(fg, gpu_ok, capsys):
         assert sel.sum() == o["n"]
         assert np.array_equal(interp[0].i_in[sel], o["i_in"]) and np.array_equal(interp[0].j_out[sel], o["j_out"])
         assert np.max(np.abs(interp[0].area[sel] - o["area"]) / o["area"]) < RTOL
+        nd = _nbits(interp[0].area[sel], orc.orc_create_xgrid_gc(ni, ni, nlon, nlat, lon[t], lat[t], lo, la, cr=True)["area"])
+        assert nd == 0, f"tile {t}: {nd} of {o['n']} exchange-cell areas differ from the _cr oracle"
         tot += o["n"]
     assert interp[0].nxgrid == tot
     R = 6371000.0
     assert abs(interp[0].area.sum() / (4 * np.pi * R * R) - 1) < 1e-9          # great-circle cells tile the sphere
     # cell areas handed back are the great-circle ones (get_input_output_cell_area with GREAT_CIRCLE)
     assert np.max(np.abs(grid_in[2].cell_area - orc.orc_get_grid_gc_area(ni, ni, lon[2], lat[2])) / grid_in[2].cell_area) < RTOL
+    for t in range(6):
+        nd = _nbits(grid_in[t].cell_area, orc.orc_get_grid_gc_area(ni, ni, lon[t], lat[t], cr=True))
+        assert nd == 0, f"tile {t}: {nd} of {ni * ni} cell areas differ from the _cr oracle"
     rng = np.random.default_rng(2)
     field_in = [fg.FieldConfig(data=rng.standard_normal((1, ni, ni)) + 3.0, var=[fg.VarConfig(name="t", interp_method=fg.CONSERVE_ORDER1)])
                 for _ in range(6)]
@@ -139,6 +154,17 @@ def test_conserve_interp_great_circle_b1(fg, gpu_ok):
         ref[d[k]] += data[o["j_in"][k] * ni + o["i_in"][k]] * (o["area"][k] / dst_area[d[k]])
     assert np.max(np.abs(got - ref)) < 1e-12 * np.max(np.abs(ref))
     assert np.count_nonzero(got) == np.count_nonzero(ref) > 0
+    # the same loop on the _cr oracle's areas: same addends in the same order, so the bits
+    ocr = orc.orc_create_xgrid_gc(ni, ni, nlon, nlat, lon[0], lat[0], lo, la, mask=mask, cr=True)
+    assert ocr["n"] == o["n"]
+    dst_area = np.zeros(nlon * nlat)
+    for k in range(o["n"]):
+        dst_area[d[k]] += ocr["area"][k]
+    ref_cr = np.zeros(nlon * nlat)
+    for k in range(o["n"]):
+        ref_cr[d[k]] += data[o["j_in"][k] * ni + o["i_in"][k]] * (ocr["area"][k] / dst_area[d[k]])
+    nd = _nbits(got, ref_cr)
+    assert nd == 0, f"{nd} of {nlon * nlat} destination values differ from the replay on the _cr oracle's areas"
     if orc.ref_available():                     # the reference's own conserve_interp_great_circle (interp.c:312)
         cref = np.empty(nlon * nlat)
         orc.ref().conserve_interp_great_circle(ni, ni, nlon, nlat, orc._dp(orc.f64(lon[0])), orc._dp(orc.f64(lat[0])),
@@ -156,16 +182,21 @@ def test_great_circle_degenerate_cases(fg, gpu_ok):
     r = fg.create_xgrid_great_circle(24, 12, 24, 12, lo, la, lo, la)
     assert r[0] == o["n"] and np.array_equal(r[1], o["i_in"]) and np.array_equal(r[3], o["i_out"]) and np.array_equal(r[4], o["j_out"])
     assert np.max(np.abs(r[5] - o["area"]) / o["area"]) < RTOL
+    nd = _nbits(r[5], orc.orc_create_xgrid_gc(24, 12, 24, 12, lo, la, lo, la, cr=True)["area"])
+    assert nd == 0, f"{nd} of {r[0]} areas differ from the _cr oracle"
     assert r[0] >= 24 * 12                              # every cell at least meets itself
     lon, lat = fg.gnomonic_ed_corners(8)
     o = orc.orc_create_xgrid_gc(8, 8, 8, 8, lon[3], lat[3], lon[3], lat[3])
     r = fg.create_xgrid_great_circle(8, 8, 8, 8, lon[3], lat[3], lon[3], lat[3])
     assert r[0] == o["n"] and np.array_equal(r[3], o["i_out"]) and np.array_equal(r[4], o["j_out"])
     assert np.max(np.abs(r[5] - o["area"]) / o["area"]) < RTOL
+    nd = _nbits(r[5], orc.orc_create_xgrid_gc(8, 8, 8, 8, lon[3], lat[3], lon[3], lat[3], cr=True)["area"])
+    assert nd == 0, f"{nd} of {r[0]} areas differ from the _cr oracle"
     # disjoint regions
     lo1, la1 = fg.latlon_corners(6, 6, 10.0, 40.0, 10.0, 40.0)
     lo2, la2 = fg.latlon_corners(5, 5, 100.0, 140.0, -40.0, -10.0)
     assert orc.orc_create_xgrid_gc(6, 6, 5, 5, lo1, la1, lo2, la2)["n"] == 0
+    assert orc.orc_create_xgrid_gc(6, 6, 5, 5, lo1, la1, lo2, la2, cr=True)["n"] == 0
     assert fg.create_xgrid_great_circle(6, 6, 5, 5, lo1, la1, lo2, la2)[0] == 0
     # single cells, partial overlap
     lo3, la3 = fg.latlon_corners(1, 1, 10.0, 20.0, 10.0, 20.0)
@@ -173,9 +204,20 @@ def test_great_circle_degenerate_cases(fg, gpu_ok):
     o = orc.orc_create_xgrid_gc(1, 1, 1, 1, lo3, la3, lo4, la4)
     r = fg.create_xgrid_great_circle(1, 1, 1, 1, lo3, la3, lo4, la4)
     assert r[0] == o["n"] == 1 and abs(r[5][0] - o["area"][0]) < RTOL * o["area"][0]
+    nd = _nbits(r[5], orc.orc_create_xgrid_gc(1, 1, 1, 1, lo3, la3, lo4, la4, cr=True)["area"])
+    assert nd == 0, f"{nd} of 1 areas differ from the _cr oracle"
     # fully masked source
     r = fg.create_xgrid_great_circle(6, 6, 6, 6, lo1, la1, lo1, la1, mask_in=np.zeros(36))
     assert r[0] == 0
+    # partly masked source (the exchange-cell area is multiplied by the mask value)
+    (margs, mask) = gc_cases.degenerate_cases(fg)["masked_cubed_to_latlon"]
+    o = orc.orc_create_xgrid_gc(*margs, mask=mask)
+    r = fg.create_xgrid_great_circle(*margs, mask_in=mask)
+    assert r[0] == o["n"] > 0 and np.array_equal(r[1], o["i_in"]) and np.array_equal(r[2], o["j_in"])
+    assert np.array_equal(r[3], o["i_out"]) and np.array_equal(r[4], o["j_out"])
+    assert np.max(np.abs(r[5] - o["area"]) / o["area"]) < RTOL
+    nd = _nbits(r[5], orc.orc_create_xgrid_gc(*margs, mask=mask, cr=True)["area"])
+    assert nd == 0, f"{nd} of {r[0]} areas differ from the _cr oracle"
 
 
 @pytest.mark.parametrize("ni,nlon,nlat", [(24, 144, 90), (96, 360, 180), (48, 1440, 720)])
@@ -209,35 +251,12 @@ def test_three_pass_clip_equals_the_one_kernel_clip(fg, gpu_ok, ni, nlon, nlat):
     assert res[2][1]["deferred"] > 0.1 * sa["pairs"]          # the overflow path really ran
 
 
-def _rotated(lon, lat, ax, ang):
-    """corner arrays rotated about the unit axis `ax` by `ang` (a curvilinear grid whose edges cross everything at odd angles)"""
-    x, y, z = np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat)
-    v = np.stack([x, y, z], -1)
-    ax = np.asarray(ax, float) / np.linalg.norm(ax)
-    c, s = np.cos(ang), np.sin(ang)
-    r = v * c + np.cross(ax, v) * s + ax * (v @ ax)[..., None] * (1 - c)
-    lo = np.arctan2(r[..., 1], r[..., 0])
-    lo[lo < 0] += 2 * np.pi
-    return np.ascontiguousarray(lo), np.ascontiguousarray(np.arcsin(np.clip(r[..., 2], -1, 1)))
-
-
 def test_three_pass_clip_on_awkward_grid_pairs(fg, gpu_ok):
     """Pairs of grids chosen to sit on the branches of the three-pass clip: edges and corners that almost coincide (shifts of
     1e-9 .. 1e-5 rad: snapped, nearly snapped and borderline-inside cases), generic crossings at odd angles (rotated grids),
-    coarse against fine, tripolar folds, regional windows.  Three passes == one-kernel clip bit for bit; the small cases also
-    against the oracle."""
-    lo72, la72 = fg.latlon_corners(72, 36)
-    reg = fg.latlon_corners(40, 30, 20.0, 100.0, -35.0, 40.0)
-    c16 = fg.gnomonic_ed_corners(16)
-    tri = fg.tripolar_corners(60, 40)
-    cases = []
-    for sh in (1e-9, 3e-8, 1e-6, 1e-5):
-        cases.append((72, 36, 72, 36, lo72, la72, np.ascontiguousarray(lo72 + sh), la72))
-    cases.append((40, 30, 40, 30) + reg + _rotated(*reg, (0.3, -0.5, 0.8), 0.37))
-    cases.append((72, 36, 40, 30, lo72, la72) + _rotated(*reg, (1.0, 0.2, 0.1), 1.1))
-    cases.append((16, 16, 40, 30, c16[0][1], c16[1][1]) + reg)
-    cases.append((16, 16, 16, 16, c16[0][0], c16[1][0]) + _rotated(c16[0][0], c16[1][0], (0.1, 0.9, 0.4), 0.05))
-    cases.append((60, 40, 72, 36) + tri + (lo72, la72))
+    coarse against fine, tripolar folds, regional windows (gc_cases.awkward_pairs).  Three passes == one-kernel clip bit for bit;
+    the small cases also against the oracle: lists, areas to 1e-10 against the plain build and in bits against the _cr build."""
+    cases = gc_cases.awkward_pairs(fg)
     def run(args):
         """plan API (errors come back as exceptions instead of the reference's exit): (xgrid dict | None, message)"""
         nxi, nyi, nxo, nyo, loi, lai, loo, lao = args
@@ -275,4 +294,43 @@ def test_three_pass_clip_on_awkward_grid_pairs(fg, gpu_ok):
             assert np.array_equal(b["i_in"], o["i_in"]) and np.array_equal(b["j_in"], o["j_in"]), ci
             assert np.array_equal(b["i_out"], o["i_out"]) and np.array_equal(b["j_out"], o["j_out"]), ci
             assert np.max(np.abs(b["area"] - o["area"]) / o["area"]) < RTOL, ci
+            nd = _nbits(b["area"], orc.orc_create_xgrid_gc(*args, cr=True)["area"])
+            assert nd == 0, f"case {ci}: {nd} of {o['n']} areas differ from the _cr oracle"
     assert nok >= 5
+
+
+@pytest.fixture(scope="module")
+def crafted():
+    """the crafted batch with what the oracle makes of it, computed once: n_out and vertices from the plain build, areas from the
+    _cr build (great_circle_area with the device's arc cosine)"""
+    a, b, fam = gc_cases.crafted_batch()
+    n_ref = np.zeros(len(a), dtype=np.int32)
+    v_ref = np.zeros((len(a), 16, 3))
+    area_cr = np.zeros(len(a))
+    for q in range(len(a)):
+        n, v = orc.orc_clip_gc(a[q], b[q])
+        assert 0 <= n <= 16
+        n_ref[q] = n
+        v_ref[q, :n] = v
+        if n > 0:
+            area_cr[q] = orc.orc_great_circle_area(*v.T, cr=True)
+    return a, b, fam, n_ref, v_ref, area_cr
+
+
+@pytest.mark.parametrize("size", [1, 63, 64, 65, 257, "all"])
+def test_clip_batch_on_the_crafted_batch(fg, gpu_ok, crafted, size):
+    """fg_gc_clip_batch on cell pairs made for the arc cosine's hard arguments (shifted and turned copies from 1e-9 rad, a vertex
+    at a pole, quads 1e-4 as tall as wide, sliver triangles, cells whose area glibc's acosl rounds the other way:
+    gc_cases.crafted_batch, shown to reach them in tests/test_gc_oracle_cr_cpu.py), at batch sizes with a partial last wave (one
+    block is one wave of 64) and the whole batch: n_out and vertices in bits against the plain oracle, ALL areas in bits
+    against great_circle_area with the device's arc cosine.  The short batches are taken across the families."""
+    a, b, fam, n_ref, v_ref, area_cr = crafted
+    sel = np.arange(len(a)) if size == "all" else np.arange(size) * (len(a) // size)
+    n_out, verts, area = fg.gc_clip_batch(a[sel], b[sel])
+    assert np.array_equal(n_out, n_ref[sel]), np.flatnonzero(n_out != n_ref[sel])[:10]
+    nd = _nbits(verts, v_ref[sel])                      # (both zero past n_out)
+    assert nd == 0, f"{nd} vertex coordinates differ from the oracle"
+    bad = np.flatnonzero(_bits(area) != _bits(area_cr[sel]))
+    assert len(bad) == 0, f"{len(bad)} of {len(sel)} areas differ from the _cr oracle, first: pair {sel[bad[0]]} ({fam[sel[bad[0]]]})"
+    if size == "all":
+        assert np.count_nonzero(n_out) > 2000

@@ -1,7 +1,8 @@
 """latlon2xyz on the device and the great-circle plan entries that start from lon / lat (fg_dev_latlon2xyz,
 fg_plan_create_great_circle_lonlat, fg_plan_create_great_circle_lonlat_dev): the unit vectors carry the bits of the compiled
 reference's latlon2xyz, so the plans are the ones fg_plan_create_great_circle builds from host-made unit vectors -- bit for bit --
-and agree with the reference's create_xgrid_great_circle to the bar test_gpu_great_circle.py sets."""
+and agree with the reference's create_xgrid_great_circle to the bar test_gpu_great_circle.py sets: lists exact, areas to 1e-10
+and 98 % in bits against the reference, all of them in bits against the oracle's _cr build (the device's arc cosine)."""
 import ctypes as C
 
 import numpy as np
@@ -160,11 +161,13 @@ def test_great_circle_lonlat_equals_xyz_entry(fg, gpu_ok, name, masked):
 @pytest.mark.parametrize("name", ["c24_tile1_144x90", "latlon_aligned_2x"])
 def test_great_circle_lonlat_vs_reference(fg, gpu_ok, name):
     """Against the reference's own entry from lon / lat (create_xgrid_great_circle of the compiled reference): lists exact,
-    areas to the bar of test_create_xgrid_great_circle_vs_oracle."""
+    areas to the bar of test_create_xgrid_great_circle_vs_oracle, and every one in bits against the oracle's _cr build."""
     assert orc.ref_available(), "oracle/_ref/libfrenc_ref.so is missing: build() makes it from the reference sources"
     args = _cases(fg)[name]
     nxi, nyi, nxo, nyo, loi, lai, loo, lao = args
     o = orc.ref_create_xgrid_gc(*args)
+    ocr = orc.orc_create_xgrid_gc(*args, cr=True)          # the oracle that rounds like the device: every area, in bits
+    assert ocr["n"] == o["n"]
     for plan in _three_plans(fg, [fg.GridConfig(nxi, nyi, loi, lai)], fg.GridConfig(nxo, nyo, loo, lao), None)[1:]:
         x = plan.get_xgrid()
         plan.destroy()
@@ -175,6 +178,8 @@ def test_great_circle_lonlat_vs_reference(fg, gpu_ok, name):
         assert rel.max() < RTOL
         same = np.mean(_bits(x["area"]) == _bits(o["area"]))
         assert same > 0.98, same
+        nd = int(np.count_nonzero(_bits(x["area"]) != _bits(ocr["area"])))
+        assert nd == 0, f"{nd} of {o['n']} exchange-cell areas differ from the _cr oracle"
 
 
 def test_great_circle_lonlat_domain_error(fg, gpu_ok):

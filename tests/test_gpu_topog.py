@@ -1,13 +1,15 @@
 """make_topog's realistic topography on the device against the reference's fixtures (tests/golden/topog_*.npz,
 tests/topog_cases.py): the source preparation, the depth after the remap, after filter_topo and after process_topo bit for bit,
 num_levels and the reference's three counts equal, for the whole chain and for each stage fed the reference's intermediate, with
-the isolated-cell step evaluated both as the in-place sweep and all cells at once; the great-circle remap to the bar of
-test_gpu_great_circle.py; the reference's errors; two handles; a second source on one handle."""
+the isolated-cell step evaluated both as the in-place sweep and all cells at once; the great-circle remap to 1e-12 of the largest
+depth against the reference's fixture (glibc's acosl rounds an angle differently now and then) and bit for bit against the remap
+replayed on the exchange cells of the oracle that rounds like the device (gc_oracle.c's _cr build); the reference's errors; two handles; a second source on one handle."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import orc
 import topog_cases as tc
 
 pytestmark = pytest.mark.gpu
@@ -84,11 +86,31 @@ def test_whole_chain_equals_the_reference(fg, fixtures, name):
 def test_great_circle_remap_then_the_stages_from_the_reference_intermediate(fg, fixtures):
     fx = fixtures["cube_c6_gca"]
     with fg.Topog(fx["x_dst"], fx["y_dst"], **tc.options(fx)) as h:
-        h.source(fx["xt_src"], fx["yt_src"], fx["data"], float(fx["missing"])).remap()
+        h.source(fx["xt_src"], fx["yt_src"], fx["data"], float(fx["missing"]))
+        src = h.source_arrays()
+        h.remap()
         got, ref = h.depth(), fx["depth_remap"]
         print("great-circle remap: max |diff|", float(np.abs(got - ref).max()), "bar", 1e-12 * float(np.abs(ref).max()))
         assert np.abs(got - ref).max() <= 1e-12 * np.abs(ref).max()
         assert h.stats()["nxgrid"] > 0
+        # conserve_interp_great_circle (interp.c:312-356) replayed on the exchange cells of the oracle that rounds like the device
+        # (gc_oracle.c's _cr build): per destination cell the sum of its areas in list order, then data * (area / sum) added in
+        # list order -- k_apply_frac's order -- so the depth after the remap in bits
+        ny_now, nxs = src["depth_src"].shape
+        ny, nx = got.shape
+        o = orc.orc_create_xgrid_gc(nxs, ny_now, nx, ny, src["x_src"], src["y_src"], fx["x_dst"] * tc.D2R, fx["y_dst"] * tc.D2R,
+                                    mask=src["mask_src"], cr=True)
+        assert o["n"] == h.stats()["nxgrid"]
+        d = o["j_out"].astype(np.int64) * nx + o["i_out"]
+        s = o["j_in"].astype(np.int64) * nxs + o["i_in"]
+        dst_area, replay = np.zeros(nx * ny), np.zeros(nx * ny)
+        for k in range(o["n"]):
+            dst_area[d[k]] += o["area"][k]
+        data = src["depth_src"].ravel()
+        for k in range(o["n"]):
+            replay[d[k]] += data[s[k]] * (o["area"][k] / dst_area[d[k]])
+        nd = int((bits(got).ravel() != bits(replay)).sum())
+        assert nd == 0, f"{nd} of {nx * ny} depths differ from the replay on the _cr oracle's exchange cells"
         h.set_depth(fx["depth_remap"]).filter()
         same("depth after filter", h.depth(), fx["depth_filter"])
         h.set_depth(with_first_row(fx, fx["depth_filter"])).process(fx["zw"])
