@@ -258,9 +258,9 @@ class XgridPlan:
         check(lib().fg_plan_accumulate_cell_sums(*args))
 
     def stats(self):
-        s = (C.c_long * 10)()
-        check(lib().fg_plan_stats(self._h, s, 10))
-        names = ["pairs", "nonempty", "nxgrid", "borderline", "bins", "bin_entries", "deferred", "heavy", "below", "exact_mode"]
+        s = (C.c_long * 11)()
+        check(lib().fg_plan_stats(self._h, s, 11))
+        names = ["pairs", "nonempty", "nxgrid", "borderline", "bins", "bin_entries", "deferred", "heavy", "below", "exact_mode", "rare"]
         return dict(zip(names, [int(v) for v in s]))
 
     PHASES = ["cell_struct", "bins", "candidates", "clip_quad", "clip_general", "compact", "rows",

@@ -699,6 +699,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   char *zero_blk = blk.get<char>(zbytes);
   int *bin_start = blk.get<int>(nslots + 1);
   int *heavy_list = blk.get<int>(nsrc + 1);
+  int *rare_list = blk.get<int>(rect ? nsrc + 1 : 1);  // rectilinear path: the cells k_candidates_rect finishes (laid out like heavy_list)
   int *big_list = blk.get<int>(nsrc + 1);
   int *pair_beg = blk.get<int>(nsrc + 1), *pair_cnt = blk.get<int>(nsrc + 1);
   FgBinEntry *bin_entries = blk.get<FgBinEntry>(nentries ? nentries : 1);
@@ -763,7 +764,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
     if (pl->polys.npoly) fgd_polylist_records(pl->polys, pl->S, pl->src_idx_f, pl->sums, &R, heavy_list, &dc->heavy_cnt, dc->err, st);
     fgd_cell_struct2r(ts, pl->tiles_dev, pl->tiles_dev, pl->ntiles, pl->polys.npoly ? 0 : nsrc, ndst, pl->S, pl->D.area, R, pl->mask_dev, order,
                       pl->src_idx_f, pl->sums, dc->err, st, dc->band_keys, (opt.cull && !pl->polys.npoly) ? 2 : 0, heavy_list, &dc->heavy_cnt,
-                      ps, pair_beg, pair_cnt, big_list, &dc->big_cnt);
+                      rare_list, &dc->rare_cnt, ps, pair_beg, pair_cnt, big_list, &dc->big_cnt);
   } else if (opt.cull && !boxm && !pl->polys.npoly) {
     // the destination grid's latitude range from its corners (a 5 us reduction), then ONE record launch in which the source
     // blocks that cannot meet it leave early (round 2 first ran a destination launch, then a source launch: two latency floors)
@@ -790,7 +791,8 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   pt.begin(PH_CANDIDATES);
   if (rect)
     fgd_candidates_rect(nsrc, pl->S, pl->mask_dev, pl->rect_tab, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list, &dc->big_cnt, st,
-                        pl->polys.npoly ? 0 : 1);         // (the record kernel made the candidates of every cell that is not listed)
+                        pl->polys.npoly ? 0 : 1,          // (the record kernel made the candidates of every cell that is not listed)
+                        rare_list, &dc->rare_cnt, dc->err);
   else
     fgd_candidates1(nsrc, pl->S, pl->mask_dev, bins, bin_start, bin_entries, ecap, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list,
                     &dc->big_cnt, st);
@@ -903,6 +905,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   pl->stats[FG_STAT_BIN_ENTRIES] = (long)hc->total[0];
   pl->stats[FG_STAT_DEFERRED] = hc->defer_cnt + hc->gc_list2_cnt;
   pl->stats[FG_STAT_HEAVY] = hc->heavy_cnt;
+  pl->stats[FG_STAT_RARE] = hc->rare_cnt;
   pl->stats[FG_STAT_BELOW] = (long)hc->stats[FG_STAT_BELOW];
 
   pl->rect_tab.bad = nullptr;                          // (lives in the scratch block released below; nothing reads it after the search)

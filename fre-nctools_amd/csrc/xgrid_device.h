@@ -53,7 +53,8 @@ enum {
   FG_STAT_HEAVY = 7,      // source cells whose candidate scan got a whole wave
   FG_STAT_BELOW = 8,      // non-empty clips rejected by the 1e-6 area ratio
   FG_STAT_EXACT = 9,      // 1 if the plan was built by the exactly sized (three-readback) search, 0 by the single-sync one
-  FG_NSTATS = 10
+  FG_STAT_RARE = 10,      // rectilinear path: source cells that need the general fix_lon (their records are finished by k_candidates_rect)
+  FG_NSTATS = 11
 };
 
 // ---- candidate pairs: one pair list in FG_NREG regions of `regcap` entries.  A wave of the candidate kernel appends the
@@ -116,6 +117,7 @@ struct FgCounters {
   unsigned rect_bad;               // rectilinear path: != 0 = the destination grid failed the check (k_rect_tables)
   int defer_cnt, big_cnt;
   int gc_list2_cnt;                // great-circle path: pairs k_gc_walk handed to the one-kernel clip
+  int rare_cnt;                    // rectilinear path: cells of rare_list (k_cell_struct2r -> k_candidates_rect)
   unsigned long long stats[FG_NSTATS];
 };
 #define G_ERRBIT_LOOKBACK 128u     // a single-pass scan waited too long for its predecessor tile (never observed)
@@ -165,8 +167,9 @@ void fgd_rect_tables(const double *lon, const double *lat, int nx, int ny, doubl
                      double dst_tlon = 3.14159265358979323846);
 void fgd_cell_struct2r(const FgTileSet &ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst, FgCells S, double *area_out,
                        FgRect R, const double *mask, int order, int *src_idx_f, double *sums, unsigned *err, hipStream_t st,
-                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt, FgPairSpace ps, int *pair_beg, int *pair_cnt,
-                       int *big_list, int *big_cnt);   // source blocks also make the candidates of their cells (all but the listed ones)
+                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt, int *rare_list, int *rare_cnt, FgPairSpace ps,
+                       int *pair_beg, int *pair_cnt, int *big_list, int *big_cnt);   // source blocks also make the candidates of their cells (all but
+                                                                                     // the listed ones); rare_list: cells whose records are still to finish
 void fgd_rect_materialize(int ndst, FgRect R, FgCells D, hipStream_t st);
 // Source "cells" given as a list of polygons (<= 8 vertices each, already in the longitude frame they are to be clipped in):
 // fills the source records a search needs (box, vertices, the caller's lon_avg and reference area), the field index, zeroes the
@@ -175,7 +178,8 @@ struct FgPolyList { const int *n; const double *lon, *lat; const double *lon_avg
 void fgd_polylist_records(FgPolyList P, FgCells S, int *src_idx_f, double *sums, const FgRect *rect, int *heavy_list, int *heavy_cnt,
                           unsigned *err, hipStream_t st);
 void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPairSpace ps, int *pair_beg, int *pair_cnt,
-                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only);
+                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only,
+                         const int *rare_list = nullptr, const int *rare_cnt = nullptr, unsigned *err = nullptr);     // listed_only (behind fgd_cell_struct2r): also finishes the cells of rare_list
 // rect != null: the destination cells come from the rectilinear tables (D holds areas only)
 void fgd_clip_general(int order, FgPairSpace ps, FgCells S, const double *mask, FgCells D,
               double *tmp_area, double *tmp_clon, double *tmp_clat, int *nacc, int *defer_list, int *defer_cnt,

@@ -248,15 +248,23 @@ void fgd_exclusive_scan1(const int *in, long n, int *out, unsigned long long *st
 // cull != null: {max key of lat_max, max of ~key of lat_min} over the destination cells (this rank's band): a cell whose
 // latitude range cannot meet the band -- the reference's strict test, create_xgrid.c:1055, would reject every pair -- gets
 // nv = 0 and area 0 and nothing else; a block without a live cell skips its vertex records altogether.
+// QUADS_ONLY (k_cell_struct2r): a cell that needs the general fix_lon -- a pole vertex, an edge of |dlon| = pi: eight of the
+// 884 736 cells of C384 -- gets its latitude box, its corners as read (in its vertex record) and *rare = true; the caller lists it and a wave of k_candidates_rect
+// finishes its record (d_finish_rare_cell).  Everything else is then a quadrilateral: four vertices in registers instead of
+// the general routine's two 12-element arrays (32 VGPRs of every wave), a four-edge area, and a staging tile of the eight live
+// coordinates per cell (vtile is [256 * 9] then, [256 * 17] otherwise); the other eight doubles of a record are stored as zeros.
+template <bool QUADS_ONLY = false>
 __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, int ncells, const FgCells &c, unsigned *err, int s0,
                                              double *vtile, double *box /* lat_min, lat_max, lon_min, lon_max */, int *tile_of,
-                                             const unsigned long long *cull = nullptr, double tlon = G_PI)
+                                             const unsigned long long *cull = nullptr, double tlon = G_PI, bool *rare = nullptr)
 {
+  constexpr int VS = QUADS_ONLY ? 9 : 17, NLIVE = QUADS_ONLY ? 8 : 16, CAP = QUADS_ONLY ? 4 : G_FIXCAP;
   const int s = s0 + threadIdx.x;
-  double *row = vtile + threadIdx.x * 17;
+  double *row = vtile + threadIdx.x * VS;
 #pragma unroll
-  for (int k = 0; k < 16; k++) row[k] = 0.0;
+  for (int k = 0; k < NLIVE; k++) row[k] = 0.0;
   int nvert = 0;
+  bool listed = false;
   if (s < ncells) {
     int t = 0;
     while (t + 1 < ntiles && s >= tiles[t + 1].cell_off) t++;
@@ -266,7 +274,7 @@ __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, in
     int i = loc % T.nx, j = loc / T.nx;
     int nxp = T.nx + 1;
     int n0 = j * nxp + i, n1 = n0 + 1, n3 = n0 + nxp, n2 = n3 + 1;
-    double x[G_FIXCAP], y[G_FIXCAP];
+    double x[CAP], y[CAP];
     x[0] = T.lon[n0]; y[0] = T.lat[n0];
     x[1] = T.lon[n1]; y[1] = T.lat[n1];
     x[2] = T.lon[n2]; y[2] = T.lat[n2];
@@ -283,11 +291,32 @@ __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, in
       out_of_band = (lmax <= bmin) || (lmin >= bmax);
     }
     int n = out_of_band ? 0 : d_fix_lon_quad_fast(x, y, tlon);
-    if (n < 0) n = d_fix_lon(x, y, 4, tlon);             // cells with a pole vertex / a half-turn edge: the general routine
+    if constexpr (!QUADS_ONLY) {
+      if (n < 0) n = d_fix_lon(x, y, 4, tlon);           // cells with a pole vertex / a half-turn edge: the general routine
+    }
     if (out_of_band) { c.nv[s] = 0; c.area[s] = 0; }
+    else if (QUADS_ONLY && n < 0) {                      // (the caller's list: the rest of the record comes from k_candidates_rect,
+      listed = true;                                     //  which finds the cell's corners, untouched, where its vertices will be)
+#pragma unroll
+      for (int k = 0; k < 4; k++) { row[k] = x[k]; row[4 + k] = y[k]; }
+    }
     else if (n < 0 || n > G_MAXV) {
       atomicOr(err, G_ERRBIT_MAXV);
       c.nv[s] = 0; c.lon_min[s] = 0; c.lon_max[s] = 0; c.lon_avg[s] = 0; c.area[s] = 0;
+    } else if constexpr (QUADS_ONLY) {                   // n = 4: the same operations in the same order as below
+      double xmin = x[0], xmax = x[0], xs = 0;
+#pragma unroll
+      for (int k = 1; k < 4; k++) { if (x[k] < xmin) xmin = x[k]; if (x[k] > xmax) xmax = x[k]; }
+#pragma unroll
+      for (int k = 0; k < 4; k++) xs += x[k];
+      xs /= 4;
+      c.lon_min[s] = xmin; c.lon_max[s] = xmax; c.lon_avg[s] = xs;
+      box[2] = xmin; box[3] = xmax; box[4] = xs;
+      c.nv[s] = 4;
+      nvert = 4;
+#pragma unroll
+      for (int k = 0; k < 4; k++) { row[k] = x[k]; row[4 + k] = y[k]; }
+      c.area[s] = d_poly_area<1>(x, y, 4);
     } else {
       double xmin = x[0], xmax = x[0], xs = 0;
       for (int k = 1; k < n; k++) { if (x[k] < xmin) xmin = x[k]; if (x[k] > xmax) xmax = x[k]; }
@@ -304,15 +333,60 @@ __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, in
       c.area[s] = d_poly_area<1>(x, y, n);
     }
   }
-  if (!__syncthreads_or(nvert != 0) && cull) return 0;        // no live cell in this block: no vertex records to store
+  if (QUADS_ONLY) *rare = listed;
+  // no live cell in this block: no vertex records to store (a listed cell is live: its block stores, as it did before)
+  if (!__syncthreads_or(nvert != 0 || listed) && cull) return 0;
   const long cnt = (long)min(256, ncells - s0) * 16;
   double *out = c.verts + (size_t)s0 * 16;
 #pragma unroll
   for (int q = 0; q < 16; q++) {
     const long e = (long)q * 256 + threadIdx.x;
-    if (e < cnt) out[e] = vtile[(e >> 4) * 17 + (e & 15)];
+    if constexpr (QUADS_ONLY) {                          // vertex k of the record at 0..3 (lon) and 8..11 (lat); 4..7 and 12..15 are zeros
+      const int k = (int)e & 15;
+      if (e < cnt) out[e] = (k & 4) ? 0.0 : vtile[(e >> 4) * VS + ((k >> 3) << 2) + (k & 3)];
+    } else if (e < cnt) out[e] = vtile[(e >> 4) * VS + (e & 15)];
   }
   return nvert;
+}
+
+// The rest of the record of a cell k_cell_struct2r listed (d_cell_record<true>): the general fix_lon and, from its vertices, what
+// d_cell_record stores -- the same routines on the same inputs.  Every lane of the wave computes the same values, lane 0 stores.
+// Returns the vertex count (0: no record) and the box.
+__device__ __forceinline__ int d_finish_rare_cell(const FgCells &c, unsigned *err, int s, int lane, double *box)
+{
+  double *v = c.verts + (size_t)s * 16;
+  double x[G_FIXCAP], y[G_FIXCAP];
+#pragma unroll
+  for (int k = 0; k < 4; k++) { x[k] = v[k]; y[k] = v[8 + k]; }      // the corners as the record kernel read them: one round of loads
+  double lmin = y[0], lmax = y[0];
+#pragma unroll
+  for (int k = 1; k < 4; k++) { if (y[k] < lmin) lmin = y[k]; if (y[k] > lmax) lmax = y[k]; }
+  box[0] = lmin; box[1] = lmax;                          // (stored, and checked for G_ERRBIT_BADLAT, by the record kernel)
+  const int n = d_fix_lon(x, y, 4, G_PI);
+  if (n < 0 || n > G_MAXV) {
+    if (lane == 0) {
+      atomicOr(err, G_ERRBIT_MAXV);
+      c.nv[s] = 0; c.lon_min[s] = 0; c.lon_max[s] = 0; c.lon_avg[s] = 0; c.area[s] = 0;
+      for (int k = 0; k < 16; k++) v[k] = 0.0;
+    }
+    return 0;
+  }
+  double xmin = x[0], xmax = x[0], xs = 0;
+  for (int k = 1; k < n; k++) { if (x[k] < xmin) xmin = x[k]; if (x[k] > xmax) xmax = x[k]; }
+  for (int k = 0; k < n; k++) xs += x[k];
+  xs /= n;
+  box[2] = xmin; box[3] = xmax; box[4] = xs;
+  const double area = d_poly_area<1>(x, y, n);
+  if (lane == 0) {
+    c.lon_min[s] = xmin; c.lon_max[s] = xmax; c.lon_avg[s] = xs;
+    c.nv[s] = n;
+    for (int k = 0; k < G_MAXV; k++) {
+      v[k] = (k < n) ? x[k] : 0.0;
+      v[8 + k] = (k < n) ? y[k] : 0.0;
+    }
+    c.area[s] = area;
+  }
+  return n;
 }
 
 __global__ __launch_bounds__(256) void k_cell_struct(const FgTile *tiles, int ntiles, int ncells, FgCells c, unsigned *err)
@@ -1049,7 +1123,10 @@ __device__ __forceinline__ int d_kth_set_bit(unsigned long long m, unsigned k)
 // without being listed as heavy (a stretched axis: d_rect_heavy goes by the MEAN spacing) re-tests and writes its own pairs,
 // as every lane did before; its slots are skipped by the others (nc = 0 in LDS).
 // Returns whether the cell is heavy (its candidates are made by a wave of k_candidates_rect instead).
+// ONE: the wave has a single cell, lane 0's (every lane passes the same s, only lane 0 is active): a cell whose record
+// k_candidates_rect has just finished.
 #define RECT_WL_WORDS 10             // LDS words per lane: excl, nc, cmask lo / hi, j0, wa0, l0, wa1 - l0, l0 + l1, wa2 - l0 - l1
+template <bool ONE = false>
 __device__ __forceinline__ bool d_rect_wave_candidates(const FgRect &R, const FgPairSpace &ps, bool active, int s, int nsrc, unsigned wave_no,
                                                        double lat_in_min, double lat_in_max, double lon_in_min, double lon_in_max,
                                                        double lon_in_avg, int *pair_beg, int *pair_cnt, int *big_list, int *big_cnt,
@@ -1083,7 +1160,7 @@ __device__ __forceinline__ bool d_rect_wave_candidates(const FgRect &R, const Fg
   base = __shfl(base, 0);
   int n_ok = 0;
   const unsigned first = base + excl;
-  if (s < nsrc && !heavy) {
+  if (s < nsrc && !heavy && (!ONE || lane == 0)) {
     const int loc0 = (int)min(first, (unsigned)ps.regcap);
     n_ok = min(cnt, ps.regcap - loc0);
     pair_beg[s] = r * ps.regcap + loc0;
@@ -1113,7 +1190,7 @@ __device__ __forceinline__ bool d_rect_wave_candidates(const FgRect &R, const Fg
   // the wave's slots that lie inside the region: o < lim is the owner's clamp t = o - excl < n_ok
   const unsigned lim = min(total, (unsigned)ps.regcap - min(base, (unsigned)ps.regcap));
   int *wsrc = ps.src + (size_t)r * ps.regcap + base, *wdst = ps.dst + (size_t)r * ps.regcap + base;
-  const int s_first = s - lane;
+  const int s_first = ONE ? s : s - lane;                    // (ONE: the owner L is always lane 0)
   for (unsigned ob = 0; ob < lim; ob += 64) {
     const unsigned o = ob + lane;
     if (o >= lim || base + o >= (unsigned)ps.regcap) continue;   // (the second test repeats, at the store, what lim holds: an attempt with
@@ -1144,15 +1221,20 @@ __device__ __forceinline__ bool d_rect_wave_candidates(const FgRect &R, const Fg
 // Rectilinear twin of k_cell_struct2: source blocks make the full records AND, from the box still in registers, the candidates of
 // their cells (d_rect_wave_candidates; the cells whose candidates a whole wave will make are listed for k_candidates_rect);
 // destination blocks store the cell AREA only.
-__global__ __launch_bounds__(256, 4) void k_cell_struct2r(FgTileSet ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst,
+// The source role is latency-bound (its predecessor: two thirds of its wave cycles not issuing), so its occupancy matters, and
+// that was set by code for cells it hardly ever meets: the general fix_lon (127 VGPRs) and a staging tile of all 16 doubles of
+// a record (38.9 KB with the tables: four blocks per CU).  The cells that need the general routine are listed (rare_list) and
+// finished by k_candidates_rect<true>; the tile holds the eight live coordinates of a quadrilateral.
+#define RECORD_WAVES 7      // waves per SIMD: 59 VGPRs; 22.5 KB of LDS per block give seven blocks per CU
+__global__ __launch_bounds__(256, RECORD_WAVES) void k_cell_struct2r(FgTileSet ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst,
                                                         int nbS, FgCells S, double *area_out, FgRect R, const double *mask, int order, int *src_idx_f,
                                                         double *sums, unsigned *err, unsigned long long *band_keys, int cull,
-                                                        int *heavy_list, int *heavy_cnt, FgPairSpace ps, int *pair_beg, int *pair_cnt,
-                                                        int *big_list, int *big_cnt)
+                                                        int *heavy_list, int *heavy_cnt, int *rare_list, int *rare_cnt, FgPairSpace ps,
+                                                        int *pair_beg, int *pair_cnt, int *big_list, int *big_cnt)
 {
-  __shared__ double vtile[256 * 17];
+  __shared__ double vtile[256 * 9];
   __shared__ FgTile sh_tiles[FG_TILESET_MAX];
-  static_assert(64 * RECT_WL_WORDS * sizeof(unsigned) <= 64 * 17 * sizeof(double), "a wave's share of vtile holds its candidate words");
+  static_assert(64 * RECT_WL_WORDS * sizeof(unsigned) <= 64 * 9 * sizeof(double), "a wave's share of vtile holds its candidate words");
   if (*R.bad) return;
   if (ts.n && (int)threadIdx.x < ts.n) sh_tiles[threadIdx.x] = ts.t[threadIdx.x];
   const bool isD = (int)blockIdx.x >= nbS;
@@ -1202,7 +1284,17 @@ __global__ __launch_bounds__(256, 4) void k_cell_struct2r(FgTileSet ts, const Fg
     double box[5] = {0, 0, 0, 0, 0};
     int tl = 0;
     const int s0 = blockIdx.x * 256, s = s0 + threadIdx.x, lane = threadIdx.x & 63;
-    const int nv = d_cell_record(tiles, ntiles, nsrc, S, err, s0, vtile, box, &tl, cull ? band_keys : nullptr);
+    bool rare = false;
+    const int nv = d_cell_record<true>(tiles, ntiles, nsrc, S, err, s0, vtile, box, &tl, cull ? band_keys : nullptr, G_PI, &rare);
+    {
+      const unsigned long long m = __ballot(rare);         // the cells whose records k_candidates_rect finishes (hardly ever any)
+      if (m) {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(rare_cnt, __popcll(m));
+        base = __shfl(base, 0);
+        if (rare) rare_list[base + __popcll(m & ((1ull << lane) - 1ull))] = s;
+      }
+    }
     if (s < nsrc && sums) { sums[s] = 0.0; sums[nsrc + s] = 0.0; sums[2 * (size_t)nsrc + s] = 0.0; }
     if (s < nsrc && src_idx_f) {
       if (order != 2) src_idx_f[s] = s;
@@ -1215,11 +1307,11 @@ __global__ __launch_bounds__(256, 4) void k_cell_struct2r(FgTileSet ts, const Fg
     }
     // the candidates, in the wave's share of vtile (d_cell_record is through with it); wave blockIdx.x * 4 + wave holds the cells
     // [64 * that, + 64), so the region hash is the one of the stand-alone kernel's block numbers
-    // (lon_avg comes back from the record this lane has just stored: held in registers across d_cell_record it cost the kernel
-    //  its fourth block per CU -- 129 VGPRs -- or, under a launch bound, 12 bytes of scratch)
+    // (lon_avg stays in a register: while the record code held the general routine's arrays it had to come back from the
+    //  record this lane had just stored, a dependent round trip, or cost the kernel a block per CU)
     const bool active = s < nsrc && nv > 0 && (!mask || mask[s] > 0.5);
-    const bool heavy = d_rect_wave_candidates(R, ps, active, s, nsrc, (unsigned)(s >> 6), box[0], box[1], box[2], box[3], active ? S.lon_avg[s] : 0.0, pair_beg, pair_cnt,
-                                              big_list, big_cnt, (unsigned *)(vtile + (threadIdx.x >> 6) * (64 * 17)));
+    const bool heavy = d_rect_wave_candidates(R, ps, active, s, nsrc, (unsigned)(s >> 6), box[0], box[1], box[2], box[3], box[4], pair_beg, pair_cnt,
+                                              big_list, big_cnt, (unsigned *)(vtile + (threadIdx.x >> 6) * (64 * 9)));
     const unsigned long long m = __ballot(heavy);
     if (m) {
       int base = 0;
@@ -1291,63 +1383,96 @@ __global__ __launch_bounds__(256) void k_rect_materialize(int ndst, FgRect R, Fg
   v[8] = ya; v[9] = ya; v[10] = yb; v[11] = yb;
 }
 
+// The candidates of ONE source cell made by a whole wave (a cell listed as heavy: pole caps, every column): count, reserve, fill.
+__device__ __forceinline__ void d_rect_cell_candidates(const FgRect &R, const FgPairSpace &ps, int s, int lane, double lat_in_min, double lat_in_max,
+                                                       double lon_in_min, double lon_in_max, double lon_in_avg, int *pair_beg, int *pair_cnt,
+                                                       int *big_list, int *big_cnt)
+{
+  const RectQuery q = d_rect_query(R, lat_in_min, lat_in_max, lon_in_min, lon_in_max);
+  const int nwc = d_rect_ncols(q), nr = q.j1 - q.j0 + 1;
+  // pass 1: the columns that pass (the same set for every row of the query); pass 2 writes row after row -- the flags are
+  // recomputed per 64-column chunk instead of listed (a list in LDS would cost every block of the launch its occupancy)
+  int nc = 0;
+  for (int kb = 0; kb < nwc; kb += 64) {
+    const int k = kb + lane;
+    const bool pass = k < nwc && d_rect_col_pass(R, d_rect_col(q, k), lon_in_min, lon_in_max, lon_in_avg);
+    nc += __popcll(__ballot(pass));
+  }
+  const long cnt_l = (long)nr * nc;
+  const int cnt = (int)min(cnt_l, 0x7fffffffL);
+  const int r = (int)(((unsigned)s * 2654435761u >> 12) % (unsigned)ps.nreg);
+  unsigned base = 0;
+  if (lane == 0 && cnt) base = atomicAdd(&ps.fill[r * FG_FILL_STRIDE], (unsigned)cnt);
+  base = __shfl(base, 0);
+  const int loc0 = (int)min(base, (unsigned)ps.regcap), n_ok = min(cnt, ps.regcap - loc0);
+  const int wbase = r * ps.regcap + loc0;
+  int cbase = 0;
+  for (int kb = 0; kb < nwc && n_ok > 0; kb += 64) {
+    const int k = kb + lane;
+    int i = 0; bool pass = false;
+    if (k < nwc) { i = d_rect_col(q, k); pass = d_rect_col_pass(R, i, lon_in_min, lon_in_max, lon_in_avg); }
+    const unsigned long long m = __ballot(pass);
+    const int at = cbase + __popcll(m & ((1ull << lane) - 1ull));
+    if (pass)
+      for (int jr = 0; jr < nr; jr++) {
+        const long kk = (long)jr * nc + at;
+        if (kk < n_ok) { ps.src[wbase + kk] = s; ps.dst[wbase + kk] = (q.j0 + jr) * R.nx + i; }
+      }
+    cbase += __popcll(m);
+  }
+  if (lane == 0) { pair_beg[s] = wbase; pair_cnt[s] = n_ok; if (n_ok > CP_SMALL) big_list[atomicAdd(big_cnt, 1)] = s; }
+}
+
 // Candidates on a rectilinear destination grid.  Blocks [0, H): a wave per listed source cell (pole caps: every column);
 // blocks [H, ...): one lane per source cell (d_rect_wave_candidates) -- none when the record kernel has made those candidates
 // itself (k_cell_struct2r), all of them for a polygon-list source.  Pairs of a cell are contiguous and in ascending destination index.
+// FINISH (behind k_cell_struct2r only, which launches no lane-per-cell blocks): the waves also take the cells that kernel
+// listed in rare_list, those that need the general fix_lon: a wave finishes the cell's record (d_finish_rare_cell; this needs
+// the sine table) and then makes its candidates, as a heavy cell's where d_rect_heavy says so (a pole cell over a fine target)
+// and by the lane form with one live lane otherwise (the same cell over a 10-degree target).  A polygon-list plan keeps the
+// small kernel without that code.
+#define RARE_BLOCKS 64       // one-wave blocks for the cells of rare_list, in front of the H blocks of the heavy list
+template <bool FINISH>
 __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells S, const double *mask, FgRect R, FgPairSpace ps,
                                                          int *pair_beg, int *pair_cnt, const int *heavy_list, const int *heavy_cnt,
-                                                         int *big_list, int *big_cnt)
+                                                         int *big_list, int *big_cnt, const int *rare_list, const int *rare_cnt, unsigned *err)
 {
-  if (*R.bad) return;
   const int lane = threadIdx.x;
-  if ((int)blockIdx.x < H) {
+  __shared__ unsigned wl[64 * RECT_WL_WORDS];
+  if (FINISH && (int)blockIdx.x < RARE_BLOCKS) d_load_trig_table();   // (barrier inside; ahead of everything the wave waits for)
+  const unsigned bad = *R.bad;
+  const int nrare = FINISH ? *rare_cnt : 0;
+  if (bad) return;
+  // FINISH: blocks [0, RARE_BLOCKS) come first and take the cells of rare_list, waves of their own, so that a listed cell -- a
+  // chain of dependent loads, the general routine, then as a rule a pole cap's candidates -- does not wait behind the two or
+  // three heavy cells of a wave of the other role (it did at first: the launch took 35 us instead of 15 at C384 -> 0.25 deg)
+  const int hb = FINISH ? (int)blockIdx.x - RARE_BLOCKS : (int)blockIdx.x;
+  if (hb >= 0 && hb < H) {
     const int nheavy = *heavy_cnt;
-    for (int h = blockIdx.x; h < nheavy; h += H) {
+    for (int h = hb; h < nheavy; h += H) {
       const int s = heavy_list[h];
-      const double lon_in_min = S.lon_min[s], lon_in_max = S.lon_max[s], lon_in_avg = S.lon_avg[s];
-      const RectQuery q = d_rect_query(R, S.lat_min[s], S.lat_max[s], lon_in_min, lon_in_max);
-      const int nwc = d_rect_ncols(q), nr = q.j1 - q.j0 + 1;
-      // pass 1: the columns that pass (the same set for every row of the query); pass 2 writes row after row -- the flags are
-      // recomputed per 64-column chunk instead of listed (a list in LDS would cost every block of the launch its occupancy)
-      int nc = 0;
-      for (int kb = 0; kb < nwc; kb += 64) {
-        const int k = kb + lane;
-        const bool pass = k < nwc && d_rect_col_pass(R, d_rect_col(q, k), lon_in_min, lon_in_max, lon_in_avg);
-        nc += __popcll(__ballot(pass));
-      }
-      const long cnt_l = (long)nr * nc;
-      const int cnt = (int)min(cnt_l, 0x7fffffffL);
-      const int r = (int)(((unsigned)s * 2654435761u >> 12) % (unsigned)ps.nreg);
-      unsigned base = 0;
-      if (lane == 0 && cnt) base = atomicAdd(&ps.fill[r * FG_FILL_STRIDE], (unsigned)cnt);
-      base = __shfl(base, 0);
-      const int loc0 = (int)min(base, (unsigned)ps.regcap), n_ok = min(cnt, ps.regcap - loc0);
-      const int wbase = r * ps.regcap + loc0;
-      int cbase = 0;
-      for (int kb = 0; kb < nwc && n_ok > 0; kb += 64) {
-        const int k = kb + lane;
-        int i = 0; bool pass = false;
-        if (k < nwc) { i = d_rect_col(q, k); pass = d_rect_col_pass(R, i, lon_in_min, lon_in_max, lon_in_avg); }
-        const unsigned long long m = __ballot(pass);
-        const int at = cbase + __popcll(m & ((1ull << lane) - 1ull));
-        if (pass)
-          for (int jr = 0; jr < nr; jr++) {
-            const long kk = (long)jr * nc + at;
-            if (kk < n_ok) { ps.src[wbase + kk] = s; ps.dst[wbase + kk] = (q.j0 + jr) * R.nx + i; }
-          }
-        cbase += __popcll(m);
-      }
-      if (lane == 0) { pair_beg[s] = wbase; pair_cnt[s] = n_ok; if (n_ok > CP_SMALL) big_list[atomicAdd(big_cnt, 1)] = s; }
+      d_rect_cell_candidates(R, ps, s, lane, S.lat_min[s], S.lat_max[s], S.lon_min[s], S.lon_max[s], S.lon_avg[s], pair_beg, pair_cnt, big_list, big_cnt);
     }
     return;
   }
-  __shared__ unsigned wl[64 * RECT_WL_WORDS];
-  const int bR = (int)blockIdx.x - H;
-  const int s = bR * 64 + lane;
-  const bool active = s < nsrc && d_src_active(S, mask, s);
-  double b[5] = {0, 0, 0, 0, 0};
-  if (active) { b[0] = S.lat_min[s]; b[1] = S.lat_max[s]; b[2] = S.lon_min[s]; b[3] = S.lon_max[s]; b[4] = S.lon_avg[s]; }
-  (void)d_rect_wave_candidates(R, ps, active, s, nsrc, (unsigned)bR, b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt, wl);
+  if constexpr (FINISH) {
+    for (int h = blockIdx.x; h < nrare; h += RARE_BLOCKS) {
+      const int s = rare_list[h];
+      const double mk = mask ? mask[s] : 1.0;              // (with the corners, not behind the record)
+      double b[5] = {0, 0, 0, 0, 0};
+      const int nv = d_finish_rare_cell(S, err, s, lane, b);
+      if (!(nv > 0 && mk > 0.5)) continue;                 // (d_src_active; pair_cnt[s] = 0 from the record kernel)
+      if (d_rect_heavy(R, b[0], b[1], b[2], b[3])) d_rect_cell_candidates(R, ps, s, lane, b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt);
+      else (void)d_rect_wave_candidates<true>(R, ps, lane == 0, s, nsrc, (unsigned)(s >> 6), b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt, wl);
+    }
+  } else {
+    const int bR = (int)blockIdx.x - H;
+    const int s = bR * 64 + lane;
+    const bool active = s < nsrc && d_src_active(S, mask, s);
+    double b[5] = {0, 0, 0, 0, 0};
+    if (active) { b[0] = S.lat_min[s]; b[1] = S.lat_max[s]; b[2] = S.lon_min[s]; b[3] = S.lon_max[s]; b[4] = S.lon_avg[s]; }
+    (void)d_rect_wave_candidates(R, ps, active, s, nsrc, (unsigned)bR, b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt, wl);
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1908,9 +2033,21 @@ __device__ __forceinline__ long d_cp_place(const FgCompactIo &io, const CpPair &
 }
 
 #define RANK_WORDS 1024      // 65536 destination indices: 45 rows of a 1440-column grid
-#define BIG_STAGE 512
 #define BIG_BLOCKS 512       // blocks of the big-cell role, in front of the lane-per-pair blocks
-#define CP_LDS_DOUBLES (RANK_WORDS + RANK_WORDS / 2 + 3 * BIG_STAGE)   // the larger of the two roles' LDS needs (24 KB)
+// The block's LDS: just under 20 KB, so that eight blocks share a CU (8 waves per SIMD, what the launch bound holds the
+// registers to).  The lane-per-pair role, which does nearly all the work of similar grids, uses 10.6 KB of it.  The big-cell
+// role divides it per cell: the bitmap over the cell's span of destination indices (at most RANK_WORDS words), half as much
+// for the prefix, and what is left in three equal parts for the staged values (d_big_stage): 336 ranks per stage under a
+// bitmap of full size, 512 for a cell of C24 over a 0.25-degree grid (30 rows: 675 words), 848 without a bitmap.  (Fixed
+// sizes -- 1024 words and 3 x 512 values, 24 KB -- held the launch at six blocks per CU; 3 x 256 values made eight fit and
+// cost the coarse -> fine plans, whose cells then took two stages and lost the loads issued ahead of the rank: compaction of
+// C24 -> 0.25 deg 0.30 -> 0.44 ms, C48 0.154 -> 0.189 ms.)
+#define CP_LDS_DOUBLES 2552
+static_assert(CP_LDS_DOUBLES >= CP_SPAN / 2 + 8 + 3 * CP_SPAN, "the lane-per-pair role's sh_d and sh_v fit the block's LDS");
+static_assert(CP_LDS_DOUBLES >= RANK_WORDS + RANK_WORDS / 2 + 3 * 8, "a bitmap of full size leaves room for a stage");
+static_assert(8 * (CP_LDS_DOUBLES * 8 + 64) <= 160 * 1024, "eight blocks of k_compact per CU");
+// ranks per stage of the big-cell role's ordered sums, for a cell whose bitmap has nw words (0: ranked by comparison)
+__device__ __forceinline__ int d_big_stage(int nw) { const int w8 = (nw + 7) & ~7; return ((CP_LDS_DOUBLES - w8 - w8 / 2) / 3) & ~7; }
 
 // The big cells: a block per cell.  Ranking a pair by comparing it with all the others of its cell is quadratic (great-circle
 // search: ~3000 pairs in each of ~600 cells); here the block marks the cell's destination indices in an LDS bitmap over their
@@ -1918,9 +2055,7 @@ __device__ __forceinline__ long d_cp_place(const FgCompactIo &io, const CpPair &
 template <int ORDER>
 __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, const FgCompactIo &io, double *lds)
 {
-  unsigned long long *bits = (unsigned long long *)lds;              // [RANK_WORDS]
-  int *pref = (int *)(lds + RANK_WORDS);                             // [RANK_WORDS]
-  double (*sval)[BIG_STAGE] = (double (*)[BIG_STAGE])(lds + RANK_WORDS + RANK_WORDS / 2);   // [3][BIG_STAGE]
+  unsigned long long *bits = (unsigned long long *)lds;              // [nw], nw <= RANK_WORDS: the cell's bitmap
   __shared__ int smin, smax;
   if (blockIdx.x == 0 && threadIdx.x < 64) {                  // candidate totals for the host's capacity checks
     unsigned long long f = 0; unsigned mx = 0;
@@ -1944,8 +2079,11 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
     const int dmin = smin, dmax = smax;
     const long span = (long)dmax - dmin + 1;
     const bool bitmap = dmax >= 0 && span <= (long)RANK_WORDS * 64;
+    const int nw = bitmap ? (int)((span + 63) >> 6) : 0, w8 = (nw + 7) & ~7;
+    int *pref = (int *)(lds + w8);                           // [nw]
+    const int stage = d_big_stage(nw);                       // ranks per stage: what the bitmap and the prefix leave, in three parts
+    double *sval = lds + w8 + w8 / 2;                        // [3][stage]
     if (bitmap) {
-      const int nw = (int)((span + 63) >> 6);
       for (int w = threadIdx.x; w < nw; w += 256) bits[w] = 0ull;
       __syncthreads();
       for (int k = threadIdx.x; k < c; k += 256) {
@@ -1963,17 +2101,17 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
       for (int w = w0; w < w1; w++) { pref[w] = run; run += __popcll(bits[w]); }
       __syncthreads();
     }
-    // exchange cells to their places; order 2: the values also go to LDS in rank order, BIG_STAGE ranks at a time, where three
+    // exchange cells to their places; order 2: the values also go to LDS in rank order, `stage` ranks at a time, where three
     // lanes (one array each) add them up in exchange-cell order -- hundreds to thousands of ordered additions per cell, which
     // from global memory (even with the loads 16 ahead) set the duration of the whole compaction
     // A cell that fits one stage (every cell of a coarse -> fine remap) takes a pair's values and row slot along with its
     // destination index, and row_ptr as soon as that is back, ahead of the rank: two rounds of loads per pair instead of
     // four.  A cell of several stages (great-circle search) passes over its pairs once per stage and loads only what the
     // stage stores.
-    const bool ahead = na <= BIG_STAGE;                    // (block-uniform)
+    const bool ahead = na <= stage;                        // (block-uniform)
     const int *const rowpos = io.tmp_rowpos ? io.tmp_rowpos : ps.dst;
     double acc = 0;
-    for (int c0 = 0; c0 < max(na, 1); c0 += BIG_STAGE) {
+    for (int c0 = 0; c0 < max(na, 1); c0 += stage) {
       for (int k = threadIdx.x; k < c; k += 256) {
         const int p = o + k;
         const int d = ps.dst[p];
@@ -1987,7 +2125,7 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
         int rank;
         if (bitmap) { const int w = (d - dmin) >> 6, b = (d - dmin) & 63; rank = pref[w] + __popcll(bits[w] & ((1ull << b) - 1ull)); }
         else { rank = 0; for (int j = 0; j < c; j++) rank += ((unsigned)ps.dst[o + j] < (unsigned)d) ? 1 : 0; }
-        if (rank < c0 || rank >= c0 + BIG_STAGE) continue;
+        if (rank < c0 || rank >= c0 + stage) continue;
         const long pos = x0 + rank;
         if (pos >= io.xcap) continue;
         if (!ahead) {
@@ -1997,15 +2135,15 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
         io.x_src[pos] = s; io.x_dst[pos] = d; io.x_area[pos] = a;
         if (ORDER == 2) {
           io.x_c1[pos] = l; io.x_c2[pos] = t;
-          sval[0][rank - c0] = a; sval[1][rank - c0] = l; sval[2][rank - c0] = t;
+          sval[rank - c0] = a; sval[stage + rank - c0] = l; sval[2 * stage + rank - c0] = t;
         }
         if (io.tmp_rowpos) io.perm[row] = FgRowEnt{(int)pos, s};
         else io.x_rowpos[pos] = atomicAdd(&io.row_cnt[d], 1);
       }
       __syncthreads();
       if (ORDER == 2 && threadIdx.x < 3 && x0 + na <= io.xcap) {
-        const double *v = sval[threadIdx.x];
-        const int n = min(BIG_STAGE, na - c0);
+        const double *v = sval + threadIdx.x * stage;
+        const int n = min(stage, na - c0);
         int k = 0;
         for (; k + 8 <= n; k += 8) {
           double t[8];
@@ -2025,7 +2163,7 @@ __device__ __forceinline__ void d_compact_big(int nsrc, const FgPairSpace &ps, c
 // Blocks [0, BIG_BLOCKS): the big cells (listed by the candidate kernel); the rest: one lane per pair.  One launch, so that the
 // few long-running big-cell blocks start first and run beside the others instead of after them.
 template <int ORDER>
-__global__ __launch_bounds__(256) void k_compact(int nsrc, FgPairSpace ps, FgCompactIo io)
+__global__ __launch_bounds__(256, 8) void k_compact(int nsrc, FgPairSpace ps, FgCompactIo io)
 {
   __shared__ double lds[CP_LDS_DOUBLES];
   if ((int)blockIdx.x < BIG_BLOCKS) { d_compact_big<ORDER>(nsrc, ps, io, lds); return; }
@@ -2197,13 +2335,13 @@ void fgd_rect_tables(const double *lon, const double *lat, int nx, int ny, doubl
 }
 void fgd_cell_struct2r(const FgTileSet &ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst, FgCells S, double *area_out,
                        FgRect R, const double *mask, int order, int *src_idx_f, double *sums, unsigned *err, hipStream_t st,
-                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt, FgPairSpace ps, int *pair_beg, int *pair_cnt,
-                       int *big_list, int *big_cnt)
+                       unsigned long long *band_keys, int cull, int *heavy_list, int *heavy_cnt, int *rare_list, int *rare_cnt, FgPairSpace ps,
+                       int *pair_beg, int *pair_cnt, int *big_list, int *big_cnt)
 {
   const int nbS = nblk(nsrc, 256), nbD = nblk(ndst, 256);
   if (nbS + nbD > 0)
     k_cell_struct2r<<<nbS + nbD, 256, 0, st>>>(ts, tiles_in, tiles_out, ntiles, nsrc, ndst, nbS, S, area_out, R, mask, order, src_idx_f, sums, err,
-                                               band_keys, cull, heavy_list, heavy_cnt, ps, pair_beg, pair_cnt, big_list, big_cnt);
+                                               band_keys, cull, heavy_list, heavy_cnt, rare_list, rare_cnt, ps, pair_beg, pair_cnt, big_list, big_cnt);
 }
 void fgd_polylist_records(FgPolyList P, FgCells S, int *src_idx_f, double *sums, const FgRect *rect, int *heavy_list, int *heavy_cnt,
                           unsigned *err, hipStream_t st)
@@ -2216,7 +2354,8 @@ void fgd_rect_materialize(int ndst, FgRect R, FgCells D, hipStream_t st)
   if (ndst > 0) k_rect_materialize<<<nblk(ndst, 256), 256, 0, st>>>(ndst, R, D);
 }
 void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPairSpace ps, int *pair_beg, int *pair_cnt,
-                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only)
+                         const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only,
+                         const int *rare_list, const int *rare_cnt, unsigned *err)
 {
   if (nsrc <= 0) return;
   const int nbR = listed_only ? 0 : nblk(nsrc, 64);       // listed_only: the record kernel made the candidates of the other cells
@@ -2224,7 +2363,13 @@ void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPa
   // nsrc / 64 = 216 waves the candidates took 0.24 ms, with nsrc / 8 0.064 -- dealing a cell's (row, column) pairs to all 64 lanes
   // through LDS instead of a lane per column made no difference on top of that)
   const int H = min(HEAVY_BLOCKS, max(64, nblk(nsrc, 8)));
-  k_candidates_rect<<<nbR + H, 64, 0, st>>>(nsrc, H, S, mask, R, ps, pair_beg, pair_cnt, heavy_list, heavy_cnt, big_list, big_cnt);
+  // listed_only = behind k_cell_struct2r: the instantiation that also finishes the cells of rare_list
+  // (its 174 VGPRs let two waves share a SIMD, 2048 on the chip: the rare-cell blocks come out of H, not on top of it)
+  const int Hf = max(H - RARE_BLOCKS, RARE_BLOCKS);
+  if (listed_only) k_candidates_rect<true><<<Hf + RARE_BLOCKS, 64, 0, st>>>(nsrc, Hf, S, mask, R, ps, pair_beg, pair_cnt, heavy_list, heavy_cnt, big_list, big_cnt,
+                                                          rare_list, rare_cnt, err);
+  else k_candidates_rect<false><<<nbR + H, 64, 0, st>>>(nsrc, H, S, mask, R, ps, pair_beg, pair_cnt, heavy_list, heavy_cnt, big_list, big_cnt,
+                                                       nullptr, nullptr, nullptr);
 }
 
 void fgd_compact(int order, int nsrc, FgPairSpace ps, const FgCompactIo &io, hipStream_t st)
