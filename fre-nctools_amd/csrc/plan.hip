@@ -440,14 +440,27 @@ struct fg_plan {
   }
 };
 
-static bool alloc_cells(fg_plan *pl, FgCells *c, size_t n)
+// Slots of the side table of compact source cells (FgCells, xgrid_device.h): cells that fix_lon leaves with more than four
+// vertices.  A cubed sphere has eight, a lat-lon grid none; a search that meets more than the table holds is repeated on the
+// generic path.  fg_set_search_wide_cap(n >= 0) lowers the capacity to n (tests of that route), n < 0 = the default.
+static int g_wide_cap = -1;
+extern "C" void fg_set_search_wide_cap(int n) { g_wide_cap = n < 0 ? -1 : n; }
+static bool alloc_cells(fg_plan *pl, FgCells *c, size_t n, bool compact = false)
 {
+  *c = FgCells{};
   c->lat_min = pl->alloc<double>(n); c->lat_max = pl->alloc<double>(n);
-  c->lon_min = pl->alloc<double>(n); c->lon_max = pl->alloc<double>(n);
+  if (!compact) { c->lon_min = pl->alloc<double>(n); c->lon_max = pl->alloc<double>(n); }
   c->lon_avg = pl->alloc<double>(n); c->area = pl->alloc<double>(n);
   c->nv = pl->alloc<int>(n);
-  c->verts = pl->alloc<double>(n * 16);
-  return c->lat_min && c->lat_max && c->lon_min && c->lon_max && c->lon_avg && c->area && c->nv && c->verts;
+  c->verts = pl->alloc<double>(n * (compact ? FG_VSTRIDE_QUAD : 16));
+  if (compact) {
+    const size_t cap = n / 16 + 64;
+    c->vstride = FG_VSTRIDE_QUAD;
+    c->wide_cap = (int)(g_wide_cap >= 0 ? std::min<size_t>((size_t)g_wide_cap, cap) : cap);
+    c->wide = pl->alloc<double>(16 * (size_t)std::max(c->wide_cap, 1));
+    if (!c->wide) return false;
+  }
+  return c->lat_min && c->lat_max && (compact || (c->lon_min && c->lon_max)) && c->lon_avg && c->area && c->nv && c->verts;
 }
 
 static int plan_base(int order, int ntiles_in, const int *nx_in, const int *ny_in, int nx_out, int ny_out,
@@ -670,7 +683,8 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   const long npairs = fgd_pairs_total(ps);            // capacity of the pair list
   const long nx_alloc = npairs;                       // nxgrid <= candidate pairs <= capacity
 
-  if (!alloc_cells(pl, &pl->S, nsrc)) return fg_fail(FG_ERR_HIP, "out of device memory");
+  // (a grid on the rectilinear path: compact source cells, written by k_cell_struct2r and k_candidates_rect<true>)
+  if (!alloc_cells(pl, &pl->S, nsrc, rect && !pl->polys.npoly)) return fg_fail(FG_ERR_HIP, "out of device memory");
   SearchBlocks blk{pl};
   struct { double *hdr, *lat_ax, *lon_ax, *col, *row, *col_min, *col_max, *col_avg; } rt{};   // the rectilinear tables, one block (FgRect, xgrid_device.h)
   if (rect) {
@@ -792,7 +806,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   if (rect)
     fgd_candidates_rect(nsrc, pl->S, pl->mask_dev, pl->rect_tab, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list, &dc->big_cnt, st,
                         pl->polys.npoly ? 0 : 1,          // (the record kernel made the candidates of every cell that is not listed)
-                        rare_list, &dc->rare_cnt, dc->err);
+                        rare_list, &dc->rare_cnt, dc->err, pl->polys.npoly ? nullptr : pl->sums);
   else
     fgd_candidates1(nsrc, pl->S, pl->mask_dev, bins, bin_start, bin_entries, ecap, ps, pair_beg, pair_cnt, heavy_list, &dc->heavy_cnt, big_list,
                     &dc->big_cnt, st);
@@ -878,6 +892,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   pt.collect(pl->phase_ms); ptot.collect(pl->phase_ms);          // (also hands the timing events back on every exit below)
   FGCHK(hipGetLastError());
   if (rect && hc->rect_bad) { caps->rect = false; return FG_RETRY; }   // not a rectilinear grid after all: every kernel of this attempt left at once
+  if (rect && (hc->err[0] & G_ERRBIT_WIDECAP)) { caps->rect = false; return FG_RETRY; }   // the side table of the compact source cells is full
   if (hc->total[0] > nentries) { caps->entries = hc->total[0]; return FG_RETRY; }
   if (hc->total[0] > 2000000000ull) return fg_fail(FG_ERR_ARG, "bin table too large");
   if (hc->total[3] > (unsigned long long)ps.regcap) {
@@ -1718,7 +1733,17 @@ extern "C" int fg_plan_get_cell_struct(const fg_plan *pl, int which, double *lat
     fgd_rect_materialize(pl->ndst, R, tmp, pl->stream);
     FGCHK(hipStreamSynchronize(pl->stream));
   }
-  const FgCells &c = which ? (pl->rect ? tmp : pl->D) : pl->S;
+  if (!which && pl->S.vstride == FG_VSTRIDE_QUAD) {   // compact source cells: the boxes' longitudes and the 128-byte records likewise
+    const size_t ns = (size_t)pl->nsrc;
+    auto get = [&](size_t bytes) { void *p = g_pool.get(pl->device, bytes); if (p) tmp_blocks.push_back(p); return p; };
+    tmp = pl->S;
+    tmp.lon_min = (double *)get(ns * 8); tmp.lon_max = (double *)get(ns * 8); tmp.verts = (double *)get(ns * 128);
+    tmp.vstride = 16; tmp.wide = nullptr; tmp.wide_cap = 0;
+    if (tmp_blocks.size() != 3) return fg_fail(FG_ERR_HIP, "out of device memory");
+    fgd_quad_materialize(pl->nsrc, pl->S, tmp.lon_min, tmp.lon_max, tmp.verts, pl->stream);
+    FGCHK(hipStreamSynchronize(pl->stream));
+  }
+  const FgCells &c = which ? (pl->rect ? tmp : pl->D) : (pl->S.vstride == FG_VSTRIDE_QUAD ? tmp : pl->S);
   size_t n = which ? pl->ndst : pl->nsrc;
   if (lat_min) FGCHK(hipMemcpy(lat_min, c.lat_min, n * sizeof(double), hipMemcpyDeviceToHost));
   if (lat_max) FGCHK(hipMemcpy(lat_max, c.lat_max, n * sizeof(double), hipMemcpyDeviceToHost));

@@ -145,8 +145,8 @@ __global__ __launch_bounds__(64) void k_xgrid_polygons(long n, const int *x_src,
   double a[PB_IN], b[PB_IN], c[PB_IN], e[PB_IN], xo[PB_CAP], yo[PB_CAP];
   const int n1 = S.nv[s];
   int n2;
-  const double *sv = S.verts + (size_t)s * 16;
-  for (int q = 0; q < 8; q++) { a[q] = sv[q]; b[q] = sv[8 + q]; }
+  const FgVerts sv = d_cell_verts(S, s, n1);
+  for (int q = 0; q < 8; q++) { a[q] = q < n1 ? sv.x[q] : 0.0; b[q] = q < n1 ? sv.y[q] : 0.0; }   // (zeros beyond n1, as a 128-byte record has them)
   double lon_out_avg;
   if (rect) {
     const int j = d / R.nx, i = d - j * R.nx;
@@ -156,8 +156,8 @@ __global__ __launch_bounds__(64) void k_xgrid_polygons(long n, const int *x_src,
     e[0] = ya; e[1] = ya; e[2] = yb; e[3] = yb;
     n2 = 4;
   } else {
-    const double *dv = D.verts + (size_t)d * 16;
-    for (int q = 0; q < 8; q++) { c[q] = dv[q]; e[q] = dv[8 + q]; }
+    const FgVerts dv = d_cell_verts(D, d, 0);            // (destination cells have 128-byte records)
+    for (int q = 0; q < 8; q++) { c[q] = dv.x[q]; e[q] = dv.y[q]; }
     lon_out_avg = D.lon_avg[d];
     n2 = D.nv[d];
   }

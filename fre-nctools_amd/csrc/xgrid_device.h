@@ -22,11 +22,42 @@ struct FgTileXyz {
 
 // per-cell records, SoA scalars + one 128-byte vertex record per cell
 // (the quantities of create_xgrid.c:991-1016 plus the cell area of :66-88)
+// The source cells of a GRID on the rectilinear path are compact (vstride = FG_VSTRIDE_QUAD): verts is [ncells][8], lon[4] then
+// lat[4] -- all but a handful of a grid's cells are quadrilaterals, and a 128-byte record of which half is zeros was a quarter of
+// what the record kernel wrote and half of what the clip loaded.  A cell that fix_lon leaves with MORE than four vertices (a lone
+// pole vertex, a half-turn edge: eight cells of C384) has its sixteen doubles in slot k of `wide`, k in the first word of its own
+// record; lon_min / lon_max are not kept then (null): they are the min / max of the record's longitudes.  Everything else --
+// destination cells, polygon lists, the generic, great-circle and box paths -- has the 128-byte record (vstride 16, 0 in an
+// empty struct).  Kernels find a cell's vertices through d_cell_verts / d_cell_quad below, never by their own arithmetic.
+#define FG_VSTRIDE_QUAD 8
 struct FgCells {
   double *lat_min, *lat_max, *lon_min, *lon_max, *lon_avg, *area;
   int *nv;
-  double *verts;       // [ncells][16]: lon[8] then lat[8], after fix_lon
+  double *verts;       // [ncells][16]: lon[8] then lat[8], after fix_lon; compact: [ncells][8], lon[4] then lat[4]
+  int vstride;         // FG_VSTRIDE_QUAD = compact, anything else = 16 doubles per cell
+  int wide_cap;        // compact: slots of `wide`
+  double *wide;        // compact: [wide_cap][16], lon[8] then lat[8], of the cells with nv > 4
 };
+#ifdef __HIPCC__
+struct FgVerts { const double *x, *y; };             // x[k], y[k]: vertex k < nv
+// the vertices of cell s, which has n = nv[s] of them
+__device__ __forceinline__ FgVerts d_cell_verts(const FgCells &c, int s, int n)
+{
+  if (c.vstride == FG_VSTRIDE_QUAD) {
+    const double *v = c.verts + (size_t)s * FG_VSTRIDE_QUAD;
+    if (n > 4) {
+      const int k = *(const int *)v;                     // (k < wide_cap by construction; `wide` has a slot 0 whatever its capacity)
+      const double *w = c.wide + (size_t)((unsigned)k < (unsigned)c.wide_cap ? k : 0) * 16;
+      return FgVerts{w, w + 8};
+    }
+    return FgVerts{v, v + 4};
+  }
+  const double *v = c.verts + (size_t)s * 16;
+  return FgVerts{v, v + 8};
+}
+// compact cells only: the cell's own record -- lon[4] then lat[4] when nv <= 4 -- for a load that does not wait for nv
+__device__ __forceinline__ double *d_cell_quad(const FgCells &c, int s) { return c.verts + (size_t)s * FG_VSTRIDE_QUAD; }
+#endif
 
 // uniform bins over latitude x (longitude mod 2pi)
 struct FgBins {
@@ -104,6 +135,7 @@ struct FgTileSet { FgTile t[FG_TILESET_MAX]; int n; };
 struct FgLl2xGrid { const double *lon, *lat; double *x, *y, *z; long n; };
 struct FgLl2xSet { FgLl2xGrid g[FG_TILESET_MAX]; int n; };
 #define G_ERRBIT_LL2X 256u
+#define G_ERRBIT_WIDECAP 512u   // rectilinear path: more source cells with over four vertices than the side table holds (FgCells)
 void fgd_latlon2xyz(const FgLl2xGrid *grids, int ngrids, unsigned *err, hipStream_t st);
 
 // device-side counters of one search (plan.hip reads them back once)
@@ -134,6 +166,7 @@ void fgd_exclusive_scan2(const int *in_a, long n_a, int *out_a, unsigned long lo
 
 // per-cell records of the source tiles and of the destination tile in ONE launch; also counts the destination cells into
 // their bins (slot_cnt), fills src_idx_f, zeroes sums[3][nsrc] (may be null) and stores the tile descriptors at tiles_out
+// (fgd_cell_struct2r: only the sums of the cells that end without a pair -- k_compact stores every other cell's)
 void fgd_cell_struct2(const FgTileSet &ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst, FgCells S, FgCells D,
                       FgBins b, int *slot_cnt, int order, int *src_idx_f, double *sums, unsigned *err, hipStream_t st,
                       unsigned long long *band_keys = nullptr, int cull = 0, double dst_tlon = 3.14159265358979323846);
@@ -171,6 +204,8 @@ void fgd_cell_struct2r(const FgTileSet &ts, const FgTile *tiles_in, FgTile *tile
                        int *pair_beg, int *pair_cnt, int *big_list, int *big_cnt);   // source blocks also make the candidates of their cells (all but
                                                                                      // the listed ones); rare_list: cells whose records are still to finish
 void fgd_rect_materialize(int ndst, FgRect R, FgCells D, hipStream_t st);
+// compact source cells (FgCells): lon_min, lon_max [nsrc] and the 128-byte records [nsrc][16], for fg_plan_get_cell_struct
+void fgd_quad_materialize(int nsrc, FgCells S, double *lon_min, double *lon_max, double *verts, hipStream_t st);
 // Source "cells" given as a list of polygons (<= 8 vertices each, already in the longitude frame they are to be clipped in):
 // fills the source records a search needs (box, vertices, the caller's lon_avg and reference area), the field index, zeroes the
 // sums, and -- rect != null -- lists the heavy ones.  make_coupler_mosaic's atmosphere x land cells against the ocean grid.
@@ -179,7 +214,8 @@ void fgd_polylist_records(FgPolyList P, FgCells S, int *src_idx_f, double *sums,
                           unsigned *err, hipStream_t st);
 void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPairSpace ps, int *pair_beg, int *pair_cnt,
                          const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only,
-                         const int *rare_list = nullptr, const int *rare_cnt = nullptr, unsigned *err = nullptr);     // listed_only (behind fgd_cell_struct2r): also finishes the cells of rare_list
+                         const int *rare_list = nullptr, const int *rare_cnt = nullptr, unsigned *err = nullptr,      // listed_only (behind fgd_cell_struct2r): also finishes the cells of rare_list
+                         double *sums = nullptr);   // ... and zeroes the sums ([3][nsrc]) of its cells that end without a pair (that launch left them alone)
 // rect != null: the destination cells come from the rectilinear tables (D holds areas only)
 void fgd_clip_general(int order, FgPairSpace ps, FgCells S, const double *mask, FgCells D,
               double *tmp_area, double *tmp_clon, double *tmp_clat, int *nacc, int *defer_list, int *defer_cnt,

@@ -252,7 +252,8 @@ void fgd_exclusive_scan1(const int *in, long n, int *out, unsigned long long *st
 // 884 736 cells of C384 -- gets its latitude box, its corners as read (in its vertex record) and *rare = true; the caller lists it and a wave of k_candidates_rect
 // finishes its record (d_finish_rare_cell).  Everything else is then a quadrilateral: four vertices in registers instead of
 // the general routine's two 12-element arrays (32 VGPRs of every wave), a four-edge area, and a staging tile of the eight live
-// coordinates per cell (vtile is [256 * 9] then, [256 * 17] otherwise); the other eight doubles of a record are stored as zeros.
+// coordinates per cell (vtile is [256 * 9] then, [256 * 17] otherwise), which ARE the cell's record: c is compact (FgCells,
+// xgrid_device.h) -- 64 bytes per cell, no lon_min / lon_max.
 template <bool QUADS_ONLY = false>
 __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, int ncells, const FgCells &c, unsigned *err, int s0,
                                              double *vtile, double *box /* lat_min, lat_max, lon_min, lon_max */, int *tile_of,
@@ -302,7 +303,8 @@ __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, in
     }
     else if (n < 0 || n > G_MAXV) {
       atomicOr(err, G_ERRBIT_MAXV);
-      c.nv[s] = 0; c.lon_min[s] = 0; c.lon_max[s] = 0; c.lon_avg[s] = 0; c.area[s] = 0;
+      c.nv[s] = 0; c.lon_avg[s] = 0; c.area[s] = 0;
+      if constexpr (!QUADS_ONLY) { c.lon_min[s] = 0; c.lon_max[s] = 0; }
     } else if constexpr (QUADS_ONLY) {                   // n = 4: the same operations in the same order as below
       double xmin = x[0], xmax = x[0], xs = 0;
 #pragma unroll
@@ -310,7 +312,7 @@ __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, in
 #pragma unroll
       for (int k = 0; k < 4; k++) xs += x[k];
       xs /= 4;
-      c.lon_min[s] = xmin; c.lon_max[s] = xmax; c.lon_avg[s] = xs;
+      c.lon_avg[s] = xs;                                 // (lon_min / lon_max: not kept for compact cells)
       box[2] = xmin; box[3] = xmax; box[4] = xs;
       c.nv[s] = 4;
       nvert = 4;
@@ -336,38 +338,39 @@ __device__ __forceinline__ int d_cell_record(const FgTile *tiles, int ntiles, in
   if (QUADS_ONLY) *rare = listed;
   // no live cell in this block: no vertex records to store (a listed cell is live: its block stores, as it did before)
   if (!__syncthreads_or(nvert != 0 || listed) && cull) return 0;
-  const long cnt = (long)min(256, ncells - s0) * 16;
-  double *out = c.verts + (size_t)s0 * 16;
+  const long cnt = (long)min(256, ncells - s0) * NLIVE;
+  double *out = QUADS_ONLY ? d_cell_quad(c, s0) : c.verts + (size_t)s0 * 16;
 #pragma unroll
-  for (int q = 0; q < 16; q++) {
+  for (int q = 0; q < NLIVE; q++) {
     const long e = (long)q * 256 + threadIdx.x;
-    if constexpr (QUADS_ONLY) {                          // vertex k of the record at 0..3 (lon) and 8..11 (lat); 4..7 and 12..15 are zeros
-      const int k = (int)e & 15;
-      if (e < cnt) out[e] = (k & 4) ? 0.0 : vtile[(e >> 4) * VS + ((k >> 3) << 2) + (k & 3)];
-    } else if (e < cnt) out[e] = vtile[(e >> 4) * VS + (e & 15)];
+    if (e < cnt) out[e] = vtile[(e / NLIVE) * VS + (e % NLIVE)];
   }
   return nvert;
 }
 
 // The rest of the record of a cell k_cell_struct2r listed (d_cell_record<true>): the general fix_lon and, from its vertices, what
 // d_cell_record stores -- the same routines on the same inputs.  Every lane of the wave computes the same values, lane 0 stores.
+// c is compact: a cell that ends with at most four vertices keeps its own 64-byte record (zeros beyond the last vertex); one with
+// more gets slot h of c.wide -- h = its place in rare_list -- and h in the first word of its record.  No slot left (more such
+// cells than c.wide_cap: no grid has them): the cell gets no record (nv = 0, so no pairs: the attempt runs to its end like any
+// other, every kernel on what its predecessors wrote) and G_ERRBIT_WIDECAP, at which the host repeats the search on the generic path.
 // Returns the vertex count (0: no record) and the box.
-__device__ __forceinline__ int d_finish_rare_cell(const FgCells &c, unsigned *err, int s, int lane, double *box)
+__device__ __forceinline__ int d_finish_rare_cell(const FgCells &c, unsigned *err, int s, int h, int lane, double *box)
 {
-  double *v = c.verts + (size_t)s * 16;
+  double *v = d_cell_quad(c, s);
   double x[G_FIXCAP], y[G_FIXCAP];
 #pragma unroll
-  for (int k = 0; k < 4; k++) { x[k] = v[k]; y[k] = v[8 + k]; }      // the corners as the record kernel read them: one round of loads
+  for (int k = 0; k < 4; k++) { x[k] = v[k]; y[k] = v[4 + k]; }      // the corners as the record kernel read them: one round of loads
   double lmin = y[0], lmax = y[0];
 #pragma unroll
   for (int k = 1; k < 4; k++) { if (y[k] < lmin) lmin = y[k]; if (y[k] > lmax) lmax = y[k]; }
   box[0] = lmin; box[1] = lmax;                          // (stored, and checked for G_ERRBIT_BADLAT, by the record kernel)
   const int n = d_fix_lon(x, y, 4, G_PI);
-  if (n < 0 || n > G_MAXV) {
+  if (n < 0 || n > G_MAXV || (n > 4 && h >= c.wide_cap)) {
     if (lane == 0) {
-      atomicOr(err, G_ERRBIT_MAXV);
-      c.nv[s] = 0; c.lon_min[s] = 0; c.lon_max[s] = 0; c.lon_avg[s] = 0; c.area[s] = 0;
-      for (int k = 0; k < 16; k++) v[k] = 0.0;
+      atomicOr(err, (n < 0 || n > G_MAXV) ? G_ERRBIT_MAXV : G_ERRBIT_WIDECAP);
+      c.nv[s] = 0; c.lon_avg[s] = 0; c.area[s] = 0;
+      for (int k = 0; k < FG_VSTRIDE_QUAD; k++) v[k] = 0.0;
     }
     return 0;
   }
@@ -378,12 +381,20 @@ __device__ __forceinline__ int d_finish_rare_cell(const FgCells &c, unsigned *er
   box[2] = xmin; box[3] = xmax; box[4] = xs;
   const double area = d_poly_area<1>(x, y, n);
   if (lane == 0) {
-    c.lon_min[s] = xmin; c.lon_max[s] = xmax; c.lon_avg[s] = xs;
+    c.lon_avg[s] = xs;
     c.nv[s] = n;
-    for (int k = 0; k < G_MAXV; k++) {
-      v[k] = (k < n) ? x[k] : 0.0;
-      v[8 + k] = (k < n) ? y[k] : 0.0;
-    }
+    if (n > 4) {
+      double *w = c.wide + (size_t)h * 16;
+      for (int k = 0; k < G_MAXV; k++) {
+        w[k] = (k < n) ? x[k] : 0.0;
+        w[8 + k] = (k < n) ? y[k] : 0.0;
+      }
+      *(int *)v = h;                                     // (nothing else reads the record of a cell with nv > 4)
+    } else
+      for (int k = 0; k < 4; k++) {
+        v[k] = (k < n) ? x[k] : 0.0;
+        v[4 + k] = (k < n) ? y[k] : 0.0;
+      }
     c.area[s] = area;
   }
   return n;
@@ -938,21 +949,37 @@ __global__ __launch_bounds__(64) void k_candidates1(int nsrc, int H, FgCells S, 
 // (RECT_COLW = 8 doubles per column record, xgrid_device.h: x'[0..3] after fix_lon (SW, SE, NE, NW), lon_min, lon_max, lon_avg, width)
 #define RECT_HDR 8            // header of the tables: lon[0], nx / (lon[nx] - lon[0]), lat[0], ny / (lat[ny] - lat[0])
 #define RECT_EPS 1.e-9
+#define RECT_VERIFY_BLOCKS 8192   // blocks of k_rect_tables that verify the corners (2M corners in one round of loads)
 #define RECT_HEAVY 48         // rows x window columns above which a source cell's candidates are made by a whole wave
 
 __global__ __launch_bounds__(256) void k_rect_tables(const double *lon, const double *lat, int nx, int ny, double *hdr, double *lat_ax,
                                                       double *lon_ax, double *col, double *col_min, double *col_max, double *col_avg, double *row,
                                                       unsigned *bad, unsigned *err, double dst_tlon)
 {
-  d_load_trig_table();                                   // (barrier inside)
+  // Blocks [0, nbT) make the tables, the others verify the corners: the table lanes' sines and fix_lon run beside the pass over the
+  // two corner arrays instead of behind their share of it, and that pass is one round of loads per lane where 1024 blocks walked
+  // the arrays in four (the launch took 13.8 us for 16.6 MB at 1440 x 720, whatever the table lanes did)
+  const int nbT = (max(nx, ny) + 1 + 255) / 256;
   const long np = (long)(nx + 1) * (ny + 1);
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x, gsz = (long)gridDim.x * 256;
   bool b = false;
-  for (long e = gid; e < np; e += gsz) {
-    const long j = e / (nx + 1); const int i = (int)(e - j * (nx + 1));
-    if (__double_as_longlong(lon[e]) != __double_as_longlong(lon[i]) ||
-        __double_as_longlong(lat[e]) != __double_as_longlong(lat[j * (nx + 1)])) b = true;
+  if ((int)blockIdx.x >= nbT) {
+    // (row, column) of corner e by one 32-bit division per lane, then carried along: a stride of gsz corners is dj rows and di columns
+    const long gid = (long)((int)blockIdx.x - nbT) * 256 + threadIdx.x, gsz = (long)((int)gridDim.x - nbT) * 256;
+    const int nxp = nx + 1;
+    const int dj = (int)(gsz / nxp), di = (int)(gsz - (long)dj * nxp);
+    long j = 0; int i = 0;
+    if (gid < np) { j = (long)((unsigned)gid / (unsigned)nxp); i = (int)(gid - j * nxp); }   // (gid < RECT_VERIFY_BLOCKS * 256)
+    for (long e = gid; e < np; e += gsz) {
+      if (__double_as_longlong(lon[e]) != __double_as_longlong(lon[i]) ||
+          __double_as_longlong(lat[e]) != __double_as_longlong(lat[j * nxp])) b = true;
+      j += dj; i += di;
+      if (i >= nxp) { i -= nxp; j++; }
+    }
+    if (__ballot(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+    return;
   }
+  d_load_trig_table();                                   // (barrier inside)
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   if (gid <= ny) {
     const double y = lat[gid * (nx + 1)];
     lat_ax[gid] = y;
@@ -977,7 +1004,10 @@ __global__ __launch_bounds__(256) void k_rect_tables(const double *lon, const do
     double x[G_FIXCAP], y[G_FIXCAP];
     x[0] = x0; x[1] = x1; x[2] = x1; x[3] = x0;
     y[0] = 0.0; y[1] = 0.0; y[2] = 0.1; y[3] = 0.1;
-    const int n = d_fix_lon(x, y, 4, dst_tlon);
+    // the quadrilateral routine: same operations in the same order; it declines (-1, nothing modified) only for an edge of
+    // |dlon| = pi -- these latitudes are no poles -- and such a column has failed the width check above
+    int n = d_fix_lon_quad_fast(x, y, dst_tlon);
+    if (n < 0) n = d_fix_lon(x, y, 4, dst_tlon);
     double *c = col + (size_t)gid * RECT_COLW;
     if (n != 4) { b = true; for (int k = 0; k < RECT_COLW; k++) c[k] = 0.0; col_min[gid] = 0.0; col_max[gid] = 0.0; col_avg[gid] = 0.0; }
     else {
@@ -1130,7 +1160,8 @@ template <bool ONE = false>
 __device__ __forceinline__ bool d_rect_wave_candidates(const FgRect &R, const FgPairSpace &ps, bool active, int s, int nsrc, unsigned wave_no,
                                                        double lat_in_min, double lat_in_max, double lon_in_min, double lon_in_max,
                                                        double lon_in_avg, int *pair_beg, int *pair_cnt, int *big_list, int *big_cnt,
-                                                       unsigned *wl /* [64 * RECT_WL_WORDS], this wave's; in other use until the first barrier */)
+                                                       unsigned *wl /* [64 * RECT_WL_WORDS], this wave's; in other use until the first barrier */,
+                                                       int *n_pairs = nullptr /* the lane's pair_cnt (0 for a cell that is heavy or not active) */)
 {
   const int lane = threadIdx.x & 63;
   int cnt = 0, nr = 0, nwc = 0, nc = 0;
@@ -1166,6 +1197,7 @@ __device__ __forceinline__ bool d_rect_wave_candidates(const FgRect &R, const Fg
     pair_beg[s] = r * ps.regcap + loc0;
     pair_cnt[s] = n_ok;
   }
+  if (n_pairs) *n_pairs = n_ok;
   {
     const bool bigc = n_ok > CP_SMALL;
     const unsigned long long bm = __ballot(bigc);
@@ -1295,7 +1327,6 @@ __global__ __launch_bounds__(256, RECORD_WAVES) void k_cell_struct2r(FgTileSet t
         if (rare) rare_list[base + __popcll(m & ((1ull << lane) - 1ull))] = s;
       }
     }
-    if (s < nsrc && sums) { sums[s] = 0.0; sums[nsrc + s] = 0.0; sums[2 * (size_t)nsrc + s] = 0.0; }
     if (s < nsrc && src_idx_f) {
       if (order != 2) src_idx_f[s] = s;
       else {
@@ -1310,8 +1341,12 @@ __global__ __launch_bounds__(256, RECORD_WAVES) void k_cell_struct2r(FgTileSet t
     // (lon_avg stays in a register: while the record code held the general routine's arrays it had to come back from the
     //  record this lane had just stored, a dependent round trip, or cost the kernel a block per CU)
     const bool active = s < nsrc && nv > 0 && (!mask || mask[s] > 0.5);
+    int npair = 0;
     const bool heavy = d_rect_wave_candidates(R, ps, active, s, nsrc, (unsigned)(s >> 6), box[0], box[1], box[2], box[3], box[4], pair_beg, pair_cnt,
-                                              big_list, big_cnt, (unsigned *)(vtile + (threadIdx.x >> 6) * (64 * 9)));
+                                              big_list, big_cnt, (unsigned *)(vtile + (threadIdx.x >> 6) * (64 * 9)), &npair);
+    // the sums of a cell that ends here without a pair: every other cell's are stored by k_compact (the lane of its first pair, or
+    // the block of a big cell), those of a heavy or listed cell that ends without one by k_candidates_rect
+    if (s < nsrc && sums && npair == 0 && !heavy && !rare) { sums[s] = 0.0; sums[nsrc + s] = 0.0; sums[2 * (size_t)nsrc + s] = 0.0; }
     const unsigned long long m = __ballot(heavy);
     if (m) {
       int base = 0;
@@ -1383,10 +1418,33 @@ __global__ __launch_bounds__(256) void k_rect_materialize(int ndst, FgRect R, Fg
   v[8] = ya; v[9] = ya; v[10] = yb; v[11] = yb;
 }
 
+// compact source cells spelled out for fg_plan_get_cell_struct (tests): the longitudes of the boxes and the 128-byte records that
+// d_cell_record<false> would have stored; zeros beyond nv and for a cell without a record
+__global__ __launch_bounds__(256) void k_quad_materialize(int nsrc, FgCells S, double *lon_min, double *lon_max, double *verts)
+{
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= nsrc) return;
+  const int n = min(S.nv[s], G_MAXV);
+  double *o = verts + (size_t)s * 16;
+  double xmin = 0.0, xmax = 0.0;
+  if (n > 0) {
+    const FgVerts v = d_cell_verts(S, s, n);
+    xmin = v.x[0]; xmax = v.x[0];
+    for (int k = 0; k < G_MAXV; k++) {
+      const double x = k < n ? v.x[k] : 0.0, y = k < n ? v.y[k] : 0.0;
+      if (k > 0 && k < n) { if (x < xmin) xmin = x; if (x > xmax) xmax = x; }
+      o[k] = x; o[8 + k] = y;
+    }
+  } else
+    for (int k = 0; k < 16; k++) o[k] = 0.0;
+  lon_min[s] = xmin; lon_max[s] = xmax;
+}
+
 // The candidates of ONE source cell made by a whole wave (a cell listed as heavy: pole caps, every column): count, reserve, fill.
+// zero_sums != null (behind k_cell_struct2r, which left this cell's sums alone): [3][nsrc], zeroed here if the cell ends without a pair
 __device__ __forceinline__ void d_rect_cell_candidates(const FgRect &R, const FgPairSpace &ps, int s, int lane, double lat_in_min, double lat_in_max,
                                                        double lon_in_min, double lon_in_max, double lon_in_avg, int *pair_beg, int *pair_cnt,
-                                                       int *big_list, int *big_cnt)
+                                                       int *big_list, int *big_cnt, double *zero_sums = nullptr, int nsrc = 0)
 {
   const RectQuery q = d_rect_query(R, lat_in_min, lat_in_max, lon_in_min, lon_in_max);
   const int nwc = d_rect_ncols(q), nr = q.j1 - q.j0 + 1;
@@ -1421,6 +1479,7 @@ __device__ __forceinline__ void d_rect_cell_candidates(const FgRect &R, const Fg
     cbase += __popcll(m);
   }
   if (lane == 0) { pair_beg[s] = wbase; pair_cnt[s] = n_ok; if (n_ok > CP_SMALL) big_list[atomicAdd(big_cnt, 1)] = s; }
+  if (zero_sums && n_ok == 0 && lane < 3) zero_sums[(size_t)lane * nsrc + s] = 0.0;
 }
 
 // Candidates on a rectilinear destination grid.  Blocks [0, H): a wave per listed source cell (pole caps: every column);
@@ -1435,7 +1494,8 @@ __device__ __forceinline__ void d_rect_cell_candidates(const FgRect &R, const Fg
 template <bool FINISH>
 __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells S, const double *mask, FgRect R, FgPairSpace ps,
                                                          int *pair_beg, int *pair_cnt, const int *heavy_list, const int *heavy_cnt,
-                                                         int *big_list, int *big_cnt, const int *rare_list, const int *rare_cnt, unsigned *err)
+                                                         int *big_list, int *big_cnt, const int *rare_list, const int *rare_cnt, unsigned *err,
+                                                         double *sums /* FINISH: [3][nsrc] or null; zeroed for a cell of this launch that ends without a pair */)
 {
   const int lane = threadIdx.x;
   __shared__ unsigned wl[64 * RECT_WL_WORDS];
@@ -1451,7 +1511,24 @@ __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells
     const int nheavy = *heavy_cnt;
     for (int h = hb; h < nheavy; h += H) {
       const int s = heavy_list[h];
-      d_rect_cell_candidates(R, ps, s, lane, S.lat_min[s], S.lat_max[s], S.lon_min[s], S.lon_max[s], S.lon_avg[s], pair_beg, pair_cnt, big_list, big_cnt);
+      double xmin, xmax;
+      if constexpr (FINISH) {                              // compact cells: the box's longitudes from the record, as d_cell_record made them
+        const double *q = d_cell_quad(S, s);
+        const int n = S.nv[s];
+        double x[G_MAXV];
+#pragma unroll
+        for (int k = 0; k < G_MAXV; k++) x[k] = k < 4 ? q[k] : 0.0;     // (asked for with the count: hardly any cell has more than four)
+        if (n > 4) {
+          const FgVerts v = d_cell_verts(S, s, n);
+#pragma unroll
+          for (int k = 0; k < G_MAXV; k++) x[k] = v.x[k];
+        }
+        xmin = x[0]; xmax = x[0];
+#pragma unroll
+        for (int k = 1; k < G_MAXV; k++) if (k < n) { if (x[k] < xmin) xmin = x[k]; if (x[k] > xmax) xmax = x[k]; }
+      } else { xmin = S.lon_min[s]; xmax = S.lon_max[s]; }
+      d_rect_cell_candidates(R, ps, s, lane, S.lat_min[s], S.lat_max[s], xmin, xmax, S.lon_avg[s], pair_beg, pair_cnt, big_list, big_cnt,
+                             FINISH ? sums : nullptr, nsrc);
     }
     return;
   }
@@ -1460,10 +1537,18 @@ __global__ __launch_bounds__(64) void k_candidates_rect(int nsrc, int H, FgCells
       const int s = rare_list[h];
       const double mk = mask ? mask[s] : 1.0;              // (with the corners, not behind the record)
       double b[5] = {0, 0, 0, 0, 0};
-      const int nv = d_finish_rare_cell(S, err, s, lane, b);
-      if (!(nv > 0 && mk > 0.5)) continue;                 // (d_src_active; pair_cnt[s] = 0 from the record kernel)
-      if (d_rect_heavy(R, b[0], b[1], b[2], b[3])) d_rect_cell_candidates(R, ps, s, lane, b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt);
-      else (void)d_rect_wave_candidates<true>(R, ps, lane == 0, s, nsrc, (unsigned)(s >> 6), b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt, wl);
+      const int nv = d_finish_rare_cell(S, err, s, h, lane, b);
+      if (!(nv > 0 && mk > 0.5)) {                         // (d_src_active; pair_cnt[s] = 0 from the record kernel)
+        if (sums && lane < 3) sums[(size_t)lane * nsrc + s] = 0.0;
+        continue;
+      }
+      if (d_rect_heavy(R, b[0], b[1], b[2], b[3])) d_rect_cell_candidates(R, ps, s, lane, b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt, sums, nsrc);
+      else {
+        int npair = 0;
+        (void)d_rect_wave_candidates<true>(R, ps, lane == 0, s, nsrc, (unsigned)(s >> 6), b[0], b[1], b[2], b[3], b[4], pair_beg, pair_cnt, big_list, big_cnt, wl, &npair);
+        npair = __shfl(npair, 0);
+        if (sums && npair == 0 && lane < 3) sums[(size_t)lane * nsrc + s] = 0.0;
+      }
     }
   } else {
     const int bR = (int)blockIdx.x - H;
@@ -1518,7 +1603,9 @@ __device__ __forceinline__ void d_finish_pair(const double *px, const double *py
 // was measured on its round trips to memory and LDS and on its exec-masked regions, kept or not, is in
 // profiles/clip_edges_summary.md (kept: the pair's loads asked for in one round; the cutting edges unrolled together with the
 // polygon's slots read in one round, neither of which pays alone).
-template <bool RECT, int T>
+// QSRC (with RECT): the source cells are compact (FgCells, xgrid_device.h) -- four vertices in the one round, and the sixteen
+// doubles of the side table under n1 > 4 (whole waves as a rule: a cell's pairs are contiguous).
+template <bool RECT, int T, bool QSRC = false>
 __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int tid, const int s, const int d,
                                               const FgCells &S, const FgCells &D, const FgRect &R, unsigned *err)
 {
@@ -1530,13 +1617,19 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
   // quad.  Asked for one after the other -- the count, then the quad, then the vertices beyond the fourth under k < n1 -- each
   // was a round trip of its own that a wave sat out.
   // (The empty asm statements keep the compiler from moving the loads back below the test.)
-  const double *sv = S.verts + (size_t)s * 16;
   double x1[NV1], y1[NV1], x2[4], y2[4];
   double lon_out_avg;
   int n1 = S.nv[s], n2 = RECT ? 4 : D.nv[d];
   double lon_in_avg = S.lon_avg[s];
+  if constexpr (QSRC) {
+    const double *sq = d_cell_quad(S, s);
 #pragma unroll
-  for (int k = 0; k < NV1; k++) { x1[k] = sv[k]; y1[k] = sv[8 + k]; }
+    for (int k = 0; k < NV1; k++) { x1[k] = k < 4 ? sq[k] : 0.0; y1[k] = k < 4 ? sq[4 + k] : 0.0; }
+  } else {
+    const FgVerts sv = d_cell_verts(S, s, 0);            // (a 128-byte record: the place does not depend on the count)
+#pragma unroll
+    for (int k = 0; k < NV1; k++) { x1[k] = sv.x[k]; y1[k] = sv.y[k]; }
+  }
   if (RECT) {
     const int j = d / R.nx, i = d - j * R.nx;
     const double *c = R.col + (size_t)i * RECT_COLW;
@@ -1545,9 +1638,9 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
     asm volatile("" : "+v"(ya), "+v"(yb));
     y2[0] = ya; y2[1] = ya; y2[2] = yb; y2[3] = yb;
   } else {
-    const double *dv = D.verts + (size_t)d * 16;
+    const FgVerts dv = d_cell_verts(D, d, 0);          // (a 128-byte record, as above)
 #pragma unroll
-    for (int k = 0; k < 4; k++) { x2[k] = dv[k]; y2[k] = dv[8 + k]; }
+    for (int k = 0; k < 4; k++) { x2[k] = dv.x[k]; y2[k] = dv.y[k]; }
     lon_out_avg = D.lon_avg[d];
 #pragma unroll
     for (int k = 0; k < 4; k++) asm volatile("" : "+v"(y2[k]));
@@ -1559,6 +1652,13 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
   for (int k = 0; k < 4; k++) asm volatile("" : "+v"(x2[k]));
   asm volatile("" : "+v"(n1), "+v"(lon_in_avg), "+v"(lon_out_avg));
   if (n1 > NV1 || n2 > 4) return -1;
+  if constexpr (QSRC) {
+    if (n1 > 4) {
+      const FgVerts sv = d_cell_verts(S, s, n1);
+#pragma unroll
+      for (int k = 0; k < NV1; k++) { x1[k] = sv.x[k]; y1[k] = sv.y[k]; }
+    }
+  }
   double shift = 0.0;
   {
     double dx = lon_out_avg - lon_in_avg;            // create_xgrid.c:1064-1074
@@ -1678,7 +1778,7 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
 #define CLIP_COMPACT 0
 #endif
 __device__ __forceinline__ int d_row_slot(int *row_cnt, bool take, int d, int lane);   // (below, with the compaction)
-template <int ORDER, bool RECT>
+template <int ORDER, bool RECT, bool QSRC = false>
 __global__ __launch_bounds__(CLIP_THREADS) __attribute__((amdgpu_waves_per_eu(CLIP_WAVES, CLIP_WAVES))) void k_clip_quad(FgPairSpace ps, FgCells S, const double *mask, FgCells D, FgRect R,
                                                  double *tmp_area, double *tmp_clon, double *tmp_clat, int *nacc,
                                                  int *defer_list, int *defer_cnt,
@@ -1720,7 +1820,7 @@ __global__ __launch_bounds__(CLIP_THREADS) __attribute__((amdgpu_waves_per_eu(CL
   bool defer = false;
   int n_cur = 0;
   if ((unsigned)(p0 + tid) - reg * (unsigned)ps.regcap < min(fill, (unsigned)ps.regcap)) {      // d_pair_live
-    n_cur = d_clip_quad_sh<RECT, T>(sh_poly, tid, s_in, d_in, S, D, R, err);
+    n_cur = d_clip_quad_sh<RECT, T, QSRC>(sh_poly, tid, s_in, d_in, S, D, R, err);
     if (n_cur < 0) { defer = true; n_cur = 0; }        // rare; the general kernel finishes this pair
     else if (n_cur == 0) ps.dst[p0 + tid] = -1;
   }
@@ -1822,7 +1922,7 @@ __global__ __launch_bounds__(GEN_THREADS) void k_clip_general(const int *defer_l
     const int p = defer_list[q];
     const int s = pair_src[p], d = pair_dst[p];
     const int n1 = S.nv[s], n2 = RECT ? 4 : D.nv[d];
-    const double *sv = S.verts + (size_t)s * 16;
+    const FgVerts sv = d_cell_verts(S, s, n1);
     const double lon_in_avg = S.lon_avg[s];
     double dvx[G_MAXV], dvy[G_MAXV], lon_out_avg;
     if (RECT) {
@@ -1834,9 +1934,9 @@ __global__ __launch_bounds__(GEN_THREADS) void k_clip_general(const int *defer_l
 #pragma unroll
       for (int k = 4; k < G_MAXV; k++) { dvx[k] = 0.0; dvy[k] = 0.0; }
     } else {
-      const double *dv = D.verts + (size_t)d * 16;
+      const FgVerts dv = d_cell_verts(D, d, n2);
 #pragma unroll
-      for (int k = 0; k < G_MAXV; k++) { dvx[k] = dv[k]; dvy[k] = dv[8 + k]; }
+      for (int k = 0; k < G_MAXV; k++) { dvx[k] = dv.x[k]; dvy[k] = dv.y[k]; }
       lon_out_avg = D.lon_avg[d];
     }
     double shift = 0.0;
@@ -1845,10 +1945,10 @@ __global__ __launch_bounds__(GEN_THREADS) void k_clip_general(const int *defer_l
       if (dx < -G_PI) shift = G_TPI; else if (dx > G_PI) shift = -G_TPI;
     }
     bool wrap = false;
-    for (int k = 0; k < n1; k++) { double xv = sv[k]; if (xv > G_TPI || xv < 0.0) wrap = true; }
+    for (int k = 0; k < n1; k++) { double xv = sv.x[k]; if (xv > G_TPI || xv < 0.0) wrap = true; }
     for (int k = 0; k < n1; k++) {
-      double xv = sv[k]; if (wrap) xv = d_pimod1(xv);
-      sh_a[k][tid] = make_double2(xv, sv[8 + k]);
+      double xv = sv.x[k]; if (wrap) xv = d_pimod1(xv);
+      sh_a[k][tid] = make_double2(xv, sv.y[k]);
     }
 #pragma unroll
     for (int k = 0; k < G_MAXV; k++)
@@ -2230,8 +2330,8 @@ __global__ __launch_bounds__(256) void k_centroids(int nsrc, FgCells S, const do
     if (whole) {
       double x[G_MAXV], y[G_MAXV];
       int n = nv;
-      const double *vp = S.verts + (size_t)s * 16;
-      for (int k = 0; k < G_MAXV; k++) { x[k] = vp[k]; y[k] = vp[8 + k]; }
+      const FgVerts vp = d_cell_verts(S, s, n);
+      for (int k = 0; k < G_MAXV; k++) { x[k] = k < n ? vp.x[k] : 0.0; y[k] = k < n ? vp.y[k] : 0.0; }   // (zeros beyond n, as a 128-byte record has them)
       cl = d_poly_ctrlon<1>(x, y, n, S.lon_avg[s]) / ca;
       ct = d_poly_ctrlat<1>(x, y, n) / ca;
     }
@@ -2305,9 +2405,10 @@ void fgd_clip_quad(int order, FgPairSpace ps, FgCells S, const double *mask, FgC
   if (np <= 0) return;
   const FgRect R = rect ? *rect : FgRect{};
   const int g = nblk(np, CLIP_THREADS);
-#define FG_LAUNCH_QUAD(O, RC) k_clip_quad<O, RC><<<g, CLIP_THREADS, 0, st>>>(ps, S, mask, D, R, tmp_area, tmp_clon, tmp_clat, nacc, defer_list, defer_cnt, stats, err, row_cnt, tmp_rowpos)
-  if (order == 2) { if (rect) FG_LAUNCH_QUAD(2, true); else FG_LAUNCH_QUAD(2, false); }
-  else            { if (rect) FG_LAUNCH_QUAD(1, true); else FG_LAUNCH_QUAD(1, false); }
+#define FG_LAUNCH_QUAD(O, RC, QS) k_clip_quad<O, RC, QS><<<g, CLIP_THREADS, 0, st>>>(ps, S, mask, D, R, tmp_area, tmp_clon, tmp_clat, nacc, defer_list, defer_cnt, stats, err, row_cnt, tmp_rowpos)
+  const bool qsrc = rect && S.vstride == FG_VSTRIDE_QUAD;    // compact source cells: a grid on the rectilinear path
+  if (order == 2) { if (qsrc) FG_LAUNCH_QUAD(2, true, true); else if (rect) FG_LAUNCH_QUAD(2, true, false); else FG_LAUNCH_QUAD(2, false, false); }
+  else            { if (qsrc) FG_LAUNCH_QUAD(1, true, true); else if (rect) FG_LAUNCH_QUAD(1, true, false); else FG_LAUNCH_QUAD(1, false, false); }
 #undef FG_LAUNCH_QUAD
 }
 
@@ -2330,8 +2431,9 @@ void fgd_rect_tables(const double *lon, const double *lat, int nx, int ny, doubl
                      double *col_min, double *col_max, double *col_avg, double *row, unsigned *bad, unsigned *err, hipStream_t st, double dst_tlon)
 {
   const long np = (long)(nx + 1) * (ny + 1);
-  const int g = (int)std::min<long>(1024, std::max<long>((np + 255) / 256, (std::max(nx, ny) + 1 + 255) / 256));
-  k_rect_tables<<<std::max(g, 1), 256, 0, st>>>(lon, lat, nx, ny, hdr, lat_ax, lon_ax, col, col_min, col_max, col_avg, row, bad, err, dst_tlon);
+  const int nbT = (std::max(nx, ny) + 1 + 255) / 256;      // (as the kernel counts them)
+  const int nbV = (int)std::min<long>(RECT_VERIFY_BLOCKS, std::max<long>((np + 255) / 256, 1));
+  k_rect_tables<<<nbT + nbV, 256, 0, st>>>(lon, lat, nx, ny, hdr, lat_ax, lon_ax, col, col_min, col_max, col_avg, row, bad, err, dst_tlon);
 }
 void fgd_cell_struct2r(const FgTileSet &ts, const FgTile *tiles_in, FgTile *tiles_out, int ntiles, int nsrc, int ndst, FgCells S, double *area_out,
                        FgRect R, const double *mask, int order, int *src_idx_f, double *sums, unsigned *err, hipStream_t st,
@@ -2353,9 +2455,13 @@ void fgd_rect_materialize(int ndst, FgRect R, FgCells D, hipStream_t st)
 {
   if (ndst > 0) k_rect_materialize<<<nblk(ndst, 256), 256, 0, st>>>(ndst, R, D);
 }
+void fgd_quad_materialize(int nsrc, FgCells S, double *lon_min, double *lon_max, double *verts, hipStream_t st)
+{
+  if (nsrc > 0) k_quad_materialize<<<nblk(nsrc, 256), 256, 0, st>>>(nsrc, S, lon_min, lon_max, verts);
+}
 void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPairSpace ps, int *pair_beg, int *pair_cnt,
                          const int *heavy_list, const int *heavy_cnt, int *big_list, int *big_cnt, hipStream_t st, int listed_only,
-                         const int *rare_list, const int *rare_cnt, unsigned *err)
+                         const int *rare_list, const int *rare_cnt, unsigned *err, double *sums)
 {
   if (nsrc <= 0) return;
   const int nbR = listed_only ? 0 : nblk(nsrc, 64);       // listed_only: the record kernel made the candidates of the other cells
@@ -2367,9 +2473,9 @@ void fgd_candidates_rect(int nsrc, FgCells S, const double *mask, FgRect R, FgPa
   // (its 174 VGPRs let two waves share a SIMD, 2048 on the chip: the rare-cell blocks come out of H, not on top of it)
   const int Hf = max(H - RARE_BLOCKS, RARE_BLOCKS);
   if (listed_only) k_candidates_rect<true><<<Hf + RARE_BLOCKS, 64, 0, st>>>(nsrc, Hf, S, mask, R, ps, pair_beg, pair_cnt, heavy_list, heavy_cnt, big_list, big_cnt,
-                                                          rare_list, rare_cnt, err);
+                                                          rare_list, rare_cnt, err, sums);
   else k_candidates_rect<false><<<nbR + H, 64, 0, st>>>(nsrc, H, S, mask, R, ps, pair_beg, pair_cnt, heavy_list, heavy_cnt, big_list, big_cnt,
-                                                       nullptr, nullptr, nullptr);
+                                                       nullptr, nullptr, nullptr, nullptr);
 }
 
 void fgd_compact(int order, int nsrc, FgPairSpace ps, const FgCompactIo &io, hipStream_t st)

@@ -381,6 +381,11 @@ void fg_set_search_finalize(int on);
  * (no bins, no per-cell records); the property is verified on the device inside the search, and a grid that fails it is searched
  * by the generic path in the same call.  0: always the generic path.  Results do not depend on it (tests/test_gpu_rect.py). */
 void fg_set_search_rect(int on);
+/* Rectilinear path, grid sources: source cells are kept as 64-byte quadrilateral records, and the few that fix_lon leaves with
+ * more than four vertices (a lone pole vertex, a half-turn edge) in a side table of ncells / 16 + 64 slots; a search that meets
+ * more of them is repeated on the generic path in the same call.  n >= 0 lowers the table's capacity to n slots (tests of that
+ * route), n < 0 restores the default.  Results do not depend on it. */
+void fg_set_search_wide_cap(int n);
 /* Longitude frame of the destination cells of a legacy search: 0 (default) create_xgrid's -- fix_lon(cell, pi), then the +-2pi shift
  * towards the source cell per pair (create_xgrid.c:1004,1062-1079); 1 make_coupler_mosaic's -- the cell is moved once per pair,
  * fix_lon(cell, mean longitude of the other cell) (make_coupler_mosaic.c:1452,1598).  Same exchange cells; the vertices (and so
