@@ -22,6 +22,9 @@ mirrors the reference's call signatures:
      check_river_data, the source bounds, the land fraction thresholds)
 * ``Topog`` / ``create_realistic_topog`` / ``zw_from_zeta``
   -- tools/make_topog/topog.c:355,551,687,830,878,987 (create_realistic_topog with filter_topo, process_topo and its adjustments)
+* ``CouplerMosaic`` / ``coupler_ocean_grid`` / ``coupler_xgrid``
+  -- tools/make_coupler_mosaic/make_coupler_mosaic.c:841,1198,1743,2018,2466 (the ocean grid's southern row, the three exchange
+     grids, the per-cell sums and centroid distances, the masks)
 
 There is NO CPU fallback: if the shared library is missing, or no HIP device is visible
 when a compute entry point is called, an exception is raised.
@@ -38,7 +41,7 @@ from .c2l import C2lPrep, find_contacts, c2l_grid_info, halo_map  # noqa: F401
 from .remap_file import write_remap_file, read_remap_file  # noqa: F401
 from .field_io import NcFile, Sweep, HostBuffer, read_field_levels  # noqa: F401
 from . import field_io  # noqa: F401
-from .coupler import coupler_xgrid  # noqa: F401
+from .coupler import coupler_xgrid, CouplerMosaic, coupler_ocean_grid  # noqa: F401
 from .bilinear import (BilinearPlan, setup_bilinear_interp, do_scalar_bilinear_interp, do_vector_bilinear_interp,  # noqa: F401
                        write_bilinear_remap_file, read_bilinear_remap_file)
 from .extrapolate import (Extrapolator, do_extrapolate, setup_vertical_interp, do_vertical_interp,  # noqa: F401
@@ -69,6 +72,7 @@ __all__ = [
     "LandNearest",
     "RiverRegrid", "river_source_grid", "river_land_frac",
     "Topog", "create_realistic_topog", "zw_from_zeta",
+    "coupler_xgrid", "CouplerMosaic", "coupler_ocean_grid",
 ]
 
 

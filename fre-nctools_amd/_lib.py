@@ -65,6 +65,8 @@ EXPORTS = [
     "fg_topog_default_opts", "fg_topog_create", "fg_topog_destroy", "fg_topog_stream", "fg_topog_set_source", "fg_topog_get_source",
     "fg_topog_remap", "fg_topog_filter", "fg_topog_process", "fg_topog_run", "fg_topog_set_depth", "fg_topog_get", "fg_topog_stats",
     "fg_topog_phase_ms", "fg_plan_apply_frac_dev", "fg_set_topog_sweep",
+    "fg_coupler_create", "fg_coupler_destroy", "fg_coupler_stream", "fg_coupler_run", "fg_coupler_count", "fg_coupler_get",
+    "fg_coupler_get_cells", "fg_coupler_write", "fg_coupler_write_xgrid", "fg_coupler_write_mask", "fg_coupler_stats", "fg_coupler_phase_ms",
 ]
 
 
@@ -499,6 +501,31 @@ def lib():
     L.fg_set_topog_sweep.restype = None
     L.fg_plan_apply_frac_dev.argtypes = [vp, vp, vp]
     L.fg_plan_apply_frac_dev.restype = C.c_int
+    L.fg_coupler_create.argtypes = [C.c_int, C.c_double, C.c_int, ip, ip, dpp, dpp, C.c_int, ip, ip, dpp, dpp, C.c_int, C.c_int, dp, dp, dp, C.c_int,
+                                    C.c_int, C.POINTER(vp)]
+    L.fg_coupler_create.restype = C.c_int
+    L.fg_coupler_destroy.argtypes = [vp]
+    L.fg_coupler_destroy.restype = None
+    L.fg_coupler_stream.argtypes = [vp]
+    L.fg_coupler_stream.restype = vp
+    L.fg_coupler_run.argtypes = [vp]
+    L.fg_coupler_run.restype = C.c_int
+    L.fg_coupler_count.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.fg_coupler_count.restype = C.c_long
+    L.fg_coupler_get.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [ip] * 4 + [dp] * 7
+    L.fg_coupler_get.restype = C.c_int
+    L.fg_coupler_get_cells.argtypes = [vp, C.c_int, C.c_int] + [dp] * 5
+    L.fg_coupler_get_cells.restype = C.c_int
+    L.fg_coupler_write.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p)]
+    L.fg_coupler_write.restype = C.c_int
+    L.fg_coupler_write_xgrid.argtypes = [C.c_char_p, C.c_char_p, C.c_long] + [ip] * 4 + [C.c_int] + [dp] * 5
+    L.fg_coupler_write_xgrid.restype = C.c_int
+    L.fg_coupler_write_mask.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int] + [dp] * 4
+    L.fg_coupler_write_mask.restype = C.c_int
+    L.fg_coupler_stats.argtypes = [vp, C.POINTER(C.c_long), C.c_int]
+    L.fg_coupler_stats.restype = C.c_int
+    L.fg_coupler_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    L.fg_coupler_phase_ms.restype = C.c_int
     _LIB = L
     return L
 

@@ -14,11 +14,22 @@ The plans apply create_xgrid's acceptance (area / min(area_src, area_dst) > 1e-6
 lists -- same products, same order, same bits as the reference loop (tests/test_gpu_coupler.py drives the reference's own
 compiled clip_2dx2d / poly_area / poly_ctrlon / fix_lon through that loop and compares bit for bit).
 
-Host logic only; all geometry runs in libfregrid_hip.  Not covered: nested atmosphere tiles, the wave grid, great-circle clip,
-lnd_same_as_atm's vertex copy (pass distinct grids), the land x ocean list and the mask / centroid bookkeeping after :1727.
+coupler_xgrid is host logic over the plans' downloaded lists; it does not cover lnd_same_as_atm's vertex copy (pass distinct
+grids), the land x ocean list or the bookkeeping after :1727.
+
+CouplerMosaic (fg_coupler_*, csrc/coupler.hip) is the tool's compute core as one device-resident pipeline:
+:1198-2127 and :2466-2811 -- land on the atmosphere grid or of its own, the three lists, the per-cell area and centroid sums, the
+centroid distances, the land and ocean masks -- with the lists and polygons kept in device memory between the searches, and the
+exchange-grid and mask files through the library's classic-netCDF writer.  coupler_ocean_grid is the numpy mirror of the ocean
+grid preparation (:841-876, :940-955).  Not covered by either: nested atmosphere tiles, the wave grid, great-circle clip, several
+ocean tiles, --check's global sums, the MPI split, the coupler mosaic file.
 """
+import ctypes as C
+import os
+
 import numpy as np
 
+from ._lib import check, lib, require_gpu
 from .conserve_interp import GridConfig, XgridPlan
 
 MIN_AREA_FRAC = 1.0e-4          # make_coupler_mosaic.c:148
@@ -100,3 +111,207 @@ def _coupler_xgrid(atm, lnd, ocn, omask, interp_order, area_ratio_thresh, device
     if order == 2:
         axl["clon"], axl["clat"] = axl_clon[fin], axl_clat[fin]
     return {"axo": axo, "axl": axl, "n_axl_polygons": int(poly["n"].size)}
+
+
+D2R = np.pi / 180               # constant.h
+TINY_VALUE = 1.0e-7             # make_coupler_mosaic.c:146
+STRING = 255                    # mpp.h
+_dpt = C.POINTER(C.c_double)
+_ipt = C.POINTER(C.c_int)
+
+
+def coupler_ocean_grid(x_deg, y_deg, omask=None):
+    """:841-876 and :940-955 in numpy.  x_deg, y_deg [ny+1, nx+1]: the ocean model grid's corners in degrees (one tile); omask
+    [ny, nx]: the ocean fraction (area_frac, or 1 where depth > sea_level), None for none.  When the first row lies above
+    -90 + 1e-7 degrees' worth of radians one row down to -90 is added (ocn_south_ext = 1) with the longitudes of the first row and
+    omask = 0.  Returns a dict: nx, ny (with the extension), ocn_south_ext, x, y [ny+1, nx+1] in radians, omask [ny, nx],
+    jo_shift = 1 - ocn_south_ext (what the exchange-grid files add to a 0-based jo, :2309, :2876), uniform (whether the first
+    row has one latitude, :846-851)."""
+    xd, yd = np.ascontiguousarray(x_deg, dtype=np.float64), np.ascontiguousarray(y_deg, dtype=np.float64)
+    if xd.ndim != 2 or xd.shape != yd.shape or xd.shape[0] < 2 or xd.shape[1] < 2:
+        raise ValueError("x_deg, y_deg must be [ny+1, nx+1]")
+    ny0, nx = xd.shape[0] - 1, xd.shape[1] - 1
+    uniform = bool(np.all(yd[0, 1:] == yd[0, :-1]))
+    min_atm_lat = -90. * D2R
+    ext = 1 if yd[0, 0] * D2R > min_atm_lat + TINY_VALUE else 0
+    ny = ny0 + ext
+    x, y = np.empty((ny + 1, nx + 1)), np.empty((ny + 1, nx + 1))
+    x[ext:] = xd * D2R
+    y[ext:] = yd * D2R
+    if ext:
+        x[0] = x[1]
+        y[0] = min_atm_lat
+    m = np.zeros((ny, nx))
+    if omask is not None:
+        om = np.ascontiguousarray(omask, dtype=np.float64)
+        if om.shape != (ny0, nx):
+            raise ValueError("make_coupler_mosaic: grid size mismatch between mosaic file and topog file")
+        m[ext:] = om
+    return dict(nx=nx, ny=ny, ocn_south_ext=ext, x=x, y=y, omask=m, jo_shift=1 - ext, uniform=uniform)
+
+
+def write_xgrid_file(path, contact, i1, j1, i2, j2, area, dist1=None, dist2=None, j2_shift=1):
+    """One exchange-grid file from host arrays (fg_coupler_write_xgrid; :2158-2244): contact, tile1_cell, tile2_cell [ncells, 2]
+    (1-based: the 0-based indices + 1, the second grid's j + j2_shift), xgrid_area, and with dist1 / dist2 (each a pair (di, dj))
+    tile1_distance / tile2_distance [ncells, 2] and the order-2 attributes of contact.  An empty list gets no file: an error here."""
+    ints = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (i1, j1, i2, j2)]
+    dbl = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (area,) + (tuple(dist1) + tuple(dist2) if dist1 is not None else ())]
+    n = dbl[0].size
+    if any(v.size != n for v in ints + dbl):
+        raise ValueError("the arrays of an exchange-grid file must have one length")
+    check(lib().fg_coupler_write_xgrid(str(path).encode(), contact.encode(), n, *[v.ctypes.data_as(_ipt) for v in ints], int(j2_shift),
+                                       *[v.ctypes.data_as(_dpt) for v in dbl], *([None] * (5 - len(dbl)))))
+
+
+def write_mask_file(path, kind, fields):
+    """ocean_mask.nc (kind "ocean": fields mask, areaO, areaX, :2055-2066) or a land mask file (kind "land": mask, area_lnd, l_area and
+    area_atm when given, :2103-2117) from host arrays [ny, nx] (fg_coupler_write_mask)."""
+    keys = {"ocean": ("mask", "areaO", "areaX"), "land": ("mask", "area_lnd", "l_area")}[kind]
+    a = [np.ascontiguousarray(fields[k], dtype=np.float64) for k in keys]
+    ny, nx = a[0].shape
+    atm = np.ascontiguousarray(fields["area_atm"], dtype=np.float64) if kind == "land" and "area_atm" in fields else None
+    if any(v.shape != (ny, nx) for v in a) or (atm is not None and atm.shape != (ny, nx)):
+        raise ValueError("the fields of a mask file must be [ny, nx]")
+    check(lib().fg_coupler_write_mask(str(path).encode(), 1 if kind == "ocean" else 0, nx, ny, *[v.ctypes.data_as(_dpt) for v in a],
+                                      atm.ctypes.data_as(_dpt) if atm is not None else None))
+
+
+class CouplerMosaic:
+    """RAII wrapper of fg_coupler.  atm: list of GridConfig (atmosphere tiles); lnd: None (land on the atmosphere grid,
+    lnd_same_as_atm), one GridConfig or a list of them; ocn: one GridConfig, the grid the tool works on (coupler_ocean_grid's x, y);
+    omask [ny_ocn, nx_ocn]: the ocean fraction; ocn_south_ext: coupler_ocean_grid's.  Corners in radians."""
+
+    AXL, AXO, LXO = 0, 1, 2
+    ATM, LND, OCN = 0, 1, 2
+
+    def __init__(self, atm, lnd, ocn, omask, interp_order=2, area_ratio_thresh=AREA_RATIO_THRESH, ocn_south_ext=0, device=0):
+        self._h = None
+        require_gpu()
+        self.atm = list(atm)
+        self.same = lnd is None
+        self.lnd = self.atm if self.same else (list(lnd) if isinstance(lnd, (list, tuple)) else [lnd])
+        self.ocn, self.order, self.ocn_south_ext, self.device = ocn, int(interp_order), int(ocn_south_ext), device
+        om = np.ascontiguousarray(omask, dtype=np.float64)
+        if om.size != ocn.nx * ocn.ny:
+            raise ValueError(f"omask must be [{ocn.ny}, {ocn.nx}]")
+
+        def table(grids):
+            keep = [(np.ascontiguousarray(g.lonc, dtype=np.float64), np.ascontiguousarray(g.latc, dtype=np.float64)) for g in grids]
+            for g, (lo, la) in zip(grids, keep):
+                if lo.size != (g.nx + 1) * (g.ny + 1) or la.size != lo.size:
+                    raise ValueError("a grid's corner arrays must be [ny+1, nx+1]")
+            n = len(grids)
+            return (keep, (C.c_int * n)(*[g.nx for g in grids]), (C.c_int * n)(*[g.ny for g in grids]),
+                    (_dpt * n)(*[k[0].ctypes.data_as(_dpt) for k in keep]), (_dpt * n)(*[k[1].ctypes.data_as(_dpt) for k in keep]))
+
+        ka, nxa, nya, loa, laa = table(self.atm)
+        kl, nxl, nyl, lol, lal = table(self.lnd)
+        ko, _, _, _, _ = table([ocn])
+        h = C.c_void_p()
+        check(lib().fg_coupler_create(self.order, float(area_ratio_thresh), len(self.atm), nxa, nya, loa, laa, 0 if self.same else len(self.lnd),
+                                      nxl, nyl, lol, lal, ocn.nx, ocn.ny, ko[0][0].ctypes.data_as(_dpt), ko[0][1].ctypes.data_as(_dpt),
+                                      om.ctypes.data_as(_dpt), self.ocn_south_ext, device, C.byref(h)))
+        self._h = h
+
+    def destroy(self):
+        if self._h is not None and self._h.value:
+            lib().fg_coupler_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stream(self):
+        """the hipStream_t (as an int) the handle queues its work on"""
+        return lib().fg_coupler_stream(self._h)
+
+    def run(self):
+        check(lib().fg_coupler_run(self._h))
+        return self
+
+    def _list(self, which, t1, t2, names):
+        n = check(lib().fg_coupler_count(self._h, which, t1, t2))
+        out = {k: np.empty(n, dtype=np.int32) for k in names}
+        out["area"] = np.empty(n)
+        dbl = ("clon", "clat", "di1", "dj1", "di2", "dj2") if self.order == 2 else ()
+        for k in dbl:
+            out[k] = np.empty(n)
+        ints = [out[k].ctypes.data_as(_ipt) for k in names]
+        dbls = [out[k].ctypes.data_as(_dpt) for k in dbl] + [None] * (6 - len(dbl))
+        check(lib().fg_coupler_get(self._h, which, t1, t2, *ints, out["area"].ctypes.data_as(_dpt), *dbls))
+        return out
+
+    def axl(self, ta, tl):
+        """atmosphere tile ta x land tile tl in the reference's order: dict ia, ja, il, jl (0-based), area, and for order 2 clon, clat
+        (the centroid integrals), di1, dj1 (tile1_distance), di2, dj2 (tile2_distance)"""
+        return self._list(self.AXL, ta, tl, ("ia", "ja", "il", "jl"))
+
+    def axo(self, ta):
+        """atmosphere tile ta x ocean: dict ia, ja, io, jo (jo counts the added southern row), area, ..."""
+        return self._list(self.AXO, ta, 0, ("ia", "ja", "io", "jo"))
+
+    def lxo(self, tl):
+        """land tile tl x ocean (land of its own only): dict il, jl, io, jo, area, ..."""
+        return self._list(self.LXO, tl, 0, ("il", "jl", "io", "jo"))
+
+    def cells(self, grid, tile=0):
+        """per cell of one tile (grid: ATM, LND, OCN), [ny, nx] each: dict area (get_grid_area), xarea (a_area / l_area / o_area),
+        frac (their ratio: the land mask, the ocean fraction) and for order 2 clon, clat (the centroid)"""
+        g = (self.atm, self.lnd, [self.ocn])[grid][tile]
+        names = ("area", "xarea", "frac") + (("clon", "clat") if self.order == 2 else ())
+        out = {k: np.empty((g.ny, g.nx)) for k in names}
+        ptr = [out[k].ctypes.data_as(_dpt) for k in names] + [None] * (5 - len(names))
+        check(lib().fg_coupler_get_cells(self._h, grid, tile, *ptr))
+        return out
+
+    def stats(self):
+        """dict: d2h_bytes (what run() copied to the host), nbad, searches, naxo, naxl, nlxo, npolygons, ocn_south_ext"""
+        s = (C.c_long * 8)()
+        check(lib().fg_coupler_stats(self._h, s, 8))
+        return dict(zip(("d2h_bytes", "nbad", "searches", "naxo", "naxl", "nlxo", "npolygons", "ocn_south_ext"), s))
+
+    def phase_ms(self):
+        """wall time in ms: dict create, axl_candidates, axo, polygons_x_ocean, lxo, sums, run"""
+        ms = (C.c_float * 7)()
+        check(lib().fg_coupler_phase_ms(self._h, ms, 7))
+        return dict(zip(("create", "axl_candidates", "axo", "polygons_x_ocean", "lxo", "sums", "run"), ms))
+
+    def write(self, directory, atm_mosaic="atmos_mosaic", lnd_mosaic="land_mosaic", ocn_mosaic="ocean_mosaic", atm_tiles=None, lnd_tiles=None,
+              ocn_tile="tile1"):
+        """The exchange-grid files (:2130-2462, :2813-2920) and ocean_mask.nc / land_mask[_tileN].nc (:2030-2120) into directory
+        (fg_coupler_write); names as the tool forms them from the mosaic and tile names.  Returns the files written; an empty list
+        gets no file."""
+        atm_tiles = list(atm_tiles or [f"tile{k + 1}" for k in range(len(self.atm))])
+        lnd_tiles = list(lnd_tiles or [f"tile{k + 1}" for k in range(len(self.lnd))])
+        if len(atm_tiles) != len(self.atm) or len(lnd_tiles) != len(self.lnd):
+            raise ValueError("one name per atmosphere tile and per land tile")
+        table = [atm_mosaic, lnd_mosaic, ocn_mosaic] + atm_tiles + lnd_tiles + [ocn_tile]
+        names = (C.c_char_p * len(table))(*[t.encode() for t in table])
+        check(lib().fg_coupler_write(self._h, str(directory).encode(), names))
+        count = lambda which, t1, t2: check(lib().fg_coupler_count(self._h, which, t1, t2))
+        files = []
+        for ta, at in enumerate(atm_tiles):
+            files += [f"{atm_mosaic}_{at}X{lnd_mosaic}_{lt}.nc" for tl, lt in enumerate(lnd_tiles) if count(self.AXL, ta, tl)]
+            files += [f"{atm_mosaic}_{at}X{ocn_mosaic}_{ocn_tile}.nc"] if count(self.AXO, ta, 0) else []
+        if not self.same:
+            files += [f"{lnd_mosaic}_{lt}X{ocn_mosaic}_{ocn_tile}.nc" for tl, lt in enumerate(lnd_tiles) if count(self.LXO, tl, 0)]
+        files.append("ocean_mask.nc")
+        files += ["land_mask.nc"] if len(self.lnd) == 1 else [f"land_mask_tile{k + 1}.nc" for k in range(len(self.lnd))]
+        return [os.path.join(str(directory), f) for f in files]
+
+
+__all__ = ["coupler_xgrid", "CouplerMosaic", "coupler_ocean_grid", "write_xgrid_file", "write_mask_file", "MIN_AREA_FRAC", "AREA_RATIO_THRESH"]

@@ -1,0 +1,714 @@
+// coupler.hip -- host orchestration of make_coupler_mosaic's exchange grids on the device (fg_coupler_*):
+// tools/make_coupler_mosaic/make_coupler_mosaic.c:1198-2127 (atmosphere x land, atmosphere x ocean, the per-cell sums, the
+// centroid distances, the masks) and :2466-2811 (land x ocean), legacy clip, one process, no nest, one ocean tile.
+// Kernels: coupler_kernels.hip; shared declarations: coupler.h; design: DESIGN.md 3.13.
+//
+// The host decides what runs and how large the buffers are.  The three nested clip loops are plans (plan.hip) in the coupler's
+// longitude frame; their exchange cells, the clipped atmosphere x land polygons and every list made of them stay in device
+// memory from one search to the next (plan_internal.h), and so do the sums, distances and masks until a getter asks for them.
+// What fg_coupler_run brings to the host is counted (fg_coupler_stats): list lengths, tile starts, the error word, and the
+// counter block every search reads back.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <initializer_list>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+#include "coupler.h"
+#include "fg_host.h"
+#include "plan_internal.h"
+
+namespace {
+struct Grid {                                   // one tile in device memory
+  int nx = 0, ny = 0, off = 0;                  // off: first cell in the grid's flattened numbering
+  double *lon = nullptr, *lat = nullptr;
+  double dlat = 0, dlon = 0;                    // what a search with this tile as destination takes (fg_dst_extents)
+  int rect_hint = 0;
+  long ncells() const { return (long)nx * ny; }
+};
+struct Cand {                                   // the remembered atmosphere x land polygons of one land tile (:1517-1546)
+  int n = 0;
+  int *pa = nullptr, *pl = nullptr, *pn = nullptr;
+  double *plon = nullptr, *plat = nullptr, *lon_avg = nullptr, *area_ref = nullptr;
+};
+}  // namespace
+
+struct fg_coupler {
+  int device = 0, order = 2, south_ext = 0;
+  double thresh = 1.0e-6;
+  bool same = false;                            // land on the atmosphere grid (lnd_same_as_atm)
+  hipStream_t stream = nullptr;
+  FgDev dev;                                    // grids, areas, the ocean fraction: as long as the handle
+  std::unique_ptr<FgDev> res;                   // what a run leaves: replaced by the next run
+  std::vector<Grid> atm, lnd;                   // same: lnd is a copy of atm (the same device arrays)
+  Grid ocn;
+  int na = 0, nl = 0, no = 0;                   // cells of the three grids
+  double *area_atm = nullptr, *area_lnd = nullptr, *area_ocn = nullptr, *omask = nullptr;
+  int *d_aoff = nullptr;                        // [ntile_atm + 1] cell offsets of the atmosphere tiles
+  // results
+  bool ran = false;
+  std::vector<CpList> axl, lxo;                 // per land tile
+  CpList axo;
+  std::vector<std::vector<int>> axl_start;      // [land tile][ntile_atm + 1]: where an atmosphere tile's cells begin in the list
+  std::vector<int> axo_start;
+  CpSums a{}, l{}, o{}, l2{}, o2{};             // l2 / o2: the sums of the land x ocean lists (:2699-2795)
+  double *a_frac = nullptr, *l_frac = nullptr, *o_frac = nullptr;
+  long d2h = 0, searches = 0, ncand = 0;
+  int nbad = 0;
+  float ms[7] = {0, 0, 0, 0, 0, 0, 0};          // create; atm x land candidates; atm x ocean; polygons x ocean; land x ocean; sums; run
+};
+
+extern "C" void fg_coupler_destroy(fg_coupler *h)
+{
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
+  delete h;
+}
+extern "C" void *fg_coupler_stream(fg_coupler *h) { return h ? (void *)h->stream : nullptr; }
+
+// get_grid_area of the tiles of one grid (:614, :736, :896): the source records of a search against a dummy cell, as the
+// library's own get_grid_area does, into area [cells of all tiles]
+static int cp_grid_area(fg_coupler *h, const std::vector<Grid> &g, const double *d_dummy, double *area)
+{
+  std::vector<int> nx, ny;
+  std::vector<const double *> lon, lat;
+  for (const Grid &t : g) { nx.push_back(t.nx); ny.push_back(t.ny); lon.push_back(t.lon); lat.push_back(t.lat); }
+  fg_plan *pl = nullptr;
+  const long rc = fg_plan_create_dev_hint(FG_CONSERVE_ORDER1, (int)g.size(), nx.data(), ny.data(), lon.data(), lat.data(), 1, 1, d_dummy, d_dummy + 4,
+                                          0.01, 0.01, 0, h->device, h->stream, &pl);
+  if (rc < 0) return (int)rc;
+  FgPlanView v;
+  int e = fg_plan_view(pl, &v);
+  if (!e && hipMemcpyAsync(area, v.src_area, (size_t)v.nsrc * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+    e = fg_fail(FG_ERR_HIP, "fg_coupler_create: copying the cell areas failed");
+  if (!e && hipStreamSynchronize(h->stream) != hipSuccess) e = fg_fail(FG_ERR_HIP, "fg_coupler_create: the cell areas failed");
+  fg_plan_destroy(pl);
+  return e;
+}
+
+static int cp_put_grid(fg_coupler *h, const char *what, int ntiles, const int *nx, const int *ny, const double *const *lon, const double *const *lat,
+                       std::vector<Grid> *out, int *total)
+{
+  if (ntiles < 1 || !nx || !ny || !lon || !lat) return fg_fail(FG_ERR_ARG, "fg_coupler_create: bad %s grid argument", what);
+  long off = 0;
+  for (int t = 0; t < ntiles; t++) {
+    if (nx[t] < 1 || ny[t] < 1 || !lon[t] || !lat[t]) return fg_fail(FG_ERR_ARG, "fg_coupler_create: bad %s tile %d", what, t);
+    Grid g;
+    g.nx = nx[t]; g.ny = ny[t]; g.off = (int)off;
+    const size_t np = (size_t)(nx[t] + 1) * (ny[t] + 1);
+    g.lon = h->dev.put(lon[t], np); g.lat = h->dev.put(lat[t], np);
+    if (!g.lon || !g.lat) return fg_fail(FG_ERR_HIP, "fg_coupler_create: device allocation or upload failed");
+    fg_dst_extents(g.nx, g.ny, lon[t], lat[t], &g.dlat, &g.dlon, &g.rect_hint);
+    off += g.ncells();
+    if (off > (1L << 28)) return fg_fail(FG_ERR_ARG, "fg_coupler_create: the %s grid has more than 2^28 cells", what);
+    out->push_back(g);
+  }
+  *total = (int)off;
+  return 0;
+}
+
+extern "C" int fg_coupler_create(int interp_order, double area_ratio_thresh, int ntile_atm, const int *nxa, const int *nya,
+                                 const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nxl, const int *nyl,
+                                 const double *const *lon_lnd, const double *const *lat_lnd, int nxo, int nyo, const double *lon_ocn,
+                                 const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out)
+{
+  if (!out) return fg_fail(FG_ERR_ARG, "fg_coupler_create: null output handle");
+  *out = nullptr;
+  if (interp_order != 1 && interp_order != 2) return fg_fail(FG_ERR_ARG, "make_coupler_mosaic: interp_order should be 1 or 2");
+  // the searches accept a pair at area / min(area1, area2) > 1e-6 (create_xgrid.c); the coupler's own tests can only reject more
+  // when its threshold is no smaller and the fractions are no larger than 1
+  if (!(area_ratio_thresh >= 1.0e-6)) return fg_fail(FG_ERR_ARG, "fg_coupler_create: area_ratio_thresh %g is below 1e-6, the ratio at which the searches accept a pair", area_ratio_thresh);
+  if (ntile_lnd < 0 || ntile_lnd > CP_MAX_LISTS || ntile_atm > CP_MAX_LISTS)
+    return fg_fail(FG_ERR_ARG, "fg_coupler_create: at most %d atmosphere and land tiles", CP_MAX_LISTS);
+  if (!lon_ocn || !lat_ocn || !omask || nxo < 1 || nyo < 1 || ocn_south_ext < 0 || ocn_south_ext >= nyo)
+    return fg_fail(FG_ERR_ARG, "fg_coupler_create: bad ocean grid argument");
+  for (long c = 0; c < (long)nxo * nyo; c++)
+    if (!(omask[c] >= 0.0 && omask[c] <= 1.0)) return fg_fail(FG_ERR_ARG, "fg_coupler_create: the ocean fraction of cell %ld is %g, outside [0, 1]", c, omask[c]);
+  fg_coupler *h = new fg_coupler;
+  struct Guard { fg_coupler *&h; bool keep = false; ~Guard() { if (!keep) fg_coupler_destroy(h); } } guard{h};
+  h->device = device; h->order = interp_order; h->thresh = area_ratio_thresh; h->south_ext = ocn_south_ext; h->same = ntile_lnd == 0;
+  if (int rc = fg_use_device("fg_coupler_create", device)) return rc;
+  const double t0 = fg_now_ms();
+  FGCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  if (int rc = cp_put_grid(h, "atmosphere", ntile_atm, nxa, nya, lon_atm, lat_atm, &h->atm, &h->na)) return rc;
+  if (h->same) { h->lnd = h->atm; h->nl = h->na; }
+  else if (int rc = cp_put_grid(h, "land", ntile_lnd, nxl, nyl, lon_lnd, lat_lnd, &h->lnd, &h->nl)) return rc;
+  {
+    std::vector<Grid> o;
+    const double *lo[1] = {lon_ocn}, *la[1] = {lat_ocn};
+    if (int rc = cp_put_grid(h, "ocean", 1, &nxo, &nyo, lo, la, &o, &h->no)) return rc;
+    h->ocn = o[0];
+  }
+  std::vector<int> aoff;
+  for (const Grid &g : h->atm) aoff.push_back(g.off);
+  aoff.push_back(h->na);
+  const double dummy[8] = {0, 0.01, 0, 0.01, 0, 0, 0.01, 0.01};
+  const double *d_dummy = h->dev.put(dummy, 8);
+  h->area_atm = h->dev.get<double>(h->na); h->area_ocn = h->dev.get<double>(h->no);
+  h->area_lnd = h->same ? h->area_atm : h->dev.get<double>(h->nl);
+  h->omask = h->dev.put(omask, (size_t)h->no);
+  h->d_aoff = h->dev.put(aoff);
+  if (!d_dummy || !h->area_atm || !h->area_ocn || !h->area_lnd || !h->omask || !h->d_aoff)
+    return fg_fail(FG_ERR_HIP, "fg_coupler_create: device allocation or upload failed");
+  if (int rc = cp_grid_area(h, h->atm, d_dummy, h->area_atm)) return rc;
+  if (!h->same) if (int rc = cp_grid_area(h, h->lnd, d_dummy, h->area_lnd)) return rc;
+  if (int rc = cp_grid_area(h, std::vector<Grid>{h->ocn}, d_dummy, h->area_ocn)) return rc;
+  h->ms[0] = (float)(fg_now_ms() - t0);
+  guard.keep = true;
+  *out = h;
+  return 0;
+}
+
+// --------------------------------------------------------------------------------------------------------------- the run
+namespace {
+struct Run {
+  fg_coupler *h;
+  FgDev &res;
+  hipStream_t st;
+  unsigned *d_err = nullptr;
+  int *d_nbad = nullptr;
+
+  int fetch(void *dst, const void *src, size_t bytes)          // device -> host, counted
+  {
+    FGCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));
+    h->d2h += (long)bytes;
+    return 0;
+  }
+  bool alloc_list(CpList *l, long cap)
+  {
+    *l = CpList{};
+    l->cap = cap;
+    const size_t n = (size_t)(cap > 0 ? cap : 1);
+    l->c1 = res.get<int>(n); l->c2 = res.get<int>(n);
+    l->area = res.get<double>(n); l->clon = res.get<double>(n); l->clat = res.get<double>(n);
+    bool ok = l->c1 && l->c2 && l->area && l->clon && l->clat;
+    for (int q = 0; q < 4; q++) { l->d[q] = res.get<double>(n); ok = ok && l->d[q]; }
+    if (ok) ok = hipMemsetAsync(l->clon, 0, n * sizeof(double), st) == hipSuccess && hipMemsetAsync(l->clat, 0, n * sizeof(double), st) == hipSuccess;
+    return ok;
+  }
+  bool alloc_sums(CpSums *s, long n)
+  {
+    const size_t m = (size_t)(n > 0 ? n : 1);
+    s->area = res.get<double>(m); s->clon = res.get<double>(m); s->clat = res.get<double>(m);
+    if (!s->area || !s->clon || !s->clat) return false;
+    return hipMemsetAsync(s->area, 0, m * sizeof(double), st) == hipSuccess && hipMemsetAsync(s->clon, 0, m * sizeof(double), st) == hipSuccess &&
+           hipMemsetAsync(s->clat, 0, m * sizeof(double), st) == hipSuccess;
+  }
+  // flags -> offsets and the total on the host
+  int scan_total(FgDev &t, long n, const int *flag, int **offs, int *total)
+  {
+    *offs = t.get<int>((size_t)(n > 0 ? n : 1));
+    int *bsum = t.get<int>((size_t)fgd_cp_scan_blocks(n)), *d_tot = t.get<int>(1);
+    if (!*offs || !bsum || !d_tot) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    fgd_cp_scan(n, flag, *offs, bsum, d_tot, st);
+    FGCHK(hipGetLastError());
+    return fetch(total, d_tot, sizeof(int));
+  }
+  long search(int ntiles, const std::vector<Grid> &src, const Grid &dst, fg_plan **pl)
+  {
+    std::vector<int> nx_, ny;
+    std::vector<const double *> lon, lat;
+    for (int t = 0; t < ntiles; t++) { nx_.push_back(src[t].nx); ny.push_back(src[t].ny); lon.push_back(src[t].lon); lat.push_back(src[t].lat); }
+    h->searches++;
+    const long nx = fg_plan_create_dev_hint(h->order, ntiles, nx_.data(), ny.data(), lon.data(), lat.data(), dst.nx, dst.ny, dst.lon, dst.lat, dst.dlat,
+                                            dst.dlon, dst.rect_hint, h->device, st, pl);
+    if (nx >= 0) h->d2h += fg_plan_search_d2h(*pl);
+    return nx;
+  }
+  int check_err()
+  {
+    unsigned e = 0;
+    if (int rc = fetch(&e, d_err, sizeof e)) return rc;
+    if (e & CP_ERR_NVERT) return fg_fail(FG_ERR_GEOM, "make_coupler_mosaic: inconsistent number of grid box coreners");
+    if (e & CP_ERR_MAXV) return fg_fail(FG_ERR_GEOM, "fg_coupler_run: an atmosphere x land polygon has more than 8 vertices");
+    return 0;
+  }
+
+  bool alloc_cand(Cand *c, long n)
+  {
+    const size_t m = (size_t)(n > 0 ? n : 1);
+    c->pa = res.get<int>(m); c->pl = res.get<int>(m); c->pn = res.get<int>(m);
+    c->plon = res.get<double>(m * 8); c->plat = res.get<double>(m * 8); c->lon_avg = res.get<double>(m); c->area_ref = res.get<double>(m);
+    return c->pa && c->pl && c->pn && c->plon && c->plat && c->lon_avg && c->area_ref;
+  }
+  // :1463-1477 for the cells of atmosphere tile t
+  int cand_same(int t, Cand *c)
+  {
+    const Grid &g = h->atm[t];
+    const long n = g.ncells();
+    FgDev tmp;
+    int *flag = tmp.get<int>((size_t)n), *offs = nullptr, total = 0;
+    if (!flag) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    const double *area = h->area_atm + g.off;
+    fgd_cp_same_flag(g.nx, g.ny, g.lon, g.lat, area, h->thresh, flag, d_err, st);
+    if (int rc = scan_total(tmp, n, flag, &offs, &total)) return rc;
+    if (!alloc_cand(c, total)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    c->n = total;
+    fgd_cp_same_emit(g.nx, g.ny, g.lon, g.lat, area, flag, offs, g.off, c->pa, c->pl, c->pn, c->plon, c->plat, c->lon_avg, c->area_ref, d_err, st);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  // :1396-1551 for land tile t of its own: a search, its polygons, the coupler's ratio test
+  int cand_own(int t, Cand *c)
+  {
+    const Grid &g = h->lnd[t];
+    fg_plan *pl = nullptr;
+    const long nx = search((int)h->atm.size(), h->atm, g, &pl);
+    if (nx < 0) return (int)nx;
+    struct Destroy { fg_plan *p; ~Destroy() { fg_plan_destroy(p); } } destroy{pl};
+    FgPlanView v;
+    if (int rc = fg_plan_view(pl, &v)) return rc;
+    FgDev tmp;
+    const size_t m = (size_t)(nx > 0 ? nx : 1);
+    int *flag = tmp.get<int>(m), *pn = tmp.get<int>(m), *offs = nullptr, total = 0;
+    double *plon = tmp.get<double>(m * 8), *plat = tmp.get<double>(m * 8);
+    if (!flag || !pn || !plon || !plat) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    const double *area_lnd = h->area_lnd + g.off;
+    if (nx > 0) if (int rc = fg_plan_polygons_dev(pl, pn, plon, plat)) return rc;
+    fgd_cp_cand_flag(nx, v.x_src, v.x_dst, v.x_area, h->area_atm, area_lnd, h->thresh, flag, st);
+    if (int rc = scan_total(tmp, nx, flag, &offs, &total)) return rc;
+    if (!alloc_cand(c, total)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    c->n = total;
+    fgd_cp_cand_emit(nx, v.x_src, v.x_dst, flag, offs, pn, plon, plat, v.src_lon_avg, h->area_atm, area_lnd, c->pa, c->pl, c->pn, c->plon, c->plat,
+                     c->lon_avg, c->area_ref, d_err, st);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  // :1604-1661 (src = the atmosphere) and :2598-2690 (src = one land tile): the search, the ocean-fraction tests, the survivors
+  int ocean_list(int ntiles, const std::vector<Grid> &src, const double *area_src, CpList *out)
+  {
+    fg_plan *pl = nullptr;
+    const long nx = search(ntiles, src, h->ocn, &pl);
+    if (nx < 0) return (int)nx;
+    struct Destroy { fg_plan *p; ~Destroy() { fg_plan_destroy(p); } } destroy{pl};
+    FgPlanView v;
+    if (int rc = fg_plan_view(pl, &v)) return rc;
+    FgDev tmp;
+    int *flag = tmp.get<int>((size_t)(nx > 0 ? nx : 1)), *offs = nullptr, total = 0;
+    if (!flag) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    fgd_cp_ocean_flag(nx, v.x_src, v.x_dst, v.x_area, h->omask, h->area_ocn, area_src, h->thresh, flag, st);
+    if (int rc = scan_total(tmp, nx, flag, &offs, &total)) return rc;
+    if (!alloc_list(out, total)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    out->n = total;
+    fgd_cp_ocean_emit(nx, v.x_src, v.x_dst, v.x_area, v.x_c1, v.x_c2, h->omask, flag, offs, *out, st);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  // :1662-1719: the remembered polygons against the ocean cells over land, the sums per polygon, the final area test
+  int poly_list(const Cand &c, CpList *out)
+  {
+    if (c.n == 0) { if (!alloc_list(out, 0)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory"); return 0; }
+    fg_plan *pl = nullptr;
+    h->searches++;
+    const Grid &o = h->ocn;
+    const long nx = fg_plan_create_polylist_dev(h->order, c.n, c.pn, c.plon, c.plat, c.lon_avg, c.area_ref, o.nx, o.ny, o.lon, o.lat, o.dlat, o.dlon,
+                                                o.rect_hint, h->device, st, &pl);
+    if (nx == FG_ERR_MAXV) return fg_fail(FG_ERR_GEOM, "fg_coupler_run: an atmosphere x land polygon has more than 8 vertices");
+    if (nx < 0) return (int)nx;
+    struct Destroy { fg_plan *p; ~Destroy() { fg_plan_destroy(p); } } destroy{pl};
+    h->d2h += fg_plan_search_d2h(pl);
+    FgPlanView v;
+    if (int rc = fg_plan_view(pl, &v)) return rc;
+    FgDev tmp;
+    const size_t m = (size_t)c.n;
+    double *s_area = tmp.get<double>(m), *s_clon = tmp.get<double>(m), *s_clat = tmp.get<double>(m);
+    int *flag = tmp.get<int>(m), *offs = nullptr, total = 0;
+    if (!s_area || !s_clon || !s_clat || !flag) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    fgd_cp_poly_sums(c.n, nx, v.x_src, v.x_dst, v.x_area, v.x_c1, v.x_c2, h->omask, c.area_ref, h->thresh, s_area, s_clon, s_clat, flag, st);
+    if (int rc = scan_total(tmp, c.n, flag, &offs, &total)) return rc;
+    if (!alloc_list(out, total)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    out->n = total;
+    fgd_cp_poly_emit(c.n, c.pa, c.pl, s_area, s_clon, s_clat, flag, offs, *out, st);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  // the terms of a list onto the cells of its first (which = 1) or second grid, in list order
+  int row_sums(const CpList &l, int which, long ncells, CpSums s)
+  {
+    if (l.n == 0) return 0;
+    FgDev tmp;
+    int *cnt = tmp.get<int>((size_t)ncells), *fill = tmp.get<int>((size_t)ncells), *rowptr = tmp.get<int>((size_t)ncells), *perm = tmp.get<int>((size_t)l.n);
+    int *bsum = tmp.get<int>((size_t)fgd_cp_scan_blocks(ncells)), *d_tot = tmp.get<int>(1);
+    if (!cnt || !fill || !rowptr || !perm || !bsum || !d_tot) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    FGCHK(hipMemsetAsync(cnt, 0, (size_t)ncells * sizeof(int), st));
+    FGCHK(hipMemsetAsync(fill, 0, (size_t)ncells * sizeof(int), st));
+    const int *key = which == 1 ? l.c1 : l.c2;
+    fgd_cp_row_count(l.n, key, cnt, st);
+    fgd_cp_scan(ncells, cnt, rowptr, bsum, d_tot, st);
+    fgd_cp_row_fill(l.n, key, rowptr, fill, perm, st);
+    fgd_cp_row_sums((int)ncells, rowptr, cnt, perm, l.area, l.clon, l.clat, h->order, s, st);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  int tile_starts(const CpList &l, std::vector<int> *starts)
+  {
+    const int nt = (int)h->atm.size();
+    FgDev tmp;
+    int *d = tmp.get<int>((size_t)nt + 1);
+    if (!d) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    fgd_cp_tile_starts(nt, h->d_aoff, l.n, l.c1, d, st);
+    FGCHK(hipGetLastError());
+    starts->resize((size_t)nt + 1);
+    return fetch(starts->data(), d, ((size_t)nt + 1) * sizeof(int));
+  }
+
+  int go()
+  {
+    const int ntl = (int)h->lnd.size();
+    d_err = res.get<unsigned>(1); d_nbad = res.get<int>(1);
+    if (!d_err || !d_nbad) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    FGCHK(hipMemsetAsync(d_err, 0, sizeof(unsigned), st));
+    FGCHK(hipMemsetAsync(d_nbad, 0, sizeof(int), st));
+    double t0 = fg_now_ms();
+    // 2. atmosphere x land candidates
+    std::vector<Cand> cand(ntl);
+    for (int t = 0; t < ntl; t++) {
+      if (int rc = h->same ? cand_same(t, &cand[t]) : cand_own(t, &cand[t])) return rc;
+      h->ncand += cand[t].n;
+    }
+    if (int rc = check_err()) return rc;
+    double t1 = fg_now_ms(); h->ms[1] = (float)(t1 - t0); t0 = t1;
+    // 3. atmosphere x ocean over sea
+    if (int rc = ocean_list((int)h->atm.size(), h->atm, h->area_atm, &h->axo)) return rc;
+    t1 = fg_now_ms(); h->ms[2] = (float)(t1 - t0); t0 = t1;
+    // 4. the remembered polygons x ocean over land
+    h->axl.assign(ntl, CpList{});
+    for (int t = 0; t < ntl; t++) if (int rc = poly_list(cand[t], &h->axl[t])) return rc;
+    t1 = fg_now_ms(); h->ms[3] = (float)(t1 - t0); t0 = t1;
+    // 5. land x ocean
+    h->lxo.assign(h->same ? 0 : ntl, CpList{});
+    for (size_t t = 0; t < h->lxo.size(); t++)
+      if (int rc = ocean_list(1, std::vector<Grid>{h->lnd[t]}, h->area_lnd + h->lnd[t].off, &h->lxo[t])) return rc;
+    t1 = fg_now_ms(); h->ms[4] = (float)(t1 - t0); t0 = t1;
+    // 6. per-cell sums
+    if (!alloc_sums(&h->a, h->na) || !alloc_sums(&h->l, h->nl) || !alloc_sums(&h->o, h->no) || !alloc_sums(&h->l2, h->nl) || !alloc_sums(&h->o2, h->no))
+      return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    h->a_frac = res.get<double>((size_t)h->na); h->l_frac = res.get<double>((size_t)h->nl); h->o_frac = res.get<double>((size_t)h->no);
+    if (!h->a_frac || !h->l_frac || !h->o_frac) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    CpListRefs refs;
+    refs.count = 0;
+    for (int t = 0; t < ntl; t++) refs.l[refs.count++] = CpListRef{h->axl[t].c1, h->axl[t].area, h->axl[t].clon, h->axl[t].clat, h->axl[t].n};
+    refs.l[refs.count++] = CpListRef{h->axo.c1, h->axo.area, h->axo.clon, h->axo.clat, h->axo.n};
+    fgd_cp_a_sums(h->na, refs, h->order, h->a, st);
+    FGCHK(hipGetLastError());
+    auto tile = [](CpSums s, int off) { return CpSums{s.area + off, s.clon + off, s.clat + off}; };
+    for (int t = 0; t < ntl; t++) if (int rc = row_sums(h->axl[t], 2, h->lnd[t].ncells(), tile(h->l, h->lnd[t].off))) return rc;
+    if (int rc = row_sums(h->axo, 2, h->no, h->o)) return rc;
+    for (size_t t = 0; t < h->lxo.size(); t++) {
+      if (int rc = row_sums(h->lxo[t], 1, h->lnd[t].ncells(), tile(h->l2, h->lnd[t].off))) return rc;
+      if (int rc = row_sums(h->lxo[t], 2, h->no, h->o2)) return rc;
+    }
+    if (h->order == 2) {
+      // 7. centroids where the area is > 0, then the distances
+      fgd_cp_centroid(h->nl, h->l, st); fgd_cp_centroid(h->no, h->o, st);
+      fgd_cp_centroid(h->nl, h->l2, st); fgd_cp_centroid(h->no, h->o2, st);
+      for (int t = 0; t < ntl; t++) fgd_cp_distances(h->axl[t], h->a, tile(h->l, h->lnd[t].off), st);
+      fgd_cp_distances(h->axo, h->a, h->o, st);
+      for (size_t t = 0; t < h->lxo.size(); t++) fgd_cp_distances(h->lxo[t], tile(h->l2, h->lnd[t].off), h->o2, st);
+    }
+    // 8. masks
+    fgd_cp_fraction(h->na, h->a.area, h->area_atm, nullptr, 0, h->a_frac, nullptr, st);
+    fgd_cp_fraction(h->nl, h->l.area, h->area_lnd, nullptr, 0, h->l_frac, nullptr, st);
+    fgd_cp_fraction(h->no, h->o.area, h->area_ocn, h->omask, h->south_ext * h->ocn.nx, h->o_frac, d_nbad, st);
+    FGCHK(hipGetLastError());
+    if (int rc = fetch(&h->nbad, d_nbad, sizeof(int))) return rc;
+    // where the tiles begin in the atmosphere-major lists
+    h->axl_start.assign(ntl, std::vector<int>());
+    for (int t = 0; t < ntl; t++) if (int rc = tile_starts(h->axl[t], &h->axl_start[t])) return rc;
+    if (int rc = tile_starts(h->axo, &h->axo_start)) return rc;
+    h->ms[5] = (float)(fg_now_ms() - t0);
+    return 0;
+  }
+};
+}  // namespace
+
+extern "C" int fg_coupler_run(fg_coupler *h)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_coupler_run: null handle");
+  FGCHK(hipSetDevice(h->device));
+  FGCHK(hipStreamSynchronize(h->stream));
+  const double t0 = fg_now_ms();
+  h->ran = false;
+  h->res.reset(new FgDev);
+  h->d2h = 0; h->searches = 0; h->ncand = 0; h->nbad = 0;
+  Run r{h, *h->res, h->stream};
+  const int saved = fg_search_frame_override(1);          // fix_lon(cell, xa_avg) per pair (:1455, :1597, :2652), for this thread's searches only
+  const int rc = r.go();
+  fg_search_frame_override(saved);
+  if (rc) { (void)hipStreamSynchronize(h->stream); h->res.reset(); return rc; }
+  h->ran = true;
+  h->ms[6] = (float)(fg_now_ms() - t0);
+  return 0;
+}
+
+// which: 0 atmosphere x land (tile1 = atmosphere tile, tile2 = land tile), 1 atmosphere x ocean (tile1), 2 land x ocean (tile1 = land tile)
+static int cp_pick(const fg_coupler *h, const char *who, int which, int t1, int t2, const CpList **l, long *k0, long *n, int *off1, int *nx1, int *nx2)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "%s: null handle", who);
+  if (!h->ran) return fg_fail(FG_ERR_STATE, "%s: fg_coupler_run has not run on this handle", who);
+  const int nta = (int)h->atm.size(), ntl = (int)h->lnd.size();
+  if (which == 0) {
+    if (t1 < 0 || t1 >= nta || t2 < 0 || t2 >= ntl) return fg_fail(FG_ERR_ARG, "%s: no atmosphere tile %d x land tile %d", who, t1, t2);
+    *l = &h->axl[t2]; *k0 = h->axl_start[t2][t1]; *n = h->axl_start[t2][t1 + 1] - *k0;
+    *off1 = h->atm[t1].off; *nx1 = h->atm[t1].nx; *nx2 = h->lnd[t2].nx;
+  } else if (which == 1) {
+    if (t1 < 0 || t1 >= nta || t2 != 0) return fg_fail(FG_ERR_ARG, "%s: no atmosphere tile %d x ocean tile %d", who, t1, t2);
+    *l = &h->axo; *k0 = h->axo_start[t1]; *n = h->axo_start[t1 + 1] - *k0;
+    *off1 = h->atm[t1].off; *nx1 = h->atm[t1].nx; *nx2 = h->ocn.nx;
+  } else if (which == 2) {
+    if (t2 != 0 || t1 < 0 || (!h->same && t1 >= ntl)) return fg_fail(FG_ERR_ARG, "%s: no land tile %d x ocean tile %d", who, t1, t2);
+    if (h->same) return fg_fail(FG_ERR_ARG, "%s: land is on the atmosphere grid: there is no land x ocean list", who);
+    *l = &h->lxo[t1]; *k0 = 0; *n = h->lxo[t1].n;
+    *off1 = 0; *nx1 = h->lnd[t1].nx; *nx2 = h->ocn.nx;
+  } else return fg_fail(FG_ERR_ARG, "%s: which must be 0 (atmosphere x land), 1 (atmosphere x ocean) or 2 (land x ocean)", who);
+  return 0;
+}
+
+extern "C" long fg_coupler_count(const fg_coupler *h, int which, int tile1, int tile2)
+{
+  const CpList *l; long k0, n; int off1, nx1, nx2;
+  if (int rc = cp_pick(h, "fg_coupler_count", which, tile1, tile2, &l, &k0, &n, &off1, &nx1, &nx2)) return rc;
+  return n;
+}
+
+extern "C" int fg_coupler_get(const fg_coupler *h, int which, int tile1, int tile2, int *i1, int *j1, int *i2, int *j2, double *area, double *clon,
+                              double *clat, double *di1, double *dj1, double *di2, double *dj2)
+{
+  const CpList *l; long k0, n; int off1, nx1, nx2;
+  if (int rc = cp_pick(h, "fg_coupler_get", which, tile1, tile2, &l, &k0, &n, &off1, &nx1, &nx2)) return rc;
+  if (h->order != 2 && (clon || clat || di1 || dj1 || di2 || dj2)) return fg_fail(FG_ERR_ARG, "fg_coupler_get: centroids and distances need interp_order 2");
+  if (n == 0) return 0;
+  FGCHK(hipSetDevice(h->device));
+  if (i1 || j1 || i2 || j2) {
+    FgDev tmp;
+    int *d = tmp.get<int>(4 * (size_t)n);
+    if (!d) return fg_fail(FG_ERR_HIP, "fg_coupler_get: out of device memory");
+    fgd_cp_indices(n, l->c1 + k0, l->c2 + k0, off1, nx1, nx2, d, d + n, d + 2 * n, d + 3 * n, h->stream);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(h->stream));
+    int *dst[4] = {i1, j1, i2, j2};
+    for (int q = 0; q < 4; q++) if (dst[q]) FGCHK(hipMemcpy(dst[q], d + (size_t)q * n, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  const double *src[7] = {l->area, l->clon, l->clat, l->d[0], l->d[1], l->d[2], l->d[3]};
+  double *dst[7] = {area, clon, clat, di1, dj1, di2, dj2};
+  for (int q = 0; q < 7; q++) if (dst[q]) FGCHK(hipMemcpy(dst[q], src[q] + k0, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// grid: 0 atmosphere, 1 land, 2 ocean (tile 0).  model_area: get_grid_area; xarea: the exchange-cell area the cell collected
+// (a_area, l_area, o_area); frac = xarea / model_area (the land and ocean masks of :2037, :2089); clon / clat: the cell's centroid
+// (order 2; the plain sums where xarea is not > 0)
+extern "C" int fg_coupler_get_cells(const fg_coupler *h, int grid, int tile, double *model_area, double *xarea, double *frac, double *clon, double *clat)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_coupler_get_cells: null handle");
+  if (!h->ran) return fg_fail(FG_ERR_STATE, "fg_coupler_get_cells: fg_coupler_run has not run on this handle");
+  const std::vector<Grid> one{h->ocn};
+  const std::vector<Grid> &g = grid == 0 ? h->atm : (grid == 1 ? h->lnd : one);
+  if (grid < 0 || grid > 2 || tile < 0 || tile >= (int)g.size()) return fg_fail(FG_ERR_ARG, "fg_coupler_get_cells: no tile %d of grid %d", tile, grid);
+  if (h->order != 2 && (clon || clat)) return fg_fail(FG_ERR_ARG, "fg_coupler_get_cells: centroids need interp_order 2");
+  const int off = grid == 2 ? 0 : g[tile].off;
+  const size_t bytes = (size_t)g[tile].ncells() * sizeof(double);
+  const CpSums &s = grid == 0 ? h->a : (grid == 1 ? h->l : h->o);
+  const double *src[5] = {grid == 0 ? h->area_atm : (grid == 1 ? h->area_lnd : h->area_ocn), s.area, grid == 0 ? h->a_frac : (grid == 1 ? h->l_frac : h->o_frac),
+                          s.clon, s.clat};
+  double *dst[5] = {model_area, xarea, frac, clon, clat};
+  FGCHK(hipSetDevice(h->device));
+  for (int q = 0; q < 5; q++) if (dst[q]) FGCHK(hipMemcpy(dst[q], src[q] + off, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// s: [0] bytes fg_coupler_run brought to the host  [1] nbad (:2038)  [2] searches  [3] atmosphere x ocean cells  [4] atmosphere x land
+// cells  [5] land x ocean cells  [6] remembered atmosphere x land polygons  [7] ocn_south_ext
+extern "C" int fg_coupler_stats(const fg_coupler *h, long *s, int n)
+{
+  if (!h || !s || n < 0) return fg_fail(FG_ERR_ARG, "fg_coupler_stats: bad argument");
+  long naxl = 0, nlxo = 0;
+  for (const CpList &l : h->axl) naxl += l.n;
+  for (const CpList &l : h->lxo) nlxo += l.n;
+  const long v[8] = {h->d2h, h->nbad, h->searches, h->ran ? h->axo.n : 0, h->ran ? naxl : 0, h->ran ? nlxo : 0, h->ncand, h->south_ext};
+  for (int k = 0; k < n && k < 8; k++) s[k] = v[k];
+  return 0;
+}
+
+extern "C" int fg_coupler_phase_ms(const fg_coupler *h, float *ms, int n)
+{
+  if (!h || !ms || n < 0) return fg_fail(FG_ERR_ARG, "fg_coupler_phase_ms: bad argument");
+  for (int k = 0; k < n && k < 7; k++) ms[k] = h->ms[k];
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------- the files
+namespace {
+enum { CP_NC_CHAR = 2, CP_NC_INT = 4, CP_NC_DOUBLE = 6, CP_STRING = 255 };      // netcdf.h's codes; mpp.h's STRING
+struct NcClose { fg_ncfile *f = nullptr; ~NcClose() { if (f) (void)fg_nc_close(f); } };
+int nc_fail(const char *what) { return fg_fail(FG_ERR_IO, "fg_coupler_write: %s: %s", what, fg_nc_last_error()); }
+int nc_var(fg_ncfile *f, const char *name, int type, int ndims, const int *dims, std::initializer_list<std::pair<const char *, const char *>> atts)
+{
+  const int v = fg_nc_def_var(f, name, type, ndims, dims);
+  if (v < 0) return v;
+  for (const auto &a : atts) if (fg_nc_put_att_text(f, v, a.first, a.second) < 0) return -1;
+  return v;
+}
+}  // namespace
+
+// One exchange-grid file from host arrays (:2158-2244, :2277-2370, :2840-2920): 0-based (i, j) of the two grids' cells, written as
+// i + 1, j1 + 1, j2 + j2_shift (1, or 1 - ocn_south_ext for an ocean second grid: :2309, :2876); di1 .. dj2 all given (order 2) or all NULL.
+extern "C" int fg_coupler_write_xgrid(const char *path_, const char *contact_, long n, const int *i1, const int *j1, const int *i2, const int *j2,
+                                      int j2_shift, const double *area_, const double *di1, const double *dj1, const double *di2, const double *dj2)
+{
+  if (!path_ || !contact_ || n < 1 || !i1 || !j1 || !i2 || !j2 || !area_) return fg_fail(FG_ERR_ARG, "fg_coupler_write_xgrid: bad argument (an empty list gets no file)");
+  const bool o2 = di1 != nullptr;
+  if ((dj1 != nullptr) != o2 || (di2 != nullptr) != o2 || (dj2 != nullptr) != o2) return fg_fail(FG_ERR_ARG, "fg_coupler_write_xgrid: four distance arrays or none");
+  const std::string path(path_), contact(contact_);
+  const int *idx[4] = {i1, j1, i2, j2};
+  const double *d[4] = {di1, dj1, di2, dj2}, *area = area_;
+  std::vector<int> cell(2 * (size_t)n);
+  std::vector<double> pair(o2 ? 2 * (size_t)n : 0);
+  NcClose c;
+  if (fg_nc_create(path.c_str(), 2, &c.f) < 0) return nc_fail(path.c_str());
+  fg_ncfile *f = c.f;
+  const int d_str = fg_nc_def_dim(f, "string", CP_STRING), d_n = fg_nc_def_dim(f, "ncells", n), d_two = fg_nc_def_dim(f, "two", 2);
+  if (d_str < 0 || d_n < 0 || d_two < 0) return nc_fail("dimensions");
+  const int dims[2] = {d_n, d_two};
+  const int v_contact = o2
+    ? nc_var(f, "contact", CP_NC_CHAR, 1, &d_str, {{"standard_name", "grid_contact_spec"}, {"contact_type", "exchange"}, {"parent1_cell", "tile1_cell"},
+             {"parent2_cell", "tile2_cell"}, {"xgrid_area_field", "xgrid_area"}, {"distant_to_parent1_centroid", "tile1_distance"},
+             {"distant_to_parent2_centroid", "tile2_distance"}})
+    : nc_var(f, "contact", CP_NC_CHAR, 1, &d_str, {{"standard_name", "grid_contact_spec"}, {"contact_type", "exchange"}, {"parent1_cell", "tile1_cell"},
+             {"parent2_cell", "tile2_cell"}, {"xgrid_area_field", "xgrid_area"}});
+  const int v_t1 = nc_var(f, "tile1_cell", CP_NC_INT, 2, dims, {{"standard_name", "parent_cell_indices_in_mosaic1"}});
+  const int v_t2 = nc_var(f, "tile2_cell", CP_NC_INT, 2, dims, {{"standard_name", "parent_cell_indices_in_mosaic2"}});
+  const int v_area = nc_var(f, "xgrid_area", CP_NC_DOUBLE, 1, &d_n, {{"standard_name", "exchange_grid_area"}, {"units", "m2"}});
+  int v_d1 = 0, v_d2 = 0;
+  if (o2) {
+    v_d1 = nc_var(f, "tile1_distance", CP_NC_DOUBLE, 2, dims, {{"standard_name", "distance_from_parent1_cell_centroid"}});
+    v_d2 = nc_var(f, "tile2_distance", CP_NC_DOUBLE, 2, dims, {{"standard_name", "distance_from_parent2_cell_centroid"}});
+  }
+  if (v_contact < 0 || v_t1 < 0 || v_t2 < 0 || v_area < 0 || v_d1 < 0 || v_d2 < 0 || fg_nc_enddef(f) < 0) return nc_fail("definitions");
+  const long s0[2] = {0, 0}, c_all[2] = {n, 2}, c_text[1] = {CP_STRING};
+  char text[CP_STRING] = {0};
+  memcpy(text, contact.c_str(), std::min<size_t>(contact.size(), CP_STRING));
+  bool ok = fg_nc_put_vara(f, v_contact, s0, c_text, text) >= 0;
+  for (long k = 0; k < n; k++) { cell[2 * k] = idx[0][k] + 1; cell[2 * k + 1] = idx[1][k] + 1; }                  // :2185-2190: Fortran indices
+  ok = ok && fg_nc_put_vara(f, v_t1, s0, c_all, cell.data()) >= 0;
+  for (long k = 0; k < n; k++) { cell[2 * k] = idx[2][k] + 1; cell[2 * k + 1] = idx[3][k] + j2_shift; }
+  ok = ok && fg_nc_put_vara(f, v_t2, s0, c_all, cell.data()) >= 0;
+  ok = ok && fg_nc_put_vara(f, v_area, s0, c_all, area) >= 0;
+  if (o2) {
+    for (long k = 0; k < n; k++) { pair[2 * k] = d[0][k]; pair[2 * k + 1] = d[1][k]; }
+    ok = ok && fg_nc_put_vara(f, v_d1, s0, c_all, pair.data()) >= 0;
+    for (long k = 0; k < n; k++) { pair[2 * k] = d[2][k]; pair[2 * k + 1] = d[3][k]; }
+    ok = ok && fg_nc_put_vara(f, v_d2, s0, c_all, pair.data()) >= 0;
+  }
+  if (!ok) return nc_fail("data");
+  fg_ncfile *g = c.f; c.f = nullptr;
+  return fg_nc_close(g) < 0 ? nc_fail("close") : 0;
+}
+
+// one list of the handle into its file; nothing for an empty list (:2136)
+static int cp_write_xgrid(const fg_coupler *h, const std::string &path, const std::string &contact, int which, int t1, int t2, int j2_shift)
+{
+  const long n = fg_coupler_count(h, which, t1, t2);
+  if (n <= 0) return (int)n;
+  const bool o2 = h->order == 2;
+  std::vector<int> idx(4 * (size_t)n);
+  std::vector<double> area((size_t)n), d(o2 ? 4 * (size_t)n : 0);
+  double *dp[4] = {o2 ? d.data() : nullptr, o2 ? d.data() + n : nullptr, o2 ? d.data() + 2 * n : nullptr, o2 ? d.data() + 3 * n : nullptr};
+  if (int rc = fg_coupler_get(h, which, t1, t2, idx.data(), idx.data() + n, idx.data() + 2 * n, idx.data() + 3 * n, area.data(), nullptr, nullptr, dp[0], dp[1],
+                              dp[2], dp[3]))
+    return rc;
+  return fg_coupler_write_xgrid(path.c_str(), contact.c_str(), n, idx.data(), idx.data() + n, idx.data() + 2 * n, idx.data() + 3 * n, j2_shift, area.data(),
+                                dp[0], dp[1], dp[2], dp[3]);
+}
+
+// ocean_mask.nc (:2055-2066) / land_mask[_tileN].nc (:2103-2117): [ny][nx] doubles, `fields` = {name, standard_name, data}
+namespace { struct MaskField { const char *name, *std; const double *data; }; }
+static int cp_write_mask(const std::string &path, int nx, int ny, std::initializer_list<MaskField> fields)
+{
+  NcClose c;
+  if (fg_nc_create(path.c_str(), 2, &c.f) < 0) return nc_fail(path.c_str());
+  fg_ncfile *f = c.f;
+  int dims[2];
+  dims[1] = fg_nc_def_dim(f, "nx", nx);
+  dims[0] = fg_nc_def_dim(f, "ny", ny);
+  if (dims[0] < 0 || dims[1] < 0) return nc_fail("dimensions");
+  std::vector<int> ids;
+  for (const MaskField &m : fields) {
+    if (!m.data) { ids.push_back(-1); continue; }
+    const int v = nc_var(f, m.name, CP_NC_DOUBLE, 2, dims, {{"standard_name", m.std}, {"units", "none"}});
+    if (v < 0) return nc_fail("definitions");
+    ids.push_back(v);
+  }
+  if (fg_nc_enddef(f) < 0) return nc_fail("definitions");
+  const long s0[2] = {0, 0}, cnt[2] = {ny, nx};
+  size_t k = 0;
+  for (const MaskField &m : fields) { if (m.data && fg_nc_put_vara(f, ids[k], s0, cnt, m.data) < 0) return nc_fail("data"); k++; }
+  fg_ncfile *g = c.f; c.f = nullptr;
+  return fg_nc_close(g) < 0 ? nc_fail("close") : 0;
+}
+
+// names: NULL, or [0] atmosphere, [1] land, [2] ocean mosaic name, then the atmosphere tiles' names, the land tiles' names (as many as
+// the handle has land tiles: the atmosphere's count when land is on its grid) and the ocean tile's name; a NULL entry or a NULL table
+// gives "atmos_mosaic", "land_mosaic", "ocean_mosaic", "tile<k>".
+extern "C" int fg_coupler_write(const fg_coupler *h, const char *directory, const char *const *names)
+{
+  if (!h || !directory) return fg_fail(FG_ERR_ARG, "fg_coupler_write: bad argument");
+  if (!h->ran) return fg_fail(FG_ERR_STATE, "fg_coupler_write: fg_coupler_run has not run on this handle");
+  const int nta = (int)h->atm.size(), ntl = (int)h->lnd.size();
+  auto name = [&](int k, const std::string &dflt) { return std::string(names && names[k] ? names[k] : dflt.c_str()); };
+  const std::string dir = std::string(directory) + "/", am = name(0, "atmos_mosaic"), lm = name(1, "land_mosaic"), omn = name(2, "ocean_mosaic");
+  std::vector<std::string> at, lt;
+  for (int t = 0; t < nta; t++) at.push_back(name(3 + t, "tile" + std::to_string(t + 1)));
+  for (int t = 0; t < ntl; t++) lt.push_back(name(3 + nta + t, "tile" + std::to_string(t + 1)));
+  const std::string ot = name(3 + nta + ntl, "tile1");
+  const int shift = 1 - h->south_ext;
+  for (int ta = 0; ta < nta; ta++) {
+    for (int tl = 0; tl < ntl; tl++)
+      if (int rc = cp_write_xgrid(h, dir + am + "_" + at[ta] + "X" + lm + "_" + lt[tl] + ".nc", am + ":" + at[ta] + "::" + lm + ":" + lt[tl], 0, ta, tl, 1)) return rc;
+    if (int rc = cp_write_xgrid(h, dir + am + "_" + at[ta] + "X" + omn + "_" + ot + ".nc", am + ":" + at[ta] + "::" + omn + ":" + ot, 1, ta, 0, shift)) return rc;
+  }
+  if (!h->same)
+    for (int tl = 0; tl < ntl; tl++)
+      if (int rc = cp_write_xgrid(h, dir + lm + "_" + lt[tl] + "X" + omn + "_" + ot + ".nc", lm + ":" + lt[tl] + "::" + omn + ":" + ot, 2, tl, 0, shift)) return rc;
+  {
+    const size_t n = (size_t)h->no, skip = (size_t)h->south_ext * h->ocn.nx;
+    std::vector<double> area(n), xarea(n), frac(n);
+    if (int rc = fg_coupler_get_cells(h, 2, 0, area.data(), xarea.data(), frac.data(), nullptr, nullptr)) return rc;
+    if (int rc = fg_coupler_write_mask((dir + "ocean_mask.nc").c_str(), 1, h->ocn.nx, h->ocn.ny - h->south_ext, frac.data() + skip, area.data() + skip,
+                                       xarea.data() + skip, nullptr)) return rc;
+  }
+  for (int tl = 0; tl < ntl; tl++) {
+    const Grid &g = h->lnd[tl];
+    const size_t n = (size_t)g.ncells();
+    std::vector<double> area(n), xarea(n), frac(n), aatm;
+    if (int rc = fg_coupler_get_cells(h, 1, tl, area.data(), xarea.data(), frac.data(), nullptr, nullptr)) return rc;
+    if (h->same) {                       // (with land of its own the reference indexes area_atm with the land tile, :2094: left out)
+      aatm.resize(n);
+      if (int rc = fg_coupler_get_cells(h, 0, tl, aatm.data(), nullptr, nullptr, nullptr, nullptr)) return rc;
+    }
+    const std::string file = ntl > 1 ? "land_mask_tile" + std::to_string(tl + 1) + ".nc" : std::string("land_mask.nc");
+    if (int rc = fg_coupler_write_mask((dir + file).c_str(), 0, g.nx, g.ny, frac.data(), area.data(), xarea.data(), h->same ? aatm.data() : nullptr)) return rc;
+  }
+  return 0;
+}
+
+// ocean_mask.nc (ocean != 0: a = areaO, b = areaX) or a land mask file (a = area_lnd, b = l_area, area_atm or NULL) from host arrays [ny][nx]
+extern "C" int fg_coupler_write_mask(const char *path, int ocean, int nx, int ny, const double *mask, const double *a, const double *b, const double *area_atm)
+{
+  if (!path || nx < 1 || ny < 1 || !mask || !a || !b) return fg_fail(FG_ERR_ARG, "fg_coupler_write_mask: bad argument");
+  if (ocean) return cp_write_mask(path, nx, ny, {{"mask", "ocean fraction at T-cell centers", mask}, {"areaO", "ocean grid area", a}, {"areaX", "ocean exchange grid area", b}});
+  return cp_write_mask(path, nx, ny, {{"mask", "land fraction at T-cell centers", mask}, {"area_atm", "area atm ", area_atm}, {"area_lnd", "area land ", a},
+                                      {"l_area", "land x area", b}});
+}

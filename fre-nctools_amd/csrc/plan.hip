@@ -17,6 +17,7 @@
 #include <type_traits>
 #include <vector>
 #include "fg_host.h"
+#include "plan_internal.h"
 #include "xgrid_device.h"
 
 // ----------------------------------------------------------------------------- errors
@@ -410,6 +411,7 @@ struct fg_plan {
   double *il_m = nullptr;                                        // order 2: merged records [source cell][3][8] (k_merge3)
   unsigned char *lv_bits = nullptr;                              // order 2, fg_plan_apply_levels: gradient-mask bits per source cell
   long stats[FG_NSTATS] = {0};
+  long search_d2h = 0;           // bytes the search read back: one counter block per attempt
   // monotone limiter scratch (fg_plan_mono_*): limited values per CSR entry, per-source-cell bounds, error word
   double *mono_x = nullptr, *mono_b = nullptr;     // mono_b: [4][nsrc] = f_bar_max | f_bar_min | f_max | f_min
   int *xerr = nullptr;
@@ -583,6 +585,7 @@ extern "C" void fg_set_search_rect(int on) { g_search_rect = on ? 1 : 0; }
 // NaN (every comparison of fix_lon's last step is then false), the per-pair shift is the same code.
 static int g_dst_frame = 0;
 extern "C" void fg_set_search_frame(int coupler) { g_dst_frame = coupler ? 1 : 0; }
+static thread_local int tl_dst_frame = -1;  // >= 0: the frame of the searches this thread starts, whatever fg_set_search_frame says (fg_search_frame_override)
 static bool host_says_not_rect(int nx, int ny, const double *lon, const double *lat)
 {
   const long nxp = nx + 1;
@@ -952,7 +955,7 @@ static long plan_search(fg_plan *pl, const SearchIn &in)
   static const bool env_exact = getenv("FREGRID_HIP_EXACT_SEARCH") && atoi(getenv("FREGRID_HIP_EXACT_SEARCH")) != 0;
   // the setters' variables are read HERE and nowhere below: a repeated attempt runs under the options of the first
   const SearchOpts opt{.exact = g_search_exact || env_exact, .cull = g_search_cull != 0, .finalize = g_search_finalize != 0,
-                       .rect = g_search_rect != 0, .dst_frame = g_dst_frame != 0, .gc_split = g_gc_split, .profile = g_profiling != 0};
+                       .rect = g_search_rect != 0, .dst_frame = (tl_dst_frame >= 0 ? tl_dst_frame : g_dst_frame) != 0, .gc_split = g_gc_split, .profile = g_profiling != 0};
   const long big = std::max((long)pl->nsrc, (long)pl->ndst);
   // 32-bit prefixes (bin starts, exchange-cell offsets, CSR rows): the bin table holds up to 3 records per destination cell
   // (+ the wide lists) and the pair list 8 per cell, so grids beyond 2^28 cells could wrap an int before the host sees a
@@ -978,6 +981,7 @@ static long plan_search(fg_plan *pl, const SearchIn &in)
   }
   if (rc == FG_RETRY) return fg_fail(FG_ERR_CAPACITY, "exchange-grid search: capacities did not settle");
   if (rc >= 0) pl->stats[FG_STAT_EXACT] = (attempts > 1) ? 1 : 0;
+  pl->search_d2h = (long)attempts * (long)sizeof(FgCounters);
   return rc;
 }
 
@@ -1396,6 +1400,69 @@ extern "C" long fg_plan_create_polylist(int order, int npoly, const int *n, cons
   const long nx = plan_search(pl, SearchIn{.lon_in = none, .lat_in = none, .lon_out = d_lo, .lat_out = d_la, .mean_dlat = x.dlat,
                                            .mean_dlon = x.dlon, .rect_hint = x.rect_hint});
   if (nx >= 0) { pl->release(d_lo); pl->release(d_la); }     // (the list stays with the plan)
+  return g.hand_over(nx, plan_out);
+}
+
+// ------------------------------------------------------------------------------------- internal entries (plan_internal.h)
+// What coupler.hip needs of a plan without a trip through the host: the exchange cells and source records where they lie, the
+// clipped polygons into device arrays, a polygon-list search fed from device arrays, and a search whose destination extents
+// and rectilinear hint the caller worked out once from its host copy of the grid.
+int fg_plan_view(const fg_plan *pl, FgPlanView *v)
+{
+  if (!pl || !v) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->searched || !pl->have_geom) return fg_fail(FG_ERR_STATE, "fg_plan_view: needs a plan from a search");
+  *v = FgPlanView{pl->nx, pl->nsrc, pl->ndst, pl->x_src, pl->x_dst, pl->x_area, pl->order == 2 ? pl->x_c1 : nullptr,
+                  pl->order == 2 ? pl->x_c2 : nullptr, pl->S.area, pl->S.lon_avg};
+  return 0;
+}
+// queued on the plan's stream; n_out [nx], lon / lat [nx][8] (device).  A polygon of more than 8 vertices keeps its count.
+int fg_plan_polygons_dev(const fg_plan *pl, int *n_out, double *lon, double *lat)
+{
+  if (!pl || !n_out || !lon || !lat) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->searched || !pl->have_geom || !pl->x_src || pl->great_circle) return fg_fail(FG_ERR_STATE, "fg_plan_polygons_dev: needs a legacy plan from a search");
+  FGCHK(hipSetDevice(pl->device));
+  fgd_xgrid_polygons(pl->nx, pl->x_src, pl->x_dst, pl->S, pl->D, pl->rect ? &pl->rect_tab : nullptr, 8, n_out, lon, lat, pl->stream);
+  FGCHK(hipGetLastError());
+  return 0;
+}
+long fg_plan_search_d2h(const fg_plan *pl) { return pl ? pl->search_d2h : 0; }
+void fg_dst_extents(int nx, int ny, const double *lon, const double *lat, double *dlat, double *dlon, int *rect_hint)
+{
+  const DstExtents x = dst_extents_host(nx, ny, lon, lat);
+  *dlat = x.dlat; *dlon = x.dlon; *rect_hint = x.rect_hint;
+}
+int fg_search_frame_override(int frame) { const int old = tl_dst_frame; tl_dst_frame = frame; return old; }
+long fg_plan_create_dev_hint(int order, int ntiles_in, const int *nx_in, const int *ny_in, const double *const *d_lon_in,
+                             const double *const *d_lat_in, int nx_out, int ny_out, const double *d_lon_out, const double *d_lat_out,
+                             double mean_dlat, double mean_dlon, int rect_hint, int device, void *stream, fg_plan **plan_out)
+{
+  PlanGuard g;
+  if (int rc = plan_base(order, ntiles_in, nx_in, ny_in, nx_out, ny_out, device, &g.pl)) return rc;
+  if (int rc = check_grid_ptrs(ntiles_in, {d_lon_in, d_lat_in}, {d_lon_out, d_lat_out})) return rc;
+  if (!(mean_dlat > 0) || !(mean_dlon > 0)) return fg_fail(FG_ERR_ARG, "fg_plan_create_dev_hint: the extents must be positive");
+  adopt_stream(g.pl, stream);
+  const long nx = plan_search(g.pl, SearchIn{.lon_in = d_lon_in, .lat_in = d_lat_in, .lon_out = d_lon_out, .lat_out = d_lat_out,
+                                             .mean_dlat = mean_dlat, .mean_dlon = mean_dlon, .rect_hint = rect_hint});
+  return g.hand_over(nx, plan_out);
+}
+// fg_plan_create_polylist with every array on the device (n [npoly], lon / lat [npoly][8], lon_avg, area_ref [npoly]); the arrays
+// stay the caller's and must outlive the search only.
+long fg_plan_create_polylist_dev(int order, int npoly, const int *d_n, const double *d_lon, const double *d_lat, const double *d_lon_avg,
+                                 const double *d_area_ref, int nx_out, int ny_out, const double *d_lon_out, const double *d_lat_out,
+                                 double mean_dlat, double mean_dlon, int rect_hint, int device, void *stream, fg_plan **plan_out)
+{
+  if (npoly < 1 || !d_n || !d_lon || !d_lat || !d_lon_avg || !d_area_ref || !d_lon_out || !d_lat_out) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!(mean_dlat > 0) || !(mean_dlon > 0)) return fg_fail(FG_ERR_ARG, "fg_plan_create_polylist_dev: the extents must be positive");
+  PlanGuard g;
+  const int one = 1;
+  if (int rc = plan_base(order, 1, &npoly, &one, nx_out, ny_out, device, &g.pl)) return rc;
+  fg_plan *pl = g.pl;
+  if (order == 2) pl->f_stride = npoly;
+  adopt_stream(pl, stream);
+  pl->polys = FgPolyList{d_n, d_lon, d_lat, d_lon_avg, d_area_ref, npoly};
+  const double *none[1] = {nullptr};
+  const long nx = plan_search(pl, SearchIn{.lon_in = none, .lat_in = none, .lon_out = d_lon_out, .lat_out = d_lat_out, .mean_dlat = mean_dlat,
+                                           .mean_dlon = mean_dlon, .rect_hint = rect_hint});
   return g.hand_over(nx, plan_out);
 }
 

@@ -967,6 +967,63 @@ void fg_set_topog_sweep(int fused);
  * first-order plan; device pointers, queued on the plan's stream and waited for */
 int  fg_plan_apply_frac_dev(fg_plan *plan, const double *data_dev, double *out_dev);
 
+/* ---- make_coupler_mosaic's exchange grids on the device (tools/make_coupler_mosaic/make_coupler_mosaic.c:1198-2127, :2466-2811;
+ * DESIGN.md 3.13): atmosphere x land, atmosphere x ocean and land x ocean lists, the per-cell area and centroid sums, the centroid
+ * distances of an order-2 exchange-grid file and the land and ocean masks.  Legacy clip, one process, no nest, no wave grid, one
+ * ocean tile, any number of atmosphere tiles, land on the atmosphere grid (lnd_same_as_atm) or as tiles of its own.  The lists and
+ * every clipped polygon stay in device memory between the searches; fg_coupler_run brings counts and error words to the host.
+ *
+ * fg_coupler_create: corner arrays in radians, [ny+1][nx+1] per tile (host).  ntile_lnd = 0: land is on the atmosphere grid and
+ * the land arguments are ignored.  The ocean grid and omask [nyo][nxo] (ocean fraction in [0, 1]) are what the tool works on, i.e.
+ * with the row down to -90 degrees already added (coupler.coupler_ocean_grid; :841-876); ocn_south_ext = the rows added (0 or 1):
+ * they are left out of nbad.  area_ratio_thresh >= 1e-6 (the tool's default; the searches accept pairs at that ratio).
+ * fg_coupler_run may be called again.  Errors: FG_ERR_ARG / FG_ERR_GEOM with the reference's message, never an abort. */
+typedef struct fg_coupler fg_coupler;
+int  fg_coupler_create(int interp_order, double area_ratio_thresh, int ntile_atm, const int *nx_atm, const int *ny_atm,
+                       const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nx_lnd, const int *ny_lnd,
+                       const double *const *lon_lnd, const double *const *lat_lnd, int nx_ocn, int ny_ocn, const double *lon_ocn,
+                       const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out);
+void fg_coupler_destroy(fg_coupler *h);
+void *fg_coupler_stream(fg_coupler *h);
+int  fg_coupler_run(fg_coupler *h);
+/* which: 0 atmosphere x land (tile1 = atmosphere tile, tile2 = land tile), 1 atmosphere x ocean (tile1 = atmosphere tile, tile2 = 0),
+ * 2 land x ocean (tile1 = land tile, tile2 = 0; land of its own only).  The list's length, or FG_ERR_*. */
+long fg_coupler_count(const fg_coupler *h, int which, int tile1, int tile2);
+/* The list in the reference's order, host arrays of fg_coupler_count entries, any may be NULL: 0-based (i, j) of the two cells,
+ * the exchange-cell area, the centroid integrals clon / clat and the distances tile1_distance (di1, dj1) and tile2_distance
+ * (di2, dj2) of :1957-2006, :2778-2800 (interp_order 2 only). */
+int  fg_coupler_get(const fg_coupler *h, int which, int tile1, int tile2, int *i1, int *j1, int *i2, int *j2, double *area,
+                    double *clon, double *clat, double *di1, double *dj1, double *di2, double *dj2);
+/* Per cell of one tile (grid: 0 atmosphere, 1 land, 2 ocean), host arrays, any may be NULL: get_grid_area; the exchange area the
+ * cell collected from the atmosphere's lists (a_area, l_area, o_area); their ratio (the land mask of :2089, the ocean fraction of
+ * :2037, rows of the southern extension included); the cell's centroid (interp_order 2; the plain sums where the area is not > 0) */
+int  fg_coupler_get_cells(const fg_coupler *h, int grid, int tile, double *model_area, double *xarea, double *frac, double *clon,
+                          double *clat);
+/* The tool's output files into `directory` (which exists), classic netCDF: one exchange-grid file per non-empty list
+ * (<atm mosaic>_<tile>X<lnd mosaic>_<tile>.nc, ...X<ocn mosaic>_<tile>.nc, <lnd mosaic>_<tile>X<ocn mosaic>_<tile>.nc) with contact,
+ * tile1_cell, tile2_cell (1-based; an ocean j carries 1 - ocn_south_ext), xgrid_area and for interp_order 2 tile1_distance and
+ * tile2_distance, attributes as make_coupler_mosaic.c:2158-2182; ocean_mask.nc (mask, areaO, areaX, without the added southern
+ * row) and land_mask.nc or land_mask_tile<k>.nc (mask, area_lnd, l_area, and area_atm when land is on the atmosphere grid).
+ * names: NULL, or a table of [0] atmosphere, [1] land, [2] ocean mosaic name, then the atmosphere tiles' names, the land tiles'
+ * names (one per land tile of the handle) and the ocean tile's name; NULL entries give "atmos_mosaic", "land_mosaic",
+ * "ocean_mosaic", "tile<k>".  The coupler mosaic file that lists these files and the provenance attributes are not written. */
+int  fg_coupler_write(const fg_coupler *h, const char *directory, const char *const *names);
+/* The two kinds of file from host arrays, for lists a caller holds itself (fg_coupler_write goes through them).  An exchange-grid
+ * file: n >= 1 cells, 0-based (i, j) of the two grids written as i + 1, j1 + 1, j2 + j2_shift; di1 .. dj2 all given (tile1_distance,
+ * tile2_distance and the order-2 attributes) or all NULL.  A mask file [ny][nx]: ocean != 0: mask, areaO = a, areaX = b; else mask,
+ * area_lnd = a, l_area = b and area_atm when given. */
+int  fg_coupler_write_xgrid(const char *path, const char *contact, long n, const int *i1, const int *j1, const int *i2, const int *j2,
+                            int j2_shift, const double *area, const double *di1, const double *dj1, const double *di2, const double *dj2);
+int  fg_coupler_write_mask(const char *path, int ocean, int nx, int ny, const double *mask, const double *a, const double *b,
+                           const double *area_atm);
+/* the first n of 8: [0] bytes fg_coupler_run copied to the host, [1] nbad: ocean cells with |omask - ocn_frac| > 1e-4 (:2038),
+ * [2] searches, [3] atmosphere x ocean cells, [4] atmosphere x land cells, [5] land x ocean cells, [6] remembered atmosphere x land
+ * polygons, [7] ocn_south_ext */
+int  fg_coupler_stats(const fg_coupler *h, long *stats, int n);
+/* wall time in ms (the first n of 7): create; atmosphere x land candidates; atmosphere x ocean; polygons x ocean; land x ocean;
+ * sums, distances and masks; the whole run */
+int  fg_coupler_phase_ms(const fg_coupler *h, float *ms, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""Time make_coupler_mosaic's exchange grids on the device (CouplerMosaic, fg_coupler_*).
+
+    python scripts/coupler_time.py [--runs 7] [--out profiles/coupler_summary.md] [--large 384 1440 1080] [--shared 96 360 200 144 90]
+    python scripts/coupler_time.py --large-only --runs 1        (the run a kernel trace wraps)
+
+Two cases.
+* large: a C<n> atmosphere with land on the atmosphere grid over a tripolar NX x NY ocean from -82 degrees (one row added by
+  coupler_ocean_grid) with a 0 / 1 mask.  The handle is made once; run() is warmed up once and repeated `runs` times.  Reported: the
+  handle's phase times (each ended by a synchronise), the bytes run() copied to the host, the list lengths and the largest
+  |a_area / area_atm - 1| over the atmosphere cells -- a missed pair leaves a gap of the order of a cell, the area_ratio_thresh
+  rejections about 1e-6 each.
+* shared: a C<n> atmosphere, a lat-lon land grid of its own and a tripolar ocean: the configuration coupler.coupler_xgrid (three
+  searches, the lists downloaded and finished in numpy) accepts.  Both paths go from host arrays to host arrays -- the pipeline's
+  time is the handle's creation, run() and the download of its atmosphere x ocean and atmosphere x land lists; it also makes the
+  land x ocean list, the sums, distances and masks, which coupler_xgrid does not.  The two alternate in one process after a warm-up
+  of each; median and largest deviation from it.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__  # noqa: E402
+
+
+def _med(v):
+    v = np.asarray(v, dtype=np.float64)
+    return float(np.median(v)), float(np.max(np.abs(v - np.median(v))))
+
+
+def _fmt(v):
+    m, d = _med(v)
+    return f"{m:.3f} ({d:.3f})"
+
+
+def block_mask(nx, ny, fractions):
+    jj, ii = np.meshgrid(np.arange(ny), np.arange(nx), indexing="ij")
+    m = np.where((ii // max(nx // 12, 1) + jj // max(ny // 9, 1)) % 3 == 0, 0.0, 1.0)
+    if fractions:
+        m[(ii + 2 * jj) % 11 == 0] = 0.35
+    return m
+
+
+def ocean(fg, nx, ny, fractions):
+    to, ta = fg.tripolar_corners(nx, ny)
+    g = fg.coupler_ocean_grid(np.degrees(to), np.degrees(ta), block_mask(nx, ny, fractions))
+    return fg.GridConfig(nx, g["ny"], g["x"], g["y"]), g["omask"], g["ocn_south_ext"]
+
+
+def cubed_sphere(fg, ni):
+    lon, lat = fg.gnomonic_ed_corners(ni)
+    return [fg.GridConfig(ni, ni, lon[t], lat[t]) for t in range(6)]
+
+
+def large(fg, size, runs):
+    ni, nx, ny = size
+    atm = cubed_sphere(fg, ni)
+    ocn, omask, ext = ocean(fg, nx, ny, False)
+    with fg.CouplerMosaic(atm, None, ocn, omask, ocn_south_ext=ext) as m:
+        m.run()
+        ph = []
+        for _ in range(runs):
+            m.run()
+            ph.append(m.phase_ms())
+        st = m.stats()
+        gap = max(float(np.max(np.abs(m.cells(m.ATM, t)["frac"] - 1))) for t in range(6))
+        create = m.phase_ms()["create"]
+    lines = [f"## C{ni} atmosphere = land over a tripolar {nx} x {ny} ocean (+{ext} southern row), 0 / 1 mask, order 2", "",
+             f"{runs} runs of one handle after a warm-up; median (largest deviation from it), ms.  Creation of the handle (uploads, the three "
+             f"grids' areas): {create:.3f} ms.", "",
+             "| atmosphere x land candidates | atmosphere x ocean | polygons x ocean | land x ocean | sums, distances, masks | run |", "|---|---|---|---|---|---|",
+             "| " + " | ".join(_fmt([p[k] for p in ph]) for k in ("axl_candidates", "axo", "polygons_x_ocean", "lxo", "sums", "run")) + " |", "",
+             f"Lists: {st['naxo']} atmosphere x ocean cells, {st['naxl']} atmosphere x land cells from {st['npolygons']} remembered polygons, "
+             f"{st['searches']} searches; nbad {st['nbad']}.", f"Bytes run() copied to the host: {st['d2h_bytes']}.",
+             f"Largest |a_area / area_atm - 1| over the atmosphere cells: {gap:.3e} (bound 1e-3: {'met' if gap < 1e-3 else 'MISSED'})."]
+    return lines, gap
+
+
+def shared(fg, size, runs):
+    ni, nx, ny, nxl, nyl = size
+    atm = cubed_sphere(fg, ni)
+    ocn, omask, ext = ocean(fg, nx, ny, True)
+    lo, la = fg.latlon_corners(nxl, nyl)
+    lnd = fg.GridConfig(nxl, nyl, lo, la)
+
+    def pipeline():
+        t0 = time.perf_counter()
+        with fg.CouplerMosaic(atm, [lnd], ocn, omask, ocn_south_ext=ext) as m:
+            t1 = time.perf_counter()
+            m.run()
+            t2 = time.perf_counter()
+            axo = [m.axo(t) for t in range(6)]
+            axl = [m.axl(t, 0) for t in range(6)]
+            t3 = time.perf_counter()
+            return dict(create=(t1 - t0) * 1e3, run=(t2 - t1) * 1e3, download=(t3 - t2) * 1e3, all_in=(t3 - t0) * 1e3, d2h=m.stats()["d2h_bytes"]), axo, axl
+
+    def parent():
+        t0 = time.perf_counter()
+        r = fg.coupler_xgrid(atm, lnd, ocn, omask, interp_order=2)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    pipeline(); parent()
+    tp, tq = [], []
+    for _ in range(runs):
+        p, axo, axl = pipeline()
+        q, r = parent()
+        tp.append(p); tq.append(q)
+    same = True
+    for name, mine, keys in (("axo", axo, ("ia", "ja", "io", "jo")), ("axl", axl, ("ia", "ja", "il", "jl"))):
+        for i, k in enumerate(keys):
+            same = same and np.array_equal(np.concatenate([t[k] for t in mine]), r[name][keys[i]])
+        for k in ("area", "clon", "clat"):
+            same = same and np.array_equal(np.concatenate([t[k] for t in mine]).view(np.uint64), r[name][k].view(np.uint64))
+    ratio = _med(tq)[0] / _med([p["all_in"] for p in tp])[0]
+    lines = [f"## C{ni} atmosphere, {nxl} x {nyl} lat-lon land, tripolar {nx} x {ny} ocean (+{ext} row), order 2: the case coupler_xgrid accepts", "",
+             f"{runs} alternating runs after a warm-up of each; host arrays to host arrays; median (largest deviation from it), ms.", "",
+             "| path | create | run | download of the two lists | all-in |", "|---|---|---|---|---|",
+             "| CouplerMosaic | " + " | ".join(_fmt([p[k] for p in tp]) for k in ("create", "run", "download", "all_in")) + " |",
+             f"| coupler_xgrid (three searches, lists finished in numpy) | | | | {_fmt(tq)} |", "",
+             f"coupler_xgrid / CouplerMosaic, all-in: {ratio:.2f}.  The pipeline's run also makes the land x ocean list, the per-cell sums, the six "
+             f"distances and the masks; it copied {tp[-1]['d2h']} bytes to the host.",
+             f"Both give the same atmosphere x ocean and atmosphere x land lists, indices and bits of area, clon, clat: {same}."]
+    return lines, ratio, same
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--large", type=int, nargs=3, default=[384, 1440, 1080], metavar=("NI", "NX", "NY"))
+    ap.add_argument("--shared", type=int, nargs=5, default=[96, 360, 200, 144, 90], metavar=("NI", "NX", "NY", "NX_LND", "NY_LND"))
+    ap.add_argument("--large-only", action="store_true")
+    args = ap.parse_args()
+    fg = __graft_entry__.load_package()
+    fg._lib.require_gpu()
+    lines = ["# make_coupler_mosaic's exchange grids on the device: timing", ""]
+    a, gap = large(fg, args.large, args.runs)
+    lines += a
+    if not args.large_only:
+        b, ratio, same = shared(fg, args.shared, args.runs)
+        lines += [""] + b
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    if not gap < 1e-3:
+        sys.exit("the atmosphere cells are not covered: gap %g" % gap)
+
+
+if __name__ == "__main__":
+    main()
