@@ -33,65 +33,104 @@ extern "C" int fg_device_count(void)
   return n;
 }
 
-// ----------------------------------------------------------------------------- memory pool
-namespace {
-struct Pool {
+// Streams and events are cached per process: creating and destroying a stream costs ~0.1 ms each on this runtime, which
+// was a quarter of a millisecond per plan (scripts/host_time.py).
+struct HandleCache {
   std::mutex mu;
-  std::map<std::pair<int, size_t>, std::vector<void *>> free_;   // (device, class bytes) -> blocks
-  std::map<void *, std::pair<int, size_t>> live_;
-  static size_t klass(size_t n)
+  std::map<int, std::vector<hipStream_t>> streams;
+  std::map<int, std::vector<hipEvent_t>> events;        // per device, like the streams: an event belongs to its device
+  static int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
+  hipStream_t get_stream(int dev)
   {
-    size_t c = 256;
-    while (c < n) c += (c < (1u << 20) ? c : (c >> 2));           // x2 up to 1 MiB, then x1.25
-    return c;
-  }
-  // FREGRID_HIP_POISON=1 (tests): every block handed out is filled with 0x7f bytes first, so that a kernel reading something it
-  // or its predecessors never wrote meets wild indices / NaN-like doubles instead of a lucky zero or a stale valid value
-  static void *poison(void *p, size_t c)
-  {
-    static const bool on = getenv("FREGRID_HIP_POISON") && atoi(getenv("FREGRID_HIP_POISON")) != 0;
-    if (on && p) { (void)hipMemset(p, 0x7f, c); (void)hipDeviceSynchronize(); }
-    return p;
-  }
-  void *get(int dev, size_t n) { return poison(get_raw(dev, n), klass(n ? n : 1)); }
-  void *get_raw(int dev, size_t n)
-  {
-    if (n == 0) n = 1;
-    size_t c = klass(n);
     {
       std::lock_guard<std::mutex> lk(mu);
-      auto it = free_.find({dev, c});
-      if (it != free_.end() && !it->second.empty()) {
-        void *p = it->second.back(); it->second.pop_back();
-        live_[p] = {dev, c};
-        return p;
-      }
+      auto &v = streams[dev];
+      if (!v.empty()) { hipStream_t s = v.back(); v.pop_back(); return s; }
     }
-    void *p = nullptr;
-    if (hipMalloc(&p, c) != hipSuccess) {
-      release_all();
-      if (hipMalloc(&p, c) != hipSuccess) return nullptr;
+    hipStream_t s = nullptr;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
+    return s;
+  }
+  void put_stream(int dev, hipStream_t s)
+  {
+    if (!s) return;
+    std::lock_guard<std::mutex> lk(mu);
+    streams[dev].push_back(s);
+  }
+  hipEvent_t get_event()
+  {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      auto &v = events[current_device()];
+      if (!v.empty()) { hipEvent_t e = v.back(); v.pop_back(); return e; }
     }
-    std::lock_guard<std::mutex> lk(mu);
-    live_[p] = {dev, c};
-    return p;
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
   }
-  void put(void *p)
+  void put_event(hipEvent_t e)
   {
-    if (!p) return;
+    if (!e) return;
     std::lock_guard<std::mutex> lk(mu);
-    auto it = live_.find(p);
-    if (it == live_.end()) return;
-    free_[it->second].push_back(p);
-    live_.erase(it);
+    events[current_device()].push_back(e);
   }
-  void release_all()
+  // ordering-only events (the plan's stream <-> its second stream in the great-circle clip, the readback of a fused search, a
+  // plan's `done` mark, the pool's tagged blocks).  dev < 0: the current device (where a new event is created in any case).
+  std::map<int, std::vector<hipEvent_t>> sync_events;
+  hipEvent_t get_sync_event(int dev = -1)
   {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      auto &v = sync_events[dev >= 0 ? dev : current_device()];
+      if (!v.empty()) { hipEvent_t e = v.back(); v.pop_back(); return e; }
+    }
+    hipEvent_t e = nullptr;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return e;
+  }
+  void put_sync_event(hipEvent_t e, int dev = -1)
+  {
+    if (!e) return;
     std::lock_guard<std::mutex> lk(mu);
-    for (auto &kv : free_) for (void *p : kv.second) (void)hipFree(p);
-    free_.clear();
+    sync_events[dev >= 0 ? dev : current_device()].push_back(e);
   }
 };
+static HandleCache g_handles;
+
+// ----------------------------------------------------------------------------- memory pool
+// The bookkeeping is dev_pool.h's; this is the policy that makes its device calls.  Events come from g_handles' ordering-only
+// cache.  Without an event (creation failed), or when the record fails, the batch's device is synchronised instead.
+#include "dev_pool.h"
+namespace {
+struct HipPoolPolicy {
+  typedef hipStream_t Stream;
+  typedef hipEvent_t Event;
+  static void *dev_malloc(size_t c) { void *p = nullptr; if (hipMalloc(&p, c) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; }
+  static void dev_free(void *p) { (void)hipFree(p); }
+  struct OnDevice {                                    // an event belongs to the device it was created on, a record to the stream's
+    int old = -1, dev;
+    explicit OnDevice(int d) : dev(d) { if (hipGetDevice(&old) != hipSuccess) old = -1; if (old != dev) (void)hipSetDevice(dev); }
+    ~OnDevice() { if (old >= 0 && old != dev) (void)hipSetDevice(old); }
+  };
+  static Event event_get(int dev) { OnDevice on(dev); return g_handles.get_sync_event(dev); }
+  static void event_put(int dev, Event e) { g_handles.put_sync_event(e, dev); }
+  static void event_record(int dev, Event e, Stream s)
+  {
+    OnDevice on(dev);
+    if (!e || hipEventRecord(e, s) != hipSuccess) { (void)hipGetLastError(); (void)hipDeviceSynchronize(); }
+  }
+  static bool event_passed(Event e) { return !e || hipEventQuery(e) != hipErrorNotReady; }
+  static void stream_wait(Stream s, Event e) { if (e && hipStreamWaitEvent(s, e, 0) != hipSuccess) (void)hipEventSynchronize(e); }
+  static void event_wait_host(Event e) { if (e) (void)hipEventSynchronize(e); }
+  static bool poison_on()
+  {
+    static const bool on = getenv("FREGRID_HIP_POISON") && atoi(getenv("FREGRID_HIP_POISON")) != 0;
+    return on;
+  }
+  // (the first synchronise: a tagged block may still be in use by queued work, and the fill runs on the null stream)
+  static void poison(void *p, size_t c) { (void)hipDeviceSynchronize(); (void)hipMemset(p, 0x7f, c); (void)hipDeviceSynchronize(); }
+};
+typedef DevPool<HipPoolPolicy> Pool;
 Pool g_pool;
 }  // namespace
 
@@ -274,68 +313,6 @@ static int g_profiling = 0;
 extern "C" void fg_set_profiling(int on) { g_profiling = on ? 1 : 0; }
 enum { PH_CELL_STRUCT = 0, PH_BINS, PH_CANDIDATES, PH_CLIP_QUAD, PH_CLIP_GENERAL, PH_COMPACT, PH_ROWS,
        PH_SEARCH_TOTAL, PH_FINALIZE, PH_APPLY, PH_COUNT };
-// Streams and events are cached per process: creating and destroying a stream costs ~0.1 ms each on this runtime, which
-// was a quarter of a millisecond per plan (scripts/host_time.py).
-struct HandleCache {
-  std::mutex mu;
-  std::map<int, std::vector<hipStream_t>> streams;
-  std::map<int, std::vector<hipEvent_t>> events;        // per device, like the streams: an event belongs to its device
-  static int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
-  hipStream_t get_stream(int dev)
-  {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      auto &v = streams[dev];
-      if (!v.empty()) { hipStream_t s = v.back(); v.pop_back(); return s; }
-    }
-    hipStream_t s = nullptr;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-    return s;
-  }
-  void put_stream(int dev, hipStream_t s)
-  {
-    if (!s) return;
-    std::lock_guard<std::mutex> lk(mu);
-    streams[dev].push_back(s);
-  }
-  hipEvent_t get_event()
-  {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      auto &v = events[current_device()];
-      if (!v.empty()) { hipEvent_t e = v.back(); v.pop_back(); return e; }
-    }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
-  }
-  void put_event(hipEvent_t e)
-  {
-    if (!e) return;
-    std::lock_guard<std::mutex> lk(mu);
-    events[current_device()].push_back(e);
-  }
-  // ordering-only events (the plan's stream <-> its second stream in the great-circle clip)
-  std::map<int, std::vector<hipEvent_t>> sync_events;
-  hipEvent_t get_sync_event()
-  {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      auto &v = sync_events[current_device()];
-      if (!v.empty()) { hipEvent_t e = v.back(); v.pop_back(); return e; }
-    }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
-    return e;
-  }
-  void put_sync_event(hipEvent_t e)
-  {
-    if (!e) return;
-    std::lock_guard<std::mutex> lk(mu);
-    sync_events[current_device()].push_back(e);
-  }
-};
-static HandleCache g_handles;
 
 struct PhaseTimer {
   bool on = false;
@@ -418,17 +395,37 @@ struct fg_plan {
   bool mono_open = false;
   unsigned *ll_err = nullptr;    // error word of a latlon2xyz conversion queued ahead of the search (great-circle plans from lon / lat)
 
+  // Stream-ordered plans (fg_set_search_async).
+  // async: the plan's search ran with the switch on; its blocks go back to the pool tagged with its stream, and fg_plan_destroy
+  //   does not drain the stream.
+  // on_stream: set while plan_search / the finalize allocate -- every block taken then is first touched by work queued on `stream`
+  //   (or on stream_b behind an event of `stream`), so the pool may hand out one that earlier work of the stream still uses.
+  //   Everywhere else alloc() takes blocks nothing uses: host copies and the transfer pool's streams write into them.
+  // INVARIANT -- when a fused search (or a finalize on a caller's stream) has returned, everything in the plan is complete
+  //   except `cen` and the CSR records (csr.e1 / csr.e2); those two are complete in stream order on `stream`.  Whoever reads them
+  //   from the host or from another stream, or moves the plan to another stream, synchronises `stream` first -- every entry that
+  //   does either did so before this invariant existed and still does; entries that only queue work on `stream` need not.
+  bool async = false, on_stream = false;
+
   template <typename T> T *alloc(size_t count)
   {
-    void *p = g_pool.get(device, count * sizeof(T));
+    void *p = on_stream ? g_pool.get(device, count * sizeof(T), stream) : g_pool.get(device, count * sizeof(T));
     if (p) owned.push_back(p);
     return (T *)p;
   }
+  void disown(void *p) { for (size_t k = 0; k < owned.size(); k++) if (owned[k] == p) { owned.erase(owned.begin() + k); break; } }
   void release(void *p)
   {
     if (!p) return;
-    for (size_t k = 0; k < owned.size(); k++) if (owned[k] == p) { owned.erase(owned.begin() + k); break; }
+    disown(p);
     g_pool.put(p);
+  }
+  // blocks that work queued on the plan's stream may still be using: one batch of the pool, left without an event of its own
+  // (the plan vouches for its stream; fg_plan_destroy or a change of stream seals the batch)
+  void release_on_stream(const std::vector<void *> &ps)
+  {
+    for (void *p : ps) disown(p);
+    g_pool.put(ps, stream, false);
   }
   // Before a search is repeated (plan_search): every block beyond the first `keep` -- those the caller staged -- goes back to the
   // pool, and so must every pointer into them.  A field that plan_search_core allocates or sets is added HERE as well.
@@ -489,15 +486,27 @@ static int plan_base(int order, int ntiles_in, const int *nx_in, const int *ny_i
   return 0;
 }
 
+// A plan whose search ran stream-ordered (fg_plan::async) does not drain its stream here: its blocks go back to the pool tagged
+// with the stream, in one batch, and its streams to the cache as they are (whoever gets them next queues behind what is left).
+// What may still be queued reads plan-owned memory only -- k_centroids and k_csr_sortgather read S, sums, cen, perm, the
+// exchange cells, src_idx_f and their scratch, never the caller's corner arrays, which nothing behind the search's readback
+// touches -- and later work of the caller (an apply) is ordered on the caller's stream like the caller's own buffers.
+// On a caller's stream the batch is sealed here: one event, recorded now, also for what the search and the finalize gave back
+// earlier, so that the pool never touches the stream after this call and the caller may destroy it.  A plan-owned stream goes
+// back to the cache, which never destroys one: its batch gets an event only if a taker on another stream needs it.
+// stream_b is idle whenever a search has returned: only the great-circle clip uses it, and joins it into `stream` ahead of the
+// readback.
 extern "C" void fg_plan_destroy(fg_plan *pl)
 {
   if (!pl) return;
   (void)hipSetDevice(pl->device);
-  if (pl->stream || !pl->own_stream) (void)hipStreamSynchronize(pl->stream);
-  if (pl->stream && pl->own_stream) g_handles.put_stream(pl->device, pl->stream);
-  if (pl->stream_b) { (void)hipStreamSynchronize(pl->stream_b); g_handles.put_stream(pl->device, pl->stream_b); }
+  const bool drain = !pl->async || !pl->apply_pt.spans.empty();      // (timing events of sweeps are read after a synchronisation)
+  if (drain && (pl->stream || !pl->own_stream)) (void)hipStreamSynchronize(pl->stream);
+  if (pl->stream_b) { if (drain) (void)hipStreamSynchronize(pl->stream_b); g_handles.put_stream(pl->device, pl->stream_b); }
   { float junk[PH_COUNT] = {0}; pl->apply_pt.collect(junk); }
-  for (void *p : pl->owned) g_pool.put(p);
+  if (pl->async) g_pool.put(pl->owned, pl->stream, !pl->own_stream);
+  else for (void *p : pl->owned) g_pool.put(p);
+  if (pl->stream && pl->own_stream) g_handles.put_stream(pl->device, pl->stream);
   delete pl;
 }
 
@@ -519,11 +528,14 @@ static void choose_bins(const fg_plan *pl, double mean_dlat, double mean_dlon, F
 
 // Device-side counters of one search (FgCounters, xgrid_device.h): one block, zeroed by the search's one memset, read back with
 // one copy into pinned host memory when the search has been queued.
+// Behind the counters, in the same page-locked block, one 64-bit word: the arrival mark of a stream-ordered search, which its
+// counter kernel stores after the counters and the host polls (k_counters_out).
+struct PinnedCounters { FgCounters c; unsigned long long mark; };
 static FgCounters *pinned_counters()
 {
-  static thread_local FgCounters *h = nullptr;
-  if (!h) { if (hipHostMalloc((void **)&h, sizeof(FgCounters), hipHostMallocDefault) != hipSuccess) h = nullptr; }
-  return h;
+  static thread_local PinnedCounters *h = nullptr;
+  if (!h) { if (hipHostMalloc((void **)&h, sizeof(PinnedCounters), hipHostMallocCoherent) != hipSuccess) h = nullptr; else h->mark = 0; }
+  return h ? &h->c : nullptr;
 }
 
 // the search proper; all grid pointers are device pointers
@@ -547,7 +559,33 @@ struct SearchIn {
 };
 // What steers a search: the values of the process-wide setters (fg_set_search_*, fg_set_gc_split, fg_set_profiling) as
 // plan_search found them when the plan-creating call started.  Every attempt of that search gets the same ones.
-struct SearchOpts { bool exact, cull, finalize, rect, dst_frame; int gc_split; bool profile; };
+struct SearchOpts { bool exact, cull, finalize, rect, dst_frame; int gc_split; bool profile, async; };
+// The counter block of a fused, stream-ordered search into the page-locked host block: one wave, queued behind the compaction
+// (the last kernel that writes a counter), so that the host has the counters while the centroid pass and the CSR records still
+// run.  Plain stores, 4 bytes a lane and round; then, when every lane's stores are out, the arrival mark the host polls for.
+__global__ __launch_bounds__(64) void k_counters_out(const unsigned *src, unsigned *dst, int nwords, unsigned long long *mark, unsigned long long seq)
+{
+  for (int k = threadIdx.x; k < nwords; k += 64) dst[k] = src[k];
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(mark, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+static_assert(sizeof(FgCounters) % sizeof(unsigned) == 0 && offsetof(PinnedCounters, mark) == sizeof(FgCounters), "FgCounters travels as 32-bit words, the mark behind them");
+// The host side: polls the mark, looking at the stream now and then so that a failed launch or a fault ends the wait.
+static hipError_t wait_counters(const FgCounters *hc, unsigned long long seq, hipStream_t st)
+{
+  const unsigned long long *mark = &((const PinnedCounters *)hc)->mark;
+  for (unsigned spin = 1;; spin++) {
+    if (__atomic_load_n(mark, __ATOMIC_ACQUIRE) == seq) return hipSuccess;
+    __builtin_ia32_pause();
+    if (spin % 65536 == 0) {
+      const hipError_t e = hipStreamQuery(st);
+      if (e == hipErrorNotReady) (void)hipGetLastError();       // (not an error; the caller has checked the launches already)
+      if (e == hipSuccess) return __atomic_load_n(mark, __ATOMIC_ACQUIRE) == seq ? hipSuccess : hipErrorUnknown;   // drained: it is there, or never will be
+      if (e != hipErrorNotReady) return e;
+    }
+  }
+}
 static const char *gc_clip_error(int code)
 {
   switch (code) {
@@ -873,25 +911,47 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   // kernel timeline, scripts/band_trace.sh).  The records are sized by the capacity of the exchange-cell arrays (the count is
   // not known yet); an attempt that has to be repeated drops them with everything else.
   const bool fuse = opt.finalize && early_rows && !pl->polys.npoly;
+  // Stream-ordered (fg_set_search_async): every counter is final when the compaction ends -- k_centroids
+  // and k_csr_sortgather write cen, the CSR records and their scratch only -- so the counters leave from HERE, and the host
+  // waits for them alone; the two kernels below are still queued or running when the search returns.
+  // A one-wave kernel on the plan's stream stores them, and behind them an arrival mark that the host polls: no event and no
+  // second stream, so nothing holds k_centroids back but the kernel's own 4-5 us (the parent's readback copy took as long at the
+  // end of the step).  The same kernel, or a copy, on the second stream between two events held k_centroids back by 7 us and
+  // cost a host wake-up through an event.
+  const bool stream_ordered = fuse && opt.async && !opt.profile;
+  static thread_local unsigned long long rb_seq = 0;
   int *fused_tmp = nullptr;
+  if (fuse) {            // the finalize's blocks first: no error return stands between the counter kernel's launch and the wait for it
+    if (order == 2) { pl->cen = pl->alloc<FgSrcRec>((size_t)nsrc + 1); pl->csr.e2 = pl->alloc<FgCsrEntry2>(nx_alloc + 1); }
+    else pl->csr.e1 = pl->alloc<FgCsrEntry1>(nx_alloc + 1);
+    if ((order == 2 && !pl->cen) || (!pl->csr.e1 && !pl->csr.e2)) return fg_fail(FG_ERR_HIP, "out of device memory");
+    fused_tmp = pl->alloc<int>(3 * (size_t)(nx_alloc + 1));     // (scratch for rows beyond the LDS staging; null = the serial last resort)
+  }
+  if (stream_ordered) {
+    unsigned *hc_dev = nullptr;
+    if (hipHostGetDevicePointer((void **)&hc_dev, hc, 0) != hipSuccess || !hc_dev) return fg_fail(FG_ERR_HIP, "the counters' host block is not mapped");
+    const int nwords = (int)(sizeof(FgCounters) / sizeof(unsigned));
+    k_counters_out<<<1, 64, 0, st>>>((const unsigned *)dc, hc_dev, nwords, (unsigned long long *)(hc_dev + nwords), ++rb_seq);
+    FGCHK(hipGetLastError());
+  }
   if (fuse) {
     pt.begin(PH_FINALIZE);
-    if (order == 2) {
-      pl->cen = pl->alloc<FgSrcRec>((size_t)nsrc + 1);
-      if (!pl->cen) return fg_fail(FG_ERR_HIP, "out of device memory");
-      fgd_centroids(nsrc, pl->S, pl->sums, pl->cen, st);
-      pl->csr.e2 = pl->alloc<FgCsrEntry2>(nx_alloc + 1);
-    } else pl->csr.e1 = pl->alloc<FgCsrEntry1>(nx_alloc + 1);
-    if (!pl->csr.e1 && !pl->csr.e2) return fg_fail(FG_ERR_HIP, "out of device memory");
+    if (order == 2) fgd_centroids(nsrc, pl->S, pl->sums, pl->cen, st);
     // (the row-length heuristic of the record kernel wants the exchange-cell count: nsrc + ndst is within a factor of it)
-    int *sg_tmp = pl->alloc<int>(3 * (size_t)(nx_alloc + 1));   // (scratch for rows beyond the LDS staging; null = the serial last resort)
     fgd_csr_sortgather(order, ndst, (long)nsrc + ndst, pl->perm, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f,
-                       order == 2 ? pl->cen : nullptr, pl->csr, st, sg_tmp, nx_alloc + 1);
-    fused_tmp = sg_tmp;
+                       order == 2 ? pl->cen : nullptr, pl->csr, st, fused_tmp, nx_alloc + 1);
     pt.end();
   }
-  FGCHK(hipMemcpyAsync(hc, dc, sizeof(FgCounters), hipMemcpyDeviceToHost, st));
-  FGCHK(hipStreamSynchronize(st));                              // the one synchronisation of a search (stream B's work is ordered before it)
+  if (stream_ordered) {
+    if (hipError_t e = hipGetLastError()) {                     // (the launches; the wait below may leave a "not ready" behind)
+      (void)hipStreamSynchronize(st);                           // (the counter kernel must not write the host block behind a later search)
+      return fg_fail(FG_ERR_HIP, "a launch of the search failed: %s", hipGetErrorString(e));
+    }
+    FGCHK(wait_counters(hc, rb_seq, st));                      // the one host wait of this search: up to the compaction, no further
+  } else {
+    FGCHK(hipMemcpyAsync(hc, dc, sizeof(FgCounters), hipMemcpyDeviceToHost, st));
+    FGCHK(hipStreamSynchronize(st));                            // the one synchronisation of a search (stream B's work is ordered before it)
+  }
   pt.collect(pl->phase_ms); ptot.collect(pl->phase_ms);          // (also hands the timing events back on every exit below)
   FGCHK(hipGetLastError());
   if (rect && hc->rect_bad) { caps->rect = false; return FG_RETRY; }   // not a rectilinear grid after all: every kernel of this attempt left at once
@@ -927,7 +987,12 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   pl->stats[FG_STAT_BELOW] = (long)hc->stats[FG_STAT_BELOW];
 
   pl->rect_tab.bad = nullptr;                          // (lives in the scratch block released below; nothing reads it after the search)
-  blk.release();                                       // scratch no longer needed
+  if (stream_ordered) {                                // k_csr_sortgather may still be reading perm and its scratch: one tagged batch
+    blk.scratch.push_back(pl->perm); blk.scratch.push_back(fused_tmp);
+    pl->release_on_stream(blk.scratch); blk.scratch.clear();
+    pl->perm = nullptr; fused_tmp = nullptr;
+  }
+  blk.release();                                      // scratch no longer needed
   pl->rows_built = true;
   pl->searched = true;
   if (fuse) {
@@ -950,12 +1015,18 @@ extern "C" void fg_set_search_mode(int exact) { g_search_exact = exact; }
 // a fraction of the source cells); fg_plan_get_cell_area then returns 0 for them.  Results are unchanged.
 extern "C" void fg_set_search_cull(int on) { g_search_cull = on ? 1 : 0; }
 extern "C" void fg_set_search_finalize(int on) { g_search_finalize = on ? 1 : 0; }
+// Stream-ordered plans.  1 (default): a fused search returns when its counters are back, with its centroid
+// pass and CSR records still queued; plans take and return their device blocks tagged with their stream, and fg_plan_destroy
+// does not drain the stream.  0: the search synchronises its stream at its end, fg_plan_destroy at its start, blocks travel
+// untagged.  The tests compare the two bit for bit.
+static int g_search_async = 1;
+extern "C" void fg_set_search_async(int on) { g_search_async = on ? 1 : 0; }
 static long plan_search(fg_plan *pl, const SearchIn &in)
 {
   static const bool env_exact = getenv("FREGRID_HIP_EXACT_SEARCH") && atoi(getenv("FREGRID_HIP_EXACT_SEARCH")) != 0;
   // the setters' variables are read HERE and nowhere below: a repeated attempt runs under the options of the first
   const SearchOpts opt{.exact = g_search_exact || env_exact, .cull = g_search_cull != 0, .finalize = g_search_finalize != 0,
-                       .rect = g_search_rect != 0, .dst_frame = (tl_dst_frame >= 0 ? tl_dst_frame : g_dst_frame) != 0, .gc_split = g_gc_split, .profile = g_profiling != 0};
+                       .rect = g_search_rect != 0, .dst_frame = (tl_dst_frame >= 0 ? tl_dst_frame : g_dst_frame) != 0, .gc_split = g_gc_split, .profile = g_profiling != 0, .async = g_search_async != 0};
   const long big = std::max((long)pl->nsrc, (long)pl->ndst);
   // 32-bit prefixes (bin starts, exchange-cell offsets, CSR rows): the bin table holds up to 3 records per destination cell
   // (+ the wide lists) and the pair list 8 per cell, so grids beyond 2^28 cells could wrap an int before the host sees a
@@ -972,13 +1043,16 @@ static long plan_search(fg_plan *pl, const SearchIn &in)
   const size_t keep = pl->owned.size();              // blocks the caller staged before the search stay
   long rc = FG_RETRY;
   int attempts = 0;
+  pl->async = opt.async;
+  pl->on_stream = pl->async;                         // (every block of the search is first touched on the plan's stream)
   for (; attempts < 4 && rc == FG_RETRY; attempts++) {
     if (attempts) {
-      (void)hipStreamSynchronize(pl->stream);
+      (void)hipStreamSynchronize(pl->stream);        // (a stream-ordered attempt left its last two kernels queued)
       pl->drop_search(keep);
     }
     rc = plan_search_core(pl, in, opt, &caps);
   }
+  pl->on_stream = false;
   if (rc == FG_RETRY) return fg_fail(FG_ERR_CAPACITY, "exchange-grid search: capacities did not settle");
   if (rc >= 0) pl->stats[FG_STAT_EXACT] = (attempts > 1) ? 1 : 0;
   pl->search_d2h = (long)attempts * (long)sizeof(FgCounters);
@@ -1191,6 +1265,7 @@ static int stage_host_grids(fg_plan *pl, const double *const *lon_in, const doub
 static void adopt_stream(fg_plan *pl, void *stream)
 {
   if (pl->own_stream && pl->stream) g_handles.put_stream(pl->device, pl->stream);
+  else if (!pl->own_stream) g_pool.seal(pl->stream);      // (the plan stops vouching for the caller's previous stream)
   pl->stream = (hipStream_t)stream; pl->own_stream = false;
 }
 
@@ -1426,6 +1501,13 @@ int fg_plan_polygons_dev(const fg_plan *pl, int *n_out, double *lon, double *lat
   return 0;
 }
 long fg_plan_search_d2h(const fg_plan *pl) { return pl ? pl->search_d2h : 0; }
+extern "C" long fg_plan_device_bytes(const fg_plan *pl, long *sizes, int nmax)
+{
+  if (!pl) return 0;
+  long sum = 0;
+  for (size_t k = 0; k < pl->owned.size(); k++) { const long b = (long)g_pool.block_bytes(pl->owned[k]); sum += b; if (sizes && (int)k < nmax) sizes[k] = b; }
+  return sum;
+}
 void fg_dst_extents(int nx, int ny, const double *lon, const double *lat, double *dlat, double *dlon, int *rect_hint)
 {
   const DstExtents x = dst_extents_host(nx, ny, lon, lat);
@@ -1592,8 +1674,18 @@ extern "C" int fg_plan_stats(const fg_plan *pl, long *stats, int n)
 // Destination-row CSR.  A searched plan arrives with row_ptr and perm (rows grouped, unsorted inside a row) already built on
 // the device by the search; a plan loaded from a remap file (fg_plan_set_xgrid) counts and fills its rows here.
 // cen != null: order 2, x_c1/x_c2 hold the centroid integrals and di/dj are formed while the records are packed.
+// The two-call finalize without its host wait: a stream-ordered plan (fg_plan::async) on a stream the CALLER supplied, profiling
+// off.  The caller orders its own buffers on that stream (total_cell_sums_dev must outlive k_centroids there, as the comment on
+// fg_plan_accumulate_cell_sums_async says of the sums).  A plan-owned stream keeps the wait: the caller has no way to order
+// total_cell_sums_dev behind it.  What is left in flight is what fg_plan's invariant names.
+static bool finalize_stream_ordered(const fg_plan *pl) { return pl->async && !pl->own_stream && !g_profiling; }
 static int build_csr(fg_plan *pl, const FgSrcRec *cen)
 {
+  struct OnStream {                                    // its blocks are first touched on the plan's stream (fg_plan::on_stream)
+    fg_plan *pl; bool was;
+    ~OnStream() { pl->on_stream = was; }
+  } on_stream{pl, pl->on_stream};
+  pl->on_stream = pl->async;
   hipStream_t st = pl->stream;
   const int ndst = pl->ndst;
   const long nx = pl->nx;
@@ -1632,9 +1724,14 @@ static int build_csr(fg_plan *pl, const FgSrcRec *cen)
   const int long_rows = !pl->rect && !pl->great_circle && pl->stats[FG_STAT_DEFERRED] > 0 && nx > 4 * (long)ndst;
   fgd_csr_sortgather(pl->order, ndst, nx, pl->perm, pl->x_area, pl->x_c1, pl->x_c2, pl->src_idx_f, cen, pl->csr, st, sg_tmp, nx + 1,
                      long_rows);
-  FGCHK(hipStreamSynchronize(st));
+  if (finalize_stream_ordered(pl)) {                   // the wait was for these three blocks only: they go back tagged instead
+    pl->release_on_stream({scratch, pl->perm, sg_tmp});
+  } else {
+    FGCHK(hipStreamSynchronize(st));
+    pl->release(scratch); pl->release(pl->perm); pl->release(sg_tmp);
+  }
+  pl->perm = nullptr;
   FGCHK(hipGetLastError());
-  pl->release(scratch); pl->release(pl->perm); pl->perm = nullptr; pl->release(sg_tmp);
   if (!pl->red_partial) { pl->red_partial = pl->alloc<double>(1024); pl->red_result = pl->alloc<double>(260); }
   if (!pl->red_partial || !pl->red_result) return fg_fail(FG_ERR_HIP, "out of device memory");
   return 0;
@@ -1652,7 +1749,11 @@ extern "C" int fg_plan_finalize(fg_plan *pl, const double *total_cell_sums_dev)
   PhaseTimer pt; pt.start(g_profiling != 0, pl->stream);
   pt.begin(PH_FINALIZE);
   if (pl->order == 2) {
+    // (first touched by k_centroids on the plan's stream: taken in stream order like build_csr's blocks -- a stream-less request
+    // would wait on the host for the block the previous plan gave back tagged, with the GPU idle: 10-20 us per finalize)
+    pl->on_stream = pl->async;
     pl->cen = pl->alloc<FgSrcRec>((size_t)pl->nsrc + 1);
+    pl->on_stream = false;
     if (!pl->cen) return fg_fail(FG_ERR_HIP, "out of device memory");
     const double *tot = total_cell_sums_dev ? total_cell_sums_dev : pl->sums;
     fgd_centroids(pl->nsrc, pl->S, tot, pl->cen, pl->stream);
@@ -1661,7 +1762,7 @@ extern "C" int fg_plan_finalize(fg_plan *pl, const double *total_cell_sums_dev)
   int rc = build_csr(pl, pl->order == 2 ? pl->cen : nullptr);
   if (rc) return rc;
   pt.end();
-  FGCHK(hipStreamSynchronize(pl->stream));
+  if (!finalize_stream_ordered(pl)) FGCHK(hipStreamSynchronize(pl->stream));
   pl->phase_ms[PH_FINALIZE] = 0; pt.collect(pl->phase_ms);
   pl->finalized = true;
   return 0;

@@ -18,6 +18,9 @@ int fg_plan_view(const fg_plan *pl, FgPlanView *v);
 int fg_plan_polygons_dev(const fg_plan *pl, int *n_out, double *lon, double *lat);
 // bytes the plan's search copied to the host (one block of counters per attempt)
 long fg_plan_search_d2h(const fg_plan *pl);
+// the plan's own block list: the pool's class size of every device block the plan holds into sizes [nmax] (may be null), their sum
+// returned (C linkage: tests/test_gpu_stream_ordered_plans.py derives its footprint allowance from it)
+extern "C" long fg_plan_device_bytes(const fg_plan *pl, long *sizes, int nmax);
 // mean cell extents and the rectilinear hint of a destination grid from its host corner arrays, as fg_plan_create derives them
 void fg_dst_extents(int nx, int ny, const double *lon, const double *lat, double *dlat, double *dlon, int *rect_hint);
 // frame >= 0: the searches this thread starts use that longitude frame (fg_set_search_frame's values) whatever the process-wide

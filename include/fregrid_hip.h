@@ -142,6 +142,9 @@ long fg_plan_create_dev(int order, int ntiles_in, const int *nx_in, const int *n
 /* A plan without a search; exchange cells are supplied by fg_plan_set_xgrid. */
 int fg_plan_create_empty(int order, int ntiles_in, const int *nx_in, const int *ny_in,
                          int nx_out, int ny_out, int device, fg_plan **plan_out);
+/* Does not synchronise the plan's stream (fg_set_search_async): work of the plan that is still queued -- an asynchronous apply
+ * with the caller's buffers among it -- stays queued, on a plan-owned stream too, so a caller that frees or reuses those buffers
+ * from the host calls fg_plan_sync first. */
 void fg_plan_destroy(fg_plan *plan);
 /* queue all further work of the plan on the caller's stream (hipStream_t) */
 int fg_plan_set_stream(fg_plan *plan, void *stream);
@@ -375,6 +378,17 @@ void fg_set_search_cull(int on);
  * with totals it is an error.  Applies to legacy-clip searches that run in one chunk (others finalize in fg_plan_finalize as
  * before).  Results do not depend on it.  Default 0. */
 void fg_set_search_finalize(int on);
+/* Stream-ordered plans.  1 (default): no call drains the GPU between one plan and the next.  A search that queues its own finalize
+ * (fg_set_search_finalize) returns as soon as its counters are back -- they are final when the compaction ends -- while its
+ * centroid pass and CSR records are still queued on the plan's stream; fg_plan_finalize with a plan on a stream the caller
+ * supplied returns without a host wait (total_cell_sums_dev is then ordered on that stream by the caller, like every buffer of
+ * an asynchronous call); fg_plan_destroy returns the plan's device blocks to the pool tagged with its stream instead of
+ * synchronising it, and the next plan on that stream reuses them in stream order, a plan on another stream behind an event.
+ * Every entry that reads a plan's results on the host, or moves it to another stream, waits for what is outstanding first, so
+ * callers see no difference but the time.  0: the search synchronises its stream at its end and fg_plan_destroy at its start.
+ * Results do not depend on it (tests/test_gpu_stream_ordered_plans.py).  With fg_set_profiling(1) a search synchronises as under 0.  A stream given to a
+ * plan lives as long as the plan, as before; after fg_plan_destroy the library does not touch it again. */
+void fg_set_search_async(int on);
 /* Rectilinear destination grids -- lon_out a function of the column and lat_out of the row, bit for bit: every target
  * get_output_grid_by_size makes (fregrid_util.c:588-654), whole or a rank's band.  1 (default): the legacy search finds the
  * candidates of a source cell by index arithmetic on the two axes and builds destination cells from per-column / per-row tables
