@@ -55,6 +55,7 @@ EXPORTS = [
     "fg_extrap_last_syncs", "fg_extrap_get_coef", "fg_extrap_coef_host", "fg_set_extrap_batch", "fg_set_extrap_coef",
     "fg_setup_vertical_interp", "fg_dev_vertical_interp",
     "fg_dev_latlon2xyz", "fg_plan_create_great_circle_lonlat", "fg_plan_create_great_circle_lonlat_dev",
+    "fg_plan_create_polylist_gc",
     "fg_runoff_create", "fg_runoff_create_from_xgrid", "fg_runoff_destroy", "fg_runoff_nxgrid", "fg_runoff_get_xgrid",
     "fg_runoff_get_maps", "fg_runoff_get_xyz", "fg_runoff_search_stats", "fg_runoff_phase_ms", "fg_runoff_stream", "fg_runoff_apply", "fg_runoff_apply_dev",
     "fg_nearest_unmasked", "fg_set_runoff_prune", "fg_runoff_tile",
@@ -65,7 +66,7 @@ EXPORTS = [
     "fg_topog_default_opts", "fg_topog_create", "fg_topog_destroy", "fg_topog_stream", "fg_topog_set_source", "fg_topog_get_source",
     "fg_topog_remap", "fg_topog_filter", "fg_topog_process", "fg_topog_run", "fg_topog_set_depth", "fg_topog_get", "fg_topog_stats",
     "fg_topog_phase_ms", "fg_plan_apply_frac_dev", "fg_set_topog_sweep",
-    "fg_coupler_create", "fg_coupler_destroy", "fg_coupler_stream", "fg_coupler_run", "fg_coupler_count", "fg_coupler_get",
+    "fg_coupler_create", "fg_coupler_create_gc", "fg_coupler_destroy", "fg_coupler_stream", "fg_coupler_run", "fg_coupler_count", "fg_coupler_get",
     "fg_coupler_get_cells", "fg_coupler_write", "fg_coupler_write_xgrid", "fg_coupler_write_mask", "fg_coupler_stats", "fg_coupler_phase_ms",
 ]
 
@@ -181,6 +182,11 @@ def lib():
     L.fg_plan_get_polygons.restype = C.c_int
     L.fg_plan_create_polylist.argtypes = [C.c_int, C.c_int, ip, dp, dp, dp, dp, C.c_int, C.c_int, dp, dp, C.c_int, C.POINTER(vp)]
     L.fg_plan_create_polylist.restype = C.c_long
+    L.fg_plan_create_polylist_gc.argtypes = [C.c_int, ip, dp, dp, dp, dp, C.c_int, C.c_int, dp, dp, C.c_int, C.POINTER(vp)]
+    L.fg_plan_create_polylist_gc.restype = C.c_long
+    # (plan_internal.h: the device-array twin, exported for the pipelines and the tests)
+    L.fg_plan_create_polylist_gc_dev.argtypes = [C.c_int] + [vp] * 5 + [C.c_int, C.c_int] + [vp] * 3 + [C.c_double, C.c_double, C.c_int, vp, C.c_int, C.POINTER(vp)]
+    L.fg_plan_create_polylist_gc_dev.restype = C.c_long
     L.fg_plan_get_cell_struct.argtypes = [vp, C.c_int] + [dp] * 5 + [ip] + [dp] * 2
     L.fg_plan_get_cell_struct.restype = C.c_int
     L.fg_plan_get_cell_area.argtypes = [vp, dp, dp]
@@ -504,6 +510,8 @@ def lib():
     L.fg_coupler_create.argtypes = [C.c_int, C.c_double, C.c_int, ip, ip, dpp, dpp, C.c_int, ip, ip, dpp, dpp, C.c_int, C.c_int, dp, dp, dp, C.c_int,
                                     C.c_int, C.POINTER(vp)]
     L.fg_coupler_create.restype = C.c_int
+    L.fg_coupler_create_gc.argtypes = L.fg_coupler_create.argtypes
+    L.fg_coupler_create_gc.restype = C.c_int
     L.fg_coupler_destroy.argtypes = [vp]
     L.fg_coupler_destroy.restype = None
     L.fg_coupler_stream.argtypes = [vp]

@@ -324,6 +324,32 @@ class XgridPlan:
                                             _dp(lo), _dp(la), device, C.byref(h)))
         return cls(h.value, order, device)
 
+    @classmethod
+    def create_polylist_gc(cls, n, x, y, z, area_ref, grid_out, device=0):
+        """A great-circle search whose source cells are convex polygons of 3..8 unit-vector vertices, clockwise
+        (fg_plan_create_polylist_gc): n [npoly], x / y / z [npoly, 8], area_ref [npoly]; grid_out in lon / lat.  First order."""
+        _lib.require_gpu()
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        x, y, z = (_f64(v).reshape(n.size, 8) for v in (x, y, z))
+        area_ref = _f64(area_ref).reshape(n.size)
+        lo, la = _f64(grid_out.lonc).reshape(-1), _f64(grid_out.latc).reshape(-1)
+        h = C.c_void_p()
+        check(lib().fg_plan_create_polylist_gc(n.size, _ip(n), _dp(x), _dp(y), _dp(z), _dp(area_ref), grid_out.nx, grid_out.ny,
+                                               _dp(lo), _dp(la), device, C.byref(h)))
+        return cls(h.value, 1, device, True)
+
+    @classmethod
+    def create_polylist_gc_dev(cls, n_t, x_t, y_t, z_t, area_ref_t, nx_out, ny_out, xyz_out_t, mean_dlat=0.0, mean_dlon=0.0,
+                               device=0, stream=None):
+        """create_polylist_gc on torch tensors already on the device (n_t int32, the others float64; xyz_out_t = (x, y, z) of the
+        destination corners).  stream None: a stream of the plan's own -- the tensors must be complete; they must outlive the call only."""
+        h = C.c_void_p()
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        check(lib().fg_plan_create_polylist_gc_dev(int(n_t.numel()), ptr(n_t), ptr(x_t), ptr(y_t), ptr(z_t), ptr(area_ref_t), nx_out, ny_out,
+                                                   ptr(xyz_out_t[0]), ptr(xyz_out_t[1]), ptr(xyz_out_t[2]), mean_dlat, mean_dlon, device,
+                                                   C.c_void_p(int(stream or 0)), 0 if stream is None else 1, C.byref(h)))
+        return cls(h.value, 1, device, True)
+
     def get_cell_area(self, ncells_out):
         a_in = np.empty(self.ncells_in, dtype=np.float64)
         a_out = np.empty(ncells_out, dtype=np.float64)

@@ -21,8 +21,10 @@ CouplerMosaic (fg_coupler_*, csrc/coupler.hip) is the tool's com
 :1198-2127 and :2466-2811 -- land on the atmosphere grid or of its own, the three lists, the per-cell area and centroid sums, the
 centroid distances, the land and ocean masks -- with the lists and polygons kept in device memory between the searches, and the
 exchange-grid and mask files through the library's classic-netCDF writer.  coupler_ocean_grid is the numpy mirror of the ocean
-grid preparation (:841-876, :940-955).  Not covered by either: nested atmosphere tiles, the wave grid, great-circle clip, several
-ocean tiles, --check's global sums, the MPI split, the coupler mosaic file.
+grid preparation (:841-876, :940-955).  CouplerMosaic(clip_method="great_circle") is the tool's GREAT_CIRCLE_CLIP branch
+(fg_coupler_create_gc, first order): unit vectors, clip_2dx2d_great_circle, and the remembered polygons searched by the great-circle
+polygon-list plan (XgridPlan.create_polylist_gc).  Not covered by either: nested atmosphere tiles, the wave grid, several ocean
+tiles, --check's global sums, the MPI split, the coupler mosaic file; coupler_xgrid is legacy clip only.
 """
 import ctypes as C
 import os
@@ -179,13 +181,18 @@ def write_mask_file(path, kind, fields):
 class CouplerMosaic:
     """RAII wrapper of fg_coupler.  atm: list of GridConfig (atmosphere tiles); lnd: None (land on the atmosphere grid,
     lnd_same_as_atm), one GridConfig or a list of them; ocn: one GridConfig, the grid the tool works on (coupler_ocean_grid's x, y);
-    omask [ny_ocn, nx_ocn]: the ocean fraction; ocn_south_ext: coupler_ocean_grid's.  Corners in radians."""
+    omask [ny_ocn, nx_ocn]: the ocean fraction; ocn_south_ext: coupler_ocean_grid's.  Corners in radians.
+    clip_method "legacy" (clip_2dx2d on lon / lat) or "great_circle" (the tool's GREAT_CIRCLE_CLIP branch, fg_coupler_create_gc:
+    clip_2dx2d_great_circle on unit vectors, what a grid with a pole inside a cell needs; interp_order must then be 1)."""
 
     AXL, AXO, LXO = 0, 1, 2
     ATM, LND, OCN = 0, 1, 2
 
-    def __init__(self, atm, lnd, ocn, omask, interp_order=2, area_ratio_thresh=AREA_RATIO_THRESH, ocn_south_ext=0, device=0):
+    def __init__(self, atm, lnd, ocn, omask, interp_order=2, area_ratio_thresh=AREA_RATIO_THRESH, ocn_south_ext=0, device=0, clip_method="legacy"):
         self._h = None
+        if clip_method not in ("legacy", "great_circle"):
+            raise ValueError("clip_method must be 'legacy' or 'great_circle'")
+        self.clip_method = clip_method
         require_gpu()
         self.atm = list(atm)
         self.same = lnd is None
@@ -208,9 +215,10 @@ class CouplerMosaic:
         kl, nxl, nyl, lol, lal = table(self.lnd)
         ko, _, _, _, _ = table([ocn])
         h = C.c_void_p()
-        check(lib().fg_coupler_create(self.order, float(area_ratio_thresh), len(self.atm), nxa, nya, loa, laa, 0 if self.same else len(self.lnd),
-                                      nxl, nyl, lol, lal, ocn.nx, ocn.ny, ko[0][0].ctypes.data_as(_dpt), ko[0][1].ctypes.data_as(_dpt),
-                                      om.ctypes.data_as(_dpt), self.ocn_south_ext, device, C.byref(h)))
+        create = lib().fg_coupler_create_gc if clip_method == "great_circle" else lib().fg_coupler_create
+        check(create(self.order, float(area_ratio_thresh), len(self.atm), nxa, nya, loa, laa, 0 if self.same else len(self.lnd),
+                     nxl, nyl, lol, lal, ocn.nx, ocn.ny, ko[0][0].ctypes.data_as(_dpt), ko[0][1].ctypes.data_as(_dpt),
+                     om.ctypes.data_as(_dpt), self.ocn_south_ext, device, C.byref(h)))
         self._h = h
 
     def destroy(self):

@@ -41,6 +41,14 @@ void fgd_cp_cand_flag(long n, const int *x_src, const int *x_dst, const double *
 void fgd_cp_cand_emit(long n, const int *x_src, const int *x_dst, const int *flag, const int *offs, const int *n_in, const double *lon_in,
                       const double *lat_in, const double *src_lon_avg, const double *area_atm, const double *area_lnd, int *pa, int *pl, int *pn,
                       double *plon, double *plat, double *lon_avg, double *area_ref, unsigned *err, hipStream_t st);
+// great-circle handle (GREAT_CIRCLE_CLIP).  The cells of a tile as [cell][4][3] clockwise unit vectors and four [cell] = 4 (what
+// fgd_gc_area_batch takes); land on the atmosphere grid: the :1507 test on those areas, flag and ref [cell] = min(area_lnd, area_atm)
+// of a remembered cell, +inf of any other; land of its own: the survivors of the plan's list with x / y / z [n][8]
+void fgd_cp_cells_xyz(int nx, int ny, const double *x, const double *y, const double *z, double *cells, int *four, hipStream_t st);
+void fgd_cp_same_gc_flag(long n, const double *xarea, const double *area, double thresh, int *flag, double *ref, hipStream_t st);
+void fgd_cp_cand_emit_gc(long n, const int *x_src, const int *x_dst, const int *flag, const int *offs, const int *n_in, const double *x_in,
+                         const double *y_in, const double *z_in, const double *area_atm, const double *area_lnd, int *pa, int *pl, int *pn,
+                         double *px, double *py, double *pz, double *area_ref, unsigned *err, hipStream_t st);
 // :1604-1661 and :2660-2686 on a plan's list: weight by the ocean fraction, the two tests, the survivors in order
 void fgd_cp_ocean_flag(long n, const int *x_src, const int *x_dst, const double *x_area, const double *omask, const double *area_ocn,
                        const double *area_src, double thresh, int *flag, hipStream_t st);

@@ -1,6 +1,7 @@
 // coupler.hip -- host orchestration of make_coupler_mosaic's exchange grids on the device (fg_coupler_*):
 // tools/make_coupler_mosaic/make_coupler_mosaic.c:1198-2127 (atmosphere x land, atmosphere x ocean, the per-cell sums, the
-// centroid distances, the masks) and :2466-2811 (land x ocean), legacy clip, one process, no nest, one ocean tile.
+// centroid distances, the masks) and :2466-2811 (land x ocean), one process, no nest, one ocean tile; LEGACY_CLIP (fg_coupler_create)
+// or GREAT_CIRCLE_CLIP at first order (fg_coupler_create_gc: unit vectors, great-circle plans, the n-gon polygon-list search).
 // Kernels: coupler_kernels.hip; shared declarations: coupler.h; design: DESIGN.md 3.13.
 //
 // The host decides what runs and how large the buffers are.  The three nested clip loops are plans (plan.hip) in the coupler's
@@ -22,11 +23,13 @@
 #include "coupler.h"
 #include "fg_host.h"
 #include "plan_internal.h"
+#include "xgrid_device.h"
 
 namespace {
 struct Grid {                                   // one tile in device memory
   int nx = 0, ny = 0, off = 0;                  // off: first cell in the grid's flattened numbering
   double *lon = nullptr, *lat = nullptr;
+  double *x = nullptr, *y = nullptr, *z = nullptr;   // great-circle handle: the corners as unit vectors (fg_dev_latlon2xyz)
   double dlat = 0, dlon = 0;                    // what a search with this tile as destination takes (fg_dst_extents)
   int rect_hint = 0;
   long ncells() const { return (long)nx * ny; }
@@ -35,6 +38,7 @@ struct Cand {                                   // the remembered atmosphere x l
   int n = 0;
   int *pa = nullptr, *pl = nullptr, *pn = nullptr;
   double *plon = nullptr, *plat = nullptr, *lon_avg = nullptr, *area_ref = nullptr;
+  double *px = nullptr, *py = nullptr, *pz = nullptr;      // great-circle handle: the vertices as unit vectors, [n][8] each
 };
 }  // namespace
 
@@ -42,6 +46,8 @@ struct fg_coupler {
   int device = 0, order = 2, south_ext = 0;
   double thresh = 1.0e-6;
   bool same = false;                            // land on the atmosphere grid (lnd_same_as_atm)
+  bool gc = false;                              // GREAT_CIRCLE_CLIP (fg_coupler_create_gc): every clip is clip_2dx2d_great_circle, order 1
+  int *d_iota = nullptr;                        // great-circle handle, land on the atmosphere grid: 0 .. na - 1
   hipStream_t stream = nullptr;
   FgDev dev;                                    // grids, areas, the ocean fraction: as long as the handle
   std::unique_ptr<FgDev> res;                   // what a run leaves: replaced by the next run
@@ -67,7 +73,11 @@ extern "C" void fg_coupler_destroy(fg_coupler *h)
 {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
+  if (h->stream) {
+    (void)hipStreamSynchronize(h->stream);
+    fg_pool_retire_stream(h->stream);             // the plans of the runs left blocks and events tagged with this stream in the pool
+    (void)hipStreamDestroy(h->stream);
+  }
   delete h;
 }
 extern "C" void *fg_coupler_stream(fg_coupler *h) { return h ? (void *)h->stream : nullptr; }
@@ -92,6 +102,37 @@ static int cp_grid_area(fg_coupler *h, const std::vector<Grid> &g, const double 
   return e;
 }
 
+// get_grid_great_circle_area of the tiles of one grid (:607, :731, :890): the source records of a great-circle search against a dummy cell
+static int cp_grid_area_gc(fg_coupler *h, const std::vector<Grid> &g, const double *d_dummy, double *area)
+{
+  std::vector<int> nx, ny;
+  std::vector<const double *> x, y, z;
+  for (const Grid &t : g) { nx.push_back(t.nx); ny.push_back(t.ny); x.push_back(t.x); y.push_back(t.y); z.push_back(t.z); }
+  fg_plan *pl = nullptr;
+  const long rc = fg_plan_create_great_circle_dev((int)g.size(), nx.data(), ny.data(), x.data(), y.data(), z.data(), nullptr, 1, 1, d_dummy, d_dummy + 4,
+                                                  d_dummy + 8, 0.01, 0.01, h->device, h->stream, 1, &pl);
+  if (rc < 0) return (int)rc;
+  FgPlanView v;
+  int e = fg_plan_view(pl, &v);
+  if (!e && hipMemcpyAsync(area, v.src_area, (size_t)v.nsrc * sizeof(double), hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+    e = fg_fail(FG_ERR_HIP, "fg_coupler_create_gc: copying the cell areas failed");
+  if (!e && hipStreamSynchronize(h->stream) != hipSuccess) e = fg_fail(FG_ERR_HIP, "fg_coupler_create_gc: the cell areas failed");
+  fg_plan_destroy(pl);
+  return e;
+}
+// latlon2xyz of every tile's corners on the device (:598-612, :722-760, :881-890), queued on the handle's stream
+static int cp_grid_xyz(fg_coupler *h, std::vector<Grid> *g)
+{
+  for (Grid &t : *g) {
+    const size_t np = (size_t)(t.nx + 1) * (t.ny + 1);
+    double *d = h->dev.get<double>(3 * np);
+    if (!d) return fg_fail(FG_ERR_HIP, "fg_coupler_create_gc: out of device memory");
+    t.x = d; t.y = d + np; t.z = d + 2 * np;
+    if (int rc = fg_dev_latlon2xyz((long)np, t.lon, t.lat, t.x, t.y, t.z, h->device, h->stream)) return rc;
+  }
+  return 0;
+}
+
 static int cp_put_grid(fg_coupler *h, const char *what, int ntiles, const int *nx, const int *ny, const double *const *lon, const double *const *lat,
                        std::vector<Grid> *out, int *total)
 {
@@ -113,14 +154,16 @@ static int cp_put_grid(fg_coupler *h, const char *what, int ntiles, const int *n
   return 0;
 }
 
-extern "C" int fg_coupler_create(int interp_order, double area_ratio_thresh, int ntile_atm, const int *nxa, const int *nya,
-                                 const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nxl, const int *nyl,
-                                 const double *const *lon_lnd, const double *const *lat_lnd, int nxo, int nyo, const double *lon_ocn,
-                                 const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out)
+static int cp_create(bool gc, int interp_order, double area_ratio_thresh, int ntile_atm, const int *nxa, const int *nya,
+                     const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nxl, const int *nyl,
+                     const double *const *lon_lnd, const double *const *lat_lnd, int nxo, int nyo, const double *lon_ocn,
+                     const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out)
 {
   if (!out) return fg_fail(FG_ERR_ARG, "fg_coupler_create: null output handle");
   *out = nullptr;
   if (interp_order != 1 && interp_order != 2) return fg_fail(FG_ERR_ARG, "make_coupler_mosaic: interp_order should be 1 or 2");
+  if (gc && interp_order != 1)                 // :593
+    return fg_fail(FG_ERR_ARG, "make_coupler_mosaic:  Currenly only implement interp_order = 1 when clip_method = 'conserve_great_circle'");
   // the searches accept a pair at area / min(area1, area2) > 1e-6 (create_xgrid.c); the coupler's own tests can only reject more
   // when its threshold is no smaller and the fractions are no larger than 1
   if (!(area_ratio_thresh >= 1.0e-6)) return fg_fail(FG_ERR_ARG, "fg_coupler_create: area_ratio_thresh %g is below 1e-6, the ratio at which the searches accept a pair", area_ratio_thresh);
@@ -133,36 +176,69 @@ extern "C" int fg_coupler_create(int interp_order, double area_ratio_thresh, int
   fg_coupler *h = new fg_coupler;
   struct Guard { fg_coupler *&h; bool keep = false; ~Guard() { if (!keep) fg_coupler_destroy(h); } } guard{h};
   h->device = device; h->order = interp_order; h->thresh = area_ratio_thresh; h->south_ext = ocn_south_ext; h->same = ntile_lnd == 0;
+  h->gc = gc;
   if (int rc = fg_use_device("fg_coupler_create", device)) return rc;
   const double t0 = fg_now_ms();
   FGCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   if (int rc = cp_put_grid(h, "atmosphere", ntile_atm, nxa, nya, lon_atm, lat_atm, &h->atm, &h->na)) return rc;
+  if (gc) if (int rc = cp_grid_xyz(h, &h->atm)) return rc;
   if (h->same) { h->lnd = h->atm; h->nl = h->na; }
-  else if (int rc = cp_put_grid(h, "land", ntile_lnd, nxl, nyl, lon_lnd, lat_lnd, &h->lnd, &h->nl)) return rc;
+  else {
+    if (int rc = cp_put_grid(h, "land", ntile_lnd, nxl, nyl, lon_lnd, lat_lnd, &h->lnd, &h->nl)) return rc;
+    if (gc) if (int rc = cp_grid_xyz(h, &h->lnd)) return rc;
+  }
   {
     std::vector<Grid> o;
     const double *lo[1] = {lon_ocn}, *la[1] = {lat_ocn};
     if (int rc = cp_put_grid(h, "ocean", 1, &nxo, &nyo, lo, la, &o, &h->no)) return rc;
+    if (gc) if (int rc = cp_grid_xyz(h, &o)) return rc;
     h->ocn = o[0];
   }
   std::vector<int> aoff;
   for (const Grid &g : h->atm) aoff.push_back(g.off);
   aoff.push_back(h->na);
   const double dummy[8] = {0, 0.01, 0, 0.01, 0, 0, 0.01, 0.01};
-  const double *d_dummy = h->dev.put(dummy, 8);
+  double dummy_xyz[12];                          // the same cell as unit vectors: x[4] | y[4] | z[4]
+  fg_latlon2xyz(4, dummy, dummy + 4, dummy_xyz, dummy_xyz + 4, dummy_xyz + 8);
+  const double *d_dummy = gc ? h->dev.put(dummy_xyz, 12) : h->dev.put(dummy, 8);
   h->area_atm = h->dev.get<double>(h->na); h->area_ocn = h->dev.get<double>(h->no);
   h->area_lnd = h->same ? h->area_atm : h->dev.get<double>(h->nl);
   h->omask = h->dev.put(omask, (size_t)h->no);
   h->d_aoff = h->dev.put(aoff);
+  if (gc && h->same) {
+    std::vector<int> iota((size_t)h->na);
+    for (int c = 0; c < h->na; c++) iota[(size_t)c] = c;
+    h->d_iota = h->dev.put(iota);
+    if (!h->d_iota) return fg_fail(FG_ERR_HIP, "fg_coupler_create: device allocation or upload failed");
+  }
   if (!d_dummy || !h->area_atm || !h->area_ocn || !h->area_lnd || !h->omask || !h->d_aoff)
     return fg_fail(FG_ERR_HIP, "fg_coupler_create: device allocation or upload failed");
-  if (int rc = cp_grid_area(h, h->atm, d_dummy, h->area_atm)) return rc;
-  if (!h->same) if (int rc = cp_grid_area(h, h->lnd, d_dummy, h->area_lnd)) return rc;
-  if (int rc = cp_grid_area(h, std::vector<Grid>{h->ocn}, d_dummy, h->area_ocn)) return rc;
+  const auto grid_area = gc ? cp_grid_area_gc : cp_grid_area;
+  if (int rc = grid_area(h, h->atm, d_dummy, h->area_atm)) return rc;
+  if (!h->same) if (int rc = grid_area(h, h->lnd, d_dummy, h->area_lnd)) return rc;
+  if (int rc = grid_area(h, std::vector<Grid>{h->ocn}, d_dummy, h->area_ocn)) return rc;
   h->ms[0] = (float)(fg_now_ms() - t0);
   guard.keep = true;
   *out = h;
   return 0;
+}
+
+extern "C" int fg_coupler_create(int interp_order, double area_ratio_thresh, int ntile_atm, const int *nxa, const int *nya,
+                                 const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nxl, const int *nyl,
+                                 const double *const *lon_lnd, const double *const *lat_lnd, int nxo, int nyo, const double *lon_ocn,
+                                 const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out)
+{
+  return cp_create(false, interp_order, area_ratio_thresh, ntile_atm, nxa, nya, lon_atm, lat_atm, ntile_lnd, nxl, nyl, lon_lnd, lat_lnd, nxo, nyo,
+                   lon_ocn, lat_ocn, omask, ocn_south_ext, device, out);
+}
+// GREAT_CIRCLE_CLIP (:587-594): the same arguments; interp_order must be 1
+extern "C" int fg_coupler_create_gc(int interp_order, double area_ratio_thresh, int ntile_atm, const int *nxa, const int *nya,
+                                    const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nxl, const int *nyl,
+                                    const double *const *lon_lnd, const double *const *lat_lnd, int nxo, int nyo, const double *lon_ocn,
+                                    const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out)
+{
+  return cp_create(true, interp_order, area_ratio_thresh, ntile_atm, nxa, nya, lon_atm, lat_atm, ntile_lnd, nxl, nyl, lon_lnd, lat_lnd, nxo, nyo,
+                   lon_ocn, lat_ocn, omask, ocn_south_ext, device, out);
 }
 
 // --------------------------------------------------------------------------------------------------------------- the run
@@ -217,8 +293,15 @@ struct Run {
     std::vector<const double *> lon, lat;
     for (int t = 0; t < ntiles; t++) { nx_.push_back(src[t].nx); ny.push_back(src[t].ny); lon.push_back(src[t].lon); lat.push_back(src[t].lat); }
     h->searches++;
-    const long nx = fg_plan_create_dev_hint(h->order, ntiles, nx_.data(), ny.data(), lon.data(), lat.data(), dst.nx, dst.ny, dst.lon, dst.lat, dst.dlat,
-                                            dst.dlon, dst.rect_hint, h->device, st, pl);
+    long nx;
+    if (h->gc) {                                   // clip_2dx2d_great_circle on every pair the caps let through
+      std::vector<const double *> x, y, z;
+      for (int t = 0; t < ntiles; t++) { x.push_back(src[t].x); y.push_back(src[t].y); z.push_back(src[t].z); }
+      nx = fg_plan_create_great_circle_dev(ntiles, nx_.data(), ny.data(), x.data(), y.data(), z.data(), nullptr, dst.nx, dst.ny, dst.x, dst.y, dst.z,
+                                           dst.dlat, dst.dlon, h->device, st, 1, pl);
+    } else
+      nx = fg_plan_create_dev_hint(h->order, ntiles, nx_.data(), ny.data(), lon.data(), lat.data(), dst.nx, dst.ny, dst.lon, dst.lat, dst.dlat,
+                                   dst.dlon, dst.rect_hint, h->device, st, pl);
     if (nx >= 0) h->d2h += fg_plan_search_d2h(*pl);
     return nx;
   }
@@ -235,8 +318,58 @@ struct Run {
   {
     const size_t m = (size_t)(n > 0 ? n : 1);
     c->pa = res.get<int>(m); c->pl = res.get<int>(m); c->pn = res.get<int>(m);
-    c->plon = res.get<double>(m * 8); c->plat = res.get<double>(m * 8); c->lon_avg = res.get<double>(m); c->area_ref = res.get<double>(m);
+    c->area_ref = res.get<double>(m);
+    if (h->gc) {                                   // unit vectors; no longitude frame, so no lon_avg
+      c->px = res.get<double>(m * 8); c->py = res.get<double>(m * 8); c->pz = res.get<double>(m * 8);
+      return c->pa && c->pl && c->pn && c->area_ref && c->px && c->py && c->pz;
+    }
+    c->plon = res.get<double>(m * 8); c->plat = res.get<double>(m * 8); c->lon_avg = res.get<double>(m);
     return c->pa && c->pl && c->pn && c->plon && c->plat && c->lon_avg && c->area_ref;
+  }
+  // great-circle handle, :1426-1437 and :1483-1507 for the cells of atmosphere tile t: the remembered polygon is the cell itself, so
+  // only its flag is kept -- ref [cells of the tile] = min(area_lnd, area_atm) where the cell is remembered, +inf where it is not
+  // (no term and no list entry can then pass a ratio test)
+  int cand_same_gc(int t, double *ref, long *count)
+  {
+    const Grid &g = h->atm[t];
+    const long n = g.ncells();
+    FgDev tmp;
+    double *cells = tmp.get<double>((size_t)n * 12), *xarea = tmp.get<double>((size_t)n);
+    int *four = tmp.get<int>((size_t)n), *flag = tmp.get<int>((size_t)n), *offs = nullptr, total = 0;
+    if (!cells || !xarea || !four || !flag) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    fgd_cp_cells_xyz(g.nx, g.ny, g.x, g.y, g.z, cells, four, st);
+    fgd_gc_area_batch((int)n, 4, cells, four, xarea, st);                                  // :1485 on the four corners as they are
+    fgd_cp_same_gc_flag(n, xarea, h->area_atm + g.off, h->thresh, flag, ref, st);
+    if (int rc = scan_total(tmp, n, flag, &offs, &total)) return rc;
+    *count = total;
+    return 0;
+  }
+  // great-circle handle, :1439 and :1483-1548 for land tile t of its own
+  int cand_own_gc(int t, Cand *c)
+  {
+    const Grid &g = h->lnd[t];
+    fg_plan *pl = nullptr;
+    const long nx = search((int)h->atm.size(), h->atm, g, &pl);
+    if (nx < 0) return (int)nx;
+    struct Destroy { fg_plan *p; ~Destroy() { fg_plan_destroy(p); } } destroy{pl};
+    FgPlanView v;
+    if (int rc = fg_plan_view(pl, &v)) return rc;
+    FgDev tmp;
+    const size_t m = (size_t)(nx > 0 ? nx : 1);
+    int *flag = tmp.get<int>(m), *pn = tmp.get<int>(m), *offs = nullptr, total = 0;
+    double *px = tmp.get<double>(m * 8), *py = tmp.get<double>(m * 8), *pz = tmp.get<double>(m * 8);
+    if (!flag || !pn || !px || !py || !pz) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    const double *area_lnd = h->area_lnd + g.off;
+    if (nx > 0) if (int rc = fg_plan_polygons_gc_dev(pl, pn, px, py, pz)) return rc;
+    fgd_cp_cand_flag(nx, v.x_src, v.x_dst, v.x_area, h->area_atm, area_lnd, h->thresh, flag, st);
+    if (int rc = scan_total(tmp, nx, flag, &offs, &total)) return rc;
+    if (!alloc_cand(c, total)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    c->n = total;
+    fgd_cp_cand_emit_gc(nx, v.x_src, v.x_dst, flag, offs, pn, px, py, pz, h->area_atm, area_lnd, c->pa, c->pl, c->pn, c->px, c->py, c->pz, c->area_ref,
+                        d_err, st);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(st));
+    return 0;
   }
   // :1463-1477 for the cells of atmosphere tile t
   int cand_same(int t, Cand *c)
@@ -284,12 +417,14 @@ struct Run {
     return 0;
   }
   // :1604-1661 (src = the atmosphere) and :2598-2690 (src = one land tile): the search, the ocean-fraction tests, the survivors
-  int ocean_list(int ntiles, const std::vector<Grid> &src, const double *area_src, CpList *out)
+  // keep != null: the plan is handed to the caller instead of destroyed (great-circle handle with land on the atmosphere grid: step 4
+  // works on the same pairs)
+  int ocean_list(int ntiles, const std::vector<Grid> &src, const double *area_src, CpList *out, fg_plan **keep = nullptr)
   {
     fg_plan *pl = nullptr;
     const long nx = search(ntiles, src, h->ocn, &pl);
     if (nx < 0) return (int)nx;
-    struct Destroy { fg_plan *p; ~Destroy() { fg_plan_destroy(p); } } destroy{pl};
+    struct Destroy { fg_plan *p; fg_plan **keep; ~Destroy() { if (keep && *keep == p) return; fg_plan_destroy(p); } } destroy{pl, keep};
     FgPlanView v;
     if (int rc = fg_plan_view(pl, &v)) return rc;
     FgDev tmp;
@@ -302,7 +437,49 @@ struct Run {
     fgd_cp_ocean_emit(nx, v.x_src, v.x_dst, v.x_area, v.x_c1, v.x_c2, h->omask, flag, offs, *out, st);
     FGCHK(hipGetLastError());
     FGCHK(hipStreamSynchronize(st));
+    if (keep) *keep = pl;
     return 0;
+  }
+  // the tail of :1662-1719 for `npoly` polygons numbered as x_src numbers them: the sums per polygon, the final test, the list.
+  // pa / pl: the atmosphere cell and the land cell of every polygon
+  int poly_tail(int npoly, const FgPlanView &v, const double *area_ref, const int *pa, const int *pl_, std::vector<CpList *> outs,
+                const std::vector<int> &first, const std::vector<int> &count)
+  {
+    FgDev tmp;
+    const size_t m = (size_t)(npoly > 0 ? npoly : 1);
+    double *s_area = tmp.get<double>(m), *s_clon = tmp.get<double>(m), *s_clat = tmp.get<double>(m);
+    int *flag = tmp.get<int>(m);
+    if (!s_area || !s_clon || !s_clat || !flag) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    fgd_cp_poly_sums(npoly, v.nx, v.x_src, v.x_dst, v.x_area, v.x_c1, v.x_c2, h->omask, area_ref, h->thresh, s_area, s_clon, s_clat, flag, st);
+    for (size_t q = 0; q < outs.size(); q++) {           // one list per land tile: polygons [first, first + count)
+      int *offs = nullptr, total = 0;
+      const int f = first[q], n = count[q];
+      if (int rc = scan_total(tmp, n, flag + f, &offs, &total)) return rc;
+      if (!alloc_list(outs[q], total)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+      outs[q]->n = total;
+      // (pa is indexed by polygon, hence + f; pl_ is NOT offset when f > 0: that only happens with land on the atmosphere grid, where
+      // pl_ is 0, 1, 2, ... and the land cell of the tile's polygon q is q, the cell's index inside its tile)
+      fgd_cp_poly_emit(n, pa + f, pl_, s_area + f, s_clon + f, s_clat + f, flag + f, offs, *outs[q], st);
+      FGCHK(hipGetLastError());
+      FGCHK(hipStreamSynchronize(st));
+    }
+    return 0;
+  }
+  // great-circle handle, :1662-1719 with land of its own: the polygon-list search, then the tail
+  int poly_list_gc(const Cand &c, CpList *out)
+  {
+    if (c.n == 0) { if (!alloc_list(out, 0)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory"); return 0; }
+    fg_plan *pl = nullptr;
+    h->searches++;
+    const Grid &o = h->ocn;
+    const long nx = fg_plan_create_polylist_gc_dev(c.n, c.pn, c.px, c.py, c.pz, c.area_ref, o.nx, o.ny, o.x, o.y, o.z, o.dlat, o.dlon, h->device, st, 1, &pl);
+    if (nx == FG_ERR_MAXV) return fg_fail(FG_ERR_GEOM, "fg_coupler_run: an atmosphere x land polygon has more than 8 vertices");
+    if (nx < 0) return (int)nx;
+    struct Destroy { fg_plan *p; ~Destroy() { fg_plan_destroy(p); } } destroy{pl};
+    h->d2h += fg_plan_search_d2h(pl);
+    FgPlanView v;
+    if (int rc = fg_plan_view(pl, &v)) return rc;
+    return poly_tail(c.n, v, c.area_ref, c.pa, c.pl, {out}, {0}, {c.n});
   }
   // :1662-1719: the remembered polygons against the ocean cells over land, the sums per polygon, the final area test
   int poly_list(const Cand &c, CpList *out)
@@ -374,18 +551,43 @@ struct Run {
     double t0 = fg_now_ms();
     // 2. atmosphere x land candidates
     std::vector<Cand> cand(ntl);
+    const bool same_gc = h->gc && h->same;
+    double *same_ref = nullptr;                    // great-circle handle, land on the atmosphere grid: see cand_same_gc
+    if (same_gc) {
+      same_ref = res.get<double>((size_t)h->na);
+      if (!same_ref) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+    }
     for (int t = 0; t < ntl; t++) {
-      if (int rc = h->same ? cand_same(t, &cand[t]) : cand_own(t, &cand[t])) return rc;
+      if (same_gc) {
+        long count = 0;
+        if (int rc = cand_same_gc(t, same_ref + h->atm[t].off, &count)) return rc;
+        h->ncand += count;
+        continue;
+      }
+      if (int rc = h->same ? cand_same(t, &cand[t]) : (h->gc ? cand_own_gc(t, &cand[t]) : cand_own(t, &cand[t]))) return rc;
       h->ncand += cand[t].n;
     }
     if (int rc = check_err()) return rc;
     double t1 = fg_now_ms(); h->ms[1] = (float)(t1 - t0); t0 = t1;
     // 3. atmosphere x ocean over sea
-    if (int rc = ocean_list((int)h->atm.size(), h->atm, h->area_atm, &h->axo)) return rc;
+    fg_plan *axo_plan = nullptr;
+    struct Destroy { fg_plan *&p; ~Destroy() { fg_plan_destroy(p); } } destroy_axo{axo_plan};
+    if (int rc = ocean_list((int)h->atm.size(), h->atm, h->area_atm, &h->axo, same_gc ? &axo_plan : nullptr)) return rc;
     t1 = fg_now_ms(); h->ms[2] = (float)(t1 - t0); t0 = t1;
     // 4. the remembered polygons x ocean over land
     h->axl.assign(ntl, CpList{});
-    for (int t = 0; t < ntl; t++) if (int rc = poly_list(cand[t], &h->axl[t])) return rc;
+    if (same_gc) {
+      // the remembered polygon IS the atmosphere cell: its clips against the ocean cells are step 3's pairs, whose unweighted areas the
+      // plan still holds (a pair that passes :1678 passes the plan's own test: lnd_frac <= 1, thresh >= 1e-6, min(.., area_ocn) <= area_atm)
+      FgPlanView v;
+      if (int rc = fg_plan_view(axo_plan, &v)) return rc;
+      std::vector<CpList *> outs;
+      std::vector<int> first, count;
+      for (int t = 0; t < ntl; t++) { outs.push_back(&h->axl[t]); first.push_back(h->atm[t].off); count.push_back((int)h->atm[t].ncells()); }
+      if (int rc = poly_tail(h->na, v, same_ref, h->d_iota, h->d_iota, outs, first, count)) return rc;
+      fg_plan_destroy(axo_plan); axo_plan = nullptr;
+    } else
+    for (int t = 0; t < ntl; t++) if (int rc = h->gc ? poly_list_gc(cand[t], &h->axl[t]) : poly_list(cand[t], &h->axl[t])) return rc;
     t1 = fg_now_ms(); h->ms[3] = (float)(t1 - t0); t0 = t1;
     // 5. land x ocean
     h->lxo.assign(h->same ? 0 : ntl, CpList{});
@@ -444,9 +646,10 @@ extern "C" int fg_coupler_run(fg_coupler *h)
   h->res.reset(new FgDev);
   h->d2h = 0; h->searches = 0; h->ncand = 0; h->nbad = 0;
   Run r{h, *h->res, h->stream};
-  const int saved = fg_search_frame_override(1);          // fix_lon(cell, xa_avg) per pair (:1455, :1597, :2652), for this thread's searches only
+  // legacy: fix_lon(cell, xa_avg) per pair (:1455, :1597, :2652), for this thread's searches only; unit vectors have no frame
+  const int saved = h->gc ? 0 : fg_search_frame_override(1);
   const int rc = r.go();
-  fg_search_frame_override(saved);
+  if (!h->gc) fg_search_frame_override(saved);
   if (rc) { (void)hipStreamSynchronize(h->stream); h->res.reset(); return rc; }
   h->ran = true;
   h->ms[6] = (float)(fg_now_ms() - t0);

@@ -182,6 +182,61 @@ void fgd_cp_cand_emit(long n, const int *x_src, const int *x_dst, const int *fla
                                                                pa, pl, pn, plon, plat, lon_avg, area_ref, err);
 }
 
+// ------------------------------------------------------------------------------------------ great-circle handle (GREAT_CIRCLE_CLIP)
+// the cells of one tile as [cell][4][3] unit vectors, clockwise (:1367-1375): (j, i) (j+1, i) (j+1, i+1) (j, i+1); four [cell] = 4
+__global__ __launch_bounds__(256) void k_cp_cells_xyz(int nx, int ny, const double *x, const double *y, const double *z, double *cells, int *four)
+{
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= nx * ny) return;
+  const int j = c / nx, i = c - j * nx;
+  const long n[4] = {(long)j * (nx + 1) + i, (long)(j + 1) * (nx + 1) + i, (long)(j + 1) * (nx + 1) + i + 1, (long)j * (nx + 1) + i + 1};
+  double *o = cells + (size_t)c * 12;
+  for (int q = 0; q < 4; q++) { o[q * 3] = x[n[q]]; o[q * 3 + 1] = y[n[q]]; o[q * 3 + 2] = z[n[q]]; }
+  four[c] = 4;
+}
+// land on the atmosphere grid (:1426-1437): the polygon is the cell, xarea its great_circle_area (:1485); the :1507 test
+__global__ __launch_bounds__(256) void k_cp_same_gc_flag(long n, const double *xarea, const double *area, double thresh, int *flag, double *ref)
+{
+  const long c = (long)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const double min_area = CP_MIN(area[c], area[c]);                        // :1488, area_lnd is area_atm here
+  const int keep = xarea[c] / min_area > thresh;                           // :1507
+  flag[c] = keep;
+  ref[c] = keep ? min_area : (double)INFINITY;                             // :1677, :1703; not remembered: nothing passes a ratio against it
+}
+// land of its own (:1517-1534): the survivors of the plan's list with their vertices as unit vectors
+__global__ __launch_bounds__(256) void k_cp_cand_emit_gc(long n, const int *x_src, const int *x_dst, const int *flag, const int *offs, const int *n_in,
+                                                          const double *x_in, const double *y_in, const double *z_in, const double *area_atm,
+                                                          const double *area_lnd, int *pa, int *pl, int *pn, double *px, double *py, double *pz,
+                                                          double *area_ref, unsigned *err)
+{
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n || !flag[k]) return;
+  const int o = offs[k], a = x_src[k], l = x_dst[k], nv = n_in[k];
+  if (nv > G_MAXV) atomicOr(err, CP_ERR_MAXV);
+  pa[o] = a; pl[o] = l; pn[o] = nv;
+  for (int q = 0; q < 8; q++) {
+    px[(size_t)o * 8 + q] = x_in[(size_t)k * 8 + q]; py[(size_t)o * 8 + q] = y_in[(size_t)k * 8 + q]; pz[(size_t)o * 8 + q] = z_in[(size_t)k * 8 + q];
+  }
+  const double al = area_lnd[l], aa = area_atm[a];
+  area_ref[o] = CP_MIN(al, aa);                                            // :1677, :1703
+}
+void fgd_cp_cells_xyz(int nx, int ny, const double *x, const double *y, const double *z, double *cells, int *four, hipStream_t st)
+{
+  k_cp_cells_xyz<<<cp_blocks((long)nx * ny, 256), 256, 0, st>>>(nx, ny, x, y, z, cells, four);
+}
+void fgd_cp_same_gc_flag(long n, const double *xarea, const double *area, double thresh, int *flag, double *ref, hipStream_t st)
+{
+  if (n > 0) k_cp_same_gc_flag<<<cp_blocks(n, 256), 256, 0, st>>>(n, xarea, area, thresh, flag, ref);
+}
+void fgd_cp_cand_emit_gc(long n, const int *x_src, const int *x_dst, const int *flag, const int *offs, const int *n_in, const double *x_in,
+                         const double *y_in, const double *z_in, const double *area_atm, const double *area_lnd, int *pa, int *pl, int *pn,
+                         double *px, double *py, double *pz, double *area_ref, unsigned *err, hipStream_t st)
+{
+  if (n > 0) k_cp_cand_emit_gc<<<cp_blocks(n, 256), 256, 0, st>>>(n, x_src, x_dst, flag, offs, n_in, x_in, y_in, z_in, area_atm, area_lnd, pa, pl, pn,
+                                                                  px, py, pz, area_ref, err);
+}
+
 // ------------------------------------------------------------------------ a grid x ocean over sea (:1601-1659, :2628, :2660-2686)
 __global__ __launch_bounds__(256) void k_cp_ocean_flag(long n, const int *x_src, const int *x_dst, const double *x_area, const double *omask,
                                                         const double *area_ocn, const double *area_src, double thresh, int *flag)

@@ -18,7 +18,8 @@
 // without one, release_all) or until seal(stream) / a put with seal = true on the same stream, which records ONE event for all
 // of them.  The pool touches a stream only inside such calls of the stream's user, or -- for unsealed batches -- later: the caller
 // leaves a batch unsealed only while it vouches for the stream's life (a plan on a caller's stream seals at fg_plan_destroy at the
-// latest; the library's own cached streams are never destroyed).  Recording every batch at its put cost 9 us per plan on the
+// latest; the library's own cached streams are never destroyed; whoever destroys a stream that plans ran on calls retire(stream)
+// first).  Recording every batch at its put cost 9 us per plan on the
 // MI355X (profiles/stream_ordered_plans_summary.md).  An event goes back to the event cache when the last block that shares it
 // leaves the free list.
 // The bookkeeping knows nothing of HIP: every device call goes through the policy H, so that tests/hostcheck/pool_check.cpp
@@ -68,6 +69,18 @@ template <class H> struct DevPool {
 
   // one event, recorded now, for every batch of `stream` that has none: afterwards the pool does not touch the stream again
   void seal(Stream stream) { std::lock_guard<std::mutex> lk(mu); seal_locked(stream); }
+
+  // The caller has synchronised `stream` and is about to destroy it.  Nothing on the device uses the stream's blocks any more, so
+  // they become untagged and their events go back to the cache: no event that was recorded on the stream stays in the pool.  (The
+  // runtime follows an event back to the stream it was recorded on when it is asked about the event -- hipEventQuery on an event of
+  // a destroyed stream reads freed memory and has answered "operation not permitted when stream is capturing".)
+  void retire(Stream stream)
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto &kv : free_)
+      for (FreeBlock &b : kv.second)
+        if (b.batch && b.batch->stream == stream) { Batch *t = b.batch; b.batch = nullptr; unref(t); }
+  }
 
   // waits for every tagged block's batch, then frees every cached block
   void release_all()

@@ -30,10 +30,17 @@
 #define GC_NCAP 14          // nodes per grid list: 4 corners + at most 8 intersections (convex x convex) + slack
 #define GC_ICAP 12          // intersection list
 #define GC_PCAP 16          // output polygon
+// n-gon x quad (gc_clip_t with N1 = 8, the polygon-list search): a convex quad's four edges cross the boundary of a convex 8-gon
+// at most twice each, so 8 intersections; list 1 then holds 8 corners + 8 intersections, list 2 stays 4 + 8.  Same slack as above.
+// The output polygon is the intersection of a convex 8-gon and a convex quad: at most 8 + 4 = 12 vertices (every edge of the
+// result lies on a different edge of one of the two), so GC_PCAP 16 holds it.  Anything beyond a capacity is error -9.
+#define GC_NGON 8
+#define GC_NCAP_NGON 18     // list 1 of the n-gon clip: 8 corners + 8 intersections + slack
 
 struct GcNode { double x, y, z, u; int intersect, inbound, inside, pad; };
 struct GcInter { double x, y, z, u, u_clip; int subj_index, clip_index, inbound, pad; };
-struct GcList { int n; GcNode v[GC_NCAP]; };
+template <int CAP> struct GcListT { static constexpr int cap = CAP; int n; GcNode v[CAP]; };
+typedef GcListT<GC_NCAP> GcList;
 
 __device__ __forceinline__ bool gc_same_point(double x1, double y1, double z1, double x2, double y2, double z2)
 {
@@ -79,7 +86,8 @@ __device__ double gc_area(int n, const double *p, int stride)
 
 // insidePolygon, mosaic_util.c:1546-1589.  The angle sum is only compared with 2*pi to 1e-8, so it is taken with the
 // fast acos first and redone with the exact one only if it lands within 1e-12 of the threshold.
-__device__ int gc_inside_polygon(const GcNode &node, const GcList &l)
+template <class L>
+__device__ int gc_inside_polygon(const GcNode &node, const L &l)
 {
   const double pnt0[3] = {node.x, node.y, node.z};
   double anglesum = 0;
@@ -201,17 +209,19 @@ __device__ int gc_line_intersect(const double *a1, const double *a2, const doubl
 }
 
 // addEnd (mosaic_util.c:1096-1135) on a grid list: append unless a point within 1e-10 is present
-__device__ int gc_add_end(GcList &l, double x, double y, double z, int intersect, double u, int inbound, int inside)
+template <class L>
+__device__ int gc_add_end(L &l, double x, double y, double z, int intersect, double u, int inbound, int inside)
 {
   for (int k = 0; k < l.n; k++) if (gc_same_point(l.v[k].x, l.v[k].y, l.v[k].z, x, y, z)) return 0;
-  if (l.n >= GC_NCAP) return -9;
+  if (l.n >= L::cap) return -9;
   GcNode &t = l.v[l.n++];
   t.x = x; t.y = y; t.z = z; t.u = u; t.intersect = intersect; t.inbound = inbound; t.inside = inside; t.pad = 0;
   return 0;
 }
 
 // insertIntersect, mosaic_util.c:1313-1397
-__device__ int gc_insert_intersect(GcList &l, double x, double y, double z, double u1, double u2, int inbound,
+template <class L>
+__device__ int gc_insert_intersect(L &l, double x, double y, double z, double u1, double u2, int inbound,
                                    double x2, double y2, double z2)
 {
   int k1 = -1;
@@ -227,7 +237,7 @@ __device__ int gc_insert_intersect(GcList &l, double x, double y, double z, doub
   if (u2 != 0 && u2 != 1) {
     if (inbound == 1) {
       int k2 = (k1 + 1 < l.n) ? k1 + 1 : 0, guard = 0;
-      while (l.v[k2].intersect) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 2 * GC_NCAP) return -7; }
+      while (l.v[k2].intersect) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 2 * L::cap) return -7; }
       l.v[k2].inside = 0;
     } else if (inbound == 2)
       l.v[k1].inside = 0;
@@ -238,7 +248,7 @@ __device__ int gc_insert_intersect(GcList &l, double x, double y, double z, doub
     else break;
     k1 = k2; k2++;
   }
-  if (l.n >= GC_NCAP) return -9;
+  if (l.n >= L::cap) return -9;
   for (int k = l.n; k > k2; k--) l.v[k] = l.v[k - 1];
   l.n++;
   GcNode &t = l.v[k2];
@@ -246,9 +256,9 @@ __device__ int gc_insert_intersect(GcList &l, double x, double y, double z, doub
   return 0;
 }
 
-__device__ __forceinline__ int gc_find(const GcList &l, double x, double y, double z)
+__device__ __forceinline__ int gc_find(const GcNode *v, int n, double x, double y, double z)
 {
-  for (int k = 0; k < l.n; k++) if (l.v[k].x == x && l.v[k].y == y && l.v[k].z == z) return k;
+  for (int k = 0; k < n; k++) if (v[k].x == x && v[k].y == y && v[k].z == z) return k;
   return -1;
 }
 
@@ -262,21 +272,24 @@ __device__ int gc_poly_add(GcPoly &pl, double x, double y, double z)
   return 0;
 }
 
-// clip_2dx2d_great_circle (create_xgrid.c:1479-1908) after its bounding-box rejects.  a, b: the four corners of the
-// two cells, [k*3 + axis].  Returns n_out (vertices in out) or a negative error code (see oracle/gc_oracle.c).
-__device__ int gc_clip(const double *a, const double *b, GcPoly &out)
+// clip_2dx2d_great_circle (create_xgrid.c:1479-1908) after its bounding-box rejects.  a: the n1 <= N1 corners of the first
+// polygon, b: the four corners of the second, [k*3 + axis].  Returns n_out (vertices in out) or a negative error code (see
+// oracle/gc_oracle.c).  C1: capacity of the first node list; the second list and the intersection list are the quad's.
+template <int N1, int C1>
+__device__ __forceinline__ int gc_clip_t(const double *a, int n1, const double *b, GcPoly &out)
 {
-  GcList g1, g2;
+  GcListT<C1> g1;
+  GcList g2;
   GcInter il[GC_ICAP];
   int nil = 0;
   g1.n = g2.n = 0; out.n = 0;
-  for (int i = 0; i < 4; i++) if (gc_add_end(g1, a[i * 3], a[i * 3 + 1], a[i * 3 + 2], 0, 0, 0, -1)) return -9;
+  for (int i = 0; i < n1; i++) if (gc_add_end(g1, a[i * 3], a[i * 3 + 1], a[i * 3 + 2], 0, 0, 0, -1)) return -9;
   for (int i = 0; i < 4; i++) if (gc_add_end(g2, b[i * 3], b[i * 3 + 1], b[i * 3 + 2], 0, 0, 0, -1)) return -9;
   const int npts1 = g1.n, npts2 = g2.n;
   for (int k = 0; k < g1.n; k++) g1.v[k].inside = gc_inside_polygon(g1.v[k], g2);
   for (int k = 0; k < g2.n; k++) g2.v[k].inside = gc_inside_polygon(g2.v[k], g1);
 
-  double pt1[4][3], pt2[4][3];
+  double pt1[N1][3], pt2[4][3];
   for (int i = 0; i < npts1; i++) { pt1[i][0] = g1.v[i].x; pt1[i][1] = g1.v[i].y; pt1[i][2] = g1.v[i].z; }
   for (int i = 0; i < npts2; i++) { pt2[i][0] = g2.v[i].x; pt2[i][1] = g2.v[i].y; pt2[i][2] = g2.v[i].z; }
 
@@ -322,7 +335,7 @@ __device__ int gc_clip(const double *a, const double *b, GcPoly &out)
   if (first < 0 && nintersect > 1) {
     for (int k = 0; k < nil; k++) {
       if (il[k].inbound) continue;
-      const int f = gc_find(g1, il[k].x, il[k].y, il[k].z);
+      const int f = gc_find(g1.v, g1.n, il[k].x, il[k].y, il[k].z);
       if (f < 0) return -8;
       const GcNode &prev = g1.v[f > 0 ? f - 1 : g1.n - 1], &next = g1.v[f + 1 < g1.n ? f + 1 : 0];
       il[k].inbound = (prev.inside == 0 && next.inside == 1) ? 2 : 1;
@@ -334,25 +347,26 @@ __device__ int gc_clip(const double *a, const double *b, GcPoly &out)
   if (first >= 0) {
     const double fx = il[first].x, fy = il[first].y, fz = il[first].z;
     const int maxiter1 = nintersect;
-    if (gc_find(g1, fx, fy, fz) < 0) return -3;
+    if (gc_find(g1.v, g1.n, fx, fy, fz) < 0) return -3;
     if (gc_poly_add(out, fx, fy, fz)) return -9;
     nintersect--;
-    GcList *curl = &g1;
+    const GcNode *cv = g1.v;                          // the list the walk is on, and its length (the lists do not change any more)
+    int cn = g1.n;
     int cur_num = 0, iter1 = 0, found1 = 0, found2 = 0;
     double cx = fx, cy = fy, cz = fz;
     while (iter1 < maxiter1) {
-      const int k1 = gc_find(*curl, cx, cy, cz);
+      const int k1 = gc_find(cv, cn, cx, cy, cz);
       if (k1 < 0) return -4;
-      int k2 = (k1 + 1 < curl->n) ? k1 + 1 : 0;
-      const int maxiter2 = curl->n;
+      int k2 = (k1 + 1 < cn) ? k1 + 1 : 0;
+      const int maxiter2 = cn;
       int iter2 = 0;
       found2 = 0;
       while (iter2 < maxiter2) {
         int t2_is_inter = 0;
-        const GcNode &t2 = curl->v[k2];
+        const GcNode &t2 = cv[k2];
         if (t2.intersect) {
           if (t2.x == fx && t2.y == fy && t2.z == fz) { found1 = 1; break; }
-          const GcNode &t3 = curl->v[(k2 + 1 < curl->n) ? k2 + 1 : 0];
+          const GcNode &t3 = cv[(k2 + 1 < cn) ? k2 + 1 : 0];
           found2 = 1;
           t2_is_inter = 1;
           if (t3.intersect || (t3.inside == 1)) found2 = 0;
@@ -362,7 +376,7 @@ __device__ int gc_clip(const double *a, const double *b, GcPoly &out)
           if (gc_poly_add(out, t2.x, t2.y, t2.z)) return -9;
           if (t2_is_inter) nintersect--;
         }
-        k2 = (k2 + 1 < curl->n) ? k2 + 1 : 0;
+        k2 = (k2 + 1 < cn) ? k2 + 1 : 0;
         iter2++;
       }
       if (found1) break;
@@ -370,8 +384,8 @@ __device__ int gc_clip(const double *a, const double *b, GcPoly &out)
       if (cx == fx && cy == fy && cz == fz) { found1 = 1; break; }
       if (gc_poly_add(out, cx, cy, cz)) return -9;
       nintersect--;
-      if (cur_num == 0) { curl = &g2; cur_num = 1; }
-      else { curl = &g1; cur_num = 0; }
+      if (cur_num == 0) { cv = g2.v; cn = g2.n; cur_num = 1; }
+      else { cv = g1.v; cn = g1.n; cur_num = 0; }
       iter1++;
     }
     if (!found1) return -5;
@@ -399,6 +413,10 @@ __device__ int gc_clip(const double *a, const double *b, GcPoly &out)
   out.n = n_out;
   return n_out;
 }
+// quad x quad: the lists and arrays of the quad version (k_gc_clip_slow, k_gc_clip_list, k_gc_clip_batch)
+__device__ int gc_clip(const double *a, const double *b, GcPoly &out) { return gc_clip_t<4, GC_NCAP>(a, 4, b, out); }
+// polygon of 3..8 corners x quad (k_gc_clip_poly, k_gc_poly_polygons)
+__device__ int gc_clip_ngon(const double *a, int n1, const double *b, GcPoly &out) { return gc_clip_t<GC_NGON, GC_NCAP_NGON>(a, n1, b, out); }
 
 // ------------------------------------------------------------------------------------------------ compact clip
 // The same algorithm with ~0.5 KB of per-lane state instead of 2.6 KB (k_gc_clip was bound by scratch traffic:
@@ -721,6 +739,77 @@ __global__ __launch_bounds__(256) void k_gc_cell_struct(const FgTileXyz *tiles, 
     if (kmin > __hip_atomic_load(&band_keys[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&band_keys[1], kmin);
   }
 }
+// The bounding cap of n corners v [n][3] (a cell's four, a polygon's 3..8): centre = the normalised corner sum, radius = the largest
+// corner distance + margin; no cap (every cell a candidate, never cap-rejected) above 0.5 rad or for a vanishing corner sum.
+struct GcCap { double cx, cy, cz, r, latc; bool nocap; };
+__device__ __forceinline__ GcCap d_gc_cap(int n, const double *v)
+{
+  GcCap k;
+  double cx = v[0], cy = v[1], cz = v[2];
+  for (int q = 1; q < n; q++) { cx += v[q * 3]; cy += v[q * 3 + 1]; cz += v[q * 3 + 2]; }
+  const double nrm = sqrt(cx * cx + cy * cy + cz * cz);
+  bool nocap = !(nrm > 1.e-3);
+  double r = 0;
+  if (!nocap) {
+    cx /= nrm; cy /= nrm; cz /= nrm;
+    for (int q = 0; q < n; q++) {
+      double d = cx * v[q * 3] + cy * v[q * 3 + 1] + cz * v[q * 3 + 2];
+      d = fmin(1.0, fmax(-1.0, d));
+      // acos loses accuracy near 1: use the chord for small separations
+      const double ex = v[q * 3] - cx, ey = v[q * 3 + 1] - cy, ez = v[q * 3 + 2] - cz;
+      const double chord = sqrt(ex * ex + ey * ey + ez * ez);
+      const double ang = (chord < 0.5) ? 2.0 * asin(0.5 * chord) : acos(d);
+      r = fmax(r, ang);
+    }
+    r = r * (1.0 + 1.e-9) + GC_CAP_MARGIN;
+    if (r > 0.5) nocap = true;
+  }
+  k.cx = cx; k.cy = cy; k.cz = cz; k.r = r; k.nocap = nocap;
+  k.latc = nocap ? 0.0 : asin(fmin(1.0, fmax(-1.0, cz)));
+  return k;
+}
+// the cap into the record (o[0..2] centre, o[3] cos radius or -2) and the longitude range of the candidate box of cell s
+__device__ __forceinline__ void d_gc_cap_store(int n, const double *v, const GcCap &k, double *o, FgCells c, int s)
+{
+  const double hpi = 0.5 * GC_PI, tpi = 2.0 * GC_PI;
+  if (k.nocap) {
+    o[0] = 0; o[1] = 0; o[2] = 1; o[3] = -2.0;
+    c.lon_min[s] = 0.0; c.lon_max[s] = tpi; c.lon_avg[s] = GC_PI;
+    return;
+  }
+  o[0] = k.cx; o[1] = k.cy; o[2] = k.cz; o[3] = cos(k.r);
+  double lonc = atan2(k.cy, k.cx);
+  if (lonc < 0) lonc += tpi;
+  // longitude: a great-circle arc that stays clear of the pole is monotone in longitude, so the polygon's extent is
+  // that of its corners; the angular margin becomes margin / cos(lat) in longitude.  Cells whose cap reaches a pole
+  // (or nearly) take the whole circle.
+  const double cosmin = cos(fmin(hpi, fabs(k.latc) + k.r));
+  if (fabs(k.latc) + k.r >= hpi - 1.e-6 || cosmin < 0.02) { c.lon_min[s] = 0.0; c.lon_max[s] = tpi; c.lon_avg[s] = GC_PI; }
+  else {
+    double dmin = 0.0, dmax = 0.0;
+    for (int q = 0; q < n; q++) {
+      double dl = atan2(v[q * 3 + 1], v[q * 3]) - lonc;
+      if (dl > GC_PI) dl -= tpi;
+      if (dl < -GC_PI) dl += tpi;
+      if (dl > GC_PI) dl -= tpi;
+      dmin = fmin(dmin, dl); dmax = fmax(dmax, dl);
+    }
+    const double mlon = (GC_CAP_MARGIN + 1.e-9) / cosmin + 1.e-9;
+    c.lon_min[s] = lonc + dmin - mlon; c.lon_max[s] = lonc + dmax + mlon; c.lon_avg[s] = lonc;
+  }
+}
+// great_circle_area of the de-duplicated corners (addEnd merges corners within 1e-10: the two pole corners of a lat-lon cap cell)
+template <int NMAX>
+__device__ __forceinline__ double d_gc_dedup_area(int n, const double *v)
+{
+  double p[NMAX * 3]; int m = 0;
+  for (int q = 0; q < n; q++) {
+    bool dup = false;
+    for (int t = 0; t < m; t++) if (gc_same_point(p[t * 3], p[t * 3 + 1], p[t * 3 + 2], v[q * 3], v[q * 3 + 1], v[q * 3 + 2])) dup = true;
+    if (!dup) { p[m * 3] = v[q * 3]; p[m * 3 + 1] = v[q * 3 + 1]; p[m * 3 + 2] = v[q * 3 + 2]; m++; }
+  }
+  return gc_area(m, p, 3);
+}
 // returns false for a culled cell; *lat_lo / *lat_hi = the latitude range of the cell's box
 __device__ __forceinline__ bool d_gc_cell_record(const FgTileXyz *tiles, int ntiles, int s, FgCells c, const unsigned long long *cull,
                                                  double *lat_lo, double *lat_hi)
@@ -734,70 +823,18 @@ __device__ __forceinline__ bool d_gc_cell_record(const FgTileXyz *tiles, int nti
   for (int k = 0; k < 4; k++) { v[k * 3] = T.x[idx[k]]; v[k * 3 + 1] = T.y[idx[k]]; v[k * 3 + 2] = T.z[idx[k]]; }
   double *o = c.verts + (size_t)s * 16;
   for (int k = 0; k < 12; k++) o[k] = v[k];
-  // bounding cap
-  double cx = v[0] + v[3] + v[6] + v[9], cy = v[1] + v[4] + v[7] + v[10], cz = v[2] + v[5] + v[8] + v[11];
-  const double nrm = sqrt(cx * cx + cy * cy + cz * cz);
-  bool nocap = !(nrm > 1.e-3);
-  double r = 0;
-  if (!nocap) {
-    cx /= nrm; cy /= nrm; cz /= nrm;
-    for (int k = 0; k < 4; k++) {
-      double d = cx * v[k * 3] + cy * v[k * 3 + 1] + cz * v[k * 3 + 2];
-      d = fmin(1.0, fmax(-1.0, d));
-      // acos loses accuracy near 1: use the chord for small separations
-      const double ex = v[k * 3] - cx, ey = v[k * 3 + 1] - cy, ez = v[k * 3 + 2] - cz;
-      const double chord = sqrt(ex * ex + ey * ey + ez * ez);
-      const double ang = (chord < 0.5) ? 2.0 * asin(0.5 * chord) : acos(d);
-      r = fmax(r, ang);
-    }
-    r = r * (1.0 + 1.e-9) + GC_CAP_MARGIN;
-    if (r > 0.5) nocap = true;
-  }
-  const double hpi = 0.5 * GC_PI, tpi = 2.0 * GC_PI;
-  const double latc = nocap ? 0.0 : asin(fmin(1.0, fmax(-1.0, cz)));
-  const double lat_min = nocap ? -hpi : fmax(-hpi, latc - r), lat_max = nocap ? hpi : fmin(hpi, latc + r);
+  const GcCap k = d_gc_cap(4, v);
+  const double hpi = 0.5 * GC_PI;
+  const double lat_min = k.nocap ? -hpi : fmax(-hpi, k.latc - k.r), lat_max = k.nocap ? hpi : fmin(hpi, k.latc + k.r);
   *lat_lo = lat_min; *lat_hi = lat_max;
   c.lat_min[s] = lat_min; c.lat_max[s] = lat_max;
   if (cull && cull[0]) {
     const double bmax = d_ord_val(cull[0]), bmin = d_ord_val(~cull[1]);
     if (lat_max <= bmin || lat_min >= bmax) { c.nv[s] = 0; c.area[s] = 0; return false; }
   }
-  {
-    // cell area on the de-duplicated vertex list (addEnd merges the two pole corners of a lat-lon cap cell)
-    double p[12]; int n = 0;
-    for (int k = 0; k < 4; k++) {
-      bool dup = false;
-      for (int m = 0; m < n; m++) if (gc_same_point(p[m * 3], p[m * 3 + 1], p[m * 3 + 2], v[k * 3], v[k * 3 + 1], v[k * 3 + 2])) dup = true;
-      if (!dup) { p[n * 3] = v[k * 3]; p[n * 3 + 1] = v[k * 3 + 1]; p[n * 3 + 2] = v[k * 3 + 2]; n++; }
-    }
-    c.area[s] = gc_area(n, p, 3);
-    c.nv[s] = 4;
-  }
-  if (nocap) {
-    o[12] = 0; o[13] = 0; o[14] = 1; o[15] = -2.0;
-    c.lon_min[s] = 0.0; c.lon_max[s] = tpi; c.lon_avg[s] = GC_PI;
-    return true;
-  }
-  o[12] = cx; o[13] = cy; o[14] = cz; o[15] = cos(r);
-  double lonc = atan2(cy, cx);
-  if (lonc < 0) lonc += tpi;
-  // longitude: a great-circle arc that stays clear of the pole is monotone in longitude, so the polygon's extent is
-  // that of its corners; the angular margin becomes margin / cos(lat) in longitude.  Cells whose cap reaches a pole
-  // (or nearly) take the whole circle.
-  const double cosmin = cos(fmin(hpi, fabs(latc) + r));
-  if (fabs(latc) + r >= hpi - 1.e-6 || cosmin < 0.02) { c.lon_min[s] = 0.0; c.lon_max[s] = tpi; c.lon_avg[s] = GC_PI; }
-  else {
-    double dmin = 0.0, dmax = 0.0;
-    for (int k = 0; k < 4; k++) {
-      double dl = atan2(v[k * 3 + 1], v[k * 3]) - lonc;
-      if (dl > GC_PI) dl -= tpi;
-      if (dl < -GC_PI) dl += tpi;
-      if (dl > GC_PI) dl -= tpi;
-      dmin = fmin(dmin, dl); dmax = fmax(dmax, dl);
-    }
-    const double mlon = (GC_CAP_MARGIN + 1.e-9) / cosmin + 1.e-9;
-    c.lon_min[s] = lonc + dmin - mlon; c.lon_max[s] = lonc + dmax + mlon; c.lon_avg[s] = lonc;
-  }
+  c.area[s] = d_gc_dedup_area<4>(4, v);
+  c.nv[s] = 4;
+  d_gc_cap_store(4, v, k, o + 12, c, s);
   return true;
 }
 
@@ -1446,4 +1483,108 @@ __global__ __launch_bounds__(64) void k_gc_area_batch(int npoly, int stride_pts,
 void fgd_gc_area_batch(int npoly, int stride_pts, const double *xyz, const int *n, double *area, hipStream_t st)
 {
   if (npoly > 0) k_gc_area_batch<<<gc_nblk(npoly, 64), 64, 0, st>>>(npoly, stride_pts, xyz, n, area);
+}
+
+// ------------------------------------------------------------------------------------------------ polygon-list search
+// Source "cells" that are convex polygons of 3..8 corners (clockwise unit vectors): make_coupler_mosaic's remembered
+// atmosphere x land polygons against the ocean cells (make_coupler_mosaic.c:1662-1696).  One 256-byte record per polygon,
+// rec[s * FG_GC_PREC + ..]: [0..23] corners xyz, [24..26] cap centre, [27] cos(cap radius) or -2 (no cap), [28] great_circle_area of
+// the de-duplicated corners (the gridArea of the "not convex" check, create_xgrid.c:1575), [29..31] zero.  S.nv = the count,
+// S.area = the caller's reference area (what the 1e-6 ratio test compares with), S.lat_* / lon_* = the cap's box as for cells.
+// The cap is the cells' (d_gc_cap, d_gc_cap_store) with n corners: the normalised corner sum, the largest corner distance + margin;
+// a cap below 0.5 rad is geodesically convex, so it holds the convex polygon its corners span.
+__global__ __launch_bounds__(256) void k_gc_poly_records(FgGcPolyList P, FgCells S, double *rec, unsigned *err)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= P.npoly) return;
+  const int n = P.n[s];
+  double *o = rec + (size_t)s * FG_GC_PREC, *o16 = S.verts + (size_t)s * 16;
+  for (int k = 0; k < 16; k++) o16[k] = 0.0;                   // (the 128-byte cell record is not used by this search)
+  if (n < 3 || n > GC_NGON) {
+    if (n > GC_NGON) atomicOr(err, G_ERRBIT_GC_POLYN);
+    for (int k = 0; k < FG_GC_PREC; k++) o[k] = 0.0;
+    S.nv[s] = 0; S.area[s] = 0; S.lat_min[s] = 0; S.lat_max[s] = 0; S.lon_min[s] = 0; S.lon_max[s] = 0; S.lon_avg[s] = 0;
+    return;
+  }
+  double v[GC_NGON * 3];
+  for (int k = 0; k < GC_NGON; k++) {
+    const bool in = k < n;
+    v[k * 3] = in ? P.x[(size_t)s * GC_NGON + k] : 0.0; v[k * 3 + 1] = in ? P.y[(size_t)s * GC_NGON + k] : 0.0; v[k * 3 + 2] = in ? P.z[(size_t)s * GC_NGON + k] : 0.0;
+  }
+  for (int k = 0; k < GC_NGON * 3; k++) o[k] = v[k];
+  const GcCap k = d_gc_cap(n, v);
+  const double hpi = 0.5 * GC_PI;
+  S.lat_min[s] = k.nocap ? -hpi : fmax(-hpi, k.latc - k.r); S.lat_max[s] = k.nocap ? hpi : fmin(hpi, k.latc + k.r);
+  o[28] = d_gc_dedup_area<GC_NGON>(n, v);                      // gridArea of the "not convex" check
+  o[29] = 0; o[30] = 0; o[31] = 0;
+  S.nv[s] = n; S.area[s] = P.area[s];
+  d_gc_cap_store(n, v, k, o + 24, S, s);
+}
+
+// gc_prefilter for a polygon record against a cell record: the range reject over all n1 corners (create_xgrid.c:1508-1528), the
+// two "not convex" checks, the cap reject
+__device__ bool gc_prefilter_ngon(const double *a, int n1, const double *b, double area2, unsigned *err)
+{
+  for (int ax = 0; ax < 3; ax++) {
+    double mn1 = a[ax], mx1 = a[ax], mn2 = b[ax], mx2 = b[ax];
+    for (int k = 1; k < n1; k++) { mn1 = fmin(mn1, a[k * 3 + ax]); mx1 = fmax(mx1, a[k * 3 + ax]); }
+    for (int k = 1; k < 4; k++) { mn2 = fmin(mn2, b[k * 3 + ax]); mx2 = fmax(mx2, b[k * 3 + ax]); }
+    if (mn1 >= mx2 + GC_RANGE_CHECK || mn2 >= mx1 + GC_RANGE_CHECK) return false;
+  }
+  const double area1 = a[28];
+  if (area1 <= 0) atomicOr(err, G_ERRBIT_GC_CONVEX1);
+  if (area2 <= 0) atomicOr(err, G_ERRBIT_GC_CONVEX2);
+  if (area1 <= 0 || area2 <= 0) return false;
+  if (a[27] > -1.5 && b[15] > -1.5) {
+    const double dotc = a[24] * b[12] + a[25] * b[13] + a[26] * b[14];
+    const double sr1 = sqrt(fmax(0.0, 1.0 - a[27] * a[27])), sr2 = sqrt(fmax(0.0, 1.0 - b[15] * b[15]));
+    const double cos_sum = a[27] * b[15] - sr1 * sr2;
+    if (dotc < cos_sum - 1.e-12) return false;
+  }
+  return true;
+}
+
+// one lane per candidate pair (polygon, destination cell), 64-lane blocks as k_gc_clip_list: the general clip, nothing else
+__global__ __launch_bounds__(64) void k_gc_clip_poly(FgPairSpace ps, FgCells S, const double *rec, FgCells D, double *tmp_area, int *nacc,
+                                                     unsigned long long *stats, unsigned *err)
+{
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (!d_pair_live(ps, p)) return;
+  const int s = ps.src[p], d = ps.dst[p];
+  const double *a = rec + (size_t)s * FG_GC_PREC, *b = D.verts + (size_t)d * 16;
+  const int n1 = min(S.nv[s], GC_NGON);
+  if (n1 < 3 || !gc_prefilter_ngon(a, n1, b, D.area[d], err)) { ps.dst[p] = -1; return; }
+  GcPoly out;
+  const int n_out = gc_clip_ngon(a, n1, b, out);
+  gc_finish(p, s, n_out, &out.p[0][0], 1.0, S.area[s], D.area[d], ps.dst, tmp_area, nacc, stats, err);
+}
+
+// the clipped polygons of exchange cells of a polygon-list plan: n_out[n], out [n][GC_PCAP][3] (fg_plan_get_polygons)
+__global__ __launch_bounds__(64) void k_gc_poly_polygons(long n, const int *x_src, const int *x_dst, const int *nv, const double *rec, FgCells D,
+                                                         double *out, int *n_out)
+{
+  const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int s = x_src[k], d = x_dst[k];
+  GcPoly o; o.n = 0;
+  const int n1 = min(nv[s], GC_NGON);
+  int no = (n1 < 3) ? 0 : gc_clip_ngon(rec + (size_t)s * FG_GC_PREC, n1, D.verts + (size_t)d * 16, o);
+  n_out[k] = no;
+  for (int q = 0; q < GC_PCAP; q++) for (int ax = 0; ax < 3; ax++) out[((size_t)k * GC_PCAP + q) * 3 + ax] = (q < no) ? o.p[q][ax] : 0.0;
+}
+
+void fgd_gc_poly_records(FgGcPolyList P, FgCells S, double *rec, unsigned *err, hipStream_t st)
+{
+  if (P.npoly > 0) k_gc_poly_records<<<gc_nblk(P.npoly, 256), 256, 0, st>>>(P, S, rec, err);
+}
+void fgd_gc_clip_poly(FgPairSpace ps, FgCells S, const double *rec, FgCells D, double *tmp_area, int *nacc, unsigned long long *stats,
+                      unsigned *err, hipStream_t st)
+{
+  const long np = fgd_pairs_total(ps);
+  if (np > 0) k_gc_clip_poly<<<gc_nblk(np, 64), 64, 0, st>>>(ps, S, rec, D, tmp_area, nacc, stats, err);
+}
+void fgd_gc_poly_polygons(long n, const int *x_src, const int *x_dst, const int *nv, const double *rec, FgCells D, double *out, int *n_out,
+                          hipStream_t st)
+{
+  if (n > 0) k_gc_poly_polygons<<<gc_nblk(n, 64), 64, 0, st>>>(n, x_src, x_dst, nv, rec, D, out, n_out);
 }

@@ -135,6 +135,9 @@ Pool g_pool;
 }  // namespace
 
 extern "C" void fg_pool_release(void) { g_pool.release_all(); }
+// plan_internal.h: before a synchronised stream that plans ran on is destroyed; and the events the pool holds (tests)
+void fg_pool_retire_stream(void *stream) { g_pool.retire((hipStream_t)stream); }
+extern "C" long fg_pool_live_events(void) { return g_pool.live_events(); }
 
 // Device memory for C callers that do not include the HIP headers (the fregrid replacement objects, integration/): blocks come
 // from the plans' caching pool; copies are synchronous.
@@ -369,6 +372,8 @@ struct fg_plan {
   bool rect = false;            // searched on the rectilinear path: D holds areas only, the cells are in rect_tab (FgRect)
   FgRect rect_tab{};
   FgPolyList polys{};           // npoly > 0: the source "cells" are this list of polygons (fg_plan_create_polylist)
+  FgGcPolyList gcpolys{};       // npoly > 0: ... this list of great-circle polygons (fg_plan_create_polylist_gc)
+  double *gc_prec = nullptr;    // their records, [npoly][FG_GC_PREC] (k_gc_poly_records)
   // exchange cells
   long nx = 0;
   int *x_src = nullptr, *x_dst = nullptr;
@@ -434,7 +439,7 @@ struct fg_plan {
     while (owned.size() > keep) { g_pool.put(owned.back()); owned.pop_back(); }
     tiles_dev = nullptr; mask_dev = nullptr; S = FgCells{}; D = FgCells{};
     x_src = x_dst = nullptr; x_area = x_c1 = x_c2 = nullptr; xoff = nullptr;
-    perm = nullptr; csr.row_ptr = nullptr; csr.e1 = nullptr; csr.e2 = nullptr; cen = nullptr; src_idx_f = nullptr; sums = nullptr;
+    perm = nullptr; csr.row_ptr = nullptr; csr.e1 = nullptr; csr.e2 = nullptr; cen = nullptr; src_idx_f = nullptr; sums = nullptr; gc_prec = nullptr;
     have_geom = false; rect = false; rect_tab = FgRect{};
   }
 };
@@ -727,6 +732,8 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   // (a grid on the rectilinear path: compact source cells, written by k_cell_struct2r and k_candidates_rect<true>)
   if (!alloc_cells(pl, &pl->S, nsrc, rect && !pl->polys.npoly)) return fg_fail(FG_ERR_HIP, "out of device memory");
   SearchBlocks blk{pl};
+  const bool gc_poly = gc && pl->gcpolys.npoly > 0;   // great-circle polygon list: records of its own, the general clip for every pair
+  if (gc_poly) pl->gc_prec = blk.keep<double>((size_t)nsrc * FG_GC_PREC);
   struct { double *hdr, *lat_ax, *lon_ax, *col, *row, *col_min, *col_max, *col_avg; } rt{};   // the rectilinear tables, one block (FgRect, xgrid_device.h)
   if (rect) {
     pl->D = FgCells{};
@@ -769,7 +776,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   int *tmp_rowpos = early_rows ? blk.get<int>(npairs + 1) : nullptr;
   // great-circle path, three-pass clip: per-pair words, and 3 tasks (edge pairs to solve) per pair of capacity -- 3.0 per LIVE
   // pair were counted at C384 -> 0.25 deg; pairs whose tasks do not fit go through the one-kernel clip instead
-  const bool gc_split = gc && opt.gc_split && npairs < (1L << 28);
+  const bool gc_split = gc && !gc_poly && opt.gc_split && npairs < (1L << 28);
   const long tcap_want = (opt.gc_split == 2) ? npairs / 64 : 3 * npairs;
   const long tcap_reg = gc_split ? std::min<long>((tcap_want / FG_NREG + 255) / 256 * 256, 0x7ffffff0L / FG_NREG) : 0;   // tasks per region
   const long tcap_all = tcap_reg * FG_NREG;
@@ -806,7 +813,8 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
     // destination cells first: a culling search (a rank's band of the target) folds their latitude ranges into band_keys, and
     // the source launch drops the cells that cannot meet that range before their (expensive) spherical-excess area
     fgd_gc_cell_struct(gct_dev + pl->ntiles, 1, ndst, pl->D, st, opt.cull ? dc->band_keys : nullptr, 1);
-    fgd_gc_cell_struct(gct_dev, pl->ntiles, nsrc, pl->S, st, opt.cull ? dc->band_keys : nullptr, 2);
+    if (gc_poly) fgd_gc_poly_records(pl->gcpolys, pl->S, pl->gc_prec, dc->err, st);
+    else fgd_gc_cell_struct(gct_dev, pl->ntiles, nsrc, pl->S, st, opt.cull ? dc->band_keys : nullptr, 2);
     fgd_src_field_index(order, pl->tiles_dev, pl->ntiles, nsrc, pl->src_idx_f, st);
   } else if (rect) {
     // tables + on-device verification of the grid, then the source records, the heavy list and the destination AREAS in one launch
@@ -864,7 +872,9 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
     pt.end();
   } else if (gc) {
     pt.begin(PH_CLIP_GENERAL);
-    if (gc_split) {
+    if (gc_poly)
+      fgd_gc_clip_poly(ps, pl->S, pl->gc_prec, pl->D, tmp_area, nacc, dc->stats, dc->err, st);
+    else if (gc_split) {
       if (!pl->stream_b) pl->stream_b = g_handles.get_stream(pl->device);
       gc_e1 = g_handles.get_sync_event(); gc_e2 = g_handles.get_sync_event();
       GcSplit g{gc_meta, gc_tbase, gc_task, gc_res, (unsigned)tcap_reg, (unsigned *)(zero_blk + z_gc_ntask), defer_list, &dc->defer_cnt,
@@ -972,6 +982,7 @@ static long plan_search_core(fg_plan *pl, const SearchIn &in, const SearchOpts &
   if (hc->err[0] & 4u) return fg_fail(FG_ERR_MAXV, "clipped polygon exceeds 16 vertices");
   if (hc->err[0] & G_ERRBIT_GC_CONVEX1) return fg_fail(FG_ERR_GEOM, "create_xgrid.c(clip_2dx2d_great_circle): grid box 1 is not convex");
   if (hc->err[0] & G_ERRBIT_GC_CONVEX2) return fg_fail(FG_ERR_GEOM, "create_xgrid.c(clip_2dx2d_great_circle): grid box 2 is not convex");
+  if (hc->err[0] & G_ERRBIT_GC_POLYN) return fg_fail(FG_ERR_MAXV, "a polygon of the list has more than 8 vertices");
   if (hc->err[0] & G_ERRBIT_GC_CLIP) return fg_fail(FG_ERR_GEOM, "%s", gc_clip_error((int)hc->err[1]));
   if (hc->err[0] & G_ERRBIT_LOOKBACK) return fg_fail(FG_ERR_HIP, "single-pass scan: a tile waited too long for its predecessor");
   pl->nx = (long)hc->xtot;
@@ -1500,6 +1511,26 @@ int fg_plan_polygons_dev(const fg_plan *pl, int *n_out, double *lon, double *lat
   FGCHK(hipGetLastError());
   return 0;
 }
+int fg_plan_polygons_gc_dev(const fg_plan *pl, int *n_out, double *x, double *y, double *z)
+{
+  if (!pl || !n_out || !x || !y || !z) return fg_fail(FG_ERR_ARG, "null argument");
+  if (!pl->searched || !pl->have_geom || !pl->x_src || !pl->great_circle || pl->gc_prec)
+    return fg_fail(FG_ERR_STATE, "fg_plan_polygons_gc_dev: needs a great-circle plan between grids from a search");
+  FGCHK(hipSetDevice(pl->device));
+  const long n = pl->nx;
+  if (n == 0) return 0;
+  const int dev = pl->device;
+  double *a = (double *)g_pool.get(dev, (size_t)n * 12 * 8), *b = (double *)g_pool.get(dev, (size_t)n * 12 * 8);
+  double *o = (double *)g_pool.get(dev, (size_t)n * FG_GC_POLY_CAP * 3 * 8), *ar = (double *)g_pool.get(dev, (size_t)n * 8);
+  struct Put4 { void *p[4]; ~Put4() { for (void *q : p) g_pool.put(q); } } put4{{a, b, o, ar}};
+  if (!a || !b || !o || !ar) return fg_fail(FG_ERR_HIP, "out of device memory");
+  fgd_xgrid_gather_gc(n, pl->x_src, pl->x_dst, pl->S, pl->D, a, b, pl->stream);
+  fgd_gc_clip_batch((int)n, a, b, o, n_out, ar, pl->stream);
+  fgd_split_xyz(n, 8, o, x, y, z, pl->stream);
+  FGCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(pl->stream));
+  return 0;
+}
 long fg_plan_search_d2h(const fg_plan *pl) { return pl ? pl->search_d2h : 0; }
 extern "C" long fg_plan_device_bytes(const fg_plan *pl, long *sizes, int nmax)
 {
@@ -1545,6 +1576,62 @@ long fg_plan_create_polylist_dev(int order, int npoly, const int *d_n, const dou
   const double *none[1] = {nullptr};
   const long nx = plan_search(pl, SearchIn{.lon_in = none, .lat_in = none, .lon_out = d_lon_out, .lat_out = d_lat_out, .mean_dlat = mean_dlat,
                                            .mean_dlon = mean_dlon, .rect_hint = rect_hint});
+  return g.hand_over(nx, plan_out);
+}
+
+// ------------------------------------------------------------------------------------- great-circle polygon lists
+// The tail of both entries: the list and the destination's unit vectors are on the device.  The search is gc_search's with the
+// list in place of the source tiles (one pseudo-tile of npoly x 1 "cells" without corner arrays).
+static long polylist_gc_search(fg_plan *pl, FgGcPolyList P, GcXyz out, DstExtents x)
+{
+  pl->gcpolys = P;
+  const GcXyz gxyz[2] = {GcXyz{nullptr, nullptr, nullptr}, out};
+  const long nx = gc_search(pl, gxyz, nullptr, x);
+  pl->gcpolys = FgGcPolyList{nullptr, nullptr, nullptr, nullptr, nullptr, P.npoly};      // (the records hold all of it from here on)
+  return nx;
+}
+
+// fg_plan_create_polylist_gc with every array on the device: n [npoly], x / y / z [npoly][8], area_ref [npoly], the destination
+// corners as unit vectors; the arrays stay the caller's and must outlive the search only.  Extents <= 0: derived from a sample.
+// use_caller_stream 0: a stream of the plan's own (the caller has finished writing the arrays), as fg_plan_create_great_circle_dev.
+long fg_plan_create_polylist_gc_dev(int npoly, const int *d_n, const double *d_x, const double *d_y, const double *d_z, const double *d_area_ref,
+                                    int nx_out, int ny_out, const double *d_x_out, const double *d_y_out, const double *d_z_out,
+                                    double mean_dlat, double mean_dlon, int device, void *stream, int use_caller_stream, fg_plan **plan_out)
+{
+  if (npoly < 1 || !d_n || !d_x || !d_y || !d_z || !d_area_ref || !d_x_out || !d_y_out || !d_z_out) return fg_fail(FG_ERR_ARG, "null argument");
+  PlanGuard g;
+  const int one = 1;
+  if (int rc = plan_base(FG_CONSERVE_ORDER1, 1, &npoly, &one, nx_out, ny_out, device, &g.pl)) return rc;
+  if (use_caller_stream) adopt_stream(g.pl, stream);
+  const long nx = polylist_gc_search(g.pl, FgGcPolyList{d_n, d_x, d_y, d_z, d_area_ref, npoly}, GcXyz{d_x_out, d_y_out, d_z_out},
+                                     DstExtents{mean_dlat, mean_dlon});
+  return g.hand_over(nx, plan_out);
+}
+
+// Host arrays; lon_out / lat_out in radians, converted on the host like fg_plan_create_great_circle.  A list of no polygons is
+// searched as one polygon without vertices (it has no candidates): the plan then has one source "cell" and no exchange cell.
+extern "C" long fg_plan_create_polylist_gc(int npoly, const int *n, const double *x, const double *y, const double *z, const double *area_ref,
+                                           int nx_out, int ny_out, const double *lon_out, const double *lat_out, int device, fg_plan **plan_out)
+{
+  if (npoly < 0 || !lon_out || !lat_out || (npoly > 0 && (!n || !x || !y || !z || !area_ref))) return fg_fail(FG_ERR_ARG, "null argument");
+  for (int k = 0; k < npoly; k++)
+    if (n[k] < 0 || n[k] > 8) return fg_fail(FG_ERR_ARG, "fg_plan_create_polylist_gc: polygon %d has %d vertices (at most 8)", k, n[k]);
+  PlanGuard g;
+  const int one = 1, np1 = npoly > 0 ? npoly : 1;
+  if (int rc = plan_base(FG_CONSERVE_ORDER1, 1, &np1, &one, nx_out, ny_out, device, &g.pl)) return rc;
+  fg_plan *pl = g.pl;
+  static const int n_none[1] = {0};
+  static const double v_none[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (npoly == 0) { n = n_none; x = y = z = v_none; area_ref = v_none; }
+  const size_t npo = (size_t)(nx_out + 1) * (ny_out + 1);
+  std::vector<double> h(3 * npo);                       // x | y | z of the destination corners
+  fg_latlon2xyz((long)npo, lon_out, lat_out, h.data(), h.data() + npo, h.data() + 2 * npo);
+  HostUpload up{pl};
+  const FgGcPolyList P{up.put(n, np1), up.put(x, (size_t)np1 * 8), up.put(y, (size_t)np1 * 8), up.put(z, (size_t)np1 * 8), up.put(area_ref, np1), np1};
+  double *d_o = up.put(h.data(), 3 * npo);
+  if (!up.run()) return fg_fail(FG_ERR_HIP, "polygon upload failed (out of device memory?)");
+  const long nx = polylist_gc_search(pl, P, GcXyz{d_o, d_o + npo, d_o + 2 * npo}, dst_extents_host(nx_out, ny_out, lon_out, lat_out));
+  if (nx >= 0) up.done();
   return g.hand_over(nx, plan_out);
 }
 
@@ -1844,7 +1931,15 @@ extern "C" int fg_plan_get_polygons(const fg_plan *pl, int maxv, int *n_out, dou
     struct Put { void *a, *b; ~Put() { g_pool.put(a); g_pool.put(b); } } put{d_n, d_v};
     if (!d_n || !d_v) return fg_fail(FG_ERR_HIP, "out of device memory");
     std::vector<XferJob> jobs;
-    if (pl->great_circle) {
+    if (pl->great_circle && pl->gc_prec) {            // a polygon list: the n-gon clip on the plan's records
+      double *o = (double *)g_pool.get(dev, (size_t)n * FG_GC_POLY_CAP * 3 * 8);
+      struct Put1 { void *p; ~Put1() { g_pool.put(p); } } put1{o};
+      if (!o) return fg_fail(FG_ERR_HIP, "out of device memory");
+      fgd_gc_poly_polygons(n, pl->x_src + k0, pl->x_dst + k0, pl->S.nv, pl->gc_prec, pl->D, o, d_n, pl->stream);
+      fgd_split_xyz(n, maxv, o, d_v, d_v + nv, d_v + 2 * nv, pl->stream);
+      FGCHK(hipStreamSynchronize(pl->stream));
+      jobs.push_back(XferJob{v2 + (size_t)k0 * maxv, d_v + 2 * nv, nv * sizeof(double), true});
+    } else if (pl->great_circle) {
       double *a = (double *)g_pool.get(dev, (size_t)n * 12 * 8), *b = (double *)g_pool.get(dev, (size_t)n * 12 * 8);
       double *o = (double *)g_pool.get(dev, (size_t)n * FG_GC_POLY_CAP * 3 * 8), *ar = (double *)g_pool.get(dev, (size_t)n * 8);
       struct Put4 { void *p[4]; ~Put4() { for (void *q : p) g_pool.put(q); } } put4{{a, b, o, ar}};

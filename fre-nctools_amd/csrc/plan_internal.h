@@ -1,4 +1,4 @@
-// plan_internal.h -- entries of plan.hip for the library's own pipelines (coupler.hip): not exported in fregrid_hip.h.  They let a
+// plan_internal.h -- entries of plan.hip for the library's own pipelines (coupler.hip, topog.hip): not exported in fregrid_hip.h.  They let a
 // pipeline keep the exchange cells, the clipped polygons and the grids of its searches in device memory from one search to the next.
 #pragma once
 #include "fregrid_hip.h"
@@ -16,6 +16,14 @@ struct FgPlanView {
 int fg_plan_view(const fg_plan *pl, FgPlanView *v);
 // the clipped polygon of every exchange cell into device arrays n_out [nx], lon / lat [nx][8]; queued on the plan's stream
 int fg_plan_polygons_dev(const fg_plan *pl, int *n_out, double *lon, double *lat);
+// the same of a great-circle plan between grids: n_out [nx], x / y / z [nx][8]; queued on the plan's stream, which the call also
+// synchronises (its scratch goes back to the pool).  A polygon of more than 8 vertices keeps its count
+int fg_plan_polygons_gc_dev(const fg_plan *pl, int *n_out, double *x, double *y, double *z);
+// A pipeline that made its own stream, ran plans on it and is about to destroy it calls this after synchronising the stream: the
+// pool's blocks that are tagged with the stream become untagged and the events recorded on it leave the pool (dev_pool.h: retire).
+void fg_pool_retire_stream(void *stream);
+// ordering events the pool holds at the moment (C linkage: tests/test_gpu_coupler_stream_retire.py)
+extern "C" long fg_pool_live_events(void);
 // bytes the plan's search copied to the host (one block of counters per attempt)
 long fg_plan_search_d2h(const fg_plan *pl);
 // the plan's own block list: the pool's class size of every device block the plan holds into sizes [nmax] (may be null), their sum
@@ -34,3 +42,10 @@ long fg_plan_create_dev_hint(int order, int ntiles_in, const int *nx_in, const i
 long fg_plan_create_polylist_dev(int order, int npoly, const int *d_n, const double *d_lon, const double *d_lat, const double *d_lon_avg,
                                  const double *d_area_ref, int nx_out, int ny_out, const double *d_lon_out, const double *d_lat_out,
                                  double mean_dlat, double mean_dlon, int rect_hint, int device, void *stream, fg_plan **plan_out);
+// fg_plan_create_polylist_gc with the list (n [npoly], x / y / z [npoly][8], area_ref [npoly]) and the destination's unit vectors
+// already on the device (stream / use_caller_stream as fg_plan_create_great_circle_dev); extents <= 0: derived from a sample of the
+// destination.  A polygon of more than 8 vertices is FG_ERR_MAXV (found by the record kernel)
+extern "C" long fg_plan_create_polylist_gc_dev(int npoly, const int *d_n, const double *d_x, const double *d_y, const double *d_z,
+                                               const double *d_area_ref, int nx_out, int ny_out, const double *d_x_out, const double *d_y_out,
+                                               const double *d_z_out, double mean_dlat, double mean_dlon, int device, void *stream,
+                                               int use_caller_stream, fg_plan **plan_out);

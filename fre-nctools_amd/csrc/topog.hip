@@ -17,6 +17,7 @@
 #include <vector>
 #include "topog.h"
 #include "fg_host.h"
+#include "plan_internal.h"
 
 // 1 (default, the faster one: profiles/topog_summary.md): remove_isolated_cells for every cell at once in the last kernel;
 // 0: as the reference's sequential sweep, one launch per anti-diagonal.  Same results.
@@ -66,7 +67,11 @@ extern "C" void fg_topog_destroy(fg_topog *h)
 {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
+  if (h->stream) {
+    (void)hipStreamSynchronize(h->stream);
+    fg_pool_retire_stream(h->stream);             // the remap's plan ran on this stream (dev_pool.h: retire)
+    (void)hipStreamDestroy(h->stream);
+  }
   delete h;
 }
 

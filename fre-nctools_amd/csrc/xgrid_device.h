@@ -367,6 +367,18 @@ struct GcSplit {
 };
 void fgd_gc_clip_split(FgPairSpace ps, FgCells S, const double *mask, FgCells D, double *tmp_area, int *nacc, GcSplit g,
                        unsigned long long *stats, unsigned *err, hipStream_t st, hipStream_t st2, hipEvent_t e1, hipEvent_t e2);
+// Great-circle polygon-list search (fg_plan_create_polylist_gc): the source "cells" are convex polygons of 3..8 corners given as
+// unit vectors, n [npoly], x / y / z [npoly][8] clockwise, area [npoly] = the reference area of the 1e-6 ratio test.  The search
+// keeps one record of FG_GC_PREC doubles per polygon (layout at k_gc_poly_records); every pair goes through the general clip.
+#define FG_GC_PREC 32
+#define G_ERRBIT_GC_POLYN 1024u    // a polygon of the list has more than 8 corners
+struct FgGcPolyList { const int *n; const double *x, *y, *z; const double *area; int npoly; };
+void fgd_gc_poly_records(FgGcPolyList P, FgCells S, double *rec, unsigned *err, hipStream_t st);
+void fgd_gc_clip_poly(FgPairSpace ps, FgCells S, const double *rec, FgCells D, double *tmp_area, int *nacc, unsigned long long *stats,
+                      unsigned *err, hipStream_t st);
+// the clipped polygons of n exchange cells of such a plan: n_out [n], out [n][FG_GC_POLY_CAP][3]
+void fgd_gc_poly_polygons(long n, const int *x_src, const int *x_dst, const int *nv, const double *rec, FgCells D, double *out, int *n_out,
+                          hipStream_t st);
 #define FG_GC_POLY_CAP 16
 void fgd_gc_clip_batch(int n, const double *a, const double *b, double *out, int *n_out, double *area, hipStream_t st);
 void fgd_gc_area_batch(int npoly, int stride_pts, const double *xyz, const int *n, double *area, hipStream_t st);

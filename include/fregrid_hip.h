@@ -230,6 +230,17 @@ int fg_plan_get_polygons(const fg_plan *plan, int maxv, int *n_out, double *v0, 
 long fg_plan_create_polylist(int order, int npoly, const int *n, const double *lon, const double *lat, const double *lon_avg,
                              const double *area_ref, int nx_out, int ny_out, const double *lon_out, const double *lat_out,
                              int device, fg_plan **plan_out);
+/* The great-circle twin: the SOURCE cells are convex polygons of 3..8 vertices given as unit vectors, clockwise as
+ * clip_2dx2d_great_circle returns them -- n[npoly], x / y / z [npoly][8] (host); area_ref[npoly] = the area the 1e-6 ratio test
+ * uses for the polygon (great_circle_area(clip) / min(area_ref, destination cell area) > 1e-6).  lon_out / lat_out: the
+ * destination corners in radians; destination areas are get_grid_great_circle_area's.  Every (polygon, candidate cell) pair is
+ * clipped by clip_2dx2d_great_circle (create_xgrid.c:1479-1908) with the polygon first; exchange cells come polygon by polygon,
+ * destination cells ascending (i_in = polygon index, j_in = t_in = 0).  First order only.  A polygon with n < 3 takes no part;
+ * n > 8 is FG_ERR_ARG; npoly = 0 gives a plan of one empty polygon and no exchange cell.  The plan is a great-circle plan:
+ * fg_plan_get_xgrid / _polygons (x, y, z) / finalize / apply work on it.  make_coupler_mosaic.c:1662-1696 clips its remembered
+ * atmosphere x land polygons against the ocean cells this way under GREAT_CIRCLE_CLIP. */
+long fg_plan_create_polylist_gc(int npoly, const int *n, const double *x, const double *y, const double *z, const double *area_ref,
+                                int nx_out, int ny_out, const double *lon_out, const double *lat_out, int device, fg_plan **plan_out);
 /* cell areas computed during the search (get_grid_area semantics): source cells
  * concatenated over tiles / destination cells.  Host arrays, may be NULL. */
 int fg_plan_get_cell_area(const fg_plan *plan, double *area_in, double *area_out);
@@ -997,6 +1008,17 @@ int  fg_coupler_create(int interp_order, double area_ratio_thresh, int ntile_atm
                        const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nx_lnd, const int *ny_lnd,
                        const double *const *lon_lnd, const double *const *lat_lnd, int nx_ocn, int ny_ocn, const double *lon_ocn,
                        const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out);
+/* The tool's GREAT_CIRCLE_CLIP branch (:587-594, taken when the atmosphere grid carries great_circle_algorithm: a pole inside a
+ * cell): the argument list of fg_coupler_create; interp_order must be 1 (:593), anything else is FG_ERR_ARG.  The corners go up as
+ * lon / lat and become unit vectors on the device (fg_dev_latlon2xyz: the reference's latlon2xyz bits); cell areas are
+ * get_grid_great_circle_area's; every clip is clip_2dx2d_great_circle, every area great_circle_area; the remembered atmosphere x
+ * land polygons are searched against the ocean by fg_plan_create_polylist_gc's device twin.  The reference clips every pair of
+ * cells in this branch; here the searches prune by bounding caps.  Every other fg_coupler_* entry works on such a
+ * handle as on an order-1 legacy handle. */
+int  fg_coupler_create_gc(int interp_order, double area_ratio_thresh, int ntile_atm, const int *nx_atm, const int *ny_atm,
+                          const double *const *lon_atm, const double *const *lat_atm, int ntile_lnd, const int *nx_lnd, const int *ny_lnd,
+                          const double *const *lon_lnd, const double *const *lat_lnd, int nx_ocn, int ny_ocn, const double *lon_ocn,
+                          const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out);
 void fg_coupler_destroy(fg_coupler *h);
 void *fg_coupler_stream(fg_coupler *h);
 int  fg_coupler_run(fg_coupler *h);

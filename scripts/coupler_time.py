@@ -3,6 +3,7 @@
 
     python scripts/coupler_time.py [--runs 7] [--out profiles/coupler_summary.md] [--large 384 1440 1080] [--shared 96 360 200 144 90]
     python scripts/coupler_time.py --large-only --runs 1        (the run a kernel trace wraps)
+    python scripts/coupler_time.py --great-circle [--runs 7] [--out FILE] [--shared 96 360 200 144 90]
 
 Two cases.
 * large: a C<n> atmosphere with land on the atmosphere grid over a tripolar NX x NY ocean from -82 degrees (one row added by
@@ -128,6 +129,68 @@ def shared(fg, size, runs):
     return lines, ratio, same
 
 
+def great_circle(fg, size, runs):
+    """--great-circle: CouplerMosaic(clip_method="great_circle") against the legacy order-1 handle on the same grids, runs alternating
+    after a warm-up of each; then the polygon-list search per candidate pair against the quad x quad great-circle search per pair
+    with fg_set_gc_split(0) (the same general clip, so the ratio is what the wider lists cost)."""
+    ni, nx, ny, nxl, nyl = size
+    atm = cubed_sphere(fg, ni)
+    ocn, omask, ext = ocean(fg, nx, ny, True)
+    lo, la = fg.latlon_corners(nxl, nyl)
+    lnd = fg.GridConfig(nxl, nyl, lo, la)
+    keys = ("axl_candidates", "axo", "polygons_x_ocean", "lxo", "sums", "run")
+    lines = []
+    na, no, nl = 6 * ni * ni, ocn.nx * ocn.ny, nxl * nyl
+    for title, land in ((f"C{ni} atmosphere = land", None), (f"C{ni} atmosphere, {nxl} x {nyl} lat-lon land", [lnd])):
+        with fg.CouplerMosaic(atm, land, ocn, omask, interp_order=1, ocn_south_ext=ext) as ml, \
+                fg.CouplerMosaic(atm, land, ocn, omask, interp_order=1, ocn_south_ext=ext, clip_method="great_circle") as mg:
+            ml.run(); mg.run()
+            pl, pg = [], []
+            for _ in range(runs):
+                ml.run(); pl.append(ml.phase_ms())
+                mg.run(); pg.append(mg.phase_ms())
+            sl, sg = ml.stats(), mg.stats()
+            cl, cg = ml.phase_ms()["create"], mg.phase_ms()["create"]
+        # what the reference's GREAT_CIRCLE_CLIP branch clips: every pair (:1253-1267, :2549-2556)
+        brute = na * no + sg["npolygons"] * no + (0 if land is None else na * nl + nl * no)
+        lines += [f"## {title}, tripolar {nx} x {ny} ocean (+{ext} row), order 1", "",
+                  f"{runs} alternating runs of the two handles after a warm-up of each; median (largest deviation from it), ms.", "",
+                  "| clip | create | " + " | ".join(keys) + " |", "|---|---|" + "---|" * len(keys),
+                  f"| legacy | {cl:.3f} | " + " | ".join(_fmt([p[k] for p in pl]) for k in keys) + " |",
+                  f"| great circle | {cg:.3f} | " + " | ".join(_fmt([p[k] for p in pg]) for k in keys) + " |", "",
+                  f"great circle: {sg['naxo']} atmosphere x ocean, {sg['naxl']} atmosphere x land, {sg['nlxo']} land x ocean cells, {sg['npolygons']} remembered "
+                  f"polygons, {sg['searches']} searches, {sg['d2h_bytes']} bytes to the host, nbad {sg['nbad']}; legacy: {sl['naxo']} / {sl['naxl']} / {sl['nlxo']}.",
+                  f"Pairs the reference's branch clips for this job (no pruning there): {brute}.", ""]
+    # the n-gon clip against the quad clip, per candidate pair
+    L = fg.lib()
+    L.fg_set_profiling(1)
+    L.fg_set_gc_split(0)
+    try:
+        p = fg.XgridPlan.create_great_circle(atm, lnd)
+        pg = p.get_polygons(8)
+        x = p.get_xgrid()
+        a_atm, a_lnd = p.get_cell_area(nl)
+        p.destroy()
+        ok = pg["n"] <= 8
+        off = np.concatenate([[0], np.cumsum([g.nx * g.ny for g in atm])])
+        ref = np.minimum(a_lnd[x["j_out"] * nxl + x["i_out"]], a_atm[off[x["t_in"]] + x["j_in"] * ni + x["i_in"]])[ok]
+        tq, tp = [], []
+        for _ in range(runs + 1):
+            q = fg.XgridPlan.create_great_circle(atm, ocn)
+            tq.append((q.phase_ms()["clip_general"], q.stats()["pairs"])); q.destroy()
+            r = fg.XgridPlan.create_polylist_gc(pg["n"][ok], pg["x"][ok], pg["y"][ok], pg["z"][ok], ref, ocn)
+            tp.append((r.phase_ms()["clip_general"], r.stats()["pairs"])); r.destroy()
+    finally:
+        L.fg_set_gc_split(1)
+        L.fg_set_profiling(0)
+    mq, mp = _med([t[0] for t in tq[1:]])[0], _med([t[0] for t in tp[1:]])[0]
+    lines += ["## The general clip per candidate pair: polygons (k_gc_clip_poly) against quads (fg_set_gc_split(0))", "",
+              "| search | candidate pairs | clip phase, ms | ns per pair |", "|---|---|---|---|",
+              f"| C{ni} -> ocean, quad x quad, one-kernel clip | {tq[-1][1]} | {_fmt([t[0] for t in tq[1:]])} | {1e6 * mq / max(tq[-1][1], 1):.1f} |",
+              f"| {int(ok.sum())} remembered polygons -> ocean | {tp[-1][1]} | {_fmt([t[0] for t in tp[1:]])} | {1e6 * mp / max(tp[-1][1], 1):.1f} |", ""]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=7)
@@ -135,9 +198,17 @@ def main():
     ap.add_argument("--large", type=int, nargs=3, default=[384, 1440, 1080], metavar=("NI", "NX", "NY"))
     ap.add_argument("--shared", type=int, nargs=5, default=[96, 360, 200, 144, 90], metavar=("NI", "NX", "NY", "NX_LND", "NY_LND"))
     ap.add_argument("--large-only", action="store_true")
+    ap.add_argument("--great-circle", action="store_true", help="the great-circle handle against the legacy one on the --shared grids")
     args = ap.parse_args()
     fg = __graft_entry__.load_package()
     fg._lib.require_gpu()
+    if args.great_circle:
+        text = "\n".join(["# make_coupler_mosaic's GREAT_CIRCLE_CLIP branch on the device: timing", ""] + great_circle(fg, args.shared, args.runs)) + "\n"
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
+        return
     lines = ["# make_coupler_mosaic's exchange grids on the device: timing", ""]
     a, gap = large(fg, args.large, args.runs)
     lines += a
