@@ -30,7 +30,7 @@ EXPORTS = [
     "fg_last_error", "fg_device_count", "fg_plan_create", "fg_plan_create_dev", "fg_plan_create_empty",
     "fg_plan_destroy", "fg_plan_set_stream", "fg_pool_release", "fg_plan_nxgrid", "fg_plan_ncells_in",
     "fg_plan_cell_sums_dev", "fg_plan_copy_cell_sums", "fg_plan_accumulate_cell_sums", "fg_plan_accumulate_cell_sums_async", "fg_dev_gather_f64", "fg_dev_scatter_f64", "fg_plan_finalize", "fg_plan_get_xgrid", "fg_plan_get_polygons", "fg_plan_create_polylist", "fg_plan_get_cell_struct",
-    "fg_plan_get_cell_area", "fg_plan_set_xgrid", "fg_plan_apply", "fg_plan_apply_interleaved", "fg_plan_apply_records", "fg_plan_apply_levels", "fg_plan_apply_records_levels", "fg_plan_levels_capacity", "fg_plan_apply_ex", "fg_plan_mono_begin",
+    "fg_plan_get_cell_area", "fg_plan_set_xgrid", "fg_plan_apply", "fg_plan_apply_interleaved", "fg_plan_apply_records", "fg_plan_apply_levels", "fg_plan_apply_records_levels", "fg_plan_levels_capacity", "fg_plan_apply_levels_ex", "fg_plan_apply_records_levels_ex", "fg_plan_levels_ex_capacity", "fg_plan_apply_ex", "fg_plan_mono_begin",
     "fg_plan_mono_minmax_dev", "fg_plan_mono_copy_minmax", "fg_plan_mono_end",
     "fg_plan_create_great_circle", "fg_plan_create_great_circle_dev", "fg_latlon2xyz", "create_xgrid_great_circle",
     "create_xgrid_great_circle_", "get_grid_great_circle_area", "get_grid_great_circle_area_", "clip_2dx2d_great_circle",
@@ -45,7 +45,7 @@ EXPORTS = [
     "fg_nc_open", "fg_nc_create", "fg_nc_def_dim", "fg_nc_def_var", "fg_nc_put_att_text", "fg_nc_put_att_double", "fg_nc_enddef",
     "fg_nc_inq_ndims", "fg_nc_inq_nvars", "fg_nc_inq_numrecs", "fg_nc_inq_dimid", "fg_nc_inq_dim", "fg_nc_inq_varid", "fg_nc_inq_var",
     "fg_nc_get_att_double", "fg_nc_get_att_text", "fg_nc_get_vara", "fg_nc_get_vara_double", "fg_nc_put_vara", "fg_nc_put_vara_double",
-    "fg_nc_close", "fg_nc_last_error", "fg_dev_widen", "fg_dev_narrow", "fg_sweep_create", "fg_sweep_run", "fg_sweep_run_levels", "fg_sweep_destroy", "fg_host_alloc", "fg_host_free",
+    "fg_nc_close", "fg_nc_last_error", "fg_dev_widen", "fg_dev_narrow", "fg_sweep_create", "fg_sweep_run", "fg_sweep_run_levels", "fg_sweep_run_levels_ex", "fg_sweep_destroy", "fg_host_alloc", "fg_host_free",
     "fg_plan_stats", "fg_set_search_mode", "fg_set_search_cull", "fg_set_search_finalize", "fg_set_search_async", "fg_set_search_rect", "fg_set_search_wide_cap", "fg_set_search_frame", "fg_set_apply_xcd", "fg_set_apply_vec", "fg_set_apply_ep", "fg_set_gc_split", "fg_set_profiling", "fg_plan_phase_ms", "fg_gnomonic_ed_corners", "fg_latlon_corners",
     "fg_bilin_create", "fg_bilin_create_from_weights", "fg_bilin_destroy", "fg_bilin_get_index_weight", "fg_bilin_npoints_fine",
     "fg_bilin_nlon_fine", "fg_bilin_nlat_fine", "fg_bilin_nlon", "fg_bilin_nlat", "fg_bilin_ncells", "fg_bilin_set_stream",
@@ -205,6 +205,12 @@ def lib():
     L.fg_plan_apply_records_levels.restype = C.c_int
     L.fg_plan_levels_capacity.argtypes = []
     L.fg_plan_levels_capacity.restype = C.c_int
+    L.fg_plan_apply_levels_ex.argtypes = [vp, C.POINTER(ApplyOpts), vp, vp, vp, vp, C.c_int, C.c_long, vp, dp]
+    L.fg_plan_apply_levels_ex.restype = C.c_int
+    L.fg_plan_apply_records_levels_ex.argtypes = [vp, C.POINTER(ApplyOpts), C.c_int, vp, vp, C.c_long, vp, dp]
+    L.fg_plan_apply_records_levels_ex.restype = C.c_int
+    L.fg_plan_levels_ex_capacity.argtypes = [C.c_int]
+    L.fg_plan_levels_ex_capacity.restype = C.c_int
     ao = C.POINTER(ApplyOpts)
     L.fg_plan_apply_ex.argtypes = [vp, ao, vp, vp, vp, vp, C.c_int, vp, dp]
     L.fg_plan_apply_ex.restype = C.c_int
@@ -296,6 +302,7 @@ def lib():
     L.fg_sweep_create.argtypes = [C.c_int, C.POINTER(vp), vp, C.c_int, C.c_int, C.POINTER(vp)]; L.fg_sweep_create.restype = C.c_int
     L.fg_sweep_run.argtypes = [vp, vp, C.c_long, C.c_double, C.c_double, C.c_double, C.POINTER(vp)]; L.fg_sweep_run.restype = C.c_int
     L.fg_sweep_run_levels.argtypes = [vp, vp, C.c_long, C.c_double, C.c_double, C.c_double, C.POINTER(vp)]; L.fg_sweep_run_levels.restype = C.c_int
+    L.fg_sweep_run_levels_ex.argtypes = [vp, C.POINTER(ApplyOpts), vp, C.c_long, C.c_double, C.c_double, C.POINTER(vp)]; L.fg_sweep_run_levels_ex.restype = C.c_int
     L.fg_sweep_destroy.argtypes = [vp]; L.fg_sweep_destroy.restype = None
     L.fg_host_alloc.argtypes = [C.c_size_t]; L.fg_host_alloc.restype = vp
     L.fg_host_free.argtypes = [vp]; L.fg_host_free.restype = None

@@ -445,6 +445,47 @@ class XgridPlan:
         return g if want_gsum else None
 
     @staticmethod
+    def _levels_opts(has_missing, missing, weight_t, cell_methods_sum, field_area_t, area_missing, cell_area_in_t, cell_area_out_t,
+                     monotonic=False):
+        addr = lambda t: t.data_ptr() if t is not None else None
+        return _lib.ApplyOpts(1 if has_missing else 0, float(missing), addr(weight_t), 1 if cell_methods_sum else 0, addr(field_area_t),
+                              float(area_missing), addr(cell_area_in_t), addr(cell_area_out_t), 1 if monotonic else 0)
+
+    def apply_levels_ex(self, data_t, out_t, nlev, grad_x_t=None, grad_y_t=None, grad_mask_t=None, has_missing=False, missing=-MAXVAL,
+                        weight_t=None, cell_methods_sum=False, field_area_t=None, area_missing=-MAXVAL, cell_area_in_t=None,
+                        cell_area_out_t=None, field_area_per_level=False, monotonic=False, want_gsum=False):
+        """The level loop of a field with a weight field, cell_methods = sum, cell_measures or --target_grid in one call
+        (fg_plan_apply_levels_ex): level k of out [nlev, ndst] is what apply_ex(nz=1) gives on level k alone with the same options.
+        Buffers as apply_levels takes them; field_area_t is [ncells_in], or [nlev, ncells_in] with field_area_per_level (an area
+        variable with a z axis).  The monotone limiter is refused.  Returns the per-level sums (numpy [nlev]) with want_gsum."""
+        o = self._levels_opts(has_missing, missing, weight_t, cell_methods_sum, field_area_t, area_missing, cell_area_in_t,
+                              cell_area_out_t, monotonic)
+        g = np.zeros(nlev, dtype=np.float64)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        check(lib().fg_plan_apply_levels_ex(self._h, C.byref(o), ptr(data_t), ptr(grad_x_t), ptr(grad_y_t), ptr(grad_mask_t), nlev,
+                                            self.ncells_in if field_area_per_level else 0, ptr(out_t), _dp(g) if want_gsum else None))
+        return g if want_gsum else None
+
+    def apply_records_levels_ex(self, nz, rec_t, maskbits_t, out_t, has_missing=False, missing=-MAXVAL, weight_t=None,
+                                cell_methods_sum=False, field_area_t=None, area_missing=-MAXVAL, cell_area_in_t=None,
+                                cell_area_out_t=None, field_area_per_level=False, monotonic=False, want_gsum=False):
+        """apply_levels_ex for nz <= 8 levels on what C2lPrep.records_levels wrote (fg_plan_apply_records_levels_ex); maskbits_t
+        may be None without has_missing.  Bit-identical to apply_levels_ex()."""
+        o = self._levels_opts(has_missing, missing, weight_t, cell_methods_sum, field_area_t, area_missing, cell_area_in_t,
+                              cell_area_out_t, monotonic)
+        g = np.zeros(nz, dtype=np.float64)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        check(lib().fg_plan_apply_records_levels_ex(self._h, C.byref(o), nz, ptr(rec_t), ptr(maskbits_t),
+                                                    self.ncells_in if field_area_per_level else 0, ptr(out_t),
+                                                    _dp(g) if want_gsum else None))
+        return g if want_gsum else None
+
+    @staticmethod
+    def levels_ex_capacity(per_level_area=False):
+        """exchange cells apply_levels_ex stages per chunk (fg_plan_levels_ex_capacity)"""
+        return int(lib().fg_plan_levels_ex_capacity(1 if per_level_area else 0))
+
+    @staticmethod
     def levels_capacity():
         """exchange cells apply_levels stages per chunk (fg_plan_levels_capacity)"""
         return int(lib().fg_plan_levels_capacity())

@@ -918,6 +918,8 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8(int ndst, FgCsr csr, const do
 // product +0.0, and the (row, level) lane carries a touched flag beside its two sums.
 //   gbits (ORDER 2): per source cell, bit k set = level k takes the flat value (fregrid_util.c:2203-2215); k_gmask_bits makes them.
 //   out, row_sum: level-major [level][out_ld], levels < nb_valid only.  The tile mapping is the identity (xcd_band is not read).
+// (Weight field, cell_measures, cell_methods = sum and --target_grid on eight levels: k_apply_ep8x below.  This kernel is the
+// bandwidth path and carries none of their gathers.)
 template <int ORDER, bool MASKED, int TPB, int CAP, int ROWS>
 __global__ __launch_bounds__(TPB) void k_apply_ep8g(int ndst, FgCsr csr, const double *rec, const unsigned char *gbits, double missing,
                                                     double *out, double *row_sum, long out_ld, int nb_valid, int xcd_band)
@@ -998,6 +1000,156 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8g(int ndst, FgCsr csr, const d
   if (row_sum) row_sum[MASKED ? (size_t)lev * out_ld + T.d : (size_t)T.d * NB + lev] = rs;
   if (MASKED || out_ld > 0) { if (lev < nb_valid) out[(size_t)lev * out_ld + T.d] = r; }
   else out[(size_t)T.d * NB + lev] = r;
+}
+
+// Eight levels with every option of do_scalar_conserve_interp but the monotone limiter (fg_plan_apply_levels_ex,
+// fg_plan_apply_records_levels_ex, fg_sweep_run_levels_ex): the sibling of k_apply_ep8g<MASKED> with k_apply_epx's per-cell
+// arithmetic.  Level k of the output is do_scalar_conserve_interp(nz = 1) on level k alone with the same options (the reference
+// refuses nz > 1 for them, conserve_interp.c:544-546, so fregrid.c:1045-1083 loops over the levels); per (exchange cell, level) the
+// operations come in the reference's order -- area *= weight, the missing test, area /= cell_area (sum) or the area_missing check
+// and area *= (field_area / cell_area) (cell_measures), value * area -- and a cell left by `continue` adds +0.0 and is not counted.
+// The --target_grid term (:842-858) is taken from every exchange cell, missing or not: area * field_area / cell_area, left to
+// right, or the plain area without cell_measures.
+//   APL false: weight, cell_area and field_area are per source cell and the same for the eight levels: the product table keeps ONE
+//     scaled area and ONE target term per exchange cell beside the 8-bit validity mask, as k_apply_ep8g keeps one area.
+//   APL true:  field_area has a level axis (area_has_zaxis, fregrid_util.c:2156-2162; e.g. volcello); fa8 holds it interleaved
+//     [source cell][8] (zero beyond nb_valid), one 64-byte gather like the field's.  Scaled area and target term are per (exchange
+//     cell, level): the table is 24 doubles per cell, so CAP is half the other form's.
+// The (row, level) lane adds three sums in CSR order and carries them from chunk to chunk.  Tile mapping: the identity.
+template <int ORDER, bool APL, int TPB, int CAP, int ROWS>
+__global__ __launch_bounds__(TPB) void k_apply_ep8x(int ndst, FgCsr csr, const double *rec, const unsigned char *gbits, FgApplyEx o,
+                                                    const double *fa8, double *out, double *row_sum, long out_ld, int nb_valid, int *err)
+{
+  constexpr int NB = 8;
+  constexpr int EPP = TPB / 2, PASS = CAP / EPP;          // gather phase: a lane pair per exchange cell, EPP cells per pass
+  constexpr int AW = APL ? NB : 1;                        // scaled areas / target terms per exchange cell
+  static_assert(ROWS * NB <= TPB && CAP % EPP == 0, "a lane per (row, level)");
+  // one buffer: the staged CSR records first (<= 32 B each), then the products, the scaled areas and the target terms
+  __shared__ __attribute__((aligned(16))) double sh_raw[CAP * (NB + 2 * AW)];
+  __shared__ unsigned char sh_vm[CAP * 2];                 // validity of levels 0-3 and 4-7 of every staged exchange cell
+  typedef CsrEntry<ORDER> Entry;
+  Entry *sh_e = reinterpret_cast<Entry *>(sh_raw);
+  double *sh_p = sh_raw, *sh_a = sh_raw + CAP * NB, *sh_t = sh_a + CAP * AW;
+  const int t = threadIdx.x;
+  const EpTile T = ep_tile<ROWS, NB>(csr, ndst, (int)blockIdx.x);
+  const int lev = T.lev, vsel = lev >> 2, vbit = lev & 3;
+  const bool scaled = o.sum || o.field_area;              // (block-uniform, as every test of `o` below)
+  double acc = 0.0, asum = 0.0, asum_t = 0.0;
+  unsigned touched = 0;
+  for (int c0 = T.q0; c0 < T.q1; c0 += CAP) {              // (block-uniform)
+    const int n = min(CAP, T.q1 - c0);
+    if (c0 > T.q0) __syncthreads();                        // the previous chunk's products have been added
+    ep_stage_loop<TPB>(sh_e, csr_entries<ORDER>(csr) + c0, n);
+    __syncthreads();
+    const int h = (t & 1) * 4;                             // four levels per lane of the pair
+    VecD<4> fv[PASS], gxv[PASS], gyv[PASS], fav[PASS];
+    Entry E[PASS];
+    double wgt[PASS], ca[PASS], fa[PASS];
+    unsigned gb[PASS];
+#pragma unroll
+    for (int j = 0; j < PASS; j++) {
+      gb[j] = 0; wgt[j] = 1.0; ca[j] = 1.0; fa[j] = 0.0;
+      if (EPP * j < n) {                                   // (block-uniform)
+        const int i = min(t / 2 + EPP * j, n - 1);
+        E[j] = sh_e[i];
+        int s;
+        if constexpr (ORDER == 2) {
+          s = E[j].idx_g;
+          const double *pf = rec + (size_t)s * (3 * NB) + h;
+          fv[j] = *reinterpret_cast<const VecD<4> *>(pf);
+          gxv[j] = *reinterpret_cast<const VecD<4> *>(pf + NB);
+          gyv[j] = *reinterpret_cast<const VecD<4> *>(pf + 2 * NB);
+          if (gbits) gb[j] = gbits[s];
+        } else {
+          s = E[j].idx_f;
+          fv[j] = *reinterpret_cast<const VecD<4> *>(rec + (size_t)s * NB + h);
+        }
+        // every value the cell may need, in the same round
+        if (o.weight) wgt[j] = o.weight[s];
+        if (scaled) ca[j] = o.cell_area[s];
+        if constexpr (APL) fav[j] = *reinterpret_cast<const VecD<4> *>(fa8 + (size_t)s * NB + h);
+        else if (o.field_area) fa[j] = o.field_area[s];
+      }
+    }
+    __syncthreads();                                       // the records are in registers: the buffer becomes the product table
+#pragma unroll
+    for (int j = 0; j < PASS; j++) {
+      const int i = t / 2 + EPP * j;
+      if (EPP * j < n && i < n) {
+        const double a0 = E[j].area;
+        double aw = a0;
+        if (o.weight) aw *= wgt[j];                        // :574 ...: the weight comes before the missing test
+        VecD<4> pv;
+        unsigned vm = 0;
+        if constexpr (!APL) {
+          double tt = 0.0, as = aw;
+          bool bad = false;
+          if (o.cell_area_out) tt = o.field_area ? (a0 * fa[j] / ca[j]) : a0;    // :845-860 (plain exchange-cell area, no weight)
+          if (o.sum) as = aw / ca[j];
+          else if (o.field_area) { bad = o.has_missing && fa[j] == o.area_missing; as = aw * (fa[j] / ca[j]); }
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            double v = fv[j].v[k];
+            bool ok = !(o.has_missing && v == o.missing);  // `if (data == missing) continue`
+            if (ok && bad) { if (h + k < nb_valid) atomicOr(err, FG_XERR_AREA_MISSING); ok = false; }
+            if constexpr (ORDER == 2) { if (!((gb[j] >> (h + k)) & 1u)) v = (v + gxv[j].v[k] * E[j].di + gyv[j].v[k] * E[j].dj); }
+            pv.v[k] = ok ? v * as : 0.0;
+            vm |= (ok ? 1u : 0u) << k;
+          }
+          if (h == 0) { sh_a[i] = as; sh_t[i] = tt; }
+        } else {
+          VecD<4> av, tv;
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            double v = fv[j].v[k];
+            const double f = fav[j].v[k];
+            bool ok = !(o.has_missing && v == o.missing);
+            if (ok && o.has_missing && f == o.area_missing) { if (h + k < nb_valid) atomicOr(err, FG_XERR_AREA_MISSING); ok = false; }
+            const double as = aw * (f / ca[j]);
+            if constexpr (ORDER == 2) { if (!((gb[j] >> (h + k)) & 1u)) v = (v + gxv[j].v[k] * E[j].di + gyv[j].v[k] * E[j].dj); }
+            pv.v[k] = ok ? v * as : 0.0;
+            av.v[k] = ok ? as : 0.0;
+            tv.v[k] = o.cell_area_out ? (a0 * f / ca[j]) : 0.0;
+            vm |= (ok ? 1u : 0u) << k;
+          }
+          *reinterpret_cast<VecD<4> *>(sh_a + i * NB + h) = av;
+          *reinterpret_cast<VecD<4> *>(sh_t + i * NB + h) = tv;
+        }
+        *reinterpret_cast<VecD<4> *>(sh_p + i * NB + h) = pv;
+        sh_vm[i * 2 + (t & 1)] = (unsigned char)vm;
+      }
+    }
+    __syncthreads();
+    if (T.lane) {                                          // three sums and the flag: four LDS reads of each in flight, adds in CSR order
+      const int qa = max(T.b, c0) - c0, qb = min(T.e, c0 + n) - c0;
+      auto term = [&](int q, double &p, double &a, double &tt, unsigned &ok) {
+        ok = (sh_vm[q * 2 + vsel] >> vbit) & 1u;
+        p = sh_p[q * NB + lev];
+        if constexpr (APL) { a = sh_a[q * NB + lev]; tt = sh_t[q * NB + lev]; }
+        else { a = ok ? sh_a[q] : 0.0; tt = sh_t[q]; }
+      };
+      int q = qa;
+      for (; q + 4 <= qb; q += 4) {
+        double p[4], a[4], tt[4];
+        unsigned ok[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) term(q + k, p[k], a[k], tt[k], ok[k]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { asum_t += tt[k]; acc += p[k]; asum += a[k]; touched |= ok[k]; }
+      }
+      for (; q < qb; q++) {
+        double p, a, tt;
+        unsigned ok;
+        term(q, p, a, tt, ok);
+        asum_t += tt; acc += p; asum += a; touched |= ok;
+      }
+    }
+  }
+  if (!T.lane || T.d >= ndst || lev >= nb_valid) return;
+  double rs;
+  const double r = apply_finish_ex(o, T.d, acc, asum, asum_t, touched != 0, rs);
+  if (row_sum) row_sum[(size_t)lev * out_ld + T.d] = rs;
+  out[(size_t)lev * out_ld + T.d] = r;
 }
 
 // grad_mask int [nb][ncells] (fg_c2l_gradient) -> one byte per source cell, bit k = level k
@@ -1282,6 +1434,28 @@ void fgd_apply_levels8(int order, int ndst, long nx, FgCsr csr, const double *re
   if (ndst <= 0) return;
   if (order == 2) apply_ep8g<2, true, FG_LEVELS_CAP, 32, 8, 2, 1>(ndst, nx, csr, rec, gbits, missing, out, row_sum, ld, nb_valid, 0, st);
   else            apply_ep8g<1, true, FG_LEVELS_CAP, 32, 8, 2, 1>(ndst, nx, csr, rec, gbits, missing, out, row_sum, ld, nb_valid, 0, st);
+}
+// the same with the options of FgApplyEx (k_apply_ep8x); fa8 != null: the per-level area, interleaved [source cell][8].  Rows per
+// tile by the mean row length, so that a tile's exchange cells about fill one chunk: 32 / 16 / 2 / 1 rows on chunks of
+// FG_LEVELS_EX_CAP, 16 / 8 / 2 / 1 on the chunks of half that size the per-level table leaves room for.
+void fgd_apply_levels8x(int order, int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, FgApplyEx o, const double *fa8,
+                        double *out, double *row_sum, long ld, int nb_valid, int *err, hipStream_t st)
+{
+  if (ndst <= 0) return;
+  auto go = [&](auto O) {
+    constexpr int ORD = decltype(O)::value;
+    if (fa8)
+      by_row_length<16, 8, 2, 1>(nx / ndst, [&](auto R) {
+        k_apply_ep8x<ORD, true, 256, FG_LEVELS_EX_CAP_Z, decltype(R)::value><<<nblk(ndst, decltype(R)::value), 256, 0, st>>>(
+            ndst, csr, rec, gbits, o, fa8, out, row_sum, ld, nb_valid, err);
+      });
+    else
+      by_row_length<32, 16, 2, 1>(nx / ndst, [&](auto R) {
+        k_apply_ep8x<ORD, false, 256, FG_LEVELS_EX_CAP, decltype(R)::value><<<nblk(ndst, decltype(R)::value), 256, 0, st>>>(
+            ndst, csr, rec, gbits, o, nullptr, out, row_sum, ld, nb_valid, err);
+      });
+  };
+  if (order == 2) go(Int<2>()); else go(Int<1>());
 }
 void fgd_gmask_bits(long n, const int *gmask, long ld, int nb, unsigned char *bits, hipStream_t st)
 {

@@ -392,6 +392,7 @@ struct fg_plan {
   double *il_f = nullptr, *il_out = nullptr, *il_rs = nullptr;   // [cell][8] scratch (order 1 field, output, row sums)
   double *il_m = nullptr;                                        // order 2: merged records [source cell][3][8] (k_merge3)
   unsigned char *lv_bits = nullptr;                              // order 2, fg_plan_apply_levels: gradient-mask bits per source cell
+  double *lx_fa = nullptr;                                       // fg_plan_apply_levels_ex: a chunk's per-level field_area [source cell][8]
   long stats[FG_NSTATS] = {0};
   long search_d2h = 0;           // bytes the search read back: one counter block per attempt
   // monotone limiter scratch (fg_plan_mono_*): limited values per CSR entry, per-source-cell bounds, error word
@@ -2434,6 +2435,141 @@ extern "C" int fg_plan_apply_ex(fg_plan *pl, const fg_apply_opts *o, const doubl
   }
   return ex_error_word(pl);
 }
+
+// ------------------------------------------------------------------- the level loop of these options, eight levels per launch
+// fg_plan_apply_ex(nz = 1) per level is what the reference does for weight / sum / cell_measures / --target_grid fields
+// (conserve_interp.c:544-546 refuse nz > 1, fregrid.c:1045-1083 loop); here eight levels share a launch of k_apply_ep8x and level k
+// keeps the bits of that one-level call, its sum included (reduced per level as levels_gsum does).  No limiter.
+extern "C" int fg_plan_levels_ex_capacity(int per_level_area) { return per_level_area ? FG_LEVELS_EX_CAP_Z : FG_LEVELS_EX_CAP; }
+
+static int levels_ex_check(fg_plan *pl, const fg_apply_opts *o, const void *data, const void *out, long field_area_ld, const char *who)
+{
+  if (!pl || !o || !data || !out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "%s: the plan is not finalized (fg_plan_finalize)", who);
+  if (o->monotonic) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter works on one level per call (fg_plan_apply_ex)", who);
+  if (field_area_ld != 0 && field_area_ld != pl->nsrc)
+    return fg_fail(FG_ERR_ARG, "%s: field_area_ld must be 0 (one area for all levels) or ncells_in (an area per level)", who);
+  if (field_area_ld != 0 && !o->field_area) return fg_fail(FG_ERR_ARG, "%s: field_area_ld is set but opts->field_area is NULL", who);
+  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
+    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
+  return 0;
+}
+
+// scratch of a call; fa8: the chunk's per-level area interleaved [source cell][8]
+static int levels_ex_scratch(fg_plan *pl, bool want_rs, bool want_il, bool want_fa8)
+{
+  int rc = levels_scratch(pl, want_rs, want_il);
+  if (rc) return rc;
+  if (!pl->xerr) { pl->xerr = pl->alloc<int>(4); if (!pl->xerr) return fg_fail(FG_ERR_HIP, "out of device memory"); }
+  if (want_fa8 && !pl->lx_fa) {
+    pl->lx_fa = pl->alloc<double>((size_t)(pl->nsrc > 0 ? pl->nsrc : 1) * 8);
+    if (!pl->lx_fa) return fg_fail(FG_ERR_HIP, "out of device memory");
+  }
+  return 0;
+}
+
+// the options as the kernel takes them; cell_methods = sum uses no field_area (:582-588 is the else branch)
+static FgApplyEx levels_ex_pack(fg_plan *pl, const fg_apply_opts *o, bool *per_level, long field_area_ld)
+{
+  FgApplyEx x = ex_pack(pl, o, nullptr);
+  if (x.sum) x.field_area = nullptr;
+  *per_level = field_area_ld != 0 && x.field_area != nullptr;
+  return x;
+}
+
+// queued (the streamed sweep, fg_sweep_run_levels_ex): the error word is neither cleared nor read here, so that the host does not wait
+// for the chunk -- fg_plan_levels_ex_begin clears it before the first chunk, fg_plan_levels_ex_end reads it after the last
+static int levels_ex_run(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
+                         const int *grad_mask, int nlev, long field_area_ld, double *out, double *gsum_out, bool queued)
+{
+  const char *who = "fg_plan_apply_levels_ex";
+  int rc = levels_ex_check(pl, o, data, out, field_area_ld, who);
+  if (rc) return rc;
+  if (nlev < 1) return fg_fail(FG_ERR_ARG, "%s: nlev must be >= 1", who);
+  if (pl->order == 2 && (!grad_x || !grad_y)) return fg_fail(FG_ERR_ARG, "%s: order 2 needs grad_x and grad_y [nlev][ncells_in]", who);
+  FGCHK(hipSetDevice(pl->device));
+  bool per_level;
+  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, field_area_ld);
+  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, true, per_level))) return rc;
+  hipStream_t st = pl->stream;
+  const int ndst = pl->ndst;
+  const bool masks = pl->order == 2 && o->has_missing && grad_mask;
+  if (!queued) FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
+  apply_span_begin(pl, st);
+  int nred = 0;
+  for (int k0 = 0; k0 < nlev; k0 += 8) {
+    const int nbv = (nlev - k0 < 8) ? nlev - k0 : 8;
+    const double *f = data + (size_t)k0 * pl->f_stride;
+    double *rs = gsum_out ? pl->il_rs : nullptr;
+    if (per_level) fgd_interleave(8, pl->nsrc, x.field_area + (size_t)k0 * field_area_ld, field_area_ld, nbv, pl->lx_fa, st);
+    if (pl->order == 2) {
+      fgd_merge3(8, pl->nsrc, pl->src_idx_f, f, pl->f_stride, grad_x + (size_t)k0 * pl->nsrc, grad_y + (size_t)k0 * pl->nsrc, pl->nsrc,
+                 nbv, pl->il_m, st);
+      if (masks) fgd_gmask_bits(pl->nsrc, grad_mask + (size_t)k0 * pl->nsrc, pl->nsrc, nbv, pl->lv_bits, st);
+    } else
+      interleave_field(pl, f, 8, nbv, st);
+    fgd_apply_levels8x(pl->order, ndst, pl->nx, pl->csr, pl->order == 2 ? pl->il_m : pl->il_f, masks ? pl->lv_bits : nullptr, x,
+                       per_level ? pl->lx_fa : nullptr, out + (size_t)k0 * ndst, rs, (long)ndst, nbv, pl->xerr, st);
+    if (gsum_out) { rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
+  }
+  apply_span_end(pl);
+  FGCHK(hipGetLastError());
+  return queued ? 0 : ex_error_word(pl);
+}
+
+extern "C" int fg_plan_apply_levels_ex(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
+                                       const int *grad_mask, int nlev, long field_area_ld, double *out, double *gsum_out)
+{
+  return levels_ex_run(pl, o, data, grad_x, grad_y, grad_mask, nlev, field_area_ld, out, gsum_out, false);
+}
+
+static int records_levels_ex_run(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
+                                 long field_area_ld, double *out, double *gsum_out, bool queued)
+{
+  const char *who = "fg_plan_apply_records_levels_ex";
+  int rc = levels_ex_check(pl, o, rec, out, field_area_ld, who);
+  if (rc) return rc;
+  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: records carry gradients, the plan is first order", who);
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per call", who);
+  if (o->has_missing && !maskbits) return fg_fail(FG_ERR_ARG, "%s: a field with missing values needs the gradient-mask bits", who);
+  FGCHK(hipSetDevice(pl->device));
+  bool per_level;
+  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, field_area_ld);
+  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, false, per_level))) return rc;
+  hipStream_t st = pl->stream;
+  if (!queued) FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
+  apply_span_begin(pl, st);
+  if (per_level) fgd_interleave(8, pl->nsrc, x.field_area, field_area_ld, nz, pl->lx_fa, st);
+  fgd_apply_levels8x(2, pl->ndst, pl->nx, pl->csr, rec, o->has_missing ? maskbits : nullptr, x, per_level ? pl->lx_fa : nullptr, out,
+                     gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, pl->xerr, st);
+  apply_span_end(pl);
+  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
+  FGCHK(hipGetLastError());
+  return queued ? 0 : ex_error_word(pl);
+}
+
+extern "C" int fg_plan_apply_records_levels_ex(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
+                                               long field_area_ld, double *out, double *gsum_out)
+{
+  return records_levels_ex_run(pl, o, nz, rec, maskbits, field_area_ld, out, gsum_out, false);
+}
+
+// for sweep.hip: the chunks of one streamed run, queued on the plan's (borrowed) stream between _begin and _end
+int fg_plan_levels_ex_begin(fg_plan *pl)
+{
+  if (!pl) return fg_fail(FG_ERR_ARG, "null argument");
+  FGCHK(hipSetDevice(pl->device));
+  if (!pl->xerr) { pl->xerr = pl->alloc<int>(4); if (!pl->xerr) return fg_fail(FG_ERR_HIP, "out of device memory"); }
+  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
+  return 0;
+}
+int fg_plan_levels_ex_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const double *data, const double *rec, const unsigned char *maskbits,
+                            double *out)
+{
+  return rec ? records_levels_ex_run(pl, o, nz, rec, maskbits, 0, out, nullptr, true)
+             : levels_ex_run(pl, o, data, nullptr, nullptr, nullptr, nz, 0, out, nullptr, true);
+}
+int fg_plan_levels_ex_end(fg_plan *pl) { return ex_error_word(pl); }
 
 // The sweep on fields the caller already keeps interleaved: data_il [F][nb], grad_x_il/grad_y_il [ncells_in][nb],
 // out_il [ndst][nb]; nb in {2, 4, 8}; no missing values.  Skips the two transposes of fg_plan_apply.

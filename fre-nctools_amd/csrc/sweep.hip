@@ -24,6 +24,10 @@ extern "C" int fg_plan_device(const fg_plan *pl);
 int fg_plan_borrow_stream(fg_plan *pl, void *stream, void **saved, int *saved_own);
 void fg_plan_return_stream(fg_plan *pl, void *saved, int saved_own);
 int fg_plan_is_finalized(const fg_plan *pl);
+int fg_plan_levels_ex_begin(fg_plan *pl);
+int fg_plan_levels_ex_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const double *data, const double *rec, const unsigned char *maskbits,
+                            double *out);
+int fg_plan_levels_ex_end(fg_plan *pl);
 int fg_c2l_borrow_stream(fg_c2l *h, void *stream, void **saved, int *saved_own);
 void fg_c2l_return_stream(fg_c2l *h, void *saved, int saved_own);
 
@@ -197,14 +201,17 @@ static int slot_retire(fg_sweep *sw, fg_sweep::Slot &sl, void *const *host_out)
   return 0;
 }
 
-// masked: every level carries missing values of its own (fg_sweep_run_levels); else every value is data (fg_sweep_run)
+// masked: every level carries missing values of its own (fg_sweep_run_levels); else every value is data (fg_sweep_run).
+// xo != null (fg_sweep_run_levels_ex): the level loop with these options, fg_plan_apply_levels_ex / _records_levels_ex per chunk;
+// `masked` is then xo->has_missing.
 static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
-                     void *const *host_out, bool masked)
+                     void *const *host_out, bool masked, const fg_apply_opts *xo = nullptr)
 {
-  if (!sw || !host_in || !host_out || nlev < 1) return fg_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null argument" : "fg_sweep_run: null argument");
-  for (size_t p = 0; p < sw->plans.size(); p++) if (!host_out[p]) return fg_fail(FG_ERR_ARG, masked ? "fg_sweep_run_levels: null output array" : "fg_sweep_run: null output array");
-  if (masked)
-    for (fg_plan *p : sw->plans) if (!fg_plan_is_finalized(p)) return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels: a plan is not finalized (fg_plan_finalize)");
+  const char *who = xo ? "fg_sweep_run_levels_ex" : masked ? "fg_sweep_run_levels" : "fg_sweep_run";
+  if (!sw || !host_in || !host_out || nlev < 1) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  for (size_t p = 0; p < sw->plans.size(); p++) if (!host_out[p]) return fg_fail(FG_ERR_ARG, "%s: null output array", who);
+  if (masked || xo)
+    for (fg_plan *p : sw->plans) if (!fg_plan_is_finalized(p)) return fg_fail(FG_ERR_ARG, "%s: a plan is not finalized (fg_plan_finalize)", who);
   FGCHK(hipSetDevice(sw->device));
   // The plans and the gradient object launch on OUR compute stream for the duration of this call only: several fg_sweep objects
   // (one per pair of file types) may share the same plans, a plan may be used directly between two runs, and either may be
@@ -226,6 +233,7 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
     borrow.saved.push_back(sv); borrow.own.push_back(ow);
   }
   if (sw->c2l) { if (fg_c2l_borrow_stream(sw->c2l, sw->s_comp, &borrow.c_saved, &borrow.c_own)) return FG_ERR_HIP; borrow.c_on = true; }
+  if (xo) for (fg_plan *p : sw->plans) { int rc = fg_plan_levels_ex_begin(p); if (rc) return rc; }
   const bool in_pinned = is_pinned(host_in);
   bool out_pinned = true;
   for (size_t p = 0; p < sw->plans.size(); p++) out_pinned = out_pinned && is_pinned(host_out[p]);
@@ -263,12 +271,15 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
     }
     double *res = narrow ? sw->d_tmp : (double *)sl.d_fin;         // [plan block][level][cell]
     if (sw->order == 2) {
-      int rc = masked ? fg_c2l_records_levels(sw->c2l, f64, nl, missing, sw->d_rec, sw->d_bits) : fg_c2l_records(sw->c2l, f64, nl, sw->d_rec);
+      // (xo: records always eight levels wide; without missing values `missing` is -1e20 and masks nothing)
+      int rc = (masked || xo) ? fg_c2l_records_levels(sw->c2l, f64, nl, missing, sw->d_rec, sw->d_bits) : fg_c2l_records(sw->c2l, f64, nl, sw->d_rec);
       if (rc) return rc;
     }
     for (size_t p = 0; p < sw->plans.size(); p++) {
       int rc;
-      if (masked)
+      if (xo)       // (queued: the area_missing word is read once, after the last chunk -- reading it here would stall the pipeline)
+        rc = fg_plan_levels_ex_chunk(sw->plans[p], xo, nl, f64, sw->order == 2 ? sw->d_rec : nullptr, masked ? sw->d_bits : nullptr, res + sw->doff[p]);
+      else if (masked)
         rc = (sw->order == 2) ? fg_plan_apply_records_levels(sw->plans[p], nl, sw->d_rec, sw->d_bits, missing, res + sw->doff[p], nullptr)
                               : fg_plan_apply_levels(sw->plans[p], f64, nullptr, nullptr, nullptr, missing, nl, res + sw->doff[p], nullptr);
       else
@@ -305,6 +316,7 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
   }
   // drain in chunk order
   for (long c = (chunk > NSLOT ? chunk - NSLOT : 0); c < chunk; c++) { int rc = slot_retire(sw, sw->slot[c % NSLOT], host_out); if (rc) return rc; }
+  if (xo) for (fg_plan *p : sw->plans) { int rc = fg_plan_levels_ex_end(p); if (rc) return rc; }
   return 0;
 }
 
@@ -320,4 +332,18 @@ extern "C" int fg_sweep_run_levels(fg_sweep *sw, const void *host_in, long nlev,
                                    void *const *host_out)
 {
   return sweep_run(sw, host_in, nlev, scale, offset, missing, host_out, true);
+}
+
+// fg_sweep_run_levels with the options of fg_plan_apply_levels_ex: the option arrays are device-resident and shared by the levels
+// (field_area_ld = 0) and by the plans, so cell_area_out -- an array over ONE plan's destination cells -- needs a sweep of one plan.
+// The missing value is the options': opts->missing with has_missing, else -1e20 (conserve_interp.c:541-542), which also steers
+// the scale / offset conversion as the `missing` argument of fg_sweep_run does.
+extern "C" int fg_sweep_run_levels_ex(fg_sweep *sw, const fg_apply_opts *opts, const void *host_in, long nlev, double scale, double offset,
+                                      void *const *host_out)
+{
+  if (!sw || !opts) return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels_ex: null argument");
+  if (opts->monotonic) return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels_ex: the monotone limiter works on one level per call (fg_plan_apply_ex)");
+  if (opts->cell_area_out && sw->plans.size() != 1)
+    return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels_ex: cell_area_out belongs to one destination grid, the sweep has %d plans", (int)sw->plans.size());
+  return sweep_run(sw, host_in, nlev, scale, offset, opts->has_missing ? opts->missing : -1.e20, host_out, opts->has_missing != 0, opts);
 }

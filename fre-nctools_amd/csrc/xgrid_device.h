@@ -317,6 +317,13 @@ struct FgApplyEx {
 #define FG_XERR_BELOW 4
 void fgd_apply_ex(int order, int ndst, FgCsr csr, const double *f, const double *gx, const double *gy, FgApplyEx o,
                   double *out, double *row_sum, int *err, hipStream_t st, long nx = -1);
+// eight levels per launch with these options (k_apply_ep8x; no limiter): rec, gbits, out, row_sum as fgd_apply_levels8 takes them
+// (gbits may be null: no gradient is masked); fa8 = the per-level field_area interleaved [source cell][8], or null when
+// o.field_area is shared by the levels
+#define FG_LEVELS_EX_CAP 256      // exchange cells staged per chunk, area shared by the levels
+#define FG_LEVELS_EX_CAP_Z 128    // ... with a per-level area: scaled area and target term per (exchange cell, level)
+void fgd_apply_levels8x(int order, int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, FgApplyEx o, const double *fa8,
+                        double *out, double *row_sum, long ld, int nb_valid, int *err, hipStream_t st);
 // monotone limiter (:617-716): per-source-cell neighbourhood bounds, exchange-cell values + their per-cell
 // extremes (atomic min/max: order independent), then the limited values
 void fgd_mono_bounds(const FgTile *tiles_dev, int ntiles, int nsrc, const int *src_idx_f, const double *f, double missing,

@@ -240,6 +240,24 @@ class Sweep:
         ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
         check(lib().fg_sweep_run_levels(self._h, a.ctypes.data_as(C.c_void_p), nlev, float(scale), float(offset), float(missing), ptrs))
 
+    def run_levels_ex(self, host_in, outs, scale=0.0, offset=0.0, has_missing=False, missing=-1.0e20, weight_t=None,
+                      cell_methods_sum=False, field_area_t=None, area_missing=-1.0e20, cell_area_in_t=None, cell_area_out_t=None):
+        """run_levels() for a variable with a weight field, cell_methods = sum, cell_measures or --target_grid
+        (fg_sweep_run_levels_ex): every level is remapped as apply_ex(nz=1) would remap it alone.  The option arrays are device
+        tensors over the source (cell_area_out_t: the destination) cells, shared by the levels and by the plans; cell_area_out_t
+        needs a sweep of one plan.  `missing` counts only with has_missing."""
+        from ._lib import ApplyOpts
+        a = host_in
+        assert a.dtype == self.in_dtype and a.flags.c_contiguous and a.shape[1] == self.ncells_in
+        nlev = a.shape[0]
+        for o, n in zip(outs, self.ndst):
+            assert o.dtype == self.out_dtype and o.flags.c_contiguous and o.shape == (nlev, n)
+        addr = lambda t: t.data_ptr() if t is not None else None
+        opts = ApplyOpts(1 if has_missing else 0, float(missing), addr(weight_t), 1 if cell_methods_sum else 0, addr(field_area_t),
+                         float(area_missing), addr(cell_area_in_t), addr(cell_area_out_t), 0)
+        ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        check(lib().fg_sweep_run_levels_ex(self._h, C.byref(opts), a.ctypes.data_as(C.c_void_p), nlev, float(scale), float(offset), ptrs))
+
     def destroy(self):
         if self._h:
             lib().fg_sweep_destroy(self._h); self._h = None

@@ -302,8 +302,9 @@ int fg_plan_apply_records(fg_plan *plan, int nz, const double *rec, double *out,
  *              fg_plan_apply_ex(has_missing, nz = 1) returns for that level, bit for bit)
  * Bad arguments -- nlev < 1, NULL buffers, an order-2 plan without gradients or mask, a plan that is not finalized -- return
  * FG_ERR_ARG, write nothing and leave the plan usable.
- * Out of scope here, one level per call through fg_plan_apply_ex as before: weight field, cell_measures, cell_methods = sum,
- * --target_grid and the monotone limiter.  integration/ keeps the reference's per-level loop. */
+ * Weight field, cell_measures, cell_methods = sum and --target_grid on many levels: fg_plan_apply_levels_ex below.  Out of scope
+ * here and there, one level per call through fg_plan_apply_ex: the monotone limiter.  integration/ keeps the reference's
+ * per-level loop. */
 int fg_plan_apply_levels(fg_plan *plan, const double *data, const double *grad_x, const double *grad_y,
                          const int *grad_mask, double missing, int nlev, double *out, double *gsum_out);
 /* The same sweep of 1 <= nz <= 8 levels on the records fg_c2l_records_levels writes: rec [ncells_in][3][8] (always eight
@@ -343,6 +344,41 @@ typedef struct fg_apply_opts {
 } fg_apply_opts;
 int fg_plan_apply_ex(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
                      const double *grad_y, const int *grad_mask, int nz, double *out, double *gsum_out);
+/* The level loop of a field that uses these options, many levels per call.  The reference refuses nz > 1 for has_missing,
+ * cell_measures and cell_methods = sum (conserve_interp.c:544-546), so fregrid.c:1045-1083 calls it once per level -- ocean
+ * diagnostics with cell_measures = "area: areacello" / "volume: volcello" or cell_methods = "area: sum" have 50-75 levels,
+ * each with its own land mask.  fg_plan_apply_levels_ex is that loop on the device, eight levels per launch: for
+ * k = 0 .. nlev-1, out level k and gsum_out[k] hold the bits of do_scalar_conserve_interp(nz = 1) -- and of
+ * fg_plan_apply_ex(opts, nz = 1) -- on level k alone with the same options (:561-616 order 1, :743-813 order 2, :815-866).
+ * Per (exchange cell, level), in the reference's order: area *= weight; the data == missing test (has_missing); area /=
+ * cell_area for sum, else with cell_measures the field_area == area_missing check and area *= (field_area / cell_area); the
+ * value times that area.  The --target_grid sum (:842-858) takes every exchange cell of the row, missing or not, with the term
+ * area * field_area / cell_area (left to right), or the plain area without cell_measures; the rescale applies where the
+ * result != missing.  With every option off the result equals fg_plan_apply_levels' bit for bit.
+ *   data, grad_x, grad_y, grad_mask, out, gsum_out: as fg_plan_apply_levels takes them.  opts->has_missing may be 0 or 1; with
+ *     0 grad_mask may be NULL (and is not read).
+ *   field_area_ld: 0 = opts->field_area is [ncells_in], shared by all levels (an area variable without a z axis);
+ *     ncells_in = it is [nlev][ncells_in] (area_has_zaxis, fregrid_util.c:2156-2162, e.g. volcello), and the --target_grid sum
+ *     is per level.  weight, cell_area_in and cell_area_out are shared by the levels, as in the reference.
+ * FG_ERR_ARG, nothing written, plan still usable: opts->monotonic != 0; field_area_ld neither 0 nor ncells_in, or != 0
+ * without field_area; sum or field_area without a cell area on a plan that holds none; NULL buffers; nlev < 1; a plan that is
+ * not finalized.  A valid (cell, level) whose field_area == area_missing: FG_ERR_DATA, "data is not missing but area is
+ * missing", as in fg_plan_apply_ex.
+ * Out of scope, one level per call through fg_plan_apply_ex as before: the monotone limiter on many levels (three kernels and
+ * a multi-rank split of its own).  integration/ keeps the reference's per-level loop (fregrid.c drives it one level per
+ * call).  use_volume: the caller passes cell_area_out = NULL, as for fg_plan_apply_ex. */
+int fg_plan_apply_levels_ex(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
+                            const double *grad_y, const int *grad_mask, int nlev, long field_area_ld, double *out,
+                            double *gsum_out);
+/* The same on the records fg_c2l_records_levels writes (rec [ncells_in][3][8], maskbits [ncells_in]; maskbits may be NULL
+ * without has_missing): order-2 plans, 1 <= nz <= 8, opts->field_area [nz][ncells_in] when field_area_ld = ncells_in.
+ * Bit-identical to fg_plan_apply_levels_ex. */
+int fg_plan_apply_records_levels_ex(fg_plan *plan, const fg_apply_opts *opts, int nz, const double *rec,
+                                    const unsigned char *maskbits, long field_area_ld, double *out, double *gsum_out);
+/* Exchange cells the sweep above stages per chunk, for an area shared by the levels (per_level_area = 0) and for an area per
+ * level (!= 0), whose table of scaled areas and target terms per (exchange cell, level) leaves room for half as many. */
+int fg_plan_levels_ex_capacity(int per_level_area);
+
 /* The monotone sweep split at the reference's mpp_min_double/mpp_max_double (:672-677) so that ranks holding bands of
  * one destination grid can all-reduce the per-source-cell extremes (MIN over f_min, MAX over f_max, ncells_in doubles
  * each, device pointers) between the two calls.  fg_plan_apply_ex(monotonic=1) is begin + end. */
@@ -589,6 +625,14 @@ int  fg_sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, do
                   void *const *host_out);
 int  fg_sweep_run_levels(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
                          void *const *host_out);
+/* fg_sweep_run_levels with the options of fg_plan_apply_levels_ex (fg_apply_opts is declared with fg_plan_apply_ex).  The
+ * option arrays are device-resident and shared by the levels (field_area_ld = 0) and by all plans of the sweep, so
+ * opts->cell_area_out is legal only for a sweep of one plan (else FG_ERR_ARG).  The missing value is the options':
+ * opts->missing with has_missing, else -1e20 (conserve_interp.c:541-542); it also steers the scale / offset conversion.
+ * Out of scope: streaming a per-level area variable (volcello) beside the field -- such a field takes
+ * fg_plan_apply_levels_ex on resident levels. */
+int  fg_sweep_run_levels_ex(fg_sweep *sw, const fg_apply_opts *opts, const void *host_in, long nlev, double scale,
+                            double offset, void *const *host_out);
 void fg_sweep_destroy(fg_sweep *sw);
 void *fg_host_alloc(size_t bytes);      /* page-locked host memory (hipHostMalloc), NULL on failure */
 void fg_host_free(void *p);
