@@ -32,6 +32,7 @@ EXPORTS = [
     "fg_plan_cell_sums_dev", "fg_plan_copy_cell_sums", "fg_plan_accumulate_cell_sums", "fg_plan_accumulate_cell_sums_async", "fg_dev_gather_f64", "fg_dev_scatter_f64", "fg_plan_finalize", "fg_plan_get_xgrid", "fg_plan_get_polygons", "fg_plan_create_polylist", "fg_plan_get_cell_struct",
     "fg_plan_get_cell_area", "fg_plan_set_xgrid", "fg_plan_apply", "fg_plan_apply_interleaved", "fg_plan_apply_records", "fg_plan_apply_levels", "fg_plan_apply_records_levels", "fg_plan_levels_capacity", "fg_plan_apply_levels_ex", "fg_plan_apply_records_levels_ex", "fg_plan_levels_ex_capacity", "fg_plan_apply_ex", "fg_plan_mono_begin",
     "fg_plan_mono_minmax_dev", "fg_plan_mono_copy_minmax", "fg_plan_mono_end",
+    "fg_plan_apply_levels_mono", "fg_plan_mono_levels_begin", "fg_plan_mono_levels_copy_minmax", "fg_plan_mono_levels_end",
     "fg_plan_create_great_circle", "fg_plan_create_great_circle_dev", "fg_latlon2xyz", "create_xgrid_great_circle",
     "create_xgrid_great_circle_", "get_grid_great_circle_area", "get_grid_great_circle_area_", "clip_2dx2d_great_circle",
     "great_circle_area", "fg_gc_clip_batch", "conserve_interp_great_circle", "fg_sincos_batch",
@@ -222,6 +223,14 @@ def lib():
     L.fg_plan_mono_copy_minmax.restype = C.c_int
     L.fg_plan_mono_end.argtypes = [vp, ao, vp, vp, dp]
     L.fg_plan_mono_end.restype = C.c_int
+    L.fg_plan_apply_levels_mono.argtypes = [vp, ao, vp, vp, vp, vp, C.c_int, vp, dp]
+    L.fg_plan_apply_levels_mono.restype = C.c_int
+    L.fg_plan_mono_levels_begin.argtypes = [vp, ao, vp, vp, vp, vp, C.c_int]
+    L.fg_plan_mono_levels_begin.restype = C.c_int
+    L.fg_plan_mono_levels_copy_minmax.argtypes = [vp, C.c_int, vp, vp]
+    L.fg_plan_mono_levels_copy_minmax.restype = C.c_int
+    L.fg_plan_mono_levels_end.argtypes = [vp, ao, vp, vp, vp, vp, vp, dp]
+    L.fg_plan_mono_levels_end.restype = C.c_int
     L.fg_plan_create_great_circle.argtypes = [C.c_int, ip, ip, dpp, dpp, dpp, C.c_int, C.c_int, dp, dp, C.c_int, C.POINTER(vp)]
     L.fg_plan_create_great_circle.restype = C.c_long
     L.fg_plan_create_great_circle_dev.argtypes = [C.c_int, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),

@@ -480,6 +480,40 @@ class XgridPlan:
                                                     _dp(g) if want_gsum else None))
         return g if want_gsum else None
 
+    def apply_levels_mono(self, data_t, out_t, nlev, grad_x_t, grad_y_t, grad_mask_t=None, has_missing=False, missing=-MAXVAL,
+                          weight_t=None, cell_methods_sum=False, field_area_t=None, cell_area_in_t=None, cell_area_out_t=None,
+                          want_gsum=False, minmax_hook=None):
+        """The level loop of the monotone sweep in one call (fg_plan_apply_levels_mono): level k of out [nlev, ndst] is what
+        apply_ex(monotonic=True, nz=1) gives on level k alone with the same options.  data [nlev, F] with the halo, grads
+        [nlev, ncells_in], grad_mask int32 [nlev, ncells_in] or None (no cell masked); weight, field_area and the cell areas are
+        shared by the levels.  With ``minmax_hook`` the sweep runs as fg_plan_mono_levels_begin / ``minmax_hook(plan, nz)`` /
+        fg_plan_mono_levels_end per chunk of eight levels: the hook all-reduces the chunk's extremes (mono_levels_copy_minmax;
+        mpp_min_double / mpp_max_double, :672-677).  Returns the per-level sums (numpy [nlev]) with want_gsum."""
+        o = self._levels_opts(has_missing, missing, weight_t, cell_methods_sum, field_area_t, -MAXVAL, cell_area_in_t, cell_area_out_t,
+                              True)
+        g = np.zeros(nlev, dtype=np.float64)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        L = lib()
+        if minmax_hook is None:
+            check(L.fg_plan_apply_levels_mono(self._h, C.byref(o), ptr(data_t), ptr(grad_x_t), ptr(grad_y_t), ptr(grad_mask_t), nlev,
+                                              ptr(out_t), _dp(g) if want_gsum else None))
+            return g if want_gsum else None
+        if nlev < 1:
+            raise ValueError("nlev must be >= 1")
+        for k0 in range(0, nlev, 8):
+            nz = min(8, nlev - k0)
+            a = [ptr(t[k0:k0 + nz]) if t is not None else ptr(None) for t in (data_t, grad_x_t, grad_y_t, grad_mask_t)]
+            check(L.fg_plan_mono_levels_begin(self._h, C.byref(o), *a, nz))
+            minmax_hook(self, nz)
+            check(L.fg_plan_mono_levels_end(self._h, C.byref(o), *a, ptr(out_t[k0:k0 + nz]), _dp(g[k0:k0 + nz]) if want_gsum else None))
+        return g if want_gsum else None
+
+    def mono_levels_copy_minmax(self, to_plan, fmin_t, fmax_t):
+        """the extremes of the chunk fg_plan_mono_levels_begin opened, out of (to_plan false) or back into the plan: device
+        tensors [nz, ncells_in] each"""
+        check(lib().fg_plan_mono_levels_copy_minmax(self._h, 1 if to_plan else 0, C.c_void_p(fmin_t.data_ptr()),
+                                                     C.c_void_p(fmax_t.data_ptr())))
+
     @staticmethod
     def levels_ex_capacity(per_level_area=False):
         """exchange cells apply_levels_ex stages per chunk (fg_plan_levels_ex_capacity)"""

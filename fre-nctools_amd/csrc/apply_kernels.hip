@@ -1002,6 +1002,38 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8g(int ndst, FgCsr csr, const d
   else out[(size_t)T.d * NB + lev] = r;
 }
 
+// The sum phase of k_apply_ep8x and k_apply_ep8m below: the (row, level) lane's part of the chunk [c0, c0 + n) from the product table
+// (APL: scaled area and target term per level) -- three sums and the flag, four LDS reads of each in flight, adds in CSR order.
+template <bool APL>
+__device__ __forceinline__ void ep8x_row_add(const EpTile &T, int c0, int n, const double *sh_p, const double *sh_a, const double *sh_t,
+                                             const unsigned char *sh_vm, double &acc, double &asum, double &asum_t, unsigned &touched)
+{
+  constexpr int NB = 8;
+  const int lev = T.lev, vsel = lev >> 2, vbit = lev & 3;
+  const int qa = max(T.b, c0) - c0, qb = min(T.e, c0 + n) - c0;
+  auto term = [&](int q, double &p, double &a, double &tt, unsigned &ok) {
+    ok = (sh_vm[q * 2 + vsel] >> vbit) & 1u;
+    p = sh_p[q * NB + lev];
+    if constexpr (APL) { a = sh_a[q * NB + lev]; tt = sh_t[q * NB + lev]; }
+    else { a = ok ? sh_a[q] : 0.0; tt = sh_t[q]; }
+  };
+  int q = qa;
+  for (; q + 4 <= qb; q += 4) {
+    double p[4], a[4], tt[4];
+    unsigned ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) term(q + k, p[k], a[k], tt[k], ok[k]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) { asum_t += tt[k]; acc += p[k]; asum += a[k]; touched |= ok[k]; }
+  }
+  for (; q < qb; q++) {
+    double p, a, tt;
+    unsigned ok;
+    term(q, p, a, tt, ok);
+    asum_t += tt; acc += p; asum += a; touched |= ok;
+  }
+}
+
 // Eight levels with every option of do_scalar_conserve_interp but the monotone limiter (fg_plan_apply_levels_ex,
 // fg_plan_apply_records_levels_ex, fg_sweep_run_levels_ex): the sibling of k_apply_ep8g<MASKED> with k_apply_epx's per-cell
 // arithmetic.  Level k of the output is do_scalar_conserve_interp(nz = 1) on level k alone with the same options (the reference
@@ -1032,7 +1064,7 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8x(int ndst, FgCsr csr, const d
   double *sh_p = sh_raw, *sh_a = sh_raw + CAP * NB, *sh_t = sh_a + CAP * AW;
   const int t = threadIdx.x;
   const EpTile T = ep_tile<ROWS, NB>(csr, ndst, (int)blockIdx.x);
-  const int lev = T.lev, vsel = lev >> 2, vbit = lev & 3;
+  const int lev = T.lev;
   const bool scaled = o.sum || o.field_area;              // (block-uniform, as every test of `o` below)
   double acc = 0.0, asum = 0.0, asum_t = 0.0;
   unsigned touched = 0;
@@ -1120,34 +1152,196 @@ __global__ __launch_bounds__(TPB) void k_apply_ep8x(int ndst, FgCsr csr, const d
       }
     }
     __syncthreads();
-    if (T.lane) {                                          // three sums and the flag: four LDS reads of each in flight, adds in CSR order
-      const int qa = max(T.b, c0) - c0, qb = min(T.e, c0 + n) - c0;
-      auto term = [&](int q, double &p, double &a, double &tt, unsigned &ok) {
-        ok = (sh_vm[q * 2 + vsel] >> vbit) & 1u;
-        p = sh_p[q * NB + lev];
-        if constexpr (APL) { a = sh_a[q * NB + lev]; tt = sh_t[q * NB + lev]; }
-        else { a = ok ? sh_a[q] : 0.0; tt = sh_t[q]; }
-      };
-      int q = qa;
-      for (; q + 4 <= qb; q += 4) {
-        double p[4], a[4], tt[4];
-        unsigned ok[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) term(q + k, p[k], a[k], tt[k], ok[k]);
-#pragma unroll
-        for (int k = 0; k < 4; k++) { asum_t += tt[k]; acc += p[k]; asum += a[k]; touched |= ok[k]; }
-      }
-      for (; q < qb; q++) {
-        double p, a, tt;
-        unsigned ok;
-        term(q, p, a, tt, ok);
-        asum_t += tt; acc += p; asum += a; touched |= ok;
-      }
-    }
+    if (T.lane) ep8x_row_add<APL>(T, c0, n, sh_p, sh_a, sh_t, sh_vm, acc, asum, asum_t, touched);
   }
   if (!T.lane || T.d >= ndst || lev >= nb_valid) return;
   double rs;
   const double r = apply_finish_ex(o, T.d, acc, asum, asum_t, touched != 0, rs);
+  if (row_sum) row_sum[(size_t)lev * out_ld + T.d] = rs;
+  out[(size_t)lev * out_ld + T.d] = r;
+}
+
+// ------------------------------------------------------------------- the monotone limiter, eight levels per launch
+// conserve_order2_monotonic (conserve_interp.c:617-742) on the chunks of fg_plan_apply_levels_mono / fg_plan_mono_levels_*: level k
+// is the one-level chain k_mono_bounds, k_mono_xdata, k_mono_limit, k_apply_epx<2, MONO> on level k alone, bit for bit.  The
+// per-source-cell numbers of a chunk live in b8 [source cell][4][8] = f_bar_max | f_bar_min | f_max | f_min, one 256-byte gather
+// per exchange cell for the eight levels; no per-exchange-cell value is stored: the sweep recomputes f + gx di + gy dj from the
+// operands the extremes kernel used.
+#define MB8 32                                             // doubles per source cell in b8
+// :622-645 per (source cell, level): CB cells per block, a wave reads consecutive cells of ONE level (the nine loads of a
+// neighbourhood are contiguous along i), the records leave through LDS in one coalesced sweep.  Levels >= nb get the initial
+// values in all four rows, so no branch of the limiter is taken for them.
+template <int CB>
+__global__ __launch_bounds__(256) void k_mono_bounds8(const FgTile *tiles, int ntiles, int nsrc, const int *src_idx_f, const double *f,
+                                                       long ld_f, int nb, double missing, double *b8)
+{
+  constexpr int NB = 8;
+  static_assert(256 % CB == 0 && NB % (256 / CB) == 0, "a thread keeps its cell");
+  __shared__ double tile[CB * (MB8 + 1)];
+  const int t = threadIdx.x % CB;
+  const long s0 = (long)blockIdx.x * CB, s = s0 + t;
+  int c = 0, ld = 0;
+  if (s < nsrc) {
+    int m = 0;
+    while (m + 1 < ntiles && s >= tiles[m + 1].cell_off) m++;
+    ld = tiles[m].nx + 2; c = src_idx_f[s];
+  }
+  for (int k = threadIdx.x / CB; k < NB; k += 256 / CB) {
+    double mx = -1.e20, mn = 1.e20;
+    if (k < nb && s < nsrc) {
+      const double *fk = f + (size_t)k * ld_f + c;
+      for (int jj = -1; jj <= 1; jj++)
+        for (int ii = -1; ii <= 1; ii++) {
+          const double v = fk[jj * ld + ii];
+          if (v != missing) { if (v > mx) mx = v; if (v < mn) mn = v; }
+        }
+    }
+    double *r = tile + t * (MB8 + 1) + k;
+    r[0] = mx; r[NB] = mn; r[2 * NB] = -1.e20; r[3 * NB] = 1.e20;
+  }
+  __syncthreads();
+  const long cnt = ((nsrc - s0) < CB ? (nsrc - s0) : CB) * MB8;  // doubles this block writes
+  for (long e = threadIdx.x; e < cnt; e += 256) b8[(size_t)s0 * MB8 + e] = tile[(e / MB8) * (MB8 + 1) + (e % MB8)];
+}
+
+// :647-669: a lane per (exchange cell, level).  The eight lanes of a cell read one CSR record (one request) and one 64-byte
+// segment of each of f, gx, gy; the value is k_mono_xdata's expression on the same operands.  The hardware's FP64 max / min, no
+// value returned.  Missing values and the levels >= nb of a partial chunk issue no atomic.
+__global__ __launch_bounds__(256) void k_mono_extremes8(long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing,
+                                                         int nb, double *b8)
+{
+  constexpr int NB = 8;
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x, q = g / NB;
+  const int k = (int)(g % NB);
+  if (q >= nx || k >= nb) return;
+  const FgCsrEntry2 E = csr.e2[q];
+  const double *pf = rec + (size_t)E.idx_g * (3 * NB) + k;
+  const double v = pf[0];
+  if (v == missing) return;
+  double x = v;
+  if (!(gbits && ((gbits[E.idx_g] >> k) & 1u))) x = v + pf[NB] * E.di + pf[2 * NB] * E.dj;
+  double *b = b8 + (size_t)E.idx_g * MB8 + k;
+  (void)atomicMax(b + 2 * NB, x);
+  (void)atomicMin(b + 3 * NB, x);
+}
+
+// f_max / f_min of nz levels between b8 and the caller's level-major buffers [nz][nsrc] (fg_plan_mono_levels_copy_minmax)
+__global__ __launch_bounds__(256) void k_mono_minmax8(int nsrc, int nz, int to_b8, double *b8, double *f_min, double *f_max)
+{
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (long)nsrc * nz) return;
+  const long s = g % nsrc;
+  const int k = (int)(g / nsrc);
+  constexpr int NB = 8;
+  double *b = b8 + (size_t)s * MB8 + k;
+  if (to_b8) { b[2 * NB] = f_max[g]; b[3 * NB] = f_min[g]; }
+  else { f_max[g] = b[2 * NB]; f_min[g] = b[3 * NB]; }
+}
+
+// The limited sweep: k_apply_ep8x<2, false> whose gather round also takes the source cell's bounds record.  Per (exchange cell,
+// level): the second-order value as in k_mono_extremes8 (same operations on the same operands: same bits), :689-713 with the
+// 1e-10 snap and the fatal checks (an error bit only for a level < nb_valid), then area *= weight, the sum / cell_measures scaling
+// and the product, in k_apply_epx<2, MONO>'s order.  A value equal to `missing` -- the field's, the second-order value's or the
+// limited one's, as the one-level chain tests its stored xdata -- adds +0.0; the branch never counts a cell as touched (:720-739),
+// so a row without area becomes `missing`.  No area_missing check.  The --target_grid term is taken from every exchange cell.
+template <int TPB, int CAP, int ROWS>
+__global__ __launch_bounds__(TPB) void k_apply_ep8m(int ndst, FgCsr csr, const double *rec, const unsigned char *gbits, const double *b8,
+                                                    FgApplyEx o, double *out, double *row_sum, long out_ld, int nb_valid, int *err)
+{
+  constexpr int NB = 8;
+  constexpr int EPP = TPB / 2, PASS = CAP / EPP;          // gather phase: a lane pair per exchange cell, EPP cells per pass
+  static_assert(ROWS * NB <= TPB && CAP % EPP == 0, "a lane per (row, level)");
+  __shared__ __attribute__((aligned(16))) double sh_raw[CAP * (NB + 2)];   // the staged CSR records, then products, areas, target terms
+  __shared__ unsigned char sh_vm[CAP * 2];
+  FgCsrEntry2 *sh_e = reinterpret_cast<FgCsrEntry2 *>(sh_raw);
+  double *sh_p = sh_raw, *sh_a = sh_raw + CAP * NB, *sh_t = sh_a + CAP;
+  const int t = threadIdx.x;
+  const EpTile T = ep_tile<ROWS, NB>(csr, ndst, (int)blockIdx.x);
+  const int lev = T.lev;
+  const bool scaled = o.sum || o.field_area;              // (block-uniform, as every test of `o` below)
+  double acc = 0.0, asum = 0.0, asum_t = 0.0;
+  unsigned touched = 0;
+  for (int c0 = T.q0; c0 < T.q1; c0 += CAP) {              // (block-uniform)
+    const int n = min(CAP, T.q1 - c0);
+    if (c0 > T.q0) __syncthreads();                        // the previous chunk's products have been added
+    ep_stage_loop<TPB>(sh_e, csr.e2 + c0, n);
+    __syncthreads();
+    const int h = (t & 1) * 4;                             // four levels per lane of the pair
+    VecD<4> fv[PASS], gxv[PASS], gyv[PASS], bmx[PASS], bmn[PASS], xmx[PASS], xmn[PASS];
+    FgCsrEntry2 E[PASS];
+    double wgt[PASS], ca[PASS], fa[PASS];
+    unsigned gb[PASS];
+#pragma unroll
+    for (int j = 0; j < PASS; j++) {
+      gb[j] = 0; wgt[j] = 1.0; ca[j] = 1.0; fa[j] = 0.0;
+      if (EPP * j < n) {                                   // (block-uniform)
+        const int i = min(t / 2 + EPP * j, n - 1);
+        E[j] = sh_e[i];
+        const int s = E[j].idx_g;
+        const double *pf = rec + (size_t)s * (3 * NB) + h, *pb = b8 + (size_t)s * MB8 + h;
+        fv[j] = *reinterpret_cast<const VecD<4> *>(pf);
+        gxv[j] = *reinterpret_cast<const VecD<4> *>(pf + NB);
+        gyv[j] = *reinterpret_cast<const VecD<4> *>(pf + 2 * NB);
+        bmx[j] = *reinterpret_cast<const VecD<4> *>(pb);
+        bmn[j] = *reinterpret_cast<const VecD<4> *>(pb + NB);
+        xmx[j] = *reinterpret_cast<const VecD<4> *>(pb + 2 * NB);
+        xmn[j] = *reinterpret_cast<const VecD<4> *>(pb + 3 * NB);
+        if (gbits) gb[j] = gbits[s];
+        if (o.weight) wgt[j] = o.weight[s];
+        if (scaled) ca[j] = o.cell_area[s];
+        if (o.field_area) fa[j] = o.field_area[s];
+      }
+    }
+    __syncthreads();                                       // the records are in registers: the buffer becomes the product table
+#pragma unroll
+    for (int j = 0; j < PASS; j++) {
+      const int i = t / 2 + EPP * j;
+      if (EPP * j < n && i < n) {
+        const double a0 = E[j].area;
+        double as = a0, tt = 0.0;
+        if (o.weight) as *= wgt[j];
+        if (o.cell_area_out) tt = o.field_area ? (a0 * fa[j] / ca[j]) : a0;      // :845-860 (plain exchange-cell area, no weight)
+        if (o.sum) as /= ca[j];
+        else if (o.field_area) as *= (fa[j] / ca[j]);
+        VecD<4> pv;
+        unsigned vm = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const double f_bar = fv[j].v[k];
+          double x = f_bar;
+          bool ok = !(f_bar == o.missing);
+          if (!((gb[j] >> (h + k)) & 1u)) x = f_bar + gxv[j].v[k] * E[j].di + gyv[j].v[k] * E[j].dj;
+          if (ok && !(x == o.missing)) {                   // k_mono_limit passes over a stored value equal to `missing`
+            const double fbmax = bmx[j].v[k], fbmin = bmn[j].v[k], fmax = xmx[j].v[k], fmin = xmn[j].v[k];
+            if (fmax > fbmax) {
+              x = f_bar + ((x - f_bar) / (fmax - f_bar)) * (fbmax - f_bar);
+              if (x > fbmax) {
+                if (x - fbmax < 1.e-10) x = fbmax;
+                if (x > fbmax && h + k < nb_valid) atomicOr(err, FG_XERR_ABOVE);
+              }
+            } else if (fmin < fbmin) {
+              x = f_bar + ((x - f_bar) / (fmin - f_bar)) * (fbmin - f_bar);
+              if (x < fbmin) {
+                if (fbmin - x < 1.e-10) x = fbmin;
+                if (x < fbmin && h + k < nb_valid) atomicOr(err, FG_XERR_BELOW);
+              }
+            }
+          }
+          ok = ok && !(x == o.missing);                    // `if (xdata == missing) continue` of the sweep
+          pv.v[k] = ok ? x * as : 0.0;
+          vm |= (ok ? 1u : 0u) << k;
+        }
+        if (h == 0) { sh_a[i] = as; sh_t[i] = tt; }
+        *reinterpret_cast<VecD<4> *>(sh_p + i * NB + h) = pv;
+        sh_vm[i * 2 + (t & 1)] = (unsigned char)vm;
+      }
+    }
+    __syncthreads();
+    if (T.lane) ep8x_row_add<false>(T, c0, n, sh_p, sh_a, sh_t, sh_vm, acc, asum, asum_t, touched);
+  }
+  if (!T.lane || T.d >= ndst || lev >= nb_valid) return;
+  double rs;
+  const double r = apply_finish_ex(o, T.d, acc, asum, asum_t, false, rs);
   if (row_sum) row_sum[(size_t)lev * out_ld + T.d] = rs;
   out[(size_t)lev * out_ld + T.d] = r;
 }
@@ -1541,6 +1735,30 @@ void fgd_mono_limit(long nx, FgCsr csr, const double *f, double missing, const d
                     const double *fmax, const double *fmin, double *xdata, int *err, hipStream_t st)
 {
   if (nx > 0) k_mono_limit<<<nblk(nx, 256), 256, 0, st>>>(nx, csr, f, missing, fbmax, fbmin, fmax, fmin, xdata, err);
+}
+void fgd_mono_bounds8(const FgTile *tiles_dev, int ntiles, int nsrc, const int *src_idx_f, const double *f, long ld_f, int nb,
+                      double missing, double *b8, hipStream_t st)
+{
+  if (nsrc > 0) k_mono_bounds8<64><<<nblk(nsrc, 64), 256, 0, st>>>(tiles_dev, ntiles, nsrc, src_idx_f, f, ld_f, nb, missing, b8);
+}
+void fgd_mono_extremes8(long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing, int nb, double *b8,
+                        hipStream_t st)
+{
+  if (nx > 0) k_mono_extremes8<<<nblk(nx * 8, 256), 256, 0, st>>>(nx, csr, rec, gbits, missing, nb, b8);
+}
+void fgd_mono_minmax8(int nsrc, int nz, int to_b8, double *b8, double *f_min, double *f_max, hipStream_t st)
+{
+  if (nsrc > 0 && nz > 0) k_mono_minmax8<<<nblk((long)nsrc * nz, 256), 256, 0, st>>>(nsrc, nz, to_b8, b8, f_min, f_max);
+}
+// rows per tile by the mean row length, so that a tile's exchange cells about fill one chunk of FG_LEVELS_MONO_CAP
+void fgd_apply_levels8m(int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, const double *b8, FgApplyEx o,
+                        double *out, double *row_sum, long ld, int nb_valid, int *err, hipStream_t st)
+{
+  if (ndst <= 0) return;
+  by_row_length<16, 8, 2, 1>(nx / ndst, [&](auto R) {
+    k_apply_ep8m<256, FG_LEVELS_MONO_CAP, decltype(R)::value><<<nblk(ndst, decltype(R)::value), 256, 0, st>>>(
+        ndst, csr, rec, gbits, b8, o, out, row_sum, ld, nb_valid, err);
+  });
 }
 
 void fgd_apply_frac(int ndst, FgCsr csr, const double *data, double *out, hipStream_t st)

@@ -399,6 +399,9 @@ struct fg_plan {
   double *mono_x = nullptr, *mono_b = nullptr;     // mono_b: [4][nsrc] = f_bar_max | f_bar_min | f_max | f_min
   int *xerr = nullptr;
   bool mono_open = false;
+  // the limiter on eight levels (fg_plan_mono_levels_*): one chunk's bounds [nsrc][4][8] = f_bar_max | f_bar_min | f_max | f_min
+  double *mono8_b = nullptr;
+  int mono8_nz = 0;              // levels of the open chunk, 0 = none open
   unsigned *ll_err = nullptr;    // error word of a latlon2xyz conversion queued ahead of the search (great-circle plans from lon / lat)
 
   // Stream-ordered plans (fg_set_search_async).
@@ -2570,6 +2573,137 @@ int fg_plan_levels_ex_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const d
              : levels_ex_run(pl, o, data, nullptr, nullptr, nullptr, nz, 0, out, nullptr, true);
 }
 int fg_plan_levels_ex_end(fg_plan *pl) { return ex_error_word(pl); }
+
+// ------------------------------------------------------------------- the level loop of the monotone sweep, eight levels per launch
+// fg_plan_apply_ex(monotonic = 1, nz = 1) per level is what the reference does (conserve_interp.c:648-651 index level 0 only,
+// fregrid.c:1045-1083 loop): four launches, an xdata array written and read again and three reads of every CSR record per level.
+// Here a chunk of eight levels takes k_merge3, k_gmask_bits and three launches -- k_mono_bounds8, k_mono_extremes8, k_apply_ep8m --
+// split between the second and the third at the reference's mpp_min_double / mpp_max_double (:672-677).
+static int mono_levels_check(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *gx, const double *gy, const char *who)
+{
+  if (!pl || !o || !data || !gx || !gy) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "%s: the plan is not finalized (fg_plan_finalize)", who);
+  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)", who);
+  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
+    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
+  return 0;
+}
+
+// scratch of one chunk, whatever the number of levels of the call
+static int mono_levels_scratch(fg_plan *pl, bool want_rs)
+{
+  int rc = levels_ex_scratch(pl, want_rs, true, false);
+  if (rc) return rc;
+  if (!pl->mono8_b) {
+    pl->mono8_b = pl->alloc<double>((size_t)(pl->nsrc > 0 ? pl->nsrc : 1) * 32);
+    if (!pl->mono8_b) return fg_fail(FG_ERR_HIP, "out of device memory");
+  }
+  return 0;
+}
+
+// records and mask bits of a chunk of nz levels
+static void mono_levels_stage(fg_plan *pl, const double *data, const double *gx, const double *gy, const int *gm, int nz, hipStream_t st)
+{
+  fgd_merge3(8, pl->nsrc, pl->src_idx_f, data, pl->f_stride, gx, gy, pl->nsrc, nz, pl->il_m, st);
+  if (gm) fgd_gmask_bits(pl->nsrc, gm, pl->nsrc, nz, pl->lv_bits, st);
+}
+// :622-669 of the chunk
+static void mono_levels_first(fg_plan *pl, double miss, const double *data, const double *gx, const double *gy, const int *gm, int nz,
+                              hipStream_t st)
+{
+  mono_levels_stage(pl, data, gx, gy, gm, nz, st);
+  fgd_mono_bounds8(pl->tiles_dev, pl->ntiles, pl->nsrc, pl->src_idx_f, data, pl->f_stride, nz, miss, pl->mono8_b, st);
+  fgd_mono_extremes8(pl->nx, pl->csr, pl->il_m, gm ? pl->lv_bits : nullptr, miss, nz, pl->mono8_b, st);
+}
+// :679-866 of the chunk, on the records and bits staged for it
+static void mono_levels_second(fg_plan *pl, const FgApplyEx &x, bool masks, int nz, double *out, bool want_rs, hipStream_t st)
+{
+  fgd_apply_levels8m(pl->ndst, pl->nx, pl->csr, pl->il_m, masks ? pl->lv_bits : nullptr, pl->mono8_b, x, out, want_rs ? pl->il_rs : nullptr,
+                     (long)pl->ndst, nz, pl->xerr, st);
+}
+
+extern "C" int fg_plan_apply_levels_mono(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
+                                         const int *grad_mask, int nlev, double *out, double *gsum_out)
+{
+  const char *who = "fg_plan_apply_levels_mono";
+  int rc = mono_levels_check(pl, o, data, grad_x, grad_y, who);
+  if (rc) return rc;
+  if (!out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (nlev < 1) return fg_fail(FG_ERR_ARG, "%s: nlev must be >= 1", who);
+  FGCHK(hipSetDevice(pl->device));
+  if ((rc = mono_levels_scratch(pl, gsum_out != nullptr))) return rc;
+  bool per_level;
+  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
+  hipStream_t st = pl->stream;
+  pl->mono8_nz = 0;                                        // an open chunk of the split entries is overwritten
+  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
+  apply_span_begin(pl, st);
+  int nred = 0;
+  for (int k0 = 0; k0 < nlev; k0 += 8) {
+    const int nbv = (nlev - k0 < 8) ? nlev - k0 : 8;
+    const int *gm = grad_mask ? grad_mask + (size_t)k0 * pl->nsrc : nullptr;
+    mono_levels_first(pl, x.missing, data + (size_t)k0 * pl->f_stride, grad_x + (size_t)k0 * pl->nsrc, grad_y + (size_t)k0 * pl->nsrc, gm,
+                      nbv, st);
+    mono_levels_second(pl, x, gm != nullptr, nbv, out + (size_t)k0 * pl->ndst, gsum_out != nullptr, st);
+    if (gsum_out) { rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
+  }
+  apply_span_end(pl);
+  FGCHK(hipGetLastError());
+  return ex_error_word(pl);                                // once, after the last chunk
+}
+
+extern "C" int fg_plan_mono_levels_begin(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x,
+                                         const double *grad_y, const int *grad_mask, int nz)
+{
+  const char *who = "fg_plan_mono_levels_begin";
+  int rc = mono_levels_check(pl, o, data, grad_x, grad_y, who);
+  if (rc) return rc;
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per begin / end pair", who);
+  FGCHK(hipSetDevice(pl->device));
+  if ((rc = mono_levels_scratch(pl, false))) return rc;
+  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
+  mono_levels_first(pl, o->has_missing ? o->missing : -1.e20, data, grad_x, grad_y, grad_mask, nz, pl->stream);
+  FGCHK(hipGetLastError());
+  pl->mono8_nz = nz;
+  return 0;
+}
+
+extern "C" int fg_plan_mono_levels_copy_minmax(fg_plan *pl, int to_plan, double *f_min, double *f_max)
+{
+  if (!pl || !f_min || !f_max) return fg_fail(FG_ERR_ARG, "fg_plan_mono_levels_copy_minmax: null argument");
+  if (!pl->mono8_nz) return fg_fail(FG_ERR_STATE, "fg_plan_mono_levels_copy_minmax: call fg_plan_mono_levels_begin first");
+  FGCHK(hipSetDevice(pl->device));
+  fgd_mono_minmax8(pl->nsrc, pl->mono8_nz, to_plan ? 1 : 0, pl->mono8_b, f_min, f_max, pl->stream);
+  FGCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(pl->stream));
+  return 0;
+}
+
+// The records and bits are staged again from the caller's arrays: il_m and lv_bits are the scratch of every many-level entry, and
+// the caller may have swept another field on this plan while its ranks exchanged the extremes.
+extern "C" int fg_plan_mono_levels_end(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
+                                       const int *grad_mask, double *out, double *gsum_out)
+{
+  const char *who = "fg_plan_mono_levels_end";
+  int rc = mono_levels_check(pl, o, data, grad_x, grad_y, who);
+  if (rc) return rc;
+  if (!out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!pl->mono8_nz) return fg_fail(FG_ERR_STATE, "%s: call fg_plan_mono_levels_begin first", who);
+  FGCHK(hipSetDevice(pl->device));
+  if ((rc = mono_levels_scratch(pl, gsum_out != nullptr))) return rc;
+  const int nz = pl->mono8_nz;
+  pl->mono8_nz = 0;
+  bool per_level;
+  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
+  hipStream_t st = pl->stream;
+  apply_span_begin(pl, st);
+  mono_levels_stage(pl, data, grad_x, grad_y, grad_mask, nz, st);
+  mono_levels_second(pl, x, grad_mask != nullptr, nz, out, gsum_out != nullptr, st);
+  apply_span_end(pl);
+  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
+  FGCHK(hipGetLastError());
+  return ex_error_word(pl);
+}
 
 // The sweep on fields the caller already keeps interleaved: data_il [F][nb], grad_x_il/grad_y_il [ncells_in][nb],
 // out_il [ndst][nb]; nb in {2, 4, 8}; no missing values.  Skips the two transposes of fg_plan_apply.

@@ -332,6 +332,21 @@ void fgd_mono_xdata(long nx, FgCsr csr, const double *f, const double *gx, const
                     double *xdata, double *fmax, double *fmin, hipStream_t st);
 void fgd_mono_limit(long nx, FgCsr csr, const double *f, double missing, const double *fbmax, const double *fbmin,
                     const double *fmax, const double *fmin, double *xdata, int *err, hipStream_t st);
+// the limiter on eight levels per launch (fg_plan_apply_levels_mono, fg_plan_mono_levels_*).  b8 holds, per source cell,
+// [4][8] doubles = f_bar_max | f_bar_min | f_max | f_min of the eight levels: one 256-byte gather per exchange cell.  rec and
+// gbits are k_merge3's records and k_gmask_bits' bytes of the chunk (gbits may be null: no gradient is masked).
+//   fgd_mono_bounds8    :622-645 on nb levels of the level-major halo'd field f (row stride ld_f); f_max / f_min start at -+1e20
+//   fgd_mono_extremes8  :647-669, atomic max / min of the second-order values into b8; no value is stored
+//   fgd_mono_minmax8    f_max / f_min of nz levels between b8 and level-major [nz][nsrc] buffers (to_b8: into b8)
+//   fgd_apply_levels8m  :679-716 on recomputed values, then the sweep with the options of FgApplyEx (k_apply_ep8m)
+#define FG_LEVELS_MONO_CAP 128    // exchange cells staged per chunk of the limited sweep
+void fgd_mono_bounds8(const FgTile *tiles_dev, int ntiles, int nsrc, const int *src_idx_f, const double *f, long ld_f, int nb,
+                      double missing, double *b8, hipStream_t st);
+void fgd_mono_extremes8(long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing, int nb, double *b8,
+                        hipStream_t st);
+void fgd_mono_minmax8(int nsrc, int nz, int to_b8, double *b8, double *f_min, double *f_max, hipStream_t st);
+void fgd_apply_levels8m(int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, const double *b8, FgApplyEx o,
+                        double *out, double *row_sum, long ld, int nb_valid, int *err, hipStream_t st);
 
 // ---- 1-D x 2-D variants (box_kernels.hip): the regular grid given by its 1-D bounds (device pointers)
 struct FgBox { const double *lon, *lat; int nx, ny; };

@@ -302,9 +302,9 @@ int fg_plan_apply_records(fg_plan *plan, int nz, const double *rec, double *out,
  *              fg_plan_apply_ex(has_missing, nz = 1) returns for that level, bit for bit)
  * Bad arguments -- nlev < 1, NULL buffers, an order-2 plan without gradients or mask, a plan that is not finalized -- return
  * FG_ERR_ARG, write nothing and leave the plan usable.
- * Weight field, cell_measures, cell_methods = sum and --target_grid on many levels: fg_plan_apply_levels_ex below.  Out of scope
- * here and there, one level per call through fg_plan_apply_ex: the monotone limiter.  integration/ keeps the reference's
- * per-level loop. */
+ * Weight field, cell_measures, cell_methods = sum and --target_grid on many levels: fg_plan_apply_levels_ex below.  The
+ * monotone limiter on many levels: fg_plan_apply_levels_mono and fg_plan_mono_levels_* further below.  integration/ keeps the
+ * reference's per-level loop. */
 int fg_plan_apply_levels(fg_plan *plan, const double *data, const double *grad_x, const double *grad_y,
                          const int *grad_mask, double missing, int nlev, double *out, double *gsum_out);
 /* The same sweep of 1 <= nz <= 8 levels on the records fg_c2l_records_levels writes: rec [ncells_in][3][8] (always eight
@@ -364,9 +364,9 @@ int fg_plan_apply_ex(fg_plan *plan, const fg_apply_opts *opts, const double *dat
  * without field_area; sum or field_area without a cell area on a plan that holds none; NULL buffers; nlev < 1; a plan that is
  * not finalized.  A valid (cell, level) whose field_area == area_missing: FG_ERR_DATA, "data is not missing but area is
  * missing", as in fg_plan_apply_ex.
- * Out of scope, one level per call through fg_plan_apply_ex as before: the monotone limiter on many levels (three kernels and
- * a multi-rank split of its own).  integration/ keeps the reference's per-level loop (fregrid.c drives it one level per
- * call).  use_volume: the caller passes cell_area_out = NULL, as for fg_plan_apply_ex. */
+ * The monotone limiter on many levels has entries of its own, three kernels and a multi-rank split: fg_plan_apply_levels_mono
+ * and fg_plan_mono_levels_* below; this entry goes on refusing opts->monotonic.  integration/ keeps the reference's per-level
+ * loop (fregrid.c drives it one level per call).  use_volume: the caller passes cell_area_out = NULL, as for fg_plan_apply_ex. */
 int fg_plan_apply_levels_ex(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
                             const double *grad_y, const int *grad_mask, int nlev, long field_area_ld, double *out,
                             double *gsum_out);
@@ -389,6 +389,47 @@ int fg_plan_mono_minmax_dev(fg_plan *plan, double **f_min, double **f_max);
  * collective library wants its own buffers (torch.distributed); synchronises the plan's stream */
 int fg_plan_mono_copy_minmax(fg_plan *plan, int to_plan, double *f_min, double *f_max);
 int fg_plan_mono_end(fg_plan *plan, const fg_apply_opts *opts, const double *data, double *out, double *gsum_out);
+
+/* The level loop of the monotone sweep (conserve_order2_monotonic / --monotonic), eight levels per launch.  The reference
+ * limits one level per call (conserve_interp.c:648-651 index level 0 only; fregrid.c:1045-1083 loops), and so does
+ * fg_plan_apply_ex(monotonic = 1).  fg_plan_apply_levels_mono is that loop on the device: for k = 0 .. nlev-1, out level k and
+ * gsum_out[k] hold the bits of do_scalar_conserve_interp(nz = 1) with MONOTONIC set (:617-742, :815-866) -- and of
+ * fg_plan_apply_ex(opts->monotonic = 1, nz = 1) -- on level k alone.  Per chunk of eight levels three kernels run beside the
+ * transposition of the inputs: the bounds of every source cell's 3 x 3 neighbourhood (:622-645), the extremes of its exchange
+ * cells' second-order values (:647-669, atomic max / min, order independent), and the sweep, which recomputes those values,
+ * limits them (:679-716) and sums them with the options below; no per-exchange-cell array is stored.
+ *   data       [nlev][F] with the one-cell halo; grad_x / grad_y [nlev][ncells_in] (device pointers, as fg_plan_apply_levels)
+ *   grad_mask  int [nlev][ncells_in], or NULL = no cell is masked (as fg_plan_mono_begin reads NULL); read whether or not the
+ *              field has missing values (:656)
+ *   out        [nlev][ndst] (device); gsum_out: host double[nlev] or NULL, the sum of :815-819 per level
+ *   opts       weight, cell_methods_sum, field_area [ncells_in] shared by the levels, cell_area_in and cell_area_out as in
+ *              fg_plan_mono_end (:731-737, :841-865); has_missing / missing as there, without has_missing the marker is -1e20
+ *              (:541).  The branch never sets out_miss: a destination cell without area becomes `missing`, never 0.0; it has
+ *              no area_missing check.  opts->monotonic is not read: these entries are the monotone ones.  A field_area with
+ *              a level axis is not taken (there is no field_area_ld argument here).
+ * FG_ERR_ARG, nothing written, plan still usable: a first-order plan; a plan that is not finalized; NULL opts, data, out or
+ * gradients; nlev < 1 (nz outside 1 .. 8 for the split); sum or field_area without a cell area on a plan that holds none.
+ * FG_ERR_DATA: the limiter's fatal checks (:697, :709) on any level, with the reference's message (" xdata is greater than
+ * f_bar_max " / " xdata is less than f_bar_min "), as fg_plan_apply_ex reports them; out is unspecified then, the plan stays
+ * usable.  The error word is read once, after the last chunk.  Device scratch is sized for one chunk whatever nlev is.
+ *
+ * The split at mpp_min_double / mpp_max_double (:672-677) for ranks that hold bands of one destination grid, 1 <= nz <= 8
+ * levels per begin / end pair: fg_plan_mono_levels_begin queues the bounds and the extremes of the chunk;
+ * fg_plan_mono_levels_copy_minmax moves the extremes of the open chunk out of (to_plan = 0) or back into (to_plan = 1) the
+ * plan -- f_min and f_max are device buffers, level-major [nz][ncells_in] each, so a rank all-reduces (MIN, MAX) one buffer per
+ * chunk instead of one per level -- and synchronises the plan's stream like fg_plan_mono_copy_minmax; fg_plan_mono_levels_end
+ * takes the same field arguments again (the caller keeps them unchanged between the two calls), limits and sweeps.
+ * fg_plan_apply_levels_mono is begin + end per chunk of eight.  copy_minmax or end without an open begin: FG_ERR_STATE.
+ * Out of scope: a records entry and the streamed sweep (fg_sweep_*) for the limiter -- both need the halo'd field beside the
+ * records fg_c2l_records_levels writes, a change to the gradient object; a per-level field_area; integration/, which
+ * fregrid.c drives one level per call. */
+int fg_plan_apply_levels_mono(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
+                              const double *grad_y, const int *grad_mask, int nlev, double *out, double *gsum_out);
+int fg_plan_mono_levels_begin(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
+                              const double *grad_y, const int *grad_mask, int nz);
+int fg_plan_mono_levels_copy_minmax(fg_plan *plan, int to_plan, double *f_min, double *f_max);
+int fg_plan_mono_levels_end(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
+                            const double *grad_y, const int *grad_mask, double *out, double *gsum_out);
 
 /* HIP stream the plan launches on (hipStream_t as void*), for event timing. */
 void *fg_plan_stream(fg_plan *plan);
