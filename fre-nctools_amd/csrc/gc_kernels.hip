@@ -36,6 +36,10 @@
 // result lies on a different edge of one of the two), so GC_PCAP 16 holds it.  Anything beyond a capacity is error -9.
 #define GC_NGON 8
 #define GC_NCAP_NGON 18     // list 1 of the n-gon clip: 8 corners + 8 intersections + slack
+// insertIntersect (mosaic_util.c:1352-1360) looks for the next node that is not an intersection by walking a circular list; when
+// every node is one the reference never returns.  The clips here stop after a full turn and report this code of their own (not
+// one of the reference's fatals; oracle/gc_oracle.c returns the same).
+#define GC_ENDLESS (-11)
 
 struct GcNode { double x, y, z, u; int intersect, inbound, inside, pad; };
 struct GcInter { double x, y, z, u, u_clip; int subj_index, clip_index, inbound, pad; };
@@ -237,7 +241,7 @@ __device__ int gc_insert_intersect(L &l, double x, double y, double z, double u1
   if (u2 != 0 && u2 != 1) {
     if (inbound == 1) {
       int k2 = (k1 + 1 < l.n) ? k1 + 1 : 0, guard = 0;
-      while (l.v[k2].intersect) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 2 * L::cap) return -7; }
+      while (l.v[k2].intersect) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 2 * L::cap) return GC_ENDLESS; }
       l.v[k2].inside = 0;
     } else if (inbound == 2)
       l.v[k1].inside = 0;
@@ -507,7 +511,7 @@ __device__ int gcf_insert(GcTables &T, int L, GcPacked &l, const double *I, doub
   if (u2 != 0 && u2 != 1) {
     if (inbound == 1) {
       int k2 = (k1 + 1 < l.n) ? k1 + 1 : 0, guard = 0;
-      while (GCN_INTER(gcp_get(l, k2))) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 32) return -7; }
+      while (GCN_INTER(gcp_get(l, k2))) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 32) return GC_ENDLESS; }
       gcp_set(l, k2, gcp_get(l, k2) & ~(1u << 6));
     } else if (inbound == 2)
       gcp_set(l, k1, gcp_get(l, k1) & ~(1u << 6));
@@ -823,7 +827,7 @@ __device__ __forceinline__ bool d_gc_cell_record(const FgTileXyz *tiles, int nti
   for (int k = 0; k < 4; k++) { v[k * 3] = T.x[idx[k]]; v[k * 3 + 1] = T.y[idx[k]]; v[k * 3 + 2] = T.z[idx[k]]; }
   double *o = c.verts + (size_t)s * 16;
   for (int k = 0; k < 12; k++) o[k] = v[k];
-  const GcCap k = d_gc_cap(4, v);
+  GcCap k = d_gc_cap(4, v);
   const double hpi = 0.5 * GC_PI;
   const double lat_min = k.nocap ? -hpi : fmax(-hpi, k.latc - k.r), lat_max = k.nocap ? hpi : fmin(hpi, k.latc + k.r);
   *lat_lo = lat_min; *lat_hi = lat_max;
@@ -832,8 +836,17 @@ __device__ __forceinline__ bool d_gc_cell_record(const FgTileXyz *tiles, int nti
     const double bmax = d_ord_val(cull[0]), bmin = d_ord_val(~cull[1]);
     if (lat_max <= bmin || lat_min >= bmax) { c.nv[s] = 0; c.area[s] = 0; return false; }
   }
-  c.area[s] = d_gc_dedup_area<4>(4, v);
+  const double area = d_gc_dedup_area<4>(4, v);
+  c.area[s] = area;
   c.nv[s] = 4;
+  if (area <= 0 && !k.nocap) {
+    // A cell the reference calls "not convex" ends its process with every cell that passes the range test (create_xgrid.c:1508-1528,
+    // 0.05 on x, y, z: up to ~5 degrees away), overlap or not: it gets no cap, so every cell is its candidate and gc_prefilter's
+    // range test decides as the reference's does.
+    k.nocap = true; k.latc = 0.0;
+    *lat_lo = -hpi; *lat_hi = hpi;
+    c.lat_min[s] = -hpi; c.lat_max[s] = hpi;
+  }
   d_gc_cap_store(4, v, k, o + 12, c, s);
   return true;
 }
@@ -1148,7 +1161,7 @@ __device__ __forceinline__ int gcw_insert(GcL64 &l, int vtx, double u_cur, int i
   if (k1 < 0) return -7;
   if (inbound == 1) {
     int k2 = (k1 + 1 < l.n) ? k1 + 1 : 0, guard = 0;
-    while ((l.inter >> k2) & 1u) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 32) return -7; }
+    while ((l.inter >> k2) & 1u) { k2 = (k2 + 1 < l.n) ? k2 + 1 : 0; if (++guard > 32) return GC_ENDLESS; }
     l.inside &= ~(1u << k2);
   } else if (inbound == 2)
     l.inside &= ~(1u << k1);
@@ -1512,11 +1525,12 @@ __global__ __launch_bounds__(256) void k_gc_poly_records(FgGcPolyList P, FgCells
     v[k * 3] = in ? P.x[(size_t)s * GC_NGON + k] : 0.0; v[k * 3 + 1] = in ? P.y[(size_t)s * GC_NGON + k] : 0.0; v[k * 3 + 2] = in ? P.z[(size_t)s * GC_NGON + k] : 0.0;
   }
   for (int k = 0; k < GC_NGON * 3; k++) o[k] = v[k];
-  const GcCap k = d_gc_cap(n, v);
+  GcCap k = d_gc_cap(n, v);
   const double hpi = 0.5 * GC_PI;
-  S.lat_min[s] = k.nocap ? -hpi : fmax(-hpi, k.latc - k.r); S.lat_max[s] = k.nocap ? hpi : fmin(hpi, k.latc + k.r);
   o[28] = d_gc_dedup_area<GC_NGON>(n, v);                      // gridArea of the "not convex" check
   o[29] = 0; o[30] = 0; o[31] = 0;
+  if (o[28] <= 0) { k.nocap = true; k.latc = 0.0; }            // "not convex": every cell a candidate, as for cells (d_gc_cell_record)
+  S.lat_min[s] = k.nocap ? -hpi : fmax(-hpi, k.latc - k.r); S.lat_max[s] = k.nocap ? hpi : fmin(hpi, k.latc + k.r);
   S.nv[s] = n; S.area[s] = P.area[s];
   d_gc_cap_store(n, v, k, o + 24, S, s);
 }

@@ -604,7 +604,13 @@ static const char *gc_clip_error(int code)
     case 6: return "After clipping, nintersect should be 0";
     case 7: return "inserAfter: point (x,y,z) is not found in the list";
     case 8: return "Error from create_xgrid.c: temp is not in list1";
-    default: return "clip_2dx2d_great_circle: more intersections than two convex quadrilaterals can have (list capacity)";
+    // the device's own (GC_ENDLESS, gc_kernels.hip): the reference does not end on such a pair and has no message for it
+    case 11: return "clip_2dx2d_great_circle: insertIntersect finds no node that is not an intersection (the reference's loop over "
+                    "the list, mosaic_util.c:1352, does not end on this pair of cells)";
+    // 9, the device's own as well: its node lists hold what two convex polygons can produce (gc_kernels.hip: GC_NCAP, GC_ICAP,
+    // GC_PCAP), the reference's pool holds more (MAXNODELIST, mosaic_util.c:1046)
+    default: return "clip_2dx2d_great_circle: more intersections than two convex polygons can have (the list capacity of the device "
+                    "clip, not a check of the reference)";
   }
 }
 

@@ -55,7 +55,13 @@ extern "C" {
 #define FG_ERR_PARALLEL   (-4)   /* clip hit parallel edges, |determ| < 1e-30 (create_xgrid.c:1314) */
 #define FG_ERR_CAPACITY   (-5)   /* caller's output arrays too small (reference: MAXXGRID fatal, :1087) */
 #define FG_ERR_STATE      (-6)   /* call made in the wrong plan state                          */
-#define FG_ERR_GEOM       (-8)   /* the great-circle clip hit one of the reference's fatal geometry checks (create_xgrid.c:1575-1834) */
+/* FG_ERR_GEOM: the great-circle clip hit one of the reference's fatal geometry checks (create_xgrid.c:1575-1834: "grid box 1 / 2 is
+ * not convex", the six fatals of the clip), or a pair the device clip cannot finish (its list capacity; a pair on which the
+ * reference's insertIntersect does not end).  fg_last_error() holds the reference's text, or one that names the limit as the
+ * device's.  Returned by every great-circle search: fg_plan_create_great_circle, _dev, _lonlat, _lonlat_dev,
+ * fg_plan_create_polylist_gc, _dev, and fg_coupler_run of a handle made by fg_coupler_create_gc, which passes the search's code and
+ * text through (and uses the code for its own two checks of the polygons).  DESIGN.md section 3.1b has the table. */
+#define FG_ERR_GEOM       (-8)
 #define FG_ERR_IO         (-9)   /* file I/O (fg_nc_*, fg_remap_*)                            */
 #define FG_ERR_NOTFOUND   (-10)  /* attribute / variable not present                          */
 #define FG_ERR_BILIN_NOTFOUND (-11) /* bilinear search: points without a lower-left corner after 10 sweeps (fg_bilin_create) */

@@ -19,6 +19,8 @@
  *  -1/-2 grid box 1/2 not convex, -3 firstIntersect not in grid1List, -4 next intersection not found,
  *  -5 did not return to the first intersection, -6 nintersect > 0 after clipping, -7 insertIntersect anchor
  *  missing, -8 setInbound anchor missing, -9 list capacity.
+ * Not a fatal of the reference: -11, every node of the list that insertIntersect walks (mosaic_util.c:1352-1360) is an intersection.
+ * The reference's while loop never ends there; this file and the device stop after a full turn.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -232,7 +234,7 @@ static int insert_intersect(GcList *l, double x, double y, double z, double u1, 
   if (u2 != 0 && u2 != 1) {
     if (inbound == 1) {                       /* goes outside: the next non-intersection vertex is outside */
       int k2 = (k1 + 1 < l->n) ? k1 + 1 : 0, guard = 0;
-      while (l->v[k2].intersect) { k2 = (k2 + 1 < l->n) ? k2 + 1 : 0; if (++guard > 2 * GC_CAP) return -7; }
+      while (l->v[k2].intersect) { k2 = (k2 + 1 < l->n) ? k2 + 1 : 0; if (++guard > 2 * GC_CAP) return -11; }
       l->v[k2].inside = 0;
     } else if (inbound == 2)
       l->v[k1].inside = 0;

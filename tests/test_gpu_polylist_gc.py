@@ -42,7 +42,8 @@ def _own_c4(fg):
 
 def _crafted(fg):
     """the crafted batch without the kinds on which the reference's clip ends the process (the plain oracle, pinned to the compiled
-    reference, returns its negative code there): (dst, kinds kept, dropped, n, xyz, area_ref, _cr reference)"""
+    reference, returns its negative code there): (dst, kinds kept, dropped, n, xyz, area_ref, _cr reference).  What the device
+    says about polygons of that kind is tests/test_gpu_gc_fatal.py's subject (inputs: tests/gc_fatal_cases.py)."""
     def make():
         dst, kinds, n, xyz = pc.crafted(fg)
         plain = pc.prims_oracle(False)
