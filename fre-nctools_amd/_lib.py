@@ -33,6 +33,8 @@ EXPORTS = [
     "fg_plan_get_cell_area", "fg_plan_set_xgrid", "fg_plan_apply", "fg_plan_apply_interleaved", "fg_plan_apply_records", "fg_plan_apply_levels", "fg_plan_apply_records_levels", "fg_plan_levels_capacity", "fg_plan_apply_levels_ex", "fg_plan_apply_records_levels_ex", "fg_plan_levels_ex_capacity", "fg_plan_apply_ex", "fg_plan_mono_begin",
     "fg_plan_mono_minmax_dev", "fg_plan_mono_copy_minmax", "fg_plan_mono_end",
     "fg_plan_apply_levels_mono", "fg_plan_mono_levels_begin", "fg_plan_mono_levels_copy_minmax", "fg_plan_mono_levels_end",
+    "fg_plan_apply_records_levels_mono", "fg_plan_mono_records_reset", "fg_plan_mono_records_begin", "fg_plan_mono_records_copy_minmax",
+    "fg_plan_mono_records_end", "fg_c2l_records_levels_mono", "fg_sweep_run_levels_mono",
     "fg_plan_create_great_circle", "fg_plan_create_great_circle_dev", "fg_latlon2xyz", "create_xgrid_great_circle",
     "create_xgrid_great_circle_", "get_grid_great_circle_area", "get_grid_great_circle_area_", "clip_2dx2d_great_circle",
     "great_circle_area", "fg_gc_clip_batch", "conserve_interp_great_circle", "fg_sincos_batch",
@@ -231,6 +233,16 @@ def lib():
     L.fg_plan_mono_levels_copy_minmax.restype = C.c_int
     L.fg_plan_mono_levels_end.argtypes = [vp, ao, vp, vp, vp, vp, vp, dp]
     L.fg_plan_mono_levels_end.restype = C.c_int
+    L.fg_plan_apply_records_levels_mono.argtypes = [vp, ao, C.c_int, vp, vp, vp, vp, dp]
+    L.fg_plan_apply_records_levels_mono.restype = C.c_int
+    L.fg_plan_mono_records_reset.argtypes = [vp, vp]
+    L.fg_plan_mono_records_reset.restype = C.c_int
+    L.fg_plan_mono_records_begin.argtypes = [vp, ao, C.c_int, vp, vp, vp]
+    L.fg_plan_mono_records_begin.restype = C.c_int
+    L.fg_plan_mono_records_copy_minmax.argtypes = [vp, C.c_int, vp, vp]
+    L.fg_plan_mono_records_copy_minmax.restype = C.c_int
+    L.fg_plan_mono_records_end.argtypes = [vp, ao, vp, vp, vp, dp]
+    L.fg_plan_mono_records_end.restype = C.c_int
     L.fg_plan_create_great_circle.argtypes = [C.c_int, ip, ip, dpp, dpp, dpp, C.c_int, C.c_int, dp, dp, C.c_int, C.POINTER(vp)]
     L.fg_plan_create_great_circle.restype = C.c_long
     L.fg_plan_create_great_circle_dev.argtypes = [C.c_int, ip, ip, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
@@ -312,6 +324,7 @@ def lib():
     L.fg_sweep_run.argtypes = [vp, vp, C.c_long, C.c_double, C.c_double, C.c_double, C.POINTER(vp)]; L.fg_sweep_run.restype = C.c_int
     L.fg_sweep_run_levels.argtypes = [vp, vp, C.c_long, C.c_double, C.c_double, C.c_double, C.POINTER(vp)]; L.fg_sweep_run_levels.restype = C.c_int
     L.fg_sweep_run_levels_ex.argtypes = [vp, C.POINTER(ApplyOpts), vp, C.c_long, C.c_double, C.c_double, C.POINTER(vp)]; L.fg_sweep_run_levels_ex.restype = C.c_int
+    L.fg_sweep_run_levels_mono.argtypes = [vp, C.POINTER(ApplyOpts), vp, C.c_long, C.c_double, C.c_double, C.POINTER(vp)]; L.fg_sweep_run_levels_mono.restype = C.c_int
     L.fg_sweep_destroy.argtypes = [vp]; L.fg_sweep_destroy.restype = None
     L.fg_host_alloc.argtypes = [C.c_size_t]; L.fg_host_alloc.restype = vp
     L.fg_host_free.argtypes = [vp]; L.fg_host_free.restype = None
@@ -374,6 +387,8 @@ def lib():
     L.fg_c2l_records.restype = C.c_int
     L.fg_c2l_records_levels.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp]
     L.fg_c2l_records_levels.restype = C.c_int
+    L.fg_c2l_records_levels_mono.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp, vp]
+    L.fg_c2l_records_levels_mono.restype = C.c_int
     L.fg_c2l_grid_info.argtypes = [C.c_int, C.c_int] + [dp] * 15
     L.fg_c2l_grid_info.restype = C.c_int
     L.fg_find_contacts.argtypes = [C.c_int, ip, ip, dpp, dpp, C.c_int] + [ip] * 10

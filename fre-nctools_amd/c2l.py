@@ -135,3 +135,10 @@ class C2lPrep:
         sweeps them."""
         check(lib().fg_c2l_records_levels(self._h, C.c_void_p(src_t.data_ptr()), nz, float(missing), C.c_void_p(rec_t.data_ptr()),
                                           C.c_void_p(maskbits_t.data_ptr())))
+
+    def records_levels_mono(self, src_t, nz, missing, rec_t, maskbits_t, b8_t):
+        """records_levels() plus the monotone limiter's bounds in the same pass (fg_c2l_records_levels_mono): b8 [ncells, 4, 8] =
+        f_bar_max | f_bar_min | f_max | f_min per level, rows 0 / 1 the maximum / minimum over the nine stencil values that differ
+        from `missing`, rows 2 / 3 -1e20 / +1e20; XgridPlan.apply_records_levels_mono sweeps the three buffers."""
+        check(lib().fg_c2l_records_levels_mono(self._h, C.c_void_p(src_t.data_ptr()), nz, float(missing), C.c_void_p(rec_t.data_ptr()),
+                                               C.c_void_p(maskbits_t.data_ptr()), C.c_void_p(b8_t.data_ptr())))

@@ -514,6 +514,56 @@ class XgridPlan:
         check(lib().fg_plan_mono_levels_copy_minmax(self._h, 1 if to_plan else 0, C.c_void_p(fmin_t.data_ptr()),
                                                      C.c_void_p(fmax_t.data_ptr())))
 
+    def apply_records_levels_mono(self, nz, rec_t, maskbits_t, b8_t, out_t, has_missing=False, missing=-MAXVAL, weight_t=None,
+                                  cell_methods_sum=False, field_area_t=None, cell_area_in_t=None, cell_area_out_t=None, want_gsum=False,
+                                  minmax_hook=None):
+        """apply_levels_mono for nz <= 8 levels on what C2lPrep.records_levels_mono wrote (fg_plan_apply_records_levels_mono):
+        rec [ncells_in, 3, 8], maskbits uint8 [ncells_in] or None (no cell masked), b8 [ncells_in, 4, 8], which the call consumes
+        (the extremes go into its rows 2 and 3; mono_records_reset puts them back for the next plan over the same source grid).
+        Bit-identical to apply_levels_mono().  With ``minmax_hook`` the sweep runs as mono_records_begin / ``minmax_hook(plan, nz)`` /
+        mono_records_end.  Returns the per-level sums (numpy [nz]) with want_gsum."""
+        o = self._levels_opts(has_missing, missing, weight_t, cell_methods_sum, field_area_t, -MAXVAL, cell_area_in_t, cell_area_out_t,
+                              True)
+        g = np.zeros(max(nz, 0), dtype=np.float64)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        L = lib()
+        if minmax_hook is None:
+            check(L.fg_plan_apply_records_levels_mono(self._h, C.byref(o), nz, ptr(rec_t), ptr(maskbits_t), ptr(b8_t), ptr(out_t),
+                                                      _dp(g) if want_gsum else None))
+        else:
+            check(L.fg_plan_mono_records_begin(self._h, C.byref(o), nz, ptr(rec_t), ptr(maskbits_t), ptr(b8_t)))
+            minmax_hook(self, nz)
+            check(L.fg_plan_mono_records_end(self._h, C.byref(o), ptr(rec_t), ptr(maskbits_t), ptr(out_t), _dp(g) if want_gsum else None))
+        return g if want_gsum else None
+
+    def mono_records_begin(self, nz, rec_t, maskbits_t, b8_t, has_missing=False, missing=-MAXVAL):
+        """first half of apply_records_levels_mono (fg_plan_mono_records_begin): the extremes of the chunk go into b8_t, which
+        stays the open chunk's bounds buffer until mono_records_end"""
+        o = self._levels_opts(has_missing, missing, None, False, None, -MAXVAL, None, None, True)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        check(lib().fg_plan_mono_records_begin(self._h, C.byref(o), nz, ptr(rec_t), ptr(maskbits_t), ptr(b8_t)))
+
+    def mono_records_copy_minmax(self, to_plan, fmin_t, fmax_t):
+        """the extremes of the chunk mono_records_begin opened, out of (to_plan false) or back into its b8: device tensors
+        [nz, ncells_in] each"""
+        check(lib().fg_plan_mono_records_copy_minmax(self._h, 1 if to_plan else 0, C.c_void_p(fmin_t.data_ptr()),
+                                                      C.c_void_p(fmax_t.data_ptr())))
+
+    def mono_records_end(self, rec_t, maskbits_t, out_t, has_missing=False, missing=-MAXVAL, weight_t=None, cell_methods_sum=False,
+                         field_area_t=None, cell_area_in_t=None, cell_area_out_t=None, nz=8, want_gsum=False):
+        """second half (fg_plan_mono_records_end) on the same rec / maskbits; nz only sizes the returned sums"""
+        o = self._levels_opts(has_missing, missing, weight_t, cell_methods_sum, field_area_t, -MAXVAL, cell_area_in_t, cell_area_out_t,
+                              True)
+        g = np.zeros(nz, dtype=np.float64)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        check(lib().fg_plan_mono_records_end(self._h, C.byref(o), ptr(rec_t), ptr(maskbits_t), ptr(out_t), _dp(g) if want_gsum else None))
+        return g if want_gsum else None
+
+    def mono_records_reset(self, b8_t):
+        """rows 2 and 3 of b8 [ncells_in, 4, 8] back to -1e20 / +1e20 (fg_plan_mono_records_reset): between two plans over one
+        source grid, instead of a second bounds pass"""
+        check(lib().fg_plan_mono_records_reset(self._h, C.c_void_p(b8_t.data_ptr())))
+
     @staticmethod
     def levels_ex_capacity(per_level_area=False):
         """exchange cells apply_levels_ex stages per chunk (fg_plan_levels_ex_capacity)"""

@@ -1238,6 +1238,17 @@ __global__ __launch_bounds__(256) void k_mono_minmax8(int nsrc, int nz, int to_b
   else { f_max[g] = b[2 * NB]; f_min[g] = b[3 * NB]; }
 }
 
+// rows 2 and 3 of every b8 record back to the start values k_mono_bounds8 gives them: a lane per double, 16 consecutive doubles
+// (128 B) per source cell.  Between two plans over one source grid, instead of a second bounds pass (fg_plan_mono_records_reset).
+__global__ __launch_bounds__(256) void k_mono_reset8(int nsrc, double *b8)
+{
+  constexpr int NB = 8;
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (long)nsrc * (2 * NB)) return;
+  const int q = (int)(g % (2 * NB));
+  b8[(size_t)(g / (2 * NB)) * MB8 + 2 * NB + q] = q < NB ? -1.e20 : 1.e20;
+}
+
 // The limited sweep: k_apply_ep8x<2, false> whose gather round also takes the source cell's bounds record.  Per (exchange cell,
 // level): the second-order value as in k_mono_extremes8 (same operations on the same operands: same bits), :689-713 with the
 // 1e-10 snap and the fatal checks (an error bit only for a level < nb_valid), then area *= weight, the sum / cell_measures scaling
@@ -1745,6 +1756,10 @@ void fgd_mono_extremes8(long nx, FgCsr csr, const double *rec, const unsigned ch
                         hipStream_t st)
 {
   if (nx > 0) k_mono_extremes8<<<nblk(nx * 8, 256), 256, 0, st>>>(nx, csr, rec, gbits, missing, nb, b8);
+}
+void fgd_mono_reset8(int nsrc, double *b8, hipStream_t st)
+{
+  if (nsrc > 0) k_mono_reset8<<<nblk((long)nsrc * 16, 256), 256, 0, st>>>(nsrc, b8);
 }
 void fgd_mono_minmax8(int nsrc, int nz, int to_b8, double *b8, double *f_min, double *f_max, hipStream_t st)
 {

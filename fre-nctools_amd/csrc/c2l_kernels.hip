@@ -293,6 +293,101 @@ __global__ __launch_bounds__(CB) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   d_store_records<NB, CB, 2>(row, c < ncells, c0, ncells, rec);
 }
 
+// d_store_records on a tile the caller owns (H * (R + 1) doubles, H = CB / PASSES), so that two stores of one kernel share it;
+// the leading barrier waits for the readers of whatever the tile held before.
+template <int R, int CB, int PASSES>
+__device__ __forceinline__ void d_store_rows(double *tile, const double *row, bool valid, long c0, long ncells, double *dst_rows)
+{
+  constexpr int H = CB / PASSES;
+#pragma unroll
+  for (int p = 0; p < PASSES; p++) {
+    __syncthreads();
+    if (valid && (int)threadIdx.x / H == p) {
+      double *dst = tile + ((int)threadIdx.x % H) * (R + 1);
+#pragma unroll
+      for (int q = 0; q < R; q++) dst[q] = row[q];
+    }
+    __syncthreads();
+    const long first = c0 + (long)p * H;
+    const long left = ncells - first;
+    const long cnt = (left < H ? (left < 0 ? 0 : left) : H) * R;
+    for (long e = threadIdx.x; e < cnt; e += CB) dst_rows[(size_t)first * R + e] = tile[(e / R) * (R + 1) + (e % R)];
+  }
+}
+
+// The limiter's bounds records b8 [cell][4][8] = f_bar_max | f_bar_min | f_max | f_min of the block's CB cells as one contiguous run:
+// rows 0 and 1 are in the tile (17 doubles per cell: thread t wrote f_bar_max of level k to tile[17 t + k], f_bar_min to
+// tile[17 t + 8 + k]), rows 2 and 3 are the start values -1e20 / +1e20 of the extremes and are written as constants.
+template <int CB>
+__device__ __forceinline__ void d_store_bounds(const double *tile, long c0, long ncells, double *b8)
+{
+  constexpr int V = 16, R = 32;
+  __syncthreads();
+  const long left = ncells - c0;
+  const long cnt = (left < CB ? (left < 0 ? 0 : left) : CB) * R;
+  for (long e = threadIdx.x; e < cnt; e += CB) {
+    const int r = (int)(e / R), q = (int)(e % R);
+    b8[(size_t)c0 * R + e] = q < V ? tile[r * (V + 1) + q] : (q < V + 8 ? -1.e20 : 1.e20);
+  }
+}
+
+// k_c2l_records_m that also takes the monotone limiter's bounds (fg_c2l_records_levels_mono; conserve_interp.c:622-645): the nine
+// stencil values a lane holds per level are exactly the 3 x 3 neighbourhood k_mono_bounds8 reads on the halo'd copy -- the centre
+// included, a neighbour of another tile through the halo map, an element no contact fills as 0.0 -- so the maximum and minimum over
+// those that differ from `missing` are taken here, in k_mono_bounds8's order and with its comparisons (same bits, signed zeros too),
+// and no halo'd copy is made.  Levels >= nz keep the start values, as there.  rec and gbits are k_c2l_records_m's.
+//   The 16 bounds of a cell do not wait in registers beside the 24 doubles of its record (that costs a wave per SIMD, or 72 spilled
+// VGPRs at four): each goes to LDS as soon as its level is done.  ONE tile serves both stores -- first the bounds of all CB cells
+// (CB x 17 doubles), then, behind a barrier, the records in two batches as d_store_records stages them -- 8704 B per one-wave block,
+// which still leaves room for four blocks per SIMD.
+template <int CB>
+__global__ __launch_bounds__(CB) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_c2l_records_mb(const C2lTile *tiles, int ntiles, long ncells, int nz, const double *src,
+                                                    const int *cell_of, C2lGeom g, double missing, double *rec, unsigned char *gbits, double *b8)
+{
+  constexpr int NB = 8, R = 3 * NB, H = CB / 2, BW = 2 * NB + 1;
+  constexpr int TILE = CB * BW > H * (R + 1) ? CB * BW : H * (R + 1);
+  __shared__ double tile[TILE];
+  const long c0 = (long)blockIdx.x * CB;
+  const long c = c0 + threadIdx.x;
+  double row[R];
+  if (c < ncells) {
+    const C2lTile T = tiles[d_find_tile(tiles, ntiles, c)];
+    const C2lCell cell(T, c, g);
+    double *bnd = tile + (int)threadIdx.x * BW;
+    int at[3][3];
+#pragma unroll
+    for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+      for (int dx = 0; dx < 3; dx++) at[dy][dx] = cell_of[T.f_off + (long)(cell.j + dy) * (T.nx + 2) + cell.i + dx];
+    unsigned bits = 0;
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+      double f = 0.0, gx = 0.0, gy = 0.0, mx = -1.e20, mn = 1.e20;
+      if (k < nz) {
+        const double *lev = src + (size_t)k * ncells;
+        double v[3][3];
+        bool m = false;
+#pragma unroll
+        for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+          for (int dx = 0; dx < 3; dx++) {
+            v[dy][dx] = (at[dy][dx] >= 0) ? lev[at[dy][dx]] : 0.0;
+            if (!(dy == 1 && dx == 1) && v[dy][dx] == missing) m = true;
+            if (v[dy][dx] != missing) { if (v[dy][dx] > mx) mx = v[dy][dx]; if (v[dy][dx] < mn) mn = v[dy][dx]; }
+          }
+        f = v[1][1];
+        cell.stencil(v, &gx, &gy);
+        bits |= (m ? 1u : 0u) << k;
+      }
+      row[k] = f; row[NB + k] = gx; row[2 * NB + k] = gy;
+      bnd[k] = mx; bnd[NB + k] = mn;
+    }
+    gbits[c] = (unsigned char)bits;
+  }
+  d_store_bounds<CB>(tile, c0, ncells, b8);
+  d_store_rows<R, CB, 2>(tile, row, c < ncells, c0, ncells, rec);
+}
+
 __global__ __launch_bounds__(256) void k_grad_mask(const C2lTile *tiles, int ntiles, long ncells, long F, int nz,
                                                     const double *data, double missing, int *mask)
 {
@@ -356,6 +451,13 @@ void fgd_c2l_records_levels(const void *tiles, int ntiles, long ncells, int nz, 
   if (ncells <= 0 || nz <= 0) return;
   C2lGeom g{geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], geom[6], geom[7], geom[8], geom[9], geom[10]};
   k_c2l_records_m<64><<<nblk(ncells, 64), 64, 0, st>>>((const C2lTile *)tiles, ntiles, ncells, nz, src, cell_of, g, missing, rec, gbits);
+}
+void fgd_c2l_records_levels_mono(const void *tiles, int ntiles, long ncells, int nz, const double *src, const int *cell_of,
+                                 const double *const *geom, double missing, double *rec, unsigned char *gbits, double *b8, hipStream_t st)
+{
+  if (ncells <= 0 || nz <= 0) return;
+  C2lGeom g{geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], geom[6], geom[7], geom[8], geom[9], geom[10]};
+  k_c2l_records_mb<64><<<nblk(ncells, 64), 64, 0, st>>>((const C2lTile *)tiles, ntiles, ncells, nz, src, cell_of, g, missing, rec, gbits, b8);
 }
 void fgd_grad_mask(const void *tiles, int ntiles, long ncells, long F, int nz, const double *data, double missing, int *mask, hipStream_t st)
 {

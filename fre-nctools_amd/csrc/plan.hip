@@ -402,6 +402,9 @@ struct fg_plan {
   // the limiter on eight levels (fg_plan_mono_levels_*): one chunk's bounds [nsrc][4][8] = f_bar_max | f_bar_min | f_max | f_min
   double *mono8_b = nullptr;
   int mono8_nz = 0;              // levels of the open chunk, 0 = none open
+  // ... on the gradient object's records (fg_plan_mono_records_*): the open chunk's bounds are the CALLER's buffer
+  double *mono8r_b = nullptr;
+  int mono8r_nz = 0;
   unsigned *ll_err = nullptr;    // error word of a latlon2xyz conversion queued ahead of the search (great-circle plans from lon / lat)
 
   // Stream-ordered plans (fg_set_search_async).
@@ -2711,6 +2714,119 @@ extern "C" int fg_plan_mono_levels_end(fg_plan *pl, const fg_apply_opts *o, cons
   return ex_error_word(pl);
 }
 
+// ------------------------------------------------------------------- the limiter on the gradient object's records
+// fg_c2l_records_levels_mono writes what mono_levels_stage and k_mono_bounds8 produce for a chunk -- rec, maskbits and b8 with rows
+// 0 / 1 filled, rows 2 / 3 at their start values -- so a chunk is k_mono_extremes8 and k_apply_ep8m straight on the caller's buffers:
+// no k_merge3, no k_gmask_bits, no bounds launch, no halo'd copy.  b8 is consumed: the extremes go into its rows 2 and 3.
+static int mono_records_check(fg_plan *pl, const fg_apply_opts *o, const double *rec, const char *who)
+{
+  if (!pl || !o || !rec) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "%s: the plan is not finalized (fg_plan_finalize)", who);
+  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)", who);
+  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
+    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
+  return 0;
+}
+
+// queued (the streamed sweep, fg_sweep_run_levels_mono): the error word is neither cleared nor read here, see levels_ex_run
+static int mono_records_run(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits, double *b8,
+                            double *out, double *gsum_out, bool queued)
+{
+  const char *who = "fg_plan_apply_records_levels_mono";
+  int rc = mono_records_check(pl, o, rec, who);
+  if (rc) return rc;
+  if (!b8 || !out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per call", who);
+  FGCHK(hipSetDevice(pl->device));
+  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, false, false))) return rc;
+  bool per_level;
+  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
+  hipStream_t st = pl->stream;
+  pl->mono8r_nz = 0;                                       // as fg_plan_apply_levels_mono closes an open chunk of its split
+  if (!queued) FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
+  apply_span_begin(pl, st);
+  fgd_mono_extremes8(pl->nx, pl->csr, rec, maskbits, x.missing, nz, b8, st);
+  fgd_apply_levels8m(pl->ndst, pl->nx, pl->csr, rec, maskbits, b8, x, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, pl->xerr, st);
+  apply_span_end(pl);
+  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
+  FGCHK(hipGetLastError());
+  return queued ? 0 : ex_error_word(pl);
+}
+
+extern "C" int fg_plan_apply_records_levels_mono(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
+                                                 double *b8, double *out, double *gsum_out)
+{
+  return mono_records_run(pl, o, nz, rec, maskbits, b8, out, gsum_out, false);
+}
+// for sweep.hip: a chunk of one streamed run, between fg_plan_levels_ex_begin and _end
+int fg_plan_mono_records_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits, double *b8,
+                               double *out)
+{
+  return mono_records_run(pl, o, nz, rec, maskbits, b8, out, nullptr, true);
+}
+
+extern "C" int fg_plan_mono_records_reset(fg_plan *pl, double *b8)
+{
+  if (!pl || !b8) return fg_fail(FG_ERR_ARG, "fg_plan_mono_records_reset: null argument");
+  FGCHK(hipSetDevice(pl->device));
+  fgd_mono_reset8(pl->nsrc, b8, pl->stream);
+  FGCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int fg_plan_mono_records_begin(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
+                                          double *b8)
+{
+  const char *who = "fg_plan_mono_records_begin";
+  int rc = mono_records_check(pl, o, rec, who);
+  if (rc) return rc;
+  if (!b8) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per begin / end pair", who);
+  FGCHK(hipSetDevice(pl->device));
+  if ((rc = levels_ex_scratch(pl, false, false, false))) return rc;
+  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
+  fgd_mono_extremes8(pl->nx, pl->csr, rec, maskbits, o->has_missing ? o->missing : -1.e20, nz, b8, pl->stream);
+  FGCHK(hipGetLastError());
+  pl->mono8r_nz = nz; pl->mono8r_b = b8;
+  return 0;
+}
+
+extern "C" int fg_plan_mono_records_copy_minmax(fg_plan *pl, int to_plan, double *f_min, double *f_max)
+{
+  if (!pl || !f_min || !f_max) return fg_fail(FG_ERR_ARG, "fg_plan_mono_records_copy_minmax: null argument");
+  if (!pl->mono8r_nz) return fg_fail(FG_ERR_STATE, "fg_plan_mono_records_copy_minmax: call fg_plan_mono_records_begin first");
+  FGCHK(hipSetDevice(pl->device));
+  fgd_mono_minmax8(pl->nsrc, pl->mono8r_nz, to_plan ? 1 : 0, pl->mono8r_b, f_min, f_max, pl->stream);
+  FGCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(pl->stream));
+  return 0;
+}
+
+// rec and maskbits are the caller's, unchanged since begin; the bounds are the buffer begin was given
+extern "C" int fg_plan_mono_records_end(fg_plan *pl, const fg_apply_opts *o, const double *rec, const unsigned char *maskbits, double *out,
+                                        double *gsum_out)
+{
+  const char *who = "fg_plan_mono_records_end";
+  int rc = mono_records_check(pl, o, rec, who);
+  if (rc) return rc;
+  if (!out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!pl->mono8r_nz) return fg_fail(FG_ERR_STATE, "%s: call fg_plan_mono_records_begin first", who);
+  FGCHK(hipSetDevice(pl->device));
+  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, false, false))) return rc;
+  const int nz = pl->mono8r_nz;
+  pl->mono8r_nz = 0;
+  bool per_level;
+  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
+  hipStream_t st = pl->stream;
+  apply_span_begin(pl, st);
+  fgd_apply_levels8m(pl->ndst, pl->nx, pl->csr, rec, maskbits, pl->mono8r_b, x, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz,
+                     pl->xerr, st);
+  apply_span_end(pl);
+  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
+  FGCHK(hipGetLastError());
+  return ex_error_word(pl);
+}
+
 // The sweep on fields the caller already keeps interleaved: data_il [F][nb], grad_x_il/grad_y_il [ncells_in][nb],
 // out_il [ndst][nb]; nb in {2, 4, 8}; no missing values.  Skips the two transposes of fg_plan_apply.
 extern "C" int fg_plan_apply_interleaved(fg_plan *pl, int nb, const double *data_il, const double *grad_x_il,
@@ -3442,6 +3558,18 @@ extern "C" int fg_c2l_records_levels(fg_c2l *h, const double *src, int nz, doubl
   FGCHK(hipSetDevice(h->device));
   fgd_c2l_records_levels(h->tiles_dev, h->ntiles, h->ncells, nz, src, h->cell_of_dev, (const double *const *)h->geom_dev, missing, rec,
                          maskbits, h->stream);
+  FGCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int fg_c2l_records_levels_mono(fg_c2l *h, const double *src, int nz, double missing, double *rec, unsigned char *maskbits,
+                                          double *b8)
+{
+  if (!h || !src || !rec || !maskbits || !b8) return fg_fail(FG_ERR_ARG, "fg_c2l_records_levels_mono: null argument");
+  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "fg_c2l_records_levels_mono: 1 to 8 levels per call");
+  FGCHK(hipSetDevice(h->device));
+  fgd_c2l_records_levels_mono(h->tiles_dev, h->ntiles, h->ncells, nz, src, h->cell_of_dev, (const double *const *)h->geom_dev, missing, rec,
+                              maskbits, b8, h->stream);
   FGCHK(hipGetLastError());
   return 0;
 }

@@ -28,6 +28,8 @@ int fg_plan_levels_ex_begin(fg_plan *pl);
 int fg_plan_levels_ex_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const double *data, const double *rec, const unsigned char *maskbits,
                             double *out);
 int fg_plan_levels_ex_end(fg_plan *pl);
+int fg_plan_mono_records_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits, double *b8,
+                               double *out);
 int fg_c2l_borrow_stream(fg_c2l *h, void *stream, void **saved, int *saved_own);
 void fg_c2l_return_stream(fg_c2l *h, void *saved, int saved_own);
 
@@ -116,6 +118,7 @@ struct fg_sweep {
   struct Slot {
     void *d_raw = nullptr, *d_fin = nullptr;     // device: levels as they came from the host; outputs as they go back
     void *pin_in = nullptr, *pin_out = nullptr;  // staging for pageable user memory (allocated on first need)
+    double *d_b8 = nullptr;                      // fg_sweep_run_levels_mono: the chunk's bounds records [ncin][4][8] (allocated on first need)
     hipEvent_t e_in = nullptr, e_comp = nullptr, e_out = nullptr;
     bool busy = false;
     // deferred copy of staged outputs to the user's pageable arrays
@@ -140,6 +143,7 @@ extern "C" void fg_sweep_destroy(fg_sweep *sw)
   for (auto &sl : sw->slot) {
     if (sl.d_raw) (void)hipFree(sl.d_raw);
     if (sl.d_fin) (void)hipFree(sl.d_fin);
+    if (sl.d_b8) (void)hipFree(sl.d_b8);
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
     if (sl.pin_out) (void)hipHostFree(sl.pin_out);
     for (hipEvent_t e : {sl.e_in, sl.e_comp, sl.e_out}) if (e) (void)hipEventDestroy(e);
@@ -203,11 +207,13 @@ static int slot_retire(fg_sweep *sw, fg_sweep::Slot &sl, void *const *host_out)
 
 // masked: every level carries missing values of its own (fg_sweep_run_levels); else every value is data (fg_sweep_run).
 // xo != null (fg_sweep_run_levels_ex): the level loop with these options, fg_plan_apply_levels_ex / _records_levels_ex per chunk;
-// `masked` is then xo->has_missing.
+// `masked` is then xo->has_missing.  mono (fg_sweep_run_levels_mono; xo != null, order 2): the limited sweep -- per chunk one
+// fg_c2l_records_levels_mono into the slot's bounds records, then per plan the extremes reset (from the second plan on: the plans
+// share the bounds, not the extremes) and the limiter's two kernels on the records.
 static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale, double offset, double missing,
-                     void *const *host_out, bool masked, const fg_apply_opts *xo = nullptr)
+                     void *const *host_out, bool masked, const fg_apply_opts *xo = nullptr, bool mono = false)
 {
-  const char *who = xo ? "fg_sweep_run_levels_ex" : masked ? "fg_sweep_run_levels" : "fg_sweep_run";
+  const char *who = mono ? "fg_sweep_run_levels_mono" : xo ? "fg_sweep_run_levels_ex" : masked ? "fg_sweep_run_levels" : "fg_sweep_run";
   if (!sw || !host_in || !host_out || nlev < 1) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
   for (size_t p = 0; p < sw->plans.size(); p++) if (!host_out[p]) return fg_fail(FG_ERR_ARG, "%s: null output array", who);
   if (masked || xo)
@@ -233,6 +239,9 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
     borrow.saved.push_back(sv); borrow.own.push_back(ow);
   }
   if (sw->c2l) { if (fg_c2l_borrow_stream(sw->c2l, sw->s_comp, &borrow.c_saved, &borrow.c_own)) return FG_ERR_HIP; borrow.c_on = true; }
+  if (mono)
+    for (auto &sl : sw->slot)
+      if (!sl.d_b8) FGCHK(hipMalloc((void **)&sl.d_b8, (size_t)(sw->ncin > 0 ? sw->ncin : 1) * 32 * sizeof(double)));
   if (xo) for (fg_plan *p : sw->plans) { int rc = fg_plan_levels_ex_begin(p); if (rc) return rc; }
   const bool in_pinned = is_pinned(host_in);
   bool out_pinned = true;
@@ -270,14 +279,20 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
       f64 = sw->d_f64;
     }
     double *res = narrow ? sw->d_tmp : (double *)sl.d_fin;         // [plan block][level][cell]
-    if (sw->order == 2) {
+    if (mono) {
+      int rc = fg_c2l_records_levels_mono(sw->c2l, f64, nl, missing, sw->d_rec, sw->d_bits, sl.d_b8);
+      if (rc) return rc;
+    } else if (sw->order == 2) {
       // (xo: records always eight levels wide; without missing values `missing` is -1e20 and masks nothing)
       int rc = (masked || xo) ? fg_c2l_records_levels(sw->c2l, f64, nl, missing, sw->d_rec, sw->d_bits) : fg_c2l_records(sw->c2l, f64, nl, sw->d_rec);
       if (rc) return rc;
     }
     for (size_t p = 0; p < sw->plans.size(); p++) {
       int rc;
-      if (xo)       // (queued: the area_missing word is read once, after the last chunk -- reading it here would stall the pipeline)
+      if (mono) {   // (queued, as below)
+        if (p > 0 && (rc = fg_plan_mono_records_reset(sw->plans[p], sl.d_b8))) return rc;
+        rc = fg_plan_mono_records_chunk(sw->plans[p], xo, nl, sw->d_rec, masked ? sw->d_bits : nullptr, sl.d_b8, res + sw->doff[p]);
+      } else if (xo)       // (queued: the area_missing word is read once, after the last chunk -- reading it here would stall the pipeline)
         rc = fg_plan_levels_ex_chunk(sw->plans[p], xo, nl, f64, sw->order == 2 ? sw->d_rec : nullptr, masked ? sw->d_bits : nullptr, res + sw->doff[p]);
       else if (masked)
         rc = (sw->order == 2) ? fg_plan_apply_records_levels(sw->plans[p], nl, sw->d_rec, sw->d_bits, missing, res + sw->doff[p], nullptr)
@@ -346,4 +361,18 @@ extern "C" int fg_sweep_run_levels_ex(fg_sweep *sw, const fg_apply_opts *opts, c
   if (opts->cell_area_out && sw->plans.size() != 1)
     return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels_ex: cell_area_out belongs to one destination grid, the sweep has %d plans", (int)sw->plans.size());
   return sweep_run(sw, host_in, nlev, scale, offset, opts->has_missing ? opts->missing : -1.e20, host_out, opts->has_missing != 0, opts);
+}
+
+// fg_sweep_run_levels_ex for a --monotonic field: the same buffers, slots, streams, events and conversions; per chunk of eight levels
+// the compute stream takes one fg_c2l_records_levels_mono and, per plan, k_mono_extremes8 and k_apply_ep8m on its records
+// (fg_plan_apply_records_levels_mono, queued).  The plans' error word is cleared before the first chunk and read once after the last.
+extern "C" int fg_sweep_run_levels_mono(fg_sweep *sw, const fg_apply_opts *opts, const void *host_in, long nlev, double scale, double offset,
+                                        void *const *host_out)
+{
+  if (!sw || !opts) return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels_mono: null argument");
+  if (sw->order != 2 || !sw->c2l)
+    return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels_mono: the monotone limiter belongs to conserve_order2 plans with their gradient object (fg_c2l)");
+  if (opts->cell_area_out && sw->plans.size() != 1)
+    return fg_fail(FG_ERR_ARG, "fg_sweep_run_levels_mono: cell_area_out belongs to one destination grid, the sweep has %d plans", (int)sw->plans.size());
+  return sweep_run(sw, host_in, nlev, scale, offset, opts->has_missing ? opts->missing : -1.e20, host_out, opts->has_missing != 0, opts, true);
 }

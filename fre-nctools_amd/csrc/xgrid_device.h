@@ -334,7 +334,8 @@ void fgd_mono_limit(long nx, FgCsr csr, const double *f, double missing, const d
                     const double *fmax, const double *fmin, double *xdata, int *err, hipStream_t st);
 // the limiter on eight levels per launch (fg_plan_apply_levels_mono, fg_plan_mono_levels_*).  b8 holds, per source cell,
 // [4][8] doubles = f_bar_max | f_bar_min | f_max | f_min of the eight levels: one 256-byte gather per exchange cell.  rec and
-// gbits are k_merge3's records and k_gmask_bits' bytes of the chunk (gbits may be null: no gradient is masked).
+// gbits are k_merge3's records and k_gmask_bits' bytes of the chunk (gbits may be null: no gradient is masked), or, with b8, what
+// k_c2l_records_mb wrote into the caller's buffers (fg_plan_apply_records_levels_mono: no bounds launch, fgd_mono_extremes8 first).
 //   fgd_mono_bounds8    :622-645 on nb levels of the level-major halo'd field f (row stride ld_f); f_max / f_min start at -+1e20
 //   fgd_mono_extremes8  :647-669, atomic max / min of the second-order values into b8; no value is stored
 //   fgd_mono_minmax8    f_max / f_min of nz levels between b8 and level-major [nz][nsrc] buffers (to_b8: into b8)
@@ -345,6 +346,9 @@ void fgd_mono_bounds8(const FgTile *tiles_dev, int ntiles, int nsrc, const int *
 void fgd_mono_extremes8(long nx, FgCsr csr, const double *rec, const unsigned char *gbits, double missing, int nb, double *b8,
                         hipStream_t st);
 void fgd_mono_minmax8(int nsrc, int nz, int to_b8, double *b8, double *f_min, double *f_max, hipStream_t st);
+//   fgd_mono_reset8     f_max / f_min of all eight levels back to -+1e20 (128 B per source cell): the bounds of one source grid serve
+//                       the next plan without a second bounds pass (fg_plan_mono_records_reset)
+void fgd_mono_reset8(int nsrc, double *b8, hipStream_t st);
 void fgd_apply_levels8m(int ndst, long nx, FgCsr csr, const double *rec, const unsigned char *gbits, const double *b8, FgApplyEx o,
                         double *out, double *row_sum, long ld, int nb_valid, int *err, hipStream_t st);
 
@@ -430,6 +434,9 @@ void fgd_c2l_records(const void *tiles, int ntiles, long ncells, int nz, int nb_
                      const double *const *geom, double *rec, hipStream_t st);
 void fgd_c2l_records_levels(const void *tiles, int ntiles, long ncells, int nz, const double *src, const int *cell_of,
                             const double *const *geom, double missing, double *rec, unsigned char *gbits, hipStream_t st);
+// ... and the limiter's bounds records b8 [ncells][4][8] beside them (k_c2l_records_mb): rows 0 / 1 from the stencil, rows 2 / 3 -+1e20
+void fgd_c2l_records_levels_mono(const void *tiles, int ntiles, long ncells, int nz, const double *src, const int *cell_of,
+                                 const double *const *geom, double missing, double *rec, unsigned char *gbits, double *b8, hipStream_t st);
 void fgd_grad_mask(const void *tiles, int ntiles, long ncells, long F, int nz, const double *data, double missing, int *mask, hipStream_t st);
 size_t fgd_c2l_tile_size(void);
 void fgd_c2l_tile_fill(void *dst, int idx, int nx, int ny, long cell_off, long f_off, long dx_off, long dy_off, long ew_off, long es_off);

@@ -258,6 +258,26 @@ class Sweep:
         ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
         check(lib().fg_sweep_run_levels_ex(self._h, C.byref(opts), a.ctypes.data_as(C.c_void_p), nlev, float(scale), float(offset), ptrs))
 
+    def run_levels_mono(self, host_in, outs, scale=0.0, offset=0.0, has_missing=False, missing=-1.0e20, weight_t=None,
+                        cell_methods_sum=False, field_area_t=None, cell_area_in_t=None, cell_area_out_t=None):
+        """run_levels_ex() for a --monotonic field (fg_sweep_run_levels_mono; conserve_order2 plans with their gradient object):
+        every level is remapped as apply_ex(monotonic=True, nz=1) would remap it alone after fill_halo and gradient.  Arguments as
+        run_levels_ex takes them; the limiter has no area_missing check."""
+        from ._lib import ApplyOpts
+        a = host_in
+        assert a.dtype == self.in_dtype and a.flags.c_contiguous and a.shape[1] == self.ncells_in
+        nlev = a.shape[0]
+        for o, n in zip(outs, self.ndst):
+            assert o.dtype == self.out_dtype and o.flags.c_contiguous and o.shape == (nlev, n)
+        addr = lambda t: t.data_ptr() if t is not None else None
+        opts = ApplyOpts(1 if has_missing else 0, float(missing), addr(weight_t), 1 if cell_methods_sum else 0, addr(field_area_t),
+                         -1.0e20, addr(cell_area_in_t), addr(cell_area_out_t), 1)
+        ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        check(lib().fg_sweep_run_levels_mono(self._h, C.byref(opts), a.ctypes.data_as(C.c_void_p), nlev, float(scale), float(offset), ptrs))
+
     def destroy(self):
         if self._h:
             lib().fg_sweep_destroy(self._h); self._h = None
+
+
+FieldSweep = Sweep

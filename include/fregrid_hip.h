@@ -426,9 +426,10 @@ int fg_plan_mono_end(fg_plan *plan, const fg_apply_opts *opts, const double *dat
  * chunk instead of one per level -- and synchronises the plan's stream like fg_plan_mono_copy_minmax; fg_plan_mono_levels_end
  * takes the same field arguments again (the caller keeps them unchanged between the two calls), limits and sweeps.
  * fg_plan_apply_levels_mono is begin + end per chunk of eight.  copy_minmax or end without an open begin: FG_ERR_STATE.
- * Out of scope: a records entry and the streamed sweep (fg_sweep_*) for the limiter -- both need the halo'd field beside the
- * records fg_c2l_records_levels writes, a change to the gradient object; a per-level field_area; integration/, which
- * fregrid.c drives one level per call. */
+ * The limiter on the gradient object's records and in the streamed sweep: fg_plan_apply_records_levels_mono,
+ * fg_plan_mono_records_* and fg_sweep_run_levels_mono below.
+ * Out of scope: the multi-rank exchange inside the streamed sweep (ranks use the records split, fg_plan_mono_records_*, on
+ * resident chunks); a field_area with a level axis; integration/, which fregrid.c drives one level per call. */
 int fg_plan_apply_levels_mono(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
                               const double *grad_y, const int *grad_mask, int nlev, double *out, double *gsum_out);
 int fg_plan_mono_levels_begin(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
@@ -436,6 +437,35 @@ int fg_plan_mono_levels_begin(fg_plan *plan, const fg_apply_opts *opts, const do
 int fg_plan_mono_levels_copy_minmax(fg_plan *plan, int to_plan, double *f_min, double *f_max);
 int fg_plan_mono_levels_end(fg_plan *plan, const fg_apply_opts *opts, const double *data, const double *grad_x,
                             const double *grad_y, const int *grad_mask, double *out, double *gsum_out);
+
+/* The limited sweep of 1 <= nz <= 8 levels on what fg_c2l_records_levels_mono writes -- rec [ncells_in][3][8], maskbits
+ * [ncells_in] (NULL = no cell is masked, as a NULL grad_mask above) and the bounds records b8 [ncells_in][4][8] = f_bar_max |
+ * f_bar_min | f_max | f_min -- order-2 plans only.  Two kernels run, the extremes (:647-669) and the limited sweep (:679-866),
+ * straight on the caller's buffers: no transposition of the inputs, no mask-bits pass, no bounds pass, no halo'd copy of the field.
+ * b8 is read AND written: the extremes go into its rows 2 and 3, so the call consumes it.  out [nz][ndst] and gsum_out[k] (host
+ * double[nz] or NULL) carry the bits of fg_plan_apply_levels_mono on the same levels, i.e. of fg_plan_apply_ex(monotonic = 1,
+ * nz = 1) per level.  opts as fg_plan_apply_levels_mono reads them (weight, cell_methods_sum, a field_area shared by the levels,
+ * cell_area_in, cell_area_out, has_missing / missing; the marker is -1e20 without has_missing).
+ * FG_ERR_ARG, nothing written, plan still usable: a first-order plan; a plan that is not finalized; NULL opts, rec, b8 or out;
+ * nz outside 1 .. 8; sum or field_area without a cell area on a plan that holds none.  FG_ERR_DATA: the limiter's fatal checks
+ * with the reference's messages, as above; the plan stays usable.
+ * Several plans over one source grid share the bounds but not the extremes: fg_plan_mono_records_reset puts rows 2 and 3 of b8
+ * back to -1e20 / +1e20 (128 bytes per source cell, on the plan's stream), so the next plan takes the same b8 without a second
+ * bounds pass.
+ * The split for ranks on records, with the semantics and state rules of fg_plan_mono_levels_*: fg_plan_mono_records_begin queues
+ * the extremes of the chunk into the caller's b8, which stays the open chunk's bounds buffer until the end (the caller keeps rec,
+ * maskbits and b8 unchanged in between); fg_plan_mono_records_copy_minmax moves f_min / f_max, level-major [nz][ncells_in] device
+ * buffers, out of (to_plan = 0) or back into (to_plan = 1) that b8 and synchronises the plan's stream; fg_plan_mono_records_end
+ * limits and sweeps.  copy_minmax or end without an open begin: FG_ERR_STATE.  fg_plan_apply_records_levels_mono is begin + end
+ * and closes an open chunk. */
+int fg_plan_apply_records_levels_mono(fg_plan *plan, const fg_apply_opts *opts, int nz, const double *rec,
+                                      const unsigned char *maskbits, double *b8, double *out, double *gsum_out);
+int fg_plan_mono_records_reset(fg_plan *plan, double *b8);
+int fg_plan_mono_records_begin(fg_plan *plan, const fg_apply_opts *opts, int nz, const double *rec,
+                               const unsigned char *maskbits, double *b8);
+int fg_plan_mono_records_copy_minmax(fg_plan *plan, int to_plan, double *f_min, double *f_max);
+int fg_plan_mono_records_end(fg_plan *plan, const fg_apply_opts *opts, const double *rec, const unsigned char *maskbits,
+                             double *out, double *gsum_out);
 
 /* HIP stream the plan launches on (hipStream_t as void*), for event timing. */
 void *fg_plan_stream(fg_plan *plan);
@@ -571,6 +601,16 @@ int  fg_c2l_records(fg_c2l *h, const double *src, int nz, double *rec);
  * cell across a cube edge or corner masks its neighbour.  Same bits as fg_c2l_fill_halo + fg_c2l_gradient(has_missing).
  * Pair with fg_plan_apply_records_levels.  Device pointers. */
 int  fg_c2l_records_levels(fg_c2l *h, const double *src, int nz, double missing, double *rec, unsigned char *maskbits);
+/* fg_c2l_records_levels plus the monotone limiter's bounds in the same pass (conserve_interp.c:622-645): rec and maskbits as
+ * above, the same bits, and b8 [ncells][4][8] = f_bar_max | f_bar_min | f_max | f_min per level.  Rows 0 and 1: the maximum and
+ * minimum over the nine values of the cell's 3 x 3 stencil that differ from `missing`, the centre included, starting from -1e20
+ * and +1e20; the values are the stencil's own, read through the halo map -- a neighbour in another tile across a cube edge or
+ * corner counts, an element no contact fills is 0.0 and is compared like any value.  Rows 2 and 3: -1e20 and +1e20, the start
+ * values of the extremes.  Levels >= nz hold the start values in all four rows.  Bit-identical to the bounds
+ * fg_plan_mono_levels_begin takes from the copy fg_c2l_fill_halo writes; no halo'd copy is made here.  Pair with
+ * fg_plan_apply_records_levels_mono.  Device pointers; b8 holds ncells * 32 doubles. */
+int  fg_c2l_records_levels_mono(fg_c2l *h, const double *src, int nz, double missing, double *rec, unsigned char *maskbits,
+                                double *b8);
 
 /* Host helpers behind fg_c2l_create, exported for tests and for callers without a mosaic file. */
 int fg_c2l_grid_info(int nx, int ny, const double *xt, const double *yt, const double *xc, const double *yc,
@@ -680,6 +720,17 @@ int  fg_sweep_run_levels(fg_sweep *sw, const void *host_in, long nlev, double sc
  * fg_plan_apply_levels_ex on resident levels. */
 int  fg_sweep_run_levels_ex(fg_sweep *sw, const fg_apply_opts *opts, const void *host_in, long nlev, double scale,
                             double offset, void *const *host_out);
+/* fg_sweep_run_levels_ex for a --monotonic field (conserve_order2_monotonic): the same buffers, slots, three streams, events,
+ * widening and narrowing; per chunk of eight levels the compute stream takes one fg_c2l_records_levels_mono and then, per plan,
+ * the extremes reset (from the second plan on) and fg_plan_apply_records_levels_mono.  Scratch per slot: one chunk's b8.  Every
+ * level of every output carries the bits of the per-level chain widen, fg_c2l_fill_halo, fg_c2l_gradient(has_missing),
+ * fg_plan_apply_ex(monotonic = 1, nz = 1), narrow on that level alone.  Options and missing value as fg_sweep_run_levels_ex
+ * (opts->monotonic is not read).  The plans' error word is cleared before the first chunk and read once after the last: a fatal
+ * level gives FG_ERR_DATA with the reference's message; the object stays clean and may be run again.  FG_ERR_ARG before anything
+ * is copied: a sweep created without a gradient object or with first-order plans; opts->cell_area_out with more than one plan; a
+ * plan that is not finalized.  Out of scope: the multi-rank exchange of the extremes inside the streamed sweep. */
+int  fg_sweep_run_levels_mono(fg_sweep *sw, const fg_apply_opts *opts, const void *host_in, long nlev, double scale,
+                              double offset, void *const *host_out);
 void fg_sweep_destroy(fg_sweep *sw);
 void *fg_host_alloc(size_t bytes);      /* page-locked host memory (hipHostMalloc), NULL on failure */
 void fg_host_free(void *p);
