@@ -39,7 +39,7 @@ from ._lib import FregridHipError, lib, lib_path  # noqa: F401
 from .grids import gnomonic_ed_corners, gnomonic_ed_grid, latlon_corners, tripolar_corners  # noqa: F401
 from .c2l import C2lPrep, find_contacts, c2l_grid_info, halo_map  # noqa: F401
 from .remap_file import write_remap_file, read_remap_file  # noqa: F401
-from .field_io import NcFile, Sweep, FieldSweep, HostBuffer, read_field_levels  # noqa: F401
+from .field_io import NcFile, Sweep, FieldSweep, BilinearSweep, HostBuffer, read_field_levels  # noqa: F401
 from . import field_io  # noqa: F401
 from .coupler import coupler_xgrid, CouplerMosaic, coupler_ocean_grid  # noqa: F401
 from .bilinear import (BilinearPlan, setup_bilinear_interp, do_scalar_bilinear_interp, do_vector_bilinear_interp,  # noqa: F401
@@ -66,7 +66,7 @@ __all__ = [
     "GridConfig", "InterpConfig", "FieldConfig", "VarConfig", "XgridPlan",
     "gnomonic_ed_corners", "latlon_corners", "lib", "lib_path", "FregridHipError",
     "BilinearPlan", "setup_bilinear_interp", "do_scalar_bilinear_interp", "do_vector_bilinear_interp",
-    "write_bilinear_remap_file", "read_bilinear_remap_file",
+    "write_bilinear_remap_file", "read_bilinear_remap_file", "BilinearSweep",
     "Extrapolator", "do_extrapolate", "setup_vertical_interp", "do_vertical_interp",
     "RunoffRegrid", "nearest_unmasked", "runoff_input_grid", "runoff_output_grid",
     "LandNearest",

@@ -54,6 +54,7 @@ EXPORTS = [
     "fg_bilin_nlon_fine", "fg_bilin_nlat_fine", "fg_bilin_nlon", "fg_bilin_nlat", "fg_bilin_ncells", "fg_bilin_set_stream",
     "fg_bilin_sync", "fg_bilin_apply_scalar", "fg_bilin_apply_vector", "fg_bilin_remap_write", "fg_bilin_remap_read",
     "fg_unit_vect_latlon", "fg_bilin_fine_grid", "fg_bilin_ambiguous_ties",
+    "fg_bilin_sweep_create", "fg_bilin_sweep_run_scalar", "fg_bilin_sweep_run_vector", "fg_bilin_sweep_destroy",
     "fg_extrap_create", "fg_extrap_destroy", "fg_extrap_set_stream", "fg_extrap_stream", "fg_extrap_run_dev", "fg_extrap_run",
     "fg_extrap_last_syncs", "fg_extrap_get_coef", "fg_extrap_coef_host", "fg_set_extrap_batch", "fg_set_extrap_coef",
     "fg_setup_vertical_interp", "fg_dev_vertical_interp",
@@ -82,6 +83,11 @@ class TopogOpts(C.Structure):
                                 "adjust_topo", "fill_isolated_cells", "dont_change_landmask", "kmt_min")] + \
         [("min_thickness", C.c_double), ("open_very_this_cell", C.c_int), ("fraction_full_cell", C.c_double),
          ("use_great_circle_algorithm", C.c_int), ("on_grid", C.c_int)]
+
+
+class FieldConv(C.Structure):
+    """fg_field_conv (include/fregrid_hip.h): a variable's scale_factor / add_offset (0 = absent) and missing value"""
+    _fields_ = [("scale", C.c_double), ("offset", C.c_double), ("missing", C.c_double)]
 
 
 class ApplyOpts(C.Structure):
@@ -355,6 +361,15 @@ def lib():
     L.fg_bilin_apply_scalar.restype = C.c_int
     L.fg_bilin_apply_vector.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp]
     L.fg_bilin_apply_vector.restype = C.c_int
+    cvp = C.POINTER(FieldConv)
+    L.fg_bilin_sweep_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.fg_bilin_sweep_create.restype = C.c_int
+    L.fg_bilin_sweep_run_scalar.argtypes = [vp, vp, C.c_long, cvp, C.c_int, C.c_int, vp]
+    L.fg_bilin_sweep_run_scalar.restype = C.c_int
+    L.fg_bilin_sweep_run_vector.argtypes = [vp, vp, vp, C.c_long, cvp, cvp, C.c_int, C.c_int, vp, vp]
+    L.fg_bilin_sweep_run_vector.restype = C.c_int
+    L.fg_bilin_sweep_destroy.argtypes = [vp]
+    L.fg_bilin_sweep_destroy.restype = None
     L.fg_bilin_remap_write.argtypes = [C.c_char_p, C.c_int, C.c_int, ip, dp]
     L.fg_bilin_remap_write.restype = C.c_int
     L.fg_bilin_remap_read.argtypes = [C.c_char_p, C.c_int, C.c_int, ip, dp]

@@ -128,6 +128,11 @@ class BilinearPlan:
     def sync(self):
         check(lib().fg_bilin_sync(self._h))
 
+    def sweep(self, in_dtype=np.float64, out_dtype=np.float64):
+        """field_io.BilinearSweep over this plan: levels streamed from host arrays in the file's type (fg_bilin_sweep)"""
+        from .field_io import BilinearSweep
+        return BilinearSweep(self, in_dtype, out_dtype)
+
     def _levels(self, t):
         import torch
         st = torch.cuda.current_stream(self.device).cuda_stream      # the applies run on the caller's current stream

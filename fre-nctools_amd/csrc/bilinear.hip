@@ -1,5 +1,6 @@
 // bilinear.hip -- host orchestration of the bilinear plan (fg_bilin_*): setup_bilinear_interp's compute and READ branches
 // (tools/fregrid/bilinear_interp.c:72-434) and do_scalar / do_vector_bilinear_interp (:436-560) on the device.
+// At the end: fg_bilin_sweep, the field loop that streams levels in their file type through a plan.
 // Kernels: bilinear_kernels.hip.  Host arithmetic that must round like the reference: bilinear_host.c, c2l_host.c.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -9,6 +10,7 @@
 #include <vector>
 #include "bilinear.h"
 #include "fg_host.h"
+#include "stream_slots.h"
 
 extern "C" {
 void fg_unit_vect_latlon(long size, const double *lon, const double *lat, double *vlon, double *vlat);
@@ -377,4 +379,227 @@ extern "C" int fg_bilin_apply_vector(fg_bilin *h, const double *u, const double 
   }
   FGCHK(hipGetLastError());
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// fg_bilin_sweep: the field loop (include/fregrid_hip.h, "streamed bilinear fields").  fg_sweep's pipeline (sweep.hip) around
+// the bilinear plan: levels travel in the file's type through NSLOT slots of CHUNK levels on a copy-in, a compute and a
+// copy-out stream; events order the three, the host waits only when it wants a slot back.  One launch per chunk gathers,
+// widens at the corners and narrows at the points (k_bl_stream_*); finer_step > 0 gathers into a double workspace shared by the
+// chunks (the compute stream is in order) and narrows in the last coarsening step.  The object reads the plan's device arrays,
+// which never change after the plan's creation, and launches on its own compute stream: the plan's stream is not touched, so
+// sweeps may share a plan and either may be destroyed first.
+using namespace fg_stream;
+static_assert(CHUNK == BL_CHUNK, "the slots hold what one k_bl_stream_* launch takes");
+
+struct fg_bilin_sweep {
+  fg_bilin *plan = nullptr;
+  int device = 0, in_type = FG_NC_DOUBLE, out_type = FG_NC_DOUBLE;
+  size_t in_sz = 8, out_sz = 8;
+  long ncells = 0, npts = 0, nout = 0;     // source cells, fine points and output points of one level
+  hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;
+  double *ws = nullptr;                    // finer_step > 0: fine levels (two fields for vectors) | ping-pong | x-sweep
+  size_t ws_cap = 0;
+  struct Slot {
+    void *d_raw[2] = {nullptr, nullptr}, *d_fin[2] = {nullptr, nullptr};     // [1]: the second component, on the first vector run
+    void *pin_in[2] = {nullptr, nullptr}, *pin_out[2] = {nullptr, nullptr};  // staging for pageable user memory, on first need
+    hipEvent_t e_in = nullptr, e_comp = nullptr, e_out = nullptr;
+    bool busy = false, staged_out = false;
+    long l0 = 0; int nl = 0;
+  } slot[NSLOT];
+};
+
+extern "C" void fg_bilin_sweep_destroy(fg_bilin_sweep *sw)
+{
+  if (!sw) return;
+  (void)hipSetDevice(sw->device);
+  for (hipStream_t s : {sw->s_in, sw->s_comp, sw->s_out}) if (s) (void)hipStreamSynchronize(s);
+  for (auto &sl : sw->slot) {                    // (the plan is not touched: it may be gone already)
+    for (int c = 0; c < 2; c++) {
+      if (sl.d_raw[c]) (void)hipFree(sl.d_raw[c]);
+      if (sl.d_fin[c]) (void)hipFree(sl.d_fin[c]);
+      if (sl.pin_in[c]) (void)hipHostFree(sl.pin_in[c]);
+      if (sl.pin_out[c]) (void)hipHostFree(sl.pin_out[c]);
+    }
+    for (hipEvent_t e : {sl.e_in, sl.e_comp, sl.e_out}) if (e) (void)hipEventDestroy(e);
+  }
+  if (sw->ws) (void)hipFree(sw->ws);
+  for (hipStream_t s : {sw->s_in, sw->s_comp, sw->s_out}) if (s) (void)hipStreamDestroy(s);
+  delete sw;
+}
+
+extern "C" int fg_bilin_sweep_create(fg_bilin *h, int in_type, int out_type, fg_bilin_sweep **out)
+{
+  if (!h || !out) return fg_fail(FG_ERR_ARG, "fg_bilin_sweep_create: null argument");
+  *out = nullptr;
+  if (!type_size(in_type) || !type_size(out_type))
+    return fg_fail(FG_ERR_ARG, "fg_bilin_sweep_create: types must be FG_NC_SHORT, FG_NC_INT, FG_NC_FLOAT or FG_NC_DOUBLE");
+  if (int rc = fg_use_device("fg_bilin_sweep_create", h->device)) return rc;
+  fg_bilin_sweep *sw = new fg_bilin_sweep();
+  sw->plan = h; sw->device = h->device; sw->in_type = in_type; sw->out_type = out_type;
+  sw->in_sz = type_size(in_type); sw->out_sz = type_size(out_type);
+  sw->ncells = h->ncells; sw->npts = h->npts; sw->nout = (long)h->nlon * h->nlat;
+  bool ok = hipStreamCreateWithFlags(&sw->s_in, hipStreamNonBlocking) == hipSuccess &&
+            hipStreamCreateWithFlags(&sw->s_comp, hipStreamNonBlocking) == hipSuccess &&
+            hipStreamCreateWithFlags(&sw->s_out, hipStreamNonBlocking) == hipSuccess;
+  for (auto &sl : sw->slot) {
+    ok = ok && hipMalloc(&sl.d_raw[0], (size_t)CHUNK * sw->ncells * sw->in_sz) == hipSuccess &&
+         hipMalloc(&sl.d_fin[0], (size_t)CHUNK * sw->nout * sw->out_sz) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&sl.e_in, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&sl.e_comp, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&sl.e_out, hipEventDisableTiming) == hipSuccess;
+  }
+  if (!ok) { (void)hipGetLastError(); fg_bilin_sweep_destroy(sw); return fg_fail(FG_ERR_HIP, "fg_bilin_sweep_create: out of device memory (or stream / event creation failed)"); }
+  *out = sw;
+  return 0;
+}
+
+// The staging copy of a chunk between pageable user memory and a pinned slot, on up to four host threads: the chunks are tens
+// of megabytes, one core copies them slower than the link moves them, and the host would then be what the pipeline waits for.
+static void bls_copy(void *dst, const void *src, size_t bytes)
+{
+  const size_t piece_min = (size_t)4 << 20;
+  unsigned hw = std::thread::hardware_concurrency();
+  size_t nt = bytes / piece_min;
+  nt = nt > 4 ? 4 : nt;
+  if (hw && nt > hw) nt = hw;
+  if (nt < 2) { memcpy(dst, src, bytes); return; }
+  const size_t part = ((bytes + nt - 1) / nt + 63) & ~(size_t)63;
+  std::vector<std::thread> w;
+  for (size_t t = 1; t < nt; t++) {
+    const size_t lo = t * part, n = lo >= bytes ? 0 : (bytes - lo < part ? bytes - lo : part);
+    if (!n) break;
+    try { w.emplace_back([=] { memcpy((char *)dst + lo, (const char *)src + lo, n); }); }
+    catch (...) { memcpy((char *)dst + lo, (const char *)src + lo, n); }       // no thread to be had: this piece here
+  }
+  memcpy(dst, src, part < bytes ? part : bytes);
+  for (std::thread &x : w) x.join();
+}
+
+// wait for a slot's chunk to be back on the host, then hand staged outputs to the user's pageable arrays
+static int bls_retire(fg_bilin_sweep *sw, fg_bilin_sweep::Slot &sl, int ncomp, void *const *host_out)
+{
+  if (!sl.busy) return 0;
+  FGCHK(hipEventSynchronize(sl.e_out));
+  if (sl.staged_out)
+    for (int c = 0; c < ncomp; c++)
+      bls_copy((char *)host_out[c] + (size_t)sl.l0 * sw->nout * sw->out_sz, sl.pin_out[c], (size_t)sl.nl * sw->nout * sw->out_sz);
+  sl.busy = false;
+  return 0;
+}
+
+// ncomp 1: a scalar field (in[0], cv[0], out[0]); 2: the components u, v of a vector field
+static int bls_run(fg_bilin_sweep *sw, const char *who, int ncomp, const void *const *in, long nlev, const fg_field_conv *const *cv,
+                   int has_missing, int fill_missing, void *const *out)
+{
+  if (!sw || nlev < 1) return fg_fail(FG_ERR_ARG, "%s: null sweep or no level", who);
+  for (int c = 0; c < ncomp; c++) if (!in[c] || !cv[c] || !out[c]) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  fg_bilin *h = sw->plan;
+  FGCHK(hipSetDevice(sw->device));
+  // On every way out -- errors included -- the three streams are drained and the slots cleared, so that a later run never
+  // copies a failed run's staged outputs.
+  struct Drain {
+    fg_bilin_sweep *sw;
+    ~Drain()
+    {
+      for (hipStream_t s : {sw->s_in, sw->s_comp, sw->s_out}) (void)hipStreamSynchronize(s);
+      for (auto &sl : sw->slot) { sl.busy = false; sl.staged_out = false; }
+    }
+  } drain{sw};
+  const size_t nin = (size_t)CHUNK * sw->ncells, nfin = (size_t)CHUNK * sw->nout, nf = (size_t)CHUNK * sw->npts;
+  if (ncomp == 2)
+    for (auto &sl : sw->slot) {
+      if (!sl.d_raw[1]) FGCHK(hipMalloc(&sl.d_raw[1], nin * sw->in_sz));
+      if (!sl.d_fin[1]) FGCHK(hipMalloc(&sl.d_fin[1], nfin * sw->out_sz));
+    }
+  const int fs = h->finer_step;
+  if (fs > 0 && sw->ws_cap < (size_t)(ncomp + 2) * nf) {
+    if (sw->ws) { (void)hipFree(sw->ws); sw->ws = nullptr; sw->ws_cap = 0; }      // (the streams are idle between runs)
+    FGCHK(hipMalloc((void **)&sw->ws, (size_t)(ncomp + 2) * nf * sizeof(double)));
+    sw->ws_cap = (size_t)(ncomp + 2) * nf;
+  }
+  bool in_pinned = true, out_pinned = true;
+  for (int c = 0; c < ncomp; c++) { in_pinned = in_pinned && is_pinned(in[c]); out_pinned = out_pinned && is_pinned(out[c]); }
+  BlConv conv[2], none = {0.0, 0.0, 0.0};
+  for (int c = 0; c < ncomp; c++) conv[c] = {cv[c]->scale, cv[c]->offset, cv[c]->missing};
+  const double missing = conv[0].missing;          // the interpolation's and the coarsening's: u's for a vector field
+  BlStream a;
+  a.npts = sw->npts; a.ncells = sw->ncells; a.nl = 0; a.elem = h->elem; a.cell = h->cell; a.weight = h->weight;
+  a.vlon_in = h->vlon_in; a.vlat_in = h->vlat_in; a.vlon_out = h->vlon_o; a.vlat_out = h->vlat_o;
+  a.has_missing = has_missing; a.fill_missing = fill_missing;
+  long chunk = 0;
+  for (long l0 = 0; l0 < nlev; l0 += CHUNK, chunk++) {
+    const int nl = (int)((nlev - l0 < CHUNK) ? nlev - l0 : CHUNK);
+    fg_bilin_sweep::Slot &sl = sw->slot[chunk % NSLOT];
+    { int rc = bls_retire(sw, sl, ncomp, out); if (rc) return rc; }
+    // --- upload (copy-in stream)
+    const size_t bytes_in = (size_t)nl * sw->ncells * sw->in_sz;
+    for (int c = 0; c < ncomp; c++) {
+      const char *src = (const char *)in[c] + (size_t)l0 * sw->ncells * sw->in_sz;
+      if (!in_pinned) {
+        if (!sl.pin_in[c]) FGCHK(hipHostMalloc(&sl.pin_in[c], nin * sw->in_sz, hipHostMallocDefault));
+        bls_copy(sl.pin_in[c], src, bytes_in);
+        src = (const char *)sl.pin_in[c];
+      }
+      FGCHK(hipMemcpyAsync(sl.d_raw[c], src, bytes_in, hipMemcpyHostToDevice, sw->s_in));
+    }
+    FGCHK(hipEventRecord(sl.e_in, sw->s_in));
+    // --- gather (widen at the corners, narrow at the points), coarsening (compute stream)
+    FGCHK(hipStreamWaitEvent(sw->s_comp, sl.e_in, 0));
+    a.nl = nl;
+    if (fs == 0) {
+      if (ncomp == 1) fgd_bl_stream_scalar(sw->in_type, sw->out_type, a, sl.d_raw[0], conv[0], conv[0], sl.d_fin[0], sw->s_comp);
+      else fgd_bl_stream_vector(sw->in_type, sw->out_type, a, sl.d_raw[0], sl.d_raw[1], conv[0], conv[1], conv[0], conv[1], sl.d_fin[0],
+                                sl.d_fin[1], sw->s_comp);
+    } else {
+      const size_t nfl = (size_t)nl * sw->npts;      // the chunk's levels lie back to back, as fg_bilin_apply_* lays them out
+      double *fine[2] = {sw->ws, sw->ws + nfl}, *pong = sw->ws + (size_t)ncomp * nf, *tmp = pong + nf;
+      if (ncomp == 1) fgd_bl_stream_scalar(sw->in_type, FG_NC_DOUBLE, a, sl.d_raw[0], conv[0], none, fine[0], sw->s_comp);
+      else fgd_bl_stream_vector(sw->in_type, FG_NC_DOUBLE, a, sl.d_raw[0], sl.d_raw[1], conv[0], conv[1], none, none, fine[0], fine[1],
+                                sw->s_comp);
+      for (int c = 0; c < ncomp; c++) {              // do_latlon_coarsening (:994-1040), as bl_coarsen above
+        int nx = h->nxo, ny = h->nyo;
+        double *cur = fine[c], *other = pong;
+        for (int s = 1; s <= fs; s++) {
+          if (s < fs) {
+            fgd_bl_redu2x(cur, nx, ny, nl, h->cosp[s - 1], h->acosp[s - 1], has_missing, missing, tmp, other, sw->s_comp);
+            double *t = cur; cur = other; other = t;
+          } else
+            fgd_bl_redu2x_typed(sw->out_type, cur, nx, ny, nl, h->cosp[s - 1], h->acosp[s - 1], has_missing, missing, tmp, conv[c],
+                                sl.d_fin[c], sw->s_comp);
+          nx = nx / 2; ny = (ny - 1) / 2 + 1;
+        }
+      }
+    }
+    FGCHK(hipGetLastError());
+    FGCHK(hipEventRecord(sl.e_comp, sw->s_comp));
+    // --- download (copy-out stream)
+    FGCHK(hipStreamWaitEvent(sw->s_out, sl.e_comp, 0));
+    const size_t bytes_out = (size_t)nl * sw->nout * sw->out_sz;
+    for (int c = 0; c < ncomp; c++) {
+      if (!out_pinned && !sl.pin_out[c]) FGCHK(hipHostMalloc(&sl.pin_out[c], nfin * sw->out_sz, hipHostMallocDefault));
+      char *dst = out_pinned ? (char *)out[c] + (size_t)l0 * sw->nout * sw->out_sz : (char *)sl.pin_out[c];
+      FGCHK(hipMemcpyAsync(dst, sl.d_fin[c], bytes_out, hipMemcpyDeviceToHost, sw->s_out));
+    }
+    FGCHK(hipEventRecord(sl.e_out, sw->s_out));
+    sl.busy = true; sl.l0 = l0; sl.nl = nl; sl.staged_out = !out_pinned;
+  }
+  // drain in chunk order
+  for (long c = (chunk > NSLOT ? chunk - NSLOT : 0); c < chunk; c++) { int rc = bls_retire(sw, sw->slot[c % NSLOT], ncomp, out); if (rc) return rc; }
+  return 0;
+}
+
+extern "C" int fg_bilin_sweep_run_scalar(fg_bilin_sweep *sw, const void *host_in, long nlev, const fg_field_conv *conv, int has_missing,
+                                         int fill_missing, void *host_out)
+{
+  const void *in[1] = {host_in}; const fg_field_conv *cv[1] = {conv}; void *out[1] = {host_out};
+  return bls_run(sw, "fg_bilin_sweep_run_scalar", 1, in, nlev, cv, has_missing, fill_missing, out);
+}
+
+extern "C" int fg_bilin_sweep_run_vector(fg_bilin_sweep *sw, const void *host_u, const void *host_v, long nlev, const fg_field_conv *conv_u,
+                                         const fg_field_conv *conv_v, int has_missing, int fill_missing, void *host_u_out,
+                                         void *host_v_out)
+{
+  const void *in[2] = {host_u, host_v}; const fg_field_conv *cv[2] = {conv_u, conv_v}; void *out[2] = {host_u_out, host_v_out};
+  return bls_run(sw, "fg_bilin_sweep_run_vector", 2, in, nlev, cv, has_missing, fill_missing, out);
 }

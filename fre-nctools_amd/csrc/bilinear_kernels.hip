@@ -13,6 +13,8 @@
 //   k_bl_gather_*   the 4-point gather with the reference's missing-value test, nz levels per lane; the vector form
 //                   projects (u, v) onto x, y, z at each corner and rotates back in the same pass
 //   k_redu2x_*      the coarsening of finer_step > 0, its missing-value quirk included
+//   k_bl_stream_*   the field loop (fg_bilin_sweep): the gathers on a chunk of eight levels in the file's type, widened at the
+//                   corner and narrowed at the point; k_redu2x_y_typed narrows behind the last coarsening step
 //
 // Comparisons: get_closest_index compares spherical angles (acosl in the reference).  They are taken with the fast acos and
 // redone with fp80.h's fg_acosl when the two sides are within 1e-13 (relative) of each other.  The nearest-centre choice
@@ -27,6 +29,7 @@
 #include "fp80.h"
 #include "acos_dd.h"
 #include "bilinear.h"
+#include "fregrid_hip.h"                       // FG_NC_*: the file types of the field loop's kernels
 
 #define BL_PI 3.14159265358979323846
 #define BL_EPSLN30 (1.e-30)
@@ -482,16 +485,10 @@ __global__ __launch_bounds__(256) void k_redu2x_x(const double *fin, int nxf, in
   tmp[(size_t)k * nxc * nyf + (size_t)j * nxc + i2] = val;
 }
 
-// y-sweep and poles: crs [nz][nyc][nxc]
-__global__ __launch_bounds__(256) void k_redu2x_y(const double *fin, const double *tmp, int nxf, int nyf, int nxc, int nyc, int nz,
-                                                  const double *acosp, int has_missing, double missvalue, double *crs)
+// y-sweep and poles of coarse point (j2, i) of level k
+__device__ __forceinline__ double bl_redu2x_y_val(const double *fin, const double *tmp, int nxf, int nyf, int nxc, int nyc,
+                                                  const double *acosp, int has_missing, double missvalue, int k, int j2, int i)
 {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = (long)nyc * nxc;
-  if (t >= per * nz) return;
-  const int k = (int)(t / per);
-  const long r = t - (long)k * per;
-  const int j2 = (int)(r / nxc), i = (int)(r % nxc);
   const double *f = fin + (size_t)k * nxf * nyf;
   const double *tp = tmp + (size_t)k * nxc * nyf + i;
   double val;
@@ -503,7 +500,139 @@ __global__ __launch_bounds__(256) void k_redu2x_y(const double *fin, const doubl
     if (has_missing && (a == missvalue || b == missvalue || c == missvalue)) val = missvalue;
     else val = acosp[j] * (a + 0.5 * (b + c));
   }
-  crs[(size_t)k * nxc * nyc + (size_t)j2 * nxc + i] = val;
+  return val;
+}
+
+// y-sweep and poles: crs [nz][nyc][nxc]
+__global__ __launch_bounds__(256) void k_redu2x_y(const double *fin, const double *tmp, int nxf, int nyf, int nxc, int nyc, int nz,
+                                                  const double *acosp, int has_missing, double missvalue, double *crs)
+{
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = (long)nyc * nxc;
+  if (t >= per * nz) return;
+  const int k = (int)(t / per);
+  const long r = t - (long)k * per;
+  const int j2 = (int)(r / nxc), i = (int)(r % nxc);
+  crs[(size_t)k * nxc * nyc + (size_t)j2 * nxc + i] = bl_redu2x_y_val(fin, tmp, nxf, nyf, nxc, nyc, acosp, has_missing, missvalue, k, j2, i);
+}
+
+// ----------------------------------------------------------------------------- the field loop (fg_bilin_sweep, bilinear.hip)
+// The gathers above on one chunk of up to BL_CHUNK levels in the FILE type (fregrid.c:1013-1112 around do_scalar / do_vector_
+// bilinear_interp): a corner value is widened where it is gathered -- get_input_data's conversion (fregrid_util.c:2097-2123) is a
+// pure function of one value, so this gives the bits of widening the level first and no double copy of the source exists -- and
+// the result leaves in the file type with write_field_data's conversion (:2376-2406).  A halo corner is init_halo's 0.0, neither
+// scaled nor offset: the reference converts the unpadded nx * ny block only (:2117-2124).  The level loop is unrolled over the
+// chunk with the raw corner loads of LB levels issued before the first use, so the independent gathers are in flight together;
+// `k < nl` (the partial last chunk) is uniform over the wave.
+template <typename T> __device__ __forceinline__ double bl_widen(T raw, const BlConv &c)
+{
+  double v = (double)raw;
+  if (c.scale != 0 && v != c.missing) v *= c.scale;
+  if (c.offset != 0 && v != c.missing) v += c.offset;
+  return v;
+}
+// (a conversion of zeros with T = double changes nothing: what finer_step > 0 stores into the fine workspace)
+template <typename T> __device__ __forceinline__ T bl_narrow(double v, const BlConv &c)
+{
+  if (c.offset != 0 && v != c.missing) v -= c.offset;
+  if (c.scale != 0 && v != c.missing) v /= c.scale;
+  return (T)v;
+}
+
+// scalar: src [nl][ncells] of Tin -> out [nl][npts] of Tout; the interpolation's missing value is the field's own (cin.missing)
+template <typename Tin, typename Tout>
+__global__ __launch_bounds__(256) void k_bl_stream_scalar(BlStream a, const Tin *src, BlConv cin, BlConv cout, Tout *out)
+{
+  constexpr int LB = BL_CHUNK;
+  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= a.npts) return;
+  const int4 c = *(const int4 *)(a.cell + 4 * n);
+  const double w[4] = {a.weight[4 * n], a.weight[4 * n + 1], a.weight[4 * n + 2], a.weight[4 * n + 3]};
+  const int cc[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+  for (int k0 = 0; k0 < BL_CHUNK; k0 += LB) {
+    Tin raw[LB][4];
+#pragma unroll
+    for (int k = 0; k < LB; k++)
+#pragma unroll
+      for (int m = 0; m < 4; m++) raw[k][m] = (k0 + k < a.nl && cc[m] >= 0) ? src[(size_t)(k0 + k) * a.ncells + cc[m]] : (Tin)0;
+#pragma unroll
+    for (int k = 0; k < LB; k++) {
+      if (k0 + k >= a.nl) break;
+      double d[4];
+#pragma unroll
+      for (int m = 0; m < 4; m++) d[m] = cc[m] >= 0 ? bl_widen(raw[k][m], cin) : 0.0;
+      out[(size_t)(k0 + k) * a.npts + n] = bl_narrow<Tout>(bl_interp(d, w, a.has_missing, cin.missing, a.fill_missing), cout);
+    }
+  }
+}
+
+// vector: u and v carry their own conversions; the interpolation's missing value is u's (bilinear_interp.c:494-495)
+template <typename Tin, typename Tout>
+__global__ __launch_bounds__(256) void k_bl_stream_vector(BlStream a, const Tin *u, const Tin *v, BlConv cu, BlConv cv, BlConv cu_out,
+                                                          BlConv cv_out, Tout *u_out, Tout *v_out)
+{
+  constexpr int LB = BL_CHUNK / 2;               // 2 * 4 * LB raw values beside the 36 doubles of unit vectors and weights
+  const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= a.npts) return;
+  const int4 c = *(const int4 *)(a.cell + 4 * n);
+  const int4 e = *(const int4 *)(a.elem + 4 * n);
+  const int cc[4] = {c.x, c.y, c.z, c.w}, ee[4] = {e.x, e.y, e.z, e.w};
+  const double w[4] = {a.weight[4 * n], a.weight[4 * n + 1], a.weight[4 * n + 2], a.weight[4 * n + 3]};
+  double lo[4][3], la[4][3];
+#pragma unroll
+  for (int m = 0; m < 4; m++)
+#pragma unroll
+    for (int x = 0; x < 3; x++) { lo[m][x] = a.vlon_in[3L * ee[m] + x]; la[m][x] = a.vlat_in[3L * ee[m] + x]; }
+  const double ol[3] = {a.vlon_out[3 * n], a.vlon_out[3 * n + 1], a.vlon_out[3 * n + 2]};
+  const double oa[3] = {a.vlat_out[3 * n], a.vlat_out[3 * n + 1], a.vlat_out[3 * n + 2]};
+#pragma unroll
+  for (int k0 = 0; k0 < BL_CHUNK; k0 += LB) {
+    Tin ru[LB][4], rv[LB][4];
+#pragma unroll
+    for (int k = 0; k < LB; k++)
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        const bool ld = k0 + k < a.nl && cc[m] >= 0;
+        const size_t at = (size_t)(k0 + k) * a.ncells + (ld ? cc[m] : 0);
+        ru[k][m] = ld ? u[at] : (Tin)0;
+        rv[k][m] = ld ? v[at] : (Tin)0;
+      }
+#pragma unroll
+    for (int k = 0; k < LB; k++) {
+      if (k0 + k >= a.nl) break;
+      double uu[4], vv[4], r[3];
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+        uu[m] = cc[m] >= 0 ? bl_widen(ru[k][m], cu) : 0.0;
+        vv[m] = cc[m] >= 0 ? bl_widen(rv[k][m], cv) : 0.0;
+      }
+#pragma unroll
+      for (int x = 0; x < 3; x++) {
+        double d[4];
+#pragma unroll
+        for (int m = 0; m < 4; m++) d[m] = uu[m] * lo[m][x] + vv[m] * la[m][x];
+        r[x] = bl_interp(d, w, a.has_missing, cu.missing, a.fill_missing);
+      }
+      u_out[(size_t)(k0 + k) * a.npts + n] = bl_narrow<Tout>(r[0] * ol[0] + r[1] * ol[1] + r[2] * ol[2], cu_out);
+      v_out[(size_t)(k0 + k) * a.npts + n] = bl_narrow<Tout>(r[0] * oa[0] + r[1] * oa[1] + r[2] * oa[2], cv_out);
+    }
+  }
+}
+
+// the last y-sweep of finer_step > 0 with the narrowing folded in: crs [nz][nyc][nxc] of Tout
+template <typename Tout>
+__global__ __launch_bounds__(256) void k_redu2x_y_typed(const double *fin, const double *tmp, int nxf, int nyf, int nxc, int nyc, int nz,
+                                                        const double *acosp, int has_missing, double missvalue, BlConv cout, Tout *crs)
+{
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = (long)nyc * nxc;
+  if (t >= per * nz) return;
+  const int k = (int)(t / per);
+  const long r = t - (long)k * per;
+  const int j2 = (int)(r / nxc), i = (int)(r % nxc);
+  const double val = bl_redu2x_y_val(fin, tmp, nxf, nyf, nxc, nyc, acosp, has_missing, missvalue, k, j2, i);
+  crs[(size_t)k * nxc * nyc + (size_t)j2 * nxc + i] = bl_narrow<Tout>(val, cout);
 }
 
 // ----------------------------------------------------------------------------- launchers (bilinear.hip)
@@ -564,4 +693,52 @@ void fgd_bl_redu2x(const double *fin, int nxf, int nyf, int nz, const double *co
   const long nx_work = (long)(nyf - 2) * nxc * nz, ny_work = (long)nyc * nxc * nz;
   if (nx_work > 0) k_redu2x_x<<<bl_nblk(nx_work, 256), 256, 0, st>>>(fin, nxf, nyf, nxc, nz, cosp, has_missing, missvalue, tmp);
   k_redu2x_y<<<bl_nblk(ny_work, 256), 256, 0, st>>>(fin, tmp, nxf, nyf, nxc, nyc, nz, acosp, has_missing, missvalue, crs);
+}
+
+// ---- the field loop's launchers: the kernel instance of a pair of file types (FG_NC_SHORT / _INT / _FLOAT / _DOUBLE)
+template <typename F> static void bl_with_type(int nc_type, F f)
+{
+  switch (nc_type) {
+    case FG_NC_SHORT: f((int16_t)0); break;
+    case FG_NC_INT: f((int32_t)0); break;
+    case FG_NC_FLOAT: f(0.0f); break;
+    default: f(0.0); break;
+  }
+}
+
+void fgd_bl_stream_scalar(int in_type, int out_type, const BlStream &a, const void *src, BlConv cin, BlConv cout, void *out,
+                          hipStream_t st)
+{
+  bl_with_type(in_type, [&](auto ti) {
+    bl_with_type(out_type, [&](auto to) {
+      using Tin = decltype(ti); using Tout = decltype(to);
+      k_bl_stream_scalar<Tin, Tout><<<bl_nblk(a.npts, 256), 256, 0, st>>>(a, (const Tin *)src, cin, cout, (Tout *)out);
+    });
+  });
+}
+
+void fgd_bl_stream_vector(int in_type, int out_type, const BlStream &a, const void *u, const void *v, BlConv cu, BlConv cv,
+                          BlConv cu_out, BlConv cv_out, void *u_out, void *v_out, hipStream_t st)
+{
+  bl_with_type(in_type, [&](auto ti) {
+    bl_with_type(out_type, [&](auto to) {
+      using Tin = decltype(ti); using Tout = decltype(to);
+      k_bl_stream_vector<Tin, Tout><<<bl_nblk(a.npts, 256), 256, 0, st>>>(a, (const Tin *)u, (const Tin *)v, cu, cv, cu_out, cv_out,
+                                                                          (Tout *)u_out, (Tout *)v_out);
+    });
+  });
+}
+
+// fgd_bl_redu2x whose y-sweep narrows to out_type: the last coarsening step of a streamed chunk
+void fgd_bl_redu2x_typed(int out_type, const double *fin, int nxf, int nyf, int nz, const double *cosp, const double *acosp,
+                         int has_missing, double missvalue, double *tmp, BlConv cout, void *crs, hipStream_t st)
+{
+  const int nxc = nxf / 2, nyc = (nyf - 1) / 2 + 1;
+  const long nx_work = (long)(nyf - 2) * nxc * nz, ny_work = (long)nyc * nxc * nz;
+  if (nx_work > 0) k_redu2x_x<<<bl_nblk(nx_work, 256), 256, 0, st>>>(fin, nxf, nyf, nxc, nz, cosp, has_missing, missvalue, tmp);
+  bl_with_type(out_type, [&](auto to) {
+    using Tout = decltype(to);
+    k_redu2x_y_typed<Tout><<<bl_nblk(ny_work, 256), 256, 0, st>>>(fin, tmp, nxf, nyf, nxc, nyc, nz, acosp, has_missing, missvalue, cout,
+                                                                  (Tout *)crs);
+  });
 }

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 #include "fg_host.h"
+#include "stream_slots.h"
 
 extern "C" int fg_plan_order(const fg_plan *pl);
 extern "C" long fg_plan_ncells_out(const fg_plan *pl);
@@ -33,12 +34,9 @@ int fg_plan_mono_records_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, cons
 int fg_c2l_borrow_stream(fg_c2l *h, void *stream, void **saved, int *saved_own);
 void fg_c2l_return_stream(fg_c2l *h, void *saved, int saved_own);
 
+using namespace fg_stream;     // NSLOT, CHUNK, type_size, is_pinned: shared with the bilinear field loop (stream_slots.h)
+
 namespace {
-constexpr int NSLOT = 3;       // buffer slots in flight
-constexpr int CHUNK = 8;       // levels per chunk: what fg_c2l_records / fg_plan_apply_records take per call
-
-size_t type_size(int t) { return t == FG_NC_SHORT ? 2 : (t == FG_NC_INT || t == FG_NC_FLOAT) ? 4 : t == FG_NC_DOUBLE ? 8 : 0; }
-
 // get_input_data's conversion (fregrid_util.c:2097-2123): widen, then `if (scale != 0) data *= scale` and
 // `if (offset != 0) data += offset`, each only where the value at that point differs from missing_value
 template <typename T>
@@ -62,13 +60,6 @@ __global__ __launch_bounds__(256) void k_narrow(long n, const double *in, double
   if (offset != 0 && v != missing) v -= offset;
   if (scale != 0 && v != missing) v /= scale;
   out[i] = (T)v;
-}
-
-bool is_pinned(const void *p)
-{
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return a.type == hipMemoryTypeHost;
 }
 }  // namespace
 

@@ -281,3 +281,52 @@ class Sweep:
 
 
 FieldSweep = Sweep
+
+
+class BilinearSweep:
+    """fg_bilin_sweep: levels of a cubed-sphere variable streamed from host memory, in the file's type, through a BilinearPlan
+    and back -- fregrid's field loop for --interp_method bilinear, scalar and vector.  Every level comes back as the per-level
+    chain fg_dev_widen -> apply_scalar / apply_vector(nz = 1) -> fg_dev_narrow would give it."""
+
+    NO_CONV = (0.0, 0.0, -1.0e20)                 # (scale, offset, missing): no scale_factor, no add_offset
+
+    def __init__(self, plan, in_dtype=np.float64, out_dtype=np.float64):
+        from ._lib import require_gpu
+        require_gpu()
+        self.plan = plan
+        self.in_dtype, self.out_dtype = np.dtype(in_dtype), np.dtype(out_dtype)
+        self.ncells, self.nlat, self.nlon = plan.ncells, plan.nlat, plan.nlon
+        self._h = C.c_void_p()
+        check(lib().fg_bilin_sweep_create(plan._h, nc_type_of(self.in_dtype), nc_type_of(self.out_dtype), C.byref(self._h)))
+
+    def _check(self, ins, outs):
+        nlev = ins[0].shape[0]
+        for a in ins:
+            assert a.dtype == self.in_dtype and a.flags.c_contiguous and a.shape == (nlev, self.ncells)
+        for o in outs:
+            assert o.dtype == self.out_dtype and o.flags.c_contiguous and o.shape[0] == nlev and o.size == nlev * self.nlat * self.nlon
+        return nlev
+
+    def run_scalar(self, host_in, out, scale=0.0, offset=0.0, missing=-1.0e20, has_missing=False, fill_missing=False):
+        """host_in [nlev][6*N*N] of in_dtype -> out [nlev][nlat][nlon] of out_dtype (numpy arrays, ideally HostBuffer.array).
+        scale / offset (0 = absent) and `missing` steer the conversions (values equal to `missing` are left alone); with
+        has_missing `missing` also marks the corners the interpolation leaves out (fill_missing: takes the heaviest corner)."""
+        from ._lib import FieldConv
+        nlev = self._check([host_in], [out])
+        cv = FieldConv(float(scale), float(offset), float(missing))
+        check(lib().fg_bilin_sweep_run_scalar(self._h, host_in.ctypes.data_as(C.c_void_p), nlev, C.byref(cv), 1 if has_missing else 0,
+                                              1 if fill_missing else 0, out.ctypes.data_as(C.c_void_p)))
+
+    def run_vector(self, u, v, u_out, v_out, conv_u=NO_CONV, conv_v=NO_CONV, has_missing=False, fill_missing=False):
+        """u, v [nlev][6*N*N] eastward / northward -> u_out, v_out [nlev][nlat][nlon].  conv_u / conv_v: (scale, offset, missing)
+        of each component; the interpolation's missing value is u's (bilinear_interp.c:494-495)."""
+        from ._lib import FieldConv
+        nlev = self._check([u, v], [u_out, v_out])
+        cu, cv = FieldConv(*[float(x) for x in conv_u]), FieldConv(*[float(x) for x in conv_v])
+        check(lib().fg_bilin_sweep_run_vector(self._h, u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), nlev, C.byref(cu),
+                                              C.byref(cv), 1 if has_missing else 0, 1 if fill_missing else 0,
+                                              u_out.ctypes.data_as(C.c_void_p), v_out.ctypes.data_as(C.c_void_p)))
+
+    def destroy(self):
+        if self._h:
+            lib().fg_bilin_sweep_destroy(self._h); self._h = None

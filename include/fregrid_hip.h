@@ -909,6 +909,36 @@ int  fg_bilin_apply_scalar(fg_bilin *h, const double *src, int nz, int has_missi
  * (missing tested on the projected values) and rotated onto the lat-lon directions (:476-560) */
 int  fg_bilin_apply_vector(fg_bilin *h, const double *u, const double *v, int nz, int has_missing, double missing, int fill_missing,
                            double *u_out, double *v_out);
+/* Streamed bilinear fields: fregrid's field loop around the bilinear plan (fregrid.c:1013-1112: get_input_data, the halo
+ * update, do_scalar / do_vector_bilinear_interp, write_field_data), built like fg_sweep above: levels cross the link in their
+ * FILE type, in chunks of up to 8 levels, through three buffer slots on a copy-in, a compute and a copy-out stream, so that the
+ * upload of chunk k+1 and the download of chunk k-1 run beside the remap of chunk k.  One kernel per chunk gathers the four
+ * corners of every fine point in the file type, widens each as get_input_data does ((double)raw, `*= scale` / `+= offset` where
+ * != missing; a halo corner stays init_halo's 0.0: the reference converts the unpadded block only, fregrid_util.c:2117-2124),
+ * interpolates, and narrows as write_field_data does; no double copy of a level exists on the device.  finer_step > 0 gathers
+ * into a double workspace, coarsens and narrows in the last coarsening step.
+ *   in_type / out_type: FG_NC_SHORT, FG_NC_INT, FG_NC_FLOAT or FG_NC_DOUBLE.
+ *   host_in (host_u, host_v) [nlev][6*N*N] of in_type, tiles back to back, no halo; outputs [nlev][nlat][nlon] of out_type.
+ *   conv: the variable's scale_factor / add_offset (0 = absent) and missing_value, for its widening and its narrowing; u and v
+ *   carry their own.  has_missing / fill_missing as fg_bilin_apply_*; the interpolation's and the coarsening's missing value is
+ *   conv->missing, for vectors conv_u->missing (bilinear_interp.c:494-495).
+ * Every level of every output carries the bits of the per-level chain fg_dev_widen, fg_bilin_apply_scalar / _vector(nz = 1),
+ * fg_dev_narrow on that level alone.  FG_ERR_ARG before anything is copied: a type outside the four, a null pointer, nlev < 1.
+ * Buffers from fg_host_alloc are used in place, other host memory is staged through the object's pinned buffers (allocated on
+ * first need, like the second component's slots and the workspace).  The object launches on its own streams and only reads
+ * the plan: the plan's stream is the same before and after a run, several sweeps -- one per pair of file types -- may share a
+ * plan, plan and sweeps may be destroyed in any order, and after an error return the object is clean and may be run again.
+ * A sweep serves one call at a time.  Out-of-range narrowing to NC_SHORT / NC_INT is parity-unpinned, as for fg_sweep.
+ * Out of scope: more than one output tile, --extrapolate before the remap. */
+typedef struct fg_bilin_sweep fg_bilin_sweep;
+typedef struct { double scale, offset, missing; } fg_field_conv;   /* scale / offset 0 = absent */
+int  fg_bilin_sweep_create(fg_bilin *h, int in_type, int out_type, fg_bilin_sweep **out);
+int  fg_bilin_sweep_run_scalar(fg_bilin_sweep *sw, const void *host_in, long nlev, const fg_field_conv *conv,
+                               int has_missing, int fill_missing, void *host_out);
+int  fg_bilin_sweep_run_vector(fg_bilin_sweep *sw, const void *host_u, const void *host_v, long nlev,
+                               const fg_field_conv *conv_u, const fg_field_conv *conv_v,
+                               int has_missing, int fill_missing, void *host_u_out, void *host_v_out);
+void fg_bilin_sweep_destroy(fg_bilin_sweep *sw);
 /* fregrid's bilinear remap file (host): dimensions nlon, nlat, three, four; index NC_INT and weight NC_DOUBLE declared
  * (three|four, nlat, nlon) and holding the point-major arrays as they lie in memory, CDF-2 like fg_remap_write.
  * fg_bilin_remap_read refuses a file whose nlon / nlat differ from the fine grid's (FG_ERR_ARG). */
