@@ -13,6 +13,9 @@ mirrors the reference's call signatures:
 
 * ``do_extrapolate`` / ``setup_vertical_interp`` / ``do_vertical_interp``
   -- tools/fregrid/fregrid_util.c:2662,756,789 (--extrapolate fill of a lat-lon source, --dst_vgrid levels)
+* ``Extrapolator.run_batch`` / ``ColumnSweep``
+  -- tools/fregrid/fregrid.c:1026-1043 (the per-record loop of --extrapolate --dst_vgrid: several records filled per launch, and
+     the whole chain fill, remap, vertical levels streamed from and to host arrays in the file's type)
 * ``RunoffRegrid`` / ``nearest_unmasked`` / ``runoff_input_grid`` / ``runoff_output_grid``
   -- tools/runoff_regrid/runoff_regrid.c:430,626,708,243,322 (setup_remap, process_data's arithmetic, nearest, the grids)
 * ``LandNearest``
@@ -39,7 +42,8 @@ from ._lib import FregridHipError, lib, lib_path  # noqa: F401
 from .grids import gnomonic_ed_corners, gnomonic_ed_grid, latlon_corners, tripolar_corners  # noqa: F401
 from .c2l import C2lPrep, find_contacts, c2l_grid_info, halo_map  # noqa: F401
 from .remap_file import write_remap_file, read_remap_file  # noqa: F401
-from .field_io import NcFile, Sweep, FieldSweep, BilinearSweep, HostBuffer, read_field_levels  # noqa: F401
+from .field_io import (NcFile, Sweep, FieldSweep, BilinearSweep, ColumnSweep, HostBuffer, read_field_levels,  # noqa: F401
+                       set_column_records)
 from . import field_io  # noqa: F401
 from .coupler import coupler_xgrid, CouplerMosaic, coupler_ocean_grid  # noqa: F401
 from .bilinear import (BilinearPlan, setup_bilinear_interp, do_scalar_bilinear_interp, do_vector_bilinear_interp,  # noqa: F401
@@ -67,7 +71,7 @@ __all__ = [
     "gnomonic_ed_corners", "latlon_corners", "lib", "lib_path", "FregridHipError",
     "BilinearPlan", "setup_bilinear_interp", "do_scalar_bilinear_interp", "do_vector_bilinear_interp",
     "write_bilinear_remap_file", "read_bilinear_remap_file", "BilinearSweep",
-    "Extrapolator", "do_extrapolate", "setup_vertical_interp", "do_vertical_interp",
+    "Extrapolator", "do_extrapolate", "setup_vertical_interp", "do_vertical_interp", "ColumnSweep", "set_column_records",
     "RunoffRegrid", "nearest_unmasked", "runoff_input_grid", "runoff_output_grid",
     "LandNearest",
     "RiverRegrid", "river_source_grid", "river_land_frac",

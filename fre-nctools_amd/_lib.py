@@ -58,6 +58,7 @@ EXPORTS = [
     "fg_extrap_create", "fg_extrap_destroy", "fg_extrap_set_stream", "fg_extrap_stream", "fg_extrap_run_dev", "fg_extrap_run",
     "fg_extrap_last_syncs", "fg_extrap_get_coef", "fg_extrap_coef_host", "fg_set_extrap_batch", "fg_set_extrap_coef",
     "fg_setup_vertical_interp", "fg_dev_vertical_interp",
+    "fg_extrap_run_batch_dev", "fg_column_create", "fg_column_run", "fg_column_destroy", "fg_set_column_records",
     "fg_dev_latlon2xyz", "fg_plan_create_great_circle_lonlat", "fg_plan_create_great_circle_lonlat_dev",
     "fg_plan_create_polylist_gc",
     "fg_runoff_create", "fg_runoff_create_from_xgrid", "fg_runoff_destroy", "fg_runoff_nxgrid", "fg_runoff_get_xgrid",
@@ -439,6 +440,16 @@ def lib():
     L.fg_extrap_run_dev.restype = C.c_int
     L.fg_extrap_run.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.c_double, ip, dp]
     L.fg_extrap_run.restype = C.c_int
+    L.fg_extrap_run_batch_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_long, C.c_long, C.c_double, C.c_double, ip, dp]
+    L.fg_extrap_run_batch_dev.restype = C.c_int
+    L.fg_column_create.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, C.POINTER(vp)]
+    L.fg_column_create.restype = C.c_int
+    L.fg_column_run.argtypes = [vp, vp, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(vp), ip, dp]
+    L.fg_column_run.restype = C.c_int
+    L.fg_column_destroy.argtypes = [vp]
+    L.fg_column_destroy.restype = None
+    L.fg_set_column_records.argtypes = [C.c_int]
+    L.fg_set_column_records.restype = C.c_int
     L.fg_extrap_last_syncs.argtypes = [vp]
     L.fg_extrap_last_syncs.restype = C.c_long
     L.fg_extrap_get_coef.argtypes = [vp, dp, dp, dp, dp]

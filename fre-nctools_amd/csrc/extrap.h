@@ -45,3 +45,26 @@ void fgd_ex_iterate(const ExGrid &g, const double *src, double *dst, const unsig
 // vertical interpolation: out[k][l] = interp[k] ? (1.-w[k])*in[a[k]][l] + w[k]*in[b[k]][l] : in[a[k]][l]
 struct ExVLevel { int a, b, interp; double w; };
 void fgd_ex_vertical(long nxy, int nk2, const ExVLevel *lev, const double *in, double *out, hipStream_t st);
+// the same for nrec records in [nrec][nk1][nxy] with write_field_data's conversion to nc_type fused: out [nrec][nk2][nxy] of that type
+void fgd_ex_vertical_narrow(int nc_type, long nxy, int nrec, int nk1, int nk2, const ExVLevel *lev, const double *in, double scale,
+                            double offset, double missing, void *out, hipStream_t st);
+
+// Several records per launch (fg_extrap_run_batch_dev).  State buf0 / buf1 [nrec][ncell], sorbits [nrec][(ncell+63)/64], slots
+// [iteration][nrec]; parity[r] names the buffer that holds record r's state (NULL in prepare: the first level, nothing to carry).
+// prepare: `in` is this level of record 0, record r lies r*rec_stride doubles on; it always writes buf0.  iterate: src -> dst for
+// every record whose prev_slots[r] (NULL for iteration 0) is still > stop_crit.  copy_out: `out` as `in`.
+void fgd_ex_prepare_batch(const ExGrid &g, int nrec, const double *in, long rec_stride, double missing, const double *buf0,
+                          const double *buf1, const int *parity, double *dst, unsigned long long *sorbits, hipStream_t st);
+void fgd_ex_iterate_batch(const ExGrid &g, int nrec, const double *src, double *dst, const unsigned long long *sorbits, double stop_crit,
+                          const unsigned long long *prev_slots, unsigned long long *slots, hipStream_t st);
+void fgd_ex_copy_out_batch(const ExGrid &g, int nrec, const double *buf0, const double *buf1, const int *parity, double *out,
+                           long rec_stride, hipStream_t st);
+
+// host side, for the column pipeline (column.hip).  ex_vertical_levels: the bracket table of do_vertical_interp for nk2 destination
+// levels after linear_vertical_interp's fatal checks (FG_ERR_DATA with its message); *need = 0: the field is left alone (lev untouched).
+#include <vector>
+int ex_vertical_levels(int nk1, const double *z1, int nk2, const double *z2, std::vector<ExVLevel> &lev, int *need);
+struct fg_extrap;
+int fg_extrap_borrow_stream(fg_extrap *h, void *stream, void **saved, int *saved_own);   // as fg_plan_borrow_stream
+void fg_extrap_return_stream(fg_extrap *h, void *saved, int saved_own);
+void fg_extrap_dims(const fg_extrap *h, int *ni, int *nj, int *device);

@@ -87,7 +87,23 @@ struct fg_extrap {
   unsigned long long *h_slots = nullptr;     // pinned
   std::vector<double> h_fac;
   long syncs = 0;                            // host synchronisations of the last run's iteration loops
+  // fg_extrap_run_batch_dev: the same state for b_cap records, grown on demand
+  int b_cap = 0;
+  double *b_buf[2] = {nullptr, nullptr};     // [b_cap][ncell]
+  unsigned long long *b_bits = nullptr;      // [b_cap][(ncell + 63) / 64]: a record's bits start on a word of their own
+  unsigned long long *b_slots = nullptr;     // [EX_MAX_ITER][nrec] of the running call
+  unsigned long long *b_h_slots = nullptr;   // pinned
+  int *b_par = nullptr, *b_h_par = nullptr;  // [b_cap] buffer that holds record r's state; device / pinned
 };
+
+static void ex_batch_free(fg_extrap *h)
+{
+  (void)hipFree(h->b_buf[0]); (void)hipFree(h->b_buf[1]); (void)hipFree(h->b_bits); (void)hipFree(h->b_slots); (void)hipFree(h->b_par);
+  if (h->b_h_slots) (void)hipHostFree(h->b_h_slots);
+  if (h->b_h_par) (void)hipHostFree(h->b_h_par);
+  h->b_buf[0] = h->b_buf[1] = nullptr; h->b_bits = h->b_slots = h->b_h_slots = nullptr; h->b_par = h->b_h_par = nullptr;
+  h->b_cap = 0;
+}
 
 extern "C" void fg_extrap_destroy(fg_extrap *h)
 {
@@ -98,6 +114,7 @@ extern "C" void fg_extrap_destroy(fg_extrap *h)
   (void)hipFree(h->fac); (void)hipFree(h->coef); (void)hipFree(h->buf[0]); (void)hipFree(h->buf[1]);
   (void)hipFree(h->sorbits); (void)hipFree(h->slots);
   if (h->h_slots) (void)hipHostFree(h->h_slots);
+  ex_batch_free(h);
   delete h;
 }
 
@@ -147,6 +164,23 @@ extern "C" int fg_extrap_set_stream(fg_extrap *h, void *stream)
   return 0;
 }
 extern "C" void *fg_extrap_stream(fg_extrap *h) { return h ? (void *)h->stream : nullptr; }
+// Internal (column.hip): queue on `stream` for the duration of one call, then take the previous stream back (the caller has
+// synchronised `stream` by then).  The handle never owns a borrowed stream.
+int fg_extrap_borrow_stream(fg_extrap *h, void *stream, void **saved, int *saved_own)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "null extrapolation handle");
+  FGCHK(hipSetDevice(h->device));
+  if (h->stream) FGCHK(hipStreamSynchronize(h->stream));
+  *saved = (void *)h->stream; *saved_own = h->own_stream ? 1 : 0;
+  h->stream = (hipStream_t)stream; h->own_stream = false;
+  return 0;
+}
+void fg_extrap_return_stream(fg_extrap *h, void *saved, int saved_own)
+{
+  if (!h) return;
+  h->stream = (hipStream_t)saved; h->own_stream = saved_own != 0;
+}
+void fg_extrap_dims(const fg_extrap *h, int *ni, int *nj, int *device) { *ni = h->ni; *nj = h->nj; *device = h->device; }
 extern "C" long fg_extrap_last_syncs(const fg_extrap *h) { return h ? h->syncs : 0; }
 
 extern "C" int fg_extrap_get_coef(fg_extrap *h, double *cfw, double *cfe, double *cfs, double *cfn)
@@ -248,6 +282,93 @@ extern "C" int fg_extrap_run(fg_extrap *h, const double *in, double *out, int nk
   return rc;
 }
 
+// ------------------------------------------------------------------------------------------------ several records per launch
+static int ex_batch_reserve(fg_extrap *h, int nrec)
+{
+  if (nrec <= h->b_cap) return 0;
+  FGCHK(hipStreamSynchronize(h->stream));
+  ex_batch_free(h);
+  const size_t ncell = (size_t)h->ni * h->nj, nwords = (ncell + 63) / 64, n = (size_t)nrec;
+  FGCHK(hipMalloc((void **)&h->b_buf[0], n * ncell * sizeof(double)));
+  FGCHK(hipMalloc((void **)&h->b_buf[1], n * ncell * sizeof(double)));
+  FGCHK(hipMalloc((void **)&h->b_bits, n * nwords * sizeof(unsigned long long)));
+  FGCHK(hipMalloc((void **)&h->b_slots, n * EX_MAX_ITER * sizeof(unsigned long long)));
+  FGCHK(hipMalloc((void **)&h->b_par, n * sizeof(int)));
+  FGCHK(hipHostMalloc((void **)&h->b_h_slots, n * EX_MAX_ITER * sizeof(unsigned long long)));
+  FGCHK(hipHostMalloc((void **)&h->b_h_par, n * sizeof(int)));
+  h->b_cap = nrec;
+  return 0;
+}
+
+// fg_extrap_run_dev for nrec records that advance through the levels in lockstep: one prepare launch per level and one launch per
+// iteration for all of them.  A record is its own problem -- its own slots (laid out [iteration][record], so a batch of launches
+// is one contiguous region: one memset per level, one copy per synchronisation), stop, ping-pong parity and mask words -- and the
+// next level starts when every record has stopped on this one.
+extern "C" int fg_extrap_run_batch_dev(fg_extrap *h, int nrec, const double *d_in, double *d_out, int nk, long level_stride,
+                                       long rec_stride, double missing, double stop_crit, int *iters_out, double *resmax_out)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_extrap_run_batch_dev: null handle");
+  if (nrec < 1 || nrec > 65535 || nk < 1 || !d_in || !d_out) return fg_fail(FG_ERR_ARG, "fg_extrap_run_batch_dev: bad argument");
+  const long ncell = (long)h->ni * h->nj;
+  if (level_stride == 0) level_stride = ncell;
+  if (level_stride < ncell) return fg_fail(FG_ERR_ARG, "fg_extrap_run_batch_dev: level_stride smaller than a level");
+  if (rec_stride == 0) rec_stride = (long)nk * level_stride;
+  if (rec_stride < (long)(nk - 1) * level_stride + ncell) return fg_fail(FG_ERR_ARG, "fg_extrap_run_batch_dev: rec_stride smaller than a record");
+  FGCHK(hipSetDevice(h->device));
+  int rc = ex_batch_reserve(h, nrec);
+  if (rc) return rc;
+  const int batch = g_batch;
+  ExGrid g;
+  g.ni = h->ni; g.nj = h->nj; g.is_cyclic = h->is_cyclic;
+  g.f.rn = h->fac; g.f.rs = h->fac + h->nj; g.f.rc = h->fac + 2 * h->nj; g.f.ce = h->fac + 3 * h->nj; g.f.cw = h->fac + 3 * h->nj + h->ni;
+  g.coef = nullptr;
+  if (g_coef_mode) {
+    rc = ex_stored_coef(h);
+    if (rc) return rc;
+    g.coef = h->coef;
+  }
+  hipStream_t st = h->stream;
+  h->syncs = 0;
+  std::vector<int> stop(nrec);
+  for (int k = 0; k < nk; k++) {
+    fgd_ex_prepare_batch(g, nrec, d_in + (long)k * level_stride, rec_stride, missing, h->b_buf[0], h->b_buf[1], k ? h->b_par : nullptr,
+                         h->b_buf[0], h->b_bits, st);
+    FGCHK(hipMemsetAsync(h->b_slots, 0, (size_t)nrec * EX_MAX_ITER * sizeof(unsigned long long), st));
+    int running = nrec;
+    for (int r = 0; r < nrec; r++) stop[r] = -1;
+    for (int n0 = 0; n0 < EX_MAX_ITER && running > 0; n0 += batch) {
+      const int n1 = n0 + batch < EX_MAX_ITER ? n0 + batch : EX_MAX_ITER;
+      for (int n = n0; n < n1; n++)                                   // iteration n: buf[n & 1] -> buf[(n + 1) & 1], every record
+        fgd_ex_iterate_batch(g, nrec, h->b_buf[n & 1], h->b_buf[(n + 1) & 1], h->b_bits, stop_crit,
+                             n ? h->b_slots + (size_t)(n - 1) * nrec : nullptr, h->b_slots + (size_t)n * nrec, st);
+      FGCHK(hipGetLastError());
+      FGCHK(hipMemcpyAsync(h->b_h_slots + (size_t)n0 * nrec, h->b_slots + (size_t)n0 * nrec,
+                           (size_t)(n1 - n0) * nrec * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      FGCHK(hipStreamSynchronize(st));
+      h->syncs++;
+      for (int r = 0; r < nrec; r++) {
+        if (stop[r] >= 0) continue;
+        for (int n = n0; n < n1; n++) {
+          double v;
+          memcpy(&v, &h->b_h_slots[(size_t)n * nrec + r], sizeof v);
+          if (v <= stop_crit || n == EX_MAX_ITER - 1) { stop[r] = n; running--; break; }   // :2769
+        }
+      }
+    }
+    for (int r = 0; r < nrec; r++) {
+      h->b_h_par[r] = (stop[r] + 1) & 1;
+      if (iters_out) iters_out[(size_t)r * nk + k] = stop[r];
+      if (resmax_out) memcpy(&resmax_out[(size_t)r * nk + k], &h->b_h_slots[(size_t)stop[r] * nrec + r], sizeof(double));
+    }
+    // (the stream is idle here, and the next write of b_h_par comes after the next synchronisation: the copy has run by then)
+    FGCHK(hipMemcpyAsync(h->b_par, h->b_h_par, (size_t)nrec * sizeof(int), hipMemcpyHostToDevice, st));
+    fgd_ex_copy_out_batch(g, nrec, h->b_buf[0], h->b_buf[1], h->b_par, d_out + (long)k * level_stride, rec_stride, st);
+  }
+  FGCHK(hipGetLastError());
+  FGCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ vertical interpolation
 extern "C" int fg_setup_vertical_interp(int nk1, const double *z1, int nk2, const double *z2, int *kstart_out, int *kend_out,
                                         int *need_interp_out)
@@ -288,6 +409,29 @@ extern "C" int fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int n
     return 0;
   }
   if (d_in == d_out) return fg_fail(FG_ERR_ARG, "fg_dev_vertical_interp: in and out must be different arrays");
+  std::vector<ExVLevel> lev;
+  rc = ex_vertical_levels(nk1, z1, nk2, z2, lev, &need);                              // (the fatal checks come after the argument check)
+  if (rc) return rc;
+  ExVLevel *d_lev = nullptr;
+  FGCHK(hipMalloc((void **)&d_lev, lev.size() * sizeof(ExVLevel)));
+  hipError_t e = hipMemcpy(d_lev, lev.data(), lev.size() * sizeof(ExVLevel), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    fgd_ex_vertical(nxy, nk2, d_lev, d_in, d_out, nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  }
+  (void)hipFree(d_lev);
+  if (e != hipSuccess) return fg_fail(FG_ERR_HIP, "fg_dev_vertical_interp: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int ex_vertical_levels(int nk1, const double *z1, int nk2, const double *z2, std::vector<ExVLevel> &lev, int *need_out)
+{
+  int kstart, kend, need;
+  int rc = fg_setup_vertical_interp(nk1, z1, nk2, z2, &kstart, &kend, &need);
+  if (rc) return rc;
+  *need_out = need;
+  if (!need) return 0;
   const int nk = kend - kstart + 1;
   if (nk < 1) return fg_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
   const double *g1 = z1, *g2 = z2 + kstart;
@@ -296,7 +440,7 @@ extern "C" int fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int n
   for (int k = 1; k < nk; k++) if (g2[k] <= g2[k - 1]) return fg_fail(FG_ERR_DATA, "interp.c: grid2 not monotonic");
   if (g1[0] > g2[0]) return fg_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
   if (g1[nk1 - 1] < g2[nk - 1]) return fg_fail(FG_ERR_DATA, "interp.c: grid2 lies outside grid1");
-  std::vector<ExVLevel> lev(nk2);
+  lev.assign(nk2, ExVLevel());
   for (int k = 0; k < nk2; k++) {
     ExVLevel &L = lev[k];
     L.a = L.b = 0; L.interp = 0; L.w = 0.0;
@@ -308,15 +452,5 @@ extern "C" int fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int n
     else if (n == 0) L.a = 0;
     else { L.interp = 1; L.a = n - 1; L.b = n; L.w = (v - g1[n - 1]) / (g1[n] - g1[n - 1]); }
   }
-  ExVLevel *d_lev = nullptr;
-  FGCHK(hipMalloc((void **)&d_lev, lev.size() * sizeof(ExVLevel)));
-  hipError_t e = hipMemcpy(d_lev, lev.data(), lev.size() * sizeof(ExVLevel), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    fgd_ex_vertical(nxy, nk2, d_lev, d_in, d_out, nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  }
-  (void)hipFree(d_lev);
-  if (e != hipSuccess) return fg_fail(FG_ERR_HIP, "fg_dev_vertical_interp: %s", hipGetErrorString(e));
   return 0;
 }

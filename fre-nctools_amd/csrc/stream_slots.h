@@ -1,4 +1,4 @@
-// stream_slots.h -- what the streamed field loops share (sweep.hip: fg_sweep, bilinear.hip: fg_bilin_sweep): the shape of the
+// stream_slots.h -- what the streamed field loops share (sweep.hip: fg_sweep, bilinear.hip: fg_bilin_sweep, column.hip: fg_column): the shape of the
 // pipeline -- NSLOT buffer slots of CHUNK levels on a copy-in, a compute and a copy-out stream -- and two host helpers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,4 +17,7 @@ inline bool is_pinned(const void *p)
   if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
   return a.type == hipMemoryTypeHost;
 }
+
+// get_input_data's conversion (sweep.hip's k_widen) queued on `st`: out[i] = (double)raw[i], scaled / offset where != missing
+void widen(int nc_type, long n, const void *raw, double scale, double offset, double missing, double *out, hipStream_t st);
 }  // namespace fg_stream

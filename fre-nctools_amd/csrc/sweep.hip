@@ -63,19 +63,25 @@ __global__ __launch_bounds__(256) void k_narrow(long n, const double *in, double
 }
 }  // namespace
 
+// k_widen on `st` for a file type (declared in stream_slots.h: the column pipeline widens with the same kernel)
+void fg_stream::widen(int nc_type, long n, const void *raw, double scale, double offset, double missing, double *out, hipStream_t st)
+{
+  const int grid = (int)((n + 255) / 256);
+  switch (nc_type) {
+    case FG_NC_SHORT: k_widen<int16_t><<<grid, 256, 0, st>>>(n, (const int16_t *)raw, scale, offset, missing, out); break;
+    case FG_NC_INT: k_widen<int32_t><<<grid, 256, 0, st>>>(n, (const int32_t *)raw, scale, offset, missing, out); break;
+    case FG_NC_FLOAT: k_widen<float><<<grid, 256, 0, st>>>(n, (const float *)raw, scale, offset, missing, out); break;
+    default: k_widen<double><<<grid, 256, 0, st>>>(n, (const double *)raw, scale, offset, missing, out); break;
+  }
+}
+
 // get_input_data's / write_field_data's conversions on device buffers, for callers that run the field loop themselves
 // (integration/field_io_hip.c).  Synchronous (null stream + device sync).
 extern "C" int fg_dev_widen(int nc_type, long n, const void *raw_dev, double scale, double offset, double missing, double *out_dev)
 {
   if (n < 0 || (n > 0 && (!raw_dev || !out_dev)) || !type_size(nc_type)) return fg_fail(FG_ERR_ARG, "fg_dev_widen: bad argument");
   if (n == 0) return 0;
-  const int grid = (int)((n + 255) / 256);
-  switch (nc_type) {
-    case FG_NC_SHORT: k_widen<int16_t><<<grid, 256>>>(n, (const int16_t *)raw_dev, scale, offset, missing, out_dev); break;
-    case FG_NC_INT: k_widen<int32_t><<<grid, 256>>>(n, (const int32_t *)raw_dev, scale, offset, missing, out_dev); break;
-    case FG_NC_FLOAT: k_widen<float><<<grid, 256>>>(n, (const float *)raw_dev, scale, offset, missing, out_dev); break;
-    default: k_widen<double><<<grid, 256>>>(n, (const double *)raw_dev, scale, offset, missing, out_dev); break;
-  }
+  widen(nc_type, n, raw_dev, scale, offset, missing, out_dev, nullptr);
   FGCHK(hipGetLastError());
   FGCHK(hipDeviceSynchronize());
   return 0;
@@ -260,13 +266,7 @@ static int sweep_run(fg_sweep *sw, const void *host_in, long nlev, double scale,
     const long n_in = (long)nl * sw->ncin;
     const double *f64 = (const double *)sl.d_raw;
     if (widen) {
-      const int grid = (int)((n_in + 255) / 256);
-      switch (sw->in_type) {
-        case FG_NC_SHORT: k_widen<int16_t><<<grid, 256, 0, sw->s_comp>>>(n_in, (const int16_t *)sl.d_raw, scale, offset, missing, sw->d_f64); break;
-        case FG_NC_INT: k_widen<int32_t><<<grid, 256, 0, sw->s_comp>>>(n_in, (const int32_t *)sl.d_raw, scale, offset, missing, sw->d_f64); break;
-        case FG_NC_FLOAT: k_widen<float><<<grid, 256, 0, sw->s_comp>>>(n_in, (const float *)sl.d_raw, scale, offset, missing, sw->d_f64); break;
-        default: k_widen<double><<<grid, 256, 0, sw->s_comp>>>(n_in, (const double *)sl.d_raw, scale, offset, missing, sw->d_f64); break;
-      }
+      fg_stream::widen(sw->in_type, n_in, sl.d_raw, scale, offset, missing, sw->d_f64, sw->s_comp);
       f64 = sw->d_f64;
     }
     double *res = narrow ? sw->d_tmp : (double *)sl.d_fin;         // [plan block][level][cell]

@@ -114,6 +114,38 @@ class Extrapolator:
                                   iters.ctypes.data_as(_ipt), resmax.ctypes.data_as(_dpt)))
         return out, iters, resmax
 
+    def run_batch(self, data, missing, stop_crit=0.005):
+        """run() for several records in the same launches (fg_extrap_run_batch_dev): data [nrec, nk, nj, ni], a numpy array or a
+        contiguous float64 torch tensor on the handle's device.  Returns (out, iters [nrec, nk], resmax [nrec, nk]); every record
+        comes back as run() gives it alone."""
+        shape = tuple(data.shape)
+        if len(shape) != 4 or shape[-2:] != (self.nj, self.ni):
+            raise ValueError(f"data must be [nrec, nk, {self.nj}, {self.ni}], got {shape}")
+        nrec, nk = shape[:2]
+        iters, resmax = np.empty((nrec, nk), dtype=np.int32), np.empty((nrec, nk))
+        tail = (nk, 0, 0, float(missing), float(stop_crit), iters.ctypes.data_as(_ipt), resmax.ctypes.data_as(_dpt))
+        if _is_torch(data):
+            import torch
+            if data.dtype != torch.float64 or not data.is_cuda or not data.is_contiguous():
+                raise ValueError("a torch input must be a contiguous float64 tensor on the device")
+            out = torch.empty_like(data)
+            torch.cuda.current_stream(data.device).synchronize()       # the handle's stream does not wait for torch's
+            check(lib().fg_extrap_run_batch_dev(self._h, nrec, data.data_ptr(), out.data_ptr(), *tail))
+            return out, iters, resmax
+        L = lib()
+        a = _f64(data)
+        out = np.empty_like(a)
+        d = L.fg_dev_alloc(a.nbytes + 8, self.device)
+        try:
+            if not d:
+                check(-2)
+            check(L.fg_dev_upload(d, a.ctypes.data, a.nbytes))
+            check(L.fg_extrap_run_batch_dev(self._h, nrec, d, d, *tail))   # in place: a level is read before it is written
+            check(L.fg_dev_download(out.ctypes.data, d, out.nbytes))
+        finally:
+            L.fg_dev_free(d)
+        return out, iters, resmax
+
 
 def do_extrapolate(ni, nj, nk, lon, lat, data_in, is_cyclic, missing_value, stop_crit, verbose=True, device=0):
     """fregrid_util.c:2662 -- returns data_out [nk, nj, ni]; prints the reference's "Stopped after ..." line per level."""

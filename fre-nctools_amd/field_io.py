@@ -330,3 +330,57 @@ class BilinearSweep:
     def destroy(self):
         if self._h:
             lib().fg_bilin_sweep_destroy(self._h); self._h = None
+
+
+def set_column_records(n):
+    """Records per chunk of ColumnSweep (test / tuning hook; < 1 restores the default).  Results never depend on it."""
+    return int(lib().fg_set_column_records(int(n)))
+
+
+class ColumnSweep:
+    """fg_column: fregrid's ocean column loop, --extrapolate --dst_vgrid, streamed.  Records [nk1][nj][ni] of a lat-lon source
+    travel in the file's type; on the device each chunk of records is widened, filled (Extrapolator.run_batch), remapped through
+    every plan (finalized conserve_order1 plans on the extrapolator's grid, one per output tile), put on the z_out levels and
+    narrowed.  z_out = None: no --dst_vgrid, the output keeps the z_in levels.  Every record comes back as the chain fg_dev_widen,
+    Extrapolator.run, XgridPlan.apply, do_vertical_interp, fg_dev_narrow gives it alone."""
+
+    def __init__(self, extrap, plans, in_dtype=np.float64, out_dtype=np.float64, z_in=None, z_out=None, nk=None):
+        self.extrap, self.plans = extrap, list(plans)
+        self.in_dtype, self.out_dtype = np.dtype(in_dtype), np.dtype(out_dtype)
+        dpt = C.POINTER(C.c_double)
+        z1 = None if z_in is None else np.ascontiguousarray(z_in, dtype=np.float64).reshape(-1)
+        z2 = None if z_out is None else np.ascontiguousarray(z_out, dtype=np.float64).reshape(-1)
+        if z1 is None and (z2 is not None or nk is None):
+            raise ValueError("ColumnSweep needs z_in (or, without z_out, the number of levels nk)")
+        self.nk1 = z1.size if z1 is not None else int(nk)
+        hs = (C.c_void_p * len(self.plans))(*[p._h for p in self.plans])
+        self._h = C.c_void_p()
+        check(lib().fg_column_create(extrap.handle, len(self.plans), hs, nc_type_of(self.in_dtype), nc_type_of(self.out_dtype),
+                                     self.nk1, z1.ctypes.data_as(dpt) if z1 is not None else None,
+                                     z2.size if z2 is not None else 0, z2.ctypes.data_as(dpt) if z2 is not None else None,
+                                     C.byref(self._h)))
+        from .extrapolate import setup_vertical_interp
+        self.nk2 = z2.size if z2 is not None and setup_vertical_interp(z1, z2)[2] else self.nk1      # need_interp = 0: left alone
+        self.ncells_in = extrap.ni * extrap.nj
+        self.ndst = [int(lib().fg_plan_ncells_out(p._h)) for p in self.plans]
+
+    def run(self, host_in, outs, scale=0.0, offset=0.0, missing=-1.0e20, stop_crit=0.005):
+        """host_in [nrec, nk1, nj, ni] of in_dtype; outs[p] [nrec, nk2, ny, nx] (any shape of nrec*nk2*ndst_p elements) of out_dtype
+        (numpy arrays, ideally HostBuffer.array).  scale / offset (0 = absent) are applied where the value differs from `missing`
+        before the fill, and undone on the way out.  Returns (iters [nrec, nk1], resmax [nrec, nk1]) of the fill."""
+        a = host_in
+        assert a.dtype == self.in_dtype and a.flags.c_contiguous and a.ndim >= 2 and a.shape[1] == self.nk1 \
+            and a.size == a.shape[0] * self.nk1 * self.ncells_in
+        nrec = a.shape[0]
+        for o, n in zip(outs, self.ndst):
+            assert o.dtype == self.out_dtype and o.flags.c_contiguous and o.size == nrec * self.nk2 * n
+        iters, resmax = np.empty((nrec, self.nk1), dtype=np.int32), np.empty((nrec, self.nk1))
+        ptrs = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+        check(lib().fg_column_run(self._h, a.ctypes.data_as(C.c_void_p), nrec, float(scale), float(offset), float(missing),
+                                  float(stop_crit), ptrs, iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                  resmax.ctypes.data_as(C.POINTER(C.c_double))))
+        return iters, resmax
+
+    def destroy(self):
+        if self._h:
+            lib().fg_column_destroy(self._h); self._h = None

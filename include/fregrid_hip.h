@@ -975,6 +975,20 @@ int  fg_extrap_run_dev(fg_extrap *h, const double *d_in, double *d_out, int nk, 
 int  fg_extrap_run(fg_extrap *h, const double *in, double *out, int nk, double missing, double stop_crit,
                    int *iters_out, double *resmax_out);
 long fg_extrap_last_syncs(const fg_extrap *h);              /* host synchronisations of the last run's iteration loops */
+/* fg_extrap_run_dev for nrec records of nk levels on the handle's grid, filled in the same launches: record r, level k at
+ * r * rec_stride + k * level_stride doubles (a stride of 0: densely packed, level_stride = ni*nj, rec_stride = nk * level_stride);
+ * d_out may equal d_in.  The records advance through the levels in lockstep -- level k of all records is prepared in one launch
+ * and iterated with ONE launch per iteration for all records (the record is a grid dimension); the next level starts when every
+ * record has stopped on this one -- but each record is its own problem: its own chain of 4000 maximum slots (a block of record r
+ * in launch n first reads slot (r, n-1) and leaves when it is <= stop_crit, so every launch behind a record's stop is a no-op for
+ * that record), its own iteration count and largest residual, its own ping-pong parity, its own mask-bit words.
+ * CONTRACT: for every record d_out, iters_out [nrec*nk] and resmax_out [nrec*nk] (host, record-major, may be NULL) are bit for bit
+ * what fg_extrap_run_dev gives for that record alone -- the reference's do_extrapolate -- whatever the other records are, in
+ * whatever order, for every value of fg_set_extrap_batch and fg_set_extrap_coef.  Host synchronisations per level:
+ * ceil((max_r iters[r][k] + 1) / batch); fg_extrap_last_syncs reports their sum.  The handle's state grows on demand to nrec
+ * records.  FG_ERR_ARG (handle still usable): nrec < 1, nk < 1, a null array, a stride smaller than a level or a record. */
+int  fg_extrap_run_batch_dev(fg_extrap *h, int nrec, const double *d_in, double *d_out, int nk, long level_stride, long rec_stride,
+                             double missing, double stop_crit, int *iters_out, double *resmax_out);
 /* the four coefficient arrays [nj*ni] (host) as the handle uses them / without a handle or a device (cfw, cfe, cfs, cfn of :2710-2718) */
 int  fg_extrap_get_coef(fg_extrap *h, double *cfw, double *cfe, double *cfs, double *cfn);
 int  fg_extrap_coef_host(int ni, int nj, const double *lon, const double *lat, double *cfw, double *cfe, double *cfs, double *cfn);
@@ -990,6 +1004,30 @@ int  fg_setup_vertical_interp(int nk1, const double *z1, int nk2, const double *
  * (1.-w)*upper + w*lower.  need_interp == 0: d_out = d_in.  The reference's fatal checks ("grid1 not monotonic",
  * "grid2 lies outside grid1", ...) return FG_ERR_DATA with its message.  Synchronous. */
 int  fg_dev_vertical_interp(long nxy, int nk1, const double *z1, int nk2, const double *z2, const double *d_in, double *d_out);
+
+/* The column loop: `fregrid --extrapolate --dst_vgrid` (fregrid.c:1026-1043) for nrec records of one lat-lon source tile, streamed.
+ *   plans     finalized conserve_order1 plans, one per destination tile, whose source grid is the extrapolator's ni x nj (same
+ *             device); anything else FG_ERR_ARG
+ *   z1 [nk1]  source levels, z2 [nk2] the --dst_vgrid levels; z2 = NULL: no --dst_vgrid, the output has nk1 levels.
+ *             linear_vertical_interp's fatal checks return FG_ERR_DATA with the reference's message from fg_column_create.
+ *   host_in   [nrec][nk1][nj][ni] in in_type; host_out[tile] [nrec][nk2][ny][nx] in out_type (FG_NC_SHORT / _INT / _FLOAT /
+ *             _DOUBLE, as fg_sweep); iters_out, resmax_out [nrec*nk1] (host, may be NULL) as fg_extrap_run_batch_dev fills them
+ * Per chunk of records, on the copy-in, compute and copy-out streams with fg_sweep's slots and events: typed upload; widening with
+ * get_input_data's rule (scale, then offset, each skipped when 0, only where data != missing); fg_extrap_run_batch_dev; the plain
+ * sweep of all records x nk1 planes through each plan (the fill cleared has_missing: no missing test); one kernel that forms
+ * (1.-w)*a + w*b per destination level and stores it in out_type; typed download.  Every value carries the bits of the chain
+ * fg_dev_widen, fg_extrap_run_dev per record, fg_plan_apply, fg_dev_vertical_interp, fg_dev_narrow.  The fill's wait for its slots
+ * is the only host synchronisation inside a chunk; the upload of the next chunk is queued before it and the download of the
+ * previous one runs beside it.  Records per chunk: fg_set_column_records(n) (test / tuning hook, returns the value in force,
+ * 0 = default); < 1 restores the default -- as many as fit with all buffers in a quarter of the free device memory, at most 8.
+ * Results never depend on it.  Streams and lifetimes as fg_sweep_run: plans and extrapolator are borrowed inside a run only. */
+typedef struct fg_column fg_column;
+int  fg_column_create(fg_extrap *ex, int nplans, fg_plan *const *plans, int in_type, int out_type,
+                      int nk1, const double *z1, int nk2, const double *z2, fg_column **out);
+int  fg_column_run(fg_column *c, const void *host_in, long nrec, double scale, double offset, double missing,
+                   double stop_crit, void *const *host_out, int *iters_out, double *resmax_out);
+void fg_column_destroy(fg_column *c);
+int  fg_set_column_records(int n);
 
 /* ---- runoff_regrid on the device (tools/runoff_regrid/runoff_regrid.c: setup_remap :430, process_data :626-675, nearest :708) ----
  * All angles in radians, as setup_remap receives them.  The exchange list is create_xgrid_1dx2d_order1's; the nearest ocean
