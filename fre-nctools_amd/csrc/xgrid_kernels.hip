@@ -1597,7 +1597,7 @@ __device__ __forceinline__ void d_finish_pair(const double *px, const double *py
 
 // Quad x quad fast path, first half: the Sutherland-Hodgman pass.  LDS: polygon [8][T] double2 (32 KiB per 256 lanes); the
 // cutting quad lives in registers.  Returns -1 if the pair must go to the general kernel (more than 4 vertices on a side, or
-// more than 8 in an intermediate polygon); otherwise the vertex count of the clipped polygon left in column tid (0: empty).
+// more than 8 in an intermediate polygon; RECT: a column that is not exactly vertical); otherwise the vertex count of the clipped polygon left in column tid (0: empty).
 // RECT: the destination cell is four values of its column record and two of the latitude axis (FgRect) -- D holds areas only.
 // The pass runs at four waves per SIMD and is bound by instruction issue, with a third of its wave cycles spent waiting: what
 // was measured on its round trips to memory and LDS and on its exec-masked regions, kept or not, is in
@@ -1652,6 +1652,12 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
   for (int k = 0; k < 4; k++) asm volatile("" : "+v"(x2[k]));
   asm volatile("" : "+v"(n1), "+v"(lon_in_avg), "+v"(lon_out_avg));
   if (n1 > NV1 || n2 > 4) return -1;
+  // RECT: the inside tests below drop the product that is an exact zero along an axis-aligned edge.  Edges 1 and 3 are
+  // horizontal by construction (y2[0] and y2[1], y2[2] and y2[3] are one value each); edges 0 and 2 are vertical where the
+  // column record's corners are equal -- the shift and d_pimod1 below give equal values for equal values, so they are equal
+  // where the edge code sees them.  A column that fix_lon left not exactly vertical (the longitude axis changes sign inside it)
+  // goes to the general kernel, which has the full formula.
+  if (RECT && !(x2[3] == x2[0] && x2[1] == x2[2])) return -1;
   if constexpr (QSRC) {
     if (n1 > 4) {
       const FgVerts sv = d_cell_verts(S, s, n1);
@@ -1721,9 +1727,19 @@ __device__ __forceinline__ int d_clip_quad_sh(double2 (*sh_poly)[T], const int t
     unsigned inmask = 0u;
 #pragma unroll
     for (int k = 0; k < CLIP_SLOTS; k++) c[k] = sh_poly[k][tid];
+    // RECT: of d_inside_edge's two products one has the factor y2_1 - y2_0 (odd e) or x2_0 - x2_1 (even e, by the guard above),
+    // an exact zero; adding +-0 to the other product cannot move it across 1e-12, so that one alone is formed, with its
+    // vertex-independent factor taken once per edge.  (The crossings below keep their full formulas: there the sign of a zero
+    // numerator reaches the result.)
+    const double axis = (e & 1) ? x2_0 - x2_1 : y2_1 - y2_0;
 #pragma unroll
     for (int k = 0; k < CLIP_SLOTS; k++)
-      if (k < n_cur) inmask |= (unsigned)d_inside_edge(x2_0, y2_0, x2_1, y2_1, c[k].x, c[k].y) << k;
+      if (k < n_cur) {
+        int in;
+        if (RECT) in = (((e & 1) ? axis * (c[k].y - y2_0) : (c[k].x - x2_0) * axis) <= 1.e-12) ? 1 : 0;
+        else in = d_inside_edge(x2_0, y2_0, x2_1, y2_1, c[k].x, c[k].y);
+        inmask |= (unsigned)in << k;
+      }
     const unsigned full = (1u << n_cur) - 1u;
     const unsigned prevmask = ((inmask << 1) | (inmask >> (n_cur - 1))) & full;     // bit k: vertex k-1 (cyclic) is inside
     const unsigned tmask = inmask ^ prevmask;                                        // bit k: edge (k-1, k) crosses the line
