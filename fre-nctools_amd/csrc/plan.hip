@@ -2101,25 +2101,38 @@ static void apply_span_end(fg_plan *pl)
 // levels per source cell of the interleaved layouts that hold nz <= 8 levels
 static int levels_pad(int nz) { return nz > 4 ? 8 : (nz > 2 ? 4 : 2); }
 
-// row sums of one launch: [cell][16] or [level <= 8][cell]
-static int ensure_il_rs(fg_plan *pl)
+// Scratch of the sweeps.  A buffer is allocated by the first call that wants it and lives as long as the plan.
+enum : unsigned {
+  SC_IL = 1,            // il_out [cell][8] and the staged chunk: il_m (order 2, records) or il_f (order 1, [cell][8])
+  SC_RS = 2,            // il_rs, the row sums of one launch: [cell][16] or [level <= 8][cell]
+  SC_BITS = 4,          // lv_bits, order 2: a chunk's gradient-mask bits per source cell
+  SC_XERR = 8,          // the error word
+  SC_FA8 = 16,          // lx_fa: a chunk's per-level field_area [source cell][8]
+  SC_MONO8 = 32,        // mono8_b: the limiter's bounds of a chunk
+  SC_ROW_SUM = 64,      // row_sum [ndst], the one-level calls
+  SC_MONO = 128         // mono_x, mono_b: the one-level limiter
+};
+template <typename T> static bool scratch_get(fg_plan *pl, T *&p, size_t n) { return p || (p = pl->alloc<T>(n)); }
+static int apply_scratch(fg_plan *pl, unsigned want)
 {
-  if (!pl->il_rs) {
-    pl->il_rs = pl->alloc<double>((size_t)pl->ndst * 16);
-    if (!pl->il_rs) return fg_fail(FG_ERR_HIP, "out of device memory");
+  const size_t ns = pl->nsrc, ns1 = pl->nsrc > 0 ? pl->nsrc : 1;
+  bool ok = true;
+  if (want & SC_IL)
+    ok = scratch_get(pl, pl->il_out, (size_t)pl->ndst * 8) &&
+         (pl->order == 2 ? scratch_get(pl, pl->il_m, ns * 24) : scratch_get(pl, pl->il_f, (size_t)pl->f_stride * 8));
+  if (ok && (want & SC_BITS) && pl->order == 2) ok = scratch_get(pl, pl->lv_bits, ns1);
+  if (ok && (want & SC_RS)) ok = scratch_get(pl, pl->il_rs, (size_t)pl->ndst * 16);
+  if (ok && (want & SC_XERR)) ok = scratch_get(pl, pl->xerr, 4);
+  if (ok && (want & SC_FA8)) ok = scratch_get(pl, pl->lx_fa, ns1 * 8);
+  if (ok && (want & SC_MONO8)) ok = scratch_get(pl, pl->mono8_b, ns1 * 32);
+  if (ok && (want & SC_ROW_SUM) && pl->row_sum_cap < pl->ndst) {
+    pl->release(pl->row_sum);
+    pl->row_sum = pl->alloc<double>(pl->ndst);
+    pl->row_sum_cap = pl->row_sum ? pl->ndst : 0;
+    ok = pl->row_sum != nullptr;
   }
-  return 0;
-}
-
-static int ensure_il_scratch(fg_plan *pl, bool want_rs)
-{
-  if (!pl->il_out) {
-    pl->il_out = pl->alloc<double>((size_t)pl->ndst * 8);
-    if (pl->order == 2) pl->il_m = pl->alloc<double>((size_t)pl->nsrc * 24);
-    else pl->il_f = pl->alloc<double>((size_t)pl->f_stride * 8);
-    if (!pl->il_out || (pl->order == 2 ? !pl->il_m : !pl->il_f)) return fg_fail(FG_ERR_HIP, "out of device memory");
-  }
-  return want_rs ? ensure_il_rs(pl) : 0;
+  if (ok && (want & SC_MONO)) ok = scratch_get(pl, pl->mono_x, pl->nx > 0 ? pl->nx : 1) && scratch_get(pl, pl->mono_b, ns * 4);
+  return ok ? 0 : fg_fail(FG_ERR_HIP, "out of device memory");
 }
 
 // levels [0, nbv) of the first-order field f (level-major, stride f_stride) -> il_f [f_stride][nbp]
@@ -2129,6 +2142,70 @@ static void interleave_field(fg_plan *pl, const double *f, int nbp, int nbv, hip
   double *outs[3] = {pl->il_f, nullptr, nullptr};
   const long lds[3] = {pl->f_stride, 0, 0}, ns[3] = {pl->f_stride, 0, 0};
   fgd_interleave3(nbp, 1, ins, lds, ns, outs, nbv, st);
+}
+
+// the error word of the sweeps that have one, read once the stream has drained
+static int ex_error_word(fg_plan *pl)
+{
+  int e = 0;
+  FGCHK(hipMemcpyAsync(&e, pl->xerr, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
+  FGCHK(hipStreamSynchronize(pl->stream));
+  if (e & FG_XERR_AREA_MISSING) return fg_fail(FG_ERR_DATA, "conserve_interp: data is not missing but area is missing");
+  if (e & FG_XERR_ABOVE) return fg_fail(FG_ERR_DATA, " xdata is greater than f_bar_max ");
+  if (e & FG_XERR_BELOW) return fg_fail(FG_ERR_DATA, " xdata is less than f_bar_min ");
+  return 0;
+}
+
+// the options as the kernels take them
+static FgApplyEx ex_pack(fg_plan *pl, const fg_apply_opts *o, const int *gmask)
+{
+  FgApplyEx x{};
+  x.weight = o->weight; x.field_area = o->field_area; x.cell_area_out = o->cell_methods_sum ? nullptr : o->cell_area_out;
+  x.cell_area = o->cell_area_in ? o->cell_area_in : (pl->have_geom ? pl->S.area : nullptr);
+  x.gmask = gmask; x.area_missing = o->area_missing;
+  x.has_missing = o->has_missing; x.missing = o->has_missing ? o->missing : -1.e20;   // conserve_interp.c:541-542
+  x.sum = o->cell_methods_sum;
+  return x;
+}
+
+// cell_methods = sum and cell_measures need the source cells' areas
+static int area_rule(const char *who, const fg_plan *pl, const fg_apply_opts *o)
+{
+  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
+    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
+  return 0;
+}
+
+// The argument rules of the many-level entries.  An entry names those that apply to it; they are tested in the order written here,
+// after the null pointers (null_arg) and the unfinalized plan.  null_late: a pointer the limiter's entries test after the area rule.
+// o is read only by the rules that concern options.  Codes and texts are include/fregrid_hip.h's.
+enum : unsigned {
+  CK_NO_LIMITER = 1, CK_LIMITER = 2, CK_FA_LD = 4, CK_AREA = 8, CK_RECORDS = 16, CK_BITS = 32, CK_NLEV = 64, CK_NZ8 = 128, CK_NZ8_PAIR = 256,
+  CK_BITS_IF_MISSING = 512, CK_GRADS = 1024, CK_GRADS_MASK = 2048
+};
+static int levels_check(const char *who, const fg_plan *pl, const fg_apply_opts *o, unsigned rules, bool null_arg, bool null_late, int nlev,
+                        long fa_ld, bool grads, bool mask)
+{
+  const bool nz8 = nlev >= 1 && nlev <= 8;
+  if (null_arg) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "%s: the plan is not finalized (fg_plan_finalize)", who);
+  if ((rules & CK_NO_LIMITER) && o->monotonic) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter works on one level per call (fg_plan_apply_ex)", who);
+  if ((rules & CK_LIMITER) && pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)", who);
+  if ((rules & CK_FA_LD) && fa_ld != 0 && fa_ld != pl->nsrc)
+    return fg_fail(FG_ERR_ARG, "%s: field_area_ld must be 0 (one area for all levels) or ncells_in (an area per level)", who);
+  if ((rules & CK_FA_LD) && fa_ld != 0 && !o->field_area) return fg_fail(FG_ERR_ARG, "%s: field_area_ld is set but opts->field_area is NULL", who);
+  if (rules & CK_AREA) { if (int rc = area_rule(who, pl, o)) return rc; }
+  if ((rules & CK_RECORDS) && pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: records carry gradients, the plan is first order", who);
+  if (null_late) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if ((rules & CK_BITS) && !mask) return fg_fail(FG_ERR_ARG, "%s: order 2 needs the gradient-mask bits", who);
+  if ((rules & CK_NLEV) && nlev < 1) return fg_fail(FG_ERR_ARG, "%s: nlev must be >= 1", who);
+  if ((rules & CK_NZ8) && !nz8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per call", who);
+  if ((rules & CK_NZ8_PAIR) && !nz8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per begin / end pair", who);
+  if ((rules & CK_BITS_IF_MISSING) && o->has_missing && !mask) return fg_fail(FG_ERR_ARG, "%s: a field with missing values needs the gradient-mask bits", who);
+  if ((rules & CK_GRADS) && pl->order == 2 && !grads) return fg_fail(FG_ERR_ARG, "%s: order 2 needs grad_x and grad_y [nlev][ncells_in]", who);
+  if ((rules & CK_GRADS_MASK) && pl->order == 2 && !(grads && mask))
+    return fg_fail(FG_ERR_ARG, "%s: order 2 needs grad_x, grad_y and grad_mask [nlev][ncells_in]", who);
+  return 0;
 }
 
 extern "C" int fg_plan_apply(fg_plan *pl, const double *data, const double *grad_x, const double *grad_y,
@@ -2147,13 +2224,7 @@ extern "C" int fg_plan_apply(fg_plan *pl, const double *data, const double *grad
   const int ndst = pl->ndst;
   const int nchunk = (nz + 7) / 8;
   if (nchunk > 256) return fg_fail(FG_ERR_ARG, "nz too large for one call (max 2048 levels)");
-  if (gsum_out && pl->row_sum_cap < ndst) {
-    pl->release(pl->row_sum);
-    pl->row_sum = pl->alloc<double>(ndst);
-    if (!pl->row_sum) { pl->row_sum_cap = 0; return fg_fail(FG_ERR_HIP, "out of device memory"); }
-    pl->row_sum_cap = ndst;
-  }
-  if (nz > 1) { int rc = ensure_il_scratch(pl, gsum_out != nullptr); if (rc) return rc; }
+  { int rc = apply_scratch(pl, (gsum_out ? SC_ROW_SUM : 0) | (nz > 1 ? SC_IL : 0) | (nz > 1 && gsum_out ? SC_RS : 0)); if (rc) return rc; }
   apply_span_begin(pl, st);
   int nred = 0;
   for (int k0 = 0; k0 < nz; k0 += 8) {
@@ -2202,7 +2273,7 @@ extern "C" int fg_plan_apply_records(fg_plan *pl, int nz, const double *rec, dou
   FGCHK(hipSetDevice(pl->device));
   hipStream_t st = pl->stream;
   const int ndst = pl->ndst, nbp = levels_pad(nz);
-  if (gsum_out) { int rc = ensure_il_rs(pl); if (rc) return rc; }
+  { int rc = apply_scratch(pl, gsum_out ? SC_RS : 0); if (rc) return rc; }
   apply_span_begin(pl, st);
   fgd_apply_il_merged(nbp, ndst, pl->nx, pl->csr, rec, -1.e20, out, gsum_out ? pl->il_rs : nullptr, (long)ndst, nz, st);
   if (gsum_out) fgd_reduce_sum(pl->il_rs, (long)ndst * nbp, pl->red_partial, pl->red_result, st);
@@ -2215,21 +2286,62 @@ extern "C" int fg_plan_apply_records(fg_plan *pl, int nz, const double *rec, dou
   return 0;
 }
 
-// ------------------------------------------------------------------- levels with missing values of their own
-// The reference's level loop (fregrid.c:1045-1083: do_scalar_conserve_interp(nz = 1, has_missing = 1) per level), eight levels
-// per launch of k_apply_ep8g<MASKED>.  Row sums are kept level-major and reduced level by level with the reduction of the one-level
-// calls, so gsum_out[k] carries the bits fg_plan_apply_ex returns for level k alone.
+// ------------------------------------------------------------------- eight levels per launch: one chunk driver
+// The reference sweeps a field whose levels have missing values, options or the limiter one level at a time (fregrid.c:1045-1083:
+// do_scalar_conserve_interp(nz = 1) per level).  Here eight levels share a launch and level k keeps the bits of that one-level call,
+// its sum included.  Three families of kernels do so, and every entry below is its argument rules and one call of run_levels:
+//   masked  k_apply_ep8g<MASKED> (fgd_apply_levels8): levels with missing values of their own
+//   ex      k_apply_ep8x (fgd_apply_levels8x): weight / sum / cell_measures / --target_grid, no limiter
+//   mono    the limiter: k_mono_bounds8 and k_mono_extremes8 (the first half, conserve_interp.c:622-669), then k_apply_ep8m (the second,
+//           :679-866); the split for ranks falls between the halves, at the reference's mpp_min_double / mpp_max_double (:672-677)
 extern "C" int fg_plan_levels_capacity(void) { return FG_LEVELS_CAP; }
 int fg_plan_is_finalized(const fg_plan *pl) { return pl && pl->finalized; }      // for sweep.hip
+enum { FAM_MASKED, FAM_EX, FAM_MONO };
+enum : unsigned {
+  RUN_QUEUED = 1,                 // a chunk of a streamed run (sweep.hip): the error word is neither cleared nor read, so that the host
+                                  // does not wait for the chunk -- fg_plan_levels_ex_begin clears it, fg_plan_levels_ex_end reads it
+  RUN_FIRST = 2, RUN_SECOND = 4,  // the halves of the limiter; the other families run as RUN_BOTH
+  RUN_BOTH = RUN_FIRST | RUN_SECOND
+};
 
-static int levels_scratch(fg_plan *pl, bool want_rs, bool want_il)
+// The levels of a call: level-major arrays (rec null) or the caller's records of one chunk.
+struct LevelSrc {
+  const double *data, *grad_x, *grad_y;      // [nlev][f_stride], [nlev][nsrc], [nlev][nsrc]; order 1 reads data alone
+  const int *grad_mask;                      // [nlev][nsrc]; null: no mask bits are staged and the kernels get none
+  const double *rec;                         // [nsrc][3][8], as k_merge3 writes them
+  const unsigned char *maskbits;             // [nsrc]
+  double *b8;                                // the limiter's bounds [nsrc][4][8], rows 0 / 1 filled (fg_c2l_records_levels_mono)
+  long field_area_ld;                        // != 0: the options' field_area is [nlev][field_area_ld]
+};
+static LevelSrc src_records(const double *rec, const unsigned char *maskbits, double *b8)    // (arrays: LevelSrc{data, gx, gy, gm})
 {
-  if (want_il) { int rc = ensure_il_scratch(pl, false); if (rc) return rc; }
-  if (want_il && pl->order == 2 && !pl->lv_bits) {
-    pl->lv_bits = pl->alloc<unsigned char>(pl->nsrc > 0 ? pl->nsrc : 1);
-    if (!pl->lv_bits) return fg_fail(FG_ERR_HIP, "out of device memory");
+  return LevelSrc{nullptr, nullptr, nullptr, nullptr, rec, maskbits, b8, 0};
+}
+
+// what the kernels of a chunk read
+struct Chunk { const double *rec; const unsigned char *bits; const double *fa8; };
+
+// levels [k0, k0 + nbv) of s, padded to eight: records stay the caller's; level-major arrays go through k_merge3 (and k_gmask_bits)
+// into il_m (lv_bits), a first-order field into il_f; per-level areas into lx_fa
+static Chunk stage_chunk(fg_plan *pl, const LevelSrc &s, const double *field_area, int k0, int nbv, hipStream_t st)
+{
+  Chunk c{s.rec, s.maskbits, nullptr};
+  if (s.field_area_ld) {
+    fgd_interleave(8, pl->nsrc, field_area + (size_t)k0 * s.field_area_ld, s.field_area_ld, nbv, pl->lx_fa, st);
+    c.fa8 = pl->lx_fa;
   }
-  return want_rs ? ensure_il_rs(pl) : 0;
+  if (s.rec) return c;
+  const double *f = s.data + (size_t)k0 * pl->f_stride;
+  const size_t g = (size_t)k0 * pl->nsrc;
+  if (pl->order == 2) {
+    fgd_merge3(8, pl->nsrc, pl->src_idx_f, f, pl->f_stride, s.grad_x + g, s.grad_y + g, pl->nsrc, nbv, pl->il_m, st);
+    if (s.grad_mask) fgd_gmask_bits(pl->nsrc, s.grad_mask + g, pl->nsrc, nbv, pl->lv_bits, st);
+    c.rec = pl->il_m; c.bits = s.grad_mask ? pl->lv_bits : nullptr;
+  } else {
+    interleave_field(pl, f, 8, nbv, st);
+    c.rec = pl->il_f;
+  }
+  return c;
 }
 
 // per-level sums of one chunk (il_rs [level][ndst]) -> red_result, handed to the host whenever the 256 result slots are full
@@ -2245,58 +2357,68 @@ static int levels_gsum(fg_plan *pl, int nbv, int *nred, double **gsum_out, bool 
   return 0;
 }
 
+// A call: the device, the scratch it wants, the error word cleared (not queued, not the second half alone), then inside one PH_APPLY
+// span every chunk of up to eight levels -- staged, swept by the family's kernels, its per-level row sums reduced with the reduction
+// of the one-level calls -- and at the end the error word read (not queued, not the first half alone; the masked family has none,
+// so without gsum_out it returns without waiting for the device).  The entries see to it that records come with nlev <= 8 (one chunk),
+// that RUN_FIRST alone comes with out == gsum_out == nullptr, and that only the limiter is ever run by halves.
+static int run_levels(fg_plan *pl, int fam, const LevelSrc &s, const FgApplyEx &x, int nlev, double *out, double *gsum_out, unsigned flags)
+{
+  FGCHK(hipSetDevice(pl->device));
+  const bool arrays = !s.rec, queued = flags & RUN_QUEUED, first = flags & RUN_FIRST, second = flags & RUN_SECOND;
+  int rc = apply_scratch(pl, (arrays ? SC_IL | SC_BITS : 0) | (gsum_out ? SC_RS : 0) | (fam != FAM_MASKED ? SC_XERR : 0) |
+                               (s.field_area_ld ? SC_FA8 : 0) | (fam == FAM_MONO && arrays ? SC_MONO8 : 0));
+  if (rc) return rc;
+  hipStream_t st = pl->stream;
+  const int ndst = pl->ndst;
+  double *rs = gsum_out ? pl->il_rs : nullptr, *b8 = arrays ? pl->mono8_b : s.b8;
+  if (fam != FAM_MASKED && first && !queued) FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
+  apply_span_begin(pl, st);
+  int nred = 0;
+  for (int k0 = 0; k0 < nlev && !rc; k0 += 8) {
+    const int nbv = std::min(8, nlev - k0);
+    const Chunk c = stage_chunk(pl, s, x.field_area, k0, nbv, st);
+    double *o = out + (size_t)k0 * ndst;
+    if (fam == FAM_MASKED)
+      fgd_apply_levels8(pl->order, ndst, pl->nx, pl->csr, c.rec, c.bits, x.missing, o, rs, (long)ndst, nbv, st);
+    else if (fam == FAM_EX)
+      fgd_apply_levels8x(pl->order, ndst, pl->nx, pl->csr, c.rec, c.bits, x, c.fa8, o, rs, (long)ndst, nbv, pl->xerr, st);
+    else {
+      if (first && arrays)
+        fgd_mono_bounds8(pl->tiles_dev, pl->ntiles, pl->nsrc, pl->src_idx_f, s.data + (size_t)k0 * pl->f_stride, pl->f_stride, nbv, x.missing,
+                         b8, st);
+      if (first) fgd_mono_extremes8(pl->nx, pl->csr, c.rec, c.bits, x.missing, nbv, b8, st);
+      if (second) fgd_apply_levels8m(ndst, pl->nx, pl->csr, c.rec, c.bits, b8, x, o, rs, (long)ndst, nbv, pl->xerr, st);
+    }
+    if (gsum_out) rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev);
+  }
+  apply_span_end(pl);                                      // on every path
+  if (rc) return rc;
+  FGCHK(hipGetLastError());
+  return (fam == FAM_MASKED || queued || !second) ? 0 : ex_error_word(pl);
+}
+
+// levels with missing values of their own: gsum_out[k] carries the bits fg_plan_apply_ex returns for level k alone
 extern "C" int fg_plan_apply_levels(fg_plan *pl, const double *data, const double *grad_x, const double *grad_y,
                                     const int *grad_mask, double missing, int nlev, double *out, double *gsum_out)
 {
-  if (!pl || !data || !out) return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: null argument");
-  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: the plan is not finalized (fg_plan_finalize)");
-  if (nlev < 1) return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: nlev must be >= 1");
-  if (pl->order == 2 && (!grad_x || !grad_y || !grad_mask))
-    return fg_fail(FG_ERR_ARG, "fg_plan_apply_levels: order 2 needs grad_x, grad_y and grad_mask [nlev][ncells_in]");
-  FGCHK(hipSetDevice(pl->device));
-  { int rc = levels_scratch(pl, gsum_out != nullptr, true); if (rc) return rc; }
-  hipStream_t st = pl->stream;
-  const int ndst = pl->ndst;
-  apply_span_begin(pl, st);
-  int nred = 0;
-  for (int k0 = 0; k0 < nlev; k0 += 8) {
-    const int nbv = (nlev - k0 < 8) ? nlev - k0 : 8;
-    const double *f = data + (size_t)k0 * pl->f_stride;
-    double *o = out + (size_t)k0 * ndst;
-    double *rs = gsum_out ? pl->il_rs : nullptr;
-    if (pl->order == 2) {
-      fgd_merge3(8, pl->nsrc, pl->src_idx_f, f, pl->f_stride, grad_x + (size_t)k0 * pl->nsrc, grad_y + (size_t)k0 * pl->nsrc, pl->nsrc,
-                 nbv, pl->il_m, st);
-      fgd_gmask_bits(pl->nsrc, grad_mask + (size_t)k0 * pl->nsrc, pl->nsrc, nbv, pl->lv_bits, st);
-      fgd_apply_levels8(2, ndst, pl->nx, pl->csr, pl->il_m, pl->lv_bits, missing, o, rs, (long)ndst, nbv, st);
-    } else {
-      interleave_field(pl, f, 8, nbv, st);
-      fgd_apply_levels8(1, ndst, pl->nx, pl->csr, pl->il_f, nullptr, missing, o, rs, (long)ndst, nbv, st);
-    }
-    if (gsum_out) { int rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
-  }
-  apply_span_end(pl);
-  FGCHK(hipGetLastError());
-  return 0;
+  if (int rc = levels_check("fg_plan_apply_levels", pl, nullptr, CK_NLEV | CK_GRADS_MASK, !pl || !data || !out, false, nlev, 0,
+                            grad_x && grad_y, grad_mask))
+    return rc;
+  FgApplyEx x{};
+  x.missing = missing;
+  return run_levels(pl, FAM_MASKED, LevelSrc{data, grad_x, grad_y, grad_mask}, x, nlev, out, gsum_out, RUN_BOTH);
 }
 
 extern "C" int fg_plan_apply_records_levels(fg_plan *pl, int nz, const double *rec, const unsigned char *maskbits, double missing,
                                             double *out, double *gsum_out)
 {
-  if (!pl || !rec || !out) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: null argument");
-  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: the plan is not finalized (fg_plan_finalize)");
-  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: records carry gradients, the plan is first order");
-  if (!maskbits) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: order 2 needs the gradient-mask bits");
-  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "fg_plan_apply_records_levels: 1 to 8 levels per call");
-  FGCHK(hipSetDevice(pl->device));
-  { int rc = levels_scratch(pl, gsum_out != nullptr, false); if (rc) return rc; }
-  hipStream_t st = pl->stream;
-  apply_span_begin(pl, st);
-  fgd_apply_levels8(2, pl->ndst, pl->nx, pl->csr, rec, maskbits, missing, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, st);
-  apply_span_end(pl);
-  if (gsum_out) { int nred = 0; int rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
-  FGCHK(hipGetLastError());
-  return 0;
+  if (int rc = levels_check("fg_plan_apply_records_levels", pl, nullptr, CK_RECORDS | CK_BITS | CK_NZ8, !pl || !rec || !out, false, nz, 0,
+                            false, maskbits))
+    return rc;
+  FgApplyEx x{};
+  x.missing = missing;
+  return run_levels(pl, FAM_MASKED, src_records(rec, maskbits, nullptr), x, nz, out, gsum_out, RUN_BOTH);
 }
 
 // ------------------------------------------------------------------- the sweep with every option
@@ -2309,48 +2431,7 @@ static int ex_check(fg_plan *pl, const fg_apply_opts *o, const double *data, con
   if (nz > 1 && o->field_area) return fg_fail(FG_ERR_ARG, "conserve_interp: cell_measures should be false when nz > 1");
   if (nz > 1 && o->cell_methods_sum) return fg_fail(FG_ERR_ARG, "conserve_interp: cell_methods should not be sum when nz > 1");
   if (pl->order == 2 && (!gx || !gy)) return fg_fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
-  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
-    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
-  return 0;
-}
-
-static int ex_error_word(fg_plan *pl)
-{
-  int e = 0;
-  FGCHK(hipMemcpyAsync(&e, pl->xerr, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
-  FGCHK(hipStreamSynchronize(pl->stream));
-  if (e & FG_XERR_AREA_MISSING) return fg_fail(FG_ERR_DATA, "conserve_interp: data is not missing but area is missing");
-  if (e & FG_XERR_ABOVE) return fg_fail(FG_ERR_DATA, " xdata is greater than f_bar_max ");
-  if (e & FG_XERR_BELOW) return fg_fail(FG_ERR_DATA, " xdata is less than f_bar_min ");
-  return 0;
-}
-
-static int ex_scratch(fg_plan *pl, bool mono)
-{
-  if (!pl->xerr) { pl->xerr = pl->alloc<int>(4); if (!pl->xerr) return fg_fail(FG_ERR_HIP, "out of device memory"); }
-  if (pl->row_sum_cap < pl->ndst) {
-    pl->release(pl->row_sum);
-    pl->row_sum = pl->alloc<double>(pl->ndst);
-    if (!pl->row_sum) { pl->row_sum_cap = 0; return fg_fail(FG_ERR_HIP, "out of device memory"); }
-    pl->row_sum_cap = pl->ndst;
-  }
-  if (mono && !pl->mono_x) {
-    pl->mono_x = pl->alloc<double>(pl->nx > 0 ? pl->nx : 1);
-    pl->mono_b = pl->alloc<double>((size_t)pl->nsrc * 4);
-    if (!pl->mono_x || !pl->mono_b) return fg_fail(FG_ERR_HIP, "out of device memory");
-  }
-  return 0;
-}
-
-static FgApplyEx ex_pack(fg_plan *pl, const fg_apply_opts *o, const int *gmask)
-{
-  FgApplyEx x{};
-  x.weight = o->weight; x.field_area = o->field_area; x.cell_area_out = o->cell_methods_sum ? nullptr : o->cell_area_out;
-  x.cell_area = o->cell_area_in ? o->cell_area_in : (pl->have_geom ? pl->S.area : nullptr);
-  x.gmask = gmask; x.area_missing = o->area_missing;
-  x.has_missing = o->has_missing; x.missing = o->has_missing ? o->missing : -1.e20;   // conserve_interp.c:541-542
-  x.sum = o->cell_methods_sum;
-  return x;
+  return area_rule(who, pl, o);
 }
 
 extern "C" int fg_plan_mono_begin(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x,
@@ -2360,7 +2441,7 @@ extern "C" int fg_plan_mono_begin(fg_plan *pl, const fg_apply_opts *o, const dou
   if (rc) return rc;
   if (pl->order != 2) return fg_fail(FG_ERR_ARG, "the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)");
   FGCHK(hipSetDevice(pl->device));
-  if ((rc = ex_scratch(pl, true))) return rc;
+  if ((rc = apply_scratch(pl, SC_XERR | SC_ROW_SUM | SC_MONO))) return rc;
   const double miss = o->has_missing ? o->missing : -1.e20;
   double *b = pl->mono_b;
   const size_t n = pl->nsrc;
@@ -2425,7 +2506,7 @@ extern "C" int fg_plan_apply_ex(fg_plan *pl, const fg_apply_opts *o, const doubl
     return fg_plan_mono_end(pl, o, data, out, gsum_out);
   }
   FGCHK(hipSetDevice(pl->device));
-  if ((rc = ex_scratch(pl, false))) return rc;
+  if ((rc = apply_scratch(pl, SC_XERR | SC_ROW_SUM))) return rc;
   if (nz > 256) return fg_fail(FG_ERR_ARG, "nz too large for one call (max 256 levels)");
   hipStream_t st = pl->stream;
   FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
@@ -2448,122 +2529,41 @@ extern "C" int fg_plan_apply_ex(fg_plan *pl, const fg_apply_opts *o, const doubl
   return ex_error_word(pl);
 }
 
-// ------------------------------------------------------------------- the level loop of these options, eight levels per launch
+// ------------------------------------------------------------------- the level loop of these options (the ex family)
 // fg_plan_apply_ex(nz = 1) per level is what the reference does for weight / sum / cell_measures / --target_grid fields
-// (conserve_interp.c:544-546 refuse nz > 1, fregrid.c:1045-1083 loop); here eight levels share a launch of k_apply_ep8x and level k
-// keeps the bits of that one-level call, its sum included (reduced per level as levels_gsum does).  No limiter.
+// (conserve_interp.c:544-546 refuse nz > 1).  Mask bits are staged and read only for an order-2 field with missing values.
 extern "C" int fg_plan_levels_ex_capacity(int per_level_area) { return per_level_area ? FG_LEVELS_EX_CAP_Z : FG_LEVELS_EX_CAP; }
 
-static int levels_ex_check(fg_plan *pl, const fg_apply_opts *o, const void *data, const void *out, long field_area_ld, const char *who)
-{
-  if (!pl || !o || !data || !out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "%s: the plan is not finalized (fg_plan_finalize)", who);
-  if (o->monotonic) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter works on one level per call (fg_plan_apply_ex)", who);
-  if (field_area_ld != 0 && field_area_ld != pl->nsrc)
-    return fg_fail(FG_ERR_ARG, "%s: field_area_ld must be 0 (one area for all levels) or ncells_in (an area per level)", who);
-  if (field_area_ld != 0 && !o->field_area) return fg_fail(FG_ERR_ARG, "%s: field_area_ld is set but opts->field_area is NULL", who);
-  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
-    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
-  return 0;
-}
-
-// scratch of a call; fa8: the chunk's per-level area interleaved [source cell][8]
-static int levels_ex_scratch(fg_plan *pl, bool want_rs, bool want_il, bool want_fa8)
-{
-  int rc = levels_scratch(pl, want_rs, want_il);
-  if (rc) return rc;
-  if (!pl->xerr) { pl->xerr = pl->alloc<int>(4); if (!pl->xerr) return fg_fail(FG_ERR_HIP, "out of device memory"); }
-  if (want_fa8 && !pl->lx_fa) {
-    pl->lx_fa = pl->alloc<double>((size_t)(pl->nsrc > 0 ? pl->nsrc : 1) * 8);
-    if (!pl->lx_fa) return fg_fail(FG_ERR_HIP, "out of device memory");
-  }
-  return 0;
-}
-
-// the options as the kernel takes them; cell_methods = sum uses no field_area (:582-588 is the else branch)
-static FgApplyEx levels_ex_pack(fg_plan *pl, const fg_apply_opts *o, bool *per_level, long field_area_ld)
+// the options as the many-level kernels take them; cell_methods = sum uses no field_area (:582-588 is the else branch)
+static FgApplyEx levels_ex_pack(fg_plan *pl, const fg_apply_opts *o)
 {
   FgApplyEx x = ex_pack(pl, o, nullptr);
   if (x.sum) x.field_area = nullptr;
-  *per_level = field_area_ld != 0 && x.field_area != nullptr;
   return x;
 }
 
-// queued (the streamed sweep, fg_sweep_run_levels_ex): the error word is neither cleared nor read here, so that the host does not wait
-// for the chunk -- fg_plan_levels_ex_begin clears it before the first chunk, fg_plan_levels_ex_end reads it after the last
-static int levels_ex_run(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
-                         const int *grad_mask, int nlev, long field_area_ld, double *out, double *gsum_out, bool queued)
+static int levels_ex_run(fg_plan *pl, const fg_apply_opts *o, bool records, LevelSrc s, int nlev, long field_area_ld, double *out,
+                         double *gsum_out, unsigned queued)
 {
-  const char *who = "fg_plan_apply_levels_ex";
-  int rc = levels_ex_check(pl, o, data, out, field_area_ld, who);
-  if (rc) return rc;
-  if (nlev < 1) return fg_fail(FG_ERR_ARG, "%s: nlev must be >= 1", who);
-  if (pl->order == 2 && (!grad_x || !grad_y)) return fg_fail(FG_ERR_ARG, "%s: order 2 needs grad_x and grad_y [nlev][ncells_in]", who);
-  FGCHK(hipSetDevice(pl->device));
-  bool per_level;
-  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, field_area_ld);
-  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, true, per_level))) return rc;
-  hipStream_t st = pl->stream;
-  const int ndst = pl->ndst;
-  const bool masks = pl->order == 2 && o->has_missing && grad_mask;
-  if (!queued) FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
-  apply_span_begin(pl, st);
-  int nred = 0;
-  for (int k0 = 0; k0 < nlev; k0 += 8) {
-    const int nbv = (nlev - k0 < 8) ? nlev - k0 : 8;
-    const double *f = data + (size_t)k0 * pl->f_stride;
-    double *rs = gsum_out ? pl->il_rs : nullptr;
-    if (per_level) fgd_interleave(8, pl->nsrc, x.field_area + (size_t)k0 * field_area_ld, field_area_ld, nbv, pl->lx_fa, st);
-    if (pl->order == 2) {
-      fgd_merge3(8, pl->nsrc, pl->src_idx_f, f, pl->f_stride, grad_x + (size_t)k0 * pl->nsrc, grad_y + (size_t)k0 * pl->nsrc, pl->nsrc,
-                 nbv, pl->il_m, st);
-      if (masks) fgd_gmask_bits(pl->nsrc, grad_mask + (size_t)k0 * pl->nsrc, pl->nsrc, nbv, pl->lv_bits, st);
-    } else
-      interleave_field(pl, f, 8, nbv, st);
-    fgd_apply_levels8x(pl->order, ndst, pl->nx, pl->csr, pl->order == 2 ? pl->il_m : pl->il_f, masks ? pl->lv_bits : nullptr, x,
-                       per_level ? pl->lx_fa : nullptr, out + (size_t)k0 * ndst, rs, (long)ndst, nbv, pl->xerr, st);
-    if (gsum_out) { rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
-  }
-  apply_span_end(pl);
-  FGCHK(hipGetLastError());
-  return queued ? 0 : ex_error_word(pl);
+  if (int rc = levels_check(records ? "fg_plan_apply_records_levels_ex" : "fg_plan_apply_levels_ex", pl, o,
+                            CK_NO_LIMITER | CK_FA_LD | CK_AREA | (records ? CK_RECORDS | CK_NZ8 | CK_BITS_IF_MISSING : CK_NLEV | CK_GRADS),
+                            !pl || !o || !(records ? s.rec : s.data) || !out, false, nlev, field_area_ld, s.grad_x && s.grad_y, s.maskbits))
+    return rc;
+  const FgApplyEx x = levels_ex_pack(pl, o);
+  s.field_area_ld = x.field_area ? field_area_ld : 0;
+  if (!o->has_missing || pl->order != 2) s.grad_mask = nullptr, s.maskbits = nullptr;
+  return run_levels(pl, FAM_EX, s, x, nlev, out, gsum_out, RUN_BOTH | queued);
 }
 
 extern "C" int fg_plan_apply_levels_ex(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
                                        const int *grad_mask, int nlev, long field_area_ld, double *out, double *gsum_out)
 {
-  return levels_ex_run(pl, o, data, grad_x, grad_y, grad_mask, nlev, field_area_ld, out, gsum_out, false);
+  return levels_ex_run(pl, o, false, LevelSrc{data, grad_x, grad_y, grad_mask}, nlev, field_area_ld, out, gsum_out, 0);
 }
-
-static int records_levels_ex_run(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
-                                 long field_area_ld, double *out, double *gsum_out, bool queued)
-{
-  const char *who = "fg_plan_apply_records_levels_ex";
-  int rc = levels_ex_check(pl, o, rec, out, field_area_ld, who);
-  if (rc) return rc;
-  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: records carry gradients, the plan is first order", who);
-  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per call", who);
-  if (o->has_missing && !maskbits) return fg_fail(FG_ERR_ARG, "%s: a field with missing values needs the gradient-mask bits", who);
-  FGCHK(hipSetDevice(pl->device));
-  bool per_level;
-  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, field_area_ld);
-  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, false, per_level))) return rc;
-  hipStream_t st = pl->stream;
-  if (!queued) FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
-  apply_span_begin(pl, st);
-  if (per_level) fgd_interleave(8, pl->nsrc, x.field_area, field_area_ld, nz, pl->lx_fa, st);
-  fgd_apply_levels8x(2, pl->ndst, pl->nx, pl->csr, rec, o->has_missing ? maskbits : nullptr, x, per_level ? pl->lx_fa : nullptr, out,
-                     gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, pl->xerr, st);
-  apply_span_end(pl);
-  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
-  FGCHK(hipGetLastError());
-  return queued ? 0 : ex_error_word(pl);
-}
-
 extern "C" int fg_plan_apply_records_levels_ex(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
                                                long field_area_ld, double *out, double *gsum_out)
 {
-  return records_levels_ex_run(pl, o, nz, rec, maskbits, field_area_ld, out, gsum_out, false);
+  return levels_ex_run(pl, o, true, src_records(rec, maskbits, nullptr), nz, field_area_ld, out, gsum_out, 0);
 }
 
 // for sweep.hip: the chunks of one streamed run, queued on the plan's (borrowed) stream between _begin and _end
@@ -2571,121 +2571,66 @@ int fg_plan_levels_ex_begin(fg_plan *pl)
 {
   if (!pl) return fg_fail(FG_ERR_ARG, "null argument");
   FGCHK(hipSetDevice(pl->device));
-  if (!pl->xerr) { pl->xerr = pl->alloc<int>(4); if (!pl->xerr) return fg_fail(FG_ERR_HIP, "out of device memory"); }
+  if (int rc = apply_scratch(pl, SC_XERR)) return rc;
   FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
   return 0;
 }
 int fg_plan_levels_ex_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const double *data, const double *rec, const unsigned char *maskbits,
                             double *out)
 {
-  return rec ? records_levels_ex_run(pl, o, nz, rec, maskbits, 0, out, nullptr, true)
-             : levels_ex_run(pl, o, data, nullptr, nullptr, nullptr, nz, 0, out, nullptr, true);
+  return levels_ex_run(pl, o, rec != nullptr, rec ? src_records(rec, maskbits, nullptr) : LevelSrc{data}, nz, 0, out, nullptr, RUN_QUEUED);
 }
 int fg_plan_levels_ex_end(fg_plan *pl) { return ex_error_word(pl); }
 
-// ------------------------------------------------------------------- the level loop of the monotone sweep, eight levels per launch
-// fg_plan_apply_ex(monotonic = 1, nz = 1) per level is what the reference does (conserve_interp.c:648-651 index level 0 only,
-// fregrid.c:1045-1083 loop): four launches, an xdata array written and read again and three reads of every CSR record per level.
-// Here a chunk of eight levels takes k_merge3, k_gmask_bits and three launches -- k_mono_bounds8, k_mono_extremes8, k_apply_ep8m --
-// split between the second and the third at the reference's mpp_min_double / mpp_max_double (:672-677).
-static int mono_levels_check(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *gx, const double *gy, const char *who)
+// ------------------------------------------------------------------- the limiter on many levels (the mono family)
+// fg_plan_apply_ex(monotonic = 1, nz = 1) per level is what the reference does (conserve_interp.c:648-651 index level 0 only):
+// four launches, an xdata array written and read again and three reads of every CSR record per level.  Mask bits are staged when
+// grad_mask is given.  mono8_nz: the levels of the chunk fg_plan_mono_levels_begin left open, 0 for none.  The records entries work
+// on what fg_c2l_records_levels_mono wrote -- rec, maskbits and b8 with rows 0 / 1 filled, rows 2 / 3 at their start values -- so a
+// chunk is k_mono_extremes8 and k_apply_ep8m straight on the caller's buffers; b8 is consumed: the extremes go into its rows 2 and 3.
+// mono8r_nz / mono8r_b: the levels and the caller's bounds buffer of the chunk fg_plan_mono_records_begin left open.
+// the rules all six entries share, with the entry's rule on the number of levels; level-major arrays come with mandatory gradients
+static int mono_check(const char *who, const fg_plan *pl, const fg_apply_opts *o, bool records, const LevelSrc &s, unsigned nz_rule, bool null_late,
+                      int nlev)
 {
-  if (!pl || !o || !data || !gx || !gy) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "%s: the plan is not finalized (fg_plan_finalize)", who);
-  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)", who);
-  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
-    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
-  return 0;
-}
-
-// scratch of one chunk, whatever the number of levels of the call
-static int mono_levels_scratch(fg_plan *pl, bool want_rs)
-{
-  int rc = levels_ex_scratch(pl, want_rs, true, false);
-  if (rc) return rc;
-  if (!pl->mono8_b) {
-    pl->mono8_b = pl->alloc<double>((size_t)(pl->nsrc > 0 ? pl->nsrc : 1) * 32);
-    if (!pl->mono8_b) return fg_fail(FG_ERR_HIP, "out of device memory");
-  }
-  return 0;
-}
-
-// records and mask bits of a chunk of nz levels
-static void mono_levels_stage(fg_plan *pl, const double *data, const double *gx, const double *gy, const int *gm, int nz, hipStream_t st)
-{
-  fgd_merge3(8, pl->nsrc, pl->src_idx_f, data, pl->f_stride, gx, gy, pl->nsrc, nz, pl->il_m, st);
-  if (gm) fgd_gmask_bits(pl->nsrc, gm, pl->nsrc, nz, pl->lv_bits, st);
-}
-// :622-669 of the chunk
-static void mono_levels_first(fg_plan *pl, double miss, const double *data, const double *gx, const double *gy, const int *gm, int nz,
-                              hipStream_t st)
-{
-  mono_levels_stage(pl, data, gx, gy, gm, nz, st);
-  fgd_mono_bounds8(pl->tiles_dev, pl->ntiles, pl->nsrc, pl->src_idx_f, data, pl->f_stride, nz, miss, pl->mono8_b, st);
-  fgd_mono_extremes8(pl->nx, pl->csr, pl->il_m, gm ? pl->lv_bits : nullptr, miss, nz, pl->mono8_b, st);
-}
-// :679-866 of the chunk, on the records and bits staged for it
-static void mono_levels_second(fg_plan *pl, const FgApplyEx &x, bool masks, int nz, double *out, bool want_rs, hipStream_t st)
-{
-  fgd_apply_levels8m(pl->ndst, pl->nx, pl->csr, pl->il_m, masks ? pl->lv_bits : nullptr, pl->mono8_b, x, out, want_rs ? pl->il_rs : nullptr,
-                     (long)pl->ndst, nz, pl->xerr, st);
+  const bool null_arg = !pl || !o || (records ? !s.rec : !s.data || !s.grad_x || !s.grad_y);
+  return levels_check(who, pl, o, CK_LIMITER | CK_AREA | nz_rule, null_arg, null_late, nlev, 0, true, true);
 }
 
 extern "C" int fg_plan_apply_levels_mono(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
                                          const int *grad_mask, int nlev, double *out, double *gsum_out)
 {
-  const char *who = "fg_plan_apply_levels_mono";
-  int rc = mono_levels_check(pl, o, data, grad_x, grad_y, who);
-  if (rc) return rc;
-  if (!out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (nlev < 1) return fg_fail(FG_ERR_ARG, "%s: nlev must be >= 1", who);
-  FGCHK(hipSetDevice(pl->device));
-  if ((rc = mono_levels_scratch(pl, gsum_out != nullptr))) return rc;
-  bool per_level;
-  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
-  hipStream_t st = pl->stream;
+  const LevelSrc s{data, grad_x, grad_y, grad_mask};
+  if (int rc = mono_check("fg_plan_apply_levels_mono", pl, o, false, s, CK_NLEV, !out, nlev)) return rc;
   pl->mono8_nz = 0;                                        // an open chunk of the split entries is overwritten
-  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
-  apply_span_begin(pl, st);
-  int nred = 0;
-  for (int k0 = 0; k0 < nlev; k0 += 8) {
-    const int nbv = (nlev - k0 < 8) ? nlev - k0 : 8;
-    const int *gm = grad_mask ? grad_mask + (size_t)k0 * pl->nsrc : nullptr;
-    mono_levels_first(pl, x.missing, data + (size_t)k0 * pl->f_stride, grad_x + (size_t)k0 * pl->nsrc, grad_y + (size_t)k0 * pl->nsrc, gm,
-                      nbv, st);
-    mono_levels_second(pl, x, gm != nullptr, nbv, out + (size_t)k0 * pl->ndst, gsum_out != nullptr, st);
-    if (gsum_out) { rc = levels_gsum(pl, nbv, &nred, &gsum_out, k0 + 8 >= nlev); if (rc) return rc; }
-  }
-  apply_span_end(pl);
-  FGCHK(hipGetLastError());
-  return ex_error_word(pl);                                // once, after the last chunk
+  return run_levels(pl, FAM_MONO, s, levels_ex_pack(pl, o), nlev, out, gsum_out, RUN_BOTH);
 }
 
 extern "C" int fg_plan_mono_levels_begin(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x,
                                          const double *grad_y, const int *grad_mask, int nz)
 {
-  const char *who = "fg_plan_mono_levels_begin";
-  int rc = mono_levels_check(pl, o, data, grad_x, grad_y, who);
-  if (rc) return rc;
-  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per begin / end pair", who);
-  FGCHK(hipSetDevice(pl->device));
-  if ((rc = mono_levels_scratch(pl, false))) return rc;
-  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
-  mono_levels_first(pl, o->has_missing ? o->missing : -1.e20, data, grad_x, grad_y, grad_mask, nz, pl->stream);
-  FGCHK(hipGetLastError());
-  pl->mono8_nz = nz;
-  return 0;
+  const LevelSrc s{data, grad_x, grad_y, grad_mask};
+  if (int rc = mono_check("fg_plan_mono_levels_begin", pl, o, false, s, CK_NZ8_PAIR, false, nz)) return rc;
+  int rc = run_levels(pl, FAM_MONO, s, levels_ex_pack(pl, o), nz, nullptr, nullptr, RUN_FIRST);
+  if (!rc) pl->mono8_nz = nz;
+  return rc;
 }
 
-extern "C" int fg_plan_mono_levels_copy_minmax(fg_plan *pl, int to_plan, double *f_min, double *f_max)
+// f_max / f_min of the open chunk (nz levels, bounds b8) out of (to_plan = 0) or back into it; synchronises the plan's stream
+static int mono8_copy_minmax(const char *who, const char *begin, fg_plan *pl, int nz, double *b8, int to_plan, double *f_min, double *f_max)
 {
-  if (!pl || !f_min || !f_max) return fg_fail(FG_ERR_ARG, "fg_plan_mono_levels_copy_minmax: null argument");
-  if (!pl->mono8_nz) return fg_fail(FG_ERR_STATE, "fg_plan_mono_levels_copy_minmax: call fg_plan_mono_levels_begin first");
+  if (!pl || !f_min || !f_max) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
+  if (!nz) return fg_fail(FG_ERR_STATE, "%s: call %s first", who, begin);
   FGCHK(hipSetDevice(pl->device));
-  fgd_mono_minmax8(pl->nsrc, pl->mono8_nz, to_plan ? 1 : 0, pl->mono8_b, f_min, f_max, pl->stream);
+  fgd_mono_minmax8(pl->nsrc, nz, to_plan ? 1 : 0, b8, f_min, f_max, pl->stream);
   FGCHK(hipGetLastError());
   FGCHK(hipStreamSynchronize(pl->stream));
   return 0;
+}
+extern "C" int fg_plan_mono_levels_copy_minmax(fg_plan *pl, int to_plan, double *f_min, double *f_max)
+{
+  return mono8_copy_minmax("fg_plan_mono_levels_copy_minmax", "fg_plan_mono_levels_begin", pl, pl ? pl->mono8_nz : 0, pl ? pl->mono8_b : nullptr,
+                           to_plan, f_min, f_max);
 }
 
 // The records and bits are staged again from the caller's arrays: il_m and lv_bits are the scratch of every many-level entry, and
@@ -2693,76 +2638,32 @@ extern "C" int fg_plan_mono_levels_copy_minmax(fg_plan *pl, int to_plan, double 
 extern "C" int fg_plan_mono_levels_end(fg_plan *pl, const fg_apply_opts *o, const double *data, const double *grad_x, const double *grad_y,
                                        const int *grad_mask, double *out, double *gsum_out)
 {
-  const char *who = "fg_plan_mono_levels_end";
-  int rc = mono_levels_check(pl, o, data, grad_x, grad_y, who);
-  if (rc) return rc;
-  if (!out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (!pl->mono8_nz) return fg_fail(FG_ERR_STATE, "%s: call fg_plan_mono_levels_begin first", who);
-  FGCHK(hipSetDevice(pl->device));
-  if ((rc = mono_levels_scratch(pl, gsum_out != nullptr))) return rc;
+  const LevelSrc s{data, grad_x, grad_y, grad_mask};
+  if (int rc = mono_check("fg_plan_mono_levels_end", pl, o, false, s, 0, !out, 1)) return rc;
+  if (!pl->mono8_nz) return fg_fail(FG_ERR_STATE, "fg_plan_mono_levels_end: call fg_plan_mono_levels_begin first");
   const int nz = pl->mono8_nz;
   pl->mono8_nz = 0;
-  bool per_level;
-  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
-  hipStream_t st = pl->stream;
-  apply_span_begin(pl, st);
-  mono_levels_stage(pl, data, grad_x, grad_y, grad_mask, nz, st);
-  mono_levels_second(pl, x, grad_mask != nullptr, nz, out, gsum_out != nullptr, st);
-  apply_span_end(pl);
-  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
-  FGCHK(hipGetLastError());
-  return ex_error_word(pl);
+  return run_levels(pl, FAM_MONO, s, levels_ex_pack(pl, o), nz, out, gsum_out, RUN_SECOND);
 }
 
-// ------------------------------------------------------------------- the limiter on the gradient object's records
-// fg_c2l_records_levels_mono writes what mono_levels_stage and k_mono_bounds8 produce for a chunk -- rec, maskbits and b8 with rows
-// 0 / 1 filled, rows 2 / 3 at their start values -- so a chunk is k_mono_extremes8 and k_apply_ep8m straight on the caller's buffers:
-// no k_merge3, no k_gmask_bits, no bounds launch, no halo'd copy.  b8 is consumed: the extremes go into its rows 2 and 3.
-static int mono_records_check(fg_plan *pl, const fg_apply_opts *o, const double *rec, const char *who)
-{
-  if (!pl || !o || !rec) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (!pl->finalized) return fg_fail(FG_ERR_ARG, "%s: the plan is not finalized (fg_plan_finalize)", who);
-  if (pl->order != 2) return fg_fail(FG_ERR_ARG, "%s: the monotone limiter belongs to conserve_order2 (conserve_interp.c:527-531)", who);
-  if ((o->cell_methods_sum || o->field_area) && !o->cell_area_in && !pl->have_geom)
-    return fg_fail(FG_ERR_ARG, "%s: cell_area_in is required (this plan was loaded from a remap file and holds no cell areas)", who);
-  return 0;
-}
-
-// queued (the streamed sweep, fg_sweep_run_levels_mono): the error word is neither cleared nor read here, see levels_ex_run
 static int mono_records_run(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits, double *b8,
-                            double *out, double *gsum_out, bool queued)
+                            double *out, double *gsum_out, unsigned queued)
 {
-  const char *who = "fg_plan_apply_records_levels_mono";
-  int rc = mono_records_check(pl, o, rec, who);
-  if (rc) return rc;
-  if (!b8 || !out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per call", who);
-  FGCHK(hipSetDevice(pl->device));
-  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, false, false))) return rc;
-  bool per_level;
-  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
-  hipStream_t st = pl->stream;
+  const LevelSrc s = src_records(rec, maskbits, b8);
+  if (int rc = mono_check("fg_plan_apply_records_levels_mono", pl, o, true, s, CK_NZ8, !b8 || !out, nz)) return rc;
   pl->mono8r_nz = 0;                                       // as fg_plan_apply_levels_mono closes an open chunk of its split
-  if (!queued) FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), st));
-  apply_span_begin(pl, st);
-  fgd_mono_extremes8(pl->nx, pl->csr, rec, maskbits, x.missing, nz, b8, st);
-  fgd_apply_levels8m(pl->ndst, pl->nx, pl->csr, rec, maskbits, b8, x, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz, pl->xerr, st);
-  apply_span_end(pl);
-  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
-  FGCHK(hipGetLastError());
-  return queued ? 0 : ex_error_word(pl);
+  return run_levels(pl, FAM_MONO, s, levels_ex_pack(pl, o), nz, out, gsum_out, RUN_BOTH | queued);
 }
-
 extern "C" int fg_plan_apply_records_levels_mono(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
                                                  double *b8, double *out, double *gsum_out)
 {
-  return mono_records_run(pl, o, nz, rec, maskbits, b8, out, gsum_out, false);
+  return mono_records_run(pl, o, nz, rec, maskbits, b8, out, gsum_out, 0);
 }
 // for sweep.hip: a chunk of one streamed run, between fg_plan_levels_ex_begin and _end
 int fg_plan_mono_records_chunk(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits, double *b8,
                                double *out)
 {
-  return mono_records_run(pl, o, nz, rec, maskbits, b8, out, nullptr, true);
+  return mono_records_run(pl, o, nz, rec, maskbits, b8, out, nullptr, RUN_QUEUED);
 }
 
 extern "C" int fg_plan_mono_records_reset(fg_plan *pl, double *b8)
@@ -2777,54 +2678,27 @@ extern "C" int fg_plan_mono_records_reset(fg_plan *pl, double *b8)
 extern "C" int fg_plan_mono_records_begin(fg_plan *pl, const fg_apply_opts *o, int nz, const double *rec, const unsigned char *maskbits,
                                           double *b8)
 {
-  const char *who = "fg_plan_mono_records_begin";
-  int rc = mono_records_check(pl, o, rec, who);
-  if (rc) return rc;
-  if (!b8) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (nz < 1 || nz > 8) return fg_fail(FG_ERR_ARG, "%s: 1 to 8 levels per begin / end pair", who);
-  FGCHK(hipSetDevice(pl->device));
-  if ((rc = levels_ex_scratch(pl, false, false, false))) return rc;
-  FGCHK(hipMemsetAsync(pl->xerr, 0, sizeof(int), pl->stream));
-  fgd_mono_extremes8(pl->nx, pl->csr, rec, maskbits, o->has_missing ? o->missing : -1.e20, nz, b8, pl->stream);
-  FGCHK(hipGetLastError());
-  pl->mono8r_nz = nz; pl->mono8r_b = b8;
-  return 0;
+  const LevelSrc s = src_records(rec, maskbits, b8);
+  if (int rc = mono_check("fg_plan_mono_records_begin", pl, o, true, s, CK_NZ8_PAIR, !b8, nz)) return rc;
+  int rc = run_levels(pl, FAM_MONO, s, levels_ex_pack(pl, o), nz, nullptr, nullptr, RUN_FIRST);
+  if (!rc) { pl->mono8r_nz = nz; pl->mono8r_b = b8; }
+  return rc;
 }
-
 extern "C" int fg_plan_mono_records_copy_minmax(fg_plan *pl, int to_plan, double *f_min, double *f_max)
 {
-  if (!pl || !f_min || !f_max) return fg_fail(FG_ERR_ARG, "fg_plan_mono_records_copy_minmax: null argument");
-  if (!pl->mono8r_nz) return fg_fail(FG_ERR_STATE, "fg_plan_mono_records_copy_minmax: call fg_plan_mono_records_begin first");
-  FGCHK(hipSetDevice(pl->device));
-  fgd_mono_minmax8(pl->nsrc, pl->mono8r_nz, to_plan ? 1 : 0, pl->mono8r_b, f_min, f_max, pl->stream);
-  FGCHK(hipGetLastError());
-  FGCHK(hipStreamSynchronize(pl->stream));
-  return 0;
+  return mono8_copy_minmax("fg_plan_mono_records_copy_minmax", "fg_plan_mono_records_begin", pl, pl ? pl->mono8r_nz : 0,
+                           pl ? pl->mono8r_b : nullptr, to_plan, f_min, f_max);
 }
 
 // rec and maskbits are the caller's, unchanged since begin; the bounds are the buffer begin was given
 extern "C" int fg_plan_mono_records_end(fg_plan *pl, const fg_apply_opts *o, const double *rec, const unsigned char *maskbits, double *out,
                                         double *gsum_out)
 {
-  const char *who = "fg_plan_mono_records_end";
-  int rc = mono_records_check(pl, o, rec, who);
-  if (rc) return rc;
-  if (!out) return fg_fail(FG_ERR_ARG, "%s: null argument", who);
-  if (!pl->mono8r_nz) return fg_fail(FG_ERR_STATE, "%s: call fg_plan_mono_records_begin first", who);
-  FGCHK(hipSetDevice(pl->device));
-  if ((rc = levels_ex_scratch(pl, gsum_out != nullptr, false, false))) return rc;
+  if (int rc = mono_check("fg_plan_mono_records_end", pl, o, true, src_records(rec, maskbits, nullptr), 0, !out, 1)) return rc;
+  if (!pl->mono8r_nz) return fg_fail(FG_ERR_STATE, "fg_plan_mono_records_end: call fg_plan_mono_records_begin first");
   const int nz = pl->mono8r_nz;
   pl->mono8r_nz = 0;
-  bool per_level;
-  const FgApplyEx x = levels_ex_pack(pl, o, &per_level, 0);
-  hipStream_t st = pl->stream;
-  apply_span_begin(pl, st);
-  fgd_apply_levels8m(pl->ndst, pl->nx, pl->csr, rec, maskbits, pl->mono8r_b, x, out, gsum_out ? pl->il_rs : nullptr, (long)pl->ndst, nz,
-                     pl->xerr, st);
-  apply_span_end(pl);
-  if (gsum_out) { int nred = 0; rc = levels_gsum(pl, nz, &nred, &gsum_out, true); if (rc) return rc; }
-  FGCHK(hipGetLastError());
-  return ex_error_word(pl);
+  return run_levels(pl, FAM_MONO, src_records(rec, maskbits, pl->mono8r_b), levels_ex_pack(pl, o), nz, out, gsum_out, RUN_SECOND);
 }
 
 // The sweep on fields the caller already keeps interleaved: data_il [F][nb], grad_x_il/grad_y_il [ncells_in][nb],
@@ -2837,7 +2711,7 @@ extern "C" int fg_plan_apply_interleaved(fg_plan *pl, int nb, const double *data
   if (nb != 2 && nb != 4 && nb != 8 && nb != 16) return fg_fail(FG_ERR_ARG, "nb must be 2, 4, 8 or 16");
   if (pl->order == 2 && (!grad_x_il || !grad_y_il)) return fg_fail(FG_ERR_ARG, "order 2 needs grad_x and grad_y");
   FGCHK(hipSetDevice(pl->device));
-  if (gsum_out) { int rc = ensure_il_scratch(pl, true); if (rc) return rc; }
+  { int rc = apply_scratch(pl, gsum_out ? SC_IL | SC_RS : 0); if (rc) return rc; }
   apply_span_begin(pl, pl->stream);
   fgd_apply_il(pl->order, nb, pl->ndst, pl->csr, data_il, grad_x_il, grad_y_il, -1.e20, out_il,
                gsum_out ? pl->il_rs : nullptr, 0, nb, pl->stream, pl->nx);
