@@ -27,7 +27,8 @@ mirrors the reference's call signatures:
   -- tools/make_topog/topog.c:355,551,687,830,878,987 (create_realistic_topog with filter_topo, process_topo and its adjustments)
 * ``CouplerMosaic`` / ``coupler_ocean_grid`` / ``coupler_xgrid``
   -- tools/make_coupler_mosaic/make_coupler_mosaic.c:841,1198,1743,2018,2466 (the ocean grid's southern row, the three exchange
-     grids, the per-cell sums and centroid distances, the masks)
+     grids, the per-cell sums and centroid distances, the masks; :1765 a nested atmosphere tile, :2976 the wave grid,
+     :3591 --check)
 
 There is NO CPU fallback: if the shared library is missing, or no HIP device is visible
 when a compute entry point is called, an exception is raised.

@@ -73,6 +73,8 @@ EXPORTS = [
     "fg_topog_phase_ms", "fg_plan_apply_frac_dev", "fg_set_topog_sweep",
     "fg_coupler_create", "fg_coupler_create_gc", "fg_coupler_destroy", "fg_coupler_stream", "fg_coupler_run", "fg_coupler_count", "fg_coupler_get",
     "fg_coupler_get_cells", "fg_coupler_write", "fg_coupler_write_xgrid", "fg_coupler_write_mask", "fg_coupler_stats", "fg_coupler_phase_ms",
+    "fg_coupler_set_nest", "fg_coupler_add_wave", "fg_coupler_get_wave_ocean", "fg_coupler_check", "fg_coupler_write_wave",
+    "fg_coupler_write_wave_xgrid", "fg_coupler_write_wave_mask",
 ]
 
 
@@ -591,6 +593,20 @@ def lib():
     L.fg_coupler_stats.restype = C.c_int
     L.fg_coupler_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
     L.fg_coupler_phase_ms.restype = C.c_int
+    L.fg_coupler_set_nest.argtypes = [vp, C.c_int]
+    L.fg_coupler_set_nest.restype = C.c_int
+    L.fg_coupler_add_wave.argtypes = [vp, C.c_int, ip, ip, dpp, dpp, C.c_int]
+    L.fg_coupler_add_wave.restype = C.c_int
+    L.fg_coupler_get_wave_ocean.argtypes = [vp, dp, dp, dp]
+    L.fg_coupler_get_wave_ocean.restype = C.c_int
+    L.fg_coupler_check.argtypes = [vp, dp, C.c_int]
+    L.fg_coupler_check.restype = C.c_int
+    L.fg_coupler_write_wave.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p)]
+    L.fg_coupler_write_wave.restype = C.c_int
+    L.fg_coupler_write_wave_xgrid.argtypes = [C.c_char_p, C.c_char_p, C.c_long] + [ip] * 4 + [C.c_int] + [dp] * 5
+    L.fg_coupler_write_wave_xgrid.restype = C.c_int
+    L.fg_coupler_write_wave_mask.argtypes = [C.c_char_p, C.c_int, C.c_int, dp]
+    L.fg_coupler_write_wave_mask.restype = C.c_int
     _LIB = L
     return L
 

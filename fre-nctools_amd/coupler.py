@@ -23,8 +23,10 @@ centroid distances, the land and ocean masks -- with the lists and polygons kept
 exchange-grid and mask files through the library's classic-netCDF writer.  coupler_ocean_grid is the numpy mirror of the ocean
 grid preparation (:841-876, :940-955).  CouplerMosaic(clip_method="great_circle") is the tool's GREAT_CIRCLE_CLIP branch
 (fg_coupler_create_gc, first order): unit vectors, clip_2dx2d_great_circle, and the remembered polygons searched by the great-circle
-polygon-list plan (XgridPlan.create_polylist_gc).  Not covered by either: nested atmosphere tiles, the wave grid, several ocean
-tiles, --check's global sums, the MPI split, the coupler mosaic file; coupler_xgrid is legacy clip only.
+polygon-list plan (XgridPlan.create_polylist_gc).  CouplerMosaic(tile_nest=...) leaves a nested atmosphere tile's terms out of the
+land and ocean cells' sums (:1765, :1792, :1857, :1903); CouplerMosaic(wav=...) adds the wave x ocean exchange grid (:2976-3535,
+legacy clip); check() is --check (:3591-3661).  Not covered: several ocean tiles, the MPI split, the coupler mosaic file, the wave
+grid on the great-circle handle; coupler_xgrid is legacy clip only and knows none of the three.
 """
 import ctypes as C
 import os
@@ -165,6 +167,26 @@ def write_xgrid_file(path, contact, i1, j1, i2, j2, area, dist1=None, dist2=None
                                        *[v.ctypes.data_as(_dpt) for v in dbl], *([None] * (5 - len(dbl)))))
 
 
+def write_wave_xgrid_file(path, contact, iw, jw, io, jo, area, dist1=None, dist2=None, jo_shift=1):
+    """A wave x ocean exchange-grid file from host arrays (fg_coupler_write_wave_xgrid; :3461-3527): write_xgrid_file's variables and
+    attributes with :3476-3477's names on tile1_cell / tile2_cell; jo_shift = 1 - ocn_south_ext (:3492)."""
+    ints = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (iw, jw, io, jo)]
+    dbl = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (area,) + (tuple(dist1) + tuple(dist2) if dist1 is not None else ())]
+    n = dbl[0].size
+    if any(v.size != n for v in ints + dbl):
+        raise ValueError("the arrays of an exchange-grid file must have one length")
+    check(lib().fg_coupler_write_wave_xgrid(str(path).encode(), contact.encode(), n, *[v.ctypes.data_as(_ipt) for v in ints], int(jo_shift),
+                                            *[v.ctypes.data_as(_dpt) for v in dbl], *([None] * (5 - len(dbl)))))
+
+
+def write_wave_mask_file(path, mask):
+    """wave_mask.nc / wave_mask_tileN.nc (:3405-3419) from a host array [ny, nx]: the single variable mask"""
+    m = np.ascontiguousarray(mask, dtype=np.float64)
+    if m.ndim != 2:
+        raise ValueError("the wave mask must be [ny, nx]")
+    check(lib().fg_coupler_write_wave_mask(str(path).encode(), m.shape[1], m.shape[0], m.ctypes.data_as(_dpt)))
+
+
 def write_mask_file(path, kind, fields):
     """ocean_mask.nc (kind "ocean": fields mask, areaO, areaX, :2055-2066) or a land mask file (kind "land": mask, area_lnd, l_area and
     area_atm when given, :2103-2117) from host arrays [ny, nx] (fg_coupler_write_mask)."""
@@ -183,12 +205,16 @@ class CouplerMosaic:
     lnd_same_as_atm), one GridConfig or a list of them; ocn: one GridConfig, the grid the tool works on (coupler_ocean_grid's x, y);
     omask [ny_ocn, nx_ocn]: the ocean fraction; ocn_south_ext: coupler_ocean_grid's.  Corners in radians.
     clip_method "legacy" (clip_2dx2d on lon / lat) or "great_circle" (the tool's GREAT_CIRCLE_CLIP branch, fg_coupler_create_gc:
-    clip_2dx2d_great_circle on unit vectors, what a grid with a pole inside a cell needs; interp_order must then be 1)."""
+    clip_2dx2d_great_circle on unit vectors, what a grid with a pole inside a cell needs; interp_order must then be 1).
+    tile_nest: None, or the index of the nested atmosphere tile (fg_coupler_set_nest; refused with land on the atmosphere grid).
+    wav: None, one GridConfig or a list of them: the wave grid's tiles (fg_coupler_add_wave; legacy clip only); wav_same_as_ocn: the
+    wave mosaic is the ocean mosaic (the names of write_wave's files)."""
 
-    AXL, AXO, LXO = 0, 1, 2
-    ATM, LND, OCN = 0, 1, 2
+    AXL, AXO, LXO, WXO = 0, 1, 2, 3
+    ATM, LND, OCN, WAV = 0, 1, 2, 3
 
-    def __init__(self, atm, lnd, ocn, omask, interp_order=2, area_ratio_thresh=AREA_RATIO_THRESH, ocn_south_ext=0, device=0, clip_method="legacy"):
+    def __init__(self, atm, lnd, ocn, omask, interp_order=2, area_ratio_thresh=AREA_RATIO_THRESH, ocn_south_ext=0, device=0, clip_method="legacy",
+                 tile_nest=None, wav=None, wav_same_as_ocn=False):
         self._h = None
         if clip_method not in ("legacy", "great_circle"):
             raise ValueError("clip_method must be 'legacy' or 'great_circle'")
@@ -220,6 +246,18 @@ class CouplerMosaic:
                      nxl, nyl, lol, lal, ocn.nx, ocn.ny, ko[0][0].ctypes.data_as(_dpt), ko[0][1].ctypes.data_as(_dpt),
                      om.ctypes.data_as(_dpt), self.ocn_south_ext, device, C.byref(h)))
         self._h = h
+        self.tile_nest = None if tile_nest is None else int(tile_nest)
+        self.wav = [] if wav is None else (list(wav) if isinstance(wav, (list, tuple)) else [wav])
+        self.wav_same_as_ocn = bool(wav_same_as_ocn)
+        try:
+            if self.tile_nest is not None:
+                check(lib().fg_coupler_set_nest(self._h, self.tile_nest))
+            if self.wav:
+                _, nxw, nyw, low, law = table(self.wav)
+                check(lib().fg_coupler_add_wave(self._h, len(self.wav), nxw, nyw, low, law, int(self.wav_same_as_ocn)))
+        except Exception:
+            self.destroy()
+            raise
 
     def destroy(self):
         if self._h is not None and self._h.value:
@@ -276,10 +314,36 @@ class CouplerMosaic:
         """land tile tl x ocean (land of its own only): dict il, jl, io, jo, area, ..."""
         return self._list(self.LXO, tl, 0, ("il", "jl", "io", "jo"))
 
+    def wxo(self, tw):
+        """wave tile tw x ocean (a handle with a wave grid): dict iw, jw, io, jo, area, and for order 2 clon, clat, di1 .. dj2"""
+        return self._list(self.WXO, tw, 0, ("iw", "jw", "io", "jo"))
+
+    def wave_ocean_cells(self):
+        """the ocean cells' wave-side sums (:3329-3332, :3366-3371; order 2), [ny, nx] each: dict xarea, clon, clat.  Not the
+        atmosphere-side o_area of cells(OCN)."""
+        out = {k: np.empty((self.ocn.ny, self.ocn.nx)) for k in ("xarea", "clon", "clat")}
+        check(lib().fg_coupler_get_wave_ocean(self._h, *[out[k].ctypes.data_as(_dpt) for k in ("xarea", "clon", "clat")]))
+        return out
+
+    def check(self):
+        """--check (:3591-3661; fg_coupler_check): dict max_ratio, max_tile, max_i, max_j (0-based; the first cell with the largest
+        |atm_xarea - area_atm| / area_atm), max_area_atm, max_atm_xarea, atm_area_sum, axl_area_sum, axo_area_sum, axo_area_frac,
+        axl_area_frac, tiling_area (percent); with a nest their _nest counterparts; with a wave grid wxo_area_sum"""
+        v = (C.c_double * 19)()
+        check(lib().fg_coupler_check(self._h, v, 19))
+        names = ("atm_area_sum", "axl_area_sum", "axo_area_sum", "axo_area_frac", "axl_area_frac", "tiling_area")
+        out = dict(max_ratio=v[0], max_tile=int(v[1]), max_i=int(v[2]), max_j=int(v[3]), max_area_atm=v[4], max_atm_xarea=v[5])
+        out.update(zip(names, v[6:12]))
+        if self.tile_nest is not None and self.tile_nest >= 0:
+            out.update(zip([k + "_nest" for k in names], v[12:18]))
+        if self.wav:
+            out["wxo_area_sum"] = v[18]
+        return out
+
     def cells(self, grid, tile=0):
-        """per cell of one tile (grid: ATM, LND, OCN), [ny, nx] each: dict area (get_grid_area), xarea (a_area / l_area / o_area),
-        frac (their ratio: the land mask, the ocean fraction) and for order 2 clon, clat (the centroid)"""
-        g = (self.atm, self.lnd, [self.ocn])[grid][tile]
+        """per cell of one tile (grid: ATM, LND, OCN, WAV), [ny, nx] each: dict area (get_grid_area), xarea (a_area / l_area / o_area /
+        w_area), frac (their ratio: the land mask, the ocean fraction, the wave mask) and for order 2 clon, clat (the centroid)"""
+        g = (self.atm, self.lnd, [self.ocn], self.wav)[grid][tile]
         names = ("area", "xarea", "frac") + (("clon", "clat") if self.order == 2 else ())
         out = {k: np.empty((g.ny, g.nx)) for k in names}
         ptr = [out[k].ctypes.data_as(_dpt) for k in names] + [None] * (5 - len(names))
@@ -287,16 +351,17 @@ class CouplerMosaic:
         return out
 
     def stats(self):
-        """dict: d2h_bytes (what run() copied to the host), nbad, searches, naxo, naxl, nlxo, npolygons, ocn_south_ext"""
-        s = (C.c_long * 8)()
-        check(lib().fg_coupler_stats(self._h, s, 8))
-        return dict(zip(("d2h_bytes", "nbad", "searches", "naxo", "naxl", "nlxo", "npolygons", "ocn_south_ext"), s))
+        """dict: d2h_bytes (what run() copied to the host), nbad, searches, naxo, naxl, nlxo, npolygons, ocn_south_ext, and with a
+        wave grid nwxo"""
+        s = (C.c_long * 9)()
+        check(lib().fg_coupler_stats(self._h, s, 9))
+        return dict(zip(("d2h_bytes", "nbad", "searches", "naxo", "naxl", "nlxo", "npolygons", "ocn_south_ext") + (("nwxo",) if self.wav else ()), s))
 
     def phase_ms(self):
-        """wall time in ms: dict create, axl_candidates, axo, polygons_x_ocean, lxo, sums, run"""
-        ms = (C.c_float * 7)()
-        check(lib().fg_coupler_phase_ms(self._h, ms, 7))
-        return dict(zip(("create", "axl_candidates", "axo", "polygons_x_ocean", "lxo", "sums", "run"), ms))
+        """wall time in ms: dict create, axl_candidates, axo, polygons_x_ocean, lxo, sums, run, and with a wave grid wxo"""
+        ms = (C.c_float * 8)()
+        check(lib().fg_coupler_phase_ms(self._h, ms, 8))
+        return dict(zip(("create", "axl_candidates", "axo", "polygons_x_ocean", "lxo", "sums", "run") + (("wxo",) if self.wav else ()), ms))
 
     def write(self, directory, atm_mosaic="atmos_mosaic", lnd_mosaic="land_mosaic", ocn_mosaic="ocean_mosaic", atm_tiles=None, lnd_tiles=None,
               ocn_tile="tile1"):
@@ -321,5 +386,23 @@ class CouplerMosaic:
         files += ["land_mask.nc"] if len(self.lnd) == 1 else [f"land_mask_tile{k + 1}.nc" for k in range(len(self.lnd))]
         return [os.path.join(str(directory), f) for f in files]
 
+    def write_wave(self, directory, wav_mosaic="wave_mosaic", ocn_mosaic="ocean_mosaic", wav_tiles=None, ocn_tile="tile1"):
+        """The wave grid's files (:3397-3421, :3430-3535; fg_coupler_write_wave) into directory: per non-empty list
+        <wav_mosaic>_<tile>X<ocn_mosaic>_<ocn_tile>.nc (wav_<...>Xocn_<...>.nc with wav_same_as_ocn) and wave_mask.nc or
+        wave_mask_tile<k>.nc.  Returns the files written."""
+        wav_tiles = list(wav_tiles or [f"tile{k + 1}" for k in range(len(self.wav))])
+        if len(wav_tiles) != len(self.wav):
+            raise ValueError("one name per wave tile")
+        table = [wav_mosaic, ocn_mosaic] + wav_tiles + [ocn_tile]
+        names = (C.c_char_p * len(table))(*[t.encode() for t in table])
+        check(lib().fg_coupler_write_wave(self._h, str(directory).encode(), names))
+        files = []
+        for tw, wt in enumerate(wav_tiles):
+            if check(lib().fg_coupler_count(self._h, self.WXO, tw, 0)):
+                files.append(f"wav_{wav_mosaic}_{wt}Xocn_{ocn_mosaic}_{ocn_tile}.nc" if self.wav_same_as_ocn else f"{wav_mosaic}_{wt}X{ocn_mosaic}_{ocn_tile}.nc")
+            files.append("wave_mask.nc" if len(self.wav) == 1 else f"wave_mask_tile{tw + 1}.nc")
+        return [os.path.join(str(directory), f) for f in files]
 
-__all__ = ["coupler_xgrid", "CouplerMosaic", "coupler_ocean_grid", "write_xgrid_file", "write_mask_file", "MIN_AREA_FRAC", "AREA_RATIO_THRESH"]
+
+__all__ = ["coupler_xgrid", "CouplerMosaic", "coupler_ocean_grid", "write_xgrid_file", "write_mask_file", "write_wave_xgrid_file",
+           "write_wave_mask_file", "MIN_AREA_FRAC", "AREA_RATIO_THRESH"]

@@ -1,5 +1,5 @@
 // coupler.h -- what coupler_kernels.hip (device) and coupler.hip (host orchestration) share of make_coupler_mosaic's exchange grids
-// (tools/make_coupler_mosaic/make_coupler_mosaic.c:1198-2127, :2466-2811; design: DESIGN.md 3.13).
+// (tools/make_coupler_mosaic/make_coupler_mosaic.c:1198-2127, :2466-2811, :2976-3535, :3591-3661; design: DESIGN.md 3.13).
 // min is the reference's macro (mosaic_util.h:35), operand order included.  Nothing here is contracted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,3 +78,11 @@ void fgd_cp_fraction(int ncells, const double *xarea, const double *area, const 
 void fgd_cp_tile_starts(int ntiles, const int *cell_off, long n, const int *c1, int *starts, hipStream_t st);
 // (i, j) of the cells [k0, k0 + n) of a list; off1 / nx1: cell offset and row length of the first grid's tile (off 0 for land and ocean)
 void fgd_cp_indices(long n, const int *c1, const int *c2, int off1, int nx1, int nx2, int *i1, int *j1, int *i2, int *j2, hipStream_t st);
+// wave x ocean (:3107-3117): the ocean corner rows [0, ny] that have a corner strictly inside (lo, hi): band [0] = the lowest, [1] = the
+// highest such row (band preset to {ny, -1}); then the flags of a plan's pairs whose ocean row lies outside [js, je] are cleared
+void fgd_cp_row_band(int nx, int ny, const double *lat, double lo, double hi, int *band, hipStream_t st);
+void fgd_cp_band_mask(long n, const int *x_dst, int nx, int js, int je, int *flag, hipStream_t st);
+// --check (:3612-3626): the largest |xarea - area| / area over the cells, the first cell among equals; best [0] = the ratio,
+// cell [0] = the cell (-1: no cell had a ratio above -1).  scratch: fgd_cp_check_blocks(n) doubles and ints
+long fgd_cp_check_blocks(long n);
+void fgd_cp_check_ratio(long n, const double *xarea, const double *area, double *sc_ratio, int *sc_cell, double *best, int *cell, hipStream_t st);

@@ -1,6 +1,7 @@
 // coupler.hip -- host orchestration of make_coupler_mosaic's exchange grids on the device (fg_coupler_*):
 // tools/make_coupler_mosaic/make_coupler_mosaic.c:1198-2127 (atmosphere x land, atmosphere x ocean, the per-cell sums, the
-// centroid distances, the masks) and :2466-2811 (land x ocean), one process, no nest, one ocean tile; LEGACY_CLIP (fg_coupler_create)
+// centroid distances, the masks) and :2466-2811 (land x ocean), one process, one ocean tile; a nested atmosphere tile (fg_coupler_set_nest),
+// the wave grid :2976-3535 (fg_coupler_add_wave) and --check :3591-3661 (fg_coupler_check); LEGACY_CLIP (fg_coupler_create)
 // or GREAT_CIRCLE_CLIP at first order (fg_coupler_create_gc: unit vectors, great-circle plans, the n-gon polygon-list search).
 // Kernels: coupler_kernels.hip; shared declarations: coupler.h; design: DESIGN.md 3.13.
 //
@@ -66,7 +67,18 @@ struct fg_coupler {
   double *a_frac = nullptr, *l_frac = nullptr, *o_frac = nullptr;
   long d2h = 0, searches = 0, ncand = 0;
   int nbad = 0;
-  float ms[7] = {0, 0, 0, 0, 0, 0, 0};          // create; atm x land candidates; atm x ocean; polygons x ocean; land x ocean; sums; run
+  float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // create; atm x land candidates; atm x ocean; polygons x ocean; land x ocean; sums; run; wave x ocean
+  // nested atmosphere tile (fg_coupler_set_nest): its terms stay out of the land and ocean cells' sums (:1765, :1792, :1857, :1903)
+  int tile_nest = -1;
+  // wave grid (fg_coupler_add_wave, :2976-3535)
+  std::vector<Grid> wav;
+  std::vector<std::pair<int, int>> wav_band;    // per wave tile: js_ocn, je_ocn of :3107-3117
+  int nw = 0;
+  bool wav_same = false;                        // wav_same_as_ocn: the file names of :3452-3455
+  double *area_wav = nullptr;
+  std::vector<CpList> wxo;                      // per wave tile
+  CpSums w{}, ow{};                             // the wave cells' sums and the ocean cells' wave-side sums (:3294-3386)
+  double *w_frac = nullptr;
 };
 
 extern "C" void fg_coupler_destroy(fg_coupler *h)
@@ -239,6 +251,57 @@ extern "C" int fg_coupler_create_gc(int interp_order, double area_ratio_thresh, 
 {
   return cp_create(true, interp_order, area_ratio_thresh, ntile_atm, nxa, nya, lon_atm, lat_atm, ntile_lnd, nxl, nyl, lon_lnd, lat_lnd, nxo, nyo,
                    lon_ocn, lat_ocn, omask, ocn_south_ext, device, out);
+}
+
+// A nested atmosphere tile (:626-640 finds it in the atmosphere mosaic's contacts; here the caller names it): an index into the
+// atmosphere tiles, -1 for none.  Refused with land on the atmosphere grid (:742).  Takes effect with the next run.
+extern "C" int fg_coupler_set_nest(fg_coupler *h, int tile_nest)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_coupler_set_nest: null handle");
+  if (tile_nest < -1 || tile_nest >= (int)h->atm.size())
+    return fg_fail(FG_ERR_ARG, "fg_coupler_set_nest: no atmosphere tile %d (the handle has %d)", tile_nest, (int)h->atm.size());
+  if (tile_nest >= 0 && h->same)
+    return fg_fail(FG_ERR_ARG, "make_coupler_mosaic: land mosaic must be different from atmos mosaic when there is nest region in atmos mosaic");
+  h->tile_nest = tile_nest;
+  h->ran = false;
+  return 0;
+}
+
+// The wave grid (:2976-3535, legacy clip): its tiles, their areas (:1036) and per tile the ocean row band of :3107-3117.
+// wav_same_as_ocn changes nothing with one ocean tile (:3119-3126) but the file names (:3452-3455).  Takes effect with the next run.
+extern "C" int fg_coupler_add_wave(fg_coupler *h, int ntile_wav, const int *nx, const int *ny, const double *const *lon, const double *const *lat,
+                                   int wav_same_as_ocn)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_coupler_add_wave: null handle");
+  if (h->gc) return fg_fail(FG_ERR_ARG, "fg_coupler_add_wave: the great-circle handle takes no wave grid (it is first order only)");
+  if (!h->wav.empty()) return fg_fail(FG_ERR_ARG, "fg_coupler_add_wave: the handle has a wave grid already");
+  if (ntile_wav < 1 || ntile_wav > CP_MAX_LISTS) return fg_fail(FG_ERR_ARG, "fg_coupler_add_wave: 1 to %d wave tiles", CP_MAX_LISTS);
+  FGCHK(hipSetDevice(h->device));
+  std::vector<Grid> wav;
+  int nw = 0;
+  if (int rc = cp_put_grid(h, "wave", ntile_wav, nx, ny, lon, lat, &wav, &nw)) return rc;
+  const double dummy[8] = {0, 0.01, 0, 0.01, 0, 0, 0.01, 0.01};
+  const double *d_dummy = h->dev.put(dummy, 8);
+  double *area = h->dev.get<double>((size_t)nw);
+  int *d_band = h->dev.get<int>(2);
+  if (!d_dummy || !area || !d_band) return fg_fail(FG_ERR_HIP, "fg_coupler_add_wave: device allocation or upload failed");
+  if (int rc = cp_grid_area(h, wav, d_dummy, area)) return rc;
+  std::vector<std::pair<int, int>> bands;
+  for (const Grid &g : wav) {
+    const double *y = lat[&g - wav.data()];
+    double yw_min = 9999, yw_max = -9999;                                  // :3071-3104 (one process: every cell of the tile)
+    for (size_t p = 0; p < (size_t)(g.nx + 1) * (g.ny + 1); p++) { if (y[p] > yw_max) yw_max = y[p]; if (y[p] < yw_min) yw_min = y[p]; }
+    int band[2] = {h->ocn.ny, -1};                                         // :3108
+    FGCHK(hipMemcpyAsync(d_band, band, sizeof band, hipMemcpyHostToDevice, h->stream));
+    fgd_cp_row_band(h->ocn.nx, h->ocn.ny, h->ocn.lat, yw_min, yw_max, d_band, h->stream);
+    FGCHK(hipGetLastError());
+    FGCHK(hipMemcpyAsync(band, d_band, sizeof band, hipMemcpyDeviceToHost, h->stream));
+    FGCHK(hipStreamSynchronize(h->stream));
+    bands.push_back({std::max(0, band[0] - 1), std::min(h->ocn.ny - 1, band[1] + 1)});      // :3116-3117
+  }
+  h->wav = wav; h->nw = nw; h->area_wav = area; h->wav_band = bands; h->wav_same = wav_same_as_ocn != 0;
+  h->ran = false;
+  return 0;
 }
 
 // --------------------------------------------------------------------------------------------------------------- the run
@@ -419,7 +482,9 @@ struct Run {
   // :1604-1661 (src = the atmosphere) and :2598-2690 (src = one land tile): the search, the ocean-fraction tests, the survivors
   // keep != null: the plan is handed to the caller instead of destroyed (great-circle handle with land on the atmosphere grid: step 4
   // works on the same pairs)
-  int ocean_list(int ntiles, const std::vector<Grid> &src, const double *area_src, CpList *out, fg_plan **keep = nullptr)
+  // band != null (wave x ocean, :3107-3117, :3162): only the ocean rows band->first .. band->second are looked at
+  int ocean_list(int ntiles, const std::vector<Grid> &src, const double *area_src, CpList *out, fg_plan **keep = nullptr,
+                 const std::pair<int, int> *band = nullptr)
   {
     fg_plan *pl = nullptr;
     const long nx = search(ntiles, src, h->ocn, &pl);
@@ -431,6 +496,7 @@ struct Run {
     int *flag = tmp.get<int>((size_t)(nx > 0 ? nx : 1)), *offs = nullptr, total = 0;
     if (!flag) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
     fgd_cp_ocean_flag(nx, v.x_src, v.x_dst, v.x_area, h->omask, h->area_ocn, area_src, h->thresh, flag, st);
+    if (band) fgd_cp_band_mask(nx, v.x_dst, h->ocn.nx, band->first, band->second, flag, st);
     if (int rc = scan_total(tmp, nx, flag, &offs, &total)) return rc;
     if (!alloc_list(out, total)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
     out->n = total;
@@ -594,6 +660,15 @@ struct Run {
     for (size_t t = 0; t < h->lxo.size(); t++)
       if (int rc = ocean_list(1, std::vector<Grid>{h->lnd[t]}, h->area_lnd + h->lnd[t].off, &h->lxo[t])) return rc;
     t1 = fg_now_ms(); h->ms[4] = (float)(t1 - t0); t0 = t1;
+    // 5w. wave x ocean (:3044-3231): the land x ocean step with a wave tile for the land tile, inside the tile's ocean row band
+    h->wxo.assign(h->wav.size(), CpList{});
+    for (size_t t = 0; t < h->wxo.size(); t++)
+      if (int rc = ocean_list(1, std::vector<Grid>{h->wav[t]}, h->area_wav + h->wav[t].off, &h->wxo[t], nullptr, &h->wav_band[t])) return rc;
+    if (!h->wav.empty()) { t1 = fg_now_ms(); h->ms[7] = (float)(t1 - t0); t0 = t1; }
+    // where the tiles begin in the atmosphere-major lists
+    h->axl_start.assign(ntl, std::vector<int>());
+    for (int t = 0; t < ntl; t++) if (int rc = tile_starts(h->axl[t], &h->axl_start[t])) return rc;
+    if (int rc = tile_starts(h->axo, &h->axo_start)) return rc;
     // 6. per-cell sums
     if (!alloc_sums(&h->a, h->na) || !alloc_sums(&h->l, h->nl) || !alloc_sums(&h->o, h->no) || !alloc_sums(&h->l2, h->nl) || !alloc_sums(&h->o2, h->no))
       return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
@@ -605,9 +680,31 @@ struct Run {
     refs.l[refs.count++] = CpListRef{h->axo.c1, h->axo.area, h->axo.clon, h->axo.clat, h->axo.n};
     fgd_cp_a_sums(h->na, refs, h->order, h->a, st);
     FGCHK(hipGetLastError());
+    if (h->tile_nest >= 0 && h->order == 2) {
+      // :1857 and :1903 enclose the a_area / a_clon / a_clat additions of :1882-1885 and :1927-1930 too: the reference's temporary a_area
+      // of the nest tile stays 0, :1946-1951 divide nothing, and the nest lists' tile-1 distances are clon / area - 0.  The cell's area
+      // sum is kept (it is atm_xarea of :2210 / :2333, which has no guard: fg_coupler_check, a_frac); the centroid is what the
+      // distances subtract: 0
+      const Grid &g = h->atm[(size_t)h->tile_nest];
+      FGCHK(hipMemsetAsync(h->a.clon + g.off, 0, (size_t)g.ncells() * sizeof(double), st));
+      FGCHK(hipMemsetAsync(h->a.clat + g.off, 0, (size_t)g.ncells() * sizeof(double), st));
+    }
     auto tile = [](CpSums s, int off) { return CpSums{s.area + off, s.clon + off, s.clat + off}; };
-    for (int t = 0; t < ntl; t++) if (int rc = row_sums(h->axl[t], 2, h->lnd[t].ncells(), tile(h->l, h->lnd[t].off))) return rc;
-    if (int rc = row_sums(h->axo, 2, h->no, h->o)) return rc;
+    // the terms of an atmosphere-major list onto the cells of its second grid, without the nest tile's (:1765, :1792, :1857, :1903):
+    // the list before the nest tile's range, then the list after it, which is the reference's order with that tile skipped
+    auto part = [](const CpList &l, long k0, long k1) {
+      CpList s = l;
+      s.n = k1 - k0; s.c1 += k0; s.c2 += k0; s.area += k0; s.clon += k0; s.clat += k0;
+      for (int q = 0; q < 4; q++) s.d[q] += k0;
+      return s;
+    };
+    auto second_grid_sums = [&](const CpList &l, const std::vector<int> &start, long ncells, CpSums s) {
+      if (h->tile_nest < 0) return row_sums(l, 2, ncells, s);
+      if (int rc = row_sums(part(l, 0, start[(size_t)h->tile_nest]), 2, ncells, s)) return rc;
+      return row_sums(part(l, start[(size_t)h->tile_nest + 1], l.n), 2, ncells, s);
+    };
+    for (int t = 0; t < ntl; t++) if (int rc = second_grid_sums(h->axl[t], h->axl_start[t], h->lnd[t].ncells(), tile(h->l, h->lnd[t].off))) return rc;
+    if (int rc = second_grid_sums(h->axo, h->axo_start, h->no, h->o)) return rc;
     for (size_t t = 0; t < h->lxo.size(); t++) {
       if (int rc = row_sums(h->lxo[t], 1, h->lnd[t].ncells(), tile(h->l2, h->lnd[t].off))) return rc;
       if (int rc = row_sums(h->lxo[t], 2, h->no, h->o2)) return rc;
@@ -620,16 +717,29 @@ struct Run {
       fgd_cp_distances(h->axo, h->a, h->o, st);
       for (size_t t = 0; t < h->lxo.size(); t++) fgd_cp_distances(h->lxo[t], tile(h->l2, h->lnd[t].off), h->o2, st);
     }
+    // the wave grid's sums (:3237-3402).  Order 1: the reference's loop (:3262-3267) gathers io / jo into g_iw / g_jw and adds into
+    // w_area2, which is never allocated -- that statement cannot execute; w_area is formed as the order-2 branch forms it
+    // (:3325-3326) and nothing else
+    if (!h->wav.empty()) {
+      if (!alloc_sums(&h->w, h->nw) || !alloc_sums(&h->ow, h->no)) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+      h->w_frac = res.get<double>((size_t)h->nw);
+      if (!h->w_frac) return fg_fail(FG_ERR_HIP, "fg_coupler_run: out of device memory");
+      for (size_t t = 0; t < h->wxo.size(); t++) {
+        if (int rc = row_sums(h->wxo[t], 1, h->wav[t].ncells(), tile(h->w, h->wav[t].off))) return rc;
+        if (h->order == 2) if (int rc = row_sums(h->wxo[t], 2, h->no, h->ow)) return rc;
+      }
+      if (h->order == 2) {
+        fgd_cp_centroid(h->nw, h->w, st); fgd_cp_centroid(h->no, h->ow, st);                  // :3344-3349, :3366-3371
+        for (size_t t = 0; t < h->wxo.size(); t++) fgd_cp_distances(h->wxo[t], tile(h->w, h->wav[t].off), h->ow, st);
+      }
+      fgd_cp_fraction(h->nw, h->w.area, h->area_wav, nullptr, 0, h->w_frac, nullptr, st);     // :3397-3402
+    }
     // 8. masks
     fgd_cp_fraction(h->na, h->a.area, h->area_atm, nullptr, 0, h->a_frac, nullptr, st);
     fgd_cp_fraction(h->nl, h->l.area, h->area_lnd, nullptr, 0, h->l_frac, nullptr, st);
     fgd_cp_fraction(h->no, h->o.area, h->area_ocn, h->omask, h->south_ext * h->ocn.nx, h->o_frac, d_nbad, st);
     FGCHK(hipGetLastError());
     if (int rc = fetch(&h->nbad, d_nbad, sizeof(int))) return rc;
-    // where the tiles begin in the atmosphere-major lists
-    h->axl_start.assign(ntl, std::vector<int>());
-    for (int t = 0; t < ntl; t++) if (int rc = tile_starts(h->axl[t], &h->axl_start[t])) return rc;
-    if (int rc = tile_starts(h->axo, &h->axo_start)) return rc;
     h->ms[5] = (float)(fg_now_ms() - t0);
     return 0;
   }
@@ -656,7 +766,8 @@ extern "C" int fg_coupler_run(fg_coupler *h)
   return 0;
 }
 
-// which: 0 atmosphere x land (tile1 = atmosphere tile, tile2 = land tile), 1 atmosphere x ocean (tile1), 2 land x ocean (tile1 = land tile)
+// which: 0 atmosphere x land (tile1 = atmosphere tile, tile2 = land tile), 1 atmosphere x ocean (tile1), 2 land x ocean (tile1 = land tile),
+// 3 wave x ocean (tile1 = wave tile)
 static int cp_pick(const fg_coupler *h, const char *who, int which, int t1, int t2, const CpList **l, long *k0, long *n, int *off1, int *nx1, int *nx2)
 {
   if (!h) return fg_fail(FG_ERR_ARG, "%s: null handle", who);
@@ -675,7 +786,12 @@ static int cp_pick(const fg_coupler *h, const char *who, int which, int t1, int 
     if (h->same) return fg_fail(FG_ERR_ARG, "%s: land is on the atmosphere grid: there is no land x ocean list", who);
     *l = &h->lxo[t1]; *k0 = 0; *n = h->lxo[t1].n;
     *off1 = 0; *nx1 = h->lnd[t1].nx; *nx2 = h->ocn.nx;
-  } else return fg_fail(FG_ERR_ARG, "%s: which must be 0 (atmosphere x land), 1 (atmosphere x ocean) or 2 (land x ocean)", who);
+  } else if (which == 3) {
+    if (h->wav.empty()) return fg_fail(FG_ERR_ARG, "%s: the handle has no wave grid", who);
+    if (t2 != 0 || t1 < 0 || t1 >= (int)h->wav.size()) return fg_fail(FG_ERR_ARG, "%s: no wave tile %d x ocean tile %d", who, t1, t2);
+    *l = &h->wxo[t1]; *k0 = 0; *n = h->wxo[t1].n;
+    *off1 = 0; *nx1 = h->wav[t1].nx; *nx2 = h->ocn.nx;
+  } else return fg_fail(FG_ERR_ARG, "%s: which must be 0 (atmosphere x land), 1 (atmosphere x ocean), 2 (land x ocean) or 3 (wave x ocean)", who);
   return 0;
 }
 
@@ -710,7 +826,7 @@ extern "C" int fg_coupler_get(const fg_coupler *h, int which, int tile1, int til
   return 0;
 }
 
-// grid: 0 atmosphere, 1 land, 2 ocean (tile 0).  model_area: get_grid_area; xarea: the exchange-cell area the cell collected
+// grid: 0 atmosphere, 1 land, 2 ocean (tile 0), 3 wave (frac: the wave mask w_area / area_wav, :3397-3402).  model_area: get_grid_area; xarea: the exchange-cell area the cell collected
 // (a_area, l_area, o_area); frac = xarea / model_area (the land and ocean masks of :2037, :2089); clon / clat: the cell's centroid
 // (order 2; the plain sums where xarea is not > 0)
 extern "C" int fg_coupler_get_cells(const fg_coupler *h, int grid, int tile, double *model_area, double *xarea, double *frac, double *clon, double *clat)
@@ -718,37 +834,132 @@ extern "C" int fg_coupler_get_cells(const fg_coupler *h, int grid, int tile, dou
   if (!h) return fg_fail(FG_ERR_ARG, "fg_coupler_get_cells: null handle");
   if (!h->ran) return fg_fail(FG_ERR_STATE, "fg_coupler_get_cells: fg_coupler_run has not run on this handle");
   const std::vector<Grid> one{h->ocn};
-  const std::vector<Grid> &g = grid == 0 ? h->atm : (grid == 1 ? h->lnd : one);
-  if (grid < 0 || grid > 2 || tile < 0 || tile >= (int)g.size()) return fg_fail(FG_ERR_ARG, "fg_coupler_get_cells: no tile %d of grid %d", tile, grid);
+  const std::vector<Grid> &g = grid == 0 ? h->atm : (grid == 1 ? h->lnd : (grid == 3 ? h->wav : one));
+  if (grid < 0 || grid > 3 || tile < 0 || tile >= (int)g.size()) return fg_fail(FG_ERR_ARG, "fg_coupler_get_cells: no tile %d of grid %d", tile, grid);
   if (h->order != 2 && (clon || clat)) return fg_fail(FG_ERR_ARG, "fg_coupler_get_cells: centroids need interp_order 2");
   const int off = grid == 2 ? 0 : g[tile].off;
   const size_t bytes = (size_t)g[tile].ncells() * sizeof(double);
-  const CpSums &s = grid == 0 ? h->a : (grid == 1 ? h->l : h->o);
-  const double *src[5] = {grid == 0 ? h->area_atm : (grid == 1 ? h->area_lnd : h->area_ocn), s.area, grid == 0 ? h->a_frac : (grid == 1 ? h->l_frac : h->o_frac),
-                          s.clon, s.clat};
+  const CpSums &s = grid == 0 ? h->a : (grid == 1 ? h->l : (grid == 3 ? h->w : h->o));
+  const double *src[5] = {grid == 0 ? h->area_atm : (grid == 1 ? h->area_lnd : (grid == 3 ? h->area_wav : h->area_ocn)), s.area,
+                          grid == 0 ? h->a_frac : (grid == 1 ? h->l_frac : (grid == 3 ? h->w_frac : h->o_frac)), s.clon, s.clat};
   double *dst[5] = {model_area, xarea, frac, clon, clat};
   FGCHK(hipSetDevice(h->device));
   for (int q = 0; q < 5; q++) if (dst[q]) FGCHK(hipMemcpy(dst[q], src[q] + off, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
+// The ocean cells' wave-side sums (:3329-3332, :3366-3371; order 2 only -- at order 1 the reference forms none): the exchange area the
+// wave x ocean lists left on every ocean cell and its centroid.  They are not the atmosphere-side o_area of fg_coupler_get_cells.
+extern "C" int fg_coupler_get_wave_ocean(const fg_coupler *h, double *xarea, double *clon, double *clat)
+{
+  if (!h) return fg_fail(FG_ERR_ARG, "fg_coupler_get_wave_ocean: null handle");
+  if (!h->ran) return fg_fail(FG_ERR_STATE, "fg_coupler_get_wave_ocean: fg_coupler_run has not run on this handle");
+  if (h->wav.empty()) return fg_fail(FG_ERR_ARG, "fg_coupler_get_wave_ocean: the handle has no wave grid");
+  if (h->order != 2) return fg_fail(FG_ERR_ARG, "fg_coupler_get_wave_ocean: the ocean cells' wave-side sums need interp_order 2");
+  const double *src[3] = {h->ow.area, h->ow.clon, h->ow.clat};
+  double *dst[3] = {xarea, clon, clat};
+  FGCHK(hipSetDevice(h->device));
+  for (int q = 0; q < 3; q++) if (dst[q]) FGCHK(hipMemcpy(dst[q], src[q], (size_t)h->no * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// --check (:2199-2219, :2326-2342, :3504, :3591-3661).  out: [0] the largest |atm_xarea - area_atm| / area_atm  [1] its tile  [2] i  [3] j
+// (the first cell with that ratio, as the `>` of :3619 picks it; -1 when no cell has a ratio)  [4] area_atm and [5] atm_xarea there
+// [6] atm_area_sum  [7] axl_area_sum  [8] axo_area_sum  [9] ocean and [10] land percentage  [11] the tiling error in percent
+// [12 .. 17] the same six for the nest tile (0 without one)  [18] wxo_area_sum (0 without a wave grid).
+// atm_xarea is a_area: the land lists' terms, then the ocean list's, in list order (:2210, :2333) -- the argmax is one device
+// reduction.  The scalar sums depend on the order of millions of terms: the area columns are brought to the host and added there
+// in the reference's order.  Nothing here is counted in fg_coupler_stats' bytes: those are fg_coupler_run's.
+#define CP_CHECK_N 19
+extern "C" int fg_coupler_check(const fg_coupler *h, double *out, int n)
+{
+  if (!h || !out || n < 0) return fg_fail(FG_ERR_ARG, "fg_coupler_check: bad argument");
+  if (!h->ran) return fg_fail(FG_ERR_STATE, "fg_coupler_check: fg_coupler_run has not run on this handle");
+  FGCHK(hipSetDevice(h->device));
+  double v[CP_CHECK_N] = {0};
+  const int nta = (int)h->atm.size(), ntl = (int)h->lnd.size();
+  {
+    FgDev tmp;
+    const size_t nb = (size_t)fgd_cp_check_blocks(h->na);
+    double *sc_r = tmp.get<double>(nb), *d_best = tmp.get<double>(1);
+    int *sc_c = tmp.get<int>(nb), *d_cell = tmp.get<int>(1);
+    if (!sc_r || !sc_c || !d_best || !d_cell) return fg_fail(FG_ERR_HIP, "fg_coupler_check: out of device memory");
+    fgd_cp_check_ratio(h->na, h->a.area, h->area_atm, sc_r, sc_c, d_best, d_cell, h->stream);
+    FGCHK(hipGetLastError());
+    FGCHK(hipStreamSynchronize(h->stream));
+    int cell = -1;
+    FGCHK(hipMemcpy(&v[0], d_best, sizeof(double), hipMemcpyDeviceToHost));
+    FGCHK(hipMemcpy(&cell, d_cell, sizeof(int), hipMemcpyDeviceToHost));
+    v[1] = v[2] = v[3] = -1;
+    for (int t = 0; t < nta && cell >= 0; t++) {
+      const Grid &g = h->atm[t];
+      if (cell < g.off || cell >= g.off + g.ncells()) continue;
+      v[1] = t; v[2] = (cell - g.off) % g.nx; v[3] = (cell - g.off) / g.nx;                  // :3621-3623
+      FGCHK(hipMemcpy(&v[4], h->area_atm + cell, sizeof(double), hipMemcpyDeviceToHost));
+      FGCHK(hipMemcpy(&v[5], h->a.area + cell, sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  std::vector<double> col;
+  auto column = [&](const double *d, long m) {
+    col.resize((size_t)(m > 0 ? m : 1));
+    if (m > 0 && hipMemcpy(col.data(), d, (size_t)m * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return fg_fail(FG_ERR_HIP, "fg_coupler_check: copying an area column failed");
+    return 0;
+  };
+  if (int rc = column(h->area_atm, h->na)) return rc;
+  for (int t = 0; t < nta; t++) {                                          // :3636-3641
+    double &s = t == h->tile_nest ? v[12] : v[6];
+    for (long c = h->atm[t].off; c < h->atm[t].off + h->atm[t].ncells(); c++) s += col[(size_t)c];
+  }
+  {
+    std::vector<std::vector<double>> axl((size_t)ntl);
+    for (int l = 0; l < ntl; l++) { if (int rc = column(h->axl[l].area, h->axl[l].n)) return rc; axl[(size_t)l] = col; }
+    for (int t = 0; t < nta; t++)                                          // :2215-2218: atmosphere tile, land tile, list order
+      for (int l = 0; l < ntl; l++) {
+        double &s = t == h->tile_nest ? v[13] : v[7];
+        for (int k = h->axl_start[l][t]; k < h->axl_start[l][t + 1]; k++) s += axl[(size_t)l][(size_t)k];
+      }
+  }
+  if (int rc = column(h->axo.area, h->axo.n)) return rc;
+  for (int t = 0; t < nta; t++) {                                          // :2338-2341
+    double &s = t == h->tile_nest ? v[14] : v[8];
+    for (int k = h->axo_start[t]; k < h->axo_start[t + 1]; k++) s += col[(size_t)k];
+  }
+  v[9] = v[8] / v[6] * 100;                                                // :3642-3644
+  v[10] = v[7] / v[6] * 100;
+  v[11] = (v[6] - v[8] - v[7]) / v[6] * 100;
+  if (h->tile_nest >= 0) {                                                 // :3653-3655
+    v[15] = v[14] / v[12] * 100;
+    v[16] = v[13] / v[12] * 100;
+    v[17] = (v[12] - v[14] - v[13]) / v[12] * 100;
+  }
+  for (const CpList &l : h->wxo) {                                         // :3504: wave tile, list order
+    if (int rc = column(l.area, l.n)) return rc;
+    for (long k = 0; k < l.n; k++) v[18] += col[(size_t)k];
+  }
+  for (int k = 0; k < n && k < CP_CHECK_N; k++) out[k] = v[k];
+  return 0;
+}
+
 // s: [0] bytes fg_coupler_run brought to the host  [1] nbad (:2038)  [2] searches  [3] atmosphere x ocean cells  [4] atmosphere x land
-// cells  [5] land x ocean cells  [6] remembered atmosphere x land polygons  [7] ocn_south_ext
+// cells  [5] land x ocean cells  [6] remembered atmosphere x land polygons  [7] ocn_south_ext  [8] wave x ocean cells
 extern "C" int fg_coupler_stats(const fg_coupler *h, long *s, int n)
 {
   if (!h || !s || n < 0) return fg_fail(FG_ERR_ARG, "fg_coupler_stats: bad argument");
-  long naxl = 0, nlxo = 0;
+  long naxl = 0, nlxo = 0, nwxo = 0;
   for (const CpList &l : h->axl) naxl += l.n;
   for (const CpList &l : h->lxo) nlxo += l.n;
-  const long v[8] = {h->d2h, h->nbad, h->searches, h->ran ? h->axo.n : 0, h->ran ? naxl : 0, h->ran ? nlxo : 0, h->ncand, h->south_ext};
-  for (int k = 0; k < n && k < 8; k++) s[k] = v[k];
+  for (const CpList &l : h->wxo) nwxo += l.n;
+  const long v[9] = {h->d2h, h->nbad, h->searches, h->ran ? h->axo.n : 0, h->ran ? naxl : 0, h->ran ? nlxo : 0, h->ncand, h->south_ext,
+                     h->ran ? nwxo : 0};
+  for (int k = 0; k < n && k < 9; k++) s[k] = v[k];
   return 0;
 }
 
 extern "C" int fg_coupler_phase_ms(const fg_coupler *h, float *ms, int n)
 {
   if (!h || !ms || n < 0) return fg_fail(FG_ERR_ARG, "fg_coupler_phase_ms: bad argument");
-  for (int k = 0; k < n && k < 7; k++) ms[k] = h->ms[k];
+  for (int k = 0; k < n && k < 8; k++) ms[k] = h->ms[k];
   return 0;
 }
 
@@ -768,8 +979,10 @@ int nc_var(fg_ncfile *f, const char *name, int type, int ndims, const int *dims,
 
 // One exchange-grid file from host arrays (:2158-2244, :2277-2370, :2840-2920): 0-based (i, j) of the two grids' cells, written as
 // i + 1, j1 + 1, j2 + j2_shift (1, or 1 - ocn_south_ext for an ocean second grid: :2309, :2876); di1 .. dj2 all given (order 2) or all NULL.
-extern "C" int fg_coupler_write_xgrid(const char *path_, const char *contact_, long n, const int *i1, const int *j1, const int *i2, const int *j2,
-                                      int j2_shift, const double *area_, const double *di1, const double *dj1, const double *di2, const double *dj2)
+// std1 / std2: the standard_name of tile1_cell / tile2_cell (the wave x ocean files have their own, :3476-3477)
+static int cp_xgrid_file(const char *std1, const char *std2, const char *path_, const char *contact_, long n, const int *i1, const int *j1,
+                         const int *i2, const int *j2, int j2_shift, const double *area_, const double *di1, const double *dj1, const double *di2,
+                         const double *dj2)
 {
   if (!path_ || !contact_ || n < 1 || !i1 || !j1 || !i2 || !j2 || !area_) return fg_fail(FG_ERR_ARG, "fg_coupler_write_xgrid: bad argument (an empty list gets no file)");
   const bool o2 = di1 != nullptr;
@@ -791,8 +1004,8 @@ extern "C" int fg_coupler_write_xgrid(const char *path_, const char *contact_, l
              {"distant_to_parent2_centroid", "tile2_distance"}})
     : nc_var(f, "contact", CP_NC_CHAR, 1, &d_str, {{"standard_name", "grid_contact_spec"}, {"contact_type", "exchange"}, {"parent1_cell", "tile1_cell"},
              {"parent2_cell", "tile2_cell"}, {"xgrid_area_field", "xgrid_area"}});
-  const int v_t1 = nc_var(f, "tile1_cell", CP_NC_INT, 2, dims, {{"standard_name", "parent_cell_indices_in_mosaic1"}});
-  const int v_t2 = nc_var(f, "tile2_cell", CP_NC_INT, 2, dims, {{"standard_name", "parent_cell_indices_in_mosaic2"}});
+  const int v_t1 = nc_var(f, "tile1_cell", CP_NC_INT, 2, dims, {{"standard_name", std1}});
+  const int v_t2 = nc_var(f, "tile2_cell", CP_NC_INT, 2, dims, {{"standard_name", std2}});
   const int v_area = nc_var(f, "xgrid_area", CP_NC_DOUBLE, 1, &d_n, {{"standard_name", "exchange_grid_area"}, {"units", "m2"}});
   int v_d1 = 0, v_d2 = 0;
   if (o2) {
@@ -820,6 +1033,20 @@ extern "C" int fg_coupler_write_xgrid(const char *path_, const char *contact_, l
   return fg_nc_close(g) < 0 ? nc_fail("close") : 0;
 }
 
+extern "C" int fg_coupler_write_xgrid(const char *path, const char *contact, long n, const int *i1, const int *j1, const int *i2, const int *j2,
+                                      int j2_shift, const double *area, const double *di1, const double *dj1, const double *di2, const double *dj2)
+{
+  return cp_xgrid_file("parent_cell_indices_in_mosaic1", "parent_cell_indices_in_mosaic2", path, contact, n, i1, j1, i2, j2, j2_shift, area, di1, dj1,
+                       di2, dj2);
+}
+// a wave x ocean exchange-grid file from host arrays (:3461-3527): the same variables; tile1_cell / tile2_cell carry :3476-3477's names
+extern "C" int fg_coupler_write_wave_xgrid(const char *path, const char *contact, long n, const int *iw, const int *jw, const int *io, const int *jo,
+                                           int jo_shift, const double *area, const double *diw, const double *djw, const double *dio,
+                                           const double *djo)
+{
+  return cp_xgrid_file("parent1_cell_indices", "parent2_cell_indices", path, contact, n, iw, jw, io, jo, jo_shift, area, diw, djw, dio, djo);
+}
+
 // one list of the handle into its file; nothing for an empty list (:2136)
 static int cp_write_xgrid(const fg_coupler *h, const std::string &path, const std::string &contact, int which, int t1, int t2, int j2_shift)
 {
@@ -832,8 +1059,9 @@ static int cp_write_xgrid(const fg_coupler *h, const std::string &path, const st
   if (int rc = fg_coupler_get(h, which, t1, t2, idx.data(), idx.data() + n, idx.data() + 2 * n, idx.data() + 3 * n, area.data(), nullptr, nullptr, dp[0], dp[1],
                               dp[2], dp[3]))
     return rc;
-  return fg_coupler_write_xgrid(path.c_str(), contact.c_str(), n, idx.data(), idx.data() + n, idx.data() + 2 * n, idx.data() + 3 * n, j2_shift, area.data(),
-                                dp[0], dp[1], dp[2], dp[3]);
+  return (which == 3 ? fg_coupler_write_wave_xgrid : fg_coupler_write_xgrid)(path.c_str(), contact.c_str(), n, idx.data(), idx.data() + n,
+                                                                             idx.data() + 2 * n, idx.data() + 3 * n, j2_shift, area.data(), dp[0], dp[1],
+                                                                             dp[2], dp[3]);
 }
 
 // ocean_mask.nc (:2055-2066) / land_mask[_tileN].nc (:2103-2117): [ny][nx] doubles, `fields` = {name, standard_name, data}
@@ -914,4 +1142,35 @@ extern "C" int fg_coupler_write_mask(const char *path, int ocean, int nx, int ny
   if (ocean) return cp_write_mask(path, nx, ny, {{"mask", "ocean fraction at T-cell centers", mask}, {"areaO", "ocean grid area", a}, {"areaX", "ocean exchange grid area", b}});
   return cp_write_mask(path, nx, ny, {{"mask", "land fraction at T-cell centers", mask}, {"area_atm", "area atm ", area_atm}, {"area_lnd", "area land ", a},
                                       {"l_area", "land x area", b}});
+}
+
+// wave_mask.nc / wave_mask_tileN.nc (:3405-3419) from a host array [ny][nx]: the single variable mask
+extern "C" int fg_coupler_write_wave_mask(const char *path, int nx, int ny, const double *mask)
+{
+  if (!path || nx < 1 || ny < 1 || !mask) return fg_fail(FG_ERR_ARG, "fg_coupler_write_wave_mask: bad argument");
+  return cp_write_mask(path, nx, ny, {{"mask", "land/sea fraction at T-cell centers", mask}});
+}
+
+// The wave grid's files (:3397-3421, :3430-3535).  names: NULL, or [0] the wave, [1] the ocean mosaic name, then the wave tiles' names
+// and the ocean tile's name; a NULL entry or a NULL table gives "wave_mosaic", "ocean_mosaic", "tile<k>".  fg_coupler_write's name table
+// is not touched.  With wav_same_as_ocn the exchange-grid files are named wav_<mosaic>_<tile>Xocn_<mosaic>_<tile>.nc (:3452-3455).
+extern "C" int fg_coupler_write_wave(const fg_coupler *h, const char *directory, const char *const *names)
+{
+  if (!h || !directory) return fg_fail(FG_ERR_ARG, "fg_coupler_write_wave: bad argument");
+  if (h->wav.empty()) return fg_fail(FG_ERR_ARG, "fg_coupler_write_wave: the handle has no wave grid");
+  if (!h->ran) return fg_fail(FG_ERR_STATE, "fg_coupler_write_wave: fg_coupler_run has not run on this handle");
+  const int ntw = (int)h->wav.size();
+  auto name = [&](int k, const std::string &dflt) { return std::string(names && names[k] ? names[k] : dflt.c_str()); };
+  const std::string dir = std::string(directory) + "/", wm = name(0, "wave_mosaic"), omn = name(1, "ocean_mosaic"), ot = name(2 + ntw, "tile1");
+  for (int tw = 0; tw < ntw; tw++) {
+    const std::string wt = name(2 + tw, "tile" + std::to_string(tw + 1));
+    const std::string file = h->wav_same ? "wav_" + wm + "_" + wt + "Xocn_" + omn + "_" + ot + ".nc" : wm + "_" + wt + "X" + omn + "_" + ot + ".nc";
+    if (int rc = cp_write_xgrid(h, dir + file, wm + ":" + wt + "::" + omn + ":" + ot, 3, tw, 0, 1 - h->south_ext)) return rc;      // :3492
+    const Grid &g = h->wav[tw];
+    std::vector<double> frac((size_t)g.ncells());
+    if (int rc = fg_coupler_get_cells(h, 3, tw, nullptr, nullptr, frac.data(), nullptr, nullptr)) return rc;
+    const std::string mask = ntw > 1 ? "wave_mask_tile" + std::to_string(tw + 1) + ".nc" : std::string("wave_mask.nc");
+    if (int rc = fg_coupler_write_wave_mask((dir + mask).c_str(), g.nx, g.ny, frac.data())) return rc;
+  }
+  return 0;
 }

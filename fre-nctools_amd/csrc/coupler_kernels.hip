@@ -466,3 +466,92 @@ void fgd_cp_indices(long n, const int *c1, const int *c2, int off1, int nx1, int
 {
   if (n > 0) k_cp_indices<<<cp_blocks(n, 256), 256, 0, st>>>(n, c1, c2, off1, nx1, nx2, i1, j1, i2, j2);
 }
+
+// ------------------------------------------------------------------------------------------- wave x ocean row band (:3107-3117)
+// one block per corner row of the ocean grid: does any corner lie strictly inside (lo, hi)?  Integer atomics on the two row numbers.
+__global__ __launch_bounds__(256) void k_cp_row_band(int nx, const double *lat, double lo, double hi, int *band)
+{
+  __shared__ int any;
+  const int j = blockIdx.x;
+  if (threadIdx.x == 0) any = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = threadIdx.x; i <= nx; i += 256) {
+    const double yy = lat[(size_t)j * (nx + 1) + i];
+    if (yy > lo && yy < hi) mine = 1;                                      // :3111
+  }
+  if (mine) atomicOr(&any, 1);
+  __syncthreads();
+  if (threadIdx.x == 0 && any) { atomicMin(&band[0], j); atomicMax(&band[1], j); }      // :3112-3113
+}
+__global__ __launch_bounds__(256) void k_cp_band_mask(long n, const int *x_dst, int nx, int js, int je, int *flag)
+{
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int jo = x_dst[k] / nx;
+  if (jo < js || jo > je) flag[k] = 0;                                     // :3162: the loop never reaches the row
+}
+void fgd_cp_row_band(int nx, int ny, const double *lat, double lo, double hi, int *band, hipStream_t st)
+{
+  k_cp_row_band<<<(unsigned)(ny + 1), 256, 0, st>>>(nx, lat, lo, hi, band);
+}
+void fgd_cp_band_mask(long n, const int *x_dst, int nx, int js, int je, int *flag, hipStream_t st)
+{
+  if (n > 0) k_cp_band_mask<<<cp_blocks(n, 256), 256, 0, st>>>(n, x_dst, nx, js, je, flag);
+}
+
+// ------------------------------------------------------------------------------------------- --check (:3612-3626)
+// The loop keeps the first cell with the largest ratio (`>`): the comparison is exact, so the largest ratio with the lowest cell
+// index among equals is the same cell whatever the order of the reduction.  A NaN ratio never passes `>` and is never kept.
+#define CP_CHECK_PER_BLOCK 2048
+long fgd_cp_check_blocks(long n) { return (n + CP_CHECK_PER_BLOCK - 1) / CP_CHECK_PER_BLOCK + 1; }
+__device__ __forceinline__ void cp_check_take(double r, int c, double &best, int &cell)
+{
+  if (c >= 0 && (r > best || (r == best && (cell < 0 || c < cell)))) { best = r; cell = c; }
+}
+__device__ __forceinline__ void cp_check_block(double &best, int &cell, double *sh_r, int *sh_c)
+{
+  const int t = threadIdx.x;
+  sh_r[t] = best; sh_c[t] = cell;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (t < d) {
+      double b = sh_r[t]; int c = sh_c[t];
+      cp_check_take(sh_r[t + d], sh_c[t + d], b, c);
+      sh_r[t] = b; sh_c[t] = c;
+    }
+    __syncthreads();
+  }
+  best = sh_r[0]; cell = sh_c[0];
+}
+__global__ __launch_bounds__(256) void k_cp_check_ratio(long n, const double *xarea, const double *area, double *sc_ratio, int *sc_cell)
+{
+  __shared__ double sh_r[256];
+  __shared__ int sh_c[256];
+  double best = -1; int cell = -1;                                         // :3607-3610
+  const long base = (long)blockIdx.x * CP_CHECK_PER_BLOCK;
+  for (int q = threadIdx.x; q < CP_CHECK_PER_BLOCK; q += 256) {
+    const long c = base + q;
+    if (c >= n) break;
+    const double a = area[c];
+    const double r = fabs(xarea[c] - a) / a;                               // :3614
+    if (r > best) { best = r; cell = (int)c; }                            // :3619 (a lane's cells ascend)
+  }
+  cp_check_block(best, cell, sh_r, sh_c);
+  if (threadIdx.x == 0) { sc_ratio[blockIdx.x] = best; sc_cell[blockIdx.x] = cell; }
+}
+__global__ __launch_bounds__(256) void k_cp_check_final(long nb, const double *sc_ratio, const int *sc_cell, double *best_out, int *cell_out)
+{
+  __shared__ double sh_r[256];
+  __shared__ int sh_c[256];
+  double best = -1; int cell = -1;
+  for (long b = threadIdx.x; b < nb; b += 256) cp_check_take(sc_ratio[b], sc_cell[b], best, cell);
+  cp_check_block(best, cell, sh_r, sh_c);
+  if (threadIdx.x == 0) { *best_out = best; *cell_out = cell; }
+}
+void fgd_cp_check_ratio(long n, const double *xarea, const double *area, double *sc_ratio, int *sc_cell, double *best, int *cell, hipStream_t st)
+{
+  const long nb = n > 0 ? (n + CP_CHECK_PER_BLOCK - 1) / CP_CHECK_PER_BLOCK : 0;
+  if (nb > 0) k_cp_check_ratio<<<(unsigned)nb, 256, 0, st>>>(n, xarea, area, sc_ratio, sc_cell);
+  k_cp_check_final<<<1, 256, 0, st>>>(nb, sc_ratio, sc_cell, best, cell);
+}

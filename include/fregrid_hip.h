@@ -1204,8 +1204,8 @@ int  fg_plan_apply_frac_dev(fg_plan *plan, const double *data_dev, double *out_d
 
 /* ---- make_coupler_mosaic's exchange grids on the device (tools/make_coupler_mosaic/make_coupler_mosaic.c:1198-2127, :2466-2811;
  * DESIGN.md 3.13): atmosphere x land, atmosphere x ocean and land x ocean lists, the per-cell area and centroid sums, the centroid
- * distances of an order-2 exchange-grid file and the land and ocean masks.  Legacy clip, one process, no nest, no wave grid, one
- * ocean tile, any number of atmosphere tiles, land on the atmosphere grid (lnd_same_as_atm) or as tiles of its own.  The lists and
+ * distances of an order-2 exchange-grid file and the land and ocean masks.  Legacy clip, one process, one ocean tile, a nested
+ * atmosphere tile (fg_coupler_set_nest), a wave grid (fg_coupler_add_wave), --check's sums (fg_coupler_check), any number of atmosphere tiles, land on the atmosphere grid (lnd_same_as_atm) or as tiles of its own.  The lists and
  * every clipped polygon stay in device memory between the searches; fg_coupler_run brings counts and error words to the host.
  *
  * fg_coupler_create: corner arrays in radians, [ny+1][nx+1] per tile (host).  ntile_lnd = 0: land is on the atmosphere grid and
@@ -1231,20 +1231,47 @@ int  fg_coupler_create_gc(int interp_order, double area_ratio_thresh, int ntile_
                           const double *lat_ocn, const double *omask, int ocn_south_ext, int device, fg_coupler **out);
 void fg_coupler_destroy(fg_coupler *h);
 void *fg_coupler_stream(fg_coupler *h);
+/* A nested atmosphere tile (make_coupler_mosaic.c:1765, :1792, :1857, :1903), named before fg_coupler_run: an index into the
+ * atmosphere tiles, -1 for none.  Its three lists and its own per-cell area sums are formed as any tile's; its terms
+ * are left out of the land and ocean cells' sums, hence out of the land and ocean masks, nbad and every list's tile-2 distances.
+ * At interp_order 2 the reference's guards also enclose its temporary a_area / a_clon / a_clat (:1882-1885, :1927-1930): the nest
+ * lists' tile-1 distances are clon / area - 0, and fg_coupler_get_cells gives clon = clat = 0 on the nest tile; its xarea is the full
+ * sum (atm_xarea of :2210 / :2333, which has no guard).
+ * FG_ERR_ARG with land on the atmosphere grid (:742) and for an index out of range.  Legacy and great-circle handles. */
+int  fg_coupler_set_nest(fg_coupler *h, int tile_nest);
+/* The wave grid (:2976-3535), given before fg_coupler_run: corner arrays as fg_coupler_create's.  The wave x ocean list is the land x
+ * ocean step with a wave tile for the land tile (ocn_frac > 1e-4, area x ocn_frac / min(area_ocn, area_wav) > thresh), inside the
+ * tile's ocean row band of :3107-3117; list order: wave tile, wave cell, ocean cell.  wav_same_as_ocn changes nothing with one ocean
+ * tile (:3119-3126) but fg_coupler_write_wave's file names.  interp_order 1: the reference's sum (:3262-3267) adds into w_area2,
+ * which is never allocated; w_area is formed as the order-2 branch forms it and nothing else.  FG_ERR_ARG on a great-circle handle
+ * (first order only: nothing of the wave sums could be pinned). */
+int  fg_coupler_add_wave(fg_coupler *h, int ntile_wav, const int *nx, const int *ny, const double *const *lon, const double *const *lat,
+                         int wav_same_as_ocn);
 int  fg_coupler_run(fg_coupler *h);
 /* which: 0 atmosphere x land (tile1 = atmosphere tile, tile2 = land tile), 1 atmosphere x ocean (tile1 = atmosphere tile, tile2 = 0),
- * 2 land x ocean (tile1 = land tile, tile2 = 0; land of its own only).  The list's length, or FG_ERR_*. */
+ * 2 land x ocean (tile1 = land tile, tile2 = 0; land of its own only), 3 wave x ocean (tile1 = wave tile, tile2 = 0).  The list's
+ * length, or FG_ERR_*. */
 long fg_coupler_count(const fg_coupler *h, int which, int tile1, int tile2);
 /* The list in the reference's order, host arrays of fg_coupler_count entries, any may be NULL: 0-based (i, j) of the two cells,
  * the exchange-cell area, the centroid integrals clon / clat and the distances tile1_distance (di1, dj1) and tile2_distance
  * (di2, dj2) of :1957-2006, :2778-2800 (interp_order 2 only). */
 int  fg_coupler_get(const fg_coupler *h, int which, int tile1, int tile2, int *i1, int *j1, int *i2, int *j2, double *area,
                     double *clon, double *clat, double *di1, double *dj1, double *di2, double *dj2);
-/* Per cell of one tile (grid: 0 atmosphere, 1 land, 2 ocean), host arrays, any may be NULL: get_grid_area; the exchange area the
+/* Per cell of one tile (grid: 0 atmosphere, 1 land, 2 ocean, 3 wave: w_area and the wave mask w_area / area_wav of :3397-3402), host arrays, any may be NULL: get_grid_area; the exchange area the
  * cell collected from the atmosphere's lists (a_area, l_area, o_area); their ratio (the land mask of :2089, the ocean fraction of
  * :2037, rows of the southern extension included); the cell's centroid (interp_order 2; the plain sums where the area is not > 0) */
 int  fg_coupler_get_cells(const fg_coupler *h, int grid, int tile, double *model_area, double *xarea, double *frac, double *clon,
                           double *clat);
+/* The ocean cells' wave-side sums (:3329-3332, :3366-3371; interp_order 2): exchange area and centroid per ocean cell from the wave x
+ * ocean lists over all wave tiles.  They are never mixed into the atmosphere-side o_area of fg_coupler_get_cells. */
+int  fg_coupler_get_wave_ocean(const fg_coupler *h, double *xarea, double *clon, double *clat);
+/* --check (:2199-2219, :2326-2342, :3504, :3591-3661), the first n of 19 doubles: [0] the largest |atm_xarea - area_atm| / area_atm,
+ * [1] its tile, [2] i, [3] j (0-based; the first cell with that ratio), [4] area_atm and [5] atm_xarea there, [6] atm_area_sum,
+ * [7] axl_area_sum, [8] axo_area_sum, [9] the ocean and [10] the land percentage, [11] the tiling error in percent, [12 .. 17] the
+ * same six of the nest tile (0 without one), [18] wxo_area_sum (0 without a wave grid).  The ratio and its cell are one device
+ * reduction; the scalar sums are added on the host from the downloaded area columns in the reference's order (atmosphere tile, land
+ * tile, list order; then per atmosphere tile the ocean list).  fg_coupler_run copies nothing more for it. */
+int  fg_coupler_check(const fg_coupler *h, double *out, int n);
 /* The tool's output files into `directory` (which exists), classic netCDF: one exchange-grid file per non-empty list
  * (<atm mosaic>_<tile>X<lnd mosaic>_<tile>.nc, ...X<ocn mosaic>_<tile>.nc, <lnd mosaic>_<tile>X<ocn mosaic>_<tile>.nc) with contact,
  * tile1_cell, tile2_cell (1-based; an ocean j carries 1 - ocn_south_ext), xgrid_area and for interp_order 2 tile1_distance and
@@ -1262,12 +1289,21 @@ int  fg_coupler_write_xgrid(const char *path, const char *contact, long n, const
                             int j2_shift, const double *area, const double *di1, const double *dj1, const double *di2, const double *dj2);
 int  fg_coupler_write_mask(const char *path, int ocean, int nx, int ny, const double *mask, const double *a, const double *b,
                            const double *area_atm);
-/* the first n of 8: [0] bytes fg_coupler_run copied to the host, [1] nbad: ocean cells with |omask - ocn_frac| > 1e-4 (:2038),
+/* The wave grid's files (:3397-3421, :3430-3535): per non-empty list <wave mosaic>_<tile>X<ocn mosaic>_<tile>.nc -- or, with
+ * wav_same_as_ocn, wav_<wave mosaic>_<tile>Xocn_<ocn mosaic>_<tile>.nc (:3452-3455) -- with contact w:tile::o:tile and the variables of
+ * the other exchange-grid files (tile2_cell's j = jo + 1 - ocn_south_ext), and wave_mask.nc or wave_mask_tile<k>.nc with the single
+ * variable mask.  names: NULL, or [0] wave, [1] ocean mosaic name, the wave tiles' names, the ocean tile's name; NULL entries give
+ * "wave_mosaic", "ocean_mosaic", "tile<k>".  fg_coupler_write's table is a different one.  _wave_xgrid / _wave_mask: from host arrays. */
+int  fg_coupler_write_wave(const fg_coupler *h, const char *directory, const char *const *names);
+int  fg_coupler_write_wave_xgrid(const char *path, const char *contact, long n, const int *iw, const int *jw, const int *io, const int *jo,
+                                 int jo_shift, const double *area, const double *diw, const double *djw, const double *dio, const double *djo);
+int  fg_coupler_write_wave_mask(const char *path, int nx, int ny, const double *mask);
+/* the first n of 9: [0] bytes fg_coupler_run copied to the host, [1] nbad: ocean cells with |omask - ocn_frac| > 1e-4 (:2038),
  * [2] searches, [3] atmosphere x ocean cells, [4] atmosphere x land cells, [5] land x ocean cells, [6] remembered atmosphere x land
- * polygons, [7] ocn_south_ext */
+ * polygons, [7] ocn_south_ext, [8] wave x ocean cells */
 int  fg_coupler_stats(const fg_coupler *h, long *stats, int n);
-/* wall time in ms (the first n of 7): create; atmosphere x land candidates; atmosphere x ocean; polygons x ocean; land x ocean;
- * sums, distances and masks; the whole run */
+/* wall time in ms (the first n of 8): create; atmosphere x land candidates; atmosphere x ocean; polygons x ocean; land x ocean;
+ * sums, distances and masks; the whole run; wave x ocean */
 int  fg_coupler_phase_ms(const fg_coupler *h, float *ms, int n);
 
 #ifdef __cplusplus

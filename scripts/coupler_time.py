@@ -4,6 +4,7 @@
     python scripts/coupler_time.py [--runs 7] [--out profiles/coupler_summary.md] [--large 384 1440 1080] [--shared 96 360 200 144 90]
     python scripts/coupler_time.py --large-only --runs 1        (the run a kernel trace wraps)
     python scripts/coupler_time.py --great-circle [--runs 7] [--out FILE] [--shared 96 360 200 144 90]
+    python scripts/coupler_time.py --nest-wave [--runs 11] [--out FILE] [--large 384 1440 1080] [--own-land 720 360]
 
 Two cases.
 * large: a C<n> atmosphere with land on the atmosphere grid over a tripolar NX x NY ocean from -82 degrees (one row added by
@@ -16,6 +17,11 @@ Two cases.
   time is the handle's creation, run() and the download of its atmosphere x ocean and atmosphere x land lists; it also makes the
   land x ocean list, the sums, distances and masks, which coupler_xgrid does not.  The two alternate in one process after a warm-up
   of each; median and largest deviation from it.
+* --nest-wave: the large case with no nest and no wave grid, and with a wave grid equal to the ocean grid (wav_same_as_ocn); then,
+  because a nest is refused with land on the atmosphere grid (make_coupler_mosaic.c:742), the same atmosphere and ocean with a
+  lat-lon land grid of its own: plain, with a nest (a block of a quarter of the edge of tile 2, halved: the seventh tile), and with
+  the wave grid, whose step is reported beside the land x ocean step of the same handle.  One handle per leg, a warm-up, `runs`
+  runs; check() is timed once per leg.
 """
 import argparse
 import os
@@ -129,6 +135,56 @@ def shared(fg, size, runs):
     return lines, ratio, same
 
 
+def nest_wave(fg, size, own_land, runs):
+    ni, nx, ny = size
+    atm = cubed_sphere(fg, ni)
+    ocn, omask, ext = ocean(fg, nx, ny, False)
+    lo, la = fg.latlon_corners(*own_land)
+    lnd = [fg.GridConfig(own_land[0], own_land[1], lo, la)]
+    # the nest: ni / 4 x ni / 4 cells of tile 2 (equatorial, 35 .. 125 E) from (ni / 4, ni / 2) halved; new corners midway in lon / lat
+    nb, i0, j0 = ni // 4, ni // 4, ni // 2
+    corners = []
+    for p in (atm[1].lonc, atm[1].latc):
+        b = np.asarray(p, dtype=np.float64).reshape(ni + 1, ni + 1)[j0:j0 + nb + 1, i0:i0 + nb + 1]
+        f = np.empty((2 * nb + 1, 2 * nb + 1))
+        f[::2, ::2] = b
+        f[::2, 1::2] = 0.5 * (b[:, :-1] + b[:, 1:])
+        f[1::2, ::2] = 0.5 * (b[:-1] + b[1:])
+        f[1::2, 1::2] = 0.5 * (f[1::2, 0:-1:2] + f[1::2, 2::2])
+        corners.append(f)
+    nest = fg.GridConfig(2 * nb, 2 * nb, corners[0], corners[1])
+    keys = ("axl_candidates", "axo", "polygons_x_ocean", "lxo", "wxo", "sums", "run")
+    legs = (("land on the atmosphere grid", atm, None, {}),
+            ("land on the atmosphere grid, wave grid = ocean grid", atm, None, dict(wav=[ocn], wav_same_as_ocn=True)),
+            (f"{own_land[0]} x {own_land[1]} land", atm, lnd, {}),
+            (f"{own_land[0]} x {own_land[1]} land, nest of {2 * nb} x {2 * nb} cells", atm + [nest], lnd, dict(tile_nest=6)),
+            (f"{own_land[0]} x {own_land[1]} land, wave grid = ocean grid", atm, lnd, dict(wav=[ocn], wav_same_as_ocn=True)))
+    lines = [f"## Nest and wave legs: C{ni} atmosphere over a tripolar {nx} x {ny} ocean (+{ext} southern row), 0 / 1 mask, order 2", "",
+             f"One handle per leg, a warm-up, {runs} runs; median (largest deviation from it), ms; check() once after the last run.", "",
+             "| leg | " + " | ".join(keys) + " | check() | bytes to the host | lists (axo / axl / lxo / wxo) |", "|---|" + "---|" * (len(keys) + 3)]
+    notes = []
+    for title, a, l, kw in legs:
+        with fg.CouplerMosaic(a, l, ocn, omask, ocn_south_ext=ext, **kw) as m:
+            m.run()
+            ph = []
+            for _ in range(runs):
+                m.run()
+                ph.append(m.phase_ms())
+            st = m.stats()
+            t0 = time.perf_counter()
+            ck = m.check()
+            t_ck = (time.perf_counter() - t0) * 1e3
+        cols = [_fmt([p[k] for p in ph]) if k in ph[0] else "-" for k in keys]
+        lines.append(f"| {title} | " + " | ".join(cols) + f" | {t_ck:.1f} | {st['d2h_bytes']} | {st['naxo']} / {st['naxl']} / {st['nlxo']} / {st.get('nwxo', '-')} |")
+        note = f"* {title}: largest area mismatch {ck['max_ratio']:.3e} at tile {ck['max_tile'] + 1}, tiling error {ck['tiling_area']:.3e} %"
+        if "tiling_area_nest" in ck:
+            note += f", nest region {ck['tiling_area_nest']:.3e} %"
+        if "wxo_area_sum" in ck:
+            note += f", wxo_area_sum / axo_area_sum = {ck['wxo_area_sum'] / ck['axo_area_sum']:.9f}"
+        notes.append(note + ".")
+    return lines + [""] + notes
+
+
 def great_circle(fg, size, runs):
     """--great-circle: CouplerMosaic(clip_method="great_circle") against the legacy order-1 handle on the same grids, runs alternating
     after a warm-up of each; then the polygon-list search per candidate pair against the quad x quad great-circle search per pair
@@ -199,11 +255,20 @@ def main():
     ap.add_argument("--shared", type=int, nargs=5, default=[96, 360, 200, 144, 90], metavar=("NI", "NX", "NY", "NX_LND", "NY_LND"))
     ap.add_argument("--large-only", action="store_true")
     ap.add_argument("--great-circle", action="store_true", help="the great-circle handle against the legacy one on the --shared grids")
+    ap.add_argument("--nest-wave", action="store_true", help="the large case with a wave grid, and with a land grid of its own plain / nest / wave")
+    ap.add_argument("--own-land", type=int, nargs=2, default=[720, 360], metavar=("NX_LND", "NY_LND"))
     args = ap.parse_args()
     fg = __graft_entry__.load_package()
     fg._lib.require_gpu()
     if args.great_circle:
         text = "\n".join(["# make_coupler_mosaic's GREAT_CIRCLE_CLIP branch on the device: timing", ""] + great_circle(fg, args.shared, args.runs)) + "\n"
+        print(text)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text)
+        return
+    if args.nest_wave:
+        text = "\n".join(nest_wave(fg, args.large, args.own_land, args.runs)) + "\n"
         print(text)
         if args.out:
             with open(args.out, "w") as f:
